@@ -7,6 +7,7 @@
 
     python bench.py --batch 1                              (ONE sample of the CFG pair per step: the half step a GPU of a CFG-parallel pair runs)
     python bench.py --gpus 2 --cfg-parallel                (one video on two GPUs: dist.CfgPair; N even: N / 2 videos in flight)
+    python bench.py --dump-outputs DIR                     (also writes the latents the last timed step left to DIR/latents.npy)
 
 --gpus N is a CLAIM the run has to earn: with no torchrun environment the script launches N rank processes itself and refuses
 (non-zero exit) when fewer than N GPUs are visible; with a torchrun environment WORLD_SIZE must equal N.  `value` is computed from
@@ -450,9 +451,14 @@ def main(argv=None):
                     "of noise_pred per step, CFG + scheduler step on both); value = video steps/s over all pairs")
     ap.add_argument("--dist-selftest", action="store_true", help="no GPU: exercise the rank launcher, the rendezvous, the chunked broadcast and its "
                     "watchdog with gloo on CPU tensors (tests/test_dist_gloo.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned to its caller -- the "
+                    "latents [1, F, C, H, W], updated in place -- as DIR/latents.npy (float32, rank 0; at most 12 MB at 720 x 1280). Inputs are "
+                    "seeded, so two builds run with the same arguments can be compared output for output")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.cfg_parallel and (args.gpus < 2 or args.gpus % 2):
         raise SystemExit("--cfg-parallel pairs the ranks up: --gpus must be even and >= 2 (one GPU: --batch 1 gives the projection)")
     if args.cfg_parallel:
@@ -627,6 +633,11 @@ def main(argv=None):
         latents.copy_(keep)
     # ---- the timed region of the contract: no event recording, no profiling inside it
     elapsed, total_steps = timed(bool(args.graph), args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # now: the passes below step `latents` further
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), latents.float().cpu().numpy())
     finite = bool(torch.isfinite(latents.float()).all().item())
     # who ran: one record per rank (device index, name, bus id), gathered on rank 0 -- n_gpus is the number of DISTINCT devices
     props = torch.cuda.get_device_properties(dev)

@@ -45,6 +45,14 @@ def test_flag_and_world_size_must_agree(bench, monkeypatch):
         bench.main(["--gpus", "0"])
 
 
+def test_steps_must_be_a_real_count(bench):
+    """ms_per_step divides by --steps: a run with no timed step is refused before anything starts"""
+    for argv in (["--steps", "0"], ["--steps", "-1"], ["--steps", "3", "--warmup", "-1"]):
+        with pytest.raises(SystemExit) as e:
+            bench.main(argv)
+        assert "--steps must be >= 1" in str(e.value.code)
+
+
 def test_value_is_never_the_flag_times_anything():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "args.gpus *" not in src and "* args.gpus" not in src

@@ -173,7 +173,7 @@ def test_vae_real_width_tiled_decoder_vs_oracle(s2v, dt_name):
         assert rel <= br and err <= ba * exp.abs().max().item(), (rel, err)
 
 
-def test_frames_uint8_matches_export_to_video_conversion(s2v):
+def test_frames_uint8_matches_export_to_video_conversion(s2v, tmp_path):
     """(postprocess_video(..., "np")[0] * 255).astype(np.uint8) of utils/export_utils.py:175, bit-exact, both dtypes"""
     g = load_golden("vae_tiny.npz")
     vae = make_vae(s2v, TINY, torch.float32, weights_of(g))
@@ -184,7 +184,7 @@ def test_frames_uint8_matches_export_to_video_conversion(s2v):
         ref = (vae.postprocess_video(video, "np")[0] * 255).astype(np.uint8)
         assert u8.dtype == np.uint8 and u8.shape == ref.shape
         assert np.array_equal(u8, ref)
-    out = s2v.video_generate.export_to_video(u8, "/tmp/s2v_test_clip.mp4", fps=8)
+    out = s2v.video_generate.export_to_video(u8, str(tmp_path / "s2v_test_clip.mp4"), fps=8)
     if out.endswith(".avi"):  # no imageio-ffmpeg on the box: Motion-JPEG AVI with the same frames
         n, fps, w, h, first = s2v.video_generate.read_avi_info(out)
         assert (n, w, h) == (u8.shape[0], u8.shape[2], u8.shape[1]) and fps == 8.0
