@@ -79,6 +79,18 @@ _SIGS.update({
     "s2v_rccl_bcast": [_P, _P, _I64, _I32, _P],
     "s2v_rccl_allgather": [_P, _P, _P, _I64, _P],
     "s2v_bcast_weights": [_P, _P, _I32, _P],
+    "s2v_rccl_alltoallv": [_P, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), _P],
+})
+# Ulysses sequence parallelism (include/s2v_hip.h: s2v_set_shard ... s2v_denoise_step_ulysses)
+SHARD_QKV_EXCHANGE, SHARD_O_EXCHANGE, SHARD_NOISE_GATHER = 1, 2, 3
+_SIGS.update({
+    "s2v_set_shard": [_P, _I32, _I32],
+    "s2v_shard_layout": [_P, ctypes.POINTER(_I32)],
+    "s2v_shard_buffers": [_P, _I32, ctypes.POINTER(_P), ctypes.POINTER(_P)] + [ctypes.POINTER(_I64)] * 4,
+    "s2v_shard_step_begin": [_P, _P, _F, ctypes.POINTER(SchedCoefC), ctypes.POINTER(_I32), _P],
+    "s2v_shard_step_resume": [_P, ctypes.POINTER(_I32), _P],
+    "s2v_shard_step_end": [_P, _P, _P, _P, _P],
+    "s2v_denoise_step_ulysses": [_P, _P, _P, _F, ctypes.POINTER(SchedCoefC), _P, _P, _P],
 })
 # VAE entry points are registered by vae.py through register_sigs()
 

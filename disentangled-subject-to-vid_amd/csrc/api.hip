@@ -105,8 +105,22 @@ struct s2v_ctx {
     long long* clk_cur = nullptr;                    // the slot of the launch a ProfScope is open around (null outside the profile pass)
     std::vector<std::pair<int, int>> clk_rec;         // (class, slot) of every stamped launch since the last s2v_profile_read_clocks
     bool prof_on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[8];
-    size_t prof_used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[9];  // PK_NUM classes (8: the Ulysses packs / unpacks)
+    size_t prof_used[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // Ulysses shard (s2v_set_shard): sp ranks share one video's step.  With a shard T, R, V, Ntok, M and Mpad above are this rank's rows of
+    // every sample -- the mini-sequence [T_r | R_r | V_r] -- and gT, gR, gV, gN the whole streams (equal to T, R, V, Ntok without a shard).
+    bool shard = false;
+    int sp = 1, sr = 0;
+    int gT = 0, gR = 0, gV = 0, gN = 0;
+    int t0 = 0, r0 = 0, v0 = 0;                // this rank's first row of each stream
+    int Vmax = 0;                              // ceil(gV / sp): rows per sample of every rank's share of the noise all-gather
+    char *QKVh = nullptr, *Oh = nullptr;       // head-sharded full-N buffers: q|k|v of head group sr [B*gN][3D/p], attention output [B*gN][D/p]
+    char *sbuf = nullptr, *rbuf = nullptr;     // send / recv of the two per-block all-to-alls
+    char *nsend = nullptr, *nrecv = nullptr;   // send [B][Vmax][Cout] / recv [sp][B][Vmax][Cout] of the noise all-gather
+    char* proj_full = nullptr;                 // the gathered projection [B][gV][Cout]
+    int *rmap = nullptr, *nmap = nullptr;      // recv row of the QKV exchange -> global row; recv row of the noise gather -> row of proj_full (-1: pad)
+    std::vector<int64_t> xcnt[3][4];           // per exchange kind: send counts, send displacements, recv counts, recv displacements (bytes)
+    int sh_layer = 0, sh_pending = 0;          // the staged step: layer in flight, exchange the caller owes (S2V_SHARD_*)
 };
 
 static const int CLK_SLOTS = 8192;
@@ -114,7 +128,7 @@ static const int CLK_SLOTS = 8192;
 // designated workgroup of the kernel stamps s_memtime / s_memrealtime at its entry and exit (common.h clk_stamp).  Kernels without stamps (or
 // launches whose designated workgroup left early) leave the slot zero and are skipped.
 #define S2V_FP8_QK_AUTO_TOKENS 40000
-enum { PK_QKV = 0, PK_ATTN = 1, PK_OUT = 2, PK_FF1 = 3, PK_FF2 = 4, PK_LNMOD = 5, PK_QKNORM = 6, PK_OTHER = 7, PK_NUM = 8 };
+enum { PK_QKV = 0, PK_ATTN = 1, PK_OUT = 2, PK_FF1 = 3, PK_FF2 = 4, PK_LNMOD = 5, PK_QKNORM = 6, PK_OTHER = 7, PK_SHARD = 8, PK_NUM = 9 };
 
 struct ProfScope {
     s2v_ctx* c; int k; hipStream_t st; bool on;
@@ -460,11 +474,34 @@ extern "C" int s2v_mark_weights_loaded(s2v_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------------------
+// rank r's share of a stream of n rows: [r*n/p, (r+1)*n/p)
+static inline void shard_range(int n, int p, int r, int* begin, int* len) {
+    const int b = (int)((int64_t)r * n / p), e = (int)((int64_t)(r + 1) * n / p);
+    *begin = b; *len = e - b;
+}
+
+extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
+    S2V_REQUIRE(c, "null context");
+    S2V_REQUIRE(world >= 1 && rank >= 0 && rank < world, "s2v_set_shard: need world >= 1 and 0 <= rank < world");
+    S2V_REQUIRE(c->cfg.num_heads % world == 0, "s2v_set_shard: the world size must divide num_heads (attention runs num_heads / world heads per rank)");
+    S2V_REQUIRE(c->cfg.weight_format == 0, "s2v_set_shard: fp8 weight formats are not supported with a shard (MX buffers are sized and quantised per local row)");
+    S2V_REQUIRE(c->cfg.out_channels * 4 * c->esz % 16 == 0, "s2v_set_shard: the projected rows must be a multiple of 16 bytes (out_channels * 4 * element size)");
+    if (c->shard && c->sp == world && c->sr == rank) return 0;
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+    if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
+    c->B = 0;
+    c->shard = true; c->sp = world; c->sr = rank;
+    c->sh_pending = 0;
+    return 0;
+}
+
 extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int32_t H, int32_t W) {
     S2V_REQUIRE(c, "null context");
     S2V_REQUIRE(B >= 1 && B <= 4, "s2v_set_geometry: batch must be 1..4");
     S2V_REQUIRE(T >= 0 && F >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "s2v_set_geometry: bad geometry");
-    if (c->ws && B == c->B && T == c->T && F == c->F && H == c->H && W == c->W) return 0;
+    if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
+    if (c->shard) S2V_REQUIRE(F * (H / 2) * (W / 2) >= c->sp, "s2v_set_geometry: every rank of a shard needs at least one video row");
     S2V_CHECK_HIP(hipDeviceSynchronize());
     if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }
@@ -472,10 +509,20 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     c->R = (H / 2) * (W / 2);
     c->V = F * c->R;
     c->Ntok = T + c->R + c->V;
+    c->gT = c->T; c->gR = c->R; c->gV = c->V; c->gN = c->Ntok;
+    c->t0 = c->r0 = c->v0 = 0;
+    if (c->shard) {  // every stream split separately: rank r keeps [T_r | R_r | V_r] of each sample
+        shard_range(c->gT, c->sp, c->sr, &c->t0, &c->T);
+        shard_range(c->gR, c->sp, c->sr, &c->r0, &c->R);
+        shard_range(c->gV, c->sp, c->sr, &c->v0, &c->V);
+        c->Ntok = c->T + c->R + c->V;
+    }
+    c->Vmax = (c->gV + c->sp - 1) / c->sp;
+    c->sh_pending = 0;
     // weight_format 3 ("fp8-auto"): fp8 linears always, fp8 QK^T from S2V_FP8_QK_AUTO_TOKENS tokens on -- there the attention is > 80 % of the
     // step and the whole-run drift of fp8-qk is the fp8 engine's (profiles/r05_whole_run_c5_10steps.txt: 8.69e-3 against 8.67e-3)
     c->fp8_qk = c->cfg.weight_format == 2 || (c->cfg.weight_format == 3 && c->Ntok >= S2V_FP8_QK_AUTO_TOKENS);
-    c->ntok_pad = (int)rup(c->Ntok, 64);
+    c->ntok_pad = (int)rup(c->gN, 64);
     c->M = (int64_t)B * c->Ntok;
     c->Mpad = rup(c->M, 256) + 256;
     c->have_rope = c->have_pos = c->have_cond = false;
@@ -483,13 +530,14 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     const int64_t D = c->D, E = c->esz;
     const int64_t Cin4 = c->cfg.in_channels * 4, Cout4 = c->cfg.out_channels * 4;
     const int64_t BVp = rup((int64_t)B * c->V, 256) + 256;
+    const int64_t BVg = rup((int64_t)B * c->gV, 256) + 256;  // patchify runs on the whole latent (== BVp without a shard)
     int64_t off = 0;
     auto carve = [&](int64_t bytes) { int64_t o = off; off += rup(bytes, 256); return o; };
     const int64_t oX = carve(c->Mpad * D * E), oXn = carve(c->Mpad * D * E), oQKV = carve(c->Mpad * 3 * D * E);
     const int64_t oH = carve(c->Mpad * 4 * D * E);
-    const int64_t oVT = carve((int64_t)B * c->cfg.num_heads * 64 * c->ntok_pad * 2);
-    const int64_t oe0 = carve(rup((int64_t)B * T + 128, 128) * D * E), oe1 = carve(rup(c->R + 128, 128) * D * E);
-    const int64_t opat = carve(BVp * Cin4 * E), otail = carve(BVp * D * E), oproj = carve(BVp * Cout4 * E);
+    const int64_t oVT = carve((int64_t)B * (c->cfg.num_heads / c->sp) * 64 * c->ntok_pad * 2);
+    const int64_t oe0 = carve(rup((int64_t)B * T + 128, 128) * D * E), oe1 = carve(rup(c->gR + 128, 128) * D * E);
+    const int64_t opat = carve(BVg * Cin4 * E), otail = carve(BVp * D * E), oproj = carve(BVp * Cout4 * E);
     const int64_t omod = carve((int64_t)B * c->mod_rows * E);
     const int64_t ote = carve(((int64_t)B * D + (int64_t)B * c->temb) * E), oemb = carve((int64_t)B * c->temb * E);
     // room for the CFG pair even when the geometry holds ONE sample of it (CFG-parallel, s2v_denoise_split_*: the peer's half arrives here)
@@ -504,9 +552,17 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     const int64_t BH = (int64_t)B * c->cfg.num_heads;
     const int64_t oq8 = carve(c->fp8_qk ? BH * c->Ntok * 64 : 0), oq8s = carve(c->fp8_qk ? BH * c->Ntok * 2 : 0);
     const int64_t ok8 = carve(c->fp8_qk ? BH * c->ntok_pad * 64 : 0), ok8s = carve(c->fp8_qk ? BH * c->ntok_pad * 4 : 0);
-    // split-K partial tiles + arrival counters (linear(): only geometries whose FF2 has at most half as many 256 x 256 tiles as CUs)
-    c->sk_tiles = (c->mfma && ((c->M + 255) / 256) * ((D + 255) / 256) * 2 <= c->num_cus) ? c->num_cus : 0;
+    // split-K partial tiles + arrival counters (linear(): only geometries whose FF2 has at most half as many 256 x 256 tiles as CUs).  A shard
+    // never splits K: split-K changes the reduction order, and a rank's row count must not pick a different one than the single engine's
+    c->sk_tiles = (!c->shard && c->mfma && ((c->M + 255) / 256) * ((D + 255) / 256) * 2 <= c->num_cus) ? c->num_cus : 0;
     const int64_t osk = carve((int64_t)c->sk_tiles * 262144), oskc = carve((int64_t)c->sk_tiles * 4);
+    // shard: the head-sharded full-N buffers, the exchange buffers and the row maps
+    const int64_t P = c->sp, Dp = D / P, Mg = (int64_t)B * c->gN, Mgpad = rup(Mg, 256) + 256;
+    const int64_t oQh = carve(c->shard ? Mgpad * 3 * Dp * E : 0), oOh = carve(c->shard ? Mgpad * Dp * E : 0);
+    const int64_t osb = carve(c->shard ? std::max(c->M * 3 * D, Mg * Dp) * E : 0), orb = carve(c->shard ? std::max(Mg * 3 * Dp, c->M * D) * E : 0);
+    const int64_t ons = carve(c->shard ? (int64_t)B * c->Vmax * Cout4 * E : 0), onr = carve(c->shard ? P * B * c->Vmax * Cout4 * E : 0);
+    const int64_t opf = carve(c->shard ? (int64_t)B * c->gV * Cout4 * E : 0);
+    const int64_t ormap = carve(c->shard ? Mg * 4 : 0), onmap = carve(c->shard ? P * B * c->Vmax * 4 : 0);
     c->ws_bytes = off;
     S2V_CHECK_HIP(hipMalloc((void**)&c->ws, c->ws_bytes));
     S2V_CHECK_HIP(hipMemset(c->ws, 0, c->ws_bytes));
@@ -519,6 +575,43 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     c->hq = (unsigned char*)(w + ohq); c->hs = (unsigned char*)(w + ohs);
     c->q8 = (unsigned char*)(w + oq8); c->q8s = (unsigned short*)(w + oq8s); c->k8 = (unsigned char*)(w + ok8); c->k8s = (unsigned*)(w + ok8s);
     c->sk_ws = (float*)(w + osk); c->sk_cnt = (unsigned*)(w + oskc);
+    if (c->shard) {
+        c->QKVh = w + oQh; c->Oh = w + oOh; c->sbuf = w + osb; c->rbuf = w + orb; c->nsend = w + ons; c->nrecv = w + onr; c->proj_full = w + opf;
+        c->rmap = (int*)(w + ormap); c->nmap = (int*)(w + onmap);
+        // rank g's rows of sample b, in g's local order [T_g | R_g | V_g], concatenated over g = the recv order of the QKV exchange (and the
+        // send order of the O exchange); each maps to its row b * gN + (stream offset) in the global [text | ref | video] sequence
+        std::vector<int> rmap, nmap;
+        rmap.reserve(Mg);
+        nmap.assign((size_t)P * B * c->Vmax, -1);
+        std::vector<int64_t> ntok(P);
+        for (int g = 0; g < P; ++g) {
+            int ts, tl, rs, rl, vs, vl;
+            shard_range(c->gT, (int)P, g, &ts, &tl); shard_range(c->gR, (int)P, g, &rs, &rl); shard_range(c->gV, (int)P, g, &vs, &vl);
+            ntok[g] = tl + rl + vl;
+            for (int b = 0; b < B; ++b) {
+                const int base = b * c->gN;
+                for (int i = 0; i < tl; ++i) rmap.push_back(base + ts + i);
+                for (int i = 0; i < rl; ++i) rmap.push_back(base + c->gT + rs + i);
+                for (int i = 0; i < vl; ++i) rmap.push_back(base + c->gT + c->gR + vs + i);
+                for (int i = 0; i < vl; ++i) nmap[((size_t)g * B + b) * c->Vmax + i] = b * c->gV + vs + i;
+            }
+        }
+        S2V_CHECK_HIP(hipMemcpy(c->rmap, rmap.data(), rmap.size() * 4, hipMemcpyHostToDevice));
+        S2V_CHECK_HIP(hipMemcpy(c->nmap, nmap.data(), nmap.size() * 4, hipMemcpyHostToDevice));
+        for (auto& k : c->xcnt) for (auto& v : k) v.assign(P, 0);
+        int64_t rq = 0, so = 0;
+        for (int g = 0; g < P; ++g) {
+            // QKV: to g my rows' head group g; from g its rows' head group sr
+            c->xcnt[0][0][g] = c->M * 3 * Dp * E; c->xcnt[0][1][g] = g * c->M * 3 * Dp * E;
+            c->xcnt[0][2][g] = B * ntok[g] * 3 * Dp * E; c->xcnt[0][3][g] = rq; rq += c->xcnt[0][2][g];
+            // O: to g its rows of head group sr; from g my rows of head group g
+            c->xcnt[1][0][g] = B * ntok[g] * Dp * E; c->xcnt[1][1][g] = so; so += c->xcnt[1][0][g];
+            c->xcnt[1][2][g] = c->M * Dp * E; c->xcnt[1][3][g] = g * c->M * Dp * E;
+            // noise: the same [B][Vmax] rows to everyone
+            c->xcnt[2][0][g] = (int64_t)B * c->Vmax * Cout4 * E; c->xcnt[2][1][g] = 0;
+            c->xcnt[2][2][g] = c->xcnt[2][0][g]; c->xcnt[2][3][g] = g * c->xcnt[2][0][g];
+        }
+    }
     return 0;
 }
 
@@ -539,8 +632,17 @@ extern "C" int s2v_set_rope(s2v_ctx* c, const float* cos_dev, const float* sin_d
     }
     const bool had_rope = c->have_rope, was_paired = c->rope_paired;
     const size_t bytes = (size_t)(c->R + c->V) * 64 * 4;
-    S2V_CHECK_HIP(hipMemcpyAsync(c->rope_cos, cos_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    S2V_CHECK_HIP(hipMemcpyAsync(c->rope_sin, sin_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (c->shard) {  // the full [ref | video] tables in, this rank's R_r + V_r rows kept
+        const size_t row = 64 * 4, rb = (size_t)c->R * row, vb = (size_t)c->V * row;
+        const size_t ro = (size_t)c->r0 * row, vo = ((size_t)c->gR + c->v0) * row;
+        S2V_CHECK_HIP(hipMemcpyAsync(c->rope_cos, (const char*)cos_dev + ro, rb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        S2V_CHECK_HIP(hipMemcpyAsync(c->rope_sin, (const char*)sin_dev + ro, rb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        S2V_CHECK_HIP(hipMemcpyAsync((char*)c->rope_cos + rb, (const char*)cos_dev + vo, vb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        S2V_CHECK_HIP(hipMemcpyAsync((char*)c->rope_sin + rb, (const char*)sin_dev + vo, vb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    } else {
+        S2V_CHECK_HIP(hipMemcpyAsync(c->rope_cos, cos_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        S2V_CHECK_HIP(hipMemcpyAsync(c->rope_sin, sin_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
     c->have_rope = true;
     // The reference builds its tables with repeat_interleave(2) (embeddings.py:get_3d_rotary_pos_embed): cos[2k] == cos[2k+1].  When
     // that holds (checked, once per geometry, on the host) a packed copy [position][32 cos | 32 sin] halves what the fused QKV
@@ -568,8 +670,9 @@ extern "C" int s2v_set_rope(s2v_ctx* c, const float* cos_dev, const float* sin_d
 extern "C" int s2v_set_pos_embed(s2v_ctx* c, const void* table_dev, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws, "s2v_set_pos_embed: call s2v_set_geometry first");
     if (!table_dev) { c->have_pos = false; return 0; }
-    S2V_CHECK_HIP(hipMemcpyAsync(c->pos_tab, table_dev, (size_t)c->V * c->D * c->esz, hipMemcpyDeviceToDevice,
-                                 (hipStream_t)stream));
+    // shard: the full [V][D] table in, this rank's V_r rows kept
+    S2V_CHECK_HIP(hipMemcpyAsync(c->pos_tab, (const char*)table_dev + (size_t)c->v0 * c->D * c->esz, (size_t)c->V * c->D * c->esz,
+                                 hipMemcpyDeviceToDevice, (hipStream_t)stream));
     c->have_pos = true;
     return 0;
 }
@@ -656,7 +759,13 @@ extern "C" int s2v_set_conditioning(s2v_ctx* c, const void* text_dev, const void
     // copied into the (padded, zero-initialised) Hb scratch.
     const int TX = c->cfg.text_embed_dim;
     if (c->T > 0) {
-        S2V_TRY(launch_convert2d(text_dev, c->dtype, TX, c->Hb, c->dtype, TX, (int64_t)c->B * c->T, TX, st));
+        if (c->shard) {  // the full [B][gT] embeddings in, this rank's T_r rows of each sample kept
+            for (int b = 0; b < c->B; ++b)
+                S2V_TRY(launch_convert2d((const char*)text_dev + ((int64_t)b * c->gT + c->t0) * TX * c->esz, c->dtype, TX,
+                                         c->Hb + (int64_t)b * c->T * TX * c->esz, c->dtype, TX, c->T, TX, st));
+        } else {
+            S2V_TRY(launch_convert2d(text_dev, c->dtype, TX, c->Hb, c->dtype, TX, (int64_t)c->B * c->T, TX, st));
+        }
         GemmArgs g{};
         g.A = c->Hb; g.lda = TX; g.W = c->text_w; g.ldw = TX; g.bias = c->text_b;
         g.C = c->e0; g.ldc = D; g.M = c->B * c->T; g.N = D; g.K = TX;
@@ -666,9 +775,9 @@ extern "C" int s2v_set_conditioning(s2v_ctx* c, const void* text_dev, const void
     const int K = c->cfg.in_channels * 4;
     S2V_TRY(launch_patchify(ref_latent_dev, 0, 1, 1, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st));
     GemmArgs g{};
-    g.A = c->patches; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;
+    g.A = c->patches + (int64_t)c->r0 * K * c->esz; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;  // shard: this rank's R_r patches
     g.C = c->e1; g.ldc = D; g.M = c->R; g.N = D; g.K = K;
-    S2V_TRY(linear(c, g, EPI_BIAS, st));
+    if (c->R > 0) S2V_TRY(linear(c, g, EPI_BIAS, st));
     c->have_cond = true;
     return 0;
 }
@@ -788,66 +897,94 @@ static int run_attention(s2v_ctx* c, int l, hipStream_t st, bool prequant = fals
     return 0;
 }
 
-static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] rows of this layer's norm1 */,
-                     int64_t mod_stride, hipStream_t st) {
+// the pieces of a block on the packed residual buffer X (rows: the context's M), in the order run_block launches them
+static int block_norm(s2v_ctx* c, int l, int half, const char* mod_base /* [B][mod_stride] rows of this layer's norm1 */, int64_t mod_stride,
+                      hipStream_t st, bool* prequant_out) {
     const LayerW& w = c->layers[l];
     const int D = c->D;
     const int64_t E = c->esz;
-    for (int half = 0; half < 2; ++half) {
-        const char* mb = mod_base + (int64_t)half * c->mc * D * E;
-        LnModArgs n{};
-        n.x = c->X; n.ldx = D; n.y = c->Xn; n.ldy = D;
-        n.w = half ? w.ln2_w : w.ln1_w; n.b = half ? w.ln2_b : w.ln1_b; n.eps = c->cfg.norm_eps;
-        n.shift_vid = mb; n.scale_vid = mb + D * E; n.shift_txt = mb + 3 * D * E; n.scale_txt = mb + 4 * D * E;
-        n.mod_stride = (int)mod_stride; n.B = c->B; n.Ntok = c->Ntok; n.text_len = c->T; n.D = D;
-        if (c->mc == 9) { n.shift_ref = mb + 6 * D * E; n.scale_ref = mb + 7 * D * E; n.ref_len = c->R; }
-        // fp8 linears: the LayerNorm output feeds exactly one projection (QKV / FF1), so it is quantised where it is produced
-        bool prequant = c->fp8;
+    const char* mb = mod_base + (int64_t)half * c->mc * D * E;
+    LnModArgs n{};
+    n.x = c->X; n.ldx = D; n.y = c->Xn; n.ldy = D;
+    n.w = half ? w.ln2_w : w.ln1_w; n.b = half ? w.ln2_b : w.ln1_b; n.eps = c->cfg.norm_eps;
+    n.shift_vid = mb; n.scale_vid = mb + D * E; n.shift_txt = mb + 3 * D * E; n.scale_txt = mb + 4 * D * E;
+    n.mod_stride = (int)mod_stride; n.B = c->B; n.Ntok = c->Ntok; n.text_len = c->T; n.D = D;
+    if (c->mc == 9) { n.shift_ref = mb + 6 * D * E; n.scale_ref = mb + 7 * D * E; n.ref_len = c->R; }
+    // fp8 linears: the LayerNorm output feeds exactly one projection (QKV / FF1), so it is quantised where it is produced
+    bool prequant = c->fp8;
 #ifdef S2V_DIAG
-        prequant = prequant && g_fused_q8;
+    prequant = prequant && g_fused_q8;
 #endif
-        if (prequant) { n.q8 = c->aq; n.q8_scale = c->aq_scale; }
-        { ProfScope ps(c, PK_LNMOD, st); S2V_TRY(launch_ln_modulate(n, c->dtype, st)); }
-        GemmArgs g{};
-        g.X = c->X; g.ldx = D; g.gate_vid = mb + 2 * D * E; g.gate_txt = mb + 5 * D * E; g.gate_stride = (int)mod_stride;
-        g.tok_per_batch = c->Ntok; g.text_len = c->T; g.M = (int)c->M; g.N = D;
-        if (c->mc == 9) { g.gate_ref = mb + 8 * D * E; g.ref_len = c->R; }
+    if (prequant) { n.q8 = c->aq; n.q8_scale = c->aq_scale; }
+    *prequant_out = prequant;
+    ProfScope ps(c, PK_LNMOD, st);
+    return launch_ln_modulate(n, c->dtype, st);
+}
+
+// the gate + residual epilogue of the out-projection (half 0) / FF2 (half 1)
+static GemmArgs block_gate(const s2v_ctx* c, int half, const char* mod_base, int64_t mod_stride) {
+    const int D = c->D;
+    const int64_t E = c->esz;
+    const char* mb = mod_base + (int64_t)half * c->mc * D * E;
+    GemmArgs g{};
+    g.X = c->X; g.ldx = D; g.gate_vid = mb + 2 * D * E; g.gate_txt = mb + 5 * D * E; g.gate_stride = (int)mod_stride;
+    g.tok_per_batch = c->Ntok; g.text_len = c->T; g.M = (int)c->M; g.N = D;
+    if (c->mc == 9) { g.gate_ref = mb + 8 * D * E; g.ref_len = c->R; }
+    return g;
+}
+
+static int block_out_proj(s2v_ctx* c, int l, GemmArgs g, hipStream_t st) {
+    const LayerW& w = c->layers[l];
+    const int D = c->D;
+    g.A = c->Xn; g.lda = D; g.W = w.wo; g.ldw = D; g.bias = w.bo; g.K = D;
+    if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
+    ProfScope ps(c, PK_OUT, st);
+    if (c->fp8) return linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_o, w.s_o, st);
+    return linear(c, g, EPI_BIAS_GATE_RES, st);
+}
+
+static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st) {
+    const LayerW& w = c->layers[l];
+    const int D = c->D;
+    GemmArgs f{};
+    f.A = c->Xn; f.lda = D; f.W = w.w1; f.ldw = D; f.bias = w.b1; f.C = c->Hb; f.ldc = 4 * D;
+    f.M = (int)c->M; f.N = 4 * D; f.K = D;
+    bool mx = c->fp8 && (4 * D) % 128 == 0;
+#ifdef S2V_DIAG
+    mx = mx && g_fp8_mx;
+#endif
+    if (mx) { f.mx_out_q = c->hq; f.mx_out_s = c->hs; f.mx_rows = (int)c->Mpad; }
+    {
+        ProfScope ps(c, PK_FF1, st);
+        if (c->fp8) S2V_TRY(linear_fp8(c, f, EPI_BIAS_GELU, w.q_1, w.s_1, st, prequant));
+        else S2V_TRY(linear(c, f, EPI_BIAS_GELU, st));
+    }
+    g.A = c->Hb; g.lda = 4 * D; g.W = w.w2; g.ldw = 4 * D; g.bias = w.b2; g.K = 4 * D;
+    if (mx) { g.A = c->hq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
+    ProfScope ps(c, PK_FF2, st);
+    if (c->fp8) return linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_2, w.s_2, st);
+    return linear(c, g, EPI_BIAS_GATE_RES, st);
+}
+
+static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] rows of this layer's norm1 */,
+                     int64_t mod_stride, hipStream_t st) {
+    for (int half = 0; half < 2; ++half) {
+        bool prequant = false;
+        S2V_TRY(block_norm(c, l, half, mod_base, mod_stride, st, &prequant));
+        const GemmArgs g = block_gate(c, half, mod_base, mod_stride);
         if (half == 0) {
             S2V_TRY(run_attention(c, l, st, prequant));
-            g.A = c->Xn; g.lda = D; g.W = w.wo; g.ldw = D; g.bias = w.bo; g.K = D;
-            if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
-            ProfScope ps(c, PK_OUT, st);
-            if (c->fp8) S2V_TRY(linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_o, w.s_o, st));
-            else S2V_TRY(linear(c, g, EPI_BIAS_GATE_RES, st));
+            S2V_TRY(block_out_proj(c, l, g, st));
         } else {
-            GemmArgs f{};
-            f.A = c->Xn; f.lda = D; f.W = w.w1; f.ldw = D; f.bias = w.b1; f.C = c->Hb; f.ldc = 4 * D;
-            f.M = (int)c->M; f.N = 4 * D; f.K = D;
-            bool mx = c->fp8 && (4 * D) % 128 == 0;
-#ifdef S2V_DIAG
-            mx = mx && g_fp8_mx;
-#endif
-            if (mx) { f.mx_out_q = c->hq; f.mx_out_s = c->hs; f.mx_rows = (int)c->Mpad; }
-            {
-                ProfScope ps(c, PK_FF1, st);
-                if (c->fp8) S2V_TRY(linear_fp8(c, f, EPI_BIAS_GELU, w.q_1, w.s_1, st, prequant));
-                else S2V_TRY(linear(c, f, EPI_BIAS_GELU, st));
-            }
-            g.A = c->Hb; g.lda = 4 * D; g.W = w.w2; g.ldw = 4 * D; g.bias = w.b2; g.K = 4 * D;
-            if (mx) { g.A = c->hq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
-            ProfScope ps(c, PK_FF2, st);
-            if (c->fp8) S2V_TRY(linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_2, w.s_2, st));
-            else S2V_TRY(linear(c, g, EPI_BIAS_GATE_RES, st));
+            S2V_TRY(block_ff(c, l, g, prequant, st));
         }
     }
     return 0;
 }
 
-static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* t_dev, void* out,
-                        hipStream_t st) {
-    S2V_REQUIRE(c->ws && c->finalized && c->have_cond, "transformer_forward: geometry, weights and conditioning required");
-    S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "transformer_forward: RoPE tables missing (s2v_set_rope)");
-    S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "transformer_forward: sincos table missing (s2v_set_pos_embed)");
+// time embedding, every modulation of the step, and the residual streams [text | ref | video] of each sample in X (a shard: this rank's rows
+// [T_r | R_r | V_r]; the latent is patchified whole and the rank's V_r patch rows embedded)
+static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* t_dev, hipStream_t st) {
     const int D = c->D, B = c->B;
     const int64_t E = c->esz;
     // 1. timestep embedding + every AdaLN modulation of the step in one batched GEMV (temb is block-invariant)
@@ -865,15 +1002,18 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, co
         S2V_TRY(launch_copy_rows(c->e1, D, nullptr, 0, xb + (int64_t)c->T * D * E, D, c->R, D, c->dtype, st));
         char* xv = xb + (int64_t)(c->T + c->R) * D * E;
         GemmArgs g{};
-        g.A = c->patches + (int64_t)b * c->V * K * E; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;
+        g.A = c->patches + ((int64_t)b * c->gV + c->v0) * K * E; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;
         g.C = xv; g.ldc = D; g.M = c->V; g.N = D; g.K = K;
         S2V_TRY(linear(c, g, EPI_BIAS, st));
         if (!c->cfg.use_rope) S2V_TRY(launch_copy_rows(xv, D, c->pos_tab, D, xv, D, c->V, D, c->dtype, st));
     }
-    // 3. blocks
-    for (int l = 0; l < c->L; ++l)
-        S2V_TRY(run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st));
-    // 4. tail
+    return 0;
+}
+
+// final norms + projection on the video rows of X -> c->proj [B * V][Cout]
+static int tail_proj(s2v_ctx* c, hipStream_t st) {
+    const int D = c->D, B = c->B;
+    const int64_t E = c->esz;
     const char* mo = c->mod + (int64_t)2 * c->L * c->mc * D * E;
     TailNormArgs t{};
     t.x = c->X; t.ldx = D; t.y = c->tailn; t.ldy = D; t.w1 = c->nf_w; t.b1 = c->nf_b; t.w2 = c->no_w; t.b2 = c->no_b;
@@ -884,8 +1024,25 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, co
     GemmArgs g{};
     g.A = c->tailn; g.lda = D; g.W = c->po_w; g.ldw = D; g.bias = c->po_b; g.C = c->proj; g.ldc = Co;
     g.M = B * c->V; g.N = Co; g.K = D;
-    S2V_TRY(linear(c, g, EPI_BIAS, st));
-    S2V_TRY(launch_unpatchify(c->proj, Co, c->V, out, B, c->F, c->cfg.out_channels, c->H, c->W, c->dtype, st));
+    return linear(c, g, EPI_BIAS, st);
+}
+
+static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* t_dev, void* out,
+                        hipStream_t st) {
+    S2V_REQUIRE(c->ws && c->finalized && c->have_cond, "transformer_forward: geometry, weights and conditioning required");
+    S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "transformer_forward: RoPE tables missing (s2v_set_rope)");
+    S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "transformer_forward: sincos table missing (s2v_set_pos_embed)");
+    S2V_REQUIRE(!c->shard, "transformer_forward: a shard context (s2v_set_shard) runs the staged step only (s2v_shard_step_* / s2v_denoise_step_ulysses)");
+    const int D = c->D;
+    const int64_t E = c->esz;
+    S2V_TRY(embed_streams(c, latents, lat_bstride, t_dev, st));
+    // 3. blocks
+    for (int l = 0; l < c->L; ++l)
+        S2V_TRY(run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st));
+    // 4. tail
+    S2V_TRY(tail_proj(c, st));
+    const int Co = c->cfg.out_channels * 4;
+    S2V_TRY(launch_unpatchify(c->proj, Co, c->V, out, c->B, c->F, c->cfg.out_channels, c->H, c->W, c->dtype, st));
     return 0;
 }
 
@@ -898,6 +1055,7 @@ extern "C" int s2v_transformer_forward(s2v_ctx* c, const void* latents, int64_t 
 extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, const void* enc0, const void* enc1,
                                  const void* temb, void* out_hidden, void* out_enc0, void* out_enc1, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws && c->finalized, "s2v_block_forward: geometry and weights required");
+    S2V_REQUIRE(!c->shard, "s2v_block_forward: a shard context (s2v_set_shard) runs the staged step only");
     S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_block_forward: bad layer");
     S2V_REQUIRE(hidden && enc1 && temb && out_hidden && out_enc1, "s2v_block_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -926,6 +1084,7 @@ extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, 
 extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
                                 void* out_encoder, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws && c->finalized, "s2v_attn_forward: geometry and weights required");
+    S2V_REQUIRE(!c->shard, "s2v_attn_forward: a shard context (s2v_set_shard) runs the staged step only");
     S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_attn_forward: bad layer");
     S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -987,6 +1146,9 @@ extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B == 2), "s2v_denoise_step: geometry with B = 1 or 2 (CFG pair) required");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
     S2V_REQUIRE(coef_host->kind == 0 || (noise && x0_hist), "s2v_denoise_step: DPM needs noise and x0_hist");
+    S2V_REQUIRE(!c->shard, use_graph ? "s2v_denoise_step: hipGraph capture is not supported for a shard context (s2v_set_shard): its step is staged around "
+                                       "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
+                                     : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     hipStream_t st = (hipStream_t)stream;
     s2v_ctx::Stage& sg = c->ring[c->ring_pos];
     c->ring_pos = (c->ring_pos + 1) % RING;
@@ -1027,6 +1189,7 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
                                        int32_t use_graph, s2v_stream stream) {
     S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_split_begin: null argument");
     S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required");
+    S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_split_begin: in/out channels must match");
     hipStream_t st = (hipStream_t)stream;
@@ -1087,6 +1250,245 @@ extern "C" int s2v_denoise_step_cfg_parallel(s2v_ctx* c, s2v_rccl_comm* comm, in
     const int64_t half = pair_half_bytes(c);
     S2V_TRY(s2v_rccl_allgather(comm, c->noise_pred + (int64_t)slot * half, c->noise_pred, half, stream));  // in place: rank r owns half r
     return s2v_denoise_split_end(c, latents, x0_hist, noise, stream);
+}
+
+// ---- Ulysses sequence parallelism: ONE video's step on p GPUs -------------------------------------------------------------------------------
+// Every row-wise kernel runs on the rank's mini-sequence [T_r | R_r | V_r] of each sample; the attention runs on heads [r*H/p, (r+1)*H/p) of all
+// gN tokens, in global token order.  Two all-to-alls per block (QKV rows -> heads, attention output heads -> rows) and one all-gather of the
+// projected video rows per step; the caller moves the bytes (s2v_shard_buffers) or s2v_denoise_step_ulysses does it over RCCL.
+int s2v_rccl_shard_check(s2v_rccl_comm* comm, int world, int rank);  // rccl.hip (not exported)
+
+static bool shard_fused_qk(const s2v_ctx* c) {
+    bool f = (c->mfma || c->h16) && c->D % 64 == 0 && (!c->have_rope || c->rope_paired);
+#ifdef S2V_DIAG
+    f = f && g_fused_qk != 0;
+#endif
+    return f;
+}
+
+// LN1 of layer l, the QKV projection with q/k LayerNorm + RoPE on the rank's rows, pack: chunk g of sbuf = [M][q_g | k_g | v_g]
+static int shard_front(s2v_ctx* c, int l, hipStream_t st) {
+    const LayerW& w = c->layers[l];
+    const int D = c->D;
+    const int64_t E = c->esz, Dp = D / c->sp;
+    const char* mb = c->mod + (int64_t)(2 * l) * c->mc * D * E;
+    bool prequant = false;
+    S2V_TRY(block_norm(c, l, 0, mb, c->mod_rows, st, &prequant));
+    GemmArgs g{};
+    g.A = c->Xn; g.lda = D; g.W = w.wqkv; g.ldw = D; g.bias = w.bqkv;
+    g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = D;
+    const bool fused = shard_fused_qk(c);
+    if (fused) {
+        g.tok_per_batch = c->Ntok; g.text_len = c->T;
+        g.qk_w[0] = w.nq_w; g.qk_b[0] = w.nq_b; g.qk_w[1] = w.nk_w; g.qk_b[1] = w.nk_b;
+        g.qk_cs = c->have_rope ? c->rope_pk : nullptr;
+        g.qk_D = D; g.qk_eps = 1e-6f;
+    }
+    {
+        ProfScope ps(c, PK_QKV, st);
+        S2V_TRY(linear(c, g, fused ? EPI_BIAS_QKNORM : EPI_BIAS, st));
+    }
+    if (!fused) {  // V^T is made after the exchange, on the head-sharded buffer
+        QkNormRopeArgs q{};
+        q.qkv = c->QKV; q.ld_qkv = 3 * D; q.B = c->B; q.H = c->cfg.num_heads; q.Ntok = c->Ntok; q.text_len = c->T;
+        q.nq_w = w.nq_w; q.nq_b = w.nq_b; q.nk_w = w.nk_w; q.nk_b = w.nk_b; q.eps = 1e-6f;
+        q.cos = c->have_rope ? c->rope_cos : nullptr; q.sin = c->have_rope ? c->rope_sin : nullptr;
+        q.vt = nullptr; q.ntok_pad = c->ntok_pad;
+        ProfScope ps(c, PK_QKNORM, st);
+        S2V_TRY(launch_qk_norm_rope(q, c->dtype, st));
+    }
+    ShardCopyArgs a{};
+    a.src = c->QKV; a.dst = c->sbuf; a.rows = (int)c->M; a.width16 = (int)(Dp * E / 16);
+    a.src_ld = 3 * D * E; a.dst_ld = 3 * Dp * E;
+    a.nseg = 3 * c->sp; a.nseg_inner = 3;
+    a.src_seg_outer = Dp * E; a.src_seg_inner = D * E; a.dst_seg_outer = c->M * 3 * Dp * E; a.dst_seg_inner = Dp * E;
+    ProfScope ps(c, PK_SHARD, st);
+    return launch_shard_copy(a, st);
+}
+
+// unpack the QKV exchange into global token order, V^T, attention on the rank's heads, pack: chunk q of sbuf = rank q's rows of the output
+static int shard_attention(s2v_ctx* c, hipStream_t st) {
+    const int64_t E = c->esz, Dp = c->D / c->sp, Mg = (int64_t)c->B * c->gN;
+    const int H = c->cfg.num_heads / c->sp;
+    {
+        ShardCopyArgs a{};
+        a.src = c->rbuf; a.dst = c->QKVh; a.rows = (int)Mg; a.width16 = (int)(3 * Dp * E / 16);
+        a.src_ld = a.dst_ld = 3 * Dp * E; a.dst_map = c->rmap; a.nseg = 1; a.nseg_inner = 1;
+        ProfScope ps(c, PK_SHARD, st);
+        S2V_TRY(launch_shard_copy(a, st));
+    }
+    const bool p16 = c->attn_p16 && c->mfma && attn_runs_q4(c->gN, false);
+    if (c->mfma || c->h16) {
+        ProfScope ps(c, PK_QKNORM, st);
+        S2V_TRY(launch_v_transpose(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->VT, c->ntok_pad, st, p16));
+    }
+    AttnArgs a{};
+    a.qkv = c->QKVh; a.ld_qkv = (int)(3 * Dp); a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Oh; a.ld_out = (int)Dp;
+    a.B = c->B; a.H = H; a.Ntok = c->gN; a.scale = 0.125f;
+    a.queue = c->attn_queue; a.num_cus = c->num_cus;
+    a.p16 = p16 ? 1 : 0;
+    a.stats = c->attn_stats;
+    a.valu_only = c->cfg.force_simple;
+    a.stagger = c->attn_stagger;
+    a.order = c->attn_order;
+    {
+        ProfScope ps(c, PK_ATTN, st);
+        a.clk = c->clk_cur;
+        if (c->mfma) S2V_TRY(launch_attn_bf16(a, st));
+        else if (c->h16) S2V_TRY(launch_attn_f16(a, st));
+        else S2V_TRY(launch_attn_simple(a, c->dtype, st));
+    }
+    ShardCopyArgs o{};
+    o.src = c->Oh; o.dst = c->sbuf; o.rows = (int)Mg; o.width16 = (int)(Dp * E / 16);
+    o.src_ld = o.dst_ld = Dp * E; o.src_map = c->rmap; o.nseg = 1; o.nseg_inner = 1;
+    ProfScope ps(c, PK_SHARD, st);
+    return launch_shard_copy(o, st);
+}
+
+// unpack the O exchange (head group g -> columns g*D/p of Xn), out-projection, LN2, FF; then the next layer's front or the tail
+static int shard_back(s2v_ctx* c, int l, hipStream_t st, int* pending) {
+    const int D = c->D;
+    const int64_t E = c->esz, Dp = D / c->sp;
+    {
+        ShardCopyArgs a{};
+        a.src = c->rbuf; a.dst = c->Xn; a.rows = (int)c->M; a.width16 = (int)(Dp * E / 16);
+        a.src_ld = Dp * E; a.dst_ld = D * E; a.nseg = c->sp; a.nseg_inner = 1;
+        a.src_seg_outer = c->M * Dp * E; a.dst_seg_outer = Dp * E;
+        ProfScope ps(c, PK_SHARD, st);
+        S2V_TRY(launch_shard_copy(a, st));
+    }
+    const char* mb = c->mod + (int64_t)(2 * l) * c->mc * D * E;
+    S2V_TRY(block_out_proj(c, l, block_gate(c, 0, mb, c->mod_rows), st));
+    bool prequant = false;
+    S2V_TRY(block_norm(c, l, 1, mb, c->mod_rows, st, &prequant));
+    S2V_TRY(block_ff(c, l, block_gate(c, 1, mb, c->mod_rows), prequant, st));
+    if (l + 1 < c->L) {
+        S2V_TRY(shard_front(c, l + 1, st));
+        *pending = S2V_SHARD_QKV_EXCHANGE;
+        return 0;
+    }
+    S2V_TRY(tail_proj(c, st));
+    const int64_t Co = c->cfg.out_channels * 4;
+    ShardCopyArgs a{};
+    a.src = c->proj; a.dst = c->nsend; a.rows = c->V; a.width16 = (int)(Co * E / 16);
+    a.src_ld = a.dst_ld = Co * E; a.nseg = c->B; a.nseg_inner = 1;
+    a.src_seg_outer = (int64_t)c->V * Co * E; a.dst_seg_outer = (int64_t)c->Vmax * Co * E;
+    ProfScope ps(c, PK_SHARD, st);
+    S2V_TRY(launch_shard_copy(a, st));
+    *pending = S2V_SHARD_NOISE_GATHER;
+    return 0;
+}
+
+extern "C" int s2v_shard_layout(s2v_ctx* c, int32_t* out) {
+    S2V_REQUIRE(c && out, "s2v_shard_layout: null argument");
+    S2V_REQUIRE(c->shard && c->ws, "s2v_shard_layout: call s2v_set_shard, then s2v_set_geometry");
+    for (int g = 0; g < c->sp; ++g) {
+        int b, n;
+        shard_range(c->gT, c->sp, g, &b, &n); out[3 * g] = n;
+        shard_range(c->gR, c->sp, g, &b, &n); out[3 * g + 1] = n;
+        shard_range(c->gV, c->sp, g, &b, &n); out[3 * g + 2] = n;
+    }
+    return 0;
+}
+
+extern "C" int s2v_shard_buffers(s2v_ctx* c, int32_t kind, void** send, void** recv, int64_t* send_counts, int64_t* send_displs,
+                                 int64_t* recv_counts, int64_t* recv_displs) {
+    S2V_REQUIRE(c && send && recv && send_counts && send_displs && recv_counts && recv_displs, "s2v_shard_buffers: null argument");
+    S2V_REQUIRE(c->shard && c->ws, "s2v_shard_buffers: call s2v_set_shard, then s2v_set_geometry");
+    S2V_REQUIRE(kind == S2V_SHARD_QKV_EXCHANGE || kind == S2V_SHARD_O_EXCHANGE || kind == S2V_SHARD_NOISE_GATHER, "s2v_shard_buffers: unknown exchange kind");
+    const int k = kind - 1;
+    *send = kind == S2V_SHARD_NOISE_GATHER ? c->nsend : c->sbuf;
+    *recv = kind == S2V_SHARD_NOISE_GATHER ? c->nrecv : c->rbuf;
+    for (int g = 0; g < c->sp; ++g) {
+        send_counts[g] = c->xcnt[k][0][g]; send_displs[g] = c->xcnt[k][1][g];
+        recv_counts[g] = c->xcnt[k][2][g]; recv_displs[g] = c->xcnt[k][3][g];
+    }
+    return 0;
+}
+
+extern "C" int s2v_shard_step_begin(s2v_ctx* c, const void* latents, float timestep, const s2v_sched_coef* coef_host, int32_t* pending,
+                                    s2v_stream stream) {
+    S2V_REQUIRE(c && latents && coef_host && pending, "s2v_shard_step_begin: null argument");
+    S2V_REQUIRE(c->shard, "s2v_shard_step_begin: not a shard context (s2v_set_shard)");
+    S2V_REQUIRE(c->ws && (c->B == 1 || c->B == 2), "s2v_shard_step_begin: geometry with B = 1 or 2 (CFG pair) required");
+    S2V_REQUIRE(c->finalized && c->have_cond, "s2v_shard_step_begin: weights and conditioning required");
+    S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "s2v_shard_step_begin: RoPE tables missing (s2v_set_rope)");
+    S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "s2v_shard_step_begin: sincos table missing (s2v_set_pos_embed)");
+    S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_shard_step_begin: in/out channels must match");
+    hipStream_t st = (hipStream_t)stream;
+    s2v_ctx::Stage& sg = c->ring[c->ring_pos];
+    c->ring_pos = (c->ring_pos + 1) % RING;
+    for (int i = 0; i < 4; ++i) sg.t[i] = timestep;
+    fill_coef(sg.c, *coef_host);
+    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * 4, hipMemcpyHostToDevice, st));
+    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
+    c->sh_pending = 0;
+    S2V_TRY(embed_streams(c, latents, 0, c->t_dev, st));
+    S2V_TRY(shard_front(c, 0, st));
+    c->split_kind = coef_host->kind;
+    c->sh_layer = 0;
+    *pending = c->sh_pending = S2V_SHARD_QKV_EXCHANGE;
+    return 0;
+}
+
+extern "C" int s2v_shard_step_resume(s2v_ctx* c, int32_t* pending, s2v_stream stream) {
+    S2V_REQUIRE(c && pending, "s2v_shard_step_resume: null argument");
+    S2V_REQUIRE(c->shard && (c->sh_pending == S2V_SHARD_QKV_EXCHANGE || c->sh_pending == S2V_SHARD_O_EXCHANGE),
+                "s2v_shard_step_resume: no exchange is pending (s2v_shard_step_begin first; after S2V_SHARD_NOISE_GATHER comes s2v_shard_step_end)");
+    hipStream_t st = (hipStream_t)stream;
+    int next = 0;
+    if (c->sh_pending == S2V_SHARD_QKV_EXCHANGE) {
+        c->sh_pending = 0;  // a failure leaves no step pending
+        S2V_TRY(shard_attention(c, st));
+        next = S2V_SHARD_O_EXCHANGE;
+    } else {
+        c->sh_pending = 0;
+        S2V_TRY(shard_back(c, c->sh_layer, st, &next));
+        if (next == S2V_SHARD_QKV_EXCHANGE) c->sh_layer++;
+    }
+    *pending = c->sh_pending = next;
+    return 0;
+}
+
+extern "C" int s2v_shard_step_end(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, s2v_stream stream) {
+    S2V_REQUIRE(c && latents, "s2v_shard_step_end: null argument");
+    S2V_REQUIRE(c->shard && c->sh_pending == S2V_SHARD_NOISE_GATHER, "s2v_shard_step_end: the noise gather is not pending");
+    S2V_REQUIRE(c->split_kind == 0 || (noise && x0_hist), "s2v_shard_step_end: DPM needs noise and x0_hist");
+    c->sh_pending = 0;
+    c->split_kind = -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t E = c->esz, Co = c->cfg.out_channels * 4;
+    {
+        ShardCopyArgs a{};
+        a.src = c->nrecv; a.dst = c->proj_full; a.rows = c->sp * c->B * c->Vmax; a.width16 = (int)(Co * E / 16);
+        a.src_ld = a.dst_ld = Co * E; a.dst_map = c->nmap; a.nseg = 1; a.nseg_inner = 1;
+        ProfScope ps(c, PK_SHARD, st);
+        S2V_TRY(launch_shard_copy(a, st));
+    }
+    S2V_TRY(launch_unpatchify(c->proj_full, (int)Co, c->gV, c->noise_pred, c->B, c->F, c->cfg.out_channels, c->H, c->W, c->dtype, st));
+    SchedArgs a{};
+    a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
+    a.n = (int64_t)c->F * c->cfg.out_channels * c->H * c->W; a.cfg = c->B == 2 ? 1 : 0; a.coef = c->coef_dev;
+    return launch_sched_step(a, c->dtype, st);
+}
+
+extern "C" int s2v_denoise_step_ulysses(s2v_ctx* c, s2v_rccl_comm* comm, void* latents, float timestep, const s2v_sched_coef* coef_host,
+                                        float* x0_hist, const void* noise, s2v_stream stream) {
+    S2V_REQUIRE(c && comm && latents && coef_host, "s2v_denoise_step_ulysses: null argument");
+    S2V_REQUIRE(c->shard, "s2v_denoise_step_ulysses: not a shard context (s2v_set_shard)");
+    S2V_REQUIRE(coef_host->kind == 0 || (noise && x0_hist), "s2v_denoise_step_ulysses: DPM needs noise and x0_hist");
+    S2V_TRY(s2v_rccl_shard_check(comm, c->sp, c->sr));
+    int pending = 0;
+    std::vector<int64_t> sc(c->sp), sd(c->sp), rc(c->sp), rd(c->sp);
+    S2V_TRY(s2v_shard_step_begin(c, latents, timestep, coef_host, &pending, stream));
+    for (;;) {
+        void *sb = nullptr, *rb = nullptr;
+        S2V_TRY(s2v_shard_buffers(c, pending, &sb, &rb, sc.data(), sd.data(), rc.data(), rd.data()));
+        S2V_TRY(s2v_rccl_alltoallv(comm, sb, sc.data(), sd.data(), rb, rc.data(), rd.data(), stream));
+        if (pending == S2V_SHARD_NOISE_GATHER) break;
+        S2V_TRY(s2v_shard_step_resume(c, &pending, stream));
+    }
+    return s2v_shard_step_end(c, latents, x0_hist, noise, stream);
 }
 
 // Per-kernel-class timing (HIP events recorded on the launch stream around every launch of the class).

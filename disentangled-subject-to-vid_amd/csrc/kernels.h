@@ -229,6 +229,18 @@ int launch_patchify(const void* lat, int64_t lat_bstride, int Bn, int F, int C, 
 // y [B*V, C*4] (feature c*4+py*2+px) -> out [B, F, C, H, W]; rows of y start at y_row0 with batch stride y_bstride rows
 int launch_unpatchify(const void* y, int ldy, int64_t y_bstride, void* out, int B, int F, int C, int H, int W, int dtype,
                       hipStream_t st);
+// Ulysses packs / unpacks (ulysses.hip): for every segment k = (ko, ki) of nseg = (nseg / nseg_inner) x nseg_inner and row i < rows,
+// width16 16-byte pieces move from src + ko * src_seg_outer + ki * src_seg_inner + smap(i) * src_ld to the same place under dst's strides;
+// smap / dmap = the row maps when given (identity otherwise), a negative map entry skips the row.  Byte offsets and strides, all 16-aligned.
+struct ShardCopyArgs {
+    const char* src; char* dst;
+    int rows, width16;
+    int64_t src_ld, dst_ld;
+    const int* src_map; const int* dst_map;
+    int nseg, nseg_inner;
+    int64_t src_seg_outer, src_seg_inner, dst_seg_outer, dst_seg_inner;
+};
+int launch_shard_copy(const ShardCopyArgs& a, hipStream_t st);
 // dst[r][:] = rnd(src[r][:] (+ add[r][:]))
 int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void* dst, int ldd, int rows, int D,
                      int dtype, hipStream_t st);

@@ -28,6 +28,8 @@ typedef int (*BroadcastFn)(const void*, void*, size_t, int, int, Comm, hipStream
 typedef int (*AllGatherFn)(const void*, void*, size_t, int, Comm, hipStream_t);
 typedef const char* (*GetErrorStringFn)(int);
 typedef int (*GroupFn)(void);
+typedef int (*SendFn)(const void*, size_t, int, int, Comm, hipStream_t);
+typedef int (*RecvFn)(void*, size_t, int, int, Comm, hipStream_t);
 
 struct Rccl {
     void* so = nullptr;
@@ -38,6 +40,8 @@ struct Rccl {
     AllGatherFn all_gather = nullptr;
     GetErrorStringFn error_string = nullptr;
     GroupFn group_start = nullptr, group_end = nullptr;
+    SendFn send = nullptr;
+    RecvFn recv = nullptr;
     std::string why;
 };
 
@@ -57,7 +61,7 @@ void bind_rccl() {
         {"ncclGetUniqueId", (void**)&g_rccl.get_unique_id}, {"ncclCommInitRank", (void**)&g_rccl.comm_init_rank},
         {"ncclCommDestroy", (void**)&g_rccl.comm_destroy}, {"ncclBroadcast", (void**)&g_rccl.broadcast}, {"ncclAllGather", (void**)&g_rccl.all_gather},
         {"ncclGetErrorString", (void**)&g_rccl.error_string}, {"ncclGroupStart", (void**)&g_rccl.group_start},
-        {"ncclGroupEnd", (void**)&g_rccl.group_end}};
+        {"ncclGroupEnd", (void**)&g_rccl.group_end}, {"ncclSend", (void**)&g_rccl.send}, {"ncclRecv", (void**)&g_rccl.recv}};
     for (auto& s : syms) {
         *s.fn = dlsym(g_rccl.so, s.name);
         if (!*s.fn) { g_rccl.why = std::string("symbol missing in librccl: ") + s.name; g_rccl.so = nullptr; return; }
@@ -152,6 +156,39 @@ extern "C" int s2v_rccl_allgather(s2v_rccl_comm* c, const void* send, void* recv
 int s2v_rccl_pair_check(s2v_rccl_comm* c, int slot) {
     S2V_REQUIRE(c && c->comm, "s2v_denoise_step_cfg_parallel: null communicator");
     S2V_REQUIRE(c->world == 2 && c->rank == slot, "s2v_denoise_step_cfg_parallel: the communicator must hold exactly the two ranks of the pair, and its rank must equal `slot`");
+    return 0;
+}
+
+// The exchanges of Ulysses sequence parallelism (api.hip s2v_denoise_step_ulysses): per peer g, send_counts[g] bytes from send + send_displs[g]
+// and recv_counts[g] bytes into recv + recv_displs[g]; one ncclGroup of ncclSend / ncclRecv pairs on `stream`, the self part a device copy.
+extern "C" int s2v_rccl_alltoallv(s2v_rccl_comm* c, const void* send, const int64_t* send_counts, const int64_t* send_displs, void* recv,
+                                  const int64_t* recv_counts, const int64_t* recv_displs, s2v_stream stream) {
+    S2V_REQUIRE(c && c->comm && send && recv && send_counts && send_displs && recv_counts && recv_displs, "s2v_rccl_alltoallv: bad argument");
+    S2V_REQUIRE(send_counts[c->rank] == recv_counts[c->rank], "s2v_rccl_alltoallv: the self part must send as many bytes as it receives");
+    for (int g = 0; g < c->world; ++g)
+        S2V_REQUIRE(send_counts[g] >= 0 && recv_counts[g] >= 0 && send_displs[g] >= 0 && recv_displs[g] >= 0, "s2v_rccl_alltoallv: negative count or displacement");
+    const hipStream_t st = (hipStream_t)stream;
+    if (send_counts[c->rank] > 0)
+        S2V_CHECK_HIP(hipMemcpyAsync((char*)recv + recv_displs[c->rank], (const char*)send + send_displs[c->rank], (size_t)send_counts[c->rank],
+                                     hipMemcpyDeviceToDevice, st));
+    if (c->world == 1) return 0;
+    int rc = g_rccl.group_start();
+    if (rc) return nccl_fail("ncclGroupStart", rc);
+    for (int g = 0; g < c->world && !rc; ++g) {
+        if (g == c->rank) continue;
+        if (send_counts[g] > 0) rc = g_rccl.send((const char*)send + send_displs[g], (size_t)send_counts[g], /*ncclUint8*/ 1, g, c->comm, st);
+        if (!rc && recv_counts[g] > 0) rc = g_rccl.recv((char*)recv + recv_displs[g], (size_t)recv_counts[g], /*ncclUint8*/ 1, g, c->comm, st);
+    }
+    const int rc_end = g_rccl.group_end();
+    if (rc) return nccl_fail("ncclSend / ncclRecv", rc);
+    if (rc_end) return nccl_fail("ncclGroupEnd", rc_end);
+    return 0;
+}
+
+// s2v_denoise_step_ulysses's communicator: exactly the shard's ranks, rank r = shard rank r
+int s2v_rccl_shard_check(s2v_rccl_comm* c, int world, int rank) {
+    S2V_REQUIRE(c && c->comm, "s2v_denoise_step_ulysses: null communicator");
+    S2V_REQUIRE(c->world == world && c->rank == rank, "s2v_denoise_step_ulysses: the communicator's world size and rank must equal the shard's (s2v_set_shard)");
     return 0;
 }
 

@@ -365,3 +365,170 @@ def run_replicas(make_engine, load_weights_rank0, prompts, run_prompt):
         broadcast_components(eng if isinstance(eng, (tuple, list)) else [eng], 0)
     mine = {p: run_prompt(eng, p, prompts[p]) for p in shard_prompts(len(prompts), rank, world)}
     return gather_results(mine, 0)
+
+
+# ---- Ulysses sequence parallelism: ONE video's step on p GPUs, attention sharded by heads ----------
+def shard_range(n, world, rank):
+    """rank's share [begin, end) of a stream of n rows: [rank * n // world, (rank + 1) * n // world)"""
+    return rank * n // world, (rank + 1) * n // world
+
+
+def shard_layout(T, R, V, world):
+    """[(T_r, R_r, V_r) for every rank]: each stream (text, reference, video) of a sample is split separately (s2v_shard_layout)"""
+    out = []
+    for r in range(world):
+        out.append(tuple(e - b for b, e in (shard_range(n, world, r) for n in (T, R, V))))
+    return out
+
+
+def shard_row_map(B, T, R, V, world):
+    """recv row of the QKV exchange -> global row: rank g's rows of sample b in g's local order [T_g | R_g | V_g], concatenated over g (the
+    index map the library builds; a permutation of range(B * (T + R + V)))"""
+    N = T + R + V
+    rows = []
+    for g in range(world):
+        (t0, t1), (r0, r1), (v0, v1) = (shard_range(n, world, g) for n in (T, R, V))
+        for b in range(B):
+            rows += [b * N + t for t in range(t0, t1)]
+            rows += [b * N + T + r for r in range(r0, r1)]
+            rows += [b * N + T + R + v for v in range(v0, v1)]
+    return rows
+
+
+def _check_contiguous(counts, displs):
+    off = 0
+    for n, d in zip(counts, displs):
+        if d != off:
+            raise RuntimeError(f"exchange layout is not rank-ordered and contiguous (counts {counts}, displacements {displs})")
+        off += n
+
+
+def _ulysses_step(engine, exchange, latents, timestep, coef, x0_hist, noise):
+    from . import _lib
+
+    pending = engine.shard_step_begin(latents, timestep, coef)
+    while True:
+        exchange(pending)
+        if pending == _lib.SHARD_NOISE_GATHER:
+            break
+        pending = engine.shard_step_resume()
+    engine.shard_step_end(latents, x0_hist, noise)
+
+
+class UlyssesLocal:
+    """p shard engines driven in lockstep by ONE process (engines[r] = rank r, set_shard(p, r) done by the caller), their exchanges done by device
+    copies on the current stream: the one-device harness of the tests and of tools/ulysses_projection.py."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        self.world = len(self.engines)
+        for r, e in enumerate(self.engines):
+            if e.shard != (self.world, r):
+                raise RuntimeError(f"engine {r} holds shard {e.shard}, expected ({self.world}, {r})")
+
+    def exchange(self, kind):
+        bufs = [e.shard_buffers(kind) for e in self.engines]
+        for q, (_, recv, _, _, rc, rd) in enumerate(bufs):
+            for g, (send, _, sc, sd, _, _) in enumerate(bufs):
+                if sc[q] != rc[g]:
+                    raise RuntimeError(f"exchange {kind}: rank {g} sends {sc[q]} bytes to rank {q}, which expects {rc[g]}")
+                recv[rd[g]:rd[g] + rc[g]].copy_(send[sd[q]:sd[q] + sc[q]])
+
+    def step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
+        """latents / x0_hist: one tensor per rank (each updated in place, all ending bit-identical); noise: shared (read only)"""
+        from . import _lib
+
+        if use_graph:
+            raise _lib.S2VError("use_graph is not supported for a Ulysses shard: the step is staged around its exchanges and runs eagerly")
+        x0 = x0_hist if x0_hist is not None else [None] * self.world
+        pend = [e.shard_step_begin(l, timestep, coef) for e, l in zip(self.engines, latents)]
+        while True:
+            self.exchange(pend[0])
+            if pend[0] == _lib.SHARD_NOISE_GATHER:
+                break
+            pend = [e.shard_step_resume() for e in self.engines]
+        for e, l, x in zip(self.engines, latents, x0):
+            e.shard_step_end(l, x, noise)
+
+
+class UlyssesGroup:
+    """Every rank of the process group shares one video's step (world = the shard's p, rank = its r).  Transports: native=True -> the library's own
+    RCCL communicator (s2v_denoise_step_ulysses: grouped ncclSend / ncclRecv, stream-ordered, one process per GPU); otherwise the staged step with
+    torch.distributed.all_to_all_single on uneven splits -- on the device for backend nccl, host-staged through pinned memory after the stream has
+    drained for any other backend with device tensors (gloo: see CfgPair.exchange for why), directly for CPU tensors."""
+
+    def __init__(self, native=False, group=None):
+        if not dist.is_initialized():
+            raise RuntimeError("UlyssesGroup needs an initialised process group")
+        self.group = group
+        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+        self.comm = RcclComm(group=group) if native else None
+        self._host = {}
+        self._dev = {}
+
+    def exchange(self, engine, kind):
+        from . import _lib
+
+        send, recv, sc, sd, rc, rd = engine.shard_buffers(kind)
+        if kind == _lib.SHARD_NOISE_GATHER:  # the same rows to every rank: all_to_all_single wants them laid out once per peer
+            src = send[sd[0]:sd[0] + sc[0]].repeat(self.world)
+            sc = [sc[0]] * self.world
+        else:
+            _check_contiguous(sc, sd)
+            src = send[:sum(sc)]
+        _check_contiguous(rc, rd)
+        dst = recv[:sum(rc)]
+        if src.is_cuda and dist.get_backend(self.group) != "nccl":
+            hs = self._host.get(("s", kind))
+            if hs is None or hs.numel() != src.numel():
+                hs = self._host[("s", kind)] = torch.empty(src.numel(), dtype=torch.uint8).pin_memory()
+            hr = self._host.get(("r", kind))
+            if hr is None or hr.numel() != dst.numel():
+                hr = self._host[("r", kind)] = torch.empty(dst.numel(), dtype=torch.uint8).pin_memory()
+            hs.copy_(src, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            dist.all_to_all_single(hr, hs, output_split_sizes=rc, input_split_sizes=sc, group=self.group)
+            dst.copy_(hr, non_blocking=True)
+            return
+        if src.is_cuda:  # nccl (= RCCL): torch-allocated buffers, the library's memory stays out of c10d's allocator bookkeeping (CfgPair.exchange)
+            out = self._dev.get(kind)
+            if out is None or out.numel() != dst.numel() or out.device != dst.device:
+                out = self._dev[kind] = torch.empty(dst.numel(), dtype=torch.uint8, device=dst.device)
+            dist.all_to_all_single(out, src.clone(), output_split_sizes=rc, input_split_sizes=sc,
+                                   group=self.group)
+            dst.copy_(out, non_blocking=True)
+            return
+        dist.all_to_all_single(dst, src.contiguous(), output_split_sizes=rc, input_split_sizes=sc,
+                               group=self.group)
+
+    def assert_same(self, **tensors):
+        """once per video: every rank must hold the SAME start latents, reference latent and embeddings (each applies the scheduler step to its own
+        copy); raises on every rank when they differ"""
+        sums = {}
+        for k, t in tensors.items():
+            if t is None:
+                sums[k] = None
+                continue
+            b = t.detach().contiguous().view(torch.uint8).to(torch.int64)
+            w = torch.arange(1, b.numel() + 1, device=b.device, dtype=torch.int64) % 65521
+            sums[k] = (tuple(t.shape), str(t.dtype), int((b.view(-1) * w).sum().item()))
+        every = [None] * self.world
+        dist.all_gather_object(every, sums, group=self.group)
+        bad = [k for k in sums if any(e[k] != every[0][k] for e in every)]
+        if bad:
+            raise RuntimeError(f"Ulysses group: the ranks were given different {bad}; pass the same tensors, or generators seeded alike, to every rank")
+
+    def step(self, engine, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
+        """one denoise step of the group's video; latents (identical on every rank) updated in place on every rank"""
+        if engine.shard != (self.world, self.rank):
+            raise RuntimeError(f"the engine holds shard {engine.shard}, this rank is ({self.world}, {self.rank}): call engine.set_shard first")
+        if self.comm is not None:
+            engine.denoise_step_ulysses(self.comm, latents, timestep, coef, x0_hist, noise, use_graph)
+            return
+        engine._shard_checks(latents, use_graph)
+        _ulysses_step(engine, lambda kind: self.exchange(engine, kind), latents, timestep, coef, x0_hist, noise)
+
+    def close(self):
+        if self.comm is not None:
+            self.comm.close()
+            self.comm = None

@@ -312,6 +312,69 @@ class S2VEngine:
         _lib.check(_lib.lib().s2v_denoise_step_cfg_parallel(self._h, comm._h, int(slot), _lib.ptr(latents), float(timestep), ctypes.byref(coef),
                                                             _lib.ptr(x0_hist), _lib.ptr(noise), int(use_graph), _lib.stream_ptr()))
 
+    # ---- Ulysses sequence parallelism: p engines share one video's step, attention sharded by heads (include/s2v_hip.h, dist.UlyssesGroup) ----------
+    def set_shard(self, world, rank):
+        """before set_geometry: this engine holds rank `rank`'s rows [T_r | R_r | V_r] of every sample and heads [rank*H/world, (rank+1)*H/world)"""
+        if self.cfg.attn_p_format == "auto":  # "auto" settles per engine from its own census: the ranks could settle on different arithmetic
+            raise _lib.S2VError("attn_p_format 'auto' is per-engine; the ranks of a Ulysses shard must run the same arithmetic: use 'bf16' or 'f16'")
+        _lib.check(_lib.lib().s2v_set_shard(self._h, int(world), int(rank)))
+        if self.shard != (int(world), int(rank)):
+            self.geometry = None
+        self.shard = (int(world), int(rank))
+
+    shard = None
+
+    def shard_layout(self):
+        """[(T_r, R_r, V_r) for every rank r] of the current geometry"""
+        p = self.shard[0]
+        out = (ctypes.c_int32 * (3 * p))()
+        _lib.check(_lib.lib().s2v_shard_layout(self._h, out))
+        return [tuple(out[3 * r:3 * r + 3]) for r in range(p)]
+
+    def shard_buffers(self, kind):
+        """(send, recv, send_counts, send_displs, recv_counts, recv_displs) of an exchange kind (_lib.SHARD_*): uint8 CUDA views of the
+        context-owned buffers and per-rank byte counts / displacements (lists)"""
+        p = self.shard[0]
+        s, r = ctypes.c_void_p(), ctypes.c_void_p()
+        arr = [(ctypes.c_int64 * p)() for _ in range(4)]
+        _lib.check(_lib.lib().s2v_shard_buffers(self._h, int(kind), ctypes.byref(s), ctypes.byref(r), *arr))
+        sc, sd, rc, rd = ([int(x) for x in a] for a in arr)
+        send = torch.as_tensor(_ArenaView(s.value, max(d + n for d, n in zip(sd, sc))), device=self.device)
+        recv = torch.as_tensor(_ArenaView(r.value, max(d + n for d, n in zip(rd, rc))), device=self.device)
+        return send, recv, sc, sd, rc, rd
+
+    def _shard_checks(self, latents, use_graph=False):
+        if self.shard is None:
+            raise _lib.S2VError("not a shard engine: call set_shard(world, rank) before set_geometry")
+        if use_graph:
+            raise _lib.S2VError("use_graph is not supported for a Ulysses shard: the step is staged around its exchanges and runs eagerly")
+        if latents is not None and (latents.dtype != self.dtype or not latents.is_contiguous()):
+            raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
+
+    def shard_step_begin(self, latents, timestep, coef):
+        """local rows up to the first exchange; returns the pending exchange kind (_lib.SHARD_QKV_EXCHANGE)"""
+        self._shard_checks(latents)
+        pending = ctypes.c_int32()
+        _lib.check(_lib.lib().s2v_shard_step_begin(self._h, _lib.ptr(latents), float(timestep), ctypes.byref(coef), ctypes.byref(pending),
+                                                   _lib.stream_ptr()))
+        return pending.value
+
+    def shard_step_resume(self):
+        """after the pending exchange has filled the recv buffer: runs up to the next exchange point and returns its kind"""
+        pending = ctypes.c_int32()
+        _lib.check(_lib.lib().s2v_shard_step_resume(self._h, ctypes.byref(pending), _lib.stream_ptr()))
+        return pending.value
+
+    def shard_step_end(self, latents, x0_hist=None, noise=None):
+        """after the noise gather: CFG + scheduler step on the whole latent, run by every rank (latents updated in place)"""
+        _lib.check(_lib.lib().s2v_shard_step_end(self._h, _lib.ptr(latents), _lib.ptr(x0_hist), _lib.ptr(noise), _lib.stream_ptr()))
+
+    def denoise_step_ulysses(self, comm, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
+        """the whole staged step with s2v_rccl_alltoallv exchanges over an RcclComm of the shard's ranks, stream-ordered"""
+        self._shard_checks(latents, use_graph)
+        _lib.check(_lib.lib().s2v_denoise_step_ulysses(self._h, comm._h, _lib.ptr(latents), float(timestep), ctypes.byref(coef),
+                                                       _lib.ptr(x0_hist), _lib.ptr(noise), _lib.stream_ptr()))
+
     def last_noise_pred(self):
         B, T, F, H, W = self.geometry
         p = ctypes.c_void_p()

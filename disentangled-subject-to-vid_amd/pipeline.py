@@ -58,10 +58,12 @@ class S2VPipeline:
     def __call__(self, prompt_embeds=None, negative_prompt_embeds=None, ref_img_states=None, height=480, width=720,
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
-                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None):
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None):
         """cfg_parallel: a dist.CfgPair -- this process runs ONE sample of the CFG pair (slot 0: negative prompt, slot 1: prompt) on its GPU and its
         peer the other; every rank of the pair passes the SAME arguments (embeddings, reference latent, latents or an equally seeded generator) and
-        returns the same latents / video bit for bit.  fused mode only."""
+        returns the same latents / video bit for bit.  fused mode only.
+        ulysses: a dist.UlyssesGroup -- the group's ranks share every step of this video (both samples of the CFG pair, the rows of each stream
+        split over the ranks, attention sharded by heads); same arguments on every rank, same latents back.  fused mode only, not with cfg_parallel."""
         if num_frames > 49:
             raise ValueError("The number of frames must be less than or equal to 49 due to static positional embeddings.")
         self.check_inputs(height, width, prompt_embeds, negative_prompt_embeds)
@@ -95,6 +97,13 @@ class S2VPipeline:
             cos, sin = torch.from_numpy(cos).to(dev), torch.from_numpy(sin).to(dev)
             ref_rope, rope = (cos[:n], sin[:n]), (cos[n:], sin[n:])
 
+        if ulysses is not None and cfg_parallel is not None:
+            raise ValueError("ulysses and cfg_parallel do not compose yet: a Ulysses group runs both samples of the CFG pair on every rank")
+        if ulysses is not None and not fused:
+            raise ValueError("ulysses runs the fused step; fused=False is the reference's seam sequence")
+        if ulysses is not None:
+            ulysses.assert_same(latents=latents, ref_img_states=ref, text=text)
+            eng.set_shard(ulysses.world, ulysses.rank)
         if cfg_parallel is not None and not fused:
             raise ValueError("cfg_parallel runs the fused step (one sample of the CFG pair per rank); fused=False is the reference's seam sequence")
         if cfg_parallel is not None:  # both ranks compute from the same inputs or the video is garbage: checked once, collectively
@@ -123,7 +132,9 @@ class S2VPipeline:
                         self._draw(noise, generator)  # the reference discards its first draw on multistep steps
                 else:
                     coef = sch.coef(t, dt, g)
-                if cfg_parallel is None:
+                if ulysses is not None:
+                    ulysses.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
+                elif cfg_parallel is None:
                     eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph)
                 else:
                     cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)

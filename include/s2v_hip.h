@@ -232,6 +232,52 @@ S2V_API int s2v_denoise_step_cfg_parallel(s2v_ctx* ctx, s2v_rccl_comm* comm, int
                                           const s2v_sched_coef* coef_host, float* x0_hist, const void* noise, int32_t use_graph,
                                           s2v_stream stream);
 
+/* ---- Ulysses sequence parallelism: ONE video's step on p GPUs, attention sharded by heads -------
+ * p ranks share one video's denoise step with both samples of the CFG pair (B = 2, or B = 1).  Each rank calls s2v_set_shard(p, r) BEFORE
+ * s2v_set_geometry and then the usual set-up with FULL-size arguments: s2v_set_geometry(B, T, F, H, W), s2v_set_rope / s2v_set_pos_embed with the
+ * whole tables, s2v_set_conditioning with the whole [B, T, text_embed_dim] embeddings; the context keeps its rank's rows.
+ *   Shard geometry: every stream is split separately, rank r keeping rows [r*n/p, (r+1)*n/p) (integer division) of the text (n = T), the
+ *   reference (n = R = H/2 * W/2) and the video (n = V = F * R) tokens of each sample: its mini-sequence [T_r | R_r | V_r].  Every row-wise
+ *   kernel (LayerNorm-modulate, the linears and their epilogues, q/k-norm + RoPE, the tail) runs on those rows; the attention runs on heads
+ *   [r*H/p, (r+1)*H/p) of all N = T + R + V tokens in global token order.  Shards are ragged (19 126 tokens at p = 4: text shards 56/57/56/57).
+ *   Requirements: p divides num_heads; weight_format 0 (no fp8); every rank holds >= 1 video row.  p = 1 computes what s2v_denoise_step does.
+ *   A shard context runs ONLY the staged step below (s2v_denoise_step, s2v_transformer_forward, the seams and CFG-parallel are refused), eagerly:
+ *   hipGraph capture is not supported for shard contexts.  Bit-identity with the single engine: split-K is never chosen on a shard (a rank's
+ *   row count must not pick another reduction order); geometries on which the single engine splits K (few row tiles and K >= 2048) differ.
+ * Staged step (any transport):
+ *   s2v_shard_step_begin   time embedding, modulation GEMV, patchify + patch embed, layer 0 LN1, QKV (+ q/k-norm, RoPE), pack
+ *                          -> *pending = S2V_SHARD_QKV_EXCHANGE;
+ *   the caller exchanges   s2v_shard_buffers(kind = *pending): all-to-all-v of bytes, send + send_displs[g] (send_counts[g] bytes) to rank g,
+ *                          recv + recv_displs[g] (recv_counts[g] bytes) from rank g;
+ *   s2v_shard_step_resume  after QKV: unpack, V^T, attention, pack -> S2V_SHARD_O_EXCHANGE;  after O: unpack, out-projection (gate + residual),
+ *                          LN2, FF, then the next layer's LN1 + QKV + pack -> S2V_SHARD_QKV_EXCHANGE, or after the last layer the tail norm
+ *                          and projection of the rank's V_r rows -> S2V_SHARD_NOISE_GATHER (an all-gather: every rank sends the same
+ *                          [B][ceil(V/p)][Cout] rows to every rank, counts and displacements say so);
+ *   s2v_shard_step_end     unpatchify of the gathered prediction, fp32 CFG + scheduler step on every rank redundantly: all ranks end with
+ *                          bit-identical latents (DPM: every rank is handed the same noise).
+ * s2v_denoise_step_ulysses is the whole sequence over the library's own communicator (world = p, rank = r), the exchanges being
+ * s2v_rccl_alltoallv stream-ordered on `stream`, without a host synchronisation. */
+#define S2V_SHARD_QKV_EXCHANGE 1   /* QKV rows -> heads: to rank g the rank's rows of head group g ([M_r][q_g | k_g | v_g]) */
+#define S2V_SHARD_O_EXCHANGE 2     /* attention output heads -> rows: to rank g its rows of this rank's head group ([M_g][D/p]) */
+#define S2V_SHARD_NOISE_GATHER 3   /* projected video rows [B][ceil(V/p)][Cout] to every rank */
+S2V_API int s2v_set_shard(s2v_ctx* ctx, int32_t world, int32_t rank);
+/* (T_r, R_r, V_r) of every rank: out[3 * p]; after s2v_set_geometry */
+S2V_API int s2v_shard_layout(s2v_ctx* ctx, int32_t* out);
+/* the send / recv buffers (context-owned device memory) and per-peer byte counts / displacements (arrays of p) of an exchange kind */
+S2V_API int s2v_shard_buffers(s2v_ctx* ctx, int32_t kind, void** send, void** recv, int64_t* send_counts, int64_t* send_displs,
+                              int64_t* recv_counts, int64_t* recv_displs);
+S2V_API int s2v_shard_step_begin(s2v_ctx* ctx, const void* latents, float timestep, const s2v_sched_coef* coef_host, int32_t* pending,
+                                 s2v_stream stream);
+S2V_API int s2v_shard_step_resume(s2v_ctx* ctx, int32_t* pending, s2v_stream stream);
+/* x0_hist / noise as s2v_denoise_step (required for the DPM kinds); s2v_last_noise_pred then holds the whole [B, F, C, H, W] prediction */
+S2V_API int s2v_shard_step_end(s2v_ctx* ctx, void* latents, float* x0_hist, const void* noise, s2v_stream stream);
+/* all-to-all-v of bytes over `comm` (grouped ncclSend / ncclRecv; the self part is a device copy), on `stream` */
+S2V_API int s2v_rccl_alltoallv(s2v_rccl_comm* comm, const void* send, const int64_t* send_counts, const int64_t* send_displs, void* recv,
+                               const int64_t* recv_counts, const int64_t* recv_displs, s2v_stream stream);
+/* comm: world and rank equal to the shard's */
+S2V_API int s2v_denoise_step_ulysses(s2v_ctx* ctx, s2v_rccl_comm* comm, void* latents, float timestep, const s2v_sched_coef* coef_host,
+                                     float* x0_hist, const void* noise, s2v_stream stream);
+
 /* ---- CogVideoX 3-D causal VAE decode ------------------------------------------------------------------------- */
 typedef struct s2v_vae s2v_vae;
 /* AutoencoderKLCogVideoX.__init__ (models/autoencoders/autoencoder_kl_cogvideox.py:1020-1052), decoder part */
