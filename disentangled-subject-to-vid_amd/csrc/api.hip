@@ -119,6 +119,13 @@ struct s2v_ctx {
     char *nsend = nullptr, *nrecv = nullptr;   // send [B][Vmax][Cout] / recv [sp][B][Vmax][Cout] of the noise all-gather
     char* proj_full = nullptr;                 // the gathered projection [B][gV][Cout]
     int *rmap = nullptr, *nmap = nullptr;      // recv row of the QKV exchange -> global row; recv row of the noise gather -> row of proj_full (-1: pad)
+    // fp8 engine (attn_mx_out): the O exchange carries the attention output as MX e4m3 -- Oh holds the bytes [B*gN][D/p], Os the block scales
+    // [D/(128p)][Os_rows] (K-tile major, mx_perm_row); omap[i] / omap[Mg + i] = where send row i's bytes (in 16-byte units) / its scale dwords
+    // (in dwords) sit in sbuf
+    bool o_mx = false;
+    unsigned char* Os = nullptr;
+    int64_t Os_rows = 0;
+    int* omap = nullptr;
     std::vector<int64_t> xcnt[3][4];           // per exchange kind: send counts, send displacements, recv counts, recv displacements (bytes)
     int sh_layer = 0, sh_pending = 0;          // the staged step: layer in flight, exchange the caller owes (S2V_SHARD_*)
 };
@@ -484,7 +491,11 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     S2V_REQUIRE(c, "null context");
     S2V_REQUIRE(world >= 1 && rank >= 0 && rank < world, "s2v_set_shard: need world >= 1 and 0 <= rank < world");
     S2V_REQUIRE(c->cfg.num_heads % world == 0, "s2v_set_shard: the world size must divide num_heads (attention runs num_heads / world heads per rank)");
-    S2V_REQUIRE(c->cfg.weight_format == 0, "s2v_set_shard: fp8 weight formats are not supported with a shard (MX buffers are sized and quantised per local row)");
+    // fp8: the attention output reaches the out-projection as MX e4m3 whose scales are dwords of four 32-column blocks = one 128-column K-tile =
+    // two heads; with an even head count per rank every dword of that image belongs to exactly one rank's head group
+    S2V_REQUIRE(c->cfg.weight_format == 0 || (c->D / world) % 128 == 0,
+                "s2v_set_shard: fp8 weight formats need an even number of heads per rank, (inner_dim / world) % 128 == 0 (the MX block-scale dwords of "
+                "the attention output hold two heads each)");
     S2V_REQUIRE(c->cfg.out_channels * 4 * c->esz % 16 == 0, "s2v_set_shard: the projected rows must be a multiple of 16 bytes (out_channels * 4 * element size)");
     if (c->shard && c->sp == world && c->sr == rank) return 0;
     S2V_CHECK_HIP(hipDeviceSynchronize());
@@ -495,6 +506,8 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     c->sh_pending = 0;
     return 0;
 }
+
+static bool attn_mx_out(const s2v_ctx* c);
 
 extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int32_t H, int32_t W) {
     S2V_REQUIRE(c, "null context");
@@ -520,8 +533,9 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     c->Vmax = (c->gV + c->sp - 1) / c->sp;
     c->sh_pending = 0;
     // weight_format 3 ("fp8-auto"): fp8 linears always, fp8 QK^T from S2V_FP8_QK_AUTO_TOKENS tokens on -- there the attention is > 80 % of the
-    // step and the whole-run drift of fp8-qk is the fp8 engine's (profiles/r05_whole_run_c5_10steps.txt: 8.69e-3 against 8.67e-3)
-    c->fp8_qk = c->cfg.weight_format == 2 || (c->cfg.weight_format == 3 && c->Ntok >= S2V_FP8_QK_AUTO_TOKENS);
+    // step and the whole-run drift of fp8-qk is the fp8 engine's (profiles/r05_whole_run_c5_10steps.txt: 8.69e-3 against 8.67e-3).  The count is the
+    // sequence the attention sees (gN): a shard decides as the single engine does
+    c->fp8_qk = c->cfg.weight_format == 2 || (c->cfg.weight_format == 3 && c->gN >= S2V_FP8_QK_AUTO_TOKENS);
     c->ntok_pad = (int)rup(c->gN, 64);
     c->M = (int64_t)B * c->Ntok;
     c->Mpad = rup(c->M, 256) + 256;
@@ -548,9 +562,9 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     const int64_t oaq = carve(c->fp8 ? c->Mpad * 4 * D : 0), oaqs = carve(c->fp8 ? c->Mpad * 4 : 0);
     // fp8: the FF1 epilogue leaves GELU(h) as MX e4m3 (bytes + one E8M0 scale per 32 columns), the FF2 reads it in place
     const int64_t ohq = carve(c->fp8 ? c->Mpad * 4 * D : 0), ohs = carve(c->fp8 ? c->Mpad * 4 * D / 32 : 0);
-    // fp8_qk: MX e4m3 images of q and k for attn_q4f (AttnArgs::q8 ... k8s)
-    const int64_t BH = (int64_t)B * c->cfg.num_heads;
-    const int64_t oq8 = carve(c->fp8_qk ? BH * c->Ntok * 64 : 0), oq8s = carve(c->fp8_qk ? BH * c->Ntok * 2 : 0);
+    // fp8_qk: MX e4m3 images of q and k for attn_q4f (AttnArgs::q8 ... k8s); a shard's attention runs its H/p heads over all gN tokens
+    const int64_t BH = (int64_t)B * (c->cfg.num_heads / c->sp);
+    const int64_t oq8 = carve(c->fp8_qk ? BH * c->gN * 64 : 0), oq8s = carve(c->fp8_qk ? BH * c->gN * 2 : 0);
     const int64_t ok8 = carve(c->fp8_qk ? BH * c->ntok_pad * 64 : 0), ok8s = carve(c->fp8_qk ? BH * c->ntok_pad * 4 : 0);
     // split-K partial tiles + arrival counters (linear(): only geometries whose FF2 has at most half as many 256 x 256 tiles as CUs).  A shard
     // never splits K: split-K changes the reduction order, and a rank's row count must not pick a different one than the single engine's
@@ -558,8 +572,15 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     const int64_t osk = carve((int64_t)c->sk_tiles * 262144), oskc = carve((int64_t)c->sk_tiles * 4);
     // shard: the head-sharded full-N buffers, the exchange buffers and the row maps
     const int64_t P = c->sp, Dp = D / P, Mg = (int64_t)B * c->gN, Mgpad = rup(Mg, 256) + 256;
+    // the O exchange: n rows of a head group are bf16 [n][D/p], or (fp8 engine) MX e4m3 [n][D/p] followed by the rows' scale dwords [n][D/(128p)],
+    // padded to 16 bytes so that every peer's chunk starts 16-byte aligned
+    c->o_mx = c->shard && attn_mx_out(c);
+    const bool omx = c->o_mx;
+    auto o_bytes = [&](int64_t n) { return omx ? n * Dp + rup(n * Dp / 32, 16) : n * Dp * E; };
     const int64_t oQh = carve(c->shard ? Mgpad * 3 * Dp * E : 0), oOh = carve(c->shard ? Mgpad * Dp * E : 0);
-    const int64_t osb = carve(c->shard ? std::max(c->M * 3 * D, Mg * Dp) * E : 0), orb = carve(c->shard ? std::max(Mg * 3 * Dp, c->M * D) * E : 0);
+    const int64_t osb = carve(c->shard ? std::max(c->M * 3 * D * E, o_bytes(Mg) + 16 * P) : 0);
+    const int64_t orb = carve(c->shard ? std::max(Mg * 3 * Dp * E, P * o_bytes(c->M)) : 0);
+    const int64_t oOs = carve(omx ? Dp / 128 * Mgpad * 4 : 0), oomap = carve(omx ? 2 * Mg * 4 : 0);
     const int64_t ons = carve(c->shard ? (int64_t)B * c->Vmax * Cout4 * E : 0), onr = carve(c->shard ? P * B * c->Vmax * Cout4 * E : 0);
     const int64_t opf = carve(c->shard ? (int64_t)B * c->gV * Cout4 * E : 0);
     const int64_t ormap = carve(c->shard ? Mg * 4 : 0), onmap = carve(c->shard ? P * B * c->Vmax * 4 : 0);
@@ -578,6 +599,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     if (c->shard) {
         c->QKVh = w + oQh; c->Oh = w + oOh; c->sbuf = w + osb; c->rbuf = w + orb; c->nsend = w + ons; c->nrecv = w + onr; c->proj_full = w + opf;
         c->rmap = (int*)(w + ormap); c->nmap = (int*)(w + onmap);
+        c->Os = omx ? (unsigned char*)(w + oOs) : nullptr; c->Os_rows = Mgpad; c->omap = omx ? (int*)(w + oomap) : nullptr;
         // rank g's rows of sample b, in g's local order [T_g | R_g | V_g], concatenated over g = the recv order of the QKV exchange (and the
         // send order of the O exchange); each maps to its row b * gN + (stream offset) in the global [text | ref | video] sequence
         std::vector<int> rmap, nmap;
@@ -600,17 +622,22 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
         S2V_CHECK_HIP(hipMemcpy(c->nmap, nmap.data(), nmap.size() * 4, hipMemcpyHostToDevice));
         for (auto& k : c->xcnt) for (auto& v : k) v.assign(P, 0);
         int64_t rq = 0, so = 0;
-        for (int g = 0; g < P; ++g) {
+        std::vector<int> omap(omx ? 2 * Mg : 0);
+        for (int g = 0, i = 0; g < P; ++g) {
             // QKV: to g my rows' head group g; from g its rows' head group sr
             c->xcnt[0][0][g] = c->M * 3 * Dp * E; c->xcnt[0][1][g] = g * c->M * 3 * Dp * E;
             c->xcnt[0][2][g] = B * ntok[g] * 3 * Dp * E; c->xcnt[0][3][g] = rq; rq += c->xcnt[0][2][g];
             // O: to g its rows of head group sr; from g my rows of head group g
-            c->xcnt[1][0][g] = B * ntok[g] * Dp * E; c->xcnt[1][1][g] = so; so += c->xcnt[1][0][g];
-            c->xcnt[1][2][g] = c->M * Dp * E; c->xcnt[1][3][g] = g * c->M * Dp * E;
+            const int64_t n = B * ntok[g];
+            if (omx)  // the chunk to g: the bytes of its n rows (send order = rmap's), then their scale dwords
+                for (int64_t j = 0; j < n; ++j, ++i) { omap[i] = (int)((so + j * Dp) / 16); omap[Mg + i] = (int)((so + n * Dp) / 4 + j * (Dp / 128)); }
+            c->xcnt[1][0][g] = o_bytes(n); c->xcnt[1][1][g] = so; so += c->xcnt[1][0][g];
+            c->xcnt[1][2][g] = o_bytes(c->M); c->xcnt[1][3][g] = g * o_bytes(c->M);
             // noise: the same [B][Vmax] rows to everyone
             c->xcnt[2][0][g] = (int64_t)B * c->Vmax * Cout4 * E; c->xcnt[2][1][g] = 0;
             c->xcnt[2][2][g] = c->xcnt[2][0][g]; c->xcnt[2][3][g] = g * c->xcnt[2][0][g];
         }
+        if (omx) S2V_CHECK_HIP(hipMemcpy(c->omap, omap.data(), omap.size() * 4, hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -1266,7 +1293,9 @@ static bool shard_fused_qk(const s2v_ctx* c) {
     return f;
 }
 
-// LN1 of layer l, the QKV projection with q/k LayerNorm + RoPE on the rank's rows, pack: chunk g of sbuf = [M][q_g | k_g | v_g]
+// LN1 of layer l, the QKV projection with q/k LayerNorm + RoPE on the rank's rows, pack: chunk g of sbuf = [M][q_g | k_g | v_g].  fp8 engine: the
+// projection is the single engine's fp8 GEMM on the LN1 pre-quantisation; with fp8 QK^T too the q/k LayerNorm + RoPE stay in the epilogue here (the
+// single engine folds them into its quantisation pass, qk_norm_quant_mx_k: the same bits) and q / k are quantised after the exchange
 static int shard_front(s2v_ctx* c, int l, hipStream_t st) {
     const LayerW& w = c->layers[l];
     const int D = c->D;
@@ -1286,7 +1315,9 @@ static int shard_front(s2v_ctx* c, int l, hipStream_t st) {
     }
     {
         ProfScope ps(c, PK_QKV, st);
-        S2V_TRY(linear(c, g, fused ? EPI_BIAS_QKNORM : EPI_BIAS, st));
+        const int epi = fused ? EPI_BIAS_QKNORM : EPI_BIAS;
+        if (c->fp8) S2V_TRY(linear_fp8(c, g, epi, w.q_qkv, w.s_qkv, st, prequant));
+        else S2V_TRY(linear(c, g, epi, st));
     }
     if (!fused) {  // V^T is made after the exchange, on the head-sharded buffer
         QkNormRopeArgs q{};
@@ -1306,10 +1337,14 @@ static int shard_front(s2v_ctx* c, int l, hipStream_t st) {
     return launch_shard_copy(a, st);
 }
 
-// unpack the QKV exchange into global token order, V^T, attention on the rank's heads, pack: chunk q of sbuf = rank q's rows of the output
+// unpack the QKV exchange into global token order, V^T, attention on the rank's heads, pack: chunk q of sbuf = rank q's rows of the output.  The
+// kernel and formats are run_attention's, chosen on the whole sequence gN; fp8 engine: the output leaves the kernel as MX e4m3 (Oh bytes, Os
+// scales) and is packed as such -- per peer its rows' bytes, then their scale dwords
 static int shard_attention(s2v_ctx* c, hipStream_t st) {
     const int64_t E = c->esz, Dp = c->D / c->sp, Mg = (int64_t)c->B * c->gN;
     const int H = c->cfg.num_heads / c->sp;
+    const bool mx = c->o_mx;
+    S2V_REQUIRE(mx == attn_mx_out(c), "shard_attention: the attention output format changed after s2v_set_geometry (set the geometry again)");
     {
         ShardCopyArgs a{};
         a.src = c->rbuf; a.dst = c->QKVh; a.rows = (int)Mg; a.width16 = (int)(3 * Dp * E / 16);
@@ -1317,7 +1352,7 @@ static int shard_attention(s2v_ctx* c, hipStream_t st) {
         ProfScope ps(c, PK_SHARD, st);
         S2V_TRY(launch_shard_copy(a, st));
     }
-    const bool p16 = c->attn_p16 && c->mfma && attn_runs_q4(c->gN, false);
+    const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(c->gN, mx));
     if (c->mfma || c->h16) {
         ProfScope ps(c, PK_QKNORM, st);
         S2V_TRY(launch_v_transpose(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->VT, c->ntok_pad, st, p16));
@@ -1331,7 +1366,18 @@ static int shard_attention(s2v_ctx* c, hipStream_t st) {
     a.valu_only = c->cfg.force_simple;
     a.stagger = c->attn_stagger;
     a.order = c->attn_order;
-    {
+    if (mx) { a.mx_q = (unsigned char*)c->Oh; a.mx_s = c->Os; a.mx_rows = (int)c->Os_rows; }
+    if (c->fp8_qk) {  // q (times scale * log2 e) and k of the rank's heads as MX e4m3, QK^T on the scaled fp8 MFMA
+        {
+            ProfScope ps(c, PK_QKNORM, st);
+            S2V_TRY(launch_qk_quant_mx(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->ntok_pad, a.scale * 1.4426950408889634f, c->q8, c->q8s, c->k8,
+                                       c->k8s, st));
+        }
+        a.q8 = c->q8; a.q8s = c->q8s; a.k8 = c->k8; a.k8s = c->k8s;
+        ProfScope ps(c, PK_ATTN, st);
+        a.clk = c->clk_cur;
+        S2V_TRY(launch_attn_q4f(a, true, st));
+    } else {
         ProfScope ps(c, PK_ATTN, st);
         a.clk = c->clk_cur;
         if (c->mfma) S2V_TRY(launch_attn_bf16(a, st));
@@ -1341,15 +1387,38 @@ static int shard_attention(s2v_ctx* c, hipStream_t st) {
     ShardCopyArgs o{};
     o.src = c->Oh; o.dst = c->sbuf; o.rows = (int)Mg; o.width16 = (int)(Dp * E / 16);
     o.src_ld = o.dst_ld = Dp * E; o.src_map = c->rmap; o.nseg = 1; o.nseg_inner = 1;
+    if (mx) { o.width16 = (int)(Dp / 16); o.src_ld = Dp; o.dst_ld = 16; o.dst_map = c->omap; }  // omap: the byte offset / 16 of each send row
     ProfScope ps(c, PK_SHARD, st);
-    return launch_shard_copy(o, st);
+    S2V_TRY(launch_shard_copy(o, st));
+    if (!mx) return 0;
+    ShardScaleArgs s{};  // scale dwords (kt, global row rmap[i]) of Os -> sbuf dword omap[Mg + i] + kt
+    s.src = (const unsigned*)c->Os; s.dst = (unsigned*)c->sbuf; s.rows = (int)Mg; s.nkt = (int)(Dp / 128); s.nseg = 1;
+    s.src_map = c->rmap; s.dst_map = c->omap + Mg;
+    s.src_row = 1; s.src_kt = c->Os_rows; s.src_perm = 1;
+    s.dst_row = 1; s.dst_kt = 1;
+    return launch_shard_scales(s, st);
 }
 
 // unpack the O exchange (head group g -> columns g*D/p of Xn), out-projection, LN2, FF; then the next layer's front or the tail
+// fp8 engine: the MX image goes where run_attention's kernel leaves it for the out-projection -- bytes to aq [M][D] at columns g*D/p, scale dwords to
+// hs at K-tiles g*D/(128p) ..., rows mx_perm_row(local row) of mx_rows = Mpad
 static int shard_back(s2v_ctx* c, int l, hipStream_t st, int* pending) {
     const int D = c->D;
     const int64_t E = c->esz, Dp = D / c->sp;
-    {
+    if (c->o_mx) {
+        const int64_t nkt = Dp / 128, chunk = c->M * Dp + rup(c->M * nkt * 4, 16);  // one peer's chunk: [M][D/p] bytes, [M][nkt] scale dwords, pad
+        ShardCopyArgs a{};
+        a.src = c->rbuf; a.dst = c->aq; a.rows = (int)c->M; a.width16 = (int)(Dp / 16);
+        a.src_ld = Dp; a.dst_ld = D; a.nseg = c->sp; a.nseg_inner = 1;
+        a.src_seg_outer = chunk; a.dst_seg_outer = Dp;
+        ShardScaleArgs s{};
+        s.src = (const unsigned*)(c->rbuf + c->M * Dp); s.dst = (unsigned*)c->hs; s.rows = (int)c->M; s.nkt = (int)nkt; s.nseg = c->sp;
+        s.src_row = nkt; s.src_kt = 1; s.src_seg = chunk / 4;
+        s.dst_row = 1; s.dst_kt = c->Mpad; s.dst_seg = nkt * c->Mpad; s.dst_perm = 1;
+        ProfScope ps(c, PK_SHARD, st);
+        S2V_TRY(launch_shard_copy(a, st));
+        S2V_TRY(launch_shard_scales(s, st));
+    } else {
         ShardCopyArgs a{};
         a.src = c->rbuf; a.dst = c->Xn; a.rows = (int)c->M; a.width16 = (int)(Dp * E / 16);
         a.src_ld = Dp * E; a.dst_ld = D * E; a.nseg = c->sp; a.nseg_inner = 1;

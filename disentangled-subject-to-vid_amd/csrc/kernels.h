@@ -241,6 +241,18 @@ struct ShardCopyArgs {
     int64_t src_seg_outer, src_seg_inner, dst_seg_outer, dst_seg_inner;
 };
 int launch_shard_copy(const ShardCopyArgs& a, hipStream_t st);
+// The O exchange of the fp8 engine carries MX e4m3 (AttnArgs::mx_q / mx_s): the bytes are whole 16-byte pieces (launch_shard_copy), the E8M0 block
+// scales are dwords of a K-tile-major array (GemmArgs::mx_a_s: dword (kt, m) at kt * mx_rows + mx_perm_row(m)).  For every segment k < nseg, row
+// i < rows and K-tile kt < nkt, one dword moves from src + k * src_seg + kt * src_kt + row(smap(i)) * src_row to the same place under dst's strides,
+// row(m) = mx_perm_row(m) on a side with perm set, m otherwise; smap / dmap as for launch_shard_copy.  Offsets and strides in dwords.
+struct ShardScaleArgs {
+    const unsigned* src; unsigned* dst;
+    int rows, nkt, nseg;
+    const int* src_map; const int* dst_map;
+    int64_t src_row, src_kt, src_seg, dst_row, dst_kt, dst_seg;
+    int src_perm, dst_perm;
+};
+int launch_shard_scales(const ShardScaleArgs& a, hipStream_t st);
 // dst[r][:] = rnd(src[r][:] (+ add[r][:]))
 int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void* dst, int ldd, int rows, int D,
                      int dtype, hipStream_t st);

@@ -1,6 +1,6 @@
 // Byte-moving kernels of Ulysses sequence parallelism: the packs and unpacks around the two
 // all-to-alls of every block and the compaction of the gathered noise prediction.  No arithmetic: every kernel copies 16-byte pieces of
-// rows, so a sharded step moves exactly the bits the single engine computes.
+// rows (or, for the MX block scales of the fp8 engine's O exchange, dwords), so a sharded step moves exactly the bits the single engine computes.
 #define S2V_HOST
 #include "common.h"
 #include "kernels.h"
@@ -39,6 +39,34 @@ __global__ __launch_bounds__(kThreads) void shard_copy_k(const ShardCopyArgs a) 
         if (doff[j] >= 0) *(u32x4*)(dst + doff[j]) = v[j];
 }
 
+// dword (segment k, row i, K-tile kt) of the MX block scales, kt fastest: the compact side of a pack / unpack is then read or written in order
+__global__ __launch_bounds__(kThreads) void shard_scales_k(const ShardScaleArgs a) {
+    const int k = blockIdx.y;
+    const unsigned* src = a.src + k * a.src_seg;
+    unsigned* dst = a.dst + k * a.dst_seg;
+    const int64_t total = (int64_t)a.rows * a.nkt;
+    const int64_t base = (int64_t)blockIdx.x * (kThreads * kUnroll) + threadIdx.x;
+    unsigned v[kUnroll];
+    int64_t doff[kUnroll];
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j) {
+        const int64_t e = base + (int64_t)j * kThreads;
+        doff[j] = -1;
+        if (e < total) {
+            const int i = (int)(e / a.nkt), kt = (int)(e - (int64_t)i * a.nkt);
+            const int si = a.src_map ? a.src_map[i] : i;
+            const int di = a.dst_map ? a.dst_map[i] : i;
+            if (si >= 0 && di >= 0) {
+                v[j] = src[kt * a.src_kt + (a.src_perm ? mx_perm_row(si) : (int64_t)si) * a.src_row];
+                doff[j] = kt * a.dst_kt + (a.dst_perm ? mx_perm_row(di) : (int64_t)di) * a.dst_row;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j)
+        if (doff[j] >= 0) dst[doff[j]] = v[j];
+}
+
 }  // namespace
 
 int launch_shard_copy(const ShardCopyArgs& a, hipStream_t st) {
@@ -52,6 +80,18 @@ int launch_shard_copy(const ShardCopyArgs& a, hipStream_t st) {
     S2V_REQUIRE((total + per - 1) / per < (1ll << 31) && a.nseg < 65536, "launch_shard_copy: grid too large");
     dim3 grid((unsigned)((total + per - 1) / per), (unsigned)a.nseg);
     hipLaunchKernelGGL(shard_copy_k, grid, dim3(kThreads), 0, st, a);
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_shard_scales(const ShardScaleArgs& a, hipStream_t st) {
+    S2V_REQUIRE(a.src && a.dst && a.rows >= 0 && a.nkt >= 1 && a.nseg >= 1, "launch_shard_scales: bad shape");
+    const int64_t total = (int64_t)a.rows * a.nkt;
+    if (total == 0) return 0;
+    const int64_t per = (int64_t)kThreads * kUnroll;
+    S2V_REQUIRE((total + per - 1) / per < (1ll << 31) && a.nseg < 65536, "launch_shard_scales: grid too large");
+    dim3 grid((unsigned)((total + per - 1) / per), (unsigned)a.nseg);
+    hipLaunchKernelGGL(shard_scales_k, grid, dim3(kThreads), 0, st, a);
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

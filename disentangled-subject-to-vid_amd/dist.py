@@ -395,6 +395,31 @@ def shard_row_map(B, T, R, V, world):
     return rows
 
 
+def shard_exchange_bytes(B, T, R, V, world, rank, inner_dim, esz, out_channels, mx=False):
+    """rank's per-peer byte counts of every exchange of a step, as s2v_shard_buffers reports them: {kind: (send_counts, send_displs, recv_counts,
+    recv_displs)} for kind 1 (QKV rows -> heads), 2 (attention output heads -> rows) and 3 (the noise all-gather), lists of `world` entries.
+    esz: bytes per element of the model dtype; out_channels: the transformer's (the projected rows are out_channels * 4 wide).
+    mx: the fp8 weight formats, whose O exchange carries the attention output as MX e4m3 -- n rows of a head group are their bytes [n][D/p] followed
+    by their E8M0 block-scale dwords [n][D/(128p)], padded to 16 bytes -- instead of bf16 [n][D/p]."""
+    Dp = inner_dim // world
+    ntok = [sum(n) for n in shard_layout(T, R, V, world)]
+    M = B * ntok[rank]
+    vmax = -(-V // world)
+
+    def o_bytes(n):
+        return n * Dp + -(-n * Dp // 32 // 16) * 16 if mx else n * Dp * esz
+
+    def displs(counts):
+        return [sum(counts[:g]) for g in range(len(counts))]
+
+    qkv = [M * 3 * Dp * esz] * world, [B * n * 3 * Dp * esz for n in ntok]
+    o = [o_bytes(B * n) for n in ntok], [o_bytes(M)] * world
+    noise = [B * vmax * out_channels * 4 * esz] * world
+    return {1: (qkv[0], displs(qkv[0]), qkv[1], displs(qkv[1])),
+            2: (o[0], displs(o[0]), o[1], displs(o[1])),
+            3: (noise, [0] * world, noise, displs(noise))}
+
+
 def _check_contiguous(counts, displs):
     off = 0
     for n, d in zip(counts, displs):

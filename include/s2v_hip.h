@@ -240,7 +240,10 @@ S2V_API int s2v_denoise_step_cfg_parallel(s2v_ctx* ctx, s2v_rccl_comm* comm, int
  *   reference (n = R = H/2 * W/2) and the video (n = V = F * R) tokens of each sample: its mini-sequence [T_r | R_r | V_r].  Every row-wise
  *   kernel (LayerNorm-modulate, the linears and their epilogues, q/k-norm + RoPE, the tail) runs on those rows; the attention runs on heads
  *   [r*H/p, (r+1)*H/p) of all N = T + R + V tokens in global token order.  Shards are ragged (19 126 tokens at p = 4: text shards 56/57/56/57).
- *   Requirements: p divides num_heads; weight_format 0 (no fp8); every rank holds >= 1 video row.  p = 1 computes what s2v_denoise_step does.
+ *   Requirements: p divides num_heads; the fp8 weight formats (1, 2, 3) need an even number of heads per rank, (inner_dim / p) % 128 == 0 (their
+ *   attention output is MX e4m3 whose block-scale dwords span one 128-column K-tile = two heads); every rank holds >= 1 video row.  p = 1 computes
+ *   what s2v_denoise_step does.  fp8: the linears quantise per row as the single engine does; weight_format 3 decides fp8 QK^T on the whole
+ *   sequence N, not on the rank's rows, so every rank takes the single engine's decision.
  *   A shard context runs ONLY the staged step below (s2v_denoise_step, s2v_transformer_forward, the seams and CFG-parallel are refused), eagerly:
  *   hipGraph capture is not supported for shard contexts.  Bit-identity with the single engine: split-K is never chosen on a shard (a rank's
  *   row count must not pick another reduction order); geometries on which the single engine splits K (few row tiles and K >= 2048) differ.
@@ -258,7 +261,9 @@ S2V_API int s2v_denoise_step_cfg_parallel(s2v_ctx* ctx, s2v_rccl_comm* comm, int
  * s2v_denoise_step_ulysses is the whole sequence over the library's own communicator (world = p, rank = r), the exchanges being
  * s2v_rccl_alltoallv stream-ordered on `stream`, without a host synchronisation. */
 #define S2V_SHARD_QKV_EXCHANGE 1   /* QKV rows -> heads: to rank g the rank's rows of head group g ([M_r][q_g | k_g | v_g]) */
-#define S2V_SHARD_O_EXCHANGE 2     /* attention output heads -> rows: to rank g its rows of this rank's head group ([M_g][D/p]) */
+#define S2V_SHARD_O_EXCHANGE 2     /* attention output heads -> rows: to rank g its rows of this rank's head group: bf16 [M_g][D/p]; fp8 weight formats:
+                                      the MX e4m3 image the out-projection reads -- bytes [M_g][D/p], then the E8M0 scales [M_g][D/(128p)] dwords
+                                      (four 32-column blocks each), padded to 16 bytes: D/p + D/(32p) bytes per row */
 #define S2V_SHARD_NOISE_GATHER 3   /* projected video rows [B][ceil(V/p)][Cout] to every rank */
 S2V_API int s2v_set_shard(s2v_ctx* ctx, int32_t world, int32_t rank);
 /* (T_r, R_r, V_r) of every rank: out[3 * p]; after s2v_set_geometry */

@@ -4,12 +4,14 @@ Builds the single engine and p shard contexts (s2v_set_shard) of the full model 
 (dist.UlyssesLocal: the exchanges are device copies) and times with HIP events on the launch stream:
   * per rank: compute ms, excluding the exchanges (events around each rank's begin / resume / end segments; the packs and unpacks are inside);
   * pack / unpack ms and their effective GB/s (bytes read + written; s2v_profile_read class 8);
-  * bytes per all-to-all per rank and per step, and a link-bound exchange time at an ASSUMED, UNMEASURED 153 GB/s per xGMI link (bench.py's
-    constant) -- each rank sends (p - 1) / p of its chunks, one link per peer;
+  * bytes per all-to-all per rank and per step (dist.shard_exchange_bytes, what s2v_shard_buffers reports; the fp8 weight formats carry the
+    attention output as MX e4m3, set against the bf16 exchange of the same geometry), and a link-bound exchange time at an ASSUMED, UNMEASURED
+    153 GB/s per xGMI link (bench.py's constant) -- each rank sends every chunk but its own, one link per peer;
   * the single engine's B = 2 step in the same process, and the per-kernel-class breakdown of both.
 The p-GPU step time printed is a PROJECTION: max-over-ranks compute + the link-bound exchange time; no multi-GPU node has run it.
 
 python tools/ulysses_projection.py --workload cogvideox-5b-49x480x720 --p 2 4
+python tools/ulysses_projection.py --workload cogvideox-5b-fp8-49x720x1280 --p 2 4        (BASELINE configs[4]; -fp8auto-: the fp8-auto preset)
 """
 import argparse
 import ctypes
@@ -23,7 +25,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 s2v = importlib.import_module("disentangled-subject-to-vid_amd")
 DEV = "cuda:0"
-WORKLOADS = {"cogvideox-5b-49x480x720": (s2v.cogvideox_5b, 226, 13, 60, 90)}
+WORKLOADS = {"cogvideox-5b-49x480x720": (s2v.cogvideox_5b, 226, 13, 60, 90),
+             # BASELINE configs[4] (49 x 720 x 1280, N = 50 626): fp8 linears, and the fp8-auto preset (+ fp8 QK^T at that length, fp16 P)
+             "cogvideox-5b-fp8-49x720x1280": (s2v.config.cogvideox_5b_fp8, 226, 13, 90, 160),
+             "cogvideox-5b-fp8auto-49x720x1280": (s2v.config.cogvideox_5b_fp8_auto, 226, 13, 90, 160)}
+# max-over-ranks compute against the single-engine step: the C3 targets, and for configs[4] an ESTIMATE (the C3 figure with attention a larger share)
+TARGETS = {"cogvideox-5b-49x480x720": {2: "0.53", 4: "0.28"}, "cogvideox-5b-fp8-49x720x1280": {4: "<= 0.29, an estimate"},
+           "cogvideox-5b-fp8auto-49x720x1280": {4: "<= 0.29, an estimate"}}
 CLASSES = ["qkv", "attn", "out", "ff1", "ff2", "lnmod", "qknorm/vt", "other", "pack/unpack"]
 LINK_GBPS = 153.0
 
@@ -59,6 +67,8 @@ def main():
     t = sch.timesteps[10]
     coef = sch.coef(t, dt, 6.0)
     E, D, N = 2, cfg.inner_dim, T + (H // 2) * (W // 2) * (F + 1)
+    R, V = (H // 2) * (W // 2), F * (H // 2) * (W // 2)
+    mx = cfg.weight_format is not None  # the fp8 formats: O exchange as MX e4m3 (D/p + D/(32p) bytes per row)
 
     def build(shard=None, src=None):
         m = s2v.HipCogVideoXTransformer3DModel(cfg, dt, DEV)
@@ -75,8 +85,11 @@ def main():
         e.set_conditioning(text, ref)
         return e
 
-    print(f"workload {a.workload}: {cfg.num_layers} layers, {cfg.num_attention_heads} heads, D = {D}, N = {N} tokens per sample, B = 2, bf16, DDIM step")
+    fmt = f"weight_format {cfg.weight_format!r}, attn_p_format {cfg.attn_p_format!r}" if mx else "bf16"
+    print(f"workload {a.workload}: {cfg.num_layers} layers, {cfg.num_attention_heads} heads, D = {D}, N = {N} tokens per sample, B = 2, {fmt}, DDIM step")
     e1 = build()
+    if mx:
+        print(f"  fp8 QK^T active on the single engine: {e1.fp8_qk_active}")
     lat = lat0.clone()
     e1.denoise_step(lat, float(t), coef)
     torch.cuda.synchronize()
@@ -142,32 +155,41 @@ def main():
             s2v._lib.check(s2v.lib().s2v_profile_read(engs[r]._h, ms, cnt, 9))
             s2v._lib.check(s2v.lib().s2v_profile_enable(engs[r]._h, 0))
             profs.append(list(ms))
-        # bytes: per rank and per block, packs / unpacks move (read + write) these; the all-to-all sends (p - 1) / p of each chunk set
+        # bytes: per rank and per block, packs / unpacks move (read + write) these; the all-to-all sends every chunk but the rank's own
         L = cfg.num_layers
         print(f"\np = {p}: shard layout (T_r, R_r, V_r) = {lay}; lockstep latents bitwise equal to the single engine: {same}")
+        if mx:
+            print(f"  fp8 QK^T active on the shards: {[e.fp8_qk_active for e in engs]}")
         worst = max(range(p), key=lambda r: best[r])
+
+        def sent(x, kind, r):  # bytes rank r puts on links: every chunk but its own
+            return sum(x[kind][0]) - x[kind][0][r]
+
+        per_step = [0.0] * p
         for r in range(p):
             Tr, Rr, Vr = lay[r]
             Mr = 2 * (Tr + Rr + Vr)
+            ob = 1 + 1 / 32 if mx else E            # bytes per element of the attention output as exchanged (MX: e4m3 + one scale byte per 32)
             qkv_b = Mr * 3 * D * E                  # local QKV of the rank
             qkvh_b = 2 * N * 3 * (D // p) * E       # head-sharded QKV of all rows
-            o_b = 2 * N * (D // p) * E              # head-sharded attention output
-            xn_b = Mr * D * E
+            o_b = 2 * N * (D // p) * ob             # head-sharded attention output
+            xn_b = Mr * D * ob
             moved = 2 * L * (qkv_b + qkvh_b + o_b + xn_b)
             pk = profs[r][8]
-            sent_qkv = qkv_b * (p - 1) / p
-            sent_o = o_b * (p - 1) / p
+            xb = s2v.dist.shard_exchange_bytes(2, T, R, V, p, r, D, E, cfg.out_channels, mx=mx)
+            x16 = s2v.dist.shard_exchange_bytes(2, T, R, V, p, r, D, E, cfg.out_channels, mx=False)
+            sent_qkv, sent_o, sent_n = sent(xb, 1, r), sent(xb, 2, r), xb[3][0][0] * (p - 1)
+            per_step[r] = L * (sent_qkv + sent_o) + sent_n
             print(f"  rank {r}: compute {best[r]:.1f} ms (excl. exchanges) = {best[r] / single:.3f} x single; pack/unpack {pk:.2f} ms for "
                   f"{moved / 1e9:.2f} GB moved = {moved / pk / 1e6 if pk > 0 else 0:.0f} GB/s")
-            print(f"          all-to-all bytes sent per block: QKV {sent_qkv / 1e6:.1f} MB, O {sent_o / 1e6:.1f} MB; per step "
-                  f"{L * (sent_qkv + sent_o) / 1e9:.2f} GB (+ noise gather {(p - 1) * 2 * (-(-(F * (H // 2) * (W // 2)) // p)) * cfg.out_channels * 4 * E / 1e6:.1f} MB)")
+            print(f"          all-to-all bytes sent per block: QKV {sent_qkv / 1e6:.1f} MB, O {sent_o / 1e6:.1f} MB"
+                  + (f" (bf16 O at this geometry: {sent(x16, 2, r) / 1e6:.1f} MB)" if mx else "")
+                  + f"; per step {per_step[r] / 1e9:.2f} GB" + (f" (bf16 exchange: {(L * (sent(x16, 1, r) + sent(x16, 2, r)) + sent_n) / 1e9:.2f} GB)" if mx else "")
+                  + f" incl. the noise gather {sent_n / 1e6:.1f} MB")
             print("          by class (ms): " + ", ".join(f"{c} {m:.1f}" for c, m in zip(CLASSES, profs[r])))
-        Tr, Rr, Vr = lay[worst]
-        Mr = 2 * (Tr + Rr + Vr)
-        per_step = cfg.num_layers * (Mr * 3 * D * E + 2 * N * (D // p) * E) * (p - 1) / p
-        link_ms = per_step / ((p - 1) * LINK_GBPS * 1e9) * 1e3
+        link_ms = max(per_step) / ((p - 1) * LINK_GBPS * 1e9) * 1e3
         print(f"  max-over-ranks compute {best[worst]:.1f} ms = {best[worst] / single:.3f} x the single-engine step "
-              f"(target {'0.28' if p == 4 else '0.53' if p == 2 else '-'})")
+              f"(target {TARGETS.get(a.workload, {}).get(p, '-')})")
         print(f"  link-bound exchange at an ASSUMED, UNMEASURED {LINK_GBPS:.0f} GB/s per xGMI link ((p - 1) links per rank): {link_ms:.1f} ms per step")
         print(f"  PROJECTION (not measured on {p} GPUs): p = {p} step ~ {best[worst] + link_ms:.1f} ms against {single:.1f} ms "
               f"({single / (best[worst] + link_ms):.2f}x) if the exchanges do not overlap compute")
