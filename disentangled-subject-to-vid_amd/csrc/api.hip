@@ -712,36 +712,14 @@ static int linear(s2v_ctx* c, const GemmArgs& g0, int epi, hipStream_t st) {
     g.w_rows_padded = (int)(rup(g.N, 256));  // every weight of the arena is carved with its rows padded to 256
     if ((c->mfma || c->h16) && g.K % 64 == 0 && g.lda % 8 == 0 && g.ldw % 8 == 0) {
         g.f16 = c->h16 ? 1 : 0;  // the fp16 model dtype takes the same dispatch on the kernels' fp16 instantiations (launch_gemm_bf16)
-        // Tile-count quantisation: the 256 x 256 kernel runs one tile per CU, so a grid that spills a few tiles into an extra
-        // round pays a whole round (C3: 150 x 12 = 1800 tiles = 7.03 rounds of 256 CUs for the out-proj / FF2).  When the
-        // last row tile is partial and dropping it saves a round, the full row tiles run on the big kernel and the row tail
-        // (108 rows at C3) on the 128 x 128 kernel.
-        const int64_t tn = (g.N + 255) / 256, tm = (g.M + 255) / 256, ncu = c->num_cus;
-        if (c->sk_tiles > 0 && g.splitk == 0) {
-            const int S = gemm_choose_splitk(tm * tn, g.K, ncu);
-            if (S > 1 && (int64_t)S * tm * tn <= c->sk_tiles) { g.splitk = S; g.sk_ws = c->sk_ws; g.sk_cnt = c->sk_cnt; }
-        }
-        // Few tiles (C1: M = 2500): half a round of 256 x 256 tiles or less and no split K (the out-projection: 80 tiles of 30 K-tiles)
-        // -> 256 x 128 tiles put twice the workgroups on the part: 36 us against 59 (tools/microbench.py gemm_c1, profiles/r03_c1_*).
-        // Measured and dropped: peeling the sparse second round of the FF1 (300 tiles on 256 CUs) off as 128 x 128 tiles -- 62 + 35 us
-        // against 100 for the two rounds on the same stream, slower (117) as a fork on the side stream.
-        if (g.splitk == 0 && epi != EPI_BIAS_QKNORM && g.tile == 0 && tm * tn * 2 <= ncu) g.tile = 1;
-        const int rem = (int)(g.M % 256);
-        bool split_tail = rem > 0 && tm > 1 && g.N >= 256 && (tm * tn + ncu - 1) / ncu > ((tm - 1) * tn + ncu - 1) / ncu;
-        // Round 6 (the B = 1 geometry of a CFG-parallel rank: M = 19 126): the persistent kernel with the trickled epilogue (gemm_g4t) takes whole
-        // 256-row tiles only, so a QKV projection whose row tail does NOT cost a round (75 x 36 = 2700 tiles = 10.5 rounds either way) used to run on
-        // gemm_g4 with the exposed q/k-norm epilogue: 0.90 ms where half the B = 2 launch is 0.80.  Split the tail off whenever that lets the whole
-        // tiles take gemm_g4t; the tail's 128 x 128 kernel returns the same bits (the B = 2 launch has mixed the two since round 5).
-        if (!split_tail && rem > 0 && tm > 1 && g.N >= 256 && c->mfma && g.splitk == 0 && g.tile == 0) {
-            GemmArgs gw = g;
-            gw.M = (int)((tm - 1) * 256);
-            split_tail = gemm_g4t_ok(gw, epi, (int)ncu);
-        }
-        if (split_tail) {
+        const GemmPlan p = gemm_plan(g, epi, c->num_cus, c->sk_tiles);  // split K, tile, row tail: gemm.hip
+        g.tile = p.tile;
+        if (p.splitk > 1) { g.splitk = p.splitk; g.sk_ws = c->sk_ws; g.sk_cnt = c->sk_cnt; }
+        if (p.tail != GEMM_NONE) {
             GemmArgs gm = g, gt = g;
             gt.clk = nullptr;  // the row tail runs beside the main launch on the side stream: one stamp per profiled launch
-            gm.M = (int)((tm - 1) * 256);
-            gt.m_begin = gm.M;
+            gm.M = p.m_main;
+            gt.m_begin = p.m_main;
             // fork: the tail runs on the side stream beside the main launch (event fork/join, valid under stream capture)
             S2V_CHECK_HIP(hipEventRecord(c->ev_fork, st));
             S2V_CHECK_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
@@ -763,15 +741,12 @@ static int linear(s2v_ctx* c, const GemmArgs& g0, int epi, hipStream_t st) {
 static int linear_fp8(s2v_ctx* c, const GemmArgs& g0, int epi, const char* wq, const float* wscale, hipStream_t st, bool prequant = false) {
     GemmArgs g = g0;
     g.clk = c->clk_cur;
-    if (g.mx_a_s) {
-        g.lda = g.K; g.W = wq; g.ldw = g.K; g.a_scale = nullptr; g.w_scale = wscale;
-        g.a_rows_padded = (int)rup(g.M, 256);
-        g.w_rows_padded = (int)rup(g.N, 256);
-        return launch_gemm_fp8(g, epi, st);
+    g.a_scale = nullptr;
+    if (!g.mx_a_s) {
+        if (!prequant) S2V_TRY(launch_quant_rows_fp8(g.A, g.lda, g.M, g.K, c->aq, c->aq_scale, st));
+        g.A = c->aq; g.a_scale = c->aq_scale;
     }
-    if (!prequant) S2V_TRY(launch_quant_rows_fp8(g.A, g.lda, g.M, g.K, c->aq, c->aq_scale, st));
-    g.A = c->aq; g.lda = g.K; g.W = wq; g.ldw = g.K;
-    g.a_scale = c->aq_scale; g.w_scale = wscale;
+    g.lda = g.K; g.W = wq; g.ldw = g.K; g.w_scale = wscale;
     g.a_rows_padded = (int)rup(g.M, 256);
     g.w_rows_padded = (int)rup(g.N, 256);
     return launch_gemm_fp8(g, epi, st);
@@ -1628,10 +1603,8 @@ extern "C" int s2v_op_linear(const void* A, const void* W, const void* bias, voi
     }
     if (impl == 2) {  // the engine's split-K form of a few-tile GEMM (linear()), with a workspace of its own: synchronous
         S2V_REQUIRE(dtype == S2V_DTYPE_BF16 && M % 256 == 0 && N % 256 == 0, "s2v_op_linear: impl 2 is bf16 with M and N multiples of 256");
-        int dev = 0, ncu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
         const int64_t tiles = (int64_t)(M / 256) * (N / 256);
-        const int S = gemm_choose_splitk(tiles, K, ncu);
+        const int S = gemm_choose_splitk(tiles, K, device_cus());
         S2V_REQUIRE(S > 1, "s2v_op_linear: impl 2: this shape does not split (tiles * 2 <= CUs, K / S a multiple of 128 and >= 1024)");
         char* ws = nullptr;
         const size_t pb = (size_t)S * tiles * 262144;

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "gemm_epi.h"
+#include "epi_dispatch.h"
 
 // ---------------------------------------------------------------------------------------------------
 // bf16 MFMA kernel
@@ -1134,18 +1135,14 @@ static int launch_q4_t(const GemmArgs& a, hipStream_t st) {
             default: break;
         }
     S2V_TRY(ensure_lds_attr(fn, 163840));
-    int dev = 0, ncu = 256;
-    S2V_CHECK_HIP(hipGetDevice(&dev));
-    S2V_CHECK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    const int grid = std::min((ncu / 8) * 8, ((tiles_m * tiles_n + 7) / 8) * 8);
+    const int grid = std::min((device_cus() / 8) * 8, ((tiles_m * tiles_n + 7) / 8) * 8);
     void* args[] = {(void*)&a, (void*)&tiles_m, (void*)&tiles_n};
     S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(grid), dim3(256), args, 163840, st));
     return 0;
 }
 #endif
 
-// compute units of the current device, queried once per device (launch-path heuristics count tile ROUNDS in these)
-static int device_cus() {
+int device_cus() {
     static int cus[64] = {0};
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
@@ -1197,6 +1194,15 @@ static int launch_stag_t(const GemmArgs& a, hipStream_t st) {
     return 0;
 }
 
+// rows [m_begin, M): the whole GEMM, or the row tail of a split one
+template <int EPI, typename T16 = bf16_t>
+static int launch_128_t(const GemmArgs& a, hipStream_t st) {
+    const int tiles_m = (a.M - a.m_begin + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
+    hipLaunchKernelGGL((gemm_bf16_128<EPI, T16>), dim3(tiles_m * tiles_n), dim3(256), 4 * TILE_BYTES, st, a, tiles_m, tiles_n);
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // 7 = 256x256x64 eight-wave ping-pong (the product schedule), 2 = staggered 256x128 ring, 0 = 128x128 double buffer; 7 falls back
 // to 2 (then 0) when the shape does not fit its tiles.  libs2v_hip_diag.so (S2V_DIAG) can also select 5 = the 256x256 eight-wave
 // lock-step ring and the compile-time ablations of gemm_bf16_pp64 (tools/ablate_gemm.py, tools/stall_pp64.py).
@@ -1206,6 +1212,30 @@ int g_gemm_impl = 9;  // 9: gemm_g4 where it qualifies, gemm_bf16_pp64 otherwise
 int g_gemm_g4t = 1;   // the persistent trickled-epilogue form of gemm_g4 where it qualifies (s2v_set_gemm_g4t: A/B switch of the diagnostics build)
 extern "C" __attribute__((visibility("default"))) int s2v_set_gemm_g4t(int on) { g_gemm_g4t = on; return 0; }
 extern "C" __attribute__((visibility("default"))) int s2v_set_gemm_impl(int impl) { g_gemm_impl = impl & 0xff; g_gemm_ablate = impl >> 8; return 0; }
+// gemm_plan of one GEMM as the engine issues it, without a device (tests/test_gemm_dispatch_cpu.py): M x N x K with the operands of linear()
+// (rows padded to 256, a bias, the gate + residual of the out-projection / FF2, the q/k-norm parameters).  flags: 1 fp16 operands, 2 a rotary
+// table (EPI_BIAS_QKNORM), 4 e4m3 operands (launch_gemm_fp8) with per-token scales of A, 8 (with 4) an MX image as A instead, 16 a VAE
+// convolution (kt = 3 over cin = K / 27 channels, launch_gemm_bf16 directly).  out = {splitk, tile, m_main, main, tail} (GemmPlan)
+extern "C" __attribute__((visibility("default"))) int s2v_diag_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t flags, int32_t ncu,
+                                                                          int64_t sk_tiles, int32_t* out) {
+    S2V_REQUIRE(out && M > 0 && N > 0 && K > 0 && ncu > 0, "s2v_diag_gemm_plan: bad argument");
+    static char p[16];  // never dereferenced: a non-null pointer where the engine passes one
+    GemmArgs g{};
+    g.A = p; g.lda = K; g.W = p; g.ldw = K; g.bias = p; g.C = p; g.ldc = N; g.M = M; g.N = N; g.K = K;
+    g.a_rows_padded = (M + 255) / 256 * 256; g.w_rows_padded = (N + 255) / 256 * 256;
+    g.X = p; g.ldx = N; g.gate_vid = p; g.gate_txt = p; g.gate_stride = N; g.R = p; g.ldr = N;
+    g.tok_per_batch = M; g.qk_w[0] = g.qk_w[1] = g.qk_b[0] = g.qk_b[1] = p; g.qk_D = N / 3; g.qk_cs = (flags & 2) ? (const float*)p : nullptr;
+    g.f16 = flags & 1;
+    if (flags & 4) {
+        g.w_scale = (const float*)p;
+        if (flags & 8) { g.mx_a_s = (const unsigned char*)p; g.mx_rows = g.a_rows_padded; }
+        else g.a_scale = (const float*)p;
+    }
+    if (flags & 16) { g.conv = 1; g.kt = 3; g.cin = K / 27; g.lda = 0; g.a_rows_padded = 0; }
+    const GemmPlan pl = gemm_plan(g, epi, ncu, sk_tiles);
+    out[0] = pl.splitk; out[1] = pl.tile; out[2] = pl.m_main; out[3] = pl.main; out[4] = pl.tail;
+    return 0;
+}
 #else
 static constexpr int g_gemm_ablate = 0;
 static constexpr int g_gemm_impl = 9;  // 9: gemm_g4 where it qualifies, gemm_bf16_pp64 otherwise (the product's choice); 7: gemm_bf16_pp64; 5 / 8: A/B references
@@ -1220,6 +1250,91 @@ static int launch_fp8_t(const GemmArgs& a, hipStream_t st) {
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// the 256-column kernels take N that is not a multiple of 256 when the weight buffer physically holds the padded rows and
+// the last tile is at least half full (N = 1920 / 5760 of the 2B model); narrower outputs go to the 128-column kernels
+static bool w_tile_ok(const GemmArgs& a) {
+    if (a.N % WBN == 0) return true;
+    return a.N > WBN && a.w_rows_padded >= ((a.N + WBN - 1) / WBN) * WBN && (a.N % WBN) >= WBN / 2;
+}
+// ... and the rows of whole 256-row tiles are present behind A (a convolution's implicit A clamps its rows)
+static bool fits_256(const GemmArgs& a) { return w_tile_ok(a) && (a.conv || a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM); }
+
+// The kernel of ONE launch as given (launch_gemm_bf16 / launch_gemm_fp8 run it; gemm_plan asks it for its main and tail launches).
+static int gemm_kernel(const GemmArgs& a, int epi, int ncu) {
+    if (a.w_scale) return g_gemm_impl == 9 && gemm_g4f_ok(a, epi) ? GEMM_G4F : GEMM_PP64_FP8;  // e4m3 operands: the four-wave generated-asm loop (gemm_g4f.hip)
+    // the row tail of a split GEMM; the fused q/k-norm without whole 256-row tiles (only the vector epilogue of the 256- and 128-row kernels implements it)
+    if (a.m_begin > 0 || (epi == EPI_BIAS_QKNORM && !fits_256(a))) return GEMM_128;
+#ifdef S2V_DIAG
+    if (g_gemm_impl == 8 && !a.conv && (epi == EPI_BIAS || epi == EPI_BIAS_GELU) && w_tile_ok(a) && a.N % 64 == 0 && a.K >= 36 * 64 &&
+        epi_vec_ok(a, epi) && a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM && a.lda % 8 == 0 && a.ldw % 8 == 0)
+        return GEMM_Q4;
+#endif
+    bool g4_epi = true, g4t_epi = true;
+#ifdef S2V_DIAG
+    if (const char* e = getenv("S2V_G4_EPI_MASK")) g4_epi = (atoi(e) >> epi) & 1;  // bisecting aid: g4 for the epilogues of the mask only
+    if (const char* e = getenv("S2V_G4T_EPI_MASK")) g4t_epi = (atoi(e) >> epi) & 1;  // same-box A/B: gemm_g4t for the epilogues of the mask only (tools/epi_mask_probe.py)
+#endif
+    // One round of tiles (<= one per CU) leaves the epilogue fully exposed, and the fused q/k-norm + rotary epilogue is the longest:
+    // eight waves run it faster than four (C1 QKV, 230 tiles: 65 us on the ping-pong kernel, 72 us on gemm_g4)
+    const int64_t out_tiles = (int64_t)((a.M + 255) / 256) * ((a.N + 255) / 256);
+    if (epi == EPI_BIAS_QKNORM && out_tiles <= ncu) g4_epi = false;
+    // the bias + GELU epilogue is the next longest: up to two rounds of tiles with a short reduction (C1 FF1: 300 tiles of 30 K-tiles) also run
+    // faster on eight waves -- same-box A/B of the C1 step, 11.50 -> 11.12 ms (tools/c1_attn_kernel_probe.py, S2V_G4_EPI_MASK); same epilogue
+    // code, bit-identical results
+    if (epi == EPI_BIAS_GELU && a.splitk <= 1 && a.K <= 2048 && out_tiles <= 2 * ncu) g4_epi = false;
+    // a convolution whose 256 x 256 tiles would leave half the CUs idle (the VAE's latent-resolution layers: M = 10800, N = 512 -> 86 tiles of
+    // 216 K-tiles, 0.52 PF, profiles/r04_vae_conv_rates.txt) runs on 256 x 128 tiles instead
+    const bool conv_few = a.conv && out_tiles * 2 <= ncu && epi != EPI_BIAS_QKNORM;
+    const bool big_tiles = (a.tile == 0 && !conv_few) || (a.conv && !conv_few) || epi == EPI_BIAS_QKNORM;  // GemmArgs::tile: the caller asks for smaller tiles
+    // a.f16 (round 5): the operands are fp16 -- the same choice on the kernels' fp16 instantiations (the four-wave asm loop with the fp16 mnemonic,
+    // the eight-wave ping-pong, the staggered 256 x 128 ring, the 128 x 128 kernel), the fused q/k-norm epilogue included; not for fp16: gemm_g4t
+    const bool g4 = g_gemm_impl == 9 && big_tiles && w_tile_ok(a) && gemm_g4_ok(a, epi);  // four-wave generated-asm K loop
+    if (g4 && g_gemm_g4t && g4t_epi && !a.f16 && gemm_g4t_ok(a, epi, ncu)) return GEMM_G4T;
+    if (g4 && g4_epi) return GEMM_G4;
+    if ((g_gemm_impl == 7 || g_gemm_impl == 8 || g_gemm_impl == 9) && big_tiles && fits_256(a)) return GEMM_PP64;
+#ifdef S2V_DIAG
+    if (g_gemm_impl == 5 && fits_256(a)) return GEMM_W8;
+#endif
+    if ((g_gemm_impl == 2 || g_gemm_impl >= 4) && (a.tile != 2 || a.conv) && epi != EPI_BIAS_QKNORM && (a.conv || a.a_rows_padded >= ((a.M + RBM - 1) / RBM) * RBM))
+        return GEMM_STAG;
+    return GEMM_128;
+}
+
+GemmPlan gemm_plan(const GemmArgs& g0, int epi, int ncu, int64_t sk_tiles) {
+    GemmArgs g = g0;
+    int m_main = g.M;
+    if (!g.conv && !g.w_scale) {  // an engine linear; a convolution (the VAE) or an fp8 GEMM runs as given
+        const int64_t tn = (g.N + 255) / 256, tm = (g.M + 255) / 256;
+        if (sk_tiles > 0 && g.splitk == 0) {
+            const int S = gemm_choose_splitk(tm * tn, g.K, ncu);
+            if (S > 1 && (int64_t)S * tm * tn <= sk_tiles) g.splitk = S;
+        }
+        // Few tiles (C1: M = 2500): half a round of 256 x 256 tiles or less and no split K (the out-projection: 80 tiles of 30 K-tiles)
+        // -> 256 x 128 tiles put twice the workgroups on the part: 36 us against 59 (tools/microbench.py gemm_c1, profiles/r03_c1_*).
+        // Measured and dropped: peeling the sparse second round of the FF1 (300 tiles on 256 CUs) off as 128 x 128 tiles -- 62 + 35 us
+        // against 100 for the two rounds on the same stream, slower (117) as a fork on the side stream.
+        if (g.splitk == 0 && epi != EPI_BIAS_QKNORM && g.tile == 0 && tm * tn * 2 <= ncu) g.tile = 1;
+        // Tile-count quantisation: the 256 x 256 kernel runs one tile per CU, so a grid that spills a few tiles into an extra
+        // round pays a whole round (C3: 150 x 12 = 1800 tiles = 7.03 rounds of 256 CUs for the out-proj / FF2).  When the
+        // last row tile is partial and dropping it saves a round, the full row tiles run on the big kernel and the row tail
+        // (108 rows at C3) on the 128 x 128 kernel.
+        // Round 6 (the B = 1 geometry of a CFG-parallel rank: M = 19 126): the persistent kernel with the trickled epilogue (gemm_g4t) takes whole
+        // 256-row tiles only, so a QKV projection whose row tail does NOT cost a round (75 x 36 = 2700 tiles = 10.5 rounds either way) used to run on
+        // gemm_g4 with the exposed q/k-norm epilogue: 0.90 ms where half the B = 2 launch is 0.80.  Split the tail off whenever that lets the whole
+        // tiles take gemm_g4t; the tail's 128 x 128 kernel returns the same bits (the B = 2 launch has mixed the two since round 5).
+        if (g.M % 256 != 0 && tm > 1 && g.N >= 256) {
+            GemmArgs gw = g;
+            gw.M = (int)((tm - 1) * 256);
+            if ((tm * tn + ncu - 1) / ncu > ((tm - 1) * tn + ncu - 1) / ncu || gemm_kernel(gw, epi, ncu) == GEMM_G4T) m_main = gw.M;
+        }
+    }
+    GemmArgs gm = g, gt = g;
+    gm.M = m_main;
+    gt.m_begin = m_main;
+    return GemmPlan{g.splitk, g.tile, m_main, gemm_kernel(gm, epi, ncu), m_main < g.M ? gemm_kernel(gt, epi, ncu) : (int)GEMM_NONE};
+}
+
 int launch_gemm_fp8(const GemmArgs& a, int epi, hipStream_t st) {
     S2V_REQUIRE(!a.conv && (a.a_scale || a.mx_a_s) && a.w_scale, "gemm_fp8: plain mode with the weight scales and row or block scales of A only");
     S2V_REQUIRE(!a.mx_out_q || (epi == EPI_BIAS_GELU && a.mx_out_s && a.N % 64 == 0), "gemm_fp8: MX output is the GELU epilogue's, N a multiple of 64");
@@ -1228,154 +1343,45 @@ int launch_gemm_fp8(const GemmArgs& a, int epi, hipStream_t st) {
     S2V_REQUIRE(a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM && a.w_rows_padded >= ((a.N + WBN - 1) / WBN) * WBN,
                 "gemm_fp8: operands must be padded to whole 256-row tiles");
     S2V_REQUIRE(epi_vec_ok(a, epi), "gemm_fp8: output rows must be 16-byte aligned and N a multiple of 8");
-    if (g_gemm_impl == 9 && gemm_g4f_ok(a, epi)) return launch_gemm_g4f(a, epi, st);  // four-wave generated-asm loop (gemm_g4f.hip)
-    switch (epi) {
-        case EPI_BIAS: return launch_fp8_t<EPI_BIAS>(a, st);
-        case EPI_BIAS_GELU: return launch_fp8_t<EPI_BIAS_GELU>(a, st);
-        case EPI_BIAS_GATE_RES: return launch_fp8_t<EPI_BIAS_GATE_RES>(a, st);
-        case EPI_BIAS_QKNORM: return launch_fp8_t<EPI_BIAS_QKNORM>(a, st);
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_fp8: bad epilogue", -1);
-    }
-}
-
-// the 256-column kernels take N that is not a multiple of 256 when the weight buffer physically holds the padded rows and
-// the last tile is at least half full (N = 1920 / 5760 of the 2B model); narrower outputs go to the 128-column kernels
-static bool w_tile_ok(const GemmArgs& a) {
-    if (a.N % WBN == 0) return true;
-    return a.N > WBN && a.w_rows_padded >= ((a.N + WBN - 1) / WBN) * WBN && (a.N % WBN) >= WBN / 2;
+    if (gemm_kernel(a, epi, 0) == GEMM_G4F) return launch_gemm_g4f(a, epi, st);  // (the fp8 choice counts no CUs)
+    return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_QKNORM>(epi, "gemm_fp8: bad epilogue",
+                                                                                   [&](auto e) { return launch_fp8_t<decltype(e)::value>(a, st); });
 }
 
 int launch_gemm_bf16(const GemmArgs& a0, int epi, hipStream_t st) {
     GemmArgs a = a0;
     a.ablate = g_gemm_ablate;
-    if (epi == EPI_BIAS_QKNORM) {  // only the vector epilogue of the 256- and 128-row kernels implements it
-        S2V_REQUIRE(!a.conv && epi_vec_ok(a, epi) && a.qk_D > 0 && a.qk_D % 64 == 0 && a.N == 3 * a.qk_D && a.tok_per_batch > 0 && a.qk_w[0] && a.qk_w[1] &&
-                        a.qk_b[0] && a.qk_b[1],
-                    "gemm_bf16: fused qk-norm needs the vector epilogue, N = 3 * qk_D and the LayerNorm parameters");
-        if (!(a.m_begin > 0) && !(w_tile_ok(a) && a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM)) {
-            const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-            if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<EPI_BIAS_QKNORM, f16_t>), dim3(tiles_m * tiles_n), dim3(256), 4 * TILE_BYTES, st, a, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_bf16_128<EPI_BIAS_QKNORM>, dim3(tiles_m * tiles_n), dim3(256), 4 * TILE_BYTES, st, a, tiles_m, tiles_n);
-            S2V_CHECK_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    if (a.m_begin > 0) {  // row tail of a split GEMM: the 128 x 128 kernel on rows [m_begin, M)
+    S2V_REQUIRE(epi != EPI_BIAS_QKNORM || (!a.conv && epi_vec_ok(a, epi) && a.qk_D > 0 && a.qk_D % 64 == 0 && a.N == 3 * a.qk_D && a.tok_per_batch > 0 &&
+                                           a.qk_w[0] && a.qk_w[1] && a.qk_b[0] && a.qk_b[1]),
+                "gemm_bf16: fused qk-norm needs the vector epilogue, N = 3 * qk_D and the LayerNorm parameters");
+    const int k = gemm_kernel(a, epi, device_cus());  // rounds are counted in THIS device's CUs
+    if (a.m_begin > 0) {
         S2V_REQUIRE(!a.conv && a.K % BK == 0 && a.lda % 8 == 0 && a.ldw % 8 == 0, "gemm_bf16: bad tail launch");
-        const int tiles_m = (a.M - a.m_begin + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-        const size_t shmem = 4 * TILE_BYTES;
-        const dim3 grid(tiles_m * tiles_n);
-#define S2V_TAIL128(E)                                                                                                              \
-    if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<E, f16_t>), grid, dim3(256), shmem, st, a, tiles_m, tiles_n);                         \
-    else hipLaunchKernelGGL(gemm_bf16_128<E>, grid, dim3(256), shmem, st, a, tiles_m, tiles_n);                                        \
-    break;
-        switch (epi) {  // a.f16: the fp16 instantiation (until round 5's last day this branch launched the bf16 kernel on fp16 operands)
-            case EPI_BIAS: S2V_TAIL128(EPI_BIAS)
-            case EPI_BIAS_GELU: S2V_TAIL128(EPI_BIAS_GELU)
-            case EPI_BIAS_GATE_RES: S2V_TAIL128(EPI_BIAS_GATE_RES)
-            case EPI_BIAS_ADD: S2V_TAIL128(EPI_BIAS_ADD)
-            case EPI_BIAS_QKNORM: S2V_TAIL128(EPI_BIAS_QKNORM)
-            default: return s2v_fail(__FILE__, __LINE__, "gemm_bf16: bad epilogue", -1);
-        }
-#undef S2V_TAIL128
-        S2V_CHECK_HIP(hipGetLastError());
-        return 0;
+    } else if (epi != EPI_BIAS_QKNORM || fits_256(a)) {  // (the fused q/k-norm on 128 x 128 tiles for want of whole 256-row tiles is launched as is)
+        S2V_REQUIRE(a.K % BK == 0, "gemm_bf16: K must be a multiple of 64");
+        S2V_REQUIRE(!a.f16 || (a.splitk <= 1 && a.mx_out_q == nullptr), "gemm (fp16): no split K or MX output");
+        if (k == GEMM_PP64 || k == GEMM_W8 || k == GEMM_STAG || k == GEMM_128)
+            S2V_REQUIRE((a.conv ? a.cin % 64 == 0 : a.lda % 8 == 0) && a.ldw % 8 == 0, "gemm_bf16: bad leading dims");
     }
-    S2V_REQUIRE(a.K % BK == 0, "gemm_bf16: K must be a multiple of 64");
-    // a.f16 (round 5): the operands are fp16 -- the same dispatch on the kernels' fp16 instantiations (the four-wave asm loop with the fp16 mnemonic,
-    // the eight-wave ping-pong, the staggered 256 x 128 ring, the 128 x 128 kernel), the fused q/k-norm epilogue included; not for fp16: gemm_g4t, split K
-    S2V_REQUIRE(!a.f16 || (a.splitk <= 1 && a.mx_out_q == nullptr), "gemm (fp16): no split K or MX output");
+    switch (k) {
 #ifdef S2V_DIAG
-    if (g_gemm_impl == 8 && !a.conv && (epi == EPI_BIAS || epi == EPI_BIAS_GELU) && w_tile_ok(a) && a.N % 64 == 0 && a.K >= 36 * 64 &&
-        epi_vec_ok(a, epi) && a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM && a.lda % 8 == 0 && a.ldw % 8 == 0) {
-        return epi == EPI_BIAS ? launch_q4_t<EPI_BIAS>(a, st) : launch_q4_t<EPI_BIAS_GELU>(a, st);
-    }
+        case GEMM_Q4: return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU>(epi, "gemm_bf16: bad epilogue", [&](auto e) { return launch_q4_t<decltype(e)::value>(a, st); });
+        case GEMM_W8:
+            return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD>(epi, "gemm_bf16: bad epilogue",
+                                                                                          [&](auto e) { return launch_w8_t<decltype(e)::value>(a, st); });
 #endif
-    bool g4_epi = true;
-#ifdef S2V_DIAG
-    if (const char* e = getenv("S2V_G4_EPI_MASK")) g4_epi = (atoi(e) >> epi) & 1;  // bisecting aid: g4 for the epilogues of the mask only
-#endif
-    // One round of tiles (<= one per CU) leaves the epilogue fully exposed, and the fused q/k-norm + rotary epilogue is the longest:
-    // eight waves run it faster than four (C1 QKV, 230 tiles: 65 us on the ping-pong kernel, 72 us on gemm_g4)
-    const int64_t out_tiles = (int64_t)((a.M + 255) / 256) * ((a.N + 255) / 256), cus = device_cus();  // rounds are counted in THIS device's CUs
-    if (epi == EPI_BIAS_QKNORM && out_tiles <= cus) g4_epi = false;
-    // the bias + GELU epilogue is the next longest: up to two rounds of tiles with a short reduction (C1 FF1: 300 tiles of 30 K-tiles) also run
-    // faster on eight waves -- same-box A/B of the C1 step, 11.50 -> 11.12 ms (tools/c1_attn_kernel_probe.py, S2V_G4_EPI_MASK); same epilogue
-    // code, bit-identical results
-    if (epi == EPI_BIAS_GELU && a.splitk <= 1 && a.K <= 2048 && out_tiles <= 2 * cus) g4_epi = false;
-    // a convolution whose 256 x 256 tiles would leave half the CUs idle (the VAE's latent-resolution layers: M = 10800, N = 512 -> 86 tiles of
-    // 216 K-tiles, 0.52 PF, profiles/r04_vae_conv_rates.txt) runs on 256 x 128 tiles instead
-    const bool conv_few = a.conv && out_tiles * 2 <= cus && epi != EPI_BIAS_QKNORM;
-    const bool big_tiles = (a.tile == 0 && !conv_few) || (a.conv && !conv_few) || epi == EPI_BIAS_QKNORM;  // GemmArgs::tile: the caller asks for smaller tiles
-    bool g4t_epi = true;
-#ifdef S2V_DIAG
-    if (const char* e = getenv("S2V_G4T_EPI_MASK")) g4t_epi = (atoi(e) >> epi) & 1;  // same-box A/B: gemm_g4t for the epilogues of the mask only (tools/epi_mask_probe.py)
-#endif
-    if (g_gemm_impl == 9 && g_gemm_g4t && g4t_epi && !a.f16 && big_tiles && w_tile_ok(a) && gemm_g4_ok(a, epi) && gemm_g4t_ok(a, epi, (int)cus)) return launch_gemm_g4t(a, epi, st);
-    if (g_gemm_impl == 9 && big_tiles && g4_epi && w_tile_ok(a) && gemm_g4_ok(a, epi)) return a.f16 ? launch_gemm_g4_f16(a, epi, st) : launch_gemm_g4(a, epi, st);  // four-wave generated-asm K loop
-    if ((g_gemm_impl == 7 || g_gemm_impl == 8 || g_gemm_impl == 9) && big_tiles && w_tile_ok(a) && (a.conv || a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM)) {
-        S2V_REQUIRE((a.conv ? a.cin % 64 == 0 : a.lda % 8 == 0) && a.ldw % 8 == 0, "gemm_bf16: bad leading dims");
-        switch (epi) {
-            case EPI_BIAS: return a.f16 ? launch_pp64_t<EPI_BIAS, f16_t>(a, st) : launch_pp64_t<EPI_BIAS>(a, st);
-            case EPI_BIAS_GELU: return a.f16 ? launch_pp64_t<EPI_BIAS_GELU, f16_t>(a, st) : launch_pp64_t<EPI_BIAS_GELU>(a, st);
-            case EPI_BIAS_GATE_RES: return a.f16 ? launch_pp64_t<EPI_BIAS_GATE_RES, f16_t>(a, st) : launch_pp64_t<EPI_BIAS_GATE_RES>(a, st);
-            case EPI_BIAS_ADD: return a.f16 ? launch_pp64_t<EPI_BIAS_ADD, f16_t>(a, st) : launch_pp64_t<EPI_BIAS_ADD>(a, st);
-            case EPI_BIAS_QKNORM: return a.f16 ? launch_pp64_t<EPI_BIAS_QKNORM, f16_t>(a, st) : launch_pp64_t<EPI_BIAS_QKNORM>(a, st);
-            default: return s2v_fail(__FILE__, __LINE__, "gemm_bf16: bad epilogue", -1);
-        }
-    }
-#ifdef S2V_DIAG
-    if (g_gemm_impl == 5 && w_tile_ok(a) && (a.conv || a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM)) {
-        S2V_REQUIRE((a.conv ? a.cin % 64 == 0 : a.lda % 8 == 0) && a.ldw % 8 == 0, "gemm_bf16: bad leading dims");
-        switch (epi) {
-            case EPI_BIAS: return launch_w8_t<EPI_BIAS>(a, st);
-            case EPI_BIAS_GELU: return launch_w8_t<EPI_BIAS_GELU>(a, st);
-            case EPI_BIAS_GATE_RES: return launch_w8_t<EPI_BIAS_GATE_RES>(a, st);
-            case EPI_BIAS_ADD: return launch_w8_t<EPI_BIAS_ADD>(a, st);
-            default: return s2v_fail(__FILE__, __LINE__, "gemm_bf16: bad epilogue", -1);
-        }
-    }
-#endif
-    if ((g_gemm_impl == 2 || g_gemm_impl >= 4) && (a.tile != 2 || a.conv) && epi != EPI_BIAS_QKNORM && (a.conv || a.a_rows_padded >= ((a.M + RBM - 1) / RBM) * RBM)) {
-        S2V_REQUIRE((a.conv ? a.cin % 64 == 0 : a.lda % 8 == 0) && a.ldw % 8 == 0, "gemm_bf16: bad leading dims");
-        switch (epi) {
-            case EPI_BIAS: return a.f16 ? launch_stag_t<EPI_BIAS, f16_t>(a, st) : launch_stag_t<EPI_BIAS>(a, st);
-            case EPI_BIAS_GELU: return a.f16 ? launch_stag_t<EPI_BIAS_GELU, f16_t>(a, st) : launch_stag_t<EPI_BIAS_GELU>(a, st);
-            case EPI_BIAS_GATE_RES: return a.f16 ? launch_stag_t<EPI_BIAS_GATE_RES, f16_t>(a, st) : launch_stag_t<EPI_BIAS_GATE_RES>(a, st);
-            case EPI_BIAS_ADD: return a.f16 ? launch_stag_t<EPI_BIAS_ADD, f16_t>(a, st) : launch_stag_t<EPI_BIAS_ADD>(a, st);
-            default: return s2v_fail(__FILE__, __LINE__, "gemm_bf16: bad epilogue", -1);
-        }
-    }
-    S2V_REQUIRE((a.conv ? a.cin % 64 == 0 : a.lda % 8 == 0) && a.ldw % 8 == 0, "gemm_bf16: bad leading dims");
-    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-    const int grid = tiles_m * tiles_n;
-    const size_t shmem = 4 * TILE_BYTES;
-    switch (epi) {
-        case EPI_BIAS:
-            if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<EPI_BIAS, f16_t>), dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_bf16_128<EPI_BIAS>, dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            break;
-        case EPI_BIAS_GELU:
-            if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<EPI_BIAS_GELU, f16_t>), dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_bf16_128<EPI_BIAS_GELU>, dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            break;
-        case EPI_BIAS_GATE_RES:
-            if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<EPI_BIAS_GATE_RES, f16_t>), dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_bf16_128<EPI_BIAS_GATE_RES>, dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            break;
-        case EPI_BIAS_ADD:
-            if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<EPI_BIAS_ADD, f16_t>), dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_bf16_128<EPI_BIAS_ADD>, dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            break;
-        case EPI_BIAS_QKNORM:
-            if (a.f16) hipLaunchKernelGGL((gemm_bf16_128<EPI_BIAS_QKNORM, f16_t>), dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_bf16_128<EPI_BIAS_QKNORM>, dim3(grid), dim3(256), shmem, st, a, tiles_m, tiles_n);
-            break;
+        case GEMM_G4T: return launch_gemm_g4t(a, epi, st);
+        case GEMM_G4: return launch_gemm_g4(a, epi, st);
+        case GEMM_PP64:
+            return epi_dispatch16<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD, EPI_BIAS_QKNORM>(
+                epi, a.f16, "gemm_bf16: bad epilogue", [&](auto e, auto t) { return launch_pp64_t<decltype(e)::value, decltype(t)>(a, st); });
+        case GEMM_STAG:
+            return epi_dispatch16<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD>(
+                epi, a.f16, "gemm_bf16: bad epilogue", [&](auto e, auto t) { return launch_stag_t<decltype(e)::value, decltype(t)>(a, st); });
         default:
-            return s2v_fail(__FILE__, __LINE__, "gemm_bf16: bad epilogue", -1);
+            return epi_dispatch16<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD, EPI_BIAS_QKNORM>(
+                epi, a.f16, "gemm_bf16: bad epilogue", [&](auto e, auto t) { return launch_128_t<decltype(e)::value, decltype(t)>(a, st); });
     }
-    S2V_CHECK_HIP(hipGetLastError());
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1428,17 +1434,11 @@ __global__ __launch_bounds__(256) void gemm_simple_k(const GemmArgs a) {
 template <typename T>
 static int launch_simple_t(const GemmArgs& a, int epi, hipStream_t st) {
     dim3 grid((a.N + 63) / 64, (a.M + 63) / 64);
-    switch (epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm_simple_k<T, EPI_BIAS>), grid, dim3(256), 0, st, a); break;
-        case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_simple_k<T, EPI_BIAS_GELU>), grid, dim3(256), 0, st, a); break;
-        case EPI_BIAS_GATE_RES:
-            hipLaunchKernelGGL((gemm_simple_k<T, EPI_BIAS_GATE_RES>), grid, dim3(256), 0, st, a);
-            break;
-        case EPI_BIAS_ADD: hipLaunchKernelGGL((gemm_simple_k<T, EPI_BIAS_ADD>), grid, dim3(256), 0, st, a); break;
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_simple: bad epilogue", -1);
-    }
-    S2V_CHECK_HIP(hipGetLastError());
-    return 0;
+    return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD>(epi, "gemm_simple: bad epilogue", [&](auto e) {
+        hipLaunchKernelGGL((gemm_simple_k<T, decltype(e)::value>), grid, dim3(256), 0, st, a);
+        S2V_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 int launch_gemm_simple(const GemmArgs& a, int epi, int dtype, hipStream_t st) {

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epi.h"
+#include "epi_dispatch.h"
 
 #define FBK 16
 
@@ -161,17 +162,6 @@ bool gemm_f32m_ok(const GemmArgs& a) {
 // shorter sides: more operand traffic per MFMA and more prologues); the cheapest wins, ties go to the larger tile.  At C3 sizes (thousands of tiles)
 // every candidate costs the same within the penalty and 128 x 128 stays; at configs[0] (M = 2500) the N = 1920 GEMMs go from 300 tiles (2 per CU on
 // 44 CUs, 1 on the rest) to 1200 tiles of 64 x 64 (5 quarter tiles per CU at most: 1.25 tile times instead of 2).
-static int f32m_cus() {
-    static int cus[64] = {0};
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
-    if (!cus[d]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256;
-        cus[d] = n;
-    }
-    return cus[d];
-}
 int f32m_pick_tile(int M, int N, int cus) {
     static const int bm[4] = {128, 128, 64, 64}, bn[4] = {128, 64, 128, 64};
     static const double pen[4] = {1.0, 1.04, 1.04, 1.08};
@@ -189,21 +179,17 @@ template <int FBM, int FBN>
 static int launch_f32m_t(const GemmArgs& a, int epi, hipStream_t st) {
     const int tiles_m = (a.M + FBM - 1) / FBM, tiles_n = (a.N + FBN - 1) / FBN;
     const dim3 grid(tiles_m * tiles_n);
-    switch (epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm_f32m_k<EPI_BIAS, FBM, FBN>), grid, dim3(256), 0, st, a, tiles_m, tiles_n); break;
-        case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_f32m_k<EPI_BIAS_GELU, FBM, FBN>), grid, dim3(256), 0, st, a, tiles_m, tiles_n); break;
-        case EPI_BIAS_GATE_RES: hipLaunchKernelGGL((gemm_f32m_k<EPI_BIAS_GATE_RES, FBM, FBN>), grid, dim3(256), 0, st, a, tiles_m, tiles_n); break;
-        case EPI_BIAS_ADD: hipLaunchKernelGGL((gemm_f32m_k<EPI_BIAS_ADD, FBM, FBN>), grid, dim3(256), 0, st, a, tiles_m, tiles_n); break;
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_f32m: bad epilogue", -1);
-    }
-    S2V_CHECK_HIP(hipGetLastError());
-    return 0;
+    return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD>(epi, "gemm_f32m: bad epilogue", [&](auto e) {
+        hipLaunchKernelGGL((gemm_f32m_k<decltype(e)::value, FBM, FBN>), grid, dim3(256), 0, st, a, tiles_m, tiles_n);
+        S2V_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 int launch_gemm_f32m(const GemmArgs& a, int epi, hipStream_t st) {
     S2V_REQUIRE(gemm_f32m_ok(a), "gemm_f32m: shape / alignment not supported (K, lda, ldw multiples of 4 floats, 16-byte aligned operands)");
     // GemmArgs::tile 30 .. 33 (s2v_op_linear impl 30 .. 33: tests and tools/f32m_bench.py) forces a candidate; otherwise the cost model picks
-    const int t = (a.tile >= 30 && a.tile <= 33) ? a.tile - 30 : f32m_pick_tile(a.M, a.N, f32m_cus());
+    const int t = (a.tile >= 30 && a.tile <= 33) ? a.tile - 30 : f32m_pick_tile(a.M, a.N, device_cus());
     switch (t) {
         case 1: return launch_f32m_t<128, 64>(a, epi, st);
         case 2: return launch_f32m_t<64, 128>(a, epi, st);

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epi.h"
+#include "epi_dispatch.h"
 #include "gemm_g4_regs.h"
 #include <cstdlib>
 #include <type_traits>
@@ -218,26 +219,7 @@ int gemm_choose_splitk(int64_t tiles, int K, int64_t ncu) {
     while (S > 1 && !(K % (128 * S) == 0 && K / (64 * S) >= 16)) --S;
     return S;
 }
-// fp16 operands: the same conditions as gemm_g4_ok without split K
-bool gemm_g4_f16_ok(const GemmArgs& a, int epi) { return a.splitk <= 1 && a.mx_out_q == nullptr && gemm_g4_ok(a, epi); }
-int launch_gemm_g4_f16(const GemmArgs& a, int epi, hipStream_t st) {
-    S2V_REQUIRE(gemm_g4_f16_ok(a, epi), "gemm_g4 (fp16): shape / epilogue not supported");
-    switch (epi) {
-        case EPI_BIAS: return launch_g4_t<EPI_BIAS, f16_t>(a, st);
-        case EPI_BIAS_GELU: return launch_g4_t<EPI_BIAS_GELU, f16_t>(a, st);
-        case EPI_BIAS_GATE_RES: return launch_g4_t<EPI_BIAS_GATE_RES, f16_t>(a, st);
-        case EPI_BIAS_ADD: return launch_g4_t<EPI_BIAS_ADD, f16_t>(a, st);
-        case EPI_BIAS_QKNORM: return launch_g4_t<EPI_BIAS_QKNORM, f16_t>(a, st);
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_g4 (fp16): bad epilogue", -1);
-    }
-}
 int launch_gemm_g4(const GemmArgs& a, int epi, hipStream_t st) {
-    switch (epi) {
-        case EPI_BIAS: return launch_g4_t<EPI_BIAS>(a, st);
-        case EPI_BIAS_GELU: return launch_g4_t<EPI_BIAS_GELU>(a, st);
-        case EPI_BIAS_GATE_RES: return launch_g4_t<EPI_BIAS_GATE_RES>(a, st);
-        case EPI_BIAS_ADD: return launch_g4_t<EPI_BIAS_ADD>(a, st);
-        case EPI_BIAS_QKNORM: return launch_g4_t<EPI_BIAS_QKNORM>(a, st);
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_g4: bad epilogue", -1);
-    }
+    return epi_dispatch16<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_ADD, EPI_BIAS_QKNORM>(
+        epi, a.f16, "gemm_g4: bad epilogue", [&](auto e, auto t) { return launch_g4_t<decltype(e)::value, decltype(t)>(a, st); });
 }

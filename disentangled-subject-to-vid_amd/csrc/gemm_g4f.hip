@@ -9,6 +9,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epi.h"
+#include "epi_dispatch.h"
 #include "gemm_g4f_regs.h"
 
 typedef __attribute__((ext_vector_type(32))) float f32x32;
@@ -134,12 +135,11 @@ bool gemm_g4f_ok(const GemmArgs& a, int epi) {
 }
 
 int launch_gemm_g4f(const GemmArgs& a, int epi, hipStream_t st) {
-    const bool mx = a.mx_a_s != nullptr;
-    switch (epi) {
-        case EPI_BIAS: return mx ? launch_g4f_t<EPI_BIAS, true>(a, st) : launch_g4f_t<EPI_BIAS, false>(a, st);
-        case EPI_BIAS_GATE_RES: return mx ? launch_g4f_t<EPI_BIAS_GATE_RES, true>(a, st) : launch_g4f_t<EPI_BIAS_GATE_RES, false>(a, st);
-        case EPI_BIAS_GELU: return launch_g4f_t<EPI_BIAS_GELU, false>(a, st);
-        case EPI_BIAS_QKNORM: return launch_g4f_t<EPI_BIAS_QKNORM, false>(a, st);
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_g4f: bad epilogue", -1);
-    }
+    return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_QKNORM>(epi, "gemm_g4f: bad epilogue", [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E == EPI_BIAS || E == EPI_BIAS_GATE_RES) {  // the epilogues with an MX form
+            if (a.mx_a_s) return launch_g4f_t<E, true>(a, st);
+        }
+        return launch_g4f_t<E, false>(a, st);
+    });
 }

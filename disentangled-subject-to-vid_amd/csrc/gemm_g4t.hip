@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gemm_epi.h"
+#include "epi_dispatch.h"
 #include "gemm_g4t_regs.h"
 
 typedef __attribute__((ext_vector_type(32))) float f32x32;
@@ -152,10 +153,7 @@ static int launch_g4t_t(const GemmArgs& a_in, hipStream_t st) {
     GemmArgs a = a_in;
     const int tiles_m = a.M / 256, tiles_n = a.N / 256;
     if (a.gm <= 0) a.gm = (tiles_n <= 16 && tiles_m >= 32 && a.K >= 8192) ? 1 : 4;  // as gemm_g4
-    int dev = 0, ncu = 256;
-    S2V_CHECK_HIP(hipGetDevice(&dev));
-    S2V_CHECK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    const int grid = (ncu / 8) * 8;
+    const int grid = (device_cus() / 8) * 8;
     const void* fn = (const void*)gemm_g4t<EPI>;
     const int lds = G4T_LDS_BYTES + (EPI == EPI_BIAS_QKNORM ? G4T_QK_CONST_BYTES : 0);
     S2V_TRY(ensure_lds_attr(fn, lds));
@@ -184,10 +182,6 @@ bool gemm_g4t_ok(const GemmArgs& a, int epi, int ncu) {
 }
 
 int launch_gemm_g4t(const GemmArgs& a, int epi, hipStream_t st) {
-    switch (epi) {
-        case EPI_BIAS: return launch_g4t_t<EPI_BIAS>(a, st);
-        case EPI_BIAS_GELU: return launch_g4t_t<EPI_BIAS_GELU>(a, st);
-        case EPI_BIAS_QKNORM: return launch_g4t_t<EPI_BIAS_QKNORM>(a, st);
-        default: return s2v_fail(__FILE__, __LINE__, "gemm_g4t: bad epilogue", -1);
-    }
+    return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_QKNORM>(epi, "gemm_g4t: bad epilogue",
+                                                                 [&](auto e) { return launch_g4t_t<decltype(e)::value>(a, st); });
 }

@@ -102,12 +102,10 @@ int launch_gemm_f16(const GemmArgs& a, int epi, hipStream_t st);
 // gemm_f32m.hip: fp32 operands on v_mfma_f32_32x32x2_f32, bit-identical to gemm_simple_k<float>
 bool gemm_f32m_ok(const GemmArgs& a);
 int launch_gemm_f32m(const GemmArgs& a, int epi, hipStream_t st);
-// gemm_g4.hip: 256 x 256 tiles, four waves, generated-asm K loop (plain bf16 operands; gemm_g4_ok says whether a call qualifies)
+// gemm_g4.hip: 256 x 256 tiles, four waves, generated-asm K loop (plain operands; gemm_g4_ok says whether a call qualifies).  a.f16: the same
+// loop on fp16 operands (v_mfma_f32_32x32x16_f16) with the fp16 form of the vector epilogue -- the fp16 model dtype's big linears
 bool gemm_g4_ok(const GemmArgs& a, int epi);
 int launch_gemm_g4(const GemmArgs& a, int epi, hipStream_t st);
-// the same loop on fp16 operands (v_mfma_f32_32x32x16_f16) with the fp16 form of the vector epilogue: the fp16 model dtype's big linears
-bool gemm_g4_f16_ok(const GemmArgs& a, int epi);
-int launch_gemm_g4_f16(const GemmArgs& a, int epi, hipStream_t st);
 // gemm_g4f.hip: the four-wave loop on e4m3 operands (launch_gemm_fp8 routes to it where gemm_g4f_ok)
 bool gemm_g4f_ok(const GemmArgs& a, int epi);
 int launch_gemm_g4f(const GemmArgs& a, int epi, hipStream_t st);
@@ -120,6 +118,22 @@ int launch_gemm_g4t(const GemmArgs& a, int epi, hipStream_t st);
 // of `ncu` CUs and leaves an even number >= 16 of K-tiles per workgroup (below that the fp32 partial traffic costs what the shorter
 // loop saves: measured on the C1 out-projection).  1 = do not split.  Workspace: S * tiles * 256 KiB of partials + tiles counters (zero).
 int gemm_choose_splitk(int64_t tiles, int K, int64_t ncu);
+// compute units of the current device, queried once per device (launch-path heuristics count tile ROUNDS in these; 256 if the query fails)
+int device_cus();
+// The kernel choice of the 16-bit and fp8 GEMMs (gemm.hip).  gemm_plan is pure -- no HIP call, the CU count is an argument -- so it runs
+// without a device (tests/test_gemm_dispatch_cpu.py through s2v_diag_gemm_plan).  For an engine linear (api.hip linear(): plain operands
+// with the rows padded to 256) it decides split K (sk_tiles = the partial tiles of the context's workspace, 0: none), GemmArgs::tile and
+// whether the partial last row tile runs as a tail launch; convolutions and fp8 GEMMs run as given.  launch_gemm_bf16 / launch_gemm_fp8
+// run the kernel it names for each launch.
+enum GemmKernel { GEMM_NONE = 0, GEMM_128, GEMM_STAG, GEMM_PP64, GEMM_G4, GEMM_G4T, GEMM_W8, GEMM_Q4, GEMM_G4F, GEMM_PP64_FP8 };
+struct GemmPlan {
+    int splitk;  // GemmArgs::splitk of the launch (0: K is not split)
+    int tile;    // GemmArgs::tile of the launches
+    int m_main;  // rows of the main launch: M, or the whole 256-row tiles when the partial last one runs as the tail launch
+    int main;    // GemmKernel of the main launch
+    int tail;    // GemmKernel of the tail launch on rows [m_main, M) (m_begin = m_main, side stream); GEMM_NONE: no tail
+};
+GemmPlan gemm_plan(const GemmArgs& g, int epi, int ncu, int64_t sk_tiles);
 // generic strided fp32 GEMM used at load time (LoRA merge): C[m,n] += alpha * sum_k A[m*sam+k*sak]*B[n*sbn+k*sbk]
 int launch_gemm_strided_f32(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbn, int64_t sbk,
                             float* C, int64_t ldc, int M, int N, int K, float alpha, hipStream_t st);
