@@ -1118,6 +1118,13 @@ static void fill_coef(SchedCoef& d, const s2v_sched_coef& s) {
     d.m1 = s.m1; d.m2 = s.m2; d.m3 = s.m3; d.m4 = s.m4; d.mn = s.mn; d.pad = 0.f;
 }
 
+extern "C" int s2v_add_noise(const void* sample, const void* noise, int64_t n, float sqrt_alpha, float sqrt_one_minus_alpha, void* out,
+                             int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(sample && noise && out && n > 0, "s2v_add_noise: bad argument");
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_add_noise: unsupported dtype");
+    return launch_add_noise(sample, noise, n, sqrt_alpha, sqrt_one_minus_alpha, out, dtype, (hipStream_t)stream);
+}
+
 extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags,
                               const void* latents_in, void* latents_out, float* x0_hist, const void* noise, int64_t n,
                               int32_t dtype, s2v_stream stream) {

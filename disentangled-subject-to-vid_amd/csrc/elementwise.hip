@@ -936,6 +936,28 @@ int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// scheduler.add_noise (scheduling_ddim_cogvideox.py:405-431, scheduling_dpm_cogvideox.py:442) of the video-to-video start
+// (pipeline_cogvideox_video2video.py:389): out = sqrt_a * x + sqrt_1ma * noise.  The host hands sqrt(alphas_cumprod[t]) and
+// sqrt(1 - alphas_cumprod[t]) already taken in T as torch takes them; both products and the sum round to T like torch's elementwise ops.
+// No fma contraction.
+template <typename T>
+__global__ void add_noise_k(const T* x, const T* noise, int64_t n, float sqrt_a, float sqrt_1ma, T* out) {
+#pragma clang fp contract(off)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float a = ET<T>::rnd(__fmul_rn(sqrt_a, ET<T>::ld(x + i)));
+        const float b = ET<T>::rnd(__fmul_rn(sqrt_1ma, ET<T>::ld(noise + i)));
+        ET<T>::st(out + i, __fadd_rn(a, b));
+    }
+}
+int launch_add_noise(const void* x, const void* noise, int64_t n, float sqrt_a, float sqrt_1ma, void* out, int dtype, hipStream_t st) {
+    const int64_t g = std::min<int64_t>((n + 255) / 256, 1 << 20);
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(add_noise_k<T>, dim3((unsigned)(g < 1 ? 1 : g)), dim3(256), 0, st, (const T*)x,
+                       (const T*)noise, n, sqrt_a, sqrt_1ma, (T*)out))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 template <typename TS, typename TD>
 __global__ void convert2d_k(const TS* src, int64_t lds_, TD* dst, int64_t ldd, int64_t rows, int64_t cols) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -303,6 +303,7 @@ struct SchedArgs {
     int out_f32;              // latents_out is fp32 and un-rounded (scheduler.step's return value)
 };
 int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st);
+int launch_add_noise(const void* x, const void* noise, int64_t n, float sqrt_a, float sqrt_1ma, void* out, int dtype, hipStream_t st);
 // dst[i] = (Tdst) src[i]
 int launch_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t st);
 // strided 2-D convert-copy: dst[r*ldd + c] = src[r*lds + c]

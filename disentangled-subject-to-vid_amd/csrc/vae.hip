@@ -92,6 +92,48 @@ int launch_dense_to_padded(const void* in, int F, int H, int W, int C, void* out
     return 0;
 }
 
+// CogVideoXDownsample3D's compress_time half (downsampling.py:322-338) fused into the write of the stride-2 conv's operand:
+// dense [F][H][W][C] -> padded [Fo][H+2][W+2][C] at (1, 1).  Frame pairs are averaged, and with an odd count the first frame is
+// kept as it is: Fo = (F + 1) / 2 for odd F, F / 2 for even F.  avg_pool1d sums the pair in fp32 and divides by 2 (exact as * 0.5),
+// then rounds once to T.  One thread per 16-byte vector of channels.
+template <typename T>
+__global__ void time_pool_to_padded_k(const T* in, int F, int H, int W, int C, T* out) {
+    constexpr int VN = V16<T>::N;
+    const int odd = F & 1, Fo = odd ? (F + 1) / 2 : F / 2, CV = C / VN;
+    const int64_t total = (int64_t)Fo * H * W * CV;
+    const int64_t fs = (int64_t)H * W * C;
+    const int Hp = H + 2, Wp = W + 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int cv = (int)(i % CV);
+        const int x = (int)((i / CV) % W);
+        const int y = (int)((i / ((int64_t)CV * W)) % H);
+        const int fo = (int)(i / ((int64_t)CV * W * H));
+        const int64_t pix = ((int64_t)y * W + x) * C + cv * VN;
+        float a[VN], b[VN];
+        T* dst = out + (((int64_t)fo * Hp + y + 1) * Wp + x + 1) * C + cv * VN;
+        if (odd && fo == 0) {
+            V16<T>::ld(in + pix, a);
+        } else {
+            const int f = odd ? 2 * fo - 1 : 2 * fo;
+            V16<T>::ld(in + f * fs + pix, a);
+            V16<T>::ld(in + (f + 1) * fs + pix, b);
+#pragma unroll
+            for (int e = 0; e < VN; ++e) a[e] = __fmul_rn(__fadd_rn(a[e], b[e]), 0.5f);
+        }
+        V16<T>::st(dst, a);
+    }
+}
+int launch_time_pool_to_padded(const void* in, int F, int H, int W, int C, void* out, int dtype, hipStream_t st) {
+    const int VN = dtype == S2V_F32 ? 4 : 8;
+    S2V_REQUIRE(F >= 1 && C % VN == 0, "time_pool_to_padded: channels must fill 16-byte vectors");
+    const int Fo = (F & 1) ? (F + 1) / 2 : F / 2;
+    const int64_t total = (int64_t)Fo * H * W * (C / VN);
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(time_pool_to_padded_k<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)in, F, H, W, C,
+                       (T*)out))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // the zero ring of a padded operand [F][Hp][Wp][C] (the implicit-GEMM convolution's padding = 1): a new window size moves the ring into
 // what was interior, and only the ring has to be cleared -- every interior cell is rewritten by the operand's producer before a
 // convolution reads it.  (Clearing whole buffers on every change of the tile size cost the tiled decode 35-40 ms of memsets.)
@@ -118,9 +160,11 @@ int launch_zero_border(void* pad, int F, int H, int W, int C, int esz, hipStream
     return 0;
 }
 
-// window (y0, x0, th, tw) of an image [C][F][H][W] -> zero-bordered channels-last operand [f_off + F][th+2][tw+2][C]
+// window (y0, x0, th, tw) of frames [fs, fs + F) of a video [C][Fall][H][W] -> zero-bordered channels-last operand
+// [f_off + F][th+2][tw+2][C]
 template <typename T>
-__global__ void image_to_padded_k(const T* img, int C, int F, int H, int W, int y0, int x0, int th, int tw, T* out, int f_off) {
+__global__ void image_to_padded_k(const T* img, int C, int F, int Fall, int fs, int H, int W, int y0, int x0, int th, int tw, T* out,
+                                  int f_off) {
     const int64_t total = (int64_t)F * th * tw * C;
     const int Hp = th + 2, Wp = tw + 2;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -128,14 +172,15 @@ __global__ void image_to_padded_k(const T* img, int C, int F, int H, int W, int 
         const int x = (int)((i / C) % tw);
         const int y = (int)((i / ((int64_t)C * tw)) % th);
         const int f = (int)(i / ((int64_t)C * tw * th));
-        out[((((int64_t)(f + f_off)) * Hp + y + 1) * Wp + x + 1) * C + c] = img[(((int64_t)c * F + f) * H + y0 + y) * W + x0 + x];
+        out[((((int64_t)(f + f_off)) * Hp + y + 1) * Wp + x + 1) * C + c] = img[(((int64_t)c * Fall + fs + f) * H + y0 + y) * W + x0 + x];
     }
 }
-int launch_image_to_padded(const void* img, int C, int F, int H, int W, int y0, int x0, int th, int tw, void* out, int f_off,
-                           int dtype, hipStream_t st) {
+int launch_image_to_padded(const void* img, int C, int F, int Fall, int fs, int H, int W, int y0, int x0, int th, int tw, void* out,
+                           int f_off, int dtype, hipStream_t st) {
+    S2V_REQUIRE(fs >= 0 && fs + F <= Fall, "image_to_padded: frame range outside the video");
     const int64_t total = (int64_t)F * th * tw * C;
-    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(image_to_padded_k<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)img, C, F, H, W, y0, x0,
-                       th, tw, (T*)out, f_off))
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(image_to_padded_k<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)img, C, F, Fall, fs, H, W,
+                       y0, x0, th, tw, (T*)out, f_off))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

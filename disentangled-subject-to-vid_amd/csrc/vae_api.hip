@@ -863,45 +863,85 @@ extern "C" int s2v_vae_enc_create(const s2v_vae_config* cfg, s2v_vae** out) {
     return 0;
 }
 
-static int enc_prepare(s2v_vae* v, int TH, int TW) {
-    if (v->th >= TH && v->tw >= TW) return 0;
+// Encoder frame batches (AutoencoderKLCogVideoX._encode, autoencoder_kl_cogvideox.py:1177-1202; num_sample_frames_batch_size = 8):
+// the first batch takes 8 + F % 8 frames, every later batch 8; one frame is one batch of one
+static std::vector<Batch> enc_frame_batches(int F) {
+    const int fbs = 8;
+    const int nb = F / fbs > 1 ? F / fbs : 1, rem = F % fbs;
+    std::vector<Batch> b;
+    for (int i = 0; i < nb; ++i) b.push_back({fbs * i + (i == 0 ? 0 : rem), std::min(fbs * (i + 1) + rem, F)});
+    return b;
+}
+// CogVideoXDownsample3D with compress_time: frame pairs averaged, the first frame kept alone when the count is odd
+static int down_frames(int F, int ct) { return !ct ? F : ((F & 1) ? (F + 1) / 2 : F / 2); }
+// frames at every level of one encoder pass over Fb input frames
+static void enc_level_frames(s2v_vae* v, int Fb, int* fl) {
+    int f = Fb, lvl = 0;
+    fl[0] = f;
+    for (auto& s : v->stages)
+        if (s.has_up) { f = down_frames(f, s.compress_time); fl[++lvl] = f; }
+}
+static int enc_latent_frames(s2v_vae* v, int F) {
+    int tot = 0, fl[8];
+    for (auto b : enc_frame_batches(F)) {
+        enc_level_frames(v, b.e - b.s, fl);
+        int lv = 0;
+        for (auto& s : v->stages) lv += s.has_up ? 1 : 0;
+        tot += fl[lv];
+    }
+    return tot;
+}
+static bool enc_frames_ok(int F) { return F == 1 || (F > 1 && (F - 1) % 8 == 0); }
+
+// One workspace set for windows up to TH x TW pixels and Fb frames per batch (the largest batch of the video, not the video).
+// Like the decoder's prepare_tile_capacity: the capacity fields are committed only after every buffer exists (a failed allocation leaves
+// the handle at "no capacity"), and a video encode on a set sized for a LARGER window rebuilds it at the requested size instead of
+// keeping the big one (an untiled 480 x 720 encode of 9 frames holds ~8 GB at the real widths; its 240 x 360 tiles need a quarter).
+static int enc_prepare(s2v_vae* v, int TH, int TW, int Fb = 1) {
+    const bool oversized = Fb > 1 && v->th > 0 && (v->th > TH || v->tw > TW);
+    if (!oversized && v->th >= TH && v->tw >= TW && v->fmax[0] >= Fb) return 0;
     S2V_CHECK_HIP(hipDeviceSynchronize());
     for (void* p : v->geo_allocs) (void)hipFree(p);
     v->geo_allocs.clear();
-    TH = std::max(TH, v->th); TW = std::max(TW, v->tw);
-    v->th = TH; v->tw = TW;
+    if (!oversized) { TH = std::max(TH, v->th); TW = std::max(TW, v->tw); }
+    Fb = std::max(Fb, v->fmax[0]);
+    v->th = v->tw = 0; v->cur_h = v->cur_w = 0;
+    for (int i = 0; i < 8; ++i) v->fmax[i] = 0;
+    int fl[8] = {0};
+    enc_level_frames(v, Fb, fl);
     int rc = 0;
     int64_t dmax = 0;
     for_each_conv(v, [&](ConvL& c) {
         const int64_t H = TH >> c.level, W = TW >> c.level;
-        const int F = c.kt == 3 ? 3 : 1;
+        const int F = fl[c.level] + (c.kt == 3 ? 2 : 0);  // the downsampler's operand holds the pooled frames: at most fl[level]
         c.pad_bytes = (int64_t)F * (H + 2) * (W + 2) * c.cin * v->esz + 1024;
         if (!rc) rc = dmalloc(v, &c.pad, c.pad_bytes, true);
-        dmax = std::max(dmax, H * W * std::max(c.cin, c.cout) * v->esz);
+        dmax = std::max(dmax, (int64_t)fl[c.level] * H * W * std::max(c.cin, c.cout) * v->esz);
     });
     if (rc) return rc;
     v->dense_bytes = dmax + (int64_t)256 * 1024 * v->esz;
     for (int i = 0; i < 3; ++i) S2V_TRY(dmalloc(v, &v->dense[i], v->dense_bytes, true));
-    S2V_TRY(dmalloc(v, &v->gn_part, gn_stats_scratch_bytes((int64_t)TH * TW, v->G) + 64, true));
-    v->cur_h = v->cur_w = 0;
+    S2V_TRY(dmalloc(v, &v->gn_part, gn_stats_scratch_bytes((int64_t)Fb * TH * TW, v->G) + 64, true));
+    v->th = TH; v->tw = TW;
+    for (int i = 0; i < 8; ++i) v->fmax[i] = fl[i];
     return 0;
 }
 
-static int run_gn_plain(s2v_vae* v, const SNormL& n, const void* x, int H, int W, void* out_pad, int f_off, hipStream_t st) {
-    S2V_TRY(launch_gn_stats(x, (int64_t)H * W, n.C, v->G, v->sums, v->gn_part, v->dtype, st));
+static int run_gn_plain(s2v_vae* v, const SNormL& n, const void* x, int F, int H, int W, void* out_pad, int f_off, hipStream_t st) {
+    S2V_TRY(launch_gn_stats(x, (int64_t)F * H * W, n.C, v->G, v->sums, v->gn_part, v->dtype, st));  // statistics over the frame batch
     SNormArgs a{};
-    a.x = x; a.F = 1; a.H = H; a.W = W; a.C = n.C; a.G = v->G; a.sums = v->sums; a.eps = v->cfg.norm_eps;
+    a.x = x; a.F = F; a.H = H; a.W = W; a.C = n.C; a.G = v->G; a.sums = v->sums; a.eps = v->cfg.norm_eps;
     a.gn_w = n.gn_w; a.gn_b = n.gn_b; a.Fz = 1; a.hz = 1; a.wz = 1; a.Cz = v->Cz;
     a.out = out_pad; a.f_off = f_off; a.silu = 1;  // yt == nullptr: plain GroupNorm
     return launch_snorm_apply(a, v->dtype, st);
 }
 
-// CogVideoXDownsample3D for one frame: F.pad(x, (0,1,0,1)) then Conv2d(3x3, stride 2): the operand sits at (1,1) of its
+// CogVideoXDownsample3D's spatial half, per frame: F.pad(x, (0,1,0,1)) then Conv2d(3x3, stride 2): the operand sits at (1,1) of its
 // zero-bordered buffer, so reading from (1,1) with stride 2 sees the zero column / row on the right / bottom only
-static int run_conv_down(s2v_vae* v, ConvL& c, int H, int W, void* out, hipStream_t st) {
+static int run_conv_down(s2v_vae* v, ConvL& c, int F, int H, int W, void* out, hipStream_t st) {
     GemmArgs g{};
     g.A = c.pad + ((int64_t)(W + 2) + 1) * c.cin * v->esz; g.W = c.w; g.ldw = 9 * c.cin; g.bias = c.b; g.C = out; g.ldc = c.cout;
-    g.M = (H / 2) * (W / 2); g.N = c.cout; g.K = 9 * c.cin;
+    g.M = F * (H / 2) * (W / 2); g.N = c.cout; g.K = 9 * c.cin;
     g.conv = 1; g.cin = c.cin; g.Hp = H + 2; g.Wp = W + 2; g.oH = H / 2; g.oW = W / 2; g.kt = 1; g.cstride = 2;
     g.w_rows_padded = (int)rup64(c.cout, 256);
     if (v->mfma && c.cin % 64 == 0) return launch_gemm_bf16(g, EPI_BIAS, st);
@@ -910,43 +950,64 @@ static int run_conv_down(s2v_vae* v, ConvL& c, int H, int W, void* out, hipStrea
     return launch_gemm_simple(g, EPI_BIAS, v->dtype, st);
 }
 
-// encoder pass over the (th x tw) pixel window at (y0, x0) of image [3][1][H][W]; dst = moments [2Cz][1][th/s][tw/s]
-static int encode_window(s2v_vae* v, const void* image, int Himg, int Wimg, int y0, int x0, int th, int tw, char* dst,
-                         hipStream_t st) {
-    S2V_TRY(set_layout(v, th, tw, st));
+// encoder pass over frames [fs, fs + Fb) (one frame batch) of the (th x tw) pixel window at (y0, x0) of video [3][Fv][H][W];
+// writes latent frames [f0, f0 + *frames_out) of dst = moments [2Cz][Fl][th/s][tw/s].  first: the batch that starts the conv caches.
+static int encode_batch(s2v_vae* v, const void* video, int Fv, int fs, int Fb, int Himg, int Wimg, int y0, int x0, int th, int tw,
+                        bool first, char* dst, int Fl, int f0, int* frames_out, hipStream_t st) {
     int cur = 0, t1 = 1, t2 = 2;
-    int H = th, W = tw;
-    S2V_TRY(launch_image_to_padded(image, v->cfg.out_channels, 1, Himg, Wimg, y0, x0, th, tw, v->conv_in.pad, 2, v->dtype, st));
-    S2V_TRY(run_conv(v, v->conv_in, 1, H, W, true, EPI_BIAS, nullptr, v->dense[cur], st));
+    int F = Fb, H = th, W = tw;
+    S2V_TRY(launch_image_to_padded(video, v->cfg.out_channels, Fb, Fv, fs, Himg, Wimg, y0, x0, th, tw, v->conv_in.pad, 2, v->dtype, st));
+    S2V_TRY(run_conv(v, v->conv_in, F, H, W, first, EPI_BIAS, nullptr, v->dense[cur], st));
     for (auto& s : v->stages) {
         for (auto& r : s.res) {
-            S2V_TRY(run_gn_plain(v, r.n1, v->dense[cur], H, W, r.c1.pad, 2, st));
-            S2V_TRY(run_conv(v, r.c1, 1, H, W, true, EPI_BIAS, nullptr, v->dense[t1], st));
-            S2V_TRY(run_gn_plain(v, r.n2, v->dense[t1], H, W, r.c2.pad, 2, st));
+            S2V_TRY(run_gn_plain(v, r.n1, v->dense[cur], F, H, W, r.c1.pad, 2, st));
+            S2V_TRY(run_conv(v, r.c1, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st));
+            S2V_TRY(run_gn_plain(v, r.n2, v->dense[t1], F, H, W, r.c2.pad, 2, st));
             if (r.has_sc) {
                 GemmArgs g{};
                 g.A = v->dense[cur]; g.lda = r.cin; g.W = r.sc.w; g.ldw = r.cin; g.bias = r.sc.b;
-                g.C = v->dense[t2]; g.ldc = r.cout; g.M = H * W; g.N = r.cout; g.K = r.cin;
+                g.C = v->dense[t2]; g.ldc = r.cout; g.M = F * H * W; g.N = r.cout; g.K = r.cin;
                 g.a_rows_padded = (int)rup64(g.M, 256);
                 if (v->mfma && r.cin % 64 == 0) S2V_TRY(launch_gemm_bf16(g, EPI_BIAS, st));
                 else if (v->h16 && gemm_f16_ok(g, EPI_BIAS)) S2V_TRY(launch_gemm_f16(g, EPI_BIAS, st));
                 else { g.valu_only = v->cfg.force_simple; S2V_TRY(launch_gemm_simple(g, EPI_BIAS, v->dtype, st)); }
-                S2V_TRY(run_conv(v, r.c2, 1, H, W, true, EPI_BIAS_ADD, v->dense[t2], v->dense[t2], st));
+                S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[t2], v->dense[t2], st));
                 std::swap(cur, t2);
             } else {
-                S2V_TRY(run_conv(v, r.c2, 1, H, W, true, EPI_BIAS_ADD, v->dense[cur], v->dense[cur], st));
+                S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[cur], v->dense[cur], st));
             }
         }
-        if (s.has_up) {  // downsampler (one frame: the temporal average pool of compress_time keeps the frame as it is)
-            S2V_TRY(launch_dense_to_padded(v->dense[cur], 1, H, W, s.up.cin, s.up.pad, 0, v->dtype, st));
-            S2V_TRY(run_conv_down(v, s.up, H, W, v->dense[t1], st));
+        if (s.has_up) {  // downsampler: the temporal average pool (compress_time, more than one frame) is fused into the operand write
+            if (s.compress_time && F > 1) {
+                S2V_TRY(launch_time_pool_to_padded(v->dense[cur], F, H, W, s.up.cin, s.up.pad, v->dtype, st));
+                F = down_frames(F, 1);
+            } else {
+                S2V_TRY(launch_dense_to_padded(v->dense[cur], F, H, W, s.up.cin, s.up.pad, 0, v->dtype, st));
+            }
+            S2V_TRY(run_conv_down(v, s.up, F, H, W, v->dense[t1], st));
             std::swap(cur, t1);
             H /= 2; W /= 2;
         }
     }
-    S2V_TRY(run_gn_plain(v, v->norm_out, v->dense[cur], H, W, v->conv_out.pad, 2, st));
-    S2V_TRY(run_conv(v, v->conv_out, 1, H, W, true, EPI_BIAS, nullptr, v->dense[t1], st));
-    return launch_to_ncfhw(v->dense[t1], 1, H, W, 2 * v->Cz, dst, 1, 0, v->dtype, st);
+    S2V_TRY(run_gn_plain(v, v->norm_out, v->dense[cur], F, H, W, v->conv_out.pad, 2, st));
+    S2V_TRY(run_conv(v, v->conv_out, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st));
+    *frames_out = F;
+    return launch_to_ncfhw(v->dense[t1], F, H, W, 2 * v->Cz, dst, Fl, f0, v->dtype, st);
+}
+
+// every frame batch of one window, conv caches threaded from batch to batch (each spatial tile has its own batches and caches)
+static int encode_window(s2v_vae* v, const void* video, int Fv, int Himg, int Wimg, int y0, int x0, int th, int tw, char* dst, int Fl,
+                         hipStream_t st) {
+    S2V_TRY(set_layout(v, th, tw, st));
+    int f0 = 0;
+    bool first = true;
+    for (auto b : enc_frame_batches(Fv)) {
+        int fo = 0;
+        S2V_TRY(encode_batch(v, video, Fv, b.s, b.e - b.s, Himg, Wimg, y0, x0, th, tw, first, dst, Fl, f0, &fo, st));
+        f0 += fo;
+        first = false;
+    }
+    return 0;
 }
 
 struct EncTileGeo { int ts_h, ts_w, ov_h, ov_w, bl_h, bl_w, lim_h, lim_w; };
@@ -974,19 +1035,17 @@ extern "C" int s2v_vae_encode_shape(s2v_vae* v, int32_t H, int32_t W, int32_t ti
     return 0;
 }
 
-extern "C" int s2v_vae_encode(s2v_vae* v, const void* image, int32_t H, int32_t W, int32_t tiling, void* moments,
-                              s2v_stream stream) {
-    S2V_REQUIRE(v && image && moments, "s2v_vae_encode: null argument");
-    S2V_REQUIRE(v->encoder, "s2v_vae_encode: this handle holds the decoder (use s2v_vae_enc_create)");
-    S2V_REQUIRE(v->finalized, "s2v_vae_encode: weights not finalized");
+static int encode_video(s2v_vae* v, const void* video, int F, int H, int W, int tiling, void* moments, hipStream_t st) {
     const int sc = spatial_scale(v);
-    hipStream_t st = (hipStream_t)stream;
+    const int Fl = enc_latent_frames(v, F);
+    int fb_max = 0;
+    for (auto b : enc_frame_batches(F)) fb_max = std::max(fb_max, b.e - b.s);
     EncTileGeo t = enc_tile_geo(v);
     const bool tiled = tiling && (W > t.ts_w || H > t.ts_h);
     if (!tiled) {
         S2V_REQUIRE(H % sc == 0 && W % sc == 0, "s2v_vae_encode: image sides must be multiples of the spatial compression");
-        S2V_TRY(enc_prepare(v, H, W));
-        return encode_window(v, image, H, W, 0, 0, H, W, (char*)moments, st);
+        S2V_TRY(enc_prepare(v, H, W, fb_max));
+        return encode_window(v, video, F, H, W, 0, 0, H, W, (char*)moments, Fl, st);
     }
     S2V_REQUIRE(t.ov_h > 0 && t.ov_w > 0, "s2v_vae_encode: degenerate tile overlap");
     std::vector<int> is, js;
@@ -994,10 +1053,11 @@ extern "C" int s2v_vae_encode(s2v_vae* v, const void* image, int32_t H, int32_t 
     for (int j = 0; j < W; j += t.ov_w) js.push_back(j);
     for (int i : is) S2V_REQUIRE(std::min(t.ts_h, H - i) % sc == 0, "s2v_vae_encode: tile height not a multiple of the spatial compression");
     for (int j : js) S2V_REQUIRE(std::min(t.ts_w, W - j) % sc == 0, "s2v_vae_encode: tile width not a multiple of the spatial compression");
-    S2V_TRY(enc_prepare(v, std::min(t.ts_h, H), std::min(t.ts_w, W)));
+    S2V_TRY(enc_prepare(v, std::min(t.ts_h, H), std::min(t.ts_w, W), fb_max));
     const size_t nt = is.size() * js.size();
     const int C = 2 * v->Cz;
-    bool realloc_tiles = v->tiles.size() != nt;
+    // per-tile moments [2Cz][Fl][th/s][tw/s] (re-allocated only when the tiling or the latent frame count changes)
+    bool realloc_tiles = v->tiles.size() != nt || v->tiles_F != Fl;
     for (size_t k = 0; !realloc_tiles && k < nt; ++k) {
         const int th = std::min(t.ts_h, H - is[k / js.size()]) / sc, tw = std::min(t.ts_w, W - js[k % js.size()]) / sc;
         if (v->tile_h[k] != th || v->tile_w[k] != tw) realloc_tiles = true;
@@ -1009,13 +1069,17 @@ extern "C" int s2v_vae_encode(s2v_vae* v, const void* image, int32_t H, int32_t 
         for (size_t k = 0; k < nt; ++k) {
             const int th = std::min(t.ts_h, H - is[k / js.size()]) / sc, tw = std::min(t.ts_w, W - js[k % js.size()]) / sc;
             v->tile_h[k] = th; v->tile_w[k] = tw;
-            S2V_CHECK_HIP(hipMalloc((void**)&v->tiles[k], (size_t)C * th * tw * v->esz + 16));
+            S2V_CHECK_HIP(hipMalloc((void**)&v->tiles[k], (size_t)C * Fl * th * tw * v->esz + 16));
         }
+        v->tiles_F = Fl;
     }
     for (size_t k = 0; k < nt; ++k)
-        S2V_TRY(encode_window(v, image, H, W, is[k / js.size()], js[k % js.size()], v->tile_h[k] * sc, v->tile_w[k] * sc, v->tiles[k], st));
+        S2V_TRY(encode_window(v, video, F, H, W, is[k / js.size()], js[k % js.size()], v->tile_h[k] * sc, v->tile_w[k] * sc, v->tiles[k],
+                              Fl, st));
     int32_t ho, wo;
     S2V_TRY(s2v_vae_encode_shape(v, H, W, 1, &ho, &wo));
+    // latent-space blends over every latent frame: a tile is [C * Fl] planes of th x tw
+    const int CF = C * Fl;
     int y0 = 0;
     for (size_t r = 0; r < is.size(); ++r) {
         int x0 = 0, ch = 0;
@@ -1025,21 +1089,48 @@ extern "C" int s2v_vae_encode(s2v_vae* v, const void* image, int32_t H, int32_t 
             if (r > 0) {
                 const size_t ka = (r - 1) * js.size() + c;
                 const int E = std::min(std::min(v->tile_h[ka], Ht), t.bl_h);
-                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, C, E, 1, v->dtype, st));
+                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, CF, E, 1, v->dtype, st));
             }
             if (c > 0) {
                 const size_t ka = k - 1;
                 const int E = std::min(std::min(v->tile_w[ka], Wt), t.bl_w);
-                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, C, E, 0, v->dtype, st));
+                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, CF, E, 0, v->dtype, st));
             }
             ch = std::min(Ht, t.lim_h);
             const int cw = std::min(Wt, t.lim_w);
-            S2V_TRY(launch_paste(v->tiles[k], Ht, Wt, ch, cw, moments, ho, wo, y0, x0, C, v->dtype, st));
+            S2V_TRY(launch_paste(v->tiles[k], Ht, Wt, ch, cw, moments, ho, wo, y0, x0, CF, v->dtype, st));
             x0 += cw;
         }
         y0 += ch;
     }
     return 0;
+}
+
+extern "C" int s2v_vae_encode(s2v_vae* v, const void* image, int32_t H, int32_t W, int32_t tiling, void* moments,
+                              s2v_stream stream) {
+    S2V_REQUIRE(v && image && moments, "s2v_vae_encode: null argument");
+    S2V_REQUIRE(v->encoder, "s2v_vae_encode: this handle holds the decoder (use s2v_vae_enc_create)");
+    S2V_REQUIRE(v->finalized, "s2v_vae_encode: weights not finalized");
+    return encode_video(v, image, 1, H, W, tiling, moments, (hipStream_t)stream);
+}
+
+extern "C" int s2v_vae_encode_video_shape(s2v_vae* v, int32_t F, int32_t H, int32_t W, int32_t tiling, int32_t* Fl, int32_t* h,
+                                          int32_t* w) {
+    S2V_REQUIRE(v && v->encoder && Fl && h && w, "s2v_vae_encode_video_shape: bad argument");
+    S2V_REQUIRE(enc_frames_ok(F), "s2v_vae_encode_video_shape: the frame count must be 1 or 8k + 1");
+    S2V_TRY(s2v_vae_encode_shape(v, H, W, tiling, h, w));
+    *Fl = enc_latent_frames(v, F);
+    return 0;
+}
+
+extern "C" int s2v_vae_encode_video(s2v_vae* v, const void* video, int32_t F, int32_t H, int32_t W, int32_t tiling, void* moments,
+                                    s2v_stream stream) {
+    S2V_REQUIRE(v && video && moments, "s2v_vae_encode_video: null argument");
+    S2V_REQUIRE(v->encoder, "s2v_vae_encode_video: this handle holds the decoder (use s2v_vae_enc_create)");
+    S2V_REQUIRE(v->finalized, "s2v_vae_encode_video: weights not finalized");
+    S2V_REQUIRE(enc_frames_ok(F), "s2v_vae_encode_video: the frame count must be 1 or 8k + 1");
+    S2V_REQUIRE(H >= 1 && W >= 1, "s2v_vae_encode_video: bad geometry");
+    return encode_video(v, video, F, H, W, tiling, moments, (hipStream_t)stream);
 }
 
 extern "C" int s2v_vae_gaussian_sample(const void* moments, const void* noise, int32_t latent_channels, int64_t n_spatial, void* out,

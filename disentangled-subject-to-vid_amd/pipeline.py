@@ -54,16 +54,52 @@ class S2VPipeline:
             latents = latents.to(device)
         return latents * self.scheduler.init_noise_sigma
 
+    @staticmethod
+    def get_timesteps(num_inference_steps, timesteps, strength, order=1):
+        """pipeline_cogvideox_video2video.py:409-415: keep the last int(n * strength) of the n timesteps"""
+        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+        t_start = max(num_inference_steps - init_timestep, 0)
+        return timesteps[t_start * order:], num_inference_steps - t_start
+
+    def prepare_video_latents(self, video, dtype, device, generator, timestep):
+        """pipeline_cogvideox_video2video.py:345-398 for one video: the posterior sample of the encoded video, then the noise, both drawn
+        from `generator` in that order; add_noise(scaling_factor * z0, noise, timestep) * init_noise_sigma -> [1,Fl,C,h,w]"""
+        vae = self.vae
+        z0 = vae.encode(video).latent_dist.sample(generator)              # [1,C,Fl,h,w]
+        # the scaling as the reference writes it (and as video_generate.reference_latents does): torch's scalar semantics for the dtype
+        z0 = vae.config.scaling_factor * z0.to(dtype).permute(0, 2, 1, 3, 4).contiguous()  # [1,Fl,C,h,w]
+        gdev = generator.device if generator is not None else device
+        noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
+        latents = self.scheduler.add_noise(z0.to(device), noise, timestep)
+        return latents * self.scheduler.init_noise_sigma
+
     @torch.no_grad()
     def __call__(self, prompt_embeds=None, negative_prompt_embeds=None, ref_img_states=None, height=480, width=720,
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
-                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None):
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
+                 video=None, strength=0.8):
         """cfg_parallel: a dist.CfgPair -- this process runs ONE sample of the CFG pair (slot 0: negative prompt, slot 1: prompt) on its GPU and its
         peer the other; every rank of the pair passes the SAME arguments (embeddings, reference latent, latents or an equally seeded generator) and
         returns the same latents / video bit for bit.  fused mode only.
         ulysses: a dist.UlyssesGroup -- the group's ranks share every step of this video (both samples of the CFG pair, the rows of each stream
-        split over the ranks, attention sharded by heads); same arguments on every rank, same latents back.  fused mode only, not with cfg_parallel."""
+        split over the ranks, attention sharded by heads); same arguments on every rank, same latents back.  fused mode only, not with cfg_parallel.
+        video: video-to-video (pipeline_cogvideox_video2video.py): [1,3,F,H,W] in [-1,1] with F = 1 or 8k + 1 and H x W = height x width.  The
+        loop starts from the encoded video noised to the first of the last int(num_inference_steps * strength) timesteps; num_frames comes
+        from the video.  strength applies only together with a video (text-to-video calls run every timestep, as before)."""
+        if strength < 0 or strength > 1:
+            raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+        if video is not None:
+            if latents is not None:
+                raise ValueError("Only one of `video` or `latents` should be provided")
+            if self.vae is None:
+                raise ValueError("video-to-video encodes the video: construct the pipeline with a `vae`")
+            if video.ndim != 5 or video.shape[0] != 1 or video.shape[1] != 3:
+                raise ValueError(f"`video` must be [1, 3, F, H, W], got {tuple(video.shape)}")
+            if (video.shape[3], video.shape[4]) != (height, width):
+                raise ValueError(f"`video` is {video.shape[3]}x{video.shape[4]} but height x width is {height}x{width}: resizing stays "
+                                 "with the caller")
+            num_frames = video.shape[2]
         if num_frames > 49:
             raise ValueError("The number of frames must be less than or equal to 49 due to static positional embeddings.")
         self.check_inputs(height, width, prompt_embeds, negative_prompt_embeds)
@@ -86,7 +122,13 @@ class S2VPipeline:
         text = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(dev, dt)
         sch.set_timesteps(num_inference_steps, device="cpu")
         timesteps = sch.timesteps
-        latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents).to(dt).contiguous()
+        if video is not None:
+            timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, timesteps, strength, sch.order)
+            if len(timesteps) == 0:
+                raise ValueError(f"strength {strength} keeps none of the {sch.num_inference_steps} timesteps")
+            latents = self.prepare_video_latents(video, dt, dev, generator, timesteps[:1]).to(dt).contiguous()
+        else:
+            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents).to(dt).contiguous()
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
         ref = ref_img_states.to(dev, dt)
         is_dpm = isinstance(sch, CogVideoXDPMScheduler)

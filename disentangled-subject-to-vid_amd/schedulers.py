@@ -67,6 +67,29 @@ class _SchedulerBase:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
+    def add_noise_scalars(self, timestep, dtype, device="cpu"):
+        """(alphas_cumprod[t] ** 0.5, (1 - alphas_cumprod[t]) ** 0.5) as add_noise takes them (scheduling_ddim_cogvideox.py:416-425): the
+        fp64 table cast to the sample dtype first, both powers taken in that dtype, on the sample's device as the reference does (torch's
+        fp32 `** 0.5` on the GPU is not the CPU's correctly rounded square root: they differ in the last bit at some timesteps)"""
+        a = torch.as_tensor(self.alphas_cumprod[int(timestep)], dtype=torch.float64).to(device).to(dtype)
+        return float(a**0.5), float((1 - a) ** 0.5)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """scheduler.add_noise (scheduling_ddim_cogvideox.py:405-431; scheduling_dpm_cogvideox.py:442) for one timestep, in the HIP
+        kernel of s2v_add_noise"""
+        t = torch.as_tensor(timesteps).reshape(-1)
+        if t.numel() != 1:
+            raise NotImplementedError("add_noise: one timestep (batch 1)")
+        if original_samples.shape != noise.shape or original_samples.dtype != noise.dtype:
+            raise ValueError("add_noise: original_samples and noise must have the same shape and dtype")
+        x = original_samples.contiguous()
+        n = noise.to(x.device).contiguous()
+        sa, sb = self.add_noise_scalars(int(t[0]), x.dtype, x.device)
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().s2v_add_noise(_lib.ptr(x), _lib.ptr(n), x.numel(), sa, sb, _lib.ptr(out),
+                                            _lib.DTYPE_OF[x.dtype], _lib.stream_ptr()))
+        return out
+
     def _alphas(self, timestep):
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' first")

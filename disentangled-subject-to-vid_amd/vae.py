@@ -3,7 +3,8 @@
 `enable_tiling / disable_tiling / enable_slicing`, `.eval()` as used by
 pipelines/cogvideo/pipeline_cogvideox.py:185-193,346-351 and src/inference.py:201-207.  Decode runs in
 libs2v_hip.so (csrc/vae.hip, vae_api.hip).  `encode(x).latent_dist.sample()` of ONE reference frame
-(src/video_generate.py:26-38) runs there too once `encoder.*` weights were loaded; video encode raises."""
+(src/video_generate.py:26-38) runs there too once `encoder.*` weights were loaded, and so does the video encode
+of video-to-video (pipeline_cogvideox_video2video.py:345-398) for F = 1 or 8k + 1 frames."""
 import ctypes
 from types import SimpleNamespace
 
@@ -38,11 +39,18 @@ _lib.register_sigs({
     "s2v_vae_encode_shape": [_P, _I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
     "s2v_vae_encode": [_P, _P, _I32, _I32, _I32, _P, _P],
     "s2v_vae_gaussian_sample": [_P, _P, _I32, _I64, _P, _I32, _P],
+    "s2v_vae_encode_video_shape": [_P, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
+    "s2v_vae_encode_video": [_P, _P, _I32, _I32, _I32, _I32, _P, _P],
 })
 
 
+def encode_frames_ok(F):
+    """frame counts the encode takes: one image, or 8k + 1 frames (AutoencoderKLCogVideoX._encode's batches of 8 + F % 8, then 8)"""
+    return F == 1 or (F > 1 and (F - 1) % 8 == 0)
+
+
 class HipDiagonalGaussianDistribution:
-    """DiagonalGaussianDistribution (autoencoders/vae.py:767-790) over device-resident moments [1,2C,1,h,w]."""
+    """DiagonalGaussianDistribution (autoencoders/vae.py:767-790) over device-resident moments [1,2C,F,h,w]."""
 
     def __init__(self, parameters):
         self.parameters = parameters
@@ -215,18 +223,27 @@ class HipAutoencoderKLCogVideoX:
             self._enc_loaded = True
 
     def encode(self, x, return_dict=True):
-        """AutoencoderKLCogVideoX.encode (:1205-1229) for the reference image: x [1,3,1,H,W] in [-1,1] ->
-        `.latent_dist` whose `.sample(generator)` is the [1,C,1,h,w] draw (src/video_generate.py:35-37)."""
+        """AutoencoderKLCogVideoX.encode (:1205-1229): x [1,3,F,H,W] in [-1,1], F = 1 (the reference image,
+        src/video_generate.py:35-37) or 8k + 1 (the input video of video-to-video) -> `.latent_dist` whose `.sample(generator)` is
+        the [1,C,(F-1)/4+1,h,w] draw."""
         if not self._enc or not self._enc_loaded:
             raise _lib.S2VError("encode: no `encoder.*` weights were loaded into this VAE")
-        if x.ndim != 5 or x.shape[0] != 1 or x.shape[2] != 1:
-            raise NotImplementedError("encode takes ONE frame [1,3,1,H,W]: video encode is outside the path")
+        if x.ndim != 5 or x.shape[0] != 1 or x.shape[1] != self.cfg.out_channels:
+            raise NotImplementedError("encode takes one video [1,3,F,H,W]")
+        F = x.shape[2]
+        if not encode_frames_ok(F):
+            raise NotImplementedError(f"encode takes F = 1 or 8k + 1 frames, not {F}")
         x = x.to(self.device, self.dtype).contiguous()
         H, W = x.shape[3], x.shape[4]
-        ho, wo = _I32(), _I32()
-        _lib.check(_lib.lib().s2v_vae_encode_shape(self._enc, H, W, int(self.use_tiling), ctypes.byref(ho), ctypes.byref(wo)))
-        mom = torch.empty((1, 2 * self.cfg.latent_channels, 1, ho.value, wo.value), dtype=self.dtype, device=self.device)
-        _lib.check(_lib.lib().s2v_vae_encode(self._enc, _lib.ptr(x), H, W, int(self.use_tiling), _lib.ptr(mom), _lib.stream_ptr()))
+        fl, ho, wo = _I32(), _I32(), _I32()
+        _lib.check(_lib.lib().s2v_vae_encode_video_shape(self._enc, F, H, W, int(self.use_tiling), ctypes.byref(fl), ctypes.byref(ho),
+                                                         ctypes.byref(wo)))
+        mom = torch.empty((1, 2 * self.cfg.latent_channels, fl.value, ho.value, wo.value), dtype=self.dtype, device=self.device)
+        if F == 1:
+            _lib.check(_lib.lib().s2v_vae_encode(self._enc, _lib.ptr(x), H, W, int(self.use_tiling), _lib.ptr(mom), _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib().s2v_vae_encode_video(self._enc, _lib.ptr(x), F, H, W, int(self.use_tiling), _lib.ptr(mom),
+                                                       _lib.stream_ptr()))
         post = HipDiagonalGaussianDistribution(mom)
         if not return_dict:
             return (post,)

@@ -19,6 +19,22 @@ def reference_latents(vae, ref_image_uint8, generator=None):
     return z.permute(0, 2, 1, 3, 4)                                                # [1,1,C,h,w]
 
 
+def video_latents(vae, video_uint8, generator=None):
+    """the video twin of reference_latents: video_uint8 [F, H, W, 3] uint8 (F = 1 or 8k + 1) -> vae.encode(x).latent_dist.sample(generator)
+    [1, C, (F-1)/4+1, h, w] in the VAE's layout, unscaled (pipeline_cogvideox_video2video.py:384-387 scales and permutes it).  The
+    pixels map to [-1, 1] exactly as the reference image's do; resizing (VideoProcessor.preprocess_video) stays with the caller."""
+    return vae.encode(_video_tensor(vae, video_uint8)).latent_dist.sample(generator)
+
+
+def _video_tensor(vae, video_uint8):
+    """uint8 [F, H, W, 3] -> [1, 3, F, H, W] in [-1, 1] on the VAE's device and dtype"""
+    v = np.asarray(video_uint8)
+    if v.ndim != 4 or v.shape[3] != 3:
+        raise ValueError("video must be [F, H, W, 3]")
+    x = torch.from_numpy(np.ascontiguousarray(v)).float() / 255.0 * 2.0 - 1.0  # [F,H,W,3]
+    return x.permute(3, 0, 1, 2).unsqueeze(0).to(device=vae.device, dtype=vae.dtype)
+
+
 def prompt_embeddings(text_encoder, input_ids, dtype=None):
     """pipeline_cogvideox.py:227-228: text_encoder(ids)[0], cast to the pipeline dtype"""
     emb = text_encoder(input_ids)[0]
@@ -27,7 +43,7 @@ def prompt_embeddings(text_encoder, input_ids, dtype=None):
 
 def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_ids, height=480, width=720, num_frames=49,
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
-              **pipe_kwargs):
+              video_uint8=None, strength=0.8, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
     `output_type` selects ("latent" / "pt").
 
@@ -41,7 +57,17 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
 
     CFG-parallel (round 6): pass `cfg_parallel=dist.CfgPair(...)` through **pipe_kwargs on BOTH ranks of a pair with the same image, ids and seed: each
     rank encodes the reference image and the prompts itself (42 ms + 10 ms, step-invariant), runs its half of every step, and both return the same
-    frames."""
+    frames.
+
+    Video-to-video: video_uint8 [F, H, W, 3] (F = 1 or 8k + 1, H x W = height x width) starts the loop from that video at `strength`
+    (pipeline_cogvideox_video2video.py).  Draw order: the reference image's posterior sample, the video's posterior sample, the noise.
+    The video's frame count replaces num_frames."""
+    if video_uint8 is not None:
+        vs = np.asarray(video_uint8).shape
+        if len(vs) != 4 or vs[3] != 3:
+            raise ValueError("video_uint8 must be [F, H, W, 3]")
+        if (vs[1], vs[2]) != (height, width):
+            raise ValueError(f"video is {vs[1]}x{vs[2]} but the requested size is {height}x{width}: resize it first (preprocess_video)")
     dev = pipe.transformer.device
     generator = None
     if seed is not None:
@@ -50,6 +76,9 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
     ref = reference_latents(pipe.vae, ref_image_uint8, generator)
     pe = prompt_embeddings(text_encoder, prompt_ids, pipe.transformer.dtype)
     ne = prompt_embeddings(text_encoder, negative_prompt_ids, pipe.transformer.dtype)
+    if video_uint8 is not None:
+        pipe_kwargs = dict(pipe_kwargs, video=_video_tensor(pipe.vae, video_uint8), strength=strength)
+        num_frames = np.asarray(video_uint8).shape[0]
     out = pipe(prompt_embeds=pe, negative_prompt_embeds=ne, ref_img_states=ref, height=height, width=width,
                num_frames=num_frames, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                use_dynamic_cfg=use_dynamic_cfg, generator=generator, latents=latents, output_type=output_type,

@@ -164,6 +164,12 @@ S2V_API int s2v_sched_step(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const 
                    const void* latents_in, void* latents_out, float* x0_hist, const void* noise, int64_t n,
                    int32_t dtype, s2v_stream stream);
 
+/* scheduler.add_noise of the video-to-video start (scheduling_ddim_cogvideox.py:405-431, scheduling_dpm_cogvideox.py:442;
+ * pipeline_cogvideox_video2video.py:389): out = sqrt_alpha * sample + sqrt_one_minus_alpha * noise over n elements of `dtype`.  sqrt_alpha / sqrt_one_minus_alpha = alphas_cumprod[t] ** 0.5 and (1 - alphas_cumprod[t]) ** 0.5 taken in
+ * `dtype` by the host (schedulers.py); each product and the sum round to `dtype` like torch's elementwise ops.  out may alias sample. */
+S2V_API int s2v_add_noise(const void* sample, const void* noise, int64_t n, float sqrt_alpha, float sqrt_one_minus_alpha, void* out,
+                          int32_t dtype, s2v_stream stream);
+
 /* One iteration of the denoise loop (custom_cogvideox_pipe.py:241-296): transformer on the CFG pair sharing
  * `latents` [1,F,C,H,W], fp32 CFG, scheduler step, round to the model dtype; latents updated IN PLACE.
  * use_graph != 0 captures the launch sequence into a hipGraph on first use and replays it afterwards
@@ -344,7 +350,7 @@ S2V_API int s2v_vae_postprocess_u8(const void* video, int32_t C, int32_t F, int3
  * Replaces pipe.vae.encode(ref_image).latent_dist.sample() of src/video_generate.py:35-37
  * (AutoencoderKLCogVideoX.encode / _encode / tiled_encode, autoencoder_kl_cogvideox.py:1177-1229,1300-1372;
  * CogVideoXEncoder3D :755-814; CogVideoXDownsample3D downsampling.py:322-353; DiagonalGaussianDistribution
- * autoencoders/vae.py:767-790).  ONE frame: video encode is outside the path.
+ * autoencoders/vae.py:767-790).  ONE frame here; s2v_vae_encode_video below takes a video.
  * s2v_vae_enc_create builds an s2v_vae handle that holds the ENCODER; its weights are loaded with s2v_vae_load_weight
  * under the reference's "encoder.*" state-dict keys, then s2v_vae_finalize; s2v_vae_destroy frees it.
  * cfg: same struct as the decoder (out_channels = image channels 3, latent_channels = 16). */
@@ -355,6 +361,14 @@ S2V_API int s2v_vae_encode_shape(s2v_vae* enc, int32_t H, int32_t W, int32_t til
  * reference's DiagonalGaussianDistribution (mean | logvar); tiling != 0 follows tiled_encode when the image exceeds
  * (sample_height/2, sample_width/2). */
 S2V_API int s2v_vae_encode(s2v_vae* enc, const void* image, int32_t H, int32_t W, int32_t tiling, void* moments, s2v_stream stream);
+/* video encode (AutoencoderKLCogVideoX._encode / tiled_encode for more than one frame, the input of video-to-video,
+ * pipeline_cogvideox_video2video.py:345-398): video [3,F,H,W] (model dtype, [-1,1]) -> moments [2*latent_channels,Fl,h,w],
+ * Fl = (F - 1) / 4 + 1.  F = 1 or 8k + 1; other frame counts are refused.  Frame batches of 8 + F % 8, then 8, frames with the
+ * causal convolutions' caches threaded through them; with tiling every spatial tile runs its own batches over all frames and the
+ * latent-space blends apply to every latent frame.  F = 1 gives the bits of s2v_vae_encode. */
+S2V_API int s2v_vae_encode_video_shape(s2v_vae* enc, int32_t F, int32_t H, int32_t W, int32_t tiling, int32_t* Fl, int32_t* h, int32_t* w);
+S2V_API int s2v_vae_encode_video(s2v_vae* enc, const void* video, int32_t F, int32_t H, int32_t W, int32_t tiling, void* moments,
+                                 s2v_stream stream);
 /* DiagonalGaussianDistribution.sample with the caller's randn: out[c,i] = mean + exp(0.5 * clamp(logvar, -30, 20)) * noise,
  * every operation rounded to `dtype` like the reference's tensor ops; moments [2*C, n_spatial], noise / out [C, n_spatial] */
 S2V_API int s2v_vae_gaussian_sample(const void* moments, const void* noise, int32_t latent_channels, int64_t n_spatial, void* out,
