@@ -8,6 +8,10 @@
     python bench.py --batch 1                              (ONE sample of the CFG pair per step: the half step a GPU of a CFG-parallel pair runs)
     python bench.py --gpus 2 --cfg-parallel                (one video on two GPUs: dist.CfgPair; N even: N / 2 videos in flight)
     python bench.py --dump-outputs DIR                     (also writes the latents the last timed step left to DIR/latents.npy)
+    python bench.py --full                                 (also the eager pass, the roofline, the CFG-parallel projection, the video and the CPU baseline)
+
+A plain run does what its headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.
+Everything else the line can carry is measured only with --full.
 
 --gpus N is a CLAIM the run has to earn: with no torchrun environment the script launches N rank processes itself and refuses
 (non-zero exit) when fewer than N GPUs are visible; with a torchrun environment WORLD_SIZE must equal N.  `value` is computed from
@@ -15,7 +19,7 @@ what the ranks report (sum of their timed steps / max elapsed over ranks), never
 
 One "step" = one iteration of the denoise loop of src/custom_cogvideox_pipe.py:241-296 on one video: the B=2 (CFG pair)
 transformer forward + fp32 CFG + DDIM scheduler step + round to bf16, all inside libs2v_hip.so, inputs resident in
-HBM; the timed region replays it from ONE captured hipGraph (--graph 1, default) and carries no profiling; the eager time and
+HBM; the timed region replays it from ONE captured hipGraph (--graph 1, default) and carries no profiling; with --full the eager time and
 the per-kernel HIP-event durations come from separate passes after it.  Workload (BASELINE.json metric): CogVideoX-5B, 49 frames 480x720 -> latents 13x60x90, N = 226+1350+17550 tokens,
 bf16, synthetic seeded weights (no checkpoints offline).  N > 1: independent replicas, one prompt per GPU, weights
 broadcast once rank0 -> all over RCCL before the timed region; value = total steps/s.
@@ -427,8 +431,9 @@ def dist_selftest(args):
         raise SystemExit(5)
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def parse_args(argv):
+    """the command line; without --full every pass beside the headline figure is switched off, as if --single-mode --no-roofline --no-vae
+    --no-cpu-baseline had been given"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -454,7 +459,19 @@ def main(argv=None):
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned to its caller -- the "
                     "latents [1, F, C, H, W], updated in place -- as DIR/latents.npy (float32, rank 0; at most 12 MB at 720 x 1280). Inputs are "
                     "seeded, so two builds run with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the other launch mode, the per-kernel "
+                    "roofline passes, the CFG-parallel projection, the VAE / T5 / one-video wall clock and the CPU oracle baseline (--single-mode, "
+                    "--no-roofline, --no-vae and --no-cpu-baseline switch single parts off again). Without it a run sets up, warms up, times the "
+                    "steps, writes --dump-outputs and prints the line")
     args = ap.parse_args(argv)
+    if not args.full:
+        args.single_mode = args.no_roofline = args.no_vae = args.no_cpu_baseline = True
+    return args
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
@@ -935,6 +952,7 @@ def main(argv=None):
                        "launcher": "self-spawned" if os.environ.get("S2V_BENCH_SPAWNED") == "1" else ("torchrun env" if env_world is not None else "single process"),
                        "ranks": ranks_info,
                        "one_device_functional_check": True if (one_dev and world > 1) else None,
+                       "full": args.full,   # False: eager_ms_per_step, roofline, wall_clock_per_video and cpu_baseline were not measured
                        "hipgraph": bool(args.graph), "graph_ms_per_step": None if graph_ms is None else round(graph_ms, 2),
                        "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 2),
                        "per_gpu_steps_per_s": round(total_steps / elapsed / n_devices / (1 if args.batch == 2 else 2), 4),

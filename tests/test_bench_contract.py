@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 import torch
@@ -51,6 +52,17 @@ def test_steps_must_be_a_real_count(bench):
         with pytest.raises(SystemExit) as e:
             bench.main(argv)
         assert "--steps must be >= 1" in str(e.value.code)
+
+
+def test_plain_run_leaves_everything_beside_the_headline_to_full(bench):
+    """without --full a run skips the other launch mode, the roofline passes (and with them the CFG-parallel projection), the video and the
+    CPU baseline; --full runs them all, and the --no-* / --single-mode flags still switch single parts off inside it"""
+    a = bench.parse_args(["--steps", "3", "--warmup", "1"])
+    assert not a.full and a.single_mode and a.no_roofline and a.no_vae and a.no_cpu_baseline
+    a = bench.parse_args(["--full"])
+    assert a.full and not (a.single_mode or a.no_roofline or a.no_vae or a.no_cpu_baseline)
+    a = bench.parse_args(["--full", "--no-vae", "--single-mode"])
+    assert a.no_vae and a.single_mode and not (a.no_roofline or a.no_cpu_baseline)
 
 
 def test_value_is_never_the_flag_times_anything():
@@ -127,9 +139,44 @@ def test_cfg_parallel_pair_on_one_device_reports_video_steps():
 def test_batch_1_reports_the_half_step_as_the_projection():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "S2V_BENCH_ONE_DEVICE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "1", "--steps", "3", "--warmup", "1", "--workload",
-                        "cogvideox-2b-9x256x256", "--no-roofline", "--single-mode"], env=env, capture_output=True, text=True, timeout=900)
+                        "cogvideox-2b-9x256x256", "--full", "--no-roofline", "--single-mode"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["config"]["samples_per_gpu_per_step"] == 1 and line["config"]["projected_cfg_parallel_ms"] == line["ms_per_step"]
     assert abs(line["value"] - 0.5e3 / line["ms_per_step"]) <= 0.02 * line["value"]   # half a step per GPU-step: two GPUs make one step
     assert "cpu_baseline" not in line and line["wall_clock_per_video"] is None
+
+
+def _bench_line(args, timeout):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "S2V_BENCH_ONE_DEVICE")}
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=timeout)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]), wall
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_little_else():
+    """the flagship workload without --full: the headline fields, none of the extras, and at most 30 s of the process outside its steps"""
+    line, wall = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1"], 600)
+    assert line["metric"].startswith("denoise steps/sec (CogVideoX-5B") and line["unit"] == "steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["steps"] == 2 and abs(line["value"] - 1e3 / line["ms_per_step"]) <= 0.02 * line["value"]
+    cfg = line["config"]
+    assert cfg["full"] is False and cfg["outputs_finite"] and cfg["eager_ms_per_step"] is None and cfg["cfg_parallel_projection"] is None
+    assert line["roofline"] is None and line["wall_clock_per_video"] is None and "cpu_baseline" not in line
+    outside = wall - (line["steps"] + line["warmup"]) * line["ms_per_step"] / 1e3
+    print(f"MEASURED plain run: {wall:.1f} s wall, {outside:.1f} s outside the steps")
+    assert outside <= 30.0, outside
+
+
+@pytest.mark.gpu
+def test_full_run_still_measures_the_extras():
+    """--full on the configs[0] geometry: the other launch mode, the roofline with its per-kernel table, the CFG-parallel projection, the
+    video and the CPU baseline are all in the line"""
+    line, _ = _bench_line(["--steps", "2", "--warmup", "1", "--workload", "cogvideox-2b-9x256x256", "--full"], 900)
+    cfg = line["config"]
+    assert cfg["full"] is True and cfg["eager_ms_per_step"] > 0 and cfg["cfg_parallel_projection"]["b1_step_ms"] > 0
+    assert "attention" in line["roofline"]["per_kernel"] and line["roofline"]["calibrated_peak"] > 0
+    assert line["wall_clock_per_video"]["s_per_video_measured"] > 0 and line["wall_clock_per_video"]["frames_finite"]
+    assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["vae_decode"]["value"] > 0

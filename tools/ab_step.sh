@@ -24,7 +24,7 @@ else
   shift
   for rep in 1 2; do
     for d in tools/ababl/*/; do
-      S2V_LIB=$d/libs2v_hip.so python bench.py --steps 8 --warmup 2 --no-vae --no-cpu-baseline --single-mode "$@" 2>/dev/null | python -c "
+      S2V_LIB=$d/libs2v_hip.so python bench.py --full --steps 8 --warmup 2 --no-vae --no-cpu-baseline --single-mode "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); pk=d['roofline']['per_kernel']
 print('%-14s %7.2f ms/step  ' % ('$(basename $d)', d['ms_per_step']) + '  '.join('%s %.3f' % (k.replace('gemm_',''), v['avg_ms']) for k, v in pk.items() if 'avg_ms' in v and k in ('gemm_qkv','attention','gemm_out','gemm_ff1_gelu','gemm_ff2')))"

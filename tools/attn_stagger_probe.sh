@@ -6,7 +6,7 @@ export S2V_LIB="$(cd "$(dirname "$0")/.." && pwd)/disentangled-subject-to-vid_am
 export TMPDIR=/tmp S2V_BENCH_SKIP_PFMT=1 S2V_BENCH_SKIP_PARITY_PASS=1
 W=${W:-cogvideox-5b-fp8-49x720x1280}
 for s in ${STAGGERS:-0 26 52 104 208}; do
-  S2V_ATTN_STAGGER=$s python bench.py --steps 2 --warmup 1 --workload $W --no-cpu-baseline --no-vae 2>/dev/null | tail -1 | python -c "
+  S2V_ATTN_STAGGER=$s python bench.py --full --steps 2 --warmup 1 --workload $W --no-cpu-baseline --no-vae 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); a=d['roofline']['per_kernel']['attention']; print('stagger $s: step', d['ms_per_step'], 'ms; attention', a['avg_ms'], 'ms', a['tflops'], 'TFLOP/s, clock', a.get('shader_clock_mhz'))"
 done
 for s in ${PMC_STAGGERS:-0 52}; do
