@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("S2V_LIB") or os.path.join(_HERE, "libs2v_hip.so")  # 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 TORCH_DTYPE = {DTYPE_F32: torch.float32, DTYPE_BF16: torch.bfloat16, DTYPE_F16: torch.float16}
 DTYPE_OF = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}
+# ModelConfigC.reserved[0]: the kind of context s2v_create makes (include/s2v_hip.h, S2V_CTX_*)
+CTX_MODEL, CTX_ATTN_WEIGHTS, CTX_ATTN_WORKSPACE = 0, 1, 2
 
 
 class ModelConfigC(ctypes.Structure):
@@ -52,6 +54,8 @@ _SIGS = {
     "s2v_transformer_forward": [_P, _P, _I64, _P, _P, _P],
     "s2v_block_forward": [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "s2v_attn_forward": [_P, _I32, _P, _P, _P, _P, _P],
+    "s2v_attn_forward_with": [_P, _P, _I32, _P, _P, _P, _P, _P],
+    "s2v_device_bytes": [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     "s2v_sched_step": [_P, ctypes.POINTER(SchedCoefC), _P, _I32, _P, _P, _P, _P, _I64, _I32, _P],
     "s2v_add_noise": [_P, _P, _I64, _F, _F, _P, _I32, _P],
     "s2v_denoise_step": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],

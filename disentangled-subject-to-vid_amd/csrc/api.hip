@@ -45,6 +45,7 @@ struct GraphKey {
 
 struct s2v_ctx {
     s2v_model_config cfg;
+    int kind = S2V_CTX_MODEL;    // cfg.reserved[0]: a model, attention weights only, or geometry + workspace only (include/s2v_hip.h)
     int D = 0, L = 0, dtype = 0, esz = 0, temb = 0;
     bool mfma = false;
     int attn_order = 0;          // AttnArgs::order (S2V_ATTN_ORDER at s2v_create of the DIAGNOSTICS build: an experiment knob, 0 in the product)
@@ -176,8 +177,75 @@ static Slot* add_slot(s2v_ctx* c, const std::string& name, char* dst, int64_t ro
     return &c->slots[name];
 }
 
+// the attn1 keys of layer l: fused QKV [rup(3D, 256)][D] + bias [3D], per-head LayerNorm(64) of q and k, out-projection [Dp][D] + bias
+static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
+    const int64_t D = c->D, E = c->esz;
+    char nm[160];
+#define NM(fmt) (snprintf(nm, sizeof(nm), "transformer_blocks.%d." fmt, l), std::string(nm))
+    add_slot(c, NM("attn1.to_q.weight"), w.wqkv, D, D, D);
+    add_slot(c, NM("attn1.to_k.weight"), w.wqkv + D * D * E, D, D, D);
+    add_slot(c, NM("attn1.to_v.weight"), w.wqkv + 2 * D * D * E, D, D, D);
+    add_slot(c, NM("attn1.to_q.bias"), w.bqkv, 1, D, D);
+    add_slot(c, NM("attn1.to_k.bias"), w.bqkv + D * E, 1, D, D);
+    add_slot(c, NM("attn1.to_v.bias"), w.bqkv + 2 * D * E, 1, D, D);
+    add_slot(c, NM("attn1.norm_q.weight"), w.nq_w, 1, 64, 64);
+    add_slot(c, NM("attn1.norm_q.bias"), w.nq_b, 1, 64, 64);
+    add_slot(c, NM("attn1.norm_k.weight"), w.nk_w, 1, 64, 64);
+    add_slot(c, NM("attn1.norm_k.bias"), w.nk_b, 1, 64, 64);
+    add_slot(c, NM("attn1.to_out.0.weight"), w.wo, D, D, D);
+    add_slot(c, NM("attn1.to_out.0.bias"), w.bo, 1, D, D);
+#undef NM
+}
+
+// S2V_CTX_ATTN_WEIGHTS: an arena of num_layers x the attn1 weights, carved exactly as a model carves them (zero pad rows included), so that a
+// workspace context runs them through the same GEMM tiles; no stream, event, scratch or workspace of its own
+static int create_attn_weights(s2v_ctx* c) {
+    if (c->D > 4096 || c->D % 8 != 0) return s2v_fail(__FILE__, __LINE__, "s2v_create: bad inner dim", -1);
+    const int64_t D = c->D, E = c->esz, Dp = rup(D, 256);
+    int64_t off = 0;
+    auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
+    struct Offs { int64_t wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo; };
+    std::vector<Offs> lo(c->L);
+    for (Offs& o : lo) {
+        o.wqkv = carve(rup(3 * D, 256) * D); o.bqkv = carve(3 * D);
+        o.nq_w = carve(64); o.nq_b = carve(64); o.nk_w = carve(64); o.nk_b = carve(64);
+        o.wo = carve(Dp * D); o.bo = carve(D);
+    }
+    c->arena_bytes = off;
+    S2V_CHECK_HIP(hipMalloc((void**)&c->arena, c->arena_bytes));
+    S2V_CHECK_HIP(hipMemset(c->arena, 0, c->arena_bytes));
+    char* A = c->arena;
+    c->layers.assign(c->L, LayerW{});
+    for (int l = 0; l < c->L; ++l) {
+        const Offs& o = lo[l];
+        LayerW& w = c->layers[l];
+        w.wqkv = A + o.wqkv; w.bqkv = A + o.bqkv; w.nq_w = A + o.nq_w; w.nq_b = A + o.nq_b;
+        w.nk_w = A + o.nk_w; w.nk_b = A + o.nk_b; w.wo = A + o.wo; w.bo = A + o.bo;
+        add_attn_slots(c, l, w);
+    }
+    return 0;
+}
+
+// the host-side scratch every context that runs launches needs: step scalars, the pinned staging ring, the capture stream
+static int create_tail(s2v_ctx* c, s2v_ctx** out) {
+    hipMalloc((void**)&c->t_dev, 4 * sizeof(float));
+    hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef));
+    hipHostMalloc((void**)&c->ring, sizeof(s2v_ctx::Stage) * RING);
+    hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
+    if (!c->t_dev || !c->coef_dev || !c->ring || !c->cap_stream) {
+        s2v_destroy(c);
+        return s2v_fail(__FILE__, __LINE__, "s2v_create: allocation failed", -2);
+    }
+    *out = c;
+    return 0;
+}
+
 extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     S2V_REQUIRE(cfg && out, "s2v_create: null argument");
+    const int kind = cfg->reserved[0];
+    S2V_REQUIRE(kind == S2V_CTX_MODEL || kind == S2V_CTX_ATTN_WEIGHTS || kind == S2V_CTX_ATTN_WORKSPACE,
+                "s2v_create: reserved[0] must be S2V_CTX_MODEL, S2V_CTX_ATTN_WEIGHTS or S2V_CTX_ATTN_WORKSPACE");
+    S2V_REQUIRE(kind == S2V_CTX_MODEL || cfg->weight_format == 0, "s2v_create: attention-only contexts hold the model dtype (weight_format 0)");
     S2V_REQUIRE(cfg->dtype == S2V_DTYPE_F32 || cfg->dtype == S2V_DTYPE_BF16 || cfg->dtype == S2V_DTYPE_F16, "s2v_create: unsupported dtype");
     S2V_REQUIRE(cfg->patch_size == 2, "s2v_create: patch_size must be 2");
     S2V_REQUIRE(cfg->num_layers > 0 && cfg->num_heads > 0, "s2v_create: bad model size");
@@ -189,10 +257,17 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     c->dtype = cfg->dtype;
     c->esz = cfg->dtype == S2V_DTYPE_F32 ? 4 : 2;
     c->temb = cfg->time_embed_dim;
+    c->kind = kind;
     {
         int dev = 0, ncu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
             c->num_cus = ncu;
+    }
+    if (kind == S2V_CTX_ATTN_WEIGHTS) {
+        const int r = create_attn_weights(c);
+        if (r) { s2v_destroy(c); return r; }
+        *out = c;
+        return 0;
     }
     if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -258,6 +333,7 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         q.q_qkv = carve_b(rup(3 * D, 256) * D); q.q_o = carve_b(Dp * D); q.q_1 = carve_b(rup(4 * D, 256) * D); q.q_2 = carve_b(Dp * 4 * D);
         q.s_qkv = carve_b(rup(3 * D, 256) * 4); q.s_o = carve_b(Dp * 4); q.s_1 = carve_b(rup(4 * D, 256) * 4); q.s_2 = carve_b(Dp * 4);
     }
+    if (kind == S2V_CTX_ATTN_WORKSPACE) return create_tail(c, out);  // no arena: the weights come from another context (s2v_attn_forward_with)
     c->arena_bytes = off;
     hipError_t e = hipMalloc((void**)&c->arena, c->arena_bytes);
     if (e != hipSuccess) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, hipGetErrorString(e), -2); }
@@ -283,18 +359,7 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         add_slot(c, NM("norm1.norm.bias"), w.ln1_b, 1, D, D);
         add_slot(c, NM("norm2.norm.weight"), w.ln2_w, 1, D, D);
         add_slot(c, NM("norm2.norm.bias"), w.ln2_b, 1, D, D);
-        add_slot(c, NM("attn1.to_q.weight"), w.wqkv, D, D, D);
-        add_slot(c, NM("attn1.to_k.weight"), w.wqkv + D * D * E, D, D, D);
-        add_slot(c, NM("attn1.to_v.weight"), w.wqkv + 2 * D * D * E, D, D, D);
-        add_slot(c, NM("attn1.to_q.bias"), w.bqkv, 1, D, D);
-        add_slot(c, NM("attn1.to_k.bias"), w.bqkv + D * E, 1, D, D);
-        add_slot(c, NM("attn1.to_v.bias"), w.bqkv + 2 * D * E, 1, D, D);
-        add_slot(c, NM("attn1.norm_q.weight"), w.nq_w, 1, 64, 64);
-        add_slot(c, NM("attn1.norm_q.bias"), w.nq_b, 1, 64, 64);
-        add_slot(c, NM("attn1.norm_k.weight"), w.nk_w, 1, 64, 64);
-        add_slot(c, NM("attn1.norm_k.bias"), w.nk_b, 1, 64, 64);
-        add_slot(c, NM("attn1.to_out.0.weight"), w.wo, D, D, D);
-        add_slot(c, NM("attn1.to_out.0.bias"), w.bo, 1, D, D);
+        add_attn_slots(c, l, w);
         add_slot(c, NM("ff.net.0.proj.weight"), w.w1, 4 * D, D, D);
         add_slot(c, NM("ff.net.0.proj.bias"), w.b1, 1, 4 * D, 4 * D);
         add_slot(c, NM("ff.net.2.weight"), w.w2, D, 4 * D, 4 * D);
@@ -325,17 +390,7 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     add_slot(c, "norm_out.linear.bias", c->mod_b + (int64_t)2 * L * MC * D * E, 1, 2 * D, 2 * D);
     add_slot(c, "proj_out.weight", c->po_w, Cout, D, D);
     add_slot(c, "proj_out.bias", c->po_b, 1, Cout, Cout);
-
-    hipMalloc((void**)&c->t_dev, 4 * sizeof(float));
-    hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef));
-    hipHostMalloc((void**)&c->ring, sizeof(s2v_ctx::Stage) * RING);
-    hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
-    if (!c->t_dev || !c->coef_dev || !c->ring || !c->cap_stream) {
-        s2v_destroy(c);
-        return s2v_fail(__FILE__, __LINE__, "s2v_create: allocation failed", -2);
-    }
-    *out = c;
-    return 0;
+    return create_tail(c, out);
 }
 
 extern "C" void s2v_destroy(s2v_ctx* c) {
@@ -425,6 +480,7 @@ extern "C" int s2v_merge_lora(s2v_ctx* c, const char* name, const float* A, cons
 
 extern "C" int s2v_finalize_weights(s2v_ctx* c, s2v_stream stream) {
     S2V_REQUIRE(c, "s2v_finalize_weights: null context");
+    S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_finalize_weights: a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
     for (auto& kv : c->slots) {
         if (!kv.second.loaded) {
             std::string m = std::string("s2v_finalize_weights: tensor was never loaded: ") + kv.first;
@@ -475,6 +531,7 @@ extern "C" int s2v_weight_arena(s2v_ctx* c, void** dev_ptr, int64_t* bytes) {
 // a replica that received the arena by broadcast marks itself loaded
 extern "C" int s2v_mark_weights_loaded(s2v_ctx* c) {
     S2V_REQUIRE(c, "null context");
+    S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_mark_weights_loaded: a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
     for (auto& kv : c->slots) kv.second.loaded = true;
     c->finalized = true;
     return 0;
@@ -489,6 +546,7 @@ static inline void shard_range(int n, int p, int r, int* begin, int* len) {
 
 extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     S2V_REQUIRE(c, "null context");
+    S2V_REQUIRE(c->kind == S2V_CTX_MODEL, "s2v_set_shard: attention-only contexts (S2V_CTX_ATTN_*) are not sharded");
     S2V_REQUIRE(world >= 1 && rank >= 0 && rank < world, "s2v_set_shard: need world >= 1 and 0 <= rank < world");
     S2V_REQUIRE(c->cfg.num_heads % world == 0, "s2v_set_shard: the world size must divide num_heads (attention runs num_heads / world heads per rank)");
     // fp8: the attention output reaches the out-projection as MX e4m3 whose scales are dwords of four 32-column blocks = one 128-column K-tile =
@@ -511,6 +569,7 @@ static bool attn_mx_out(const s2v_ctx* c);
 
 extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int32_t H, int32_t W) {
     S2V_REQUIRE(c, "null context");
+    S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WEIGHTS, "s2v_set_geometry: an attention-weights context (S2V_CTX_ATTN_WEIGHTS) never carves a workspace");
     S2V_REQUIRE(B >= 1 && B <= 4, "s2v_set_geometry: batch must be 1..4");
     S2V_REQUIRE(T >= 0 && F >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "s2v_set_geometry: bad geometry");
     if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
@@ -816,9 +875,9 @@ static bool attn_mx_out(const s2v_ctx* c) {
 #endif
     return mx;
 }
-static int run_attention(s2v_ctx* c, int l, hipStream_t st, bool prequant = false) {
+// w: the layer's weights -- c's own, or another context's of the same dtype / heads / weight_format (s2v_attn_forward_with)
+static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false) {
     // Xn -> QKV -> (qk-norm, rope, V^T) -> attention -> Xn (reused as the attention output buffer)
-    const LayerW& w = c->layers[l];
     const int D = c->D;
     GemmArgs g{};
     g.A = c->Xn; g.lda = D; g.W = w.wqkv; g.ldw = D; g.bias = w.bqkv;
@@ -975,7 +1034,7 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
         S2V_TRY(block_norm(c, l, half, mod_base, mod_stride, st, &prequant));
         const GemmArgs g = block_gate(c, half, mod_base, mod_stride);
         if (half == 0) {
-            S2V_TRY(run_attention(c, l, st, prequant));
+            S2V_TRY(run_attention(c, c->layers[l], st, prequant));
             S2V_TRY(block_out_proj(c, l, g, st));
         } else {
             S2V_TRY(block_ff(c, l, g, prequant, st));
@@ -1083,13 +1142,9 @@ extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, 
     return 0;
 }
 
-extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
-                                void* out_encoder, s2v_stream stream) {
-    S2V_REQUIRE(c && c->ws && c->finalized, "s2v_attn_forward: geometry and weights required");
-    S2V_REQUIRE(!c->shard, "s2v_attn_forward: a shard context (s2v_set_shard) runs the staged step only");
-    S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_attn_forward: bad layer");
-    S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward: null argument");
-    hipStream_t st = (hipStream_t)stream;
+// the AttnProcessor seam on c's geometry and workspace with the weights w (c's own layer, or another context's)
+static int attn_forward_impl(s2v_ctx* c, const LayerW& w, const void* hidden, const void* encoder, void* out_hidden, void* out_encoder,
+                             hipStream_t st) {
     const int D = c->D, B = c->B, TR = c->T + c->R;
     const int64_t E = c->esz;
     for (int b = 0; b < B; ++b) {
@@ -1097,8 +1152,7 @@ extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, c
         S2V_TRY(launch_copy_rows((const char*)encoder + (int64_t)b * TR * D * E, D, nullptr, 0, xb, D, TR, D, c->dtype, st));
         S2V_TRY(launch_copy_rows((const char*)hidden + (int64_t)b * c->V * D * E, D, nullptr, 0, xb + (int64_t)TR * D * E, D, c->V, D, c->dtype, st));
     }
-    S2V_TRY(run_attention(c, layer, st));
-    const LayerW& w = c->layers[layer];
+    S2V_TRY(run_attention(c, w, st));
     GemmArgs g{};
     g.A = c->Xn; g.lda = D; g.W = w.wo; g.ldw = D; g.bias = w.bo; g.C = c->Hb; g.ldc = D; g.M = (int)c->M; g.N = D; g.K = D;
     if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
@@ -1109,6 +1163,36 @@ extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, c
         S2V_TRY(launch_copy_rows(xb, D, nullptr, 0, (char*)out_encoder + (int64_t)b * TR * D * E, D, TR, D, c->dtype, st));
         S2V_TRY(launch_copy_rows(xb + (int64_t)TR * D * E, D, nullptr, 0, (char*)out_hidden + (int64_t)b * c->V * D * E, D, c->V, D, c->dtype, st));
     }
+    return 0;
+}
+
+extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
+                                void* out_encoder, s2v_stream stream) {
+    S2V_REQUIRE(c && c->ws && c->finalized, "s2v_attn_forward: geometry and weights required");
+    S2V_REQUIRE(!c->shard, "s2v_attn_forward: a shard context (s2v_set_shard) runs the staged step only");
+    S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_attn_forward: bad layer");
+    S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward: null argument");
+    return attn_forward_impl(c, c->layers[layer], hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
+}
+
+extern "C" int s2v_attn_forward_with(s2v_ctx* c, const s2v_ctx* wc, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
+                                     void* out_encoder, s2v_stream stream) {
+    S2V_REQUIRE(c && wc, "s2v_attn_forward_with: null context");
+    S2V_REQUIRE(c->ws, "s2v_attn_forward_with: the workspace context has no geometry (s2v_set_geometry)");
+    S2V_REQUIRE(!c->shard && !wc->shard, "s2v_attn_forward_with: a shard context (s2v_set_shard) runs the staged step only");
+    S2V_REQUIRE(wc->finalized && wc->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_attn_forward_with: the weights are not loaded (s2v_finalize_weights)");
+    S2V_REQUIRE(wc->dtype == c->dtype, "s2v_attn_forward_with: the weights context has another dtype");
+    S2V_REQUIRE(wc->cfg.num_heads == c->cfg.num_heads && wc->D == c->D, "s2v_attn_forward_with: the weights context has another num_heads / inner dim");
+    S2V_REQUIRE(wc->cfg.weight_format == c->cfg.weight_format, "s2v_attn_forward_with: the weights context has another weight_format");
+    S2V_REQUIRE(layer >= 0 && layer < (int)wc->layers.size(), "s2v_attn_forward_with: bad layer");
+    S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward_with: null argument");
+    return attn_forward_impl(c, wc->layers[layer], hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
+}
+
+extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
+    S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
+    *arena = c->arena ? c->arena_bytes : 0;
+    *workspace = c->ws ? c->ws_bytes : 0;
     return 0;
 }
 
@@ -1710,6 +1794,7 @@ extern "C" int s2v_op_ff_fp8(const void* x, const void* w1, const void* b1, cons
 // caller that sees more than a fraction of a percent of slow paths on its data switches back with s2v_set_attn_p_format.
 extern "C" int s2v_attn_slow_stats(s2v_ctx* c, uint64_t* slow, uint64_t* total, int32_t reset) {
     S2V_REQUIRE(c && slow && total, "s2v_attn_slow_stats: null argument");
+    S2V_REQUIRE(c->attn_stats, "s2v_attn_slow_stats: an attention-weights context (S2V_CTX_ATTN_WEIGHTS) runs no attention");
     unsigned long long h[512];
     S2V_CHECK_HIP(hipDeviceSynchronize());
     S2V_CHECK_HIP(hipMemcpy(h, c->attn_stats, 4096, hipMemcpyDeviceToHost));

@@ -17,7 +17,10 @@ class _ArenaView:
 
 
 class S2VEngine:
-    def __init__(self, cfg: TransformerConfig, dtype=torch.bfloat16, device="cuda:0", force_simple=False):
+    def __init__(self, cfg: TransformerConfig, dtype=torch.bfloat16, device="cuda:0", force_simple=False, kind=_lib.CTX_MODEL):
+        """kind: _lib.CTX_MODEL (a whole model), or one of the two halves of the model-wide AttnProcessor (include/s2v_hip.h, S2V_CTX_*):
+        CTX_ATTN_WEIGHTS (the attn1 weights of cfg.num_layers blocks, no workspace) / CTX_ATTN_WORKSPACE (geometry, workspace and rotary
+        tables, no weights; runs another engine's weights through attn_forward_with)"""
         if dtype not in _lib.DTYPE_OF:
             raise _lib.S2VError(f"unsupported model dtype {dtype} (float32, bfloat16 and float16 are implemented)")
         if cfg.attention_head_dim != 64:
@@ -42,6 +45,8 @@ class S2VEngine:
         if cfg.attn_p_format not in ("bf16", "f16", "auto"):
             raise _lib.S2VError(f"unknown attn_p_format {cfg.attn_p_format!r} ('bf16', 'f16' or 'auto')")
         c.attn_p_format = 0 if cfg.attn_p_format == "bf16" else 1
+        c.reserved[0] = kind
+        self.kind = kind
         # "auto" (opt-in): start with fp16 P (faster on smooth score distributions) and look at the slow-path census after the first denoise
         # step of a geometry (re-armed by set_geometry); more than AUTO_SLOW_FRACTION of the (wave, KV tile) pairs on the slow path -> bf16 P
         # (threshold 2^64).  The census read synchronises the device (s2v_attn_slow_stats): the deciding step runs eagerly, never inside a
@@ -98,13 +103,20 @@ class S2VEngine:
                 # the reference only reports adapter keys it cannot place (src/inference.py:96-105) and carries on
                 self.unexpected_lora_keys.append(k)
                 continue
-            A2 = A.to(self.device).float().reshape(A.shape[0], -1).contiguous()
-            B2 = B.to(self.device).float().contiguous()
-            _lib.check(_lib.lib().s2v_merge_lora(self._h, k.encode(), _lib.ptr(A2), _lib.ptr(B2), A2.shape[0],
-                                                 float(lora_scale), _lib.stream_ptr()))
-            self._keep += [A2, B2]  # the merge is stream-ordered
+            self.merge_lora(k, A, B, lora_scale)
         if self.unexpected_lora_keys:
             print(f"Loading adapter weights led to unexpected keys not found in the model: {self.unexpected_lora_keys}")
+        self.finalize_weights()
+
+    def merge_lora(self, name, A, B, scale):
+        """W[name] += scale * B A (s2v_merge_lora: A [r, in..] and B [out, r] as fp32, after load_weight(name), before finalize_weights)"""
+        A2 = A.to(self.device).float().reshape(A.shape[0], -1).contiguous()
+        B2 = B.to(self.device).float().contiguous()
+        _lib.check(_lib.lib().s2v_merge_lora(self._h, name.encode(), _lib.ptr(A2), _lib.ptr(B2), A2.shape[0],
+                                             float(scale), _lib.stream_ptr()))
+        self._keep += [A2, B2]  # the merge is stream-ordered
+
+    def finalize_weights(self):
         _lib.check(_lib.lib().s2v_finalize_weights(self._h, _lib.stream_ptr()))
         torch.cuda.synchronize(self.device)
         self._keep.clear()
@@ -130,6 +142,12 @@ class S2VEngine:
 
     def mark_weights_loaded(self):
         _lib.check(_lib.lib().s2v_mark_weights_loaded(self._h))
+
+    def device_bytes(self):
+        """(weight arena, workspace): device bytes the library holds for this context (s2v_device_bytes)"""
+        a, w = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.lib().s2v_device_bytes(self._h, ctypes.byref(a), ctypes.byref(w)))
+        return a.value, w.value
 
     # ---- geometry / tables / conditioning ----------------------------------------------------------------------
     def _bump(self, *kinds):
@@ -249,6 +267,15 @@ class S2VEngine:
         oh, oe = torch.empty_like(hidden), torch.empty_like(encoder)
         _lib.check(_lib.lib().s2v_attn_forward(self._h, layer, _lib.ptr(hidden), _lib.ptr(encoder), _lib.ptr(oh),
                                                _lib.ptr(oe), _lib.stream_ptr()))
+        return oh, oe
+
+    def attn_forward_with(self, weights, layer, hidden, encoder):
+        """attn_forward on this engine's geometry, workspace and rotary tables with layer `layer` of the engine `weights`
+        (s2v_attn_forward_with: same dtype, heads and weight_format; bit-identical to an engine holding those weights itself)"""
+        hidden, encoder = (x.to(self.device, self.dtype).contiguous() for x in (hidden, encoder))
+        oh, oe = torch.empty_like(hidden), torch.empty_like(encoder)
+        _lib.check(_lib.lib().s2v_attn_forward_with(self._h, weights._h, layer, _lib.ptr(hidden), _lib.ptr(encoder), _lib.ptr(oh),
+                                                    _lib.ptr(oe), _lib.stream_ptr()))
         return oh, oe
 
     AUTO_SLOW_FRACTION = 5e-3   # a slow path costs ~2.5 KV tiles of time, fp16 P saves ~4 %: break-even near 1.7 % of the pairs

@@ -151,31 +151,154 @@ class HipCogVideoXBlock(torch.nn.Module):
         return eng.block_forward(self.layer, hidden_states, encoder_hidden_states, enc_hidden_states1, temb)
 
 
+_ATTN_PARTS = (("to_q", lambda a: a.to_q), ("to_k", lambda a: a.to_k), ("to_v", lambda a: a.to_v), ("to_out.0", lambda a: a.to_out[0]),
+               ("norm_q", lambda a: a.norm_q), ("norm_k", lambda a: a.norm_k))
+_TUNER_ATTRS = ("base_layer", "lora_A", "lora_B", "scaling", "active_adapters", "merged", "disable_adapters")
+
+
+def _is_tuner_layer(mod):
+    """a PEFT LoRA tuner layer, duck-typed: what peft.tuners.lora.LoraLayer exposes"""
+    return all(hasattr(mod, a) for a in _TUNER_ATTRS)
+
+
+def _attn_state(attn):
+    """[(key name, base weight, base bias, [(A [r, in], B [out, r], scale) of the adapters to merge])] of the six attn1 parts, and the flat list
+    of what the weights depend on (tensors and adapter settings) that _AttnPool keys a module's slot on"""
+    parts, deps = [], []
+    for name, get in _ATTN_PARTS:
+        mod = get(attn)
+        deltas = []
+        if _is_tuner_layer(mod):
+            base = mod.base_layer
+            merged, disabled = bool(mod.merged), bool(mod.disable_adapters)
+            active = mod.active_adapters
+            active = [active] if isinstance(active, str) else list(active)
+            deps += [merged, disabled, tuple(active)]
+            if not merged and not disabled:  # merged: the delta is in base_layer.weight already; disabled: the base layer alone
+                for a in active:
+                    if a not in mod.lora_A:
+                        continue  # peft skips an active adapter this layer does not carry
+                    if getattr(mod, "use_dora", {}).get(a, False):
+                        raise NotImplementedError(f"DoRA adapter {a!r} on {name}: only plain LoRA (W + scaling * B A) is merged")
+                    A, B, sc = mod.lora_A[a].weight, mod.lora_B[a].weight, float(mod.scaling[a])
+                    deltas.append((A, B, sc))
+                    deps += [A, B, sc]
+        else:
+            base = mod
+        parts.append((name, base.weight, base.bias, deltas))
+        deps += [base.weight, base.bias]
+    return parts, deps
+
+
+def _dep_key(deps):
+    """identity + in-place version + storage address of every tensor (held by STRONG reference, as _Cache does), the value of every setting"""
+    return tuple((d, d._version, d.data_ptr()) if torch.is_tensor(d) else (None, d, None) for d in deps)
+
+
+def _same_key(key, deps):
+    return (key is not None and len(key) == len(deps)
+            and all((k[0] is d and k[1] == d._version and k[2] == d.data_ptr()) if torch.is_tensor(d) else (k[0] is None and k[1] == d)
+                    for k, d in zip(key, deps)))
+
+
+class _AttnPool:
+    """Every Attention module of one (device, dtype, heads, inner dim, force_simple) runs on ONE workspace engine (geometry, activation
+    workspace, rotary tables: S2V_CTX_ATTN_WORKSPACE) with its own attention-weights engine (the module's attn1 weights alone, re-packed
+    as a model packs them: S2V_CTX_ATTN_WEIGHTS), through s2v_attn_forward_with."""
+
+    def __init__(self, heads, dtype, device, force_simple):
+        self.cfg = TransformerConfig(num_layers=1, num_attention_heads=heads, time_embed_dim=8, text_embed_dim=64,
+                                     use_rotary_positional_embeddings=True)
+        self.dtype, self.device, self.force_simple = dtype, device, force_simple
+        self.engine = S2VEngine(self.cfg, dtype, device, force_simple, kind=_lib.CTX_ATTN_WORKSPACE)
+        self.slots = {}       # id(attn) -> (weights engine, key, attn); the module is kept alive: id(attn) stays unique
+        self.geometry_changes = 0
+
+    def weights_for(self, attn):
+        parts, deps = _attn_state(attn)
+        slot = self.slots.get(id(attn))
+        if slot is not None and _same_key(slot[1], deps):
+            return slot[0]
+        eng = S2VEngine(self.cfg, self.dtype, self.device, self.force_simple, kind=_lib.CTX_ATTN_WEIGHTS)
+        p = "transformer_blocks.0.attn1."
+        for name, w, b, _ in parts:
+            eng.load_weight(p + name + ".weight", w.detach())
+            eng.load_weight(p + name + ".bias", b.detach())
+        for name, _, _, deltas in parts:
+            for A, B, sc in deltas:
+                eng.merge_lora(p + name + ".weight", A.detach(), B.detach(), sc)
+        eng.finalize_weights()
+        if slot is not None:
+            slot[0].close()
+        self.slots[id(attn)] = (eng, _dep_key(deps), attn)
+        return eng
+
+    def set_geometry(self, geo):
+        self.engine.set_geometry(*geo)
+        self.geometry_changes += 1
+
+    def memory_bytes(self):
+        weights = sum(s[0].device_bytes()[0] for s in self.slots.values()) + self.engine.device_bytes()[0]
+        return {"weights": weights, "workspace": self.engine.device_bytes()[1]}
+
+    def close(self):
+        for s in self.slots.values():
+            s[0].close()
+        self.slots.clear()
+        self.engine.close()
+
+
+_POOLS = {}  # (device, dtype, heads, inner dim, force_simple) -> _AttnPool, shared by every HipCogVideoXAttnProcessor2_0 of the process
+
+
 class HipCogVideoXAttnProcessor2_0:
-    """AttnProcessor seam: `attn.set_processor(HipCogVideoXAttnProcessor2_0())`.  Weights are read from the
-    Attention module that owns them (to_q/to_k/to_v/to_out[0]/norm_q/norm_k, attention_processor.py:2049-2090) and
-    re-packed once per module into a one-layer context."""
+    """AttnProcessor seam: `attn.set_processor(HipCogVideoXAttnProcessor2_0())`, or model-wide through the reference's
+    `transformer.set_attn_processor(proc)` (cogvideox_transformer_3d.py:376-408) -- one instance or a dict of instances alike.
+
+    Weights are read from the Attention module that owns them (to_q/to_k/to_v/to_out[0]/norm_q/norm_k, attention_processor.py:2049-2090)
+    and re-packed into an attention-only weights context per module; every module of a (device, dtype, heads, inner dim, force_simple)
+    runs on ONE process-wide workspace (_AttnPool): one activation workspace and one rotary-table upload per model, not per module.
+    A module is re-packed before the call whenever what its weights depend on changed (identity, in-place version and storage of its
+    twelve tensors and of its adapter tensors, and the adapter settings): load_state_dict, an in-place copy_, a fuse / unfuse or
+    enable / disable of adapters.  Writes through `.data` that keep the storage escape the version counter.
+
+    PEFT LoRA tuner layers (duck-typed: base_layer, lora_A / lora_B keyed by adapter name, scaling, active_adapters, merged,
+    disable_adapters) are honoured by merging W + sum over the active adapters of scaling[a] * B_a A_a into the module's weights context
+    (s2v_merge_lora, fp32 A and B, rounded once per adapter to the model dtype) with the bias of base_layer; nothing is added when
+    `merged` (the delta is in base_layer.weight already), the base layer alone when `disable_adapters`.  This is the merge the engine
+    applies to checkpoints: the reference adds the adapter branch at run time, so parity is unpinned for the PEFT
+    runtime path.  DoRA adapters raise NotImplementedError."""
 
     def __init__(self, force_simple=False):
-        self._engines = {}
         self._force_simple = force_simple
+        self._keys = set()
 
-    def _engine_for(self, attn, dtype, device):
-        key = id(attn)
-        if key not in self._engines:
-            heads = attn.heads
-            cfg = TransformerConfig(num_layers=1, num_attention_heads=heads, time_embed_dim=8, text_embed_dim=64,
-                                    use_rotary_positional_embeddings=True)
-            eng = S2VEngine(cfg, dtype, device, self._force_simple)
-            p = "transformer_blocks.0.attn1."
-            for name, mod in (("to_q", attn.to_q), ("to_k", attn.to_k), ("to_v", attn.to_v), ("to_out.0", attn.to_out[0]),
-                              ("norm_q", attn.norm_q), ("norm_k", attn.norm_k)):
-                eng.load_weight(p + name + ".weight", mod.weight.detach())
-                eng.load_weight(p + name + ".bias", mod.bias.detach())
-            torch.cuda.synchronize()
-            eng.mark_weights_loaded()  # only attn1 is used through s2v_attn_forward
-            self._engines[key] = (eng, attn)  # the module is kept alive: id(attn) stays unique
-        return self._engines[key]
+    def _pool_for(self, attn, dtype, device, D):
+        key = (device, dtype, attn.heads, D, self._force_simple)
+        if key not in _POOLS:
+            _POOLS[key] = _AttnPool(attn.heads, dtype, device, self._force_simple)
+        self._keys.add(key)
+        return _POOLS[key]
+
+    def pools(self):
+        """the pools this processor has run on (and that release_pools has not dropped)"""
+        return [_POOLS[k] for k in self._keys if k in _POOLS]
+
+    def memory_bytes(self):
+        """{"weights", "workspace"}: device bytes the library holds for the pools this processor runs on (s2v_device_bytes): every module's
+        attention-weights context, and each pool's one workspace"""
+        out = {"weights": 0, "workspace": 0}
+        for pool in self.pools():
+            for k, v in pool.memory_bytes().items():
+                out[k] += v
+        return out
+
+    @staticmethod
+    def release_pools():
+        """free every pool of the process (weights contexts and workspaces); a processor called afterwards re-packs its modules"""
+        for pool in _POOLS.values():
+            pool.close()
+        _POOLS.clear()
 
     def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask=None, image_rotary_emb=None,
                  ref_img_seq_start=0, ref_img_seq_end=0, position_delta=None, embed_ref_img=False,
@@ -192,16 +315,18 @@ class HipCogVideoXAttnProcessor2_0:
             raise NotImplementedError("the fork always calls with embed_ref_img=True and the reference-image tokens at "
                                       "the tail of encoder_hidden_states (cogvideox_transformer_3d.py:510-512)")
         T, R = ref_img_seq_start, ref_img_seq_end - ref_img_seq_start
-        eng, _ = self._engine_for(attn, hidden_states.dtype, hidden_states.device)
+        pool = self._pool_for(attn, hidden_states.dtype, hidden_states.device, D)
+        weights = pool.weights_for(attn)
+        eng = pool.engine
         geo = (B, T, V // R, 2, 2 * R)
         if V % R != 0:
             raise RuntimeError("video tokens must be a whole number of frames of the reference image's token count")
         if eng.geometry != geo:
-            eng.set_geometry(*geo)
+            pool.set_geometry(geo)
         if image_rotary_emb is not None:
             ref = ref_image_rotary_emb
             key = (image_rotary_emb[0], image_rotary_emb[1], None if ref is None else ref[0], None if ref is None else ref[1])
             eng.ensure_rope(key, lambda: _rope_pair(image_rotary_emb, ref, R))
         else:
             eng.ensure_no_rope()
-        return eng.attn_forward(0, hidden_states, encoder_hidden_states)
+        return eng.attn_forward_with(weights, 0, hidden_states, encoder_hidden_states)

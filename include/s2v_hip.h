@@ -77,8 +77,21 @@ typedef struct s2v_model_config {
                                *     adds on the P registers, flushed to fp32 per KV tile; the deferred maximum falls to 2^14, i.e. the slow
                                *     path re-adopts the row maximum when a later score exceeds it by ~9.7 natural units -- faster on smooth
                                *     score distributions, slower on spiky ones; tests/test_gpu_parity.py holds both against fp64 SDPA) */
-    int32_t reserved[2];
+    int32_t reserved[2];      /* reserved[0]: the kind of context s2v_create makes (S2V_CTX_*, 0 = a whole model); reserved[1]: 0 */
 } s2v_model_config;
+
+/* reserved[0] of s2v_model_config.  The AttnProcessor seam installed on every Attention module of a model
+ * keeps each module's attention weights in an S2V_CTX_ATTN_WEIGHTS context and runs all of them with ONE S2V_CTX_ATTN_WORKSPACE
+ * context's geometry, workspace and rotary tables (s2v_attn_forward_with): one activation workspace per model instead of one per module. */
+enum {
+    S2V_CTX_MODEL = 0,          /* a whole model: weight arena of num_layers blocks + embeddings; workspace at s2v_set_geometry; every entry point */
+    S2V_CTX_ATTN_WEIGHTS = 1,   /* attention weights only: num_layers x transformer_blocks.<l>.attn1.{to_q,to_k,to_v,to_out.0,norm_q,norm_k}.{weight,bias}
+                                 * in the fused QKV / out-projection layout of a model's arena (s2v_load_weight, s2v_merge_lora, s2v_finalize_weights on
+                                 * those keys).  It never carves a workspace (s2v_set_geometry refuses it) and runs nothing itself; weight_format 0 */
+    S2V_CTX_ATTN_WORKSPACE = 2  /* geometry, workspace and rotary tables without weights (no arena): s2v_set_geometry, s2v_set_rope, then
+                                 * s2v_attn_forward_with; s2v_finalize_weights / s2v_mark_weights_loaded refuse it, so every entry point that needs
+                                 * its own weights does too; weight_format 0 */
+};
 
 S2V_API const char* s2v_last_error(void);
 S2V_API const char* s2v_version(void);
@@ -144,6 +157,16 @@ S2V_API int s2v_block_forward(s2v_ctx* ctx, int32_t layer, const void* hidden, c
  * hidden [B,V,D] and encoder [B,T+R,D] are the already-modulated inputs; outputs have the same shapes. */
 S2V_API int s2v_attn_forward(s2v_ctx* ctx, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
                      void* out_encoder, s2v_stream stream);
+/* s2v_attn_forward with another context's weights: ctx's geometry, workspace and rotary tables (ctx: S2V_CTX_ATTN_WORKSPACE, or a model),
+ * `weights`' layer `layer` (weights: a finalized S2V_CTX_ATTN_WEIGHTS context, or a model).  The same launches as s2v_attn_forward -- the
+ * fused QKV GEMM with the q/k-norm + RoPE epilogue, the attention, the out-projection -- so the outputs are bit-identical to a model
+ * context holding the same weights at the same geometry.  Refuses a ctx without a geometry, differing dtype, num_heads, inner dim or
+ * weight_format, a shard context on either side (s2v_set_shard), and weights that are not loaded. */
+S2V_API int s2v_attn_forward_with(s2v_ctx* ctx, const s2v_ctx* weights, int32_t layer, const void* hidden, const void* encoder,
+                          void* out_hidden, void* out_encoder, s2v_stream stream);
+/* Device bytes the context holds: its weight arena (0 for S2V_CTX_ATTN_WORKSPACE) and its activation workspace (0 before s2v_set_geometry
+ * and for S2V_CTX_ATTN_WEIGHTS).  The fixed buffers of a few KiB and the transient LoRA-merge scratch are not counted. */
+S2V_API int s2v_device_bytes(s2v_ctx* ctx, int64_t* arena, int64_t* workspace);
 
 /* Per-step scheduler scalars, computed on the host exactly as scheduling_ddim_cogvideox.py:364-394 /
  * scheduling_dpm_cogvideox.py:306-434 do (fp64), then cast; see s2v schedulers.py. */
