@@ -43,6 +43,10 @@ _SIGS = {
     "s2v_load_weight": [_P, ctypes.c_char_p, _P, ctypes.POINTER(_I64), _I32, _I32, _P],
     "s2v_merge_lora": [_P, ctypes.c_char_p, _P, _P, _I32, _F, _P],
     "s2v_finalize_weights": [_P, _P],
+    "s2v_lora_attach": [_P, ctypes.c_char_p, _P, _P, _I32, _F, _P],
+    "s2v_lora_set_scale": [_P, ctypes.c_char_p, _P, _P, _I32, _F, _P],
+    "s2v_lora_detach": [_P, _P],
+    "s2v_lora_state": [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_F), ctypes.POINTER(_I64)],
     "s2v_weight_arena": [_P, ctypes.POINTER(_P), ctypes.POINTER(_I64)],
     "s2v_weight_slot": [_P, ctypes.c_char_p, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     "s2v_mark_weights_loaded": [_P],
@@ -68,6 +72,7 @@ _SIGS = {
     "s2v_profile_read": [_P, ctypes.POINTER(_F), ctypes.POINTER(_I32), _I32],
     "s2v_profile_read_clocks": [_P, ctypes.POINTER(_F), _I32],
     "s2v_op_linear": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "s2v_op_linear_lora": [_P, _P, _P, _P, _P, _I32, _F, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P],
     "s2v_op_ff_fp8": [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P],
     "s2v_op_mod_gemv": [_P, _P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P],
     "s2v_op_attention": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],

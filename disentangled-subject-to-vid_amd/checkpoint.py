@@ -145,6 +145,16 @@ def load_transformer(model, transformer_dir, lora_dir=None, lora_alpha=64, rank=
     return sorted(lora) if lora else []
 
 
+def swap_lora(model, lora_dir, lora_alpha=64, rank=128):
+    """another adapter on a loaded runtime-mode model (TransformerConfig.lora_runtime_rank > 0): read + attach, no base weight is
+    touched or read again.  `model`: HipCogVideoXTransformer3DModel (or an S2VEngine).  Returns the adapter's keys like load_transformer.
+    The engine remembers it as the adapter attached last: model.disable_adapters() / enable_adapters() switch THIS adapter."""
+    eng = getattr(model, "engine", model)
+    lora = read_lora(lora_dir)
+    eng.attach_lora(lora, lora_alpha / rank)
+    return sorted(lora)
+
+
 def load_vae_decoder(vae, vae_dir):
     sd = {k: t for k, t in iter_tensors(model_files(vae_dir)) if k.startswith("decoder.")}
     vae.load_state_dict(sd)

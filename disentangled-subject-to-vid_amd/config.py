@@ -38,6 +38,11 @@ class TransformerConfig:
     # (S2VEngine.denoise_step).  "auto" decides per engine from its own data: replicas may settle differently -- use it for throughput
     # runs, not where ranks must agree bit for bit.
     attn_p_format: str = "bf16"
+    # 0 (default): the subject-LoRA is merged into the weights at load time -- no per-step cost.  r > 0: the runtime adapter mode with room
+    # for adapters of rank <= r (include/s2v_hip.h, s2v_lora_attach): the six token linears of every block run base + branch as the
+    # reference's unmerged PEFT model does, and S2VEngine.attach_lora / set_lora_scale / detach_lora swap, rescale and remove the adapter
+    # after the weights are finalized
+    lora_runtime_rank: int = 0
 
     @property
     def inner_dim(self):

@@ -26,12 +26,21 @@ struct Slot {
     char* dst = nullptr;   // destination inside the arena
     int64_t rows = 0, cols = 0, ld = 0;
     bool loaded = false;
+    // runtime LoRA (lora_runtime_rank > 0): how s2v_lora_attach reaches this weight -- LORA_BRANCH: the adapter branch runs beside the base
+    // weight (s * B in the tail columns [tail_col, tail_col + lr) of the weight's rows, A in rows of the layer's A stack at lora_a);
+    // LORA_REMERGE: the live slot is rebuilt from the context's base copy with the merge arithmetic of s2v_merge_lora
+    int lora = 0;
+    char* lora_a = nullptr;
+    int64_t tail_col = 0;
 };
+enum { LORA_NONE = 0, LORA_BRANCH = 1, LORA_REMERGE = 2 };
 
 struct LayerW {
     char *ln1_w, *ln1_b, *ln2_w, *ln2_b;
     char *wqkv, *bqkv, *nq_w, *nq_b, *nk_w, *nk_b, *wo, *bo;
     char *w1, *b1, *w2, *b2;
+    // runtime LoRA: the A stacks of the four adapted linears, model dtype, zero without an adapter: [3 lr][D] (q | k | v), [lr][D], [lr][D], [lr][4 D]
+    char *a_qkv = nullptr, *a_o = nullptr, *a_1 = nullptr, *a_2 = nullptr;
     // weight_format 1: e4m3 copies [N_pad][K] of the four big linears + per-output-channel scales (quantised at finalize)
     char *q_qkv = nullptr, *q_o = nullptr, *q_1 = nullptr, *q_2 = nullptr;
     float *s_qkv = nullptr, *s_o = nullptr, *s_1 = nullptr, *s_2 = nullptr;
@@ -63,6 +72,22 @@ struct s2v_ctx {
     float* aq_scale = nullptr;   // workspace: their per-token scales [Mpad]
     unsigned char *hq = nullptr, *hs = nullptr;  // workspace (fp8): GELU(FF1) as MX e4m3 [Mpad][4D] + block scales [Mpad][4D / 32]
     bool finalized = false;
+    // runtime LoRA (cfg.reserved[1] = lora_runtime_rank; include/s2v_hip.h).  lr > 0: the four adapted linears of every block are carved with
+    // ld = K + R (R = 3 lr for the fused QKV, lr otherwise), Xn / Hb rows have room for T = x . A^T behind column K, and with an adapter
+    // attached every adapted GEMM runs with K' = K + R after a down-projection (lora.hip) has written T
+    int lora_cap = 0;            // the rank asked for (0: mode off)
+    int lr = 0;                  // lora_cap padded to what the GEMM dispatch needs (64, or 128 when D % 128 == 0); 0 with the mode off / fp8
+    std::unordered_map<std::string, int> lora_names;   // attached: weight name -> rank
+    int lora_rank = 0; float lora_scale = 0.f;          // of the last attach / rescale (s2v_lora_state)
+    int64_t graph_captures = 0;
+    // the attached state as the ARENA carries it (three words at the arena's end: names attached, rank, scale bits), so that a replica
+    // whose arena was filled by a broadcast runs the adapter it received (s2v_mark_weights_loaded reads them back)
+    char* lora_hdr = nullptr;
+    int32_t lora_hdr_host[4] = {0, 0, 0, 0};
+    int lora_replica = 0;        // names attached on the context this arena was copied from (0 on the context that attached them itself)
+    bool lora_on() const { return !lora_names.empty() || lora_replica > 0; }
+    char *base_mod = nullptr, *base_patch = nullptr, *base_text = nullptr;   // base copies of the re-merged weights (inside the arena)
+    int64_t base_mod_bytes = 0, base_patch_bytes = 0, base_text_bytes = 0;
     // weights
     int num_cus = 256;
     int sk_tiles = 0; float* sk_ws = nullptr; unsigned* sk_cnt = nullptr;  // split-K workspace of the geometry (0: none)
@@ -106,8 +131,8 @@ struct s2v_ctx {
     long long* clk_cur = nullptr;                    // the slot of the launch a ProfScope is open around (null outside the profile pass)
     std::vector<std::pair<int, int>> clk_rec;         // (class, slot) of every stamped launch since the last s2v_profile_read_clocks
     bool prof_on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[9];  // PK_NUM classes (8: the Ulysses packs / unpacks)
-    size_t prof_used[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[10];  // PK_NUM classes (8: the Ulysses packs / unpacks, 9: the LoRA down-projections)
+    size_t prof_used[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // Ulysses shard (s2v_set_shard): sp ranks share one video's step.  With a shard T, R, V, Ntok, M and Mpad above are this rank's rows of
     // every sample -- the mini-sequence [T_r | R_r | V_r] -- and gT, gR, gV, gN the whole streams (equal to T, R, V, Ntok without a shard).
     bool shard = false;
@@ -136,7 +161,7 @@ static const int CLK_SLOTS = 8192;
 // designated workgroup of the kernel stamps s_memtime / s_memrealtime at its entry and exit (common.h clk_stamp).  Kernels without stamps (or
 // launches whose designated workgroup left early) leave the slot zero and are skipped.
 #define S2V_FP8_QK_AUTO_TOKENS 40000
-enum { PK_QKV = 0, PK_ATTN = 1, PK_OUT = 2, PK_FF1 = 3, PK_FF2 = 4, PK_LNMOD = 5, PK_QKNORM = 6, PK_OTHER = 7, PK_SHARD = 8, PK_NUM = 9 };
+enum { PK_QKV = 0, PK_ATTN = 1, PK_OUT = 2, PK_FF1 = 3, PK_FF2 = 4, PK_LNMOD = 5, PK_QKNORM = 6, PK_OTHER = 7, PK_SHARD = 8, PK_LORA = 9, PK_NUM = 10 };
 
 struct ProfScope {
     s2v_ctx* c; int k; hipStream_t st; bool on;
@@ -179,12 +204,15 @@ static Slot* add_slot(s2v_ctx* c, const std::string& name, char* dst, int64_t ro
 
 // the attn1 keys of layer l: fused QKV [rup(3D, 256)][D] + bias [3D], per-head LayerNorm(64) of q and k, out-projection [Dp][D] + bias
 static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
-    const int64_t D = c->D, E = c->esz;
+    const int64_t D = c->D, E = c->esz, lr = c->lr, ldq = D + 3 * lr, ldo = D + lr;
     char nm[160];
 #define NM(fmt) (snprintf(nm, sizeof(nm), "transformer_blocks.%d." fmt, l), std::string(nm))
-    add_slot(c, NM("attn1.to_q.weight"), w.wqkv, D, D, D);
-    add_slot(c, NM("attn1.to_k.weight"), w.wqkv + D * D * E, D, D, D);
-    add_slot(c, NM("attn1.to_v.weight"), w.wqkv + 2 * D * D * E, D, D, D);
+    Slot* sq[3];
+    sq[0] = add_slot(c, NM("attn1.to_q.weight"), w.wqkv, D, D, ldq);
+    sq[1] = add_slot(c, NM("attn1.to_k.weight"), w.wqkv + D * ldq * E, D, D, ldq);
+    sq[2] = add_slot(c, NM("attn1.to_v.weight"), w.wqkv + 2 * D * ldq * E, D, D, ldq);
+    // block-diagonal tail of the fused QKV: part p keeps s * B_p in the tail columns [p lr, (p + 1) lr) of its own rows, zeros elsewhere
+    for (int p = 0; lr && p < 3; ++p) { sq[p]->lora = LORA_BRANCH; sq[p]->lora_a = w.a_qkv + p * lr * D * E; sq[p]->tail_col = D + p * lr; }
     add_slot(c, NM("attn1.to_q.bias"), w.bqkv, 1, D, D);
     add_slot(c, NM("attn1.to_k.bias"), w.bqkv + D * E, 1, D, D);
     add_slot(c, NM("attn1.to_v.bias"), w.bqkv + 2 * D * E, 1, D, D);
@@ -192,35 +220,50 @@ static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
     add_slot(c, NM("attn1.norm_q.bias"), w.nq_b, 1, 64, 64);
     add_slot(c, NM("attn1.norm_k.weight"), w.nk_w, 1, 64, 64);
     add_slot(c, NM("attn1.norm_k.bias"), w.nk_b, 1, 64, 64);
-    add_slot(c, NM("attn1.to_out.0.weight"), w.wo, D, D, D);
+    Slot* so = add_slot(c, NM("attn1.to_out.0.weight"), w.wo, D, D, ldo);
+    if (lr) { so->lora = LORA_BRANCH; so->lora_a = w.a_o; so->tail_col = D; }
     add_slot(c, NM("attn1.to_out.0.bias"), w.bo, 1, D, D);
 #undef NM
+}
+
+// lora_runtime_rank (cfg.reserved[1]) -> the padded rank the layout is carved for
+static int lora_setup(s2v_ctx* c) {
+    c->lora_cap = c->cfg.reserved[1];
+    if (c->lora_cap < 0 || c->lora_cap > 128) return s2v_fail(__FILE__, __LINE__, "s2v_create: lora_runtime_rank (reserved[1]) must be 0 .. 128", -1);
+    // the fp8 weight formats keep no 16-bit operand for a branch to extend: nothing is carved, s2v_lora_attach refuses
+    const bool fp8 = c->cfg.weight_format != 0;
+    c->lr = (c->lora_cap > 0 && !fp8) ? (int)rup(c->lora_cap, c->D % 128 == 0 ? 128 : 64) : 0;
+    return 0;
 }
 
 // S2V_CTX_ATTN_WEIGHTS: an arena of num_layers x the attn1 weights, carved exactly as a model carves them (zero pad rows included), so that a
 // workspace context runs them through the same GEMM tiles; no stream, event, scratch or workspace of its own
 static int create_attn_weights(s2v_ctx* c) {
     if (c->D > 4096 || c->D % 8 != 0) return s2v_fail(__FILE__, __LINE__, "s2v_create: bad inner dim", -1);
-    const int64_t D = c->D, E = c->esz, Dp = rup(D, 256);
+    const int64_t D = c->D, E = c->esz, Dp = rup(D, 256), lr = c->lr;
     int64_t off = 0;
     auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
-    struct Offs { int64_t wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo; };
+    struct Offs { int64_t wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, a_qkv, a_o; };
     std::vector<Offs> lo(c->L);
     for (Offs& o : lo) {
-        o.wqkv = carve(rup(3 * D, 256) * D); o.bqkv = carve(3 * D);
+        o.wqkv = carve(rup(3 * D, 256) * (D + 3 * lr)); o.bqkv = carve(3 * D);
         o.nq_w = carve(64); o.nq_b = carve(64); o.nk_w = carve(64); o.nk_b = carve(64);
-        o.wo = carve(Dp * D); o.bo = carve(D);
+        o.wo = carve(Dp * (D + lr)); o.bo = carve(D);
+        o.a_qkv = carve(3 * lr * D); o.a_o = carve(lr * D);
     }
+    const int64_t o_lora_hdr = carve(lr ? 128 : 0);
     c->arena_bytes = off;
     S2V_CHECK_HIP(hipMalloc((void**)&c->arena, c->arena_bytes));
     S2V_CHECK_HIP(hipMemset(c->arena, 0, c->arena_bytes));
     char* A = c->arena;
+    if (lr) c->lora_hdr = A + o_lora_hdr;
     c->layers.assign(c->L, LayerW{});
     for (int l = 0; l < c->L; ++l) {
         const Offs& o = lo[l];
         LayerW& w = c->layers[l];
         w.wqkv = A + o.wqkv; w.bqkv = A + o.bqkv; w.nq_w = A + o.nq_w; w.nq_b = A + o.nq_b;
         w.nk_w = A + o.nk_w; w.nk_b = A + o.nk_b; w.wo = A + o.wo; w.bo = A + o.bo;
+        w.a_qkv = A + o.a_qkv; w.a_o = A + o.a_o;
         add_attn_slots(c, l, w);
     }
     return 0;
@@ -258,6 +301,7 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     c->esz = cfg->dtype == S2V_DTYPE_F32 ? 4 : 2;
     c->temb = cfg->time_embed_dim;
     c->kind = kind;
+    if (lora_setup(c)) { delete c; return -1; }
     {
         int dev = 0, ncu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
@@ -297,17 +341,19 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     // two passes: size, then carve
     int64_t off = 0;
     auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
-    struct Offs { int64_t ln1_w, ln1_b, ln2_w, ln2_b, wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, w1, b1, w2, b2; };
+    struct Offs { int64_t ln1_w, ln1_b, ln2_w, ln2_b, wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, w1, b1, w2, b2, a_qkv, a_o, a_1, a_2; };
     std::vector<Offs> lo(L);
     const int64_t Dp = rup(D, 256);  // weight rows are padded to the 256-column GEMM tile (zero rows)
+    const int64_t lr = c->lr;        // runtime LoRA: the adapted weights get lr (QKV: 3 lr) zero tail columns, ld = K + R
     for (int l = 0; l < L; ++l) {
         Offs& o = lo[l];
         o.ln1_w = carve(D); o.ln1_b = carve(D); o.ln2_w = carve(D); o.ln2_b = carve(D);
-        o.wqkv = carve(rup(3 * D, 256) * D); o.bqkv = carve(3 * D);
+        o.wqkv = carve(rup(3 * D, 256) * (D + 3 * lr)); o.bqkv = carve(3 * D);
         o.nq_w = carve(64); o.nq_b = carve(64); o.nk_w = carve(64); o.nk_b = carve(64);
-        o.wo = carve(Dp * D); o.bo = carve(D);
-        o.w1 = carve(rup(4 * D, 256) * D); o.b1 = carve(4 * D);
-        o.w2 = carve(Dp * 4 * D); o.b2 = carve(D);
+        o.wo = carve(Dp * (D + lr)); o.bo = carve(D);
+        o.w1 = carve(rup(4 * D, 256) * (D + lr)); o.b1 = carve(4 * D);
+        o.w2 = carve(Dp * (4 * D + lr)); o.b2 = carve(D);
+        o.a_qkv = carve(3 * lr * D); o.a_o = carve(lr * D); o.a_1 = carve(lr * D); o.a_2 = carve(lr * 4 * D);
     }
     const int64_t o_patch_w = carve(Dp * Kp), o_patch_b = carve(D);
     const int64_t o_text_w = carve(Dp * TX), o_text_b = carve(D);
@@ -319,6 +365,11 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     const int64_t MC = c->mc;
     c->mod_rows = 2 * L * MC * D + 2 * D;
     const int64_t o_mod_w = carve(c->mod_rows * TE), o_mod_b = carve(c->mod_rows);
+    // runtime LoRA: base copies of the weights an attach re-merges (every norm{1,2}.linear of the modulation stack, patch_embed.proj,
+    // patch_embed.text_proj), filled by s2v_finalize_weights
+    c->base_mod_bytes = lr ? c->mod_rows * TE * E : 0; c->base_patch_bytes = lr ? Dp * Kp * E : 0; c->base_text_bytes = lr ? Dp * TX * E : 0;
+    const int64_t o_base_mod = carve(lr ? c->mod_rows * TE : 0), o_base_patch = carve(lr ? Dp * Kp : 0), o_base_text = carve(lr ? Dp * TX : 0);
+    const int64_t o_lora_hdr = carve(lr ? 128 : 0);
     // fp8 copies live in the same arena (one broadcast replicates everything a replica needs)
     c->fp8 = cfg->weight_format >= 1 && cfg->weight_format <= 3;
     c->fp8_qk = cfg->weight_format == 2;
@@ -349,6 +400,7 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         w.wqkv = A + o.wqkv; w.bqkv = A + o.bqkv; w.nq_w = A + o.nq_w; w.nq_b = A + o.nq_b;
         w.nk_w = A + o.nk_w; w.nk_b = A + o.nk_b; w.wo = A + o.wo; w.bo = A + o.bo;
         w.w1 = A + o.w1; w.b1 = A + o.b1; w.w2 = A + o.w2; w.b2 = A + o.b2;
+        w.a_qkv = A + o.a_qkv; w.a_o = A + o.a_o; w.a_1 = A + o.a_1; w.a_2 = A + o.a_2;
         if (c->fp8) {
             const QOffs& q = qo[l];
             w.q_qkv = A + q.q_qkv; w.q_o = A + q.q_o; w.q_1 = A + q.q_1; w.q_2 = A + q.q_2;
@@ -360,13 +412,14 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         add_slot(c, NM("norm2.norm.weight"), w.ln2_w, 1, D, D);
         add_slot(c, NM("norm2.norm.bias"), w.ln2_b, 1, D, D);
         add_attn_slots(c, l, w);
-        add_slot(c, NM("ff.net.0.proj.weight"), w.w1, 4 * D, D, D);
+        Slot* s1 = add_slot(c, NM("ff.net.0.proj.weight"), w.w1, 4 * D, D, D + lr);
         add_slot(c, NM("ff.net.0.proj.bias"), w.b1, 1, 4 * D, 4 * D);
-        add_slot(c, NM("ff.net.2.weight"), w.w2, D, 4 * D, 4 * D);
+        Slot* s2 = add_slot(c, NM("ff.net.2.weight"), w.w2, D, 4 * D, 4 * D + lr);
         add_slot(c, NM("ff.net.2.bias"), w.b2, 1, D, D);
-        add_slot(c, NM("norm1.linear.weight"), A + o_mod_w + (int64_t)(2 * l) * MC * D * TE * E, 6 * D, TE, TE);
+        if (lr) { s1->lora = LORA_BRANCH; s1->lora_a = w.a_1; s1->tail_col = D; s2->lora = LORA_BRANCH; s2->lora_a = w.a_2; s2->tail_col = 4 * D; }
+        add_slot(c, NM("norm1.linear.weight"), A + o_mod_w + (int64_t)(2 * l) * MC * D * TE * E, 6 * D, TE, TE)->lora = lr ? LORA_REMERGE : LORA_NONE;
         add_slot(c, NM("norm1.linear.bias"), A + o_mod_b + (int64_t)(2 * l) * MC * D * E, 1, 6 * D, 6 * D);
-        add_slot(c, NM("norm2.linear.weight"), A + o_mod_w + (int64_t)(2 * l + 1) * MC * D * TE * E, 6 * D, TE, TE);
+        add_slot(c, NM("norm2.linear.weight"), A + o_mod_w + (int64_t)(2 * l + 1) * MC * D * TE * E, 6 * D, TE, TE)->lora = lr ? LORA_REMERGE : LORA_NONE;
         add_slot(c, NM("norm2.linear.bias"), A + o_mod_b + (int64_t)(2 * l + 1) * MC * D * E, 1, 6 * D, 6 * D);
 #undef NM
     }
@@ -374,9 +427,10 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     c->te1_w = A + o_te1_w; c->te1_b = A + o_te1_b; c->te2_w = A + o_te2_w; c->te2_b = A + o_te2_b;
     c->nf_w = A + o_nf_w; c->nf_b = A + o_nf_b; c->no_w = A + o_no_w; c->no_b = A + o_no_b;
     c->po_w = A + o_po_w; c->po_b = A + o_po_b; c->mod_w = A + o_mod_w; c->mod_b = A + o_mod_b;
-    add_slot(c, "patch_embed.proj.weight", c->patch_w, D, Kp, Kp);
+    if (lr) { c->base_mod = A + o_base_mod; c->base_patch = A + o_base_patch; c->base_text = A + o_base_text; c->lora_hdr = A + o_lora_hdr; }
+    add_slot(c, "patch_embed.proj.weight", c->patch_w, D, Kp, Kp)->lora = lr ? LORA_REMERGE : LORA_NONE;
     add_slot(c, "patch_embed.proj.bias", c->patch_b, 1, D, D);
-    add_slot(c, "patch_embed.text_proj.weight", c->text_w, D, TX, TX);
+    add_slot(c, "patch_embed.text_proj.weight", c->text_w, D, TX, TX)->lora = lr ? LORA_REMERGE : LORA_NONE;
     add_slot(c, "patch_embed.text_proj.bias", c->text_b, 1, D, D);
     add_slot(c, "time_embedding.linear_1.weight", c->te1_w, TE, D, D);
     add_slot(c, "time_embedding.linear_1.bias", c->te1_b, 1, TE, TE);
@@ -449,21 +503,16 @@ extern "C" int s2v_load_weight(s2v_ctx* c, const char* name, const void* dev_ptr
     return 0;
 }
 
-extern "C" int s2v_merge_lora(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale,
-                              s2v_stream stream) {
-    S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_merge_lora: bad argument");
-    S2V_REQUIRE(!c->finalized, "s2v_merge_lora: weights already finalized");
-    auto it = c->slots.find(name);
-    S2V_REQUIRE(it != c->slots.end(), "s2v_merge_lora: unknown tensor name");
-    Slot& s = it->second;
-    S2V_REQUIRE(s.loaded && s.rows > 1, "s2v_merge_lora: base weight must be a loaded matrix");
-    hipStream_t st = (hipStream_t)stream;
+// W[name] += scale * B.A in fp32, rounded once to the model dtype: the arithmetic of s2v_merge_lora (load time) and of the weights a
+// runtime attach re-merges from their base copy
+static int merge_into(s2v_ctx* c, const char* name, Slot& s, const float* A, const float* B, int32_t rank, float scale, hipStream_t st) {
     // lora_adaln_scope 1: on norm{1,2}.linear the LoRA reaches only the reference-image copy of chunks 0-2 (rows [0, 3D) of B)
     const bool scoped = c->mc == 9 && is_adaln_linear(name);
     char* dst = scoped ? s.dst + 6 * (int64_t)c->D * s.ld * c->esz : s.dst;
     const int64_t rows = scoped ? 3 * (int64_t)c->D : s.rows;
     // one fp32 scratch for all merges of a load (grown to the largest slot, freed by s2v_finalize_weights / s2v_destroy): no
-    // allocation or synchronisation per key
+    // allocation or synchronisation per key.  A runtime-mode context allocates it again at its first attach after finalize and keeps it
+    // until s2v_destroy (the largest re-merged slot in fp32: 50 MB at 5B, not counted by s2v_device_bytes)
     const size_t need = sizeof(float) * (size_t)rows * (size_t)s.cols;
     if (need > c->lora_tmp_bytes) {
         if (c->lora_tmp) { S2V_CHECK_HIP(hipStreamSynchronize(st)); (void)hipFree(c->lora_tmp); c->lora_tmp = nullptr; c->lora_tmp_bytes = 0; }
@@ -476,6 +525,17 @@ extern "C" int s2v_merge_lora(s2v_ctx* c, const char* name, const float* A, cons
     if (!r) r = launch_gemm_strided_f32(B, rank, 1, A, 1, s.cols, tmp, s.cols, (int)rows, (int)s.cols, rank, scale, st);
     if (!r) r = launch_convert2d(tmp, S2V_F32, s.cols, dst, c->dtype, s.ld, rows, s.cols, st);
     return r;  // stream-ordered: the caller keeps A and B alive until the stream has passed (as for s2v_load_weight)
+}
+
+extern "C" int s2v_merge_lora(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale,
+                              s2v_stream stream) {
+    S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_merge_lora: bad argument");
+    S2V_REQUIRE(!c->finalized, "s2v_merge_lora: weights already finalized");
+    auto it = c->slots.find(name);
+    S2V_REQUIRE(it != c->slots.end(), "s2v_merge_lora: unknown tensor name");
+    Slot& s = it->second;
+    S2V_REQUIRE(s.loaded && s.rows > 1, "s2v_merge_lora: base weight must be a loaded matrix");
+    return merge_into(c, name, s, A, B, rank, scale, (hipStream_t)stream);
 }
 
 extern "C" int s2v_finalize_weights(s2v_ctx* c, s2v_stream stream) {
@@ -504,6 +564,13 @@ extern "C" int s2v_finalize_weights(s2v_ctx* c, s2v_stream stream) {
         (void)hipFree(c->lora_tmp);
         c->lora_tmp = nullptr;
         c->lora_tmp_bytes = 0;
+    }
+    if (c->lr && c->kind == S2V_CTX_MODEL) {
+        // runtime LoRA: what the re-merged weights hold now is their base (a LoRA merged before this call stays part of it)
+        hipStream_t st = (hipStream_t)stream;
+        S2V_CHECK_HIP(hipMemcpyAsync(c->base_mod, c->mod_w, (size_t)c->base_mod_bytes, hipMemcpyDeviceToDevice, st));
+        S2V_CHECK_HIP(hipMemcpyAsync(c->base_patch, c->patch_w, (size_t)c->base_patch_bytes, hipMemcpyDeviceToDevice, st));
+        S2V_CHECK_HIP(hipMemcpyAsync(c->base_text, c->text_w, (size_t)c->base_text_bytes, hipMemcpyDeviceToDevice, st));
     }
     c->finalized = true;
     return 0;
@@ -534,6 +601,17 @@ extern "C" int s2v_mark_weights_loaded(s2v_ctx* c) {
     S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_mark_weights_loaded: a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
     for (auto& kv : c->slots) kv.second.loaded = true;
     c->finalized = true;
+    if (c->lora_hdr) {  // the arena may carry an attached adapter: run it
+        S2V_CHECK_HIP(hipDeviceSynchronize());
+        S2V_CHECK_HIP(hipMemcpy(c->lora_hdr_host, c->lora_hdr, sizeof(c->lora_hdr_host), hipMemcpyDeviceToHost));
+        c->lora_names.clear();
+        c->lora_replica = c->lora_hdr_host[0] > 0 ? c->lora_hdr_host[0] : 0;
+        c->lora_rank = c->lora_replica ? c->lora_hdr_host[1] : 0;
+        memcpy(&c->lora_scale, &c->lora_hdr_host[2], sizeof(float));
+        if (!c->lora_replica) c->lora_scale = 0.f;
+        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+        c->have_cond = false;
+    }
     return 0;
 }
 
@@ -548,6 +626,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     S2V_REQUIRE(c, "null context");
     S2V_REQUIRE(c->kind == S2V_CTX_MODEL, "s2v_set_shard: attention-only contexts (S2V_CTX_ATTN_*) are not sharded");
     S2V_REQUIRE(world >= 1 && rank >= 0 && rank < world, "s2v_set_shard: need world >= 1 and 0 <= rank < world");
+    S2V_REQUIRE(c->lora_cap == 0, "s2v_set_shard: a shard context does not support the runtime adapter mode (lora_runtime_rank > 0)");
     S2V_REQUIRE(c->cfg.num_heads % world == 0, "s2v_set_shard: the world size must divide num_heads (attention runs num_heads / world heads per rank)");
     // fp8: the attention output reaches the out-projection as MX e4m3 whose scales are dwords of four 32-column blocks = one 128-column K-tile =
     // two heads; with an even head count per rank every dword of that image belongs to exactly one rank's head group
@@ -606,8 +685,9 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     const int64_t BVg = rup((int64_t)B * c->gV, 256) + 256;  // patchify runs on the whole latent (== BVp without a shard)
     int64_t off = 0;
     auto carve = [&](int64_t bytes) { int64_t o = off; off += rup(bytes, 256); return o; };
-    const int64_t oX = carve(c->Mpad * D * E), oXn = carve(c->Mpad * D * E), oQKV = carve(c->Mpad * 3 * D * E);
-    const int64_t oH = carve(c->Mpad * 4 * D * E);
+    // runtime LoRA: the rows of Xn and Hb have room for T = x . A^T behind column K (3 lr / lr columns)
+    const int64_t oX = carve(c->Mpad * D * E), oXn = carve(c->Mpad * (D + 3 * c->lr) * E), oQKV = carve(c->Mpad * 3 * D * E);
+    const int64_t oH = carve(c->Mpad * (4 * D + c->lr) * E);
     const int64_t oVT = carve((int64_t)B * (c->cfg.num_heads / c->sp) * 64 * c->ntok_pad * 2);
     const int64_t oe0 = carve(rup((int64_t)B * T + 128, 128) * D * E), oe1 = carve(rup(c->gR + 128, 128) * D * E);
     const int64_t opat = carve(BVg * Cin4 * E), otail = carve(BVp * D * E), oproj = carve(BVp * Cout4 * E);
@@ -876,12 +956,22 @@ static bool attn_mx_out(const s2v_ctx* c) {
     return mx;
 }
 // w: the layer's weights -- c's own, or another context's of the same dtype / heads / weight_format (s2v_attn_forward_with)
-static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false) {
+// runtime LoRA: T = rnd(x . A^T) into the columns [K, K + N) of the rows of x (lora.hip); the GEMM that follows runs with K' = K + N
+static int lora_down(s2v_ctx* c, char* x, int ldx, const char* A, int N, int K, hipStream_t st) {
+    LoraDownArgs a{};
+    a.x = x; a.ldx = ldx; a.A = A; a.lda = K; a.out = x + (int64_t)K * c->esz; a.ldo = ldx; a.M = (int)c->M; a.N = N; a.K = K;
+    ProfScope ps(c, PK_LORA, st);
+    return launch_lora_down(a, c->dtype, (c->mfma || c->h16) && K % 64 == 0, st);
+}
+
+// lora: the weights carry an attached adapter (their context's lora_names is not empty)
+static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false) {
     // Xn -> QKV -> (qk-norm, rope, V^T) -> attention -> Xn (reused as the attention output buffer)
-    const int D = c->D;
+    const int D = c->D, pX = D + 3 * c->lr;
+    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_qkv, 3 * c->lr, D, st));
     GemmArgs g{};
-    g.A = c->Xn; g.lda = D; g.W = w.wqkv; g.ldw = D; g.bias = w.bqkv;
-    g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = D;
+    g.A = c->Xn; g.lda = pX; g.W = w.wqkv; g.ldw = pX; g.bias = w.bqkv;
+    g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = lora ? pX : D;
     // MFMA path: the per-head LayerNorm + rotary embedding of q and k run in the projection's epilogue (EPI_BIAS_QKNORM), on the
     // rounded projection as the stand-alone kernel does; only the V^T production remains a pass of its own
     // fp8 QK^T (weight_format 2 / 3 beyond its token threshold): q and k reach the attention kernel only as MX e4m3 images, so their LayerNorm + rotary
@@ -922,7 +1012,7 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
         S2V_TRY(launch_qk_norm_rope(q, c->dtype, st));
     }
     AttnArgs a{};
-    a.qkv = c->QKV; a.ld_qkv = 3 * D; a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Xn; a.ld_out = D;
+    a.qkv = c->QKV; a.ld_qkv = 3 * D; a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Xn; a.ld_out = pX;
     a.B = c->B; a.H = c->cfg.num_heads; a.Ntok = c->Ntok; a.scale = 0.125f;
     a.queue = c->attn_queue; a.num_cus = c->num_cus;  // launches of one context are ordered on its stream: one queue suffices
     a.p16 = p16 ? 1 : 0;
@@ -966,7 +1056,7 @@ static int block_norm(s2v_ctx* c, int l, int half, const char* mod_base /* [B][m
     const int64_t E = c->esz;
     const char* mb = mod_base + (int64_t)half * c->mc * D * E;
     LnModArgs n{};
-    n.x = c->X; n.ldx = D; n.y = c->Xn; n.ldy = D;
+    n.x = c->X; n.ldx = D; n.y = c->Xn; n.ldy = D + 3 * c->lr;
     n.w = half ? w.ln2_w : w.ln1_w; n.b = half ? w.ln2_b : w.ln1_b; n.eps = c->cfg.norm_eps;
     n.shift_vid = mb; n.scale_vid = mb + D * E; n.shift_txt = mb + 3 * D * E; n.scale_txt = mb + 4 * D * E;
     n.mod_stride = (int)mod_stride; n.B = c->B; n.Ntok = c->Ntok; n.text_len = c->T; n.D = D;
@@ -996,8 +1086,10 @@ static GemmArgs block_gate(const s2v_ctx* c, int half, const char* mod_base, int
 
 static int block_out_proj(s2v_ctx* c, int l, GemmArgs g, hipStream_t st) {
     const LayerW& w = c->layers[l];
-    const int D = c->D;
-    g.A = c->Xn; g.lda = D; g.W = w.wo; g.ldw = D; g.bias = w.bo; g.K = D;
+    const int D = c->D, pX = D + 3 * c->lr;
+    const bool lora = c->lora_on();
+    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
+    g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.K = lora ? D + c->lr : D;
     if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
     ProfScope ps(c, PK_OUT, st);
     if (c->fp8) return linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_o, w.s_o, st);
@@ -1006,10 +1098,12 @@ static int block_out_proj(s2v_ctx* c, int l, GemmArgs g, hipStream_t st) {
 
 static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st) {
     const LayerW& w = c->layers[l];
-    const int D = c->D;
+    const int D = c->D, pX = D + 3 * c->lr, pH = 4 * D + c->lr;
+    const bool lora = c->lora_on();
+    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_1, c->lr, D, st));
     GemmArgs f{};
-    f.A = c->Xn; f.lda = D; f.W = w.w1; f.ldw = D; f.bias = w.b1; f.C = c->Hb; f.ldc = 4 * D;
-    f.M = (int)c->M; f.N = 4 * D; f.K = D;
+    f.A = c->Xn; f.lda = pX; f.W = w.w1; f.ldw = D + c->lr; f.bias = w.b1; f.C = c->Hb; f.ldc = pH;
+    f.M = (int)c->M; f.N = 4 * D; f.K = lora ? D + c->lr : D;
     bool mx = c->fp8 && (4 * D) % 128 == 0;
 #ifdef S2V_DIAG
     mx = mx && g_fp8_mx;
@@ -1020,7 +1114,8 @@ static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st
         if (c->fp8) S2V_TRY(linear_fp8(c, f, EPI_BIAS_GELU, w.q_1, w.s_1, st, prequant));
         else S2V_TRY(linear(c, f, EPI_BIAS_GELU, st));
     }
-    g.A = c->Hb; g.lda = 4 * D; g.W = w.w2; g.ldw = 4 * D; g.bias = w.b2; g.K = 4 * D;
+    if (lora) S2V_TRY(lora_down(c, c->Hb, pH, w.a_2, c->lr, 4 * D, st));
+    g.A = c->Hb; g.lda = pH; g.W = w.w2; g.ldw = pH; g.bias = w.b2; g.K = lora ? pH : 4 * D;
     if (mx) { g.A = c->hq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
     ProfScope ps(c, PK_FF2, st);
     if (c->fp8) return linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_2, w.s_2, st);
@@ -1034,7 +1129,7 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
         S2V_TRY(block_norm(c, l, half, mod_base, mod_stride, st, &prequant));
         const GemmArgs g = block_gate(c, half, mod_base, mod_stride);
         if (half == 0) {
-            S2V_TRY(run_attention(c, c->layers[l], st, prequant));
+            S2V_TRY(run_attention(c, c->layers[l], st, prequant, c->lora_on()));
             S2V_TRY(block_out_proj(c, l, g, st));
         } else {
             S2V_TRY(block_ff(c, l, g, prequant, st));
@@ -1143,18 +1238,19 @@ extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, 
 }
 
 // the AttnProcessor seam on c's geometry and workspace with the weights w (c's own layer, or another context's)
-static int attn_forward_impl(s2v_ctx* c, const LayerW& w, const void* hidden, const void* encoder, void* out_hidden, void* out_encoder,
+static int attn_forward_impl(s2v_ctx* c, const LayerW& w, bool lora, const void* hidden, const void* encoder, void* out_hidden, void* out_encoder,
                              hipStream_t st) {
-    const int D = c->D, B = c->B, TR = c->T + c->R;
+    const int D = c->D, B = c->B, TR = c->T + c->R, pX = D + 3 * c->lr;
     const int64_t E = c->esz;
     for (int b = 0; b < B; ++b) {
-        char* xb = c->Xn + (int64_t)b * c->Ntok * D * E;
-        S2V_TRY(launch_copy_rows((const char*)encoder + (int64_t)b * TR * D * E, D, nullptr, 0, xb, D, TR, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows((const char*)hidden + (int64_t)b * c->V * D * E, D, nullptr, 0, xb + (int64_t)TR * D * E, D, c->V, D, c->dtype, st));
+        char* xb = c->Xn + (int64_t)b * c->Ntok * pX * E;
+        S2V_TRY(launch_copy_rows((const char*)encoder + (int64_t)b * TR * D * E, D, nullptr, 0, xb, pX, TR, D, c->dtype, st));
+        S2V_TRY(launch_copy_rows((const char*)hidden + (int64_t)b * c->V * D * E, D, nullptr, 0, xb + (int64_t)TR * pX * E, pX, c->V, D, c->dtype, st));
     }
-    S2V_TRY(run_attention(c, w, st));
+    S2V_TRY(run_attention(c, w, st, false, lora));
+    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
     GemmArgs g{};
-    g.A = c->Xn; g.lda = D; g.W = w.wo; g.ldw = D; g.bias = w.bo; g.C = c->Hb; g.ldc = D; g.M = (int)c->M; g.N = D; g.K = D;
+    g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.C = c->Hb; g.ldc = D; g.M = (int)c->M; g.N = D; g.K = lora ? D + c->lr : D;
     if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
     if (c->fp8) S2V_TRY(linear_fp8(c, g, EPI_BIAS, w.q_o, w.s_o, st));  // the same operands run_block feeds its out-projection
     else S2V_TRY(linear(c, g, EPI_BIAS, st));
@@ -1172,7 +1268,7 @@ extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, c
     S2V_REQUIRE(!c->shard, "s2v_attn_forward: a shard context (s2v_set_shard) runs the staged step only");
     S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_attn_forward: bad layer");
     S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward: null argument");
-    return attn_forward_impl(c, c->layers[layer], hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
+    return attn_forward_impl(c, c->layers[layer], c->lora_on(), hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
 }
 
 extern "C" int s2v_attn_forward_with(s2v_ctx* c, const s2v_ctx* wc, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
@@ -1184,9 +1280,148 @@ extern "C" int s2v_attn_forward_with(s2v_ctx* c, const s2v_ctx* wc, int32_t laye
     S2V_REQUIRE(wc->dtype == c->dtype, "s2v_attn_forward_with: the weights context has another dtype");
     S2V_REQUIRE(wc->cfg.num_heads == c->cfg.num_heads && wc->D == c->D, "s2v_attn_forward_with: the weights context has another num_heads / inner dim");
     S2V_REQUIRE(wc->cfg.weight_format == c->cfg.weight_format, "s2v_attn_forward_with: the weights context has another weight_format");
+    S2V_REQUIRE(wc->lora_cap == c->lora_cap, "s2v_attn_forward_with: the weights context has another lora_runtime_rank (the workspace owns the activation "
+                                             "pitch, the weights context the tails and the A stacks: create both with the same value)");
     S2V_REQUIRE(layer >= 0 && layer < (int)wc->layers.size(), "s2v_attn_forward_with: bad layer");
     S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward_with: null argument");
-    return attn_forward_impl(c, wc->layers[layer], hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
+    return attn_forward_impl(c, wc->layers[layer], wc->lora_on(), hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
+}
+
+// ---- runtime LoRA: attach / rescale / detach after s2v_finalize_weights (include/s2v_hip.h) ---------------------------------------------
+static int lora_checks(s2v_ctx* c, const char* fn) {
+    static thread_local std::string m;
+    auto fail = [&](const char* why) { m = std::string(fn) + ": " + why; return s2v_fail(__FILE__, __LINE__, m.c_str(), -1); };
+    if (c->lora_cap == 0) return fail("the runtime adapter mode is off (lora_runtime_rank = 0: this context merges LoRA at load time, s2v_merge_lora)");
+    if (c->cfg.weight_format != 0) return fail("fp8 weight formats have no runtime adapter branch (weight_format must be 0, the model dtype)");
+    if (c->shard) return fail("a shard context (s2v_set_shard) does not support runtime adapters");
+    if (c->kind == S2V_CTX_ATTN_WORKSPACE) return fail("a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
+    if (!c->finalized) return fail("the weights are not finalized (before s2v_finalize_weights use s2v_merge_lora)");
+    return 0;
+}
+
+// the base copy of a re-merged slot: same offset inside the copy of its region
+static char* lora_base_of(s2v_ctx* c, const char* live) {
+    if (live >= c->mod_w && live < c->mod_w + c->base_mod_bytes) return c->base_mod + (live - c->mod_w);
+    if (live >= c->patch_w && live < c->patch_w + c->base_patch_bytes) return c->base_patch + (live - c->patch_w);
+    if (live >= c->text_w && live < c->text_w + c->base_text_bytes) return c->base_text + (live - c->text_w);
+    return nullptr;
+}
+
+// the values of one adapter: branch weights get A into the stack (with_a) and rnd(scale * B) into the tail; re-merged weights are rebuilt
+// from their base copy with s2v_merge_lora's arithmetic
+static int lora_write(s2v_ctx* c, const char* name, Slot& s, const float* A, const float* B, int rank, float scale, bool with_a, hipStream_t st) {
+    const int64_t E = c->esz;
+    if (s.lora == LORA_BRANCH) {
+        if (with_a) S2V_TRY(launch_lora_pack_a(A, rank, c->lr, (int)s.cols, s.lora_a, s.cols, c->dtype, st));
+        return launch_lora_pack_b(B, rank, c->lr, (int)s.rows, scale, s.dst + s.tail_col * E, s.ld, c->dtype, st);
+    }
+    char* base = lora_base_of(c, s.dst);
+    S2V_REQUIRE(base, "s2v_lora_attach: no base copy for this weight");
+    const int64_t bytes = s.rows * s.ld * E;
+    S2V_CHECK_HIP(hipMemcpyAsync(s.dst, base, (size_t)bytes, hipMemcpyDeviceToDevice, st));
+    // lora_adaln_scope 1: the reference-image copy of chunks 0-2 sits right behind the six chunks and starts as their base values
+    if (c->mc == 9 && is_adaln_linear(name)) S2V_CHECK_HIP(hipMemcpyAsync(s.dst + bytes, base, (size_t)(bytes / 2), hipMemcpyDeviceToDevice, st));
+    // patch_embed.proj / text_proj made the hoisted conditioning: it has to be set again (a captured step reads the buffers it rewrites)
+    if (!is_adaln_linear(name)) c->have_cond = false;
+    return merge_into(c, name, s, A, B, rank, scale, st);
+}
+
+static int lora_find(s2v_ctx* c, const char* fn, const char* name, int rank, Slot** out) {
+    static thread_local std::string m;
+    auto it = c->slots.find(name);
+    if (it == c->slots.end() || it->second.lora == LORA_NONE) {
+        m = std::string(fn) + (it == c->slots.end() ? ": unknown tensor name: " : ": not a LoRA target of this context: ") + name;
+        return s2v_fail(__FILE__, __LINE__, m.c_str(), -3);
+    }
+    if (rank > c->lora_cap) {
+        m = std::string(fn) + ": rank " + std::to_string(rank) + " is over the capacity lora_runtime_rank = " + std::to_string(c->lora_cap) + " of this context (" + name + ")";
+        return s2v_fail(__FILE__, __LINE__, m.c_str(), -1);
+    }
+    *out = &it->second;
+    return 0;
+}
+
+// the attached state into the arena (stream-ordered behind the values it describes)
+static int lora_write_hdr(s2v_ctx* c, hipStream_t st) {
+    c->lora_hdr_host[0] = (int32_t)(c->lora_names.size() + (size_t)c->lora_replica);
+    c->lora_hdr_host[1] = c->lora_rank;
+    memcpy(&c->lora_hdr_host[2], &c->lora_scale, sizeof(float));
+    S2V_CHECK_HIP(hipMemcpyAsync(c->lora_hdr, c->lora_hdr_host, sizeof(c->lora_hdr_host), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+static void lora_drop_graph(s2v_ctx* c) {
+    if (c->gexec) { (void)hipDeviceSynchronize(); hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+}
+
+extern "C" int s2v_lora_attach(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream) {
+    S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_lora_attach: bad argument");
+    S2V_TRY(lora_checks(c, "s2v_lora_attach"));
+    Slot* s = nullptr;
+    S2V_TRY(lora_find(c, "s2v_lora_attach", name, rank, &s));
+    S2V_TRY(lora_write(c, name, *s, A, B, rank, scale, true, (hipStream_t)stream));
+    lora_drop_graph(c);   // with the first adapter the adapted GEMMs change to K' = K + R: the captured step is re-captured at its next use
+    if (c->lora_replica) { c->lora_replica = 0; }   // a replica that attaches itself owns its state from here on
+    c->lora_names[name] = rank;
+    c->lora_rank = rank; c->lora_scale = scale;
+    return lora_write_hdr(c, (hipStream_t)stream);
+}
+
+extern "C" int s2v_lora_set_scale(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream) {
+    S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_lora_set_scale: bad argument");
+    S2V_TRY(lora_checks(c, "s2v_lora_set_scale"));
+    Slot* s = nullptr;
+    S2V_TRY(lora_find(c, "s2v_lora_set_scale", name, rank, &s));
+    auto it = c->lora_names.find(name);
+    S2V_REQUIRE(it != c->lora_names.end() && it->second == rank, "s2v_lora_set_scale: no adapter of this rank was attached under this name on this context (s2v_lora_attach)");
+    // values only: the same launches read the same addresses, a captured step stays valid
+    S2V_TRY(lora_write(c, name, *s, A, B, rank, scale, false, (hipStream_t)stream));
+    c->lora_scale = scale;
+    return lora_write_hdr(c, (hipStream_t)stream);
+}
+
+extern "C" int s2v_lora_detach(s2v_ctx* c, s2v_stream stream) {
+    S2V_REQUIRE(c, "s2v_lora_detach: null context");
+    S2V_TRY(lora_checks(c, "s2v_lora_detach"));
+    hipStream_t st = (hipStream_t)stream;
+    if (!c->lora_on()) return 0;
+    const int64_t D = c->D, E = c->esz, lr = c->lr, Dp = rup(D, 256);
+    const bool model = c->kind == S2V_CTX_MODEL;
+    for (auto& w : c->layers) {  // zero tails and A stacks: a later attach of fewer names must not meet these values
+        S2V_CHECK_HIP(hipMemset2DAsync(w.wqkv + D * E, (size_t)((D + 3 * lr) * E), 0, (size_t)(3 * lr * E), (size_t)rup(3 * D, 256), st));
+        S2V_CHECK_HIP(hipMemset2DAsync(w.wo + D * E, (size_t)((D + lr) * E), 0, (size_t)(lr * E), (size_t)Dp, st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_qkv, 0, (size_t)(3 * lr * D * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_o, 0, (size_t)(lr * D * E), st));
+        if (!model) continue;
+        S2V_CHECK_HIP(hipMemset2DAsync(w.w1 + D * E, (size_t)((D + lr) * E), 0, (size_t)(lr * E), (size_t)rup(4 * D, 256), st));
+        S2V_CHECK_HIP(hipMemset2DAsync(w.w2 + 4 * D * E, (size_t)((4 * D + lr) * E), 0, (size_t)(lr * E), (size_t)Dp, st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_1, 0, (size_t)(lr * D * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_2, 0, (size_t)(lr * 4 * D * E), st));
+    }
+    if (model) {
+        // the modulation stack interleaves, under lora_adaln_scope 1, the reference-image copies with the six chunks: rebuild slot by slot
+        for (auto& kv : c->slots) {
+            Slot& s = kv.second;
+            if (s.lora != LORA_REMERGE) continue;
+            char* base = lora_base_of(c, s.dst);
+            const int64_t bytes = s.rows * s.ld * E;
+            S2V_CHECK_HIP(hipMemcpyAsync(s.dst, base, (size_t)bytes, hipMemcpyDeviceToDevice, st));
+            if (c->mc == 9 && is_adaln_linear(kv.first.c_str())) S2V_CHECK_HIP(hipMemcpyAsync(s.dst + bytes, base, (size_t)(bytes / 2), hipMemcpyDeviceToDevice, st));
+        }
+    }
+    if (model) c->have_cond = false;   // patch_embed.proj / text_proj are the base again: s2v_set_conditioning comes next
+    lora_drop_graph(c);
+    c->lora_names.clear();
+    c->lora_replica = 0;
+    c->lora_rank = 0; c->lora_scale = 0.f;
+    return lora_write_hdr(c, st);
+}
+
+extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, float* scale, int64_t* graph_captures) {
+    S2V_REQUIRE(c && attached && rank && scale && graph_captures, "s2v_lora_state: null argument");
+    *attached = (int32_t)c->lora_names.size() + c->lora_replica;
+    *rank = c->lora_rank; *scale = c->lora_scale; *graph_captures = c->graph_captures;
+    return 0;
 }
 
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
@@ -1262,6 +1497,7 @@ extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const
         e = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
         hipGraphDestroy(graph);
         S2V_CHECK_HIP(e);
+        c->graph_captures++;
         c->gkey = key;
     }
     S2V_CHECK_HIP(hipGraphLaunch(c->gexec, st));
@@ -1307,6 +1543,7 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
         e = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
         hipGraphDestroy(graph);
         S2V_CHECK_HIP(e);
+        c->graph_captures++;
         c->gkey = key;
     }
     S2V_CHECK_HIP(hipGraphLaunch(c->gexec, st));
@@ -1722,6 +1959,58 @@ extern "C" int s2v_op_linear(const void* A, const void* W, const void* bias, voi
     }
     g.valu_only = 1;
     return launch_gemm_simple(g, epilogue, dtype, (hipStream_t)stream);
+}
+
+// One adapted linear as the runtime adapter mode runs it (s2v_lora_attach), on operands of its own: x and W are copied into scratch rows with room
+// for the K extension, A goes into a stack and rnd(scale * B) into W's tail (the attach-time kernels), the down-projection writes T behind x, and
+// the GEMM the engine's linear() would launch for this shape runs with K' = K + R.  Allocates its scratch; synchronous.
+extern "C" int s2v_op_linear_lora(const void* x, const void* W, const void* bias, const float* A, const float* B, int32_t rank, float scale, void* C,
+                                  int32_t M, int32_t N, int32_t K, int32_t epilogue, const void* aux0, const void* aux1, int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(x && W && A && B && C && rank > 0 && M > 0 && N > 0, "s2v_op_linear_lora: bad argument");
+    S2V_REQUIRE(dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_linear_lora: bf16 or fp16 (the dtypes whose linears run on the matrix cores)");
+    S2V_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GATE_RES || epilogue == EPI_BIAS_QKNORM,
+                "s2v_op_linear_lora: epilogue must be 0 (bias), 1 (GELU), 2 (gate + residual) or 4 (q/k-norm)");
+    S2V_REQUIRE(K % 64 == 0 && N % 8 == 0 && rank <= 128, "s2v_op_linear_lora: K a multiple of 64, N of 8, rank <= 128");
+    S2V_REQUIRE(epilogue != EPI_BIAS_GATE_RES || aux0, "s2v_op_linear_lora: epilogue 2 needs the gate vector [N] in aux0 (C is the residual, updated in place)");
+    S2V_REQUIRE(epilogue != EPI_BIAS_QKNORM || (aux0 && aux1 && N % 192 == 0), "s2v_op_linear_lora: epilogue 4 needs N = 3 * qk_D, LayerNorm weights [2][64] in aux0 and biases [2][64] in aux1");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t E = 2, R = rup(rank, K % 128 == 0 ? 128 : 64), Kx = K + R, Mp = rup(M, 256) + 256, Np = rup(N, 256);
+    const int64_t bx = rup(Mp * Kx * E, 256), bw = rup(Np * Kx * E, 256), ba = rup(R * K * E, 256);
+    char* ws = nullptr;
+    S2V_CHECK_HIP(hipMalloc((void**)&ws, (size_t)(bx + bw + ba)));
+    char *xe = ws, *we = ws + bx, *as = we + bw;
+    auto run = [&]() -> int {
+        S2V_CHECK_HIP(hipMemsetAsync(ws, 0, (size_t)(bx + bw + ba), st));
+        S2V_TRY(launch_convert2d(x, dtype, K, xe, dtype, Kx, M, K, st));
+        S2V_TRY(launch_convert2d(W, dtype, K, we, dtype, Kx, N, K, st));
+        S2V_TRY(launch_lora_pack_a(A, rank, (int)R, K, as, K, dtype, st));
+        S2V_TRY(launch_lora_pack_b(B, rank, (int)R, N, scale, we + (int64_t)K * E, Kx, dtype, st));
+        LoraDownArgs d{};
+        d.x = xe; d.ldx = (int)Kx; d.A = as; d.lda = K; d.out = xe + (int64_t)K * E; d.ldo = (int)Kx; d.M = M; d.N = (int)R; d.K = K;
+        S2V_TRY(launch_lora_down(d, dtype, true, st));
+        GemmArgs g{};
+        g.A = xe; g.lda = (int)Kx; g.W = we; g.ldw = (int)Kx; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = (int)Kx;
+        g.a_rows_padded = (int)rup(M, 256); g.w_rows_padded = (int)Np; g.f16 = dtype == S2V_DTYPE_F16 ? 1 : 0;
+        g.tok_per_batch = M; g.text_len = 0;
+        if (epilogue == EPI_BIAS_GATE_RES) { g.X = C; g.ldx = N; g.gate_vid = aux0; g.gate_txt = aux0; g.gate_stride = 0; }
+        if (epilogue == EPI_BIAS_QKNORM) {
+            g.qk_w[0] = aux0; g.qk_w[1] = (const char*)aux0 + 64 * E; g.qk_b[0] = aux1; g.qk_b[1] = (const char*)aux1 + 64 * E;
+            g.qk_cs = nullptr; g.qk_D = N / 3; g.qk_eps = 1e-6f;
+        }
+        const GemmPlan p = gemm_plan(g, epilogue, device_cus(), 0);  // the choice linear() makes, the row tail on the same stream
+        g.tile = p.tile;
+        if (p.tail != GEMM_NONE) {
+            GemmArgs gm = g, gt = g;
+            gm.M = p.m_main; gt.m_begin = p.m_main;
+            S2V_TRY(launch_gemm_bf16(gm, epilogue, st));
+            return launch_gemm_bf16(gt, epilogue, st);
+        }
+        return launch_gemm_bf16(g, epilogue, st);
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    return rc;
 }
 
 // C = epilogue(dequant(quant_rows(A) . quant_rows(W)^T) + bias): both bf16 operands are quantised per row to e4m3 (dynamic

@@ -138,6 +138,21 @@ GemmPlan gemm_plan(const GemmArgs& g, int epi, int ncu, int64_t sk_tiles);
 int launch_gemm_strided_f32(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbn, int64_t sbk,
                             float* C, int64_t ldc, int M, int N, int K, float alpha, hipStream_t st);
 
+// ---- runtime LoRA (lora.hip) ----------------------------------------------------
+// out[m][n] = rnd(sum_k x[m][k] * A[n][k]), fp32 accumulation: the adapter's down-projection.  x [M][K] (rows ldx apart), A [N][K] (the
+// layer's A stack, rows lda apart), out rows ldo apart -- in the engine `out` is column K of the buffer x lives in.
+struct LoraDownArgs {
+    const void* x; int ldx;
+    const void* A; int lda;
+    void* out; int ldo;
+    int M, N, K;
+};
+// mfma: the 16-bit model dtypes on v_mfma_f32_32x32x16_{bf16,f16} (N % 64 == 0, N <= 384, K % 64 == 0); otherwise the generic kernel
+int launch_lora_down(const LoraDownArgs& a, int dtype, bool mfma, hipStream_t st);
+// attach time: A [rank][K] fp32 -> `rows` rows of the stack (rows past rank zero); scale * B [N][rank] fp32 -> `cols` tail columns (past rank zero)
+int launch_lora_pack_a(const float* A, int rank, int rows, int K, void* dst, int64_t ldd, int dtype, hipStream_t st);
+int launch_lora_pack_b(const float* B, int rank, int cols, int N, float scale, void* dst, int64_t ldd, int dtype, hipStream_t st);
+
 // ---- attention ---------------------------------------------------------------
 // qkv: [B*Ntok (+pad), 3*D] rows = tokens; q at col h*64, k at col D+h*64, v at col 2D+h*64.
 // out: [B*Ntok, D] (col h*64+d).  softmax(q k^T / 8) v, no mask  (attention_processor.py:2083-2087)

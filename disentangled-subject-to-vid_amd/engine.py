@@ -46,7 +46,12 @@ class S2VEngine:
             raise _lib.S2VError(f"unknown attn_p_format {cfg.attn_p_format!r} ('bf16', 'f16' or 'auto')")
         c.attn_p_format = 0 if cfg.attn_p_format == "bf16" else 1
         c.reserved[0] = kind
+        c.reserved[1] = int(getattr(cfg, "lora_runtime_rank", 0) or 0)
         self.kind = kind
+        # runtime adapter mode: the attached adapter's fp32 device copies {name: (A2, B2)} (set_lora_scale re-reads them), and the last
+        # adapter attached with its current scale, kept across detach_lora so that enable_lora can put it back (lora_kept_bytes counts it)
+        self._lora = None
+        self._lora_last = None
         # "auto" (opt-in): start with fp16 P (faster on smooth score distributions) and look at the slow-path census after the first denoise
         # step of a geometry (re-armed by set_geometry); more than AUTO_SLOW_FRACTION of the (wave, KV tile) pairs on the slow path -> bf16 P
         # (threshold 2^64).  The census read synchronises the device (s2v_attn_slow_stats): the deciding step runs eagerly, never inside a
@@ -88,25 +93,126 @@ class S2VEngine:
 
     def load_state_dict(self, sd, lora=None, lora_scale=0.5):
         """sd: {reference state-dict key: tensor}; lora: {weight key: (A [r,in..], B [out,r])} merged as
-        W + lora_scale * B A (src/inference.py:218-229: alpha/r = 64/128)."""
+        W + lora_scale * B A (src/inference.py:218-229: alpha/r = 64/128).  In the runtime adapter mode (cfg.lora_runtime_rank > 0) the
+        base weights are finalized as they are and the adapter is attached (attach_lora) instead of merged."""
         for k, v in sd.items():
             if "pos_embedding" in k:
                 continue  # non-persistent buffer, rebuilt by tables.sincos_table
             self.load_weight(k, v)
-        known = None
+        if self.cfg.lora_runtime_rank > 0:
+            self.finalize_weights()
+            self.unexpected_lora_keys = []
+            if lora:
+                self.attach_lora(lora, lora_scale)
+            return
+        placed = self._place_lora(lora)
+        for k, (A, B) in placed.items():
+            self.merge_lora(k, A, B, lora_scale)
+        self.finalize_weights()
+
+    def _place_lora(self, lora):
+        """the adapter keys this model has; the others are reported as the reference does (src/inference.py:96-105) and skipped"""
+        known, placed = None, {}
         self.unexpected_lora_keys = []
-        for k, (A, B) in (lora or {}).items():
+        for k, ab in (lora or {}).items():
             if known is None:
                 from .weights import state_dict_shapes
                 known = set(state_dict_shapes(self.cfg))
             if k not in known:
-                # the reference only reports adapter keys it cannot place (src/inference.py:96-105) and carries on
                 self.unexpected_lora_keys.append(k)
                 continue
-            self.merge_lora(k, A, B, lora_scale)
+            placed[k] = ab
         if self.unexpected_lora_keys:
             print(f"Loading adapter weights led to unexpected keys not found in the model: {self.unexpected_lora_keys}")
-        self.finalize_weights()
+        return placed
+
+    # ---- runtime adapters (cfg.lora_runtime_rank > 0; include/s2v_hip.h, s2v_lora_*) --------------------------------------------------
+    def _lora_refusals(self, what, rank=0):
+        """the library's own refusals, taken before anything is changed (attach_lora detaches first): the state stays as it was"""
+        if self.cfg.lora_runtime_rank <= 0:
+            raise _lib.S2VError(f"{what}: the runtime adapter mode is off (lora_runtime_rank = 0: this engine merges LoRA at load time)")
+        if self.cfg.weight_format is not None:
+            raise _lib.S2VError(f"{what}: fp8 weight formats have no runtime adapter branch (weight_format {self.cfg.weight_format!r})")
+        if self.shard is not None:
+            raise _lib.S2VError(f"{what}: a shard engine (set_shard) does not support runtime adapters")
+        if rank > self.cfg.lora_runtime_rank:
+            raise _lib.S2VError(f"{what}: rank {rank} is over the capacity lora_runtime_rank = {self.cfg.lora_runtime_rank}")
+
+    def attach_lora(self, lora, scale=0.5):
+        """replace the attached adapter by lora = {weight key: (A [r, in..], B [out, r])} at `scale`, after finalize_weights: the six token
+        linears of every block run base + branch, the other targets are re-merged from their base copy; no base weight is touched"""
+        ranks = [int(A.shape[0]) for A, _ in lora.values()]
+        self._lora_refusals("attach_lora", max(ranks, default=0))
+        placed = self._place_lora(lora) if self.kind == _lib.CTX_MODEL else dict(lora)
+        dev = {k: (A.to(self.device).float().reshape(A.shape[0], -1).contiguous(), B.to(self.device).float().contiguous())
+               for k, (A, B) in placed.items()}
+        for k, (A2, B2) in dev.items():
+            if B2.ndim != 2 or B2.shape[1] != A2.shape[0]:
+                raise _lib.S2VError(f"attach_lora: {k}: A {tuple(A2.shape)} and B {tuple(B2.shape)} do not share a rank")
+        # every name is checked before anything changes: s2v_weight_slot knows the names of THIS context (an attention-weights context
+        # holds the attn1 keys only) and the base shapes
+        off, rows, cols, ld = (ctypes.c_int64() for _ in range(4))
+        for k, (A2, B2) in dev.items():
+            _lib.check(_lib.lib().s2v_weight_slot(self._h, k.encode(), ctypes.byref(off), ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(ld)))
+            if (B2.shape[0], A2.shape[1]) != (rows.value, cols.value):
+                raise _lib.S2VError(f"attach_lora: {k}: B A is {B2.shape[0]} x {A2.shape[1]}, the weight is {rows.value} x {cols.value}")
+        _lib.check(_lib.lib().s2v_lora_detach(self._h, _lib.stream_ptr()))
+        self._lora = None
+        try:
+            for k, (A2, B2) in dev.items():
+                _lib.check(_lib.lib().s2v_lora_attach(self._h, k.encode(), _lib.ptr(A2), _lib.ptr(B2), A2.shape[0], float(scale), _lib.stream_ptr()))
+        except Exception:
+            # a refusal part way (a name that is no LoRA target of this context): never half attached -- the base model, loudly
+            _lib.lib().s2v_lora_detach(self._h, _lib.stream_ptr())
+            self._lora_changed()
+            raise
+        self._lora = dev
+        self._lora_last = (dev, float(scale))
+        self._lora_changed()
+
+    def set_lora_scale(self, scale):
+        """the attached adapter at another scale: bit for bit what attach_lora(lora, scale) gives; a captured denoise step is kept"""
+        self._lora_refusals("set_lora_scale")
+        if not self._lora:
+            raise _lib.S2VError("set_lora_scale: no adapter is attached")
+        for k, (A2, B2) in self._lora.items():
+            _lib.check(_lib.lib().s2v_lora_set_scale(self._h, k.encode(), _lib.ptr(A2), _lib.ptr(B2), A2.shape[0], float(scale), _lib.stream_ptr()))
+        self._lora_last = (self._lora, float(scale))
+        self._lora_changed()
+
+    def detach_lora(self):
+        """the base model"""
+        self._lora_refusals("detach_lora")
+        _lib.check(_lib.lib().s2v_lora_detach(self._h, _lib.stream_ptr()))
+        self._lora = None
+        self._lora_changed()
+
+    def enable_lora(self):
+        """put back the adapter that was attached last (attach_lora, load_state_dict, checkpoint.swap_lora) at the scale it had last"""
+        self._lora_refusals("enable_lora")
+        if self._lora is not None:
+            return
+        if self._lora_last is None:
+            raise _lib.S2VError("enable_lora: no adapter has been attached to this engine")
+        self.attach_lora(*self._lora_last)
+
+    def forget_lora(self):
+        """drop the kept fp32 copies of a detached adapter (enable_lora then has nothing to put back)"""
+        if self._lora is None:
+            self._lora_last = None
+
+    @property
+    def lora_kept_bytes(self):
+        """device bytes of the fp32 A / B copies this engine keeps for set_lora_scale / enable_lora (torch tensors: outside s2v_device_bytes)"""
+        kept = self._lora_last[0] if self._lora_last else (self._lora or {})
+        return sum(A.numel() * 4 + B.numel() * 4 for A, B in kept.values())
+
+    @property
+    def lora_state(self):
+        """{"attached": names attached, "rank", "scale": of the last attach / rescale, "graph_captures": hipGraph captures so far}"""
+        n, r, s, g = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_float(), ctypes.c_int64()
+        _lib.check(_lib.lib().s2v_lora_state(self._h, ctypes.byref(n), ctypes.byref(r), ctypes.byref(s), ctypes.byref(g)))
+        return {"attached": n.value, "rank": r.value, "scale": s.value, "graph_captures": g.value}
 
     def merge_lora(self, name, A, B, scale):
         """W[name] += scale * B A (s2v_merge_lora: A [r, in..] and B [out, r] as fp32, after load_weight(name), before finalize_weights)"""
@@ -173,6 +279,7 @@ class S2VEngine:
                 self.set_attn_p_format("f16")
             self._attn_auto_pending = True
         self._rope_key, self.have_rope = None, None
+        self._cond_args = None
         self._bump("rope", "cond")
 
     def clear_rope(self):
@@ -238,7 +345,16 @@ class S2VEngine:
             raise _lib.S2VError("ref_img_states must be [1,1,C,H,W] with the geometry's H, W")
         _lib.check(_lib.lib().s2v_set_conditioning(self._h, _lib.ptr(text), _lib.ptr(ref), _lib.stream_ptr()))
         torch.cuda.current_stream().synchronize()
+        self._cond_args = (text, ref) if self.cfg.lora_runtime_rank > 0 else None
         self._bump("cond")
+
+    _cond_args = None
+
+    def _lora_changed(self):
+        """patch_embed.proj / text_proj may have been re-merged: the hoisted conditioning is computed again from the inputs it was set with"""
+        torch.cuda.current_stream().synchronize()
+        if self.kind == _lib.CTX_MODEL and self._cond_args is not None and self.geometry is not None:
+            self.set_conditioning(*self._cond_args)
 
     # ---- compute -------------------------------------------------------------------------------------------
     def forward(self, latents, timesteps, shared_latent=False):

@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from .config import TransformerConfig
 from .engine import S2VEngine
+from .weights import concat_lora
 
 
 def _rope_pair(image_rotary_emb, ref_image_rotary_emb, R):
@@ -76,6 +77,17 @@ class HipCogVideoXTransformer3DModel:
 
     def load_state_dict(self, sd, lora=None, lora_scale=0.5, strict=True):
         self.engine.load_state_dict(sd, lora, lora_scale)
+
+    # PEFT's switches on a runtime-mode model (TransformerConfig.lora_runtime_rank > 0); the engine refuses them with the mode off.  The
+    # engine alone knows which adapter was attached last and at which scale (load_state_dict, engine.attach_lora, checkpoint.swap_lora)
+    def set_adapters_scale(self, scale):
+        self.engine.set_lora_scale(scale)
+
+    def disable_adapters(self):
+        self.engine.detach_lora()
+
+    def enable_adapters(self):
+        self.engine.enable_lora()
 
     def __call__(self, hidden_states, ref_img_states=None, encoder_hidden_states=None, timestep=None,
                  timestep_cond=None, image_rotary_emb=None, ref_image_rotary_emb=None, attention_kwargs=None,
@@ -161,10 +173,11 @@ def _is_tuner_layer(mod):
     return all(hasattr(mod, a) for a in _TUNER_ATTRS)
 
 
-def _attn_state(attn):
+def _attn_state(attn, split=False):
     """[(key name, base weight, base bias, [(A [r, in], B [out, r], scale) of the adapters to merge])] of the six attn1 parts, and the flat list
-    of what the weights depend on (tensors and adapter settings) that _AttnPool keys a module's slot on"""
-    parts, deps = [], []
+    of what the weights depend on (tensors and adapter settings) that _AttnPool keys a module's slot on.  split (lora="runtime"): the list
+    comes as (base weights and whether they hold a merged delta, adapter tensors and settings): a change of the second re-attaches, it does not re-pack"""
+    parts, deps, base_deps = [], [], []
     for name, get in _ATTN_PARTS:
         mod = get(attn)
         deltas = []
@@ -174,6 +187,7 @@ def _attn_state(attn):
             active = mod.active_adapters
             active = [active] if isinstance(active, str) else list(active)
             deps += [merged, disabled, tuple(active)]
+            base_deps.append(merged)
             if not merged and not disabled:  # merged: the delta is in base_layer.weight already; disabled: the base layer alone
                 for a in active:
                     if a not in mod.lora_A:
@@ -187,6 +201,10 @@ def _attn_state(attn):
             base = mod
         parts.append((name, base.weight, base.bias, deltas))
         deps += [base.weight, base.bias]
+        base_deps += [base.weight, base.bias]
+    if split:
+        nb = set(map(id, base_deps))
+        return parts, (base_deps, [d for d in deps if not (torch.is_tensor(d) and id(d) in nb)])
     return parts, deps
 
 
@@ -206,15 +224,67 @@ class _AttnPool:
     workspace, rotary tables: S2V_CTX_ATTN_WORKSPACE) with its own attention-weights engine (the module's attn1 weights alone, re-packed
     as a model packs them: S2V_CTX_ATTN_WEIGHTS), through s2v_attn_forward_with."""
 
-    def __init__(self, heads, dtype, device, force_simple):
+    def __init__(self, heads, dtype, device, force_simple, lora_runtime_rank=0):
+        # the workspace engine owns the activation pitch, every weights engine the tails and the A stacks: one lora_runtime_rank for all
         self.cfg = TransformerConfig(num_layers=1, num_attention_heads=heads, time_embed_dim=8, text_embed_dim=64,
-                                     use_rotary_positional_embeddings=True)
+                                     use_rotary_positional_embeddings=True, lora_runtime_rank=lora_runtime_rank)
         self.dtype, self.device, self.force_simple = dtype, device, force_simple
         self.engine = S2VEngine(self.cfg, dtype, device, force_simple, kind=_lib.CTX_ATTN_WORKSPACE)
         self.slots = {}       # id(attn) -> (weights engine, key, attn); the module is kept alive: id(attn) stays unique
         self.geometry_changes = 0
 
+    def weights_for_runtime(self, attn):
+        """lora="runtime": the slot keys the base weights and the adapter separately -- (weights engine, (base key, adapter key), attn).  A changed
+        scaling, disable_adapters or another active adapter re-attaches (the tails and A stacks: megabytes) on the SAME weights engine"""
+        parts, (base_deps, ad_deps) = _attn_state(attn, split=True)
+        slot = self.slots.get(id(attn))
+        p = "transformer_blocks.0.attn1."
+        if slot is not None and _same_key(slot[1][0], base_deps):
+            eng = slot[0]
+            if _same_key(slot[1][1], ad_deps):
+                return eng
+        else:
+            eng = None
+        # the capacity is checked before anything is allocated or changed
+        lora, cap = {}, self.cfg.lora_runtime_rank
+        for name, _, _, deltas in parts:
+            if not deltas:
+                continue
+            total = sum(int(A.shape[0]) for A, _, _ in deltas)
+            if total > cap:
+                raise _lib.S2VError(f"{name}: the active adapters' ranks sum to {total}, over the capacity lora_runtime_rank = {cap} "
+                                    f"(several active adapters are concatenated along r)")
+            # several active adapters on one layer: [A_1; A_2], [s_1 B_1 | s_2 B_2] at scale 1 is the sum of the branches
+            lora[p + name + ".weight"] = concat_lora([(A.detach(), B.detach(), sc) for A, B, sc in deltas])
+        fresh = eng is None
+        if fresh:
+            eng = S2VEngine(self.cfg, self.dtype, self.device, self.force_simple, kind=_lib.CTX_ATTN_WEIGHTS)
+        try:
+            if fresh:
+                for name, w, b, _ in parts:
+                    eng.load_weight(p + name + ".weight", w.detach())
+                    eng.load_weight(p + name + ".bias", b.detach())
+                eng.finalize_weights()
+            if lora:
+                eng.attach_lora(lora, 1.0)
+            elif eng.lora_state["attached"]:
+                eng.detach_lora()
+        except Exception:
+            if fresh:
+                eng.close()               # the old slot, if any, stays as it was
+            else:
+                self.slots.pop(id(attn))  # attach_lora left it detached: the next call re-packs
+                eng.close()
+            raise
+        eng.forget_lora()                 # the module owns its adapter tensors: no second copy kept for a detached context
+        if fresh and slot is not None:
+            slot[0].close()
+        self.slots[id(attn)] = (eng, (_dep_key(base_deps), _dep_key(ad_deps)), attn)
+        return eng
+
     def weights_for(self, attn):
+        if self.cfg.lora_runtime_rank > 0:
+            return self.weights_for_runtime(attn)
         parts, deps = _attn_state(attn)
         slot = self.slots.get(id(attn))
         if slot is not None and _same_key(slot[1], deps):
@@ -266,17 +336,26 @@ class HipCogVideoXAttnProcessor2_0:
     disable_adapters) are honoured by merging W + sum over the active adapters of scaling[a] * B_a A_a into the module's weights context
     (s2v_merge_lora, fp32 A and B, rounded once per adapter to the model dtype) with the bias of base_layer; nothing is added when
     `merged` (the delta is in base_layer.weight already), the base layer alone when `disable_adapters`.  This is the merge the engine
-    applies to checkpoints: the reference adds the adapter branch at run time, so parity is unpinned for the PEFT
-    runtime path.  DoRA adapters raise NotImplementedError."""
+    applies to checkpoints and the default, lora="merge": it costs nothing per call.
 
-    def __init__(self, force_simple=False):
+    lora="runtime" runs the adapter as the reference does, as a branch beside the base weights (include/s2v_hip.h, s2v_lora_attach:
+    T = rnd(x A^T), rnd(s B) in the weight's tail, one fp32 accumulator under the unchanged epilogue): a tuner layer that is unmerged and
+    enabled is ATTACHED to the module's weights context, whose slot keys the base weights and the adapter separately, so a changed scaling,
+    disable_adapters or another active adapter re-attaches and does not re-pack the module.  Several active adapters on one layer are
+    concatenated along r while their ranks sum to at most lora_runtime_rank (S2VError otherwise).  The PEFT runtime path is pinned by
+    tests/test_gpu_lora_runtime.py against PEFT's Linear.forward restated in fp32.  DoRA adapters raise NotImplementedError in both modes."""
+
+    def __init__(self, force_simple=False, lora="merge", lora_runtime_rank=128):
+        if lora not in ("merge", "runtime"):
+            raise ValueError(f"lora must be 'merge' or 'runtime', got {lora!r}")
         self._force_simple = force_simple
+        self._rank = int(lora_runtime_rank) if lora == "runtime" else 0
         self._keys = set()
 
     def _pool_for(self, attn, dtype, device, D):
-        key = (device, dtype, attn.heads, D, self._force_simple)
+        key = (device, dtype, attn.heads, D, self._force_simple) + ((self._rank,) if self._rank else ())
         if key not in _POOLS:
-            _POOLS[key] = _AttnPool(attn.heads, dtype, device, self._force_simple)
+            _POOLS[key] = _AttnPool(attn.heads, dtype, device, self._force_simple, self._rank)
         self._keys.add(key)
         return _POOLS[key]
 

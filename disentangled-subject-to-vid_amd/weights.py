@@ -93,6 +93,17 @@ def synthetic_lora(cfg, rank=128, seed=99, device="cpu", std=0.02):
     return out
 
 
+def concat_lora(adapters):
+    """several adapters active on one layer as ONE adapter of the summed rank: adapters = [(A_i [r_i, in..], B_i [out, r_i], s_i)] ->
+    (A, B) with A = [A_1; A_2; ...] stacked along r and B = [s_1 B_1 | s_2 B_2 | ...], to be attached at scale 1:
+    B . (A x) = sum_i s_i B_i (A_i x), the sum of the branches (fp32 tensors; the scales are folded in fp32)"""
+    if not adapters:
+        raise ValueError("concat_lora: no adapter")
+    A = torch.cat([a.float().reshape(a.shape[0], -1) for a, _, _ in adapters], dim=0)
+    B = torch.cat([float(s) * b.float() for _, b, s in adapters], dim=1)
+    return A, B
+
+
 def vae_decoder_shapes(cfg):
     """state-dict keys/shapes of AutoencoderKLCogVideoX.decoder (autoencoder_kl_cogvideox.py:860-919)"""
     rc = list(reversed(cfg.block_out_channels))

@@ -77,7 +77,11 @@ typedef struct s2v_model_config {
                                *     adds on the P registers, flushed to fp32 per KV tile; the deferred maximum falls to 2^14, i.e. the slow
                                *     path re-adopts the row maximum when a later score exceeds it by ~9.7 natural units -- faster on smooth
                                *     score distributions, slower on spiky ones; tests/test_gpu_parity.py holds both against fp64 SDPA) */
-    int32_t reserved[2];      /* reserved[0]: the kind of context s2v_create makes (S2V_CTX_*, 0 = a whole model); reserved[1]: 0 */
+    int32_t reserved[2];      /* reserved[0]: the kind of context s2v_create makes (S2V_CTX_*, 0 = a whole model);
+                               * reserved[1] = lora_runtime_rank: 0 = LoRA exists only as the load-time merge (s2v_merge_lora; the default: it costs
+                               *     nothing per step); r in 1 .. 128 = the runtime adapter mode with room for adapters of rank <= r per layer
+                               *     (s2v_lora_attach below): the arena and the workspace are carved larger, the arithmetic without an adapter is
+                               *     unchanged */
 } s2v_model_config;
 
 /* reserved[0] of s2v_model_config.  The AttnProcessor seam installed on every Attention module of a model
@@ -110,7 +114,8 @@ S2V_API int s2v_load_weight(s2v_ctx* ctx, const char* name, const void* dev_ptr,
  * Must be called after s2v_load_weight(name) and before s2v_finalize_weights. */
 S2V_API int s2v_merge_lora(s2v_ctx* ctx, const char* name, const float* A, const float* B, int32_t rank, float scale,
                    s2v_stream stream);
-/* Checks that every tensor was loaded; after this call the weights are immutable. */
+/* Checks that every tensor was loaded; after this call the base weights are immutable (a runtime-mode context then takes adapters:
+ * s2v_lora_attach). */
 S2V_API int s2v_finalize_weights(s2v_ctx* ctx, s2v_stream stream);
 /* Total bytes of context-owned weights (for the broadcast) and access to the packed arena so that ONE
  * collective can replicate a finalized model rank0 -> all. */
@@ -119,6 +124,41 @@ S2V_API int s2v_weight_arena(s2v_ctx* ctx, void** dev_ptr, int64_t* bytes);
  * in elements of the model dtype (rows of the fused QKV / stacked modulation buffers are `ld` apart).  What a checkpoint tool
  * needs to read a merged weight back (W + (alpha/r) B A of src/inference.py:218-229) without knowing the packing. */
 S2V_API int s2v_weight_slot(s2v_ctx* ctx, const char* name, int64_t* offset_bytes, int64_t* rows, int64_t* cols, int64_t* ld);
+
+/* ---- runtime adapters (lora_runtime_rank = reserved[1] > 0): what the reference's PEFT model does, the adapter NOT merged -----------------
+ * src/inference.py:218-229 attaches the subject-LoRA with PEFT and never merges it: every adapted Linear computes
+ * base(x) + scaling * lora_B(lora_A(x)) at run time.  In this mode the six token linears of every block -- attn1.to_q / to_k / to_v (the fused
+ * QKV), attn1.to_out.0, ff.net.0.proj, ff.net.2 -- run the branch beside the base weight, for W [N, K], A [r, K], B [N, r], scale s:
+ *     T  = rnd(x . A^T)                     a down-projection kernel of its own; the point where PEFT rounds lora_A's output
+ *     Bs = rnd(s * B)                       once, at attach / rescale time, the product taken in fp32
+ *     y  = epilogue(x . W^T + T . Bs^T + b) ONE fp32 accumulator under the unchanged epilogue (q/k-norm + RoPE, GELU, gate + residual)
+ * as a K extension of the base GEMM: y = [x | T] . [W | Bs]^T with K' = K + R (R = the rank padded to 64 / 128 with zero columns; the fused
+ * QKV carries a block-diagonal tail of 3 R).  Without an adapter the launches use K and produce the bytes of a lora_runtime_rank = 0 context.
+ * The other LoRA targets (patch_embed.proj, patch_embed.text_proj, norm{1,2}.linear: two rows, hoisted conditioning, or K = 64 < r) are
+ * RE-MERGED: the context keeps a base copy of them and attach / rescale / detach rebuild the live weight from it with s2v_merge_lora's
+ * arithmetic, so their bytes equal a merged context's (lora_adaln_scope 1 included).  Tails, A stacks and base copies live inside the weight
+ * arena: s2v_weight_arena, s2v_bcast_weights and the replica path carry an attached adapter; s2v_weight_slot keeps returning the base
+ * [rows, cols] with the larger ld; s2v_device_bytes counts all of it.
+ * s2v_lora_attach: the arguments of s2v_merge_lora (fp32 device pointers, the reference's weight name, conv A as [r, C * 2 * 2]), legal AFTER
+ *   s2v_finalize_weights; replaces what is attached under `name`.  Refused, with a message that says which: the mode off, an fp8
+ *   weight_format, a shard context, a rank over lora_runtime_rank, a name that is unknown or no LoRA target of the context (an
+ *   S2V_CTX_ATTN_WEIGHTS context takes the four attn1 names).  hipGraph: an attach or a detach changes K' and drops the captured step (as
+ *   s2v_set_rope does; it is re-captured at its next use).
+ * s2v_lora_set_scale: the same A and B under another scale; the result equals, bit for bit, attaching them at that scale.  It rewrites
+ *   values only (the tail of a branch weight, a re-merged weight) and KEEPS a captured step.  The caller keeps A and B (the library keeps no
+ *   fp32 copy).
+ * s2v_lora_detach: the base model; zeroes every tail and A stack, restores the re-merged weights.
+ * Conditioning: patch_embed.proj and patch_embed.text_proj made the hoisted conditioning, so after an attach, rescale or detach that
+ *   reaches them the forward entry points ask for s2v_set_conditioning again (a captured step reads the buffers it rewrites and stays valid).
+ * Replicas: the attached state (names attached, rank, scale) is kept inside the arena too; s2v_mark_weights_loaded on a context whose arena was
+ *   filled from another's (s2v_bcast_weights) reads it and runs the adapter it received.
+ *   Such a replica holds the values but not the names: s2v_lora_set_scale on it is refused until it has attached an adapter itself, and
+ *   s2v_lora_state reports the count, rank and scale its source wrote last.
+ * s2v_lora_state: names attached, rank and scale of the last attach / rescale, hipGraph captures this context has made so far. */
+S2V_API int s2v_lora_attach(s2v_ctx* ctx, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream);
+S2V_API int s2v_lora_set_scale(s2v_ctx* ctx, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream);
+S2V_API int s2v_lora_detach(s2v_ctx* ctx, s2v_stream stream);
+S2V_API int s2v_lora_state(s2v_ctx* ctx, int32_t* attached, int32_t* rank, float* scale, int64_t* graph_captures);
 
 /* Token geometry of the next calls: batch B (2 = CFG pair), text tokens T, latent frames F and latent H x W
  * (R = (H/2)(W/2) reference-image tokens, V = F*R video tokens, sequence order [text | ref | video]).
@@ -161,7 +201,8 @@ S2V_API int s2v_attn_forward(s2v_ctx* ctx, int32_t layer, const void* hidden, co
  * `weights`' layer `layer` (weights: a finalized S2V_CTX_ATTN_WEIGHTS context, or a model).  The same launches as s2v_attn_forward -- the
  * fused QKV GEMM with the q/k-norm + RoPE epilogue, the attention, the out-projection -- so the outputs are bit-identical to a model
  * context holding the same weights at the same geometry.  Refuses a ctx without a geometry, differing dtype, num_heads, inner dim or
- * weight_format, a shard context on either side (s2v_set_shard), and weights that are not loaded. */
+ * weight_format or lora_runtime_rank (the workspace context owns the activation pitch, the weights context the tails and the A stacks), a shard
+ * context on either side (s2v_set_shard), and weights that are not loaded.  Weights with an attached adapter run the branch. */
 S2V_API int s2v_attn_forward_with(s2v_ctx* ctx, const s2v_ctx* weights, int32_t layer, const void* hidden, const void* encoder,
                           void* out_hidden, void* out_encoder, s2v_stream stream);
 /* Device bytes the context holds: its weight arena (0 for S2V_CTX_ATTN_WORKSPACE) and its activation workspace (0 before s2v_set_geometry
@@ -204,7 +245,7 @@ S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 
 /* Live per-kernel timing for the roofline report (bench.py): HIP events are recorded on the launch stream around
  * every launch of a class; classes 0 qkv GEMM, 1 attention, 2 out-proj GEMM, 3 FF1 GEMM, 4 FF2 GEMM,
- * 5 LN-modulate, 6 qk-norm/rope/V^T.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
+ * 5 LN-modulate, 6 qk-norm/rope/V^T, 7 the modulation GEMV, 8 the Ulysses packs, 9 the runtime-LoRA down-projections.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
  * device, returns total ms and launch counts per class since the previous read, and resets the counters. */
 S2V_API int s2v_profile_enable(s2v_ctx* ctx, int32_t on);
 S2V_API int s2v_profile_read(s2v_ctx* ctx, float* ms_by_class, int32_t* launches_by_class, int32_t nclass);
@@ -441,6 +482,16 @@ S2V_API int s2v_t5_encode(s2v_t5* t5, const int64_t* input_ids_dev, int32_t B, i
  * reduction (M, N multiples of 256; fails if the shape does not qualify; allocates its workspace, synchronous) */
 S2V_API int s2v_op_linear(const void* A, const void* W, const void* bias, void* C, int32_t M, int32_t N, int32_t K,
                   int32_t epilogue, int32_t dtype, int32_t impl, s2v_stream stream);
+/* One adapted linear as the runtime adapter mode computes it (s2v_lora_attach): y = epilogue([x | T] . [W | rnd(scale * B)]^T + bias) with
+ * T = rnd(x . A^T) from the down-projection kernel -- the attach-time packing, the down-projection and the K-extended GEMM that a context's
+ * linear would launch for this shape, on the caller's operands.  x [M, K], W [N, K], bias [N] in `dtype` (bf16 or fp16); A [rank, K], B [N, rank]
+ * fp32; K a multiple of 64, rank <= 128.  epilogue 0 = bias, 1 = bias + GELU(tanh): C [M, N] out;  2 = gate + residual: C is the residual
+ * [M, N], updated in place as C + gate * (acc + bias) with every product and sum rounded as the block does, aux0 = gate [N];  4 = the fused
+ * q/k-norm without rotary embedding: N = 3 * qk_D, per-head LayerNorm(64, eps 1e-6) on columns < 2 N / 3, aux0 = LayerNorm weights [2][64]
+ * (q, k), aux1 = biases [2][64].  Allocates its scratch, synchronous.  tests/test_gpu_lora_runtime.py holds its error against fp64 to the error
+ * of PEFT's Linear.forward evaluated in the same dtype. */
+S2V_API int s2v_op_linear_lora(const void* x, const void* W, const void* bias, const float* A, const float* B, int32_t rank, float scale, void* C,
+                               int32_t M, int32_t N, int32_t K, int32_t epilogue, const void* aux0, const void* aux1, int32_t dtype, s2v_stream stream);
 /* qkv [B*Ntok (+64 rows of slack), 3*H*64] -> out [B*Ntok, H*64]; impl 0 = MFMA flash kernel (needs vt scratch
  * [B*H*64*ceil64(Ntok)] bf16, zero-filled by the caller), 1 = generic */
 /* W8A8 linear on the fp8 matrix cores (BASELINE configs[4]: "fp8 (CDNA4 fp8 MFMA) weights"): A [M,K] and W [N,K] bf16 are
