@@ -91,6 +91,7 @@ struct s2v_ctx {
     // weights
     int num_cus = 256;
     int sk_tiles = 0; float* sk_ws = nullptr; unsigned* sk_cnt = nullptr;  // split-K workspace of the geometry (0: none)
+    unsigned* vt_amax = nullptr;             // AttnArgs::vt_amax: VT_AMAX_WORDS words (attn_p_format 1)
     int* attn_queue = nullptr;               // nine counters of the persistent attention launch (zero between launches)
     unsigned long long* attn_stats = nullptr;  // AttnArgs::stats: 256 x [slow paths, (wave, KV tile) pairs] of the attn_q4 launches (s2v_attn_slow_stats)
     hipStream_t side = nullptr;              // fork/join stream for the row-tail launches of split GEMMs
@@ -329,6 +330,10 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         s2v_destroy(c);
         return s2v_fail(__FILE__, __LINE__, "s2v_create: attention census allocation failed", -2);
     }
+    if (hipMalloc((void**)&c->vt_amax, sizeof(unsigned) * VT_AMAX_WORDS) != hipSuccess || hipMemset(c->vt_amax, 0, sizeof(unsigned) * VT_AMAX_WORDS) != hipSuccess) {
+        s2v_destroy(c);
+        return s2v_fail(__FILE__, __LINE__, "s2v_create: V^T magnitude words allocation failed", -2);
+    }
     if (hipMalloc((void**)&c->attn_queue, 64) != hipSuccess || hipMemset(c->attn_queue, 0, 64) != hipSuccess) {
         s2v_destroy(c);
         return s2v_fail(__FILE__, __LINE__, "s2v_create: attention queue allocation failed", -2);
@@ -459,6 +464,7 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->t_dev) hipFree(c->t_dev);
     if (c->ws) hipFree(c->ws);
     if (c->attn_queue) hipFree(c->attn_queue);
+    if (c->vt_amax) hipFree(c->vt_amax);
     if (c->attn_stats) hipFree(c->attn_stats);
     if (c->clk_buf) hipFree(c->clk_buf);
     if (c->arena) hipFree(c->arena);
@@ -999,15 +1005,16 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
     }
     // fp16 P / V^T is the four-wave kernels' (attn_q4h / attn_q4fh); short sequences run attn_pp on bf16 V^T
     const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(c->Ntok, attn_mx_out(c)));
+    S2V_REQUIRE(!p16 || (int64_t)c->B * c->cfg.num_heads <= VT_AMAX_WORDS, "attention: B * heads too large for the fp16 V^T");
     if (fused_qk || norm_in_quant) {
         ProfScope ps(c, PK_QKNORM, st);
-        S2V_TRY(launch_v_transpose(c->QKV, 3 * D, c->B, c->cfg.num_heads, c->Ntok, c->VT, c->ntok_pad, st, p16));
+        S2V_TRY(launch_v_transpose(c->QKV, 3 * D, c->B, c->cfg.num_heads, c->Ntok, c->VT, c->ntok_pad, st, p16 ? c->vt_amax : nullptr));
     } else {
         QkNormRopeArgs q{};
         q.qkv = c->QKV; q.ld_qkv = 3 * D; q.B = c->B; q.H = c->cfg.num_heads; q.Ntok = c->Ntok; q.text_len = c->T;
         q.nq_w = w.nq_w; q.nq_b = w.nq_b; q.nk_w = w.nk_w; q.nk_b = w.nk_b; q.eps = 1e-6f;
         q.cos = c->have_rope ? c->rope_cos : nullptr; q.sin = c->have_rope ? c->rope_sin : nullptr;
-        q.vt = (c->mfma || c->h16) ? c->VT : nullptr; q.ntok_pad = c->ntok_pad; q.vt_f16 = p16 ? 1 : 0;  // fp16 dtype: the pass moves fp16 bits
+        q.vt = (c->mfma || c->h16) ? c->VT : nullptr; q.ntok_pad = c->ntok_pad; q.vt_f16 = p16 ? 1 : 0; q.vt_amax = c->vt_amax;  // fp16 dtype: the pass moves fp16 bits
         ProfScope ps(c, PK_QKNORM, st);
         S2V_TRY(launch_qk_norm_rope(q, c->dtype, st));
     }
@@ -1015,7 +1022,7 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
     a.qkv = c->QKV; a.ld_qkv = 3 * D; a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Xn; a.ld_out = pX;
     a.B = c->B; a.H = c->cfg.num_heads; a.Ntok = c->Ntok; a.scale = 0.125f;
     a.queue = c->attn_queue; a.num_cus = c->num_cus;  // launches of one context are ordered on its stream: one queue suffices
-    a.p16 = p16 ? 1 : 0;
+    a.p16 = p16 ? 1 : 0; a.vt_amax = c->vt_amax;
     a.stats = c->attn_stats;
     a.valu_only = c->cfg.force_simple;
     a.stagger = c->attn_stagger;
@@ -1656,15 +1663,16 @@ static int shard_attention(s2v_ctx* c, hipStream_t st) {
         S2V_TRY(launch_shard_copy(a, st));
     }
     const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(c->gN, mx));
+    S2V_REQUIRE(!p16 || (int64_t)c->B * H <= VT_AMAX_WORDS, "shard_attention: B * heads too large for the fp16 V^T");
     if (c->mfma || c->h16) {
         ProfScope ps(c, PK_QKNORM, st);
-        S2V_TRY(launch_v_transpose(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->VT, c->ntok_pad, st, p16));
+        S2V_TRY(launch_v_transpose(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->VT, c->ntok_pad, st, p16 ? c->vt_amax : nullptr));
     }
     AttnArgs a{};
     a.qkv = c->QKVh; a.ld_qkv = (int)(3 * Dp); a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Oh; a.ld_out = (int)Dp;
     a.B = c->B; a.H = H; a.Ntok = c->gN; a.scale = 0.125f;
     a.queue = c->attn_queue; a.num_cus = c->num_cus;
-    a.p16 = p16 ? 1 : 0;
+    a.p16 = p16 ? 1 : 0; a.vt_amax = c->vt_amax;
     a.stats = c->attn_stats;
     a.valu_only = c->cfg.force_simple;
     a.stagger = c->attn_stagger;
@@ -2114,23 +2122,35 @@ extern "C" int s2v_op_mod_gemv(const void* emb, const void* W, const void* bias,
 
 // attention with QK^T on the scaled fp8 MFMA as weight_format 2 runs it: q (times scale * log2 e) and k of the bf16 qkv rows become MX e4m3
 // images in `scratch` (also returned to the caller for inspection: layout in kernels.h AttnArgs::q8 ... k8s, offsets below), V^T and P.V stay bf16.
-extern "C" int s2v_op_attention_fp8qk(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B, int32_t H,
-                                      int32_t Ntok, s2v_stream stream) {
+static int op_attention_fp8qk(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B, int32_t H,
+                              int32_t Ntok, bool p16, s2v_stream stream) {
     S2V_REQUIRE(qkv && vt_scratch && scratch && out, "s2v_op_attention_fp8qk: null argument");
     const int D = H * 64;
     const int64_t ntok_pad = rup(Ntok, 64), BH = (int64_t)B * H;
     const int64_t oq8 = 0, oq8s = oq8 + rup(BH * Ntok * 64, 256), ok8 = oq8s + rup(BH * Ntok * 2, 256), ok8s = ok8 + rup(BH * ntok_pad * 64, 256);
-    S2V_REQUIRE(scratch_bytes >= ok8s + BH * ntok_pad * 4, "s2v_op_attention_fp8qk: scratch too small (B*H*(66*Ntok + 68*ntok_pad) + 1024 bytes)");
+    const int64_t oam = rup(ok8s + BH * ntok_pad * 4, 256);  // p16: the magnitude words of the fp16 V^T (AttnArgs::vt_amax) behind the images
+    S2V_REQUIRE(scratch_bytes >= (p16 ? oam + BH * 4 : ok8s + BH * ntok_pad * 4),
+                "s2v_op_attention_fp8qk: scratch too small (B*H*(66*Ntok + 68*ntok_pad) + 1024 bytes; fp16 P: 256 + 4*B*H more)");
     AttnArgs a{};
     a.qkv = qkv; a.ld_qkv = 3 * D; a.out = out; a.ld_out = D; a.B = B; a.H = H; a.Ntok = Ntok; a.scale = 0.125f;
     a.ntok_pad = (int)ntok_pad; a.vt = vt_scratch;
     char* w = (char*)scratch;
     a.q8 = (unsigned char*)(w + oq8); a.q8s = (unsigned short*)(w + oq8s); a.k8 = (unsigned char*)(w + ok8); a.k8s = (unsigned*)(w + ok8s);
     hipStream_t st = (hipStream_t)stream;
-    S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st));
+    if (p16) { a.p16 = 1; a.vt_amax = (const unsigned*)(w + oam); }
+    S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, p16 ? (unsigned*)(w + oam) : nullptr));
     S2V_TRY(launch_qk_quant_mx(qkv, 3 * D, B, H, Ntok, a.ntok_pad, a.scale * 1.4426950408889634f, (unsigned char*)a.q8, (unsigned short*)a.q8s,
                                (unsigned char*)a.k8, (unsigned*)a.k8s, st));
     return launch_attn_q4f(a, false, st);
+}
+extern "C" int s2v_op_attention_fp8qk(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B, int32_t H,
+                                      int32_t Ntok, s2v_stream stream) {
+    return op_attention_fp8qk(qkv, vt_scratch, scratch, scratch_bytes, out, B, H, Ntok, false, stream);
+}
+// the same with P and V^T in fp16 (attn_p_format 1 under weight_format 2: attn_q4fh)
+extern "C" int s2v_op_attention_fp8qk_p16(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B, int32_t H,
+                                          int32_t Ntok, s2v_stream stream) {
+    return op_attention_fp8qk(qkv, vt_scratch, scratch, scratch_bytes, out, B, H, Ntok, true, stream);
 }
 
 extern "C" int s2v_op_attention(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok,
@@ -2145,14 +2165,20 @@ extern "C" int s2v_op_attention(const void* qkv, void* vt_scratch, void* out, in
         S2V_REQUIRE(dtype == S2V_DTYPE_BF16 && vt_scratch, "s2v_op_attention: impl 0 / 3 / 4 are bf16 and need vt_scratch");
         a.vt = vt_scratch;
         a.p16 = (impl == 4 || (impl == 3 && attn_runs_q4(Ntok, false))) ? 1 : 0;
-        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, a.p16 != 0));
+        if (a.p16) {  // operator level: one buffer of magnitude words per process, on the device of the first such call (restriction stated in s2v_hip.h)
+            static unsigned* op_vt_amax = nullptr;
+            S2V_REQUIRE((int64_t)B * H <= VT_AMAX_WORDS, "s2v_op_attention: B * H too large for the fp16 V^T");
+            if (!op_vt_amax) S2V_CHECK_HIP(hipMalloc((void**)&op_vt_amax, sizeof(unsigned) * VT_AMAX_WORDS));
+            a.vt_amax = op_vt_amax;
+        }
+        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, const_cast<unsigned*>(a.vt_amax)));
         if (impl == 4) return launch_attn_q4h(a, false, st);
         return launch_attn_bf16(a, st);
     }
     if (impl == 6) {  // fp16 on v_mfma_f32_32x32x16_f16 (what the fp16 engine runs); vt_scratch as for impl 0
         S2V_REQUIRE(dtype == S2V_DTYPE_F16 && vt_scratch, "s2v_op_attention: impl 6 is fp16 and needs vt_scratch");
         a.vt = vt_scratch;
-        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, false));
+        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st));
         return launch_attn_f16(a, st);
     }
     if (impl == 5) {  // fp32 on the fp32 matrix pipe (what the fp32 engine runs)

@@ -235,7 +235,8 @@ __device__ __forceinline__ void attn_qx_item(const AttnArgs& a, int nqb, int wg,
 #pragma unroll
     for (int j = 0; j < JB; ++j) {
         const float l_tot = LR[j] + __shfl_xor(LR[j], 32, 64);
-        const float inv = 1.0f / l_tot;
+        float inv = 1.0f / l_tot;
+        if constexpr (P16 && !H16) inv *= __uint_as_float((unsigned)(127 - vt_f16_shift(a.vt_amax[b * a.H + h])) << 23);  // V^T holds V * 2^shift
         u32x2 og[8];
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
@@ -402,6 +403,7 @@ int launch_attn_q4(const AttnArgs& a, bool persistent, hipStream_t st) { return 
 int launch_attn_q8(const AttnArgs& a, bool persistent, hipStream_t st) { return launch_attn_qx<1>(a, persistent, st); }
 int launch_attn_q4f(const AttnArgs& a, bool persistent, hipStream_t st) {
     S2V_REQUIRE(a.q8 && a.k8 && a.q8s && a.k8s && a.vt, "attn_q4f: the MX images of q / k (launch_qk_quant_mx) and V^T are required");
+    S2V_REQUIRE(!a.p16 || a.vt_amax, "attn_q4f: fp16 P needs the magnitude words of the fp16 V^T (launch_v_transpose(..., vt_amax))");
     return a.p16 ? launch_attn_qx<2, true, true>(a, persistent, st) : launch_attn_qx<2, true>(a, persistent, st);
 }
 // fp16 model dtype: qkv / out fp16, a.vt = fp16 V^T (the transpose pass moves the bits); the four-wave kernel with fp16 q, k, P
@@ -410,6 +412,6 @@ int launch_attn_q4hh(const AttnArgs& a, bool persistent, hipStream_t st) {
     return launch_attn_qx<2, false, true, true>(a, persistent, st);
 }
 int launch_attn_q4h(const AttnArgs& a, bool persistent, hipStream_t st) {
-    S2V_REQUIRE(a.p16 && a.vt, "attn_q4h: the fp16 V^T (launch_v_transpose(..., to_f16)) is required");
+    S2V_REQUIRE(a.p16 && a.vt && a.vt_amax, "attn_q4h: the fp16 V^T and its magnitude words (launch_v_transpose(..., vt_amax)) are required");
     return launch_attn_qx<2, false, true>(a, persistent, st);
 }

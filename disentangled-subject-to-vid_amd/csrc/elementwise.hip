@@ -438,16 +438,34 @@ __global__ __launch_bounds__(256) void qk_norm_rope_k(const QkNormRopeArgs a) {
 // V [B*Ntok, .] (cols 2D + h*64 + d) -> V^T [B][H][64][ntok_pad]; inside every aligned 16-token group the
 // tokens are stored in the order [0-3, 8-11, 4-7, 12-15] (bits 2 and 3 of the token index swapped) which is the
 // k-slot order the PV MFMA of attn_bf16_k consumes.  64 tokens x 64 dims per block through LDS.
-// to_f16: the values are written as fp16 (attn_q4h: P.V on the fp16 MFMA).  A bf16 value converts exactly when its magnitude lies in
-// [2^-14, 65504]; below, it rounds into the fp16 subnormals; ABOVE, it is SATURATED to +-65504 -- an infinity in V^T would turn the whole
-// head-dim column into NaN through 0 * inf in P.V, which no slow-path census would notice.  Values of that size do not occur
-// in V of this model (LayerNorm-ed inputs through one projection); bf16 P (attn_p_format 0, the default) has no such bound.
+// vamax non-null: the values are written as fp16 (attn_q4h: P.V on the fp16 MFMA), times 2^vt_f16_shift(vamax[b * H + h]) (kernels.h): the head's
+// largest magnitude lands in [2^14, 2^15), so V does not saturate (below a largest magnitude of 2^115: vt_f16_shift's clamp) and every value down to 2^-29 of the largest converts exactly (below, it
+// rounds into the fp16 subnormals).  Inf / NaN in V switch the scaling off; an infinity is then SATURATED to +-65504 -- in V^T it would turn the
+// whole head-dim column into NaN through 0 * inf in P.V, which no slow-path census would notice.
+__global__ __launch_bounds__(256) void v_amax_k(const bf16_t* qkv, int ld_qkv, int H, int Ntok, unsigned* vamax) {
+    const int n0 = blockIdx.x * 64, h = blockIdx.y, b = blockIdx.z;
+    const int D = H * 64;
+    unsigned m = 0;
+    for (int i = threadIdx.x; i < 64 * 8; i += 256) {
+        const int n = n0 + (i >> 3), cc = (i & 7) * 8;
+        if (n < Ntok) {
+            const u32x4 val = *(const u32x4*)(qkv + (size_t)(b * Ntok + n) * ld_qkv + 2 * D + h * 64 + cc);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m = max(m, max(val[e] & 0x7fffu, (val[e] >> 16) & 0x7fffu));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(vamax + b * H + h, m);
+}
 __global__ __launch_bounds__(256) void v_transpose_k(const bf16_t* qkv, int ld_qkv, int B, int H, int Ntok, bf16_t* vt,
-                                                     int ntok_pad, int to_f16) {
+                                                     int ntok_pad, const unsigned* vamax) {
     __shared__ bf16_t tile[64][64 + 2];
     const int n0 = blockIdx.x * 64, h = blockIdx.y, b = blockIdx.z;
     const int D = H * 64;
     const int tid = threadIdx.x;
+    const bool to_f16 = vamax != nullptr;
+    const float vscale = to_f16 ? __uint_as_float((unsigned)(127 + vt_f16_shift(vamax[b * H + h])) << 23) : 1.0f;
     // load: 64 rows x 128 B, 8 lanes x 16 B per row
     for (int i = tid; i < 64 * 8; i += 256) {
         const int rr = i >> 3, cc = (i & 7) * 8;
@@ -468,7 +486,7 @@ __global__ __launch_bounds__(256) void v_transpose_k(const bf16_t* qkv, int ld_q
         if (n0 + tok < Ntok) {
             bf16_t v = tile[tok][d];
             if (to_f16) {
-                float f = __uint_as_float((unsigned)v << 16);
+                float f = __uint_as_float((unsigned)v << 16) * vscale;
                 f = f != f ? f : fminf(fmaxf(f, -65504.0f), 65504.0f);  // NaN stays NaN (it is one in bf16 too); +-inf and > 65504 saturate
                 v = __builtin_bit_cast(unsigned short, (_Float16)f);
             }
@@ -651,13 +669,19 @@ int launch_qk_norm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t st) {
     S2V_CHECK_HIP(hipGetLastError());
     if (a.vt != nullptr) {
         S2V_REQUIRE(dtype == S2V_BF16 || (dtype == S2V_F16 && !a.vt_f16), "V^T is produced for 16-bit storage only (fp16 rows are moved as they are)");
-        S2V_TRY(launch_v_transpose(a.qkv, a.ld_qkv, a.B, a.H, a.Ntok, a.vt, a.ntok_pad, st, a.vt_f16 != 0));
+        S2V_REQUIRE(!a.vt_f16 || a.vt_amax, "an fp16 V^T needs the per-head magnitude words (QkNormRopeArgs::vt_amax)");
+        S2V_TRY(launch_v_transpose(a.qkv, a.ld_qkv, a.B, a.H, a.Ntok, a.vt, a.ntok_pad, st, a.vt_f16 ? a.vt_amax : nullptr));
     }
     return 0;
 }
-int launch_v_transpose(const void* qkv, int ld_qkv, int B, int H, int Ntok, void* vt, int ntok_pad, hipStream_t st, bool to_f16) {
+int launch_v_transpose(const void* qkv, int ld_qkv, int B, int H, int Ntok, void* vt, int ntok_pad, hipStream_t st, unsigned* vt_amax) {
     dim3 g2((Ntok + 63) / 64, H, B);
-    hipLaunchKernelGGL(v_transpose_k, g2, dim3(256), 0, st, (const bf16_t*)qkv, ld_qkv, B, H, Ntok, (bf16_t*)vt, ntok_pad, to_f16 ? 1 : 0);
+    if (vt_amax != nullptr) {
+        S2V_CHECK_HIP(hipMemsetAsync(vt_amax, 0, sizeof(unsigned) * B * H, st));
+        hipLaunchKernelGGL(v_amax_k, g2, dim3(256), 0, st, (const bf16_t*)qkv, ld_qkv, H, Ntok, vt_amax);
+        S2V_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(v_transpose_k, g2, dim3(256), 0, st, (const bf16_t*)qkv, ld_qkv, B, H, Ntok, (bf16_t*)vt, ntok_pad, (const unsigned*)vt_amax);
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

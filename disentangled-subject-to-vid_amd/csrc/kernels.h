@@ -174,9 +174,12 @@ struct AttnArgs {
     //   k8 [B][H][ntok_pad][64] bytes (rows past Ntok zero), k8s [B][H][ntok_pad / 64][64] dwords: dword (hi * 32 + r) of a 64-key tile holds in
     //   byte kb the E8M0 scale of (key 32 kb + r, block hi) -- the scale VGPR of the QK^T MFMA, loaded as is
     const unsigned char* q8; const unsigned short* q8s; const unsigned char* k8; const unsigned* k8s;
-    // attn_p_format 1 (attn_q4h / attn_q4fh): `vt` holds fp16 (launch_v_transpose(..., to_f16 = true)), P is built as fp16 pairs and summed by
+    // attn_p_format 1 (attn_q4h / attn_q4fh): `vt` holds fp16 (launch_v_transpose(..., vt_amax)), P is built as fp16 pairs and summed by
     // packed fp16 adds, P.V runs on v_mfma_f32_32x32x16_f16; deferred maximum 2^14 instead of 2^64 (gen_attn_q4.py, P16).  attn_q4 forms only.
     int p16;
+    // p16 with bf16 storage: [B * H] words written by launch_v_transpose -- bits of the largest |V| of each (batch, head); V^T holds V * 2^vt_f16_shift
+    // of that word and the kernel's epilogue takes the power of two out again (exact; see vt_f16_shift)
+    const unsigned* vt_amax;
     // optional census of the deferred-maximum slow path (attn_q4 forms): 256 slots of two counters, slot = workgroup & 255:
     // [2 s] += slow paths taken, [2 s + 1] += (wave, KV tile) pairs run.  The engine reads it to decide whether fp16 P pays on the data at hand.
     unsigned long long* stats;
@@ -190,6 +193,18 @@ struct AttnArgs {
 #ifndef ATTN_PP_MAX_TOKENS
 #define ATTN_PP_MAX_TOKENS 4608
 #endif
+// fp16 V^T of bf16 V (attn_p_format 1): fp16 has three exponent bits fewer than bf16, and V stored as it is would round everything under 2^-14 into
+// subnormals and saturate above 65504.  Each (batch, head) is therefore stored times the power of two that puts its largest magnitude into
+// [2^14, 2^15): nothing saturates (short of a largest magnitude of 2^115 and more, where the shift is clamped at -100 and v_transpose_k's clamp
+// to +-65504 takes over), and values down to 2^-29 of the largest keep every bit.  amax_bits: bf16 bit pattern (sign cleared) of that magnitude;
+// zero, inf and NaN leave V as it is.
+#define VT_AMAX_WORDS 4096  // words the engine and the operator entry hold for AttnArgs::vt_amax (B * H of a launch must fit)
+__host__ __device__ static inline int vt_f16_shift(unsigned amax_bits) {
+    const int e = (int)((amax_bits >> 7) & 0xffu);
+    if (e == 0 || e == 255) return 0;
+    const int s = 14 - (e - 127);
+    return s > 100 ? 100 : (s < -100 ? -100 : s);
+}
 static inline bool attn_runs_q4(int Ntok, bool mx_out) { return mx_out || Ntok > ATTN_PP_MAX_TOKENS; }
 // q / k of the (normalised, rotated) QKV buffer -> the MX e4m3 images above (elementwise.hip)
 int launch_qk_quant_mx(const void* qkv, int ld_qkv, int B, int H, int Ntok, int ntok_pad, float q_prescale, unsigned char* q8, unsigned short* q8s,
@@ -239,10 +254,12 @@ struct QkNormRopeArgs {
     const float* cos; const float* sin;
     void* vt; int ntok_pad;   // null => skip
     int vt_f16;               // V^T as fp16 (AttnArgs::p16)
+    unsigned* vt_amax;        // vt_f16: AttnArgs::vt_amax, [B * H] words
 };
 int launch_qk_norm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t st);
 // bf16 V [B*Ntok, ld] (cols 2D + h*64 + d) -> V^T [B][H][64][ntok_pad] in the k-slot order attn_bf16 consumes
-int launch_v_transpose(const void* qkv, int ld_qkv, int B, int H, int Ntok, void* vt, int ntok_pad, hipStream_t st, bool to_f16 = false);
+// vt_amax non-null: V^T as fp16, each (batch, head) scaled by 2^vt_f16_shift of its largest magnitude, which is left in vt_amax[b * H + h]
+int launch_v_transpose(const void* qkv, int ld_qkv, int B, int H, int Ntok, void* vt, int ntok_pad, hipStream_t st, unsigned* vt_amax = nullptr);
 
 // timestep sinusoid -> Linear -> SiLU -> Linear  (embeddings.py:27-78, 864-876)
 int launch_time_embed(const float* t_dev, int B, int D, const void* w1, const void* b1, const void* w2, const void* b2,

@@ -521,7 +521,10 @@ S2V_API int s2v_op_mod_gemv(const void* emb, const void* W, const void* bias, vo
 S2V_API int s2v_attn_slow_stats(s2v_ctx* ctx, uint64_t* slow, uint64_t* total, int32_t reset);
 S2V_API int s2v_set_attn_p_format(s2v_ctx* ctx, int32_t attn_p_format);
 S2V_API int s2v_op_attention(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype,
-                     int32_t impl, s2v_stream stream);   /* impl: 0 product dispatch (bf16), 1 generic (VALU), 3 = 0 with attn_p_format 1, 4 = attn_q4h (fp16 P) at any length, 5 = fp32 / fp16 storage on the fp32 matrix pipe (what the fp32 engine runs), 6 = fp16 on v_mfma_f32_32x32x16_f16 (what the fp16 engine runs; vt scratch as impl 0) */
+                     int32_t impl, s2v_stream stream);   /* impl: 0 product dispatch (bf16), 1 generic (VALU), 3 = 0 with attn_p_format 1, 4 = attn_q4h (fp16 P) at any length, 5 = fp32 / fp16 storage on the fp32 matrix pipe (what the fp32 engine runs), 6 = fp16 on v_mfma_f32_32x32x16_f16 (what the fp16 engine runs; vt scratch as impl 0).
+                                                          * impl 3 / 4 keep the per-(batch, head) magnitude words of the fp16 V^T in ONE buffer per process, allocated on the
+                                                          * device current at the first such call and never freed: such calls must stay on that device and be ordered
+                                                          * against one another (one stream, or events); B * H <= 4096.  Contexts hold their own words. */
 /* The same joint attention (F.scaled_dot_product_attention at attention_processor.py:2083-2087, head_dim 64, scale 1/8) as weight_format 2
  * runs it: q (times scale * log2 e) and k of the bf16 qkv rows [B*Ntok, 3*H*64] are quantised to MX e4m3 (32-element blocks along the
  * head dimension, E8M0 scales) into `scratch` and QK^T runs on v_mfma_scale_f32_32x32x64_f8f6f4; V^T (vt_scratch: B*H*64*rup(Ntok,64)
@@ -530,6 +533,11 @@ S2V_API int s2v_op_attention(const void* qkv, void* vt_scratch, void* out, int32
  * dword hi*32+r = scale of (key 32*kb+r, block hi)).  No reference arithmetic exists for fp8 (parity unpinned). */
 S2V_API int s2v_op_attention_fp8qk(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B,
                                    int32_t H, int32_t Ntok, s2v_stream stream);
+/* The same with P and V^T in fp16 (attn_p_format 1 under weight_format 2): vt_scratch then holds fp16, each (batch, head) times a power of two
+ * taken from its largest |V| (the kernel divides it out again); scratch >= the size above + 256 + 4*B*H bytes (the magnitude words follow the
+ * images, 256-byte aligned). */
+S2V_API int s2v_op_attention_fp8qk_p16(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B,
+                                       int32_t H, int32_t Ntok, s2v_stream stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+# test_attention_f32m_vs_fp64_and_valu, second assertion: relative L2 of the whole output against fp64 SDPA <= 2 x the worst value measured on
+# the MI355X over the operator-level fp32 attention comparisons (measured 8.46e-7 -> 1.7e-6; the rule and number of test_gpu_parity.py ATTN_REL_L2_BARS)
+ATTN_REL_L2_BAR_F32 = 1.7e-6
 
 
 def _linear(s2v, A, W, b, epi, impl):
@@ -75,6 +78,10 @@ def test_attention_f32m_vs_fp64_and_valu(s2v, B, H, N):
     scale = max(1.0, ref.abs().max().item())
     assert (outs[5] - ref).abs().max().item() <= 2e-5 * scale
     assert (outs[5] - outs[1]).abs().max().item() <= 1e-5 * scale
+    for impl in (5, 1):
+        r = ((outs[impl] - ref).norm() / ref.norm()).item()
+        print(f"MEASURED-ATTN-RELL2 f32 f32m impl {impl} B{B} H{H} N{N}: {r:.3e}")
+        assert r <= ATTN_REL_L2_BAR_F32, (impl, r)
 
 
 @pytest.mark.parametrize("variant", ["rope", "sincos"])

@@ -10,6 +10,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+# test_attention_kernel_choice_by_sequence_length, second assertion: relative L2 of the whole output against fp64 SDPA <= 2 x the worst value
+# measured on the MI355X over the operator-level bf16 attention comparisons (measured 3.15e-3 -> 6.3e-3; the rule and number of test_gpu_parity.py ATTN_REL_L2_BARS)
+ATTN_REL_L2_BAR_BF16 = 6.3e-3
 
 
 def run(L, A, W, b, M, N, K, epi, impl):
@@ -280,6 +283,9 @@ def test_attention_kernel_choice_by_sequence_length(s2v, B, H, N):
         got = outs[variant].double().cpu()
         assert torch.isfinite(got).all()
         assert (got - ref).abs().max().item() <= 2e-2 * scale, (variant, (got - ref).abs().max().item())  # test_op_attention's tolerance
+        r = ((got - ref).norm() / ref.norm()).item()
+        print(f"MEASURED-ATTN-RELL2 bf16 kernel_choice variant {variant} B{B} H{H} N{N}: {r:.3e}")
+        assert r <= ATTN_REL_L2_BAR_BF16, (variant, r)
     assert (outs[6].double() - outs[10].double()).abs().max().item() <= 1.6e-2 * scale
 
 
