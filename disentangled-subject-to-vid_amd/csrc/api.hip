@@ -52,6 +52,9 @@ struct GraphKey {
     bool operator==(const GraphKey& o) const { return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot; }
 };
 
+// kernel classes of the per-class timing (ProfScope, s2v_profile_*): 8 = the Ulysses packs / unpacks, 9 = the LoRA down-projections
+enum { PK_QKV = 0, PK_ATTN = 1, PK_OUT = 2, PK_FF1 = 3, PK_FF2 = 4, PK_LNMOD = 5, PK_QKNORM = 6, PK_OTHER = 7, PK_SHARD = 8, PK_LORA = 9, PK_NUM = 10 };
+
 struct s2v_ctx {
     s2v_model_config cfg;
     int kind = S2V_CTX_MODEL;    // cfg.reserved[0]: a model, attention weights only, or geometry + workspace only (include/s2v_hip.h)
@@ -132,8 +135,8 @@ struct s2v_ctx {
     long long* clk_cur = nullptr;                    // the slot of the launch a ProfScope is open around (null outside the profile pass)
     std::vector<std::pair<int, int>> clk_rec;         // (class, slot) of every stamped launch since the last s2v_profile_read_clocks
     bool prof_on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[10];  // PK_NUM classes (8: the Ulysses packs / unpacks, 9: the LoRA down-projections)
-    size_t prof_used[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[PK_NUM];
+    size_t prof_used[PK_NUM] = {};
     // Ulysses shard (s2v_set_shard): sp ranks share one video's step.  With a shard T, R, V, Ntok, M and Mpad above are this rank's rows of
     // every sample -- the mini-sequence [T_r | R_r | V_r] -- and gT, gR, gV, gN the whole streams (equal to T, R, V, Ntok without a shard).
     bool shard = false;
@@ -162,7 +165,6 @@ static const int CLK_SLOTS = 8192;
 // designated workgroup of the kernel stamps s_memtime / s_memrealtime at its entry and exit (common.h clk_stamp).  Kernels without stamps (or
 // launches whose designated workgroup left early) leave the slot zero and are skipped.
 #define S2V_FP8_QK_AUTO_TOKENS 40000
-enum { PK_QKV = 0, PK_ATTN = 1, PK_OUT = 2, PK_FF1 = 3, PK_FF2 = 4, PK_LNMOD = 5, PK_QKNORM = 6, PK_OTHER = 7, PK_SHARD = 8, PK_LORA = 9, PK_NUM = 10 };
 
 struct ProfScope {
     s2v_ctx* c; int k; hipStream_t st; bool on;
@@ -227,20 +229,17 @@ static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
 #undef NM
 }
 
-// lora_runtime_rank (cfg.reserved[1]) -> the padded rank the layout is carved for
-static int lora_setup(s2v_ctx* c) {
+// lora_runtime_rank (cfg.reserved[1], 0 .. 128: s2v_create) -> the padded rank the layout is carved for
+static void lora_setup(s2v_ctx* c) {
     c->lora_cap = c->cfg.reserved[1];
-    if (c->lora_cap < 0 || c->lora_cap > 128) return s2v_fail(__FILE__, __LINE__, "s2v_create: lora_runtime_rank (reserved[1]) must be 0 .. 128", -1);
     // the fp8 weight formats keep no 16-bit operand for a branch to extend: nothing is carved, s2v_lora_attach refuses
     const bool fp8 = c->cfg.weight_format != 0;
     c->lr = (c->lora_cap > 0 && !fp8) ? (int)rup(c->lora_cap, c->D % 128 == 0 ? 128 : 64) : 0;
-    return 0;
 }
 
 // S2V_CTX_ATTN_WEIGHTS: an arena of num_layers x the attn1 weights, carved exactly as a model carves them (zero pad rows included), so that a
 // workspace context runs them through the same GEMM tiles; no stream, event, scratch or workspace of its own
 static int create_attn_weights(s2v_ctx* c) {
-    if (c->D > 4096 || c->D % 8 != 0) return s2v_fail(__FILE__, __LINE__, "s2v_create: bad inner dim", -1);
     const int64_t D = c->D, E = c->esz, Dp = rup(D, 256), lr = c->lr;
     int64_t off = 0;
     auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
@@ -271,17 +270,12 @@ static int create_attn_weights(s2v_ctx* c) {
 }
 
 // the host-side scratch every context that runs launches needs: step scalars, the pinned staging ring, the capture stream
-static int create_tail(s2v_ctx* c, s2v_ctx** out) {
+static bool create_tail(s2v_ctx* c) {
     hipMalloc((void**)&c->t_dev, 4 * sizeof(float));
     hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef));
     hipHostMalloc((void**)&c->ring, sizeof(s2v_ctx::Stage) * RING);
     hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
-    if (!c->t_dev || !c->coef_dev || !c->ring || !c->cap_stream) {
-        s2v_destroy(c);
-        return s2v_fail(__FILE__, __LINE__, "s2v_create: allocation failed", -2);
-    }
-    *out = c;
-    return 0;
+    return c->t_dev && c->coef_dev && c->ring && c->cap_stream;
 }
 
 extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
@@ -294,15 +288,30 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     S2V_REQUIRE(cfg->patch_size == 2, "s2v_create: patch_size must be 2");
     S2V_REQUIRE(cfg->num_layers > 0 && cfg->num_heads > 0, "s2v_create: bad model size");
     S2V_REQUIRE(cfg->in_channels * 4 <= 4096 && cfg->out_channels > 0, "s2v_create: bad channel count");
+    // everything that depends on the configuration alone is refused here, before anything is allocated
+    S2V_REQUIRE(cfg->reserved[1] >= 0 && cfg->reserved[1] <= 128, "s2v_create: lora_runtime_rank (reserved[1]) must be 0 .. 128");
+    const int Dc = cfg->num_heads * 64;
+    const bool mfma = cfg->dtype == S2V_DTYPE_BF16 && !cfg->force_simple;
+    if (kind == S2V_CTX_ATTN_WEIGHTS) {
+        S2V_REQUIRE(Dc <= 4096 && Dc % 8 == 0, "s2v_create: bad inner dim");
+    } else {
+        S2V_REQUIRE(Dc <= 4096, "s2v_create: D > 4096 unsupported");
+        S2V_REQUIRE(cfg->time_embed_dim % 8 == 0 && Dc % 8 == 0, "bad dims");
+        S2V_REQUIRE(cfg->lora_adaln_scope == 0 || cfg->lora_adaln_scope == 1, "s2v_create: lora_adaln_scope must be 0 or 1");
+        S2V_REQUIRE(cfg->attn_p_format == 0 || cfg->attn_p_format == 1, "s2v_create: attn_p_format must be 0 (bf16) or 1 (fp16)");
+        S2V_REQUIRE(cfg->weight_format >= 0 && cfg->weight_format <= 3, "s2v_create: weight_format must be 0, 1, 2 or 3");
+        S2V_REQUIRE(cfg->weight_format == 0 || (mfma && Dc % 128 == 0),
+                    "s2v_create: weight_format 1 / 2 (fp8) needs the bf16 MFMA path and inner_dim % 128 == 0");
+    }
     s2v_ctx* c = new s2v_ctx();
     c->cfg = *cfg;
-    c->D = cfg->num_heads * 64;
+    c->D = Dc;
     c->L = cfg->num_layers;
     c->dtype = cfg->dtype;
     c->esz = cfg->dtype == S2V_DTYPE_F32 ? 4 : 2;
     c->temb = cfg->time_embed_dim;
     c->kind = kind;
-    if (lora_setup(c)) { delete c; return -1; }
+    lora_setup(c);
     {
         int dev = 0, ncu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
@@ -314,32 +323,24 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         *out = c;
         return 0;
     }
+    // the one exit of a failed allocation below
+    auto fail = [&](const char* msg) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, msg, -2); };
     if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-        s2v_destroy(c);
-        return s2v_fail(__FILE__, __LINE__, "s2v_create: stream / event creation failed", -2);
-    }
-    c->mfma = (cfg->dtype == S2V_DTYPE_BF16) && !cfg->force_simple;
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
+        return fail("s2v_create: stream / event creation failed");
+    c->mfma = mfma;
     c->h16 = (cfg->dtype == S2V_DTYPE_F16) && !cfg->force_simple;
 #ifdef S2V_DIAG  // experiment knobs of the diagnostics build only; clamped: slot * stagger * 64 cycles of s_sleep per launch
     if (const char* e = getenv("S2V_ATTN_STAGGER")) c->attn_stagger = std::min(std::max(atoi(e), 0), 64);
     if (const char* e = getenv("S2V_ATTN_ORDER")) c->attn_order = atoi(e) ? 1 : 0;
 #endif
-    if (hipMalloc((void**)&c->attn_stats, 4096) != hipSuccess || hipMemset(c->attn_stats, 0, 4096) != hipSuccess) {
-        s2v_destroy(c);
-        return s2v_fail(__FILE__, __LINE__, "s2v_create: attention census allocation failed", -2);
-    }
-    if (hipMalloc((void**)&c->vt_amax, sizeof(unsigned) * VT_AMAX_WORDS) != hipSuccess || hipMemset(c->vt_amax, 0, sizeof(unsigned) * VT_AMAX_WORDS) != hipSuccess) {
-        s2v_destroy(c);
-        return s2v_fail(__FILE__, __LINE__, "s2v_create: V^T magnitude words allocation failed", -2);
-    }
-    if (hipMalloc((void**)&c->attn_queue, 64) != hipSuccess || hipMemset(c->attn_queue, 0, 64) != hipSuccess) {
-        s2v_destroy(c);
-        return s2v_fail(__FILE__, __LINE__, "s2v_create: attention queue allocation failed", -2);
-    }
-    if (c->D > 4096) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, "s2v_create: D > 4096 unsupported", -1); }
-    if (c->temb % 8 != 0 || c->D % 8 != 0) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, "bad dims", -1); }
+    if (hipMalloc((void**)&c->attn_stats, 4096) != hipSuccess || hipMemset(c->attn_stats, 0, 4096) != hipSuccess)
+        return fail("s2v_create: attention census allocation failed");
+    if (hipMalloc((void**)&c->vt_amax, sizeof(unsigned) * VT_AMAX_WORDS) != hipSuccess || hipMemset(c->vt_amax, 0, sizeof(unsigned) * VT_AMAX_WORDS) != hipSuccess)
+        return fail("s2v_create: V^T magnitude words allocation failed");
+    if (hipMalloc((void**)&c->attn_queue, 64) != hipSuccess || hipMemset(c->attn_queue, 0, 64) != hipSuccess)
+        return fail("s2v_create: attention queue allocation failed");
 
     const int64_t D = c->D, E = c->esz, L = c->L, TE = c->temb;
     const int64_t Kp = cfg->in_channels * 4, Cout = cfg->out_channels * 4, TX = cfg->text_embed_dim;
@@ -365,7 +366,6 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     const int64_t o_te1_w = carve(TE * D), o_te1_b = carve(TE), o_te2_w = carve(TE * TE), o_te2_b = carve(TE);
     const int64_t o_nf_w = carve(D), o_nf_b = carve(D), o_no_w = carve(D), o_no_b = carve(D);
     const int64_t o_po_w = carve(rup(Cout, 256) * D), o_po_b = carve(Cout);
-    if (cfg->lora_adaln_scope != 0 && cfg->lora_adaln_scope != 1) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, "s2v_create: lora_adaln_scope must be 0 or 1", -1); }
     c->mc = cfg->lora_adaln_scope ? 9 : 6;
     const int64_t MC = c->mc;
     c->mod_rows = 2 * L * MC * D + 2 * D;
@@ -379,9 +379,6 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     c->fp8 = cfg->weight_format >= 1 && cfg->weight_format <= 3;
     c->fp8_qk = cfg->weight_format == 2;
     c->attn_p16 = cfg->attn_p_format == 1;
-    if (cfg->attn_p_format != 0 && cfg->attn_p_format != 1) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, "s2v_create: attn_p_format must be 0 (bf16) or 1 (fp16)", -1); }
-    if (cfg->weight_format < 0 || cfg->weight_format > 3) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, "s2v_create: weight_format must be 0, 1, 2 or 3", -1); }
-    if (c->fp8 && (!c->mfma || D % 128 != 0)) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, "s2v_create: weight_format 1 / 2 (fp8) needs the bf16 MFMA path and inner_dim % 128 == 0", -1); }
     struct QOffs { int64_t q_qkv, q_o, q_1, q_2, s_qkv, s_o, s_1, s_2; };
     std::vector<QOffs> qo(c->fp8 ? L : 0);
     auto carve_b = [&](int64_t bytes) { int64_t o = off; off += rup(bytes, 256); return o; };
@@ -389,12 +386,15 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         q.q_qkv = carve_b(rup(3 * D, 256) * D); q.q_o = carve_b(Dp * D); q.q_1 = carve_b(rup(4 * D, 256) * D); q.q_2 = carve_b(Dp * 4 * D);
         q.s_qkv = carve_b(rup(3 * D, 256) * 4); q.s_o = carve_b(Dp * 4); q.s_1 = carve_b(rup(4 * D, 256) * 4); q.s_2 = carve_b(Dp * 4);
     }
-    if (kind == S2V_CTX_ATTN_WORKSPACE) return create_tail(c, out);  // no arena: the weights come from another context (s2v_attn_forward_with)
+    if (kind == S2V_CTX_ATTN_WORKSPACE) {  // no arena: the weights come from another context (s2v_attn_forward_with)
+        if (!create_tail(c)) return fail("s2v_create: allocation failed");
+        *out = c;
+        return 0;
+    }
     c->arena_bytes = off;
     hipError_t e = hipMalloc((void**)&c->arena, c->arena_bytes);
-    if (e != hipSuccess) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, hipGetErrorString(e), -2); }
-    e = hipMemset(c->arena, 0, c->arena_bytes);
-    if (e != hipSuccess) { s2v_destroy(c); return s2v_fail(__FILE__, __LINE__, hipGetErrorString(e), -2); }
+    if (e == hipSuccess) e = hipMemset(c->arena, 0, c->arena_bytes);
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     char* A = c->arena;
     c->layers.resize(L);
     char nm[160];
@@ -449,7 +449,9 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     add_slot(c, "norm_out.linear.bias", c->mod_b + (int64_t)2 * L * MC * D * E, 1, 2 * D, 2 * D);
     add_slot(c, "proj_out.weight", c->po_w, Cout, D, D);
     add_slot(c, "proj_out.bias", c->po_b, 1, Cout, Cout);
-    return create_tail(c, out);
+    if (!create_tail(c)) return fail("s2v_create: allocation failed");
+    *out = c;
+    return 0;
 }
 
 extern "C" void s2v_destroy(s2v_ctx* c) {
@@ -470,6 +472,11 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->arena) hipFree(c->arena);
     if (c->lora_tmp) hipFree(c->lora_tmp);
     delete c;
+}
+
+// the captured step bakes in what it was captured under: whoever changes that drops the graph, and the next graph step captures again
+static void drop_graph(s2v_ctx* c) {
+    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
 }
 
 // "transformer_blocks.<l>.norm{1,2}.linear.{weight,bias}"
@@ -615,7 +622,7 @@ extern "C" int s2v_mark_weights_loaded(s2v_ctx* c) {
         c->lora_rank = c->lora_replica ? c->lora_hdr_host[1] : 0;
         memcpy(&c->lora_scale, &c->lora_hdr_host[2], sizeof(float));
         if (!c->lora_replica) c->lora_scale = 0.f;
-        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+        drop_graph(c);
         c->have_cond = false;
     }
     return 0;
@@ -642,7 +649,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     S2V_REQUIRE(c->cfg.out_channels * 4 * c->esz % 16 == 0, "s2v_set_shard: the projected rows must be a multiple of 16 bytes (out_channels * 4 * element size)");
     if (c->shard && c->sp == world && c->sr == rank) return 0;
     S2V_CHECK_HIP(hipDeviceSynchronize());
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+    drop_graph(c);
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
     c->B = 0;
     c->shard = true; c->sp = world; c->sr = rank;
@@ -660,7 +667,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
     if (c->shard) S2V_REQUIRE(F * (H / 2) * (W / 2) >= c->sp, "s2v_set_geometry: every rank of a shard needs at least one video row");
     S2V_CHECK_HIP(hipDeviceSynchronize());
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+    drop_graph(c);
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }
     c->B = B; c->T = T; c->F = F; c->H = H; c->W = W;
     c->R = (H / 2) * (W / 2);
@@ -796,9 +803,8 @@ extern "C" int s2v_fp8_qk_active(s2v_ctx* c, int32_t* active) {
 extern "C" int s2v_set_rope(s2v_ctx* c, const float* cos_dev, const float* sin_dev, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws, "s2v_set_rope: call s2v_set_geometry first");
     // the captured step bakes in have_rope and the fused-epilogue decision (rope_paired): a change of either drops the graph
-    auto drop_graph = [&]() { if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } };
     if (!cos_dev || !sin_dev) {
-        if (c->have_rope) drop_graph();
+        if (c->have_rope) drop_graph(c);
         c->have_rope = false;
         return 0;
     }
@@ -827,7 +833,7 @@ extern "C" int s2v_set_rope(s2v_ctx* c, const float* cos_dev, const float* sin_d
     bool paired = true;
     for (size_t i = 0; i < n && paired; i += 2) paired = hc[i] == hc[i + 1] && hs[i] == hs[i + 1];
     c->rope_paired = paired;
-    if (!had_rope || was_paired != paired) drop_graph();
+    if (!had_rope || was_paired != paired) drop_graph(c);
     if (paired) {
         for (size_t p = 0; p < n / 64; ++p)
             for (int k = 0; k < 32; ++k) {
@@ -952,6 +958,8 @@ extern "C" __attribute__((visibility("default"))) int s2v_diag_qkv_qknorm(const 
     g.qk_w[0] = nq_w; g.qk_b[0] = nq_b; g.qk_w[1] = nk_w; g.qk_b[1] = nk_b; g.qk_cs = cs; g.qk_D = D; g.qk_eps = eps;
     return launch_gemm_bf16(g, EPI_BIAS_QKNORM, (hipStream_t)stream);
 }
+#else
+static const int g_fused_qk = 1;
 #endif
 // mx_out (fp8 engine, MFMA path): the attention kernel leaves its output as MX e4m3 in c->aq / c->hs for the out-projection instead of bf16 in Xn
 static bool attn_mx_out(const s2v_ctx* c) {
@@ -961,7 +969,6 @@ static bool attn_mx_out(const s2v_ctx* c) {
 #endif
     return mx;
 }
-// w: the layer's weights -- c's own, or another context's of the same dtype / heads / weight_format (s2v_attn_forward_with)
 // runtime LoRA: T = rnd(x . A^T) into the columns [K, K + N) of the rows of x (lora.hip); the GEMM that follows runs with K' = K + N
 static int lora_down(s2v_ctx* c, char* x, int ldx, const char* A, int N, int K, hipStream_t st) {
     LoraDownArgs a{};
@@ -970,89 +977,107 @@ static int lora_down(s2v_ctx* c, char* x, int ldx, const char* A, int N, int K, 
     return launch_lora_down(a, c->dtype, (c->mfma || c->h16) && K % 64 == 0, st);
 }
 
-// lora: the weights carry an attached adapter (their context's lora_names is not empty)
-static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false) {
-    // Xn -> QKV -> (qk-norm, rope, V^T) -> attention -> Xn (reused as the attention output buffer)
-    const int D = c->D, pX = D + 3 * c->lr;
+// ---- attention: one QKV projection and one core for the single engine (run_attention) and the Ulysses shard (shard_front, shard_attention) ----
+// May the per-head LayerNorm + rotary embedding of q and k ride in the QKV projection's epilogue (EPI_BIAS_QKNORM), on the rounded projection
+// as the stand-alone kernel does?  The matrix-core kernels only, and rotary tables in the paired form (s2v_set_rope).  g_fused_qk is the A/B
+// switch of the diagnostics build: 0 stand-alone kernel, 3 epilogue even for fp8 QK^T (run_attention)
+static bool qk_epilogue_ok(const s2v_ctx* c) {
+    return (c->mfma || c->h16) && c->D % 64 == 0 && (!c->have_rope || c->rope_paired) && g_fused_qk != 0;
+}
+
+static void set_qk_epilogue(const s2v_ctx* c, const LayerW& w, GemmArgs& g) {
+    g.tok_per_batch = c->Ntok; g.text_len = c->T;
+    g.qk_w[0] = w.nq_w; g.qk_b[0] = w.nq_b; g.qk_w[1] = w.nk_w; g.qk_b[1] = w.nk_b;
+    g.qk_cs = c->have_rope ? c->rope_pk : nullptr;
+    g.qk_D = c->D; g.qk_eps = 1e-6f;
+}
+
+// q/k LayerNorm + rotary embedding on the context's rows of QKV, without V^T: who wants it adds vt / vt_f16 / vt_amax
+static QkNormRopeArgs qk_norm_args(const s2v_ctx* c, const LayerW& w) {
+    QkNormRopeArgs q{};
+    q.qkv = c->QKV; q.ld_qkv = 3 * c->D; q.B = c->B; q.H = c->cfg.num_heads; q.Ntok = c->Ntok; q.text_len = c->T; q.ntok_pad = c->ntok_pad;
+    q.nq_w = w.nq_w; q.nq_b = w.nq_b; q.nk_w = w.nk_w; q.nk_b = w.nk_b; q.eps = 1e-6f;
+    q.cos = c->have_rope ? c->rope_cos : nullptr; q.sin = c->have_rope ? c->rope_sin : nullptr;
+    return q;
+}
+
+// Xn (row pitch pX) -> QKV on the context's rows.  lora: the weights carry an attached adapter (their context's lora_names is not empty) and the
+// GEMM runs with K = pX behind the down-projection; qk_epi: EPI_BIAS_QKNORM; prequant: linear_fp8
+static int qkv_proj(s2v_ctx* c, const LayerW& w, int pX, bool lora, bool qk_epi, bool prequant, hipStream_t st) {
+    const int D = c->D;
     if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_qkv, 3 * c->lr, D, st));
     GemmArgs g{};
     g.A = c->Xn; g.lda = pX; g.W = w.wqkv; g.ldw = pX; g.bias = w.bqkv;
     g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = lora ? pX : D;
-    // MFMA path: the per-head LayerNorm + rotary embedding of q and k run in the projection's epilogue (EPI_BIAS_QKNORM), on the
-    // rounded projection as the stand-alone kernel does; only the V^T production remains a pass of its own
-    // fp8 QK^T (weight_format 2 / 3 beyond its token threshold): q and k reach the attention kernel only as MX e4m3 images, so their LayerNorm + rotary
-    // embedding ride in the pass that makes the images (qk_norm_quant_mx_k: the same bytes moved, the same bits produced) and the projection keeps the plain
-    // bias epilogue -- its exposed q/k-norm epilogue is 20-25 % of an fp8 tile, whose K loop is half as long as the bf16 one
-#ifdef S2V_DIAG
-    const bool fuse_any = (c->mfma || c->h16) && D % 64 == 0 && (!c->have_rope || c->rope_paired) && g_fused_qk != 0;  // A/B switch of the diagnostics build:
-    const bool norm_in_quant = fuse_any && c->fp8_qk && g_fused_qk != 3;                                               // 0 stand-alone kernel, 3 epilogue even for fp8 QK^T
-#else
-    const bool fuse_any = (c->mfma || c->h16) && D % 64 == 0 && (!c->have_rope || c->rope_paired);
-    const bool norm_in_quant = fuse_any && c->fp8_qk;
-#endif
-    const bool fused_qk = fuse_any && !norm_in_quant;
-    if (fused_qk) {
-        g.tok_per_batch = c->Ntok; g.text_len = c->T;
-        g.qk_w[0] = w.nq_w; g.qk_b[0] = w.nq_b; g.qk_w[1] = w.nk_w; g.qk_b[1] = w.nk_b;
-        g.qk_cs = c->have_rope ? c->rope_pk : nullptr;
-        g.qk_D = D; g.qk_eps = 1e-6f;
-    }
-    {
-        ProfScope ps(c, PK_QKV, st);
-        const int epi = fused_qk ? EPI_BIAS_QKNORM : EPI_BIAS;
-        if (c->fp8) S2V_TRY(linear_fp8(c, g, epi, w.q_qkv, w.s_qkv, st, prequant));
-        else S2V_TRY(linear(c, g, epi, st));
-    }
+    if (qk_epi) set_qk_epilogue(c, w, g);
+    ProfScope ps(c, PK_QKV, st);
+    const int epi = qk_epi ? EPI_BIAS_QKNORM : EPI_BIAS;
+    if (c->fp8) return linear_fp8(c, g, epi, w.q_qkv, w.s_qkv, st, prequant);
+    return linear(c, g, epi, st);
+}
+
+// what the callers of attn_core differ in: the q | k | v rows, heads and tokens per sample (the kernel and its formats are chosen on Ntok), the
+// output rows and, fp8 engine (attn_mx_out), where the output goes as MX e4m3 instead: bytes, block scales, rows of the scale image
+struct AttnOperands {
+    const void* qkv; int ld_qkv, H, Ntok;
+    void* out; int ld_out;
+    unsigned char *mx_q, *mx_s; int64_t mx_rows;
+};
+// where q and k get their LayerNorm + rotary embedding: before the core (the projection's epilogue; a shard: at the latest before its exchange);
+// by the core in the stand-alone pass over c->QKV, which writes V^T as well; by the core inside the MX quantisation of fp8 QK^T
+enum { QK_DONE = 0, QK_STANDALONE = 1, QK_IN_QUANT = 2 };
+
+// (q/k-norm,) V^T, (fp8 QK^T: q and k as MX e4m3,) attention.  w: the layer's norm weights, for QK_STANDALONE / QK_IN_QUANT
+static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w, hipStream_t st) {
+    const bool mx = attn_mx_out(c), matrix = c->mfma || c->h16;
     // fp16 P / V^T is the four-wave kernels' (attn_q4h / attn_q4fh); short sequences run attn_pp on bf16 V^T
-    const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(c->Ntok, attn_mx_out(c)));
-    S2V_REQUIRE(!p16 || (int64_t)c->B * c->cfg.num_heads <= VT_AMAX_WORDS, "attention: B * heads too large for the fp16 V^T");
-    if (fused_qk || norm_in_quant) {
-        ProfScope ps(c, PK_QKNORM, st);
-        S2V_TRY(launch_v_transpose(c->QKV, 3 * D, c->B, c->cfg.num_heads, c->Ntok, c->VT, c->ntok_pad, st, p16 ? c->vt_amax : nullptr));
-    } else {
-        QkNormRopeArgs q{};
-        q.qkv = c->QKV; q.ld_qkv = 3 * D; q.B = c->B; q.H = c->cfg.num_heads; q.Ntok = c->Ntok; q.text_len = c->T;
-        q.nq_w = w.nq_w; q.nq_b = w.nq_b; q.nk_w = w.nk_w; q.nk_b = w.nk_b; q.eps = 1e-6f;
-        q.cos = c->have_rope ? c->rope_cos : nullptr; q.sin = c->have_rope ? c->rope_sin : nullptr;
-        q.vt = (c->mfma || c->h16) ? c->VT : nullptr; q.ntok_pad = c->ntok_pad; q.vt_f16 = p16 ? 1 : 0; q.vt_amax = c->vt_amax;  // fp16 dtype: the pass moves fp16 bits
+    const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(o.Ntok, mx));
+    S2V_REQUIRE(!p16 || (int64_t)c->B * o.H <= VT_AMAX_WORDS, "attention: B * heads too large for the fp16 V^T");
+    if (qk == QK_STANDALONE) {
+        QkNormRopeArgs q = qk_norm_args(c, *w);
+        q.vt = matrix ? c->VT : nullptr; q.vt_f16 = p16 ? 1 : 0; q.vt_amax = c->vt_amax;  // fp16 dtype: the pass moves fp16 bits
         ProfScope ps(c, PK_QKNORM, st);
         S2V_TRY(launch_qk_norm_rope(q, c->dtype, st));
+    } else if (matrix) {
+        ProfScope ps(c, PK_QKNORM, st);
+        S2V_TRY(launch_v_transpose(o.qkv, o.ld_qkv, c->B, o.H, o.Ntok, c->VT, c->ntok_pad, st, p16 ? c->vt_amax : nullptr));
     }
     AttnArgs a{};
-    a.qkv = c->QKV; a.ld_qkv = 3 * D; a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Xn; a.ld_out = pX;
-    a.B = c->B; a.H = c->cfg.num_heads; a.Ntok = c->Ntok; a.scale = 0.125f;
+    a.qkv = o.qkv; a.ld_qkv = o.ld_qkv; a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = o.out; a.ld_out = o.ld_out;
+    a.B = c->B; a.H = o.H; a.Ntok = o.Ntok; a.scale = 0.125f;
     a.queue = c->attn_queue; a.num_cus = c->num_cus;  // launches of one context are ordered on its stream: one queue suffices
     a.p16 = p16 ? 1 : 0; a.vt_amax = c->vt_amax;
     a.stats = c->attn_stats;
     a.valu_only = c->cfg.force_simple;
     a.stagger = c->attn_stagger;
     a.order = c->attn_order;
-    if (attn_mx_out(c)) { a.mx_q = (unsigned char*)c->aq; a.mx_s = c->hs; a.mx_rows = (int)c->Mpad; }
-    if (c->fp8_qk) {  // weight_format 2: q (times scale * log2 e) and k as MX e4m3, QK^T on the scaled fp8 MFMA (the pass is timed with the V^T pass)
-        {
-            ProfScope ps(c, PK_QKNORM, st);
-            if (norm_in_quant) {
-                QkNormRopeArgs q{};
-                q.qkv = c->QKV; q.ld_qkv = 3 * D; q.B = c->B; q.H = c->cfg.num_heads; q.Ntok = c->Ntok; q.text_len = c->T; q.ntok_pad = c->ntok_pad;
-                q.nq_w = w.nq_w; q.nq_b = w.nq_b; q.nk_w = w.nk_w; q.nk_b = w.nk_b; q.eps = 1e-6f;
-                q.cos = c->have_rope ? c->rope_cos : nullptr; q.sin = c->have_rope ? c->rope_sin : nullptr;
-                S2V_TRY(launch_qk_norm_quant_mx(q, a.scale * 1.4426950408889634f, c->q8, c->q8s, c->k8, c->k8s, st));
-            } else {
-                S2V_TRY(launch_qk_quant_mx(c->QKV, 3 * D, c->B, c->cfg.num_heads, c->Ntok, c->ntok_pad, a.scale * 1.4426950408889634f, c->q8, c->q8s, c->k8,
-                                           c->k8s, st));
-            }
-        }
+    if (mx) { a.mx_q = o.mx_q; a.mx_s = o.mx_s; a.mx_rows = (int)o.mx_rows; }
+    if (c->fp8_qk) {  // q (times scale * log2 e) and k as MX e4m3, QK^T on the scaled fp8 MFMA (the pass is timed with the V^T pass)
+        const float prescale = a.scale * 1.4426950408889634f;
         a.q8 = c->q8; a.q8s = c->q8s; a.k8 = c->k8; a.k8s = c->k8s;
-        ProfScope ps(c, PK_ATTN, st);
-        a.clk = c->clk_cur;
-        return launch_attn_q4f(a, true, st);
+        ProfScope ps(c, PK_QKNORM, st);
+        if (qk == QK_IN_QUANT) S2V_TRY(launch_qk_norm_quant_mx(qk_norm_args(c, *w), prescale, c->q8, c->q8s, c->k8, c->k8s, st));
+        else S2V_TRY(launch_qk_quant_mx(o.qkv, o.ld_qkv, c->B, o.H, o.Ntok, c->ntok_pad, prescale, c->q8, c->q8s, c->k8, c->k8s, st));
     }
     ProfScope ps(c, PK_ATTN, st);
     a.clk = c->clk_cur;
-    if (c->mfma) S2V_TRY(launch_attn_bf16(a, st));
-    else if (c->h16) S2V_TRY(launch_attn_f16(a, st));   // fp16 dtype: q, k, V^T, P in fp16 on v_mfma_f32_32x32x16_f16
-    else S2V_TRY(launch_attn_simple(a, c->dtype, st));
-    return 0;
+    if (c->fp8_qk) return launch_attn_q4f(a, true, st);
+    if (c->mfma) return launch_attn_bf16(a, st);
+    if (c->h16) return launch_attn_f16(a, st);   // fp16 dtype: q, k, V^T, P in fp16 on v_mfma_f32_32x32x16_f16
+    return launch_attn_simple(a, c->dtype, st);
+}
+
+// Xn -> QKV -> (qk-norm, rope, V^T) -> attention -> Xn (reused as the attention output buffer; fp8 engine: MX e4m3 in aq / hs)
+// w: the layer's weights -- c's own, or another context's of the same dtype / heads / weight_format (s2v_attn_forward_with)
+static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false) {
+    const int D = c->D, pX = D + 3 * c->lr;
+    // fp8 QK^T (weight_format 2 / 3 beyond its token threshold): q and k reach the attention kernel only as MX e4m3 images, so their LayerNorm + rotary
+    // embedding ride in the pass that makes the images (qk_norm_quant_mx_k: the same bytes moved, the same bits produced) and the projection keeps the plain
+    // bias epilogue -- its exposed q/k-norm epilogue is 20-25 % of an fp8 tile, whose K loop is half as long as the bf16 one
+    const bool epi_ok = qk_epilogue_ok(c), norm_in_quant = epi_ok && c->fp8_qk && g_fused_qk != 3;
+    S2V_TRY(qkv_proj(c, w, pX, lora, epi_ok && !norm_in_quant, prequant, st));
+    const AttnOperands o{c->QKV, 3 * D, c->cfg.num_heads, c->Ntok, c->Xn, pX, (unsigned char*)c->aq, c->hs, c->Mpad};
+    return attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st);
 }
 
 // the pieces of a block on the packed residual buffer X (rows: the context's M), in the order run_block launches them
@@ -1091,16 +1116,18 @@ static GemmArgs block_gate(const s2v_ctx* c, int half, const char* mod_base, int
     return g;
 }
 
-static int block_out_proj(s2v_ctx* c, int l, GemmArgs g, hipStream_t st) {
-    const LayerW& w = c->layers[l];
+// the out-projection of what run_attention / the shard's O exchange left: Xn, or (attn_mx_out) the MX image in aq / hs, against w.wo behind the
+// adapter's down-projection.  g carries the destination and the epilogue's own fields; timed: the GEMM counts as PK_OUT (the block, not the
+// AttnProcessor seam)
+static int out_proj(s2v_ctx* c, const LayerW& w, bool lora, GemmArgs g, int epi, bool timed, hipStream_t st) {
     const int D = c->D, pX = D + 3 * c->lr;
-    const bool lora = c->lora_on();
     if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
-    g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.K = lora ? D + c->lr : D;
+    g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.M = (int)c->M; g.N = D; g.K = lora ? D + c->lr : D;
     if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
+    auto gemm = [&]() { return c->fp8 ? linear_fp8(c, g, epi, w.q_o, w.s_o, st) : linear(c, g, epi, st); };
+    if (!timed) return gemm();
     ProfScope ps(c, PK_OUT, st);
-    if (c->fp8) return linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_o, w.s_o, st);
-    return linear(c, g, EPI_BIAS_GATE_RES, st);
+    return gemm();
 }
 
 static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st) {
@@ -1137,7 +1164,7 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
         const GemmArgs g = block_gate(c, half, mod_base, mod_stride);
         if (half == 0) {
             S2V_TRY(run_attention(c, c->layers[l], st, prequant, c->lora_on()));
-            S2V_TRY(block_out_proj(c, l, g, st));
+            S2V_TRY(out_proj(c, c->layers[l], c->lora_on(), g, EPI_BIAS_GATE_RES, true, st));
         } else {
             S2V_TRY(block_ff(c, l, g, prequant, st));
         }
@@ -1215,6 +1242,25 @@ extern "C" int s2v_transformer_forward(s2v_ctx* c, const void* latents, int64_t 
     return forward_impl(c, latents, lat_bstride, timesteps_dev, out, (hipStream_t)stream);
 }
 
+// the residual streams of every sample between the caller's dense tensors (s0: n0 rows, s1: n1 rows, video: V rows per sample; n0 + n1 = T + R)
+// and a packed buffer [B][n0 | n1 | V] of row pitch `pitch` elements -- into it, or out of it.  A stream without rows is skipped
+static int copy_streams(s2v_ctx* c, bool to_packed, char* packed, int pitch, char* s0, int n0, char* s1, int n1, char* video, hipStream_t st) {
+    const int D = c->D;
+    const int64_t E = c->esz;
+    char* const src[3] = {s0, s1, video};
+    const int n[3] = {n0, n1, c->V};
+    for (int b = 0; b < c->B; ++b) {
+        char* pk = packed + (int64_t)b * c->Ntok * pitch * E;
+        for (int i = 0; i < 3; pk += (int64_t)n[i] * pitch * E, ++i) {
+            if (!n[i]) continue;
+            char* t = src[i] + (int64_t)b * n[i] * D * E;
+            if (to_packed) S2V_TRY(launch_copy_rows(t, D, nullptr, 0, pk, pitch, n[i], D, c->dtype, st));
+            else S2V_TRY(launch_copy_rows(pk, pitch, nullptr, 0, t, D, n[i], D, c->dtype, st));
+        }
+    }
+    return 0;
+}
+
 extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, const void* enc0, const void* enc1,
                                  const void* temb, void* out_hidden, void* out_enc0, void* out_enc1, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws && c->finalized, "s2v_block_forward: geometry and weights required");
@@ -1228,45 +1274,21 @@ extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, 
     const int64_t r0 = (int64_t)(2 * layer) * c->mc * D;
     char* modl = c->mod;  // [B][12D]
     S2V_TRY(launch_mod_gemv(temb, B, c->temb, c->mod_w + r0 * c->temb * E, c->mod_b + r0 * E, 2 * c->mc * D, modl, c->dtype, st));
-    for (int b = 0; b < B; ++b) {
-        char* xb = c->X + (int64_t)b * c->Ntok * D * E;
-        if (c->T) S2V_TRY(launch_copy_rows((const char*)enc0 + (int64_t)b * c->T * D * E, D, nullptr, 0, xb, D, c->T, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows((const char*)enc1 + (int64_t)b * c->R * D * E, D, nullptr, 0, xb + (int64_t)c->T * D * E, D, c->R, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows((const char*)hidden + (int64_t)b * c->V * D * E, D, nullptr, 0, xb + (int64_t)(c->T + c->R) * D * E, D, c->V, D, c->dtype, st));
-    }
+    S2V_TRY(copy_streams(c, true, c->X, D, (char*)enc0, c->T, (char*)enc1, c->R, (char*)hidden, st));
     S2V_TRY(run_block(c, layer, modl, 2 * c->mc * D, st));
-    for (int b = 0; b < B; ++b) {
-        const char* xb = c->X + (int64_t)b * c->Ntok * D * E;
-        if (c->T) S2V_TRY(launch_copy_rows(xb, D, nullptr, 0, (char*)out_enc0 + (int64_t)b * c->T * D * E, D, c->T, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows(xb + (int64_t)c->T * D * E, D, nullptr, 0, (char*)out_enc1 + (int64_t)b * c->R * D * E, D, c->R, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows(xb + (int64_t)(c->T + c->R) * D * E, D, nullptr, 0, (char*)out_hidden + (int64_t)b * c->V * D * E, D, c->V, D, c->dtype, st));
-    }
-    return 0;
+    return copy_streams(c, false, c->X, D, (char*)out_enc0, c->T, (char*)out_enc1, c->R, (char*)out_hidden, st);
 }
 
-// the AttnProcessor seam on c's geometry and workspace with the weights w (c's own layer, or another context's)
+// the AttnProcessor seam on c's geometry and workspace with the weights w (c's own layer, or another context's); encoder = [text | ref] of each sample
 static int attn_forward_impl(s2v_ctx* c, const LayerW& w, bool lora, const void* hidden, const void* encoder, void* out_hidden, void* out_encoder,
                              hipStream_t st) {
-    const int D = c->D, B = c->B, TR = c->T + c->R, pX = D + 3 * c->lr;
-    const int64_t E = c->esz;
-    for (int b = 0; b < B; ++b) {
-        char* xb = c->Xn + (int64_t)b * c->Ntok * pX * E;
-        S2V_TRY(launch_copy_rows((const char*)encoder + (int64_t)b * TR * D * E, D, nullptr, 0, xb, pX, TR, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows((const char*)hidden + (int64_t)b * c->V * D * E, D, nullptr, 0, xb + (int64_t)TR * pX * E, pX, c->V, D, c->dtype, st));
-    }
+    const int D = c->D, TR = c->T + c->R;
+    S2V_TRY(copy_streams(c, true, c->Xn, D + 3 * c->lr, nullptr, 0, (char*)encoder, TR, (char*)hidden, st));
     S2V_TRY(run_attention(c, w, st, false, lora));
-    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
     GemmArgs g{};
-    g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.C = c->Hb; g.ldc = D; g.M = (int)c->M; g.N = D; g.K = lora ? D + c->lr : D;
-    if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
-    if (c->fp8) S2V_TRY(linear_fp8(c, g, EPI_BIAS, w.q_o, w.s_o, st));  // the same operands run_block feeds its out-projection
-    else S2V_TRY(linear(c, g, EPI_BIAS, st));
-    for (int b = 0; b < B; ++b) {
-        const char* xb = c->Hb + (int64_t)b * c->Ntok * D * E;
-        S2V_TRY(launch_copy_rows(xb, D, nullptr, 0, (char*)out_encoder + (int64_t)b * TR * D * E, D, TR, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows(xb + (int64_t)TR * D * E, D, nullptr, 0, (char*)out_hidden + (int64_t)b * c->V * D * E, D, c->V, D, c->dtype, st));
-    }
-    return 0;
+    g.C = c->Hb; g.ldc = D;
+    S2V_TRY(out_proj(c, w, lora, g, EPI_BIAS, false, st));  // the same operands run_block feeds its out-projection
+    return copy_streams(c, false, c->Hb, D, nullptr, 0, (char*)out_encoder, TR, (char*)out_hidden, st);
 }
 
 extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, const void* encoder, void* out_hidden,
@@ -1358,7 +1380,8 @@ static int lora_write_hdr(s2v_ctx* c, hipStream_t st) {
 }
 
 static void lora_drop_graph(s2v_ctx* c) {
-    if (c->gexec) { (void)hipDeviceSynchronize(); hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+    if (c->gexec) (void)hipDeviceSynchronize();  // the graph may still be replaying
+    drop_graph(c);
 }
 
 extern "C" int s2v_lora_attach(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream) {
@@ -1467,12 +1490,51 @@ extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const
     return launch_sched_step(a, dtype, (hipStream_t)stream);
 }
 
-static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
-    S2V_TRY(forward_impl(c, latents, 0, c->t_dev, c->noise_pred, st));
+// the step's scalars to the device: timestep and scheduler coefficients through the next slot of the pinned ring (the uploads are
+// asynchronous: a slot must outlive its copies, RING steps ahead of the device are allowed)
+static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_host, hipStream_t st) {
+    s2v_ctx::Stage& sg = c->ring[c->ring_pos];
+    c->ring_pos = (c->ring_pos + 1) % RING;
+    for (int i = 0; i < 4; ++i) sg.t[i] = timestep;
+    fill_coef(sg.c, *coef_host);
+    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * 4, hipMemcpyHostToDevice, st));
+    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// the graph cache: replay the captured `body` on st; a first use or another key captures body(cap_stream) anew.  A body that fails ends the
+// capture and returns its code with no graph held
+template <class Body>
+static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body body) {
+    if (!c->gexec || !(c->gkey == key)) {
+        drop_graph(c);
+        hipGraph_t graph = nullptr;
+        S2V_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
+        const int r = body(c->cap_stream);
+        hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
+        if (r != 0) { if (graph) hipGraphDestroy(graph); return r; }
+        S2V_CHECK_HIP(e);
+        e = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        S2V_CHECK_HIP(e);
+        c->graph_captures++;
+        c->gkey = key;
+    }
+    S2V_CHECK_HIP(hipGraphLaunch(c->gexec, st));
+    return 0;
+}
+
+// (CFG +) scheduler step on the context's noise_pred with the coefficients stage_step uploaded, latents updated in place
+static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, int cfg_flag, hipStream_t st) {
     SchedArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
-    a.n = (int64_t)c->F * c->cfg.out_channels * c->H * c->W; a.cfg = c->B == 2 ? 1 : 0; a.coef = c->coef_dev;
+    a.n = (int64_t)c->F * c->cfg.out_channels * c->H * c->W; a.cfg = cfg_flag; a.coef = c->coef_dev;
     return launch_sched_step(a, c->dtype, st);
+}
+
+static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
+    S2V_TRY(forward_impl(c, latents, 0, c->t_dev, c->noise_pred, st));
+    return sched_on_pair(c, latents, x0_hist, noise, c->B == 2 ? 1 : 0, st);
 }
 
 extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
@@ -1485,30 +1547,9 @@ extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const
                                        "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
                                      : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     hipStream_t st = (hipStream_t)stream;
-    s2v_ctx::Stage& sg = c->ring[c->ring_pos];
-    c->ring_pos = (c->ring_pos + 1) % RING;
-    for (int i = 0; i < 4; ++i) sg.t[i] = timestep;
-    fill_coef(sg.c, *coef_host);
-    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * 4, hipMemcpyHostToDevice, st));
-    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
+    S2V_TRY(stage_step(c, timestep, coef_host, st));
     if (!use_graph) return step_launches(c, latents, x0_hist, noise, st);
-    GraphKey key{latents, x0_hist, noise, -1};
-    if (!c->gexec || !(c->gkey == key)) {
-        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
-        hipGraph_t graph = nullptr;
-        S2V_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-        int r = step_launches(c, latents, x0_hist, noise, c->cap_stream);
-        hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
-        if (r != 0) { if (graph) hipGraphDestroy(graph); return r; }
-        S2V_CHECK_HIP(e);
-        e = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        S2V_CHECK_HIP(e);
-        c->graph_captures++;
-        c->gkey = key;
-    }
-    S2V_CHECK_HIP(hipGraphLaunch(c->gexec, st));
-    return 0;
+    return launch_captured(c, GraphKey{latents, x0_hist, noise, -1}, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s); });
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------
@@ -1523,37 +1564,19 @@ static int64_t pair_half_bytes(const s2v_ctx* c) { return (int64_t)c->F * c->cfg
 
 extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float timestep, const s2v_sched_coef* coef_host, int32_t slot,
                                        int32_t use_graph, s2v_stream stream) {
+    // a begin is pending only once its forward is on the stream: whatever fails below, s2v_denoise_split_end finds none
+    if (c) c->split_kind = -1;
     S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_split_begin: null argument");
     S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required");
     S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_split_begin: in/out channels must match");
     hipStream_t st = (hipStream_t)stream;
-    s2v_ctx::Stage& sg = c->ring[c->ring_pos];
-    c->ring_pos = (c->ring_pos + 1) % RING;
-    for (int i = 0; i < 4; ++i) sg.t[i] = timestep;
-    fill_coef(sg.c, *coef_host);
-    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * 4, hipMemcpyHostToDevice, st));
-    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
+    S2V_TRY(stage_step(c, timestep, coef_host, st));
     char* out = c->noise_pred + (int64_t)slot * pair_half_bytes(c);
+    auto forward = [&](hipStream_t s) { return forward_impl(c, latents, 0, c->t_dev, out, s); };
+    S2V_TRY(use_graph ? launch_captured(c, GraphKey{(void*)latents, nullptr, nullptr, slot}, st, forward) : forward(st));
     c->split_kind = coef_host->kind;
-    if (!use_graph) return forward_impl(c, latents, 0, c->t_dev, out, st);
-    GraphKey key{(void*)latents, nullptr, nullptr, slot};
-    if (!c->gexec || !(c->gkey == key)) {
-        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
-        hipGraph_t graph = nullptr;
-        S2V_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-        int r = forward_impl(c, latents, 0, c->t_dev, out, c->cap_stream);
-        hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
-        if (r != 0) { if (graph) hipGraphDestroy(graph); return r; }
-        S2V_CHECK_HIP(e);
-        e = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        S2V_CHECK_HIP(e);
-        c->graph_captures++;
-        c->gkey = key;
-    }
-    S2V_CHECK_HIP(hipGraphLaunch(c->gexec, st));
     return 0;
 }
 
@@ -1571,10 +1594,7 @@ extern "C" int s2v_denoise_split_end(s2v_ctx* c, void* latents, float* x0_hist, 
     S2V_REQUIRE(c->split_kind >= 0, "s2v_denoise_split_end: no s2v_denoise_split_begin is pending (its coefficients are the step's)");
     S2V_REQUIRE(c->split_kind == 0 || (noise && x0_hist), "s2v_denoise_split_end: DPM needs noise and x0_hist");
     c->split_kind = -1;
-    SchedArgs a{};
-    a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
-    a.n = (int64_t)c->F * c->cfg.out_channels * c->H * c->W; a.cfg = 1; a.coef = c->coef_dev;  // the coefficients s2v_denoise_split_begin uploaded
-    return launch_sched_step(a, c->dtype, (hipStream_t)stream);
+    return sched_on_pair(c, latents, x0_hist, noise, 1, (hipStream_t)stream);  // the coefficients s2v_denoise_split_begin uploaded
 }
 
 extern "C" int s2v_denoise_step_cfg_parallel(s2v_ctx* c, s2v_rccl_comm* comm, int32_t slot, void* latents, float timestep,
@@ -1595,14 +1615,6 @@ extern "C" int s2v_denoise_step_cfg_parallel(s2v_ctx* c, s2v_rccl_comm* comm, in
 // projected video rows per step; the caller moves the bytes (s2v_shard_buffers) or s2v_denoise_step_ulysses does it over RCCL.
 int s2v_rccl_shard_check(s2v_rccl_comm* comm, int world, int rank);  // rccl.hip (not exported)
 
-static bool shard_fused_qk(const s2v_ctx* c) {
-    bool f = (c->mfma || c->h16) && c->D % 64 == 0 && (!c->have_rope || c->rope_paired);
-#ifdef S2V_DIAG
-    f = f && g_fused_qk != 0;
-#endif
-    return f;
-}
-
 // LN1 of layer l, the QKV projection with q/k LayerNorm + RoPE on the rank's rows, pack: chunk g of sbuf = [M][q_g | k_g | v_g].  fp8 engine: the
 // projection is the single engine's fp8 GEMM on the LN1 pre-quantisation; with fp8 QK^T too the q/k LayerNorm + RoPE stay in the epilogue here (the
 // single engine folds them into its quantisation pass, qk_norm_quant_mx_k: the same bits) and q / k are quantised after the exchange
@@ -1613,30 +1625,11 @@ static int shard_front(s2v_ctx* c, int l, hipStream_t st) {
     const char* mb = c->mod + (int64_t)(2 * l) * c->mc * D * E;
     bool prequant = false;
     S2V_TRY(block_norm(c, l, 0, mb, c->mod_rows, st, &prequant));
-    GemmArgs g{};
-    g.A = c->Xn; g.lda = D; g.W = w.wqkv; g.ldw = D; g.bias = w.bqkv;
-    g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = D;
-    const bool fused = shard_fused_qk(c);
-    if (fused) {
-        g.tok_per_batch = c->Ntok; g.text_len = c->T;
-        g.qk_w[0] = w.nq_w; g.qk_b[0] = w.nq_b; g.qk_w[1] = w.nk_w; g.qk_b[1] = w.nk_b;
-        g.qk_cs = c->have_rope ? c->rope_pk : nullptr;
-        g.qk_D = D; g.qk_eps = 1e-6f;
-    }
-    {
-        ProfScope ps(c, PK_QKV, st);
-        const int epi = fused ? EPI_BIAS_QKNORM : EPI_BIAS;
-        if (c->fp8) S2V_TRY(linear_fp8(c, g, epi, w.q_qkv, w.s_qkv, st, prequant));
-        else S2V_TRY(linear(c, g, epi, st));
-    }
-    if (!fused) {  // V^T is made after the exchange, on the head-sharded buffer
-        QkNormRopeArgs q{};
-        q.qkv = c->QKV; q.ld_qkv = 3 * D; q.B = c->B; q.H = c->cfg.num_heads; q.Ntok = c->Ntok; q.text_len = c->T;
-        q.nq_w = w.nq_w; q.nq_b = w.nq_b; q.nk_w = w.nk_w; q.nk_b = w.nk_b; q.eps = 1e-6f;
-        q.cos = c->have_rope ? c->rope_cos : nullptr; q.sin = c->have_rope ? c->rope_sin : nullptr;
-        q.vt = nullptr; q.ntok_pad = c->ntok_pad;
+    const bool fused = qk_epilogue_ok(c);
+    S2V_TRY(qkv_proj(c, w, D, false, fused, prequant, st));
+    if (!fused) {  // vt stays null: V^T is made after the exchange, on the head-sharded buffer
         ProfScope ps(c, PK_QKNORM, st);
-        S2V_TRY(launch_qk_norm_rope(q, c->dtype, st));
+        S2V_TRY(launch_qk_norm_rope(qk_norm_args(c, w), c->dtype, st));
     }
     ShardCopyArgs a{};
     a.src = c->QKV; a.dst = c->sbuf; a.rows = (int)c->M; a.width16 = (int)(Dp * E / 16);
@@ -1662,39 +1655,8 @@ static int shard_attention(s2v_ctx* c, hipStream_t st) {
         ProfScope ps(c, PK_SHARD, st);
         S2V_TRY(launch_shard_copy(a, st));
     }
-    const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(c->gN, mx));
-    S2V_REQUIRE(!p16 || (int64_t)c->B * H <= VT_AMAX_WORDS, "shard_attention: B * heads too large for the fp16 V^T");
-    if (c->mfma || c->h16) {
-        ProfScope ps(c, PK_QKNORM, st);
-        S2V_TRY(launch_v_transpose(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->VT, c->ntok_pad, st, p16 ? c->vt_amax : nullptr));
-    }
-    AttnArgs a{};
-    a.qkv = c->QKVh; a.ld_qkv = (int)(3 * Dp); a.vt = c->VT; a.ntok_pad = c->ntok_pad; a.out = c->Oh; a.ld_out = (int)Dp;
-    a.B = c->B; a.H = H; a.Ntok = c->gN; a.scale = 0.125f;
-    a.queue = c->attn_queue; a.num_cus = c->num_cus;
-    a.p16 = p16 ? 1 : 0; a.vt_amax = c->vt_amax;
-    a.stats = c->attn_stats;
-    a.valu_only = c->cfg.force_simple;
-    a.stagger = c->attn_stagger;
-    a.order = c->attn_order;
-    if (mx) { a.mx_q = (unsigned char*)c->Oh; a.mx_s = c->Os; a.mx_rows = (int)c->Os_rows; }
-    if (c->fp8_qk) {  // q (times scale * log2 e) and k of the rank's heads as MX e4m3, QK^T on the scaled fp8 MFMA
-        {
-            ProfScope ps(c, PK_QKNORM, st);
-            S2V_TRY(launch_qk_quant_mx(c->QKVh, (int)(3 * Dp), c->B, H, c->gN, c->ntok_pad, a.scale * 1.4426950408889634f, c->q8, c->q8s, c->k8,
-                                       c->k8s, st));
-        }
-        a.q8 = c->q8; a.q8s = c->q8s; a.k8 = c->k8; a.k8s = c->k8s;
-        ProfScope ps(c, PK_ATTN, st);
-        a.clk = c->clk_cur;
-        S2V_TRY(launch_attn_q4f(a, true, st));
-    } else {
-        ProfScope ps(c, PK_ATTN, st);
-        a.clk = c->clk_cur;
-        if (c->mfma) S2V_TRY(launch_attn_bf16(a, st));
-        else if (c->h16) S2V_TRY(launch_attn_f16(a, st));
-        else S2V_TRY(launch_attn_simple(a, c->dtype, st));
-    }
+    const AttnOperands q{c->QKVh, (int)(3 * Dp), H, c->gN, c->Oh, (int)Dp, (unsigned char*)c->Oh, c->Os, c->Os_rows};
+    S2V_TRY(attn_core(c, q, QK_DONE, nullptr, st));  // fp8 QK^T: q / k of the rank's heads are quantised here, after the exchange
     ShardCopyArgs o{};
     o.src = c->Oh; o.dst = c->sbuf; o.rows = (int)Mg; o.width16 = (int)(Dp * E / 16);
     o.src_ld = o.dst_ld = Dp * E; o.src_map = c->rmap; o.nseg = 1; o.nseg_inner = 1;
@@ -1738,7 +1700,7 @@ static int shard_back(s2v_ctx* c, int l, hipStream_t st, int* pending) {
         S2V_TRY(launch_shard_copy(a, st));
     }
     const char* mb = c->mod + (int64_t)(2 * l) * c->mc * D * E;
-    S2V_TRY(block_out_proj(c, l, block_gate(c, 0, mb, c->mod_rows), st));
+    S2V_TRY(out_proj(c, c->layers[l], c->lora_on(), block_gate(c, 0, mb, c->mod_rows), EPI_BIAS_GATE_RES, true, st));
     bool prequant = false;
     S2V_TRY(block_norm(c, l, 1, mb, c->mod_rows, st, &prequant));
     S2V_TRY(block_ff(c, l, block_gate(c, 1, mb, c->mod_rows), prequant, st));
@@ -1796,12 +1758,7 @@ extern "C" int s2v_shard_step_begin(s2v_ctx* c, const void* latents, float times
     S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "s2v_shard_step_begin: sincos table missing (s2v_set_pos_embed)");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_shard_step_begin: in/out channels must match");
     hipStream_t st = (hipStream_t)stream;
-    s2v_ctx::Stage& sg = c->ring[c->ring_pos];
-    c->ring_pos = (c->ring_pos + 1) % RING;
-    for (int i = 0; i < 4; ++i) sg.t[i] = timestep;
-    fill_coef(sg.c, *coef_host);
-    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * 4, hipMemcpyHostToDevice, st));
-    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
+    S2V_TRY(stage_step(c, timestep, coef_host, st));
     c->sh_pending = 0;
     S2V_TRY(embed_streams(c, latents, 0, c->t_dev, st));
     S2V_TRY(shard_front(c, 0, st));
@@ -1846,10 +1803,7 @@ extern "C" int s2v_shard_step_end(s2v_ctx* c, void* latents, float* x0_hist, con
         S2V_TRY(launch_shard_copy(a, st));
     }
     S2V_TRY(launch_unpatchify(c->proj_full, (int)Co, c->gV, c->noise_pred, c->B, c->F, c->cfg.out_channels, c->H, c->W, c->dtype, st));
-    SchedArgs a{};
-    a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
-    a.n = (int64_t)c->F * c->cfg.out_channels * c->H * c->W; a.cfg = c->B == 2 ? 1 : 0; a.coef = c->coef_dev;
-    return launch_sched_step(a, c->dtype, st);
+    return sched_on_pair(c, latents, x0_hist, noise, c->B == 2 ? 1 : 0, st);
 }
 
 extern "C" int s2v_denoise_step_ulysses(s2v_ctx* c, s2v_rccl_comm* comm, void* latents, float timestep, const s2v_sched_coef* coef_host,
@@ -2108,7 +2062,7 @@ extern "C" int s2v_set_attn_p_format(s2v_ctx* c, int32_t fmt) {
     if (c->attn_p16 != (fmt == 1)) {
         S2V_CHECK_HIP(hipDeviceSynchronize());
         c->attn_p16 = fmt == 1;
-        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+        drop_graph(c);
     }
     return 0;
 }

@@ -209,6 +209,49 @@ def test_two_ranks_on_one_device_pipeline_bitwise(s2v):
             assert (a == exp).all(), f"{sched} graph={graph}: CFG-parallel differs from the one-process pipeline"
 
 
+def test_a_failed_begin_leaves_no_step_pending(s2v):
+    """s2v_denoise_split_begin on an engine without conditioning fails in the forward's host-side checks, before any launch, eager and under
+    capture; the s2v_denoise_split_end after it must find nothing pending (it would run CFG + the scheduler step on a stale pair buffer).  The
+    context stays usable: with the conditioning set, one begin / end pair gives the latents of an engine that never saw a failure"""
+    import ctypes
+
+    L = s2v._lib
+    lib = L.lib()
+    cfg = s2v.tiny(use_rope=True, heads=2, layers=1, text_dim=64, temb=64)
+    sd = s2v.weights.synthetic_state_dict(cfg, seed=73, parity=True)
+    T, F, H, W = 5, 2, 8, 12
+    text, ref, lat0 = _inputs(cfg, T, F, H, W, 74)
+    lat0 = lat0.bfloat16().contiguous()
+    sch = s2v.CogVideoXDDIMScheduler(snr_shift_scale=1.0)
+    sch.set_timesteps(3)
+    coef = sch.coef(sch.timesteps[0], torch.bfloat16, 6.0)
+    m = s2v.HipCogVideoXTransformer3DModel(cfg, torch.bfloat16, DEV)
+    m.load_state_dict(sd)
+    e = m.engine
+    e.set_geometry(1, T, F, H, W)
+    e.prepare_tables(H * 8, W * 8)
+    lat = lat0.clone()
+    for graph in (0, 1):
+        assert lib.s2v_denoise_split_begin(e._h, L.ptr(lat), 999.0, ctypes.byref(coef), 1, graph, L.stream_ptr()) != 0
+        assert b"conditioning" in lib.s2v_last_error()
+        assert lib.s2v_denoise_split_end(e._h, L.ptr(lat), None, None, L.stream_ptr()) != 0, f"graph={graph}: end accepted after a failed begin"
+        assert b"pending" in lib.s2v_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(lat, lat0), "a refused step touched the latents"
+    e.set_conditioning(text[1:2], ref)
+    e.denoise_split_begin(lat, 999.0, coef, 1)
+    e.denoise_split_end(lat)
+    m1, e1 = _engine(s2v, cfg, torch.bfloat16, sd, 1, text[1:2], ref, T, F, H, W)
+    exp = lat0.clone()
+    e1.denoise_split_begin(exp, 999.0, coef, 1)
+    e1.denoise_split_end(exp)
+    torch.cuda.synchronize()
+    assert torch.isfinite(lat.float()).all() and not torch.equal(lat, lat0)
+    assert torch.equal(lat, exp), "the context that saw the failed begins computes something else"
+    e.close()
+    e1.close()
+
+
 def test_split_entry_points_reject_what_they_cannot_run(s2v):
     """argument validation of the CFG-parallel C ABI: a B = 2 geometry (the pair already lives on this GPU), a slot outside {0, 1}, null pointers,
     and attn_p_format 'auto' (settled per engine from its own census: the two ranks of a pair could diverge) fail loudly with a message"""

@@ -153,6 +153,31 @@ def test_missing_library_fails_loudly(s2v, monkeypatch):
         s2v._lib.lib()
 
 
+def test_create_refuses_a_bad_configuration_before_it_allocates(s2v):
+    """every check of s2v_create that depends on the configuration alone comes before the first stream, event or buffer: the refusal is a bad
+    argument (-1) with its message, with or without a device"""
+    L = s2v._lib
+
+    def rc_and_message(kind=L.CTX_MODEL, lora_rank=0, **kw):
+        c = L.ModelConfigC(num_layers=1, num_heads=2, in_channels=16, out_channels=16, patch_size=2, time_embed_dim=64, text_embed_dim=64,
+                           use_rope=1, dtype=L.DTYPE_BF16, norm_eps=1e-5)
+        c.reserved[0], c.reserved[1] = kind, lora_rank
+        for k, v in kw.items():
+            setattr(c, k, v)
+        h = ctypes.c_void_p()
+        rc = L.lib().s2v_create(ctypes.byref(c), ctypes.byref(h))
+        assert not h.value
+        return rc, L.lib().s2v_last_error().decode()
+
+    for kw, msg in ((dict(attn_p_format=5), "attn_p_format must be 0 (bf16) or 1 (fp16)"), (dict(weight_format=7), "weight_format must be 0, 1, 2 or 3"),
+                    (dict(weight_format=1, dtype=L.DTYPE_F16), "needs the bf16 MFMA path"), (dict(weight_format=2, num_heads=3), "inner_dim % 128 == 0"),
+                    (dict(lora_adaln_scope=2), "lora_adaln_scope must be 0 or 1"), (dict(time_embed_dim=12), "bad dims"),
+                    (dict(num_heads=65), "D > 4096 unsupported"), (dict(lora_rank=200), "lora_runtime_rank (reserved[1]) must be 0 .. 128"),
+                    (dict(kind=L.CTX_ATTN_WEIGHTS, num_heads=65), "bad inner dim"), (dict(kind=L.CTX_ATTN_WORKSPACE, attn_p_format=5), "attn_p_format")):
+        rc, m = rc_and_message(**kw)
+        assert rc == -1 and msg in m, (kw, rc, m)
+
+
 def test_cpu_tensor_is_rejected(s2v):
     with pytest.raises(s2v.S2VError):
         s2v._lib.ptr(torch.zeros(4))
