@@ -48,10 +48,11 @@ DIAG_LIB = os.path.join(HERE, "libs2v_hip_diag.so")
 # generated asm (outputs are committed): generator -> EVERY file it writes (a missing one of them re-runs the generator).
 # tests/test_host_cpu.py holds this table to the truth twice: every `#include "*.inc"` / `*_regs.h` under csrc/ must appear here, and each
 # generator, re-run into a scratch directory (S2V_GEN_OUT), must write exactly these files with exactly the committed bytes.
-GENERATORS = [("gen_attn_q4.py", ["attn_q4_body.inc", "attn_q4h_body.inc", "attn_q4f_body.inc", "attn_q4fh_body.inc", "attn_q4hh_body.inc", "attn_q8_body.inc", "attn_q4_regs.h"]),
-              ("gen_gemm_g4.py", ["gemm_g4_body.inc", "gemm_g4_body_f16.inc", "gemm_g4_sk_sum.inc", "gemm_g4_regs.h"]),
+GENERATORS = [("gen_attn_q4.py", ["attn_q4_body.inc", "attn_q4h_body.inc", "attn_q4f_body.inc", "attn_q4fh_body.inc", "attn_q8_body.inc", "attn_q4_regs.h"]),
+              ("gen_gemm_g4.py", ["gemm_g4_body.inc", "gemm_g4_sk_sum.inc", "gemm_g4_regs.h"]),
               ("gen_gemm_g4t.py", ["gemm_g4t_body_gelu.inc", "gemm_g4t_body_bias.inc", "gemm_g4t_body_qknorm.inc", "gemm_g4t_regs.h"]),
               ("gen_gemm_g4f.py", ["gemm_g4f_body_a3.inc", "gemm_g4f_body_mx.inc", "gemm_g4f_regs.h"])]
+GEN_COMMON = os.path.join(CSRC, "asmgen.py")  # imported by every generator: an input of each of them
 
 
 def build_library(force=False, verbose=True, diag=False):
@@ -70,7 +71,7 @@ def build_library(force=False, verbose=True, diag=False):
     headers = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith((".h", ".inc"))]
     headers.append(os.path.join(HERE, "..", "include", "s2v_hip.h"))
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    gen_srcs = [os.path.join(CSRC, g) for g, _ in gens]
+    gen_srcs = [os.path.join(CSRC, g) for g, _ in gens] + [GEN_COMMON]
     whole = _digest(srcs + headers + gen_srcs, FLAGS + [f"{k}:{v}" for k, v in sorted(EXTRA.items())])
     if not force and os.path.exists(LIB) and _read(LIB + ".stamp") == whole:
         if verbose:
@@ -80,9 +81,9 @@ def build_library(force=False, verbose=True, diag=False):
     for g, outs in gens:
         gp, ops = os.path.join(CSRC, g), [os.path.join(CSRC, o) for o in outs]
         stamp = os.path.join(objdir, g + ".stamp")
-        d = _digest([gp])
+        d = _digest([gp, GEN_COMMON])
         missing = [o for o in ops if not os.path.exists(o)]
-        if force or missing or (_read(stamp) != d and any(_stale(o, [gp]) for o in ops)):
+        if force or missing or (_read(stamp) != d and any(_stale(o, [gp, GEN_COMMON]) for o in ops)):
             if verbose:
                 print(f"{sys.executable} {gp}", flush=True)
             subprocess.check_call([sys.executable, gp])

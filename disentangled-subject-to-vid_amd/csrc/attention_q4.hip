@@ -70,8 +70,8 @@ extern "C" __attribute__((visibility("default"))) int s2v_attn_slow_read(unsigne
 // kernel's.  No reference code for it (the reference has no fp8 path): parity unpinned, selected only by weight_format 2.
 // P16 (JB = 2 only, attn_q4h / attn_q4fh): P and V^T in fp16, row sums by packed fp16 adds, deferred maximum 2^14 (gen_attn_q4.py, P16); the
 // code around the body is the same -- the format lives in the V^T buffer (AttnArgs::p16) and in the generated instructions.
-// H16 (JB = 2, with P16, not F8: attn_q4hh): the fp16 model dtype -- q, k and the output are fp16 as well; only the QK^T mnemonic of the body differs from
-// attn_q4h's, and the code around it converts q and packs O as fp16.
+// H16 (JB = 2, with P16, not F8: attn_q4hh): the fp16 model dtype -- q, k and the output are fp16 as well; the body is attn_q4h's with its QK^T MFMAs on fp16 (string
+// macro Q4H_QK16 around the #include), and the code around it converts q and packs O as fp16.
 template <int JB, bool F8 = false, bool P16 = false, bool H16 = false>
 __device__ __forceinline__ void attn_qx_item(const AttnArgs& a, int nqb, int wg, char* smem, unsigned& slow_acc, unsigned& tile_acc) {
     static_assert((!F8 && !P16) || JB == 2, "the fp8 QK^T and fp16 P bodies exist for the four-wave form only");
@@ -198,17 +198,21 @@ __device__ __forceinline__ void attn_qx_item(const AttnArgs& a, int nqb, int wg,
                 : Q4F_CLOBBERS);
         }
     } else if constexpr (H16) {
-        asm volatile(
-#include "attn_q4hh_body.inc"
-            : "=" Q4HH_OT0(OT[0]), "=" Q4HH_OT1(OT[JB - 1]), "=" Q4HH_LRUN(LR), "+" Q4HH_PTR(ptr), "=" Q4HH_CNT(slow_cnt)
-            : Q4HH_QF(qf), Q4HH_VIN(vin), Q4HH_SIN(sin)
-            : Q4HH_CLOBBERS);
-    } else if constexpr (P16) {
+#define Q4H_QK16 "f16"
         asm volatile(
 #include "attn_q4h_body.inc"
             : "=" Q4H_OT0(OT[0]), "=" Q4H_OT1(OT[JB - 1]), "=" Q4H_LRUN(LR), "+" Q4H_PTR(ptr), "=" Q4H_CNT(slow_cnt)
             : Q4H_QF(qf), Q4H_VIN(vin), Q4H_SIN(sin)
             : Q4H_CLOBBERS);
+#undef Q4H_QK16
+    } else if constexpr (P16) {
+#define Q4H_QK16 "bf16"
+        asm volatile(
+#include "attn_q4h_body.inc"
+            : "=" Q4H_OT0(OT[0]), "=" Q4H_OT1(OT[JB - 1]), "=" Q4H_LRUN(LR), "+" Q4H_PTR(ptr), "=" Q4H_CNT(slow_cnt)
+            : Q4H_QF(qf), Q4H_VIN(vin), Q4H_SIN(sin)
+            : Q4H_CLOBBERS);
+#undef Q4H_QK16
     } else if constexpr (JB == 2) {
         asm volatile(
 #include "attn_q4_body.inc"

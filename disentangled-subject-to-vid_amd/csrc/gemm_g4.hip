@@ -34,8 +34,8 @@ extern "C" __attribute__((visibility("default"))) int s2v_g4_debug_read(unsigned
 #define G4_STAMP(i) do { } while (0)
 #endif
 
-// T16 = f16_t (round 5): the fp16 model dtype's linears -- the K loop with v_mfma_f32_32x32x16_f16 (gemm_g4_body_f16.inc: the same generated
-// statement, one mnemonic changed) and the shared vector epilogue decoding / packing fp16 (gemm_epi.h H2<T16>); no split K, no fused q/k norm
+// T16 = f16_t (round 5): the fp16 model dtype's linears -- the K loop with v_mfma_f32_32x32x16_f16 (the same generated statement: its MFMA
+// lines take the element type from the string macro G4_T16) and the shared vector epilogue decoding / packing fp16 (gemm_epi.h H2<T16>); no split K, no fused q/k norm
 template <int EPI, typename T16 = bf16_t>
 __global__ __launch_bounds__(256, 1) void gemm_g4(const GemmArgs a, int tiles_m, int tiles_n) {
     extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x [A 256 rows x 128 B | W 256 rows x 128 B]
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void gemm_g4(const GemmArgs a, int tiles_m,
         voff[p] = (unsigned)(2 * ((int64_t)(srow + p * 32) * a.lda + scol));
         voff[8 + p] = (unsigned)(2 * ((int64_t)(srow + p * 32) * a.ldw + scol));
     }
-    // L2 prefetch: lane l touches the cache line of row (l & 7) * 32 + wave * 8 + (l >> 3) -- the 64 rows of this wave's eight pieces
+    // dead operand (offsets of the rejected L2 prefetch; the body reads neither): still bound, because without it hipcc renumbers the registers around the statement
     u32x2 vpf;
     vpf[0] = (unsigned)(2 * (int64_t)((lane & 7) * 32 + srow) * a.lda);
     vpf[1] = (unsigned)(2 * (int64_t)((lane & 7) * 32 + srow) * a.ldw);
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256, 1) void gemm_g4(const GemmArgs a, int tiles_m,
     ptr[1] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ap >> 32));
     ptr[2] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wp);
     ptr[3] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(wp >> 32));
-    u32x2 sin = {lds0 + wave * 1024, (unsigned)((Ks / 64 - 2 - (G4_PF > 2 ? G4_PF : 2)) / 2)};  // pairs of K-tiles in the asm loop
+    u32x2 sin = {lds0 + wave * 1024, (unsigned)((Ks / 64 - 4) / 2)};  // pairs of K-tiles in the asm loop
 
     // split K: slot (tile, z) of the fp32 partials, [wave][64 register quads][lane] x 16 B
     const int tile = (m0 >> 8) * tiles_n + (n0 >> 8);
@@ -113,19 +113,23 @@ __global__ __launch_bounds__(256, 1) void gemm_g4(const GemmArgs a, int tiles_m,
     G4_STAMP(1);
     f32x32 AC[8];  // acc[i][j] (i: 32-column block of W rows, j: 32-row block of A rows) = registers 64 i + 16 j of a[0:255]
     if constexpr (std::is_same<T16, f16_t>::value) {
-        asm volatile(
-#include "gemm_g4_body_f16.inc"
-            : "=" G4_ACC0(AC[0]), "=" G4_ACC1(AC[1]), "=" G4_ACC2(AC[2]), "=" G4_ACC3(AC[3]), "=" G4_ACC4(AC[4]), "=" G4_ACC5(AC[5]),
-              "=" G4_ACC6(AC[6]), "=" G4_ACC7(AC[7]), "+" G4_PTR(ptr), "+" G4_SIN(sin), "+" G4_VADDR(vaddr)
-            : G4_VOFF(voff), G4_VPF(vpf), G4_SK(sk), G4_VSK(voff16)
-            : G4_CLOBBERS);
-    } else {
+#define G4_T16 "f16"
         asm volatile(
 #include "gemm_g4_body.inc"
             : "=" G4_ACC0(AC[0]), "=" G4_ACC1(AC[1]), "=" G4_ACC2(AC[2]), "=" G4_ACC3(AC[3]), "=" G4_ACC4(AC[4]), "=" G4_ACC5(AC[5]),
               "=" G4_ACC6(AC[6]), "=" G4_ACC7(AC[7]), "+" G4_PTR(ptr), "+" G4_SIN(sin), "+" G4_VADDR(vaddr)
             : G4_VOFF(voff), G4_VPF(vpf), G4_SK(sk), G4_VSK(voff16)
             : G4_CLOBBERS);
+#undef G4_T16
+    } else {
+#define G4_T16 "bf16"
+        asm volatile(
+#include "gemm_g4_body.inc"
+            : "=" G4_ACC0(AC[0]), "=" G4_ACC1(AC[1]), "=" G4_ACC2(AC[2]), "=" G4_ACC3(AC[3]), "=" G4_ACC4(AC[4]), "=" G4_ACC5(AC[5]),
+              "=" G4_ACC6(AC[6]), "=" G4_ACC7(AC[7]), "+" G4_PTR(ptr), "+" G4_SIN(sin), "+" G4_VADDR(vaddr)
+            : G4_VOFF(voff), G4_VPF(vpf), G4_SK(sk), G4_VSK(voff16)
+            : G4_CLOBBERS);
+#undef G4_T16
     }
     G4_STAMP(2);
     __builtin_amdgcn_s_barrier();  // every wave is done with the stages: the epilogue patches alias them
@@ -210,7 +214,7 @@ static int launch_g4_t(const GemmArgs& a_in, hipStream_t st) {
 bool gemm_g4_ok(const GemmArgs& a, int epi) {
     const int S = a.splitk > 1 ? a.splitk : 1;
     const int nT = a.K / S / 64;
-    return !a.conv && a.K % (128 * S) == 0 && nT >= (G4_PF > 2 ? G4_PF : 2) + 2 && a.lda % 8 == 0 && a.ldw % 8 == 0 && epi_vec_ok(a, epi) && a.m_begin == 0 &&
+    return !a.conv && a.K % (128 * S) == 0 && nT >= 4 && a.lda % 8 == 0 && a.ldw % 8 == 0 && epi_vec_ok(a, epi) && a.m_begin == 0 &&
            a.a_rows_padded >= ((a.M + 255) / 256) * 256;
 }
 int gemm_choose_splitk(int64_t tiles, int K, int64_t ncu) {

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generator of the hand-scheduled body of attn_q4 (csrc/attention_q4.hip): writes attn_q4_body.inc -- ONE asm statement that
 takes a work item from "K / V^T tiles 0-3 / 0-1 staged, Q fragments loaded" to "O^T accumulators and row sums complete" -- and
-attn_q4_regs.h (the physical-register constraints and the clobber list of that statement).  Run by build.py when the
-generated files are older than this script; the outputs are committed.
+attn_q4_regs.h (the physical-register constraints and the clobber list of that statement); the fp8-QK^T, fp16-P and eight-wave forms
+(attn_q4f / attn_q4h / attn_q4fh / attn_q8 bodies) come from the same stream.  Run by build.py when stale; the outputs are committed.
 
 Why generated asm: with more than 256 registers per lane hipcc selects the AGPR form for every MFMA builtin and copies the
 scores to VGPRs for the softmax, and its allocator does not fit S (128) + -m (32) + P (32) into the 256 VGPRs without
@@ -10,7 +10,7 @@ shuttling tuples through AGPRs; the loop is issue-bound (about six fillers per M
 A first version kept the rare paths in C++ and left the asm at the checks: the register shuffling and scratch spills hipcc put
 around each exit cost 3.8 ms of a 10.9 ms launch, so everything between the prologue's DMA and the epilogue is in here.
 
-Two forms from one generator (Q4_JB = 32-row blocks per wave): JB = 2 -> attn_q4, four waves x 64 rows, one wave per SIMD, a K / V^T
+Two forms from one generator (JB = 32-row blocks per wave): JB = 2 -> attn_q4, four waves x 64 rows, one wave per SIMD, a K / V^T
 fragment feeds two MFMAs; JB = 1 -> attn_q8, eight waves x 32 rows, two waves per SIMD running the SAME fine-grained stream
 (MFMA, five fillers, MFMA ...) side by side -- a lone wave issues one VALU per 4.9 cycles (8.9 for v_exp_f32), so at head
 dimension 64 (16 MFMA = 512 matrix-pipe cycles against 80 softmax VALU per 32 rows) one wave per SIMD is issue-bound.
@@ -31,7 +31,8 @@ Phases: A = iterations t < nt - 5 (threshold 2^64: a check fires only for a genu
 every check enters the rare-path handler, which applies the staging clamp, the tail mask and the real threshold).
 """
 import os
-import sys
+
+from asmgen import ablations, ar, define_clobbers, define_regs, drops_opcodes, emitter, out_dir, ptr_advance, sr, vr, write_inc
 
 JB = 2  # set by main() per output
 # F8 (set by main() for attn_q4f_body.inc, JB = 2 only): Q and K are MX e4m3 images (32-element blocks along the head dimension, one E8M0 scale
@@ -55,9 +56,9 @@ F8 = False
 #     is dropped only below 2^-25 of the weight of the row's maximum key, the whole tail of N <= 2^17 such keys weighs < 2^-8 of that key alone;
 #   * P keeps 11 significant bits (bf16: 8), V^T is converted bf16 -> fp16 by the transpose pass (exact above 2^-14).
 P16 = False
-# H16 (attn_q4hh_body.inc, JB = 2, with P16): q and k are fp16 too (the fp16 model dtype, src/inference.py:191) -- QK^T on v_mfma_f32_32x32x16_f16.  The
-# register map, the schedule and every other instruction are attn_q4h's: staging and fragment reads move 16-bit elements whatever they encode.
-H16 = False
+# The fp16 model dtype (attn_q4hh: q and k fp16 too) runs the SAME body: the QK^T lines of attn_q4h_body.inc end in the string macro Q4H_QK16 ("bf16"
+# or "f16"), which attention_q4.hip defines around each #include -- staging and fragment reads move 16-bit elements whatever they encode.
+QK16 = 'v_mfma_f32_32x32x16_" Q4H_QK16 "'  # closes and reopens the string literal of the line
 # Deferred maximum: a row keeps the maximum its first tile adopted until a partial row sum of a later tile exceeds 2^64, i.e. until some
 # p = exp2(s - m) does -- fp32 and bf16 share the exponent range, sums and P.V stay below 2^64 * N * |v| << 2^127, and every quantity is
 # scale-free, so nothing is lost by letting m lag (keys 2^126 below the adopted maximum flush to zero, as they would below any maximum).
@@ -76,27 +77,24 @@ def thr_b():   # phase B: -1, every check fires
 
 def cmp_thr(s_thr):   # vcc <- v[VS] beyond the threshold in SGPR s_thr (or NaN)
     return f"v_cmp_ngt_f16 vcc, s{s_thr}, {vr(VS)}" if P16 else f"v_cmp_nge_f32 vcc, s{s_thr}, {vr(VS)}"
-ORDER = os.environ.get("Q4_ORDER", "")  # placement experiments
-READPOS = os.environ.get("Q4_READPOS", "first")  # fragment read first in its gap: -3 % against last (A/B, profiles/r03_attn_q4_placement.txt)
-READS = os.environ.get("Q4_READS", "")
-DMAPOS = os.environ.get("Q4_DMAPOS", "")
-SPLIT = os.environ.get("Q4_SPLIT", "")
-# Row sums: "add" = four v_add_f32 per four scores on the fp32 exp2 results (product).  "dot" = v_dot2c_f32_bf16 acc, <1.0 | 1.0>, pk:
-# ONE instruction adds the two bf16 values of a packed P register (the numbers the P.V MFMA multiplies) to the row sum -- 8 softmax
-# VALU per four scores instead of 10, results correct (harness: 46 checks ok) -- but the dot2 issues slower than the two adds it
-# replaces: 7.95 ms against 7.40 at C3 on the same box (tools/q4_ablate.sh build "dot=Q4_SUM=dot" "add=Q4_SUM=add"), so it stays an option.
-# "pk" = v_pk_add_f32 on the accumulator pair (two adds per instruction, fp32 as now): 8.15 ms against 7.43.  Both packed forms cost more
-# issue time than the two plain VALU they replace (round 2 measured 21.5 cycles per v_pk_*_f32 beside an MFMA stream): on this part the
-# softmax stream cannot be shortened by wider VALU instructions.
-SUM = os.environ.get("Q4_SUM", "add")
-ABLATE = set(filter(None, os.environ.get("Q4_ABLATE", "").split(",")))  # timing experiments only (results are wrong)
+
+
+# Softmax stream of the bf16 forms: per group of four scores, exp2 x 4 of this group, then v_add_f32 x 4 (row sums on the fp32 exp2 results) and
+# v_cvt_pk x 2 of the group before -- five per MFMA gap, the fragment read first in its gap, the LDS-DMA last in its.  Rejected (HISTORY.md, attention
+# and section 12):
+#   * the read last in its gap: +3 %; exp2 last in its gap, a uniform [exp add exp add cvt] gap, 6 / 4 ops in gaps without / with a read, all reads in the
+#     first eight gaps, the LDS-DMA first in its gap: 7.36-7.48 ms against 7.40 at C3 (profiles/r03_attn_q4_placement.txt)
+#   * row sums by v_dot2c_f32_bf16 on the packed P registers: 7.95 ms against 7.40; by v_pk_add_f32: 8.15 against 7.43 (HISTORY.md)
+#   * row sums on the matrix pipe, a ninth MFMA per k-step (profiles/r03_attn_sum_by_mfma.txt)
+ABLATE = ablations("Q4_ABLATE")  # timing experiments of tools/q4_ablate.sh (results are wrong)
+DROPS = {"nodma": ["global_load_lds_dwordx4"], "noread": ["ds_read_b128"], "nobar": ["s_barrier"],
+         "nosoft": ["v_exp_f32", "v_add_f32", "v_mov_b32", "v_cvt_pk_bf16_f32", "v_cvt_pk_f16_f32", "v_pk_add_f16"]}
 S_KPTR, S_VPTR, S_T, S_END, S_KADV, S_VADV, S_NT, S_KSTR, S_NTOK, S_M0W, S_THR, S_RET, S_X0, S_X1, S_CNT, S_ONES = 36, 38, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53
 S_KSB, S_KSX, S_NTM1, S_KSA = 54, 56, 57, 58  # F8: IN K block-scale base (64-bit); scratch; nt - 1; address of the tile being loaded (64-bit)
 
 
-def layout(jb, f8=False, p16=False, h16=False):
-    global JB, ST, NEGM, PK, TMP, PS, VIN, LRUN, VS, OT, QF, KF, VF, NM, F8, KS, QS, KIN, P16, H16
-    H16 = h16
+def layout(jb, f8=False, p16=False):
+    global JB, ST, NEGM, PK, TMP, PS, VIN, LRUN, VS, OT, QF, KF, VF, NM, F8, KS, QS, KIN, P16
     JB = jb
     F8 = f8
     P16 = p16
@@ -111,14 +109,6 @@ def layout(jb, f8=False, p16=False, h16=False):
     KS = VS + 12           # F8: ring of four K block-scale registers (tile t -> KS + (t & 3)); IN: the first three
     QS = KS + 4            # F8: IN Q block scales of row block j
     KIN = QS + 2           # F8: IN [0 / 1] address of chunks hi / 2 + hi of the lane's key in slot 0 (e4m3 K tile), [2] 4 * lane (scale dword of a tile)
-
-
-def vr(base, n=1):
-    return f"v{base}" if n == 1 else f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=1):
-    return f"a{base}" if n == 1 else f"a[{base}:{base + n - 1}]"
 
 
 def st(buf, j, kb):
@@ -153,20 +143,6 @@ def soft_stream(sb, kb, sset):
         e0 = (g & 3) * 4
         dst = pk(g >> 2, kb * 2 + (e0 >> 3)) + ((e0 & 7) >> 1) + c
         return f"v_cvt_pk_bf16_f32 {vr(dst)}, {vr(tmp(g, 2 * c))}, {vr(tmp(g, 2 * c + 1))}"
-
-    def dot(g, c):
-        e0 = (g & 3) * 4
-        src = pk(g >> 2, kb * 2 + (e0 >> 3)) + ((e0 & 7) >> 1) + c
-        acc = vr(ps(sset, g >> 2, c))
-        if kb == 0 and (g & 3) == 0:  # first touch of this accumulator in the tile
-            return f"v_dot2_f32_bf16 {acc}, {vr(src)}, s{S_ONES}, 0"
-        return f"v_dot2c_f32_bf16 {acc}, s{S_ONES}, {vr(src)}"
-
-    def pkadd(g, h):  # two row-sum adds in one v_pk_add_f32: accumulators ps[.][j][0:1] += exp2 results tmp[g][2h : 2h + 1]
-        acc = vr(ps(sset, g >> 2, 0), 2)
-        if kb == 0 and (g & 3) == 0 and h == 0:
-            return f"v_pk_add_f32 {acc}, {vr(tmp(g, 0), 2)}, 0"
-        return f"v_pk_add_f32 {acc}, {acc}, {vr(tmp(g, 2 * h), 2)}"
 
     def cvth(g, c):
         e0 = (g & 3) * 4
@@ -208,44 +184,10 @@ def soft_stream(sb, kb, sset):
                     assert pos // 4 >= 4 * ss + 2 * jj + 2, (o, pos)
         assert len(ops) == 32 * JB + (JB if kb == 1 else 0)
         return ops
-    if SUM == "pk":
-        ops = [exp(0, x) for x in range(4)]
-        for g in range(1, ng):
-            ops += [exp(g, 0), exp(g, 1), pkadd(g - 1, 0), cvt(g - 1, 0), exp(g, 2), exp(g, 3), pkadd(g - 1, 1), cvt(g - 1, 1)]
-        ops += [pkadd(ng - 1, 0), cvt(ng - 1, 0), pkadd(ng - 1, 1), cvt(ng - 1, 1)]
-        assert len(ops) == 32 * JB
-        return ops
-    if SUM == "dot":  # per group of four scores: exp2 x 4 of this group, cvt_pk x 2 + dot2 x 2 of the group before
-        ops = [exp(0, x) for x in range(4)]
-        for g in range(1, ng):
-            ops += [exp(g, 0), exp(g, 1), cvt(g - 1, 0), dot(g - 1, 0), exp(g, 2), exp(g, 3), cvt(g - 1, 1), dot(g - 1, 1)]
-        ops += [cvt(ng - 1, 0), dot(ng - 1, 0), cvt(ng - 1, 1), dot(ng - 1, 1)]
-        assert len(ops) == 32 * JB
-        return ops
-    if ORDER == "uniform":  # every gap of five = [exp, add, exp, add, cvt]: two exp2 per gap; adds / cvt belong to the group before
-        ops = []
-        for g in range(ng + 1):
-            for h in range(2):
-                if g < ng:
-                    ops.append(exp(g, 2 * h))
-                if g > 0:
-                    ops.append(add(g - 1, 2 * h))
-                if g < ng:
-                    ops.append(exp(g, 2 * h + 1))
-                if g > 0:
-                    ops.append(add(g - 1, 2 * h + 1))
-                    ops.append(cvt(g - 1, h))
-    elif ORDER == "explast":  # per pair of gaps: [add add cvt cvt exp][add add exp exp exp]: exp2 at the END of a gap
-        ops = [exp(0, x) for x in range(4)]
-        for g in range(1, ng):
-            ops += [add(g - 1, 0), add(g - 1, 1), cvt(g - 1, 0), add(g - 1, 2), add(g - 1, 3), cvt(g - 1, 1), exp(g, 0), exp(g, 1), exp(g, 2), exp(g, 3)]
-        ops += [add(ng - 1, x) for x in range(4)] + [cvt(ng - 1, 0), cvt(ng - 1, 1)]
-    else:
-        ops = [exp(0, x) for x in range(4)]
-        for g in range(1, ng):
-            ops += [exp(g, 0), exp(g, 1), add(g - 1, 0), add(g - 1, 1), exp(g, 2), exp(g, 3), add(g - 1, 2), add(g - 1, 3),
-                    cvt(g - 1, 0), cvt(g - 1, 1)]
-        ops += [add(ng - 1, x) for x in range(4)] + [cvt(ng - 1, 0), cvt(ng - 1, 1)]
+    ops = [exp(0, x) for x in range(4)]
+    for g in range(1, ng):
+        ops += [exp(g, 0), exp(g, 1), add(g - 1, 0), add(g - 1, 1), exp(g, 2), exp(g, 3), add(g - 1, 2), add(g - 1, 3), cvt(g - 1, 0), cvt(g - 1, 1)]
+    ops += [add(ng - 1, x) for x in range(4)] + [cvt(ng - 1, 0), cvt(ng - 1, 1)]
     assert len(ops) == 40 * JB
     return ops
 
@@ -273,7 +215,7 @@ def qk_mfma(buf, i):
     j, kb, kk = i % JB, (i // JB) & 1, i // (2 * JB)
     d = vr(st(buf, j, kb), 16)
     c = vr(NEGM + 16 * j, 16) if kk == 0 else d
-    return f"v_mfma_f32_32x32x16_{'f16' if H16 else 'bf16'} {d}, {ar(KF + 4 * (kk * 2 + kb), 4)}, {ar(QF + 16 * j + 4 * kk, 4)}, {c}"
+    return f"{QK16 if P16 else 'v_mfma_f32_32x32x16_bf16'} {d}, {ar(KF + 4 * (kk * 2 + kb), 4)}, {ar(QF + 16 * j + 4 * kk, 4)}, {c}"
 
 
 def pv_mfma(i):
@@ -385,40 +327,22 @@ def mask_tile(emit, buf, s_kv0):
 
 
 def gen():
-    L = []
-    ctx = set()
+    by_opcode = drops_opcodes(ABLATE, DROPS)
 
-    def emit(ln):
-        op = ln.split()[0]
-        if "nodma" in ABLATE and op == "global_load_lds_dwordx4":
-            return
-        if "noread" in ABLATE and op == "ds_read_b128":
-            return
-        if "nosoft" in ABLATE and op in ("v_exp_f32", "v_add_f32", "v_mov_b32", "v_cvt_pk_bf16_f32", "v_cvt_pk_f16_f32", "v_pk_add_f16"):
-            return
-        if "movexp" in ABLATE and op == "v_exp_f32":
-            ln = ln.replace("v_exp_f32", "v_mov_b32")
-        if "nobar" in ABLATE and op == "s_barrier":
-            return
-        if "nowait" in ABLATE and ln.startswith("s_waitcnt lgkmcnt"):
-            return
-        if "nomfma" in ABLATE and op.startswith("v_mfma"):
-            return
-        if "noadd" in ABLATE and (op == "v_add_f32" or (op == "v_mov_b32" and "main" in ctx)):  # row sums off the VALU (timing of a sum-by-MFMA form)
-            return
-        L.append(ln)
+    def drop(ln):
+        return by_opcode(ln) or ("nowait" in ABLATE and ln.startswith("s_waitcnt lgkmcnt")) or ("nomfma" in ABLATE and ln.startswith("v_mfma"))
 
-    def soft_lo(i):  # first softmax op of gap i: five per gap (four with the dot2 row sums), or (SPLIT = "64") six in gaps without a fragment read and four in those with one
-        if SUM in ("dot", "pk") or P16:
-            return 4 * i
-        if SPLIT == "64" and JB == 2:
-            return 5 * i + (i & 1)
-        return 5 * i
+    L, put = emitter(drop)
+
+    def emit(*lines):  # movexp: the transcendental at the price of a plain VALU
+        put(*(ln.replace("v_exp_f32", "v_mov_b32") if "movexp" in ABLATE and ln.split()[0] == "v_exp_f32" else ln for ln in lines))
+
+    def soft_lo(i):  # first softmax op of gap i: five per gap (P16: four)
+        return (4 if P16 else 5) * i
 
     # where the extra fillers of a segment go (gap index -> instruction), besides five softmax ops per gap
     gap_m0 = [3, 9] if JB == 2 else [2]     # M0 <- LDS address of the wave's piece p
     gap_dma = [5, 11] if JB == 2 else [4]   # the piece's LDS-DMA (at least one instruction after the M0 write)
-    read_gaps = range(0, NM, JB) if READS != "front" else range(8)            # eight fragment reads per segment
 
     emit(f"; ---- attn_q{8 // JB} body (generated by gen_attn_q4.py; do not edit)")
     # ---------------- state
@@ -431,7 +355,7 @@ def gen():
     emit(f"s_mov_b32 s{S_T}, 0")
     emit(f"s_mov_b32 s{S_CNT}, 0")               # OUT: slow paths taken by this wave (diagnostics)
     emit(f"s_mov_b32 s{S_THR}, {thr_a()}")      # 2^64 (P16: 2^14 as fp16)
-    emit(f"s_mov_b32 s{S_ONES}, 0x3f803f80")         # bf16 (1.0, 1.0)
+    emit(f"s_mov_b32 s{S_ONES}, 0x3f803f80")         # bf16 (1.0, 1.0): read by nothing since the dot2 row sums went; the emitted stream is pinned
     emit(f"s_mov_b32 s{S_KADV}, s{S_KSTR}")
     emit(f"s_mov_b32 s{S_VADV}, 128")
     if F8:
@@ -471,7 +395,6 @@ def gen():
     slow_path(emit, 0, True)
     emit("s_branch L_q4_e0_%=")
     # ---------------- main loop, unrolled over four tiles (U = t mod 4: st buffers and LDS slots are immediates)
-    ctx.add("main")
     for U in range(4):
         cur, nxt = U & 1, (U & 1) ^ 1
         # segment 1: S(t+1) = K(t+1).Q^T -> st[nxt]; second half of P(t); V^T(t) fragments; K(t+4) pieces
@@ -480,13 +403,13 @@ def gen():
         soft = soft_stream(cur, 1, cur)
         for i in range(NM):
             first, last = [], []
-            if i in read_gaps:
-                (first if READPOS == "first" else last).append(frag_read(VF, list(read_gaps).index(i), U, True))
+            if i % JB == 0:  # eight fragment reads per segment
+                first.append(frag_read(VF, i // JB, U, True))
             for p in range(1 if F8 else JB):  # F8: an e4m3 K tile is one piece per wave
                 if i == gap_m0[p]:
                     last.append(f"s_add_u32 m0, s{S_M0W}, {U * 16384 + p * 4096}")
                 if i == gap_dma[p]:
-                    (first if DMAPOS == "first" else last).append(f"global_load_lds_dwordx4 {vr(VIN + 4 + p)}, s[{S_KPTR}:{S_KPTR + 1}]")
+                    last.append(f"global_load_lds_dwordx4 {vr(VIN + 4 + p)}, {sr(S_KPTR, 2)}")
             if F8 and i == gap_m0[1]:   # block scales of K tile min(t + 3, nt - 1) -> ring register (t + 3) & 3
                 last += [f"s_add_u32 s{S_KSX}, s{S_T}, 3", f"s_min_u32 s{S_KSX}, s{S_KSX}, s{S_NTM1}", f"s_lshl_b32 s{S_KSX}, s{S_KSX}, 8"]
             if F8 and i == gap_m0[1] + 1:
@@ -494,13 +417,12 @@ def gen():
             if F8 and i == gap_dma[1]:
                 last.append(f"global_load_dword {vr(KS + ((U + 3) & 3))}, {vr(KIN + 2)}, s[{S_KSA}:{S_KSA + 1}]")
             if i == NM - 2:
-                last += [f"s_add_u32 s{S_KPTR}, s{S_KPTR}, s{S_KADV}", f"s_addc_u32 s{S_KPTR + 1}, s{S_KPTR + 1}, 0"]
+                last += ptr_advance(S_KPTR, f"s{S_KADV}")
             if F8:  # four 64-cycle MFMAs, one per four gaps of the softmax stream
                 head = [qk_mfma_f8(nxt, i // 4, (U + 1) & 3)] if i % 4 == 0 else []
             else:
                 head = [qk_mfma(nxt, i)]
-            for ln in head + first + soft[soft_lo(i):(soft_lo(i + 1) if i + 1 < NM else len(soft))] + last:
-                emit(ln)
+            emit(*head, *first, *soft[soft_lo(i):(soft_lo(i + 1) if i + 1 < NM else len(soft))], *last)
         # check of tile t: the partial row sums against the threshold (any lane)
         max_ps(emit, cur)
         emit(cmp_thr(S_THR))  # row sum > threshold, or NaN
@@ -515,9 +437,9 @@ def gen():
             first, last = [], []
             if F8:
                 if i in (0, 2, 4, 6):
-                    (first if READPOS == "first" else last).append(frag_read_k8(i >> 1, slot2))
-            elif i in read_gaps:
-                (first if READPOS == "first" else last).append(frag_read(KF, list(read_gaps).index(i), slot2, False))
+                    first.append(frag_read_k8(i >> 1, slot2))
+            elif i % JB == 0:
+                first.append(frag_read(KF, i // JB, slot2, False))
             if P16:  # l += the two halves of the packed fp16 accumulator of tile t (complete since segment 1): one instruction per gap
                 jj, st4 = i >> 3, (i & 7) >> 1
                 if (i & 1) == 1:
@@ -533,15 +455,9 @@ def gen():
                 if i == gap_m0[p]:
                     last.append(f"s_add_u32 m0, s{S_M0W}, {slot2 * 16384 + 8192 + p * 4096}")
                 if i == gap_dma[p]:
-                    (first if DMAPOS == "first" else last).append(f"global_load_lds_dwordx4 {vr(VIN + 6 + p)}, s[{S_VPTR}:{S_VPTR + 1}]")
-            extra = []
-            if "summfma" in ABLATE and (i & 1) == 1:  # timing only: one more MFMA per (row block, k-step), as a sum-by-MFMA form would issue
-                jx = (i >> 1) % JB
-                extra = [f"v_mfma_f32_32x32x16_bf16 {ar(VF + 32 + 16 * jx, 16)}, {ar(VF + 64, 4)}, {vr(pk(jx, i // (2 * JB)), 4)}, {ar(VF + 32 + 16 * jx, 16)}"]
-            for ln in [pv_mfma(i)] + first + soft[soft_lo(i):soft_lo(i + 1)] + last + extra:
-                emit(ln)
-        emit(f"s_add_u32 s{S_VPTR}, s{S_VPTR}, s{S_VADV}")
-        emit(f"s_addc_u32 s{S_VPTR + 1}, s{S_VPTR + 1}, 0")
+                    last.append(f"global_load_lds_dwordx4 {vr(VIN + 6 + p)}, {sr(S_VPTR, 2)}")
+            emit(pv_mfma(i), *first, *soft[soft_lo(i):soft_lo(i + 1)], *last)
+        emit(*ptr_advance(S_VPTR, f"s{S_VADV}"))
         emit(f"s_waitcnt vmcnt({2 * JB})")
         emit("s_barrier")
         emit(f"s_add_u32 s{S_T}, s{S_T}, 1")
@@ -549,7 +465,6 @@ def gen():
         emit("s_cbranch_scc0 L_q4_phase_%=")
         if U == 3:
             emit("s_branch L_q4_e0_%=")
-    ctx.discard("main")
     # ---------------- end of a phase: A -> B (threshold -1, no more K advance), or finished
     emit("L_q4_phase_%=:")
     emit(f"s_cmp_ge_u32 s{S_T}, s{S_NT}")
@@ -602,15 +517,12 @@ def gen():
 
 
 def main():
-    here = os.environ.get("S2V_GEN_OUT") or os.path.dirname(os.path.abspath(__file__))  # S2V_GEN_OUT: tests/test_host_cpu.py regenerates into a scratch directory
+    here = out_dir(__file__)
     with open(os.path.join(here, "attn_q4_regs.h"), "w") as f:
         f.write("// generated by gen_attn_q4.py: the physical registers the bodies of attn_q4 (JB = 2) / attn_q8 (JB = 1) own\n#pragma once\n")
-        for jb, name, f8, p16, h16 in ((2, "Q4", False, False, False), (1, "Q8", False, False, False), (2, "Q4F", True, False, False), (2, "Q4H", False, True, False),
-                                       (2, "Q4FH", True, True, False), (2, "Q4HH", False, True, True)):
-            layout(jb, f8, p16, h16)
-            with open(os.path.join(here, f"attn_{name.lower()}_body.inc"), "w") as g:
-                for ln in gen():
-                    g.write('"' + ln + '\\n\\t"\n')
+        for jb, name, f8, p16 in ((2, "Q4", False, False), (1, "Q8", False, False), (2, "Q4F", True, False), (2, "Q4H", False, True), (2, "Q4FH", True, True)):
+            layout(jb, f8, p16)
+            write_inc(os.path.join(here, f"attn_{name.lower()}_body.inc"), gen())
             clob = [f"v{r}" for r in list(range(0, VIN)) + list(range(VS, VS + 12))] + [f"a{r}" for r in range(KF, VF + 32)]
             clob += [f"s{r}" for r in (S_T, S_END, S_KADV, S_VADV, S_THR, S_RET, S_X0, S_X1, S_ONES)]
             extra = []
@@ -619,9 +531,9 @@ def main():
                 extra = [("KS", "v", KS, 4), ("QS", "v", QS, 2), ("KIN", "v", KIN, 4), ("KSB", "s", S_KSB, 2)]  # KS is in / out ("+"): the body reloads the ring
             for nm, cls, base, n in [("VIN", "v", VIN, 8), ("LRUN", "v", LRUN, 2), ("QF", "a", QF, (8 if f8 else 16) * jb), ("PTR", "s", S_KPTR, 4),
                                      ("SIN", "s", S_NT, 4)] + extra + [(f"OT{j}", "a", OT + 32 * j, 32) for j in range(jb)]:
-                f.write(f'#define {name}_{nm} "{{{cls}[{base}:{base + n - 1}]}}"\n')
-            f.write(f'#define {name}_CNT "{{s{S_CNT}}}"\n')
-            f.write(f"#define {name}_CLOBBERS " + ", ".join(f'"{c}"' for c in clob) + ', "vcc", "scc", "m0", "memory"\n')
+                f.write(define_regs(f"{name}_{nm}", cls, base, n))
+            f.write(define_regs(f"{name}_CNT", "s", S_CNT))
+            f.write(define_clobbers(f"{name}_CLOBBERS", clob))
 
 
 if __name__ == "__main__":

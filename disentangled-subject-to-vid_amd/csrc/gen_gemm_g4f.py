@@ -25,16 +25,10 @@ A stage rotation (a3); s[44:45] IN scale source (mx), s47 IN bytes between the s
 """
 import os
 
+from asmgen import ar, define_clobbers, define_regs, emitter, frag_read, lds_dma, m0_piece, out_dir, ptr_advance, sr, vr, write_inc
+
 FRAG, VADDR, VOFF, ABASE, V_SH, V_SOFF, V_SRD, V_SB, V_UNIT = 0, 128, 144, 160, 164, 165, 166, 168, 176
 S_A, S_W, S_M0W, S_CNT, S_ANEXT, S_ADMA, S_AM0, S_SC, S_SM0 = 36, 38, 40, 41, 42, 43, 48, 44, 46
-
-
-def vr(b, n=1):
-    return f"v{b}" if n == 1 else f"v[{b}:{b + n - 1}]"
-
-
-def ar(b, n):
-    return f"a[{b}:{b + n - 1}]"
 
 
 def wf(buf, i):
@@ -64,12 +58,9 @@ def mfma(emit, M, t_par, s, k, first):
     emit(f"v_mfma_scale_f32_32x32x64_f8f6f4 {acc}, {vr(wf(s, i), 8)}, {vr(af(s, j), 8)}, {c}, {vr(V_UNIT)}, {sb} op_sel_hi:[0,{hi},0]")
 
 
-def frag_read(emit, buf, n, kk, g, s):
+def frag(buf, n, kk, g, s):
     """chunk kk of fragment n (0-3 W, 4-7 A) of step s of the K-tile whose fragment-address set is g -> buffer buf"""
-    if n < 4:
-        emit(f"ds_read_b128 {vr(wf(buf, n) + 4 * kk, 4)}, {vr(vaddr(True, g, 2 * s + kk))} offset:{n * 4096}")
-    else:
-        emit(f"ds_read_b128 {vr(af(buf, n - 4) + 4 * kk, 4)}, {vr(vaddr(False, g, 2 * s + kk))} offset:{(n - 4) * 4096}")
+    return frag_read((wf(buf, n) if n < 4 else af(buf, n - 4)) + 4 * kk, vaddr(n < 4, g, 2 * s + kk), n)
 
 
 def ktile(emit, M, g, first=False, dma=True, last=False):
@@ -79,8 +70,7 @@ def ktile(emit, M, g, first=False, dma=True, last=False):
     mx = M.mx
     for s in range(2):
         if s == 1 and not last:
-            emit(f"s_waitcnt vmcnt({8 if dma else 0}) lgkmcnt(0)")
-            emit("s_barrier")
+            emit(f"s_waitcnt vmcnt({8 if dma else 0}) lgkmcnt(0)", "s_barrier")
         else:
             emit("s_waitcnt lgkmcnt(0)")
         if mx and s == 0:  # byte 0 / 2 = blocks hi / 2 + hi of the K-tile
@@ -93,67 +83,54 @@ def ktile(emit, M, g, first=False, dma=True, last=False):
             mfma(emit, M, g, s, k, first)
             n, kk = k >> 1, k & 1
             if s == 0:
-                frag_read(emit, 1, n, kk, g, 1)              # this K-tile's step 1
+                emit(frag(1, n, kk, g, 1))                   # this K-tile's step 1
             elif not last:
-                frag_read(emit, 0, n, kk, g ^ 1, 0)          # the next K-tile's step 0 (behind the barrier)
+                emit(frag(0, n, kk, g ^ 1, 0))               # the next K-tile's step 0 (behind the barrier)
             p = k >> 1
             if mx and s == 0 and k == 0 and not last:        # scales of K-tile t+1, older than every A piece of this step
-                emit(f"global_load_dwordx4 {vr(V_SB + 4 * (g ^ 1), 4)}, {vr(V_SOFF)}, s[{S_SC}:{S_SC + 1}]")
+                emit(f"global_load_dwordx4 {vr(V_SB + 4 * (g ^ 1), 4)}, {vr(V_SOFF)}, {sr(S_SC, 2)}")
             if s == 0 and dma:   # A piece p of K-tile t+2 -> A stage (t+2) % 3
-                emit(f"s_add_u32 m0, s{S_AM0}, {p * 4096}" if k & 1 == 0 else f"global_load_lds_dwordx4 {vr(VOFF + p)}, s[{S_A}:{S_A + 1}]")
+                emit(m0_piece(S_AM0, p * 4096) if k & 1 == 0 else lds_dma(VOFF + p, S_A))
             if s == 0 and not last and k >= 12:  # A fragment addresses of K-tile t+1 (set g^1)
                 emit(f"v_add_u32 {vr(vaddr(False, g ^ 1, k - 12))}, s{S_ANEXT}, {vr(ABASE + k - 12)}")
             if s == 1 and dma:   # W piece p of K-tile t+2 -> W stage g
-                emit(f"s_add_u32 m0, s{S_M0W}, {M.W_BASE + g * M.W_STRIDE + p * 4096}" if k & 1 == 0 else f"global_load_lds_dwordx4 {vr(VOFF + 8 + p)}, s[{S_W}:{S_W + 1}]")
+                emit(m0_piece(S_M0W, M.W_BASE + g * M.W_STRIDE + p * 4096) if k & 1 == 0 else lds_dma(VOFF + 8 + p, S_W))
         if s == 0 and dma:
-            emit(f"s_add_u32 s{S_A}, s{S_A}, 128")
-            emit(f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0")
+            emit(*ptr_advance(S_A))
         if s == 0 and not last:
-            emit(f"s_mov_b32 s{S_ANEXT}, s{S_ADMA}")
-            emit(f"s_add_u32 s{S_ADMA}, s{S_ADMA}, {M.A_STRIDE}")
-            emit(f"s_cmp_ge_u32 s{S_ADMA}, {3 * M.A_STRIDE}")
-            emit(f"s_cselect_b32 s{S_ADMA}, 0, s{S_ADMA}")
+            emit(f"s_mov_b32 s{S_ANEXT}, s{S_ADMA}", f"s_add_u32 s{S_ADMA}, s{S_ADMA}, {M.A_STRIDE}", f"s_cmp_ge_u32 s{S_ADMA}, {3 * M.A_STRIDE}",
+                 f"s_cselect_b32 s{S_ADMA}, 0, s{S_ADMA}")
             if mx:
-                emit(f"s_add_u32 s{S_SC}, s{S_SC}, s{S_SM0 + 1}")
-                emit(f"s_addc_u32 s{S_SC + 1}, s{S_SC + 1}, 0")
+                emit(*ptr_advance(S_SC, f"s{S_SM0 + 1}"))
         if s == 1 and dma:
-            emit(f"s_add_u32 s{S_W}, s{S_W}, 128")
-            emit(f"s_addc_u32 s{S_W + 1}, s{S_W + 1}, 0")
+            emit(*ptr_advance(S_W))
 
 
 def prologue(emit, M):
     def pieces(is_w, stage):
+        base, sp = ((M.W_BASE + stage * M.W_STRIDE), S_W) if is_w else (stage * M.A_STRIDE, S_A)
         for p in range(8):
-            base = (M.W_BASE + stage * M.W_STRIDE) if is_w else stage * M.A_STRIDE
-            emit(f"s_add_u32 m0, s{S_M0W}, {base + p * 4096}")
-            emit("s_nop 0")
-            emit(f"global_load_lds_dwordx4 {vr(VOFF + (8 if is_w else 0) + p)}, s[{S_W if is_w else S_A}:{(S_W if is_w else S_A) + 1}]")
-        sp = S_W if is_w else S_A
-        emit(f"s_add_u32 s{sp}, s{sp}, 128")
-        emit(f"s_addc_u32 s{sp + 1}, s{sp + 1}, 0")
+            emit(m0_piece(S_M0W, base + p * 4096), "s_nop 0", lds_dma(VOFF + (8 if is_w else 0) + p, sp))
+        emit(*ptr_advance(sp))
 
     emit(f"v_mov_b32 {vr(V_UNIT)}, 0x7f7f7f7f")
     if M.mx:   # K-tile 0's scale dwords first (K-tile 1's follow in step 0 of K-tile 0)
-        emit(f"global_load_dwordx4 {vr(V_SB, 4)}, {vr(V_SOFF)}, s[{S_SC}:{S_SC + 1}]")
-        emit(f"s_add_u32 s{S_SC}, s{S_SC}, s{S_SM0 + 1}")
-        emit(f"s_addc_u32 s{S_SC + 1}, s{S_SC + 1}, 0")
+        emit(f"global_load_dwordx4 {vr(V_SB, 4)}, {vr(V_SOFF)}, {sr(S_SC, 2)}", *ptr_advance(S_SC, f"s{S_SM0 + 1}"))
     # K-tiles 0 and 1 whole; K-tile 2's A half follows in step 0 of K-tile 0
     pieces(False, 0); pieces(True, 0); pieces(False, 1); pieces(True, 1)
     emit(f"s_mov_b32 s{S_ANEXT}, {M.A_STRIDE}")
     emit(f"s_mov_b32 s{S_ADMA}, {2 * M.A_STRIDE}")
     for x in range(4):
         emit(f"v_mov_b32 {vr(ABASE + x)}, {vr(vaddr(False, 0, x))}")
-    emit("s_waitcnt vmcnt(16)")
-    emit("s_barrier")
+    emit("s_waitcnt vmcnt(16)", "s_barrier")
     for n in range(8):
         for kk in range(2):
-            frag_read(emit, 0, n, kk, 0, 0)
+            emit(frag(0, n, kk, 0, 0))
 
 
 def gen(mx):
     M = Map(mx)
-    L = []
-    emit = L.append
+    L, emit = emitter()
     emit(f"; ---- gemm_g4f K loop, {'mx' if mx else 'a3'} (generated by gen_gemm_g4f.py; do not edit)")
     prologue(emit, M)
     ktile(emit, M, 0, first=True)
@@ -175,25 +152,22 @@ def gen(mx):
 
 
 def main():
-    here = os.environ.get("S2V_GEN_OUT") or os.path.dirname(os.path.abspath(__file__))  # S2V_GEN_OUT: tests/test_host_cpu.py regenerates into a scratch directory
+    here = out_dir(__file__)
     maps = {}
     for mx in (False, True):
-        body, M = gen(mx)
-        maps[mx] = M
-        with open(os.path.join(here, f"gemm_g4f_body_{'mx' if mx else 'a3'}.inc"), "w") as f:
-            for ln in body:
-                f.write('"' + ln + '\\n\\t"\n')
+        body, maps[mx] = gen(mx)
+        write_inc(os.path.join(here, f"gemm_g4f_body_{'mx' if mx else 'a3'}.inc"), body)
     with open(os.path.join(here, "gemm_g4f_regs.h"), "w") as f:
         f.write("// generated by gen_gemm_g4f.py: register constraints and LDS maps of gemm_g4f\n#pragma once\n")
         for mx, tag in ((False, "A3"), (True, "MX")):
             M = maps[mx]
             f.write(f"#define G4F_{tag}_LDS_BYTES {M.LDS}\n#define G4F_{tag}_A_STRIDE {M.A_STRIDE}\n#define G4F_{tag}_W_BASE {M.W_BASE}\n#define G4F_{tag}_W_STRIDE {M.W_STRIDE}\n#define G4F_{tag}_S_BASE {M.S_BASE}\n")
         for k in range(8):
-            f.write(f'#define G4F_ACC{k} "{{a[{32 * k}:{32 * k + 31}]}}"\n')
-        f.write(f'#define G4F_VADDR "{{v[{VADDR}:{VADDR + 15}]}}"\n#define G4F_VOFF "{{v[{VOFF}:{VOFF + 15}]}}"\n#define G4F_VMX "{{v[{V_SH}:{V_SH + 3}]}}"\n')
-        f.write(f'#define G4F_PTR "{{s[{S_A}:{S_A + 3}]}}"\n#define G4F_SIN "{{s[{S_M0W}:{S_M0W + 1}]}}"\n#define G4F_SSC "{{s[{S_SC}:{S_SC + 1}]}}"\n#define G4F_SSM0 "{{s[{S_SM0}:{S_SM0 + 1}]}}"\n')
+            f.write(define_regs(f"G4F_ACC{k}", "a", 32 * k, 32))
+        f.write(define_regs("G4F_VADDR", "v", VADDR, 16) + define_regs("G4F_VOFF", "v", VOFF, 16) + define_regs("G4F_VMX", "v", V_SH, 4))
+        f.write(define_regs("G4F_PTR", "s", S_A, 4) + define_regs("G4F_SIN", "s", S_M0W, 2) + define_regs("G4F_SSC", "s", S_SC, 2) + define_regs("G4F_SSM0", "s", S_SM0, 2))
         clob = [f"v{r}" for r in range(0, 128)] + [f"v{r}" for r in range(ABASE, V_SH)] + [f"v{r}" for r in range(V_SB, V_UNIT + 1)] + [f"s{S_ANEXT}", f"s{S_ADMA}", f"s{S_AM0}"]
-        f.write("#define G4F_CLOBBERS " + ", ".join(f'"{c}"' for c in clob) + ', "vcc", "scc", "m0", "memory"\n')
+        f.write(define_clobbers("G4F_CLOBBERS", clob))
 
 
 if __name__ == "__main__":

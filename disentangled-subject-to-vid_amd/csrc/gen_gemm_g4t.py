@@ -19,9 +19,11 @@ Structure of one tile iteration (register map below):
   5. the K loop of tile i; its first TK + 1 K-tiles are unrolled and carry the TRICKLE of tile i-1 behind their MFMAs (TPS issue slots
      per MFMA): per 32-row x 64-column unit [GELU in place on E], 8 ds_write_b64 into the wave's 4-KiB patch (rows of 128 B, 16-byte
      chunks XOR-swizzled by row & 7), 4 ds_read_b128 row-major, 4 full-line global_store_dwordx4.  LDS ops of a wave complete in order
-     and the loop already waits lgkmcnt(0) at every step; stores are only issued in steps 3 / 0 / 1 so that the loop's own vmcnt(0) of
-     step 3 (for the LDS-DMA) never waits for a young store;
-  6. the generic loop and the three tail K-tiles of gen_gemm_g4.py, unchanged.
+     and the loop already waits lgkmcnt(0) at every step; stores are only issued in steps 1 and 2, behind the K-tile's W pieces, and
+     the loop's wait of step 3 is vmcnt(number of those stores): it never waits for a young store (STORE_STEPS below);
+  6. the generic loop and the three tail K-tiles.
+The K loop is the two-stage one gemm_g4 had in round 3 ([A | W] x 64 KiB: W pieces of K-tile t+1 in step 0, vmcnt + barrier at step 3, A
+pieces of K-tile t+2 behind it): the patches and the tile records take the LDS that gemm_g4's third A stage uses.
 The LAST tile of a workgroup leaves its accumulators to the C++ epilogue (gemm_epi.h), as gemm_g4 does for every tile.
 Arithmetic is that of gemm_epi.h instruction for instruction (y = acc + bias, one v_cvt_pk_bf16_f32; GELU = x * rcp(1 + exp2(x *
 fma(x * x, k1, k0))) on the rounded value): results are bit-identical to gemm_g4 (tests/test_gpu_gemm_schedules.py).
@@ -52,19 +54,19 @@ scratch (GELU k1 during the trickle); s[64:71] the record.
 import os
 import sys
 
+from asmgen import ablations, ar, define_clobbers, define_regs, emitter, frag_read, lds_dma, m0_piece, out_dir, ptr_advance, vr, write_inc
+
 EPI = {"bias": 0, "gelu": 1, "qknorm": 4}
 # Stores and the loop's vmcnt: vmcnt counts loads, LDS-DMA and stores in issue order (gfx9: one counter, in-order), and a store is only
-# counted down when L2 has acknowledged it -- measured: with stores anywhere in the K-tile and the loop's vmcnt(0) of step 3, the 128 KiB
-# of C stores of a tile cost 0.12 ms of a 2.17-ms FF1 launch (tools/g4t_ablate.sh nostore).  So stores go out in steps 1-2 only, BEHIND
-# the K-tile's W pieces (step 0), and the wait of step 3 is vmcnt(number of those stores): every LDS-DMA piece has landed, the young
-# stores stay in flight and have a whole further K-tile to complete (the next wait covers them).
-STORE_STEPS = tuple(int(x) for x in os.environ.get("G4T_STORE_STEPS", "1,2").split(","))
-COUNTED = os.environ.get("G4T_COUNTED", "1") == "1"
-SPREAD = int(os.environ.get("G4T_SPREAD", "1"))
-TPS = float(os.environ.get("G4T_TPS", "3"))   # trickle issue slots per MFMA (a transcendental counts two, SALU a half)
-ABLATE = set(filter(None, os.environ.get("G4T_ABLATE", "").split(",")))
-TPS_QK = float(os.environ.get("G4T_TPS_QK", "3"))   # the same for the q/k-norm trickle
-QK_DIST = int(os.environ.get("G4T_QK_DIST", "64"))  # MFMAs between the request of a row's rotary values and their first use (below: the trickle idles)
+# counted down when L2 has acknowledged it.  So stores go out in steps 1-2 only, BEHIND the K-tile's W pieces (step 0), and the wait of
+# step 3 is vmcnt(number of those stores): every LDS-DMA piece has landed, the young stores stay in flight and have a whole further
+# K-tile to complete (the next wait covers them).  Rejected: stores anywhere in the K-tile under a vmcnt(0) of step 3 -- the 128 KiB of C
+# stores of a tile cost 0.12 ms of a 2.17-ms FF1 launch (tools/g4t_ablate.sh nostore, profiles/r04_gemm_g4t_ablate.txt).
+STORE_STEPS = (1, 2)
+TPS = 3.0      # trickle issue slots per MFMA (a transcendental counts two, SALU a half)
+TPS_QK = 3.0   # the same for the q/k-norm trickle
+QK_DIST = 64   # MFMAs between the request of a row's rotary values and their first use (below: the trickle idles)
+ABLATE = ablations("G4T_ABLATE")  # timing experiments of tools/g4t_ablate.sh (results are wrong): nogelu, nostore, nodrain, notrickle, qk_noload, qk_nocompute
 
 FRAG, VADDR, VOFF = 0, 64, 80
 V_ST, V_DSW, V_DSR, V_BOFF, E0, R0, G0, V_TAB, V_K0 = 96, 97, 98, 99, 100, 228, 244, 254, 255
@@ -77,17 +79,9 @@ S_PB, S_PC, S_LDC8, S_HAVE, S_ST, S_MASK, S_WCOFF, S_WBOFF, S_BIAS, S_C, S_CB, S
 # s[64:71], idle during a K loop.  v99 IN carries (wm * 128 + (lane >> 3)) << 8 above the bias offset.
 S_CS, S_TOK, S_TEXT, S_INVTOK, S_EPS, S_PREV7, S_CUR7, S_CB0, S_SM = 72, 74, 75, 76, 77, 78, 79, 80, 64
 QK_CONST_BYTES, QK_LN_OFF = 64 + 512, 64
-A_STRIDE, W_BASE = 65536, 32768
+A_STRIDE, W_BASE, W_STRIDE = 65536, 32768, 65536
 PATCH_BASE, PATCH_WAVE, TABLE_BASE, TABLE_BYTES = 131072, 4096, 131072 + 16384, 2048
 GELU_K0, GELU_K1 = 0xc0135761, 0xbdd2d3e7   # -log2(e) * 2 sqrt(2 / pi) and that times 0.044715 (common.h gelu_tanh_fast), as hipcc encodes them
-
-
-def vr(b, n=1):
-    return f"v{b}" if n == 1 else f"v[{b}:{b + n - 1}]"
-
-
-def ar(b, n):
-    return f"a[{b}:{b + n - 1}]"
 
 
 def wf(buf, i):
@@ -100,6 +94,11 @@ def af(buf, j):
 
 def vaddr(is_w, g, s):
     return VADDR + (8 if is_w else 0) + 4 * g + s
+
+
+def frag(buf, n, g, s):
+    """fragment n (0-3 W, 4-7 A) of step s of the K-tile in stage g -> buffer buf"""
+    return frag_read(wf(buf, n) if n < 4 else af(buf, n - 4), vaddr(n < 4, g, s), n)
 
 
 def ereg(i, j, rq, h):
@@ -123,8 +122,8 @@ class Trickle:
       ("", 0, "dist", tag, n)             passes once n MFMAs have been emitted since group `tag` left (the wait above then finds the
                                           data there: a waiting wave issues no MFMA either)"""
 
-    def __init__(self, prog):
-        self.prog, self.pos, self.syncs, self.mark = prog, 0, 0, -1
+    def __init__(self, prog, tps):
+        self.prog, self.tps, self.pos, self.syncs, self.mark = prog, tps, 0, 0, -1
         self.young_stores = 0   # stores issued since the last LDS-DMA piece: the loop's vmcnt wait may leave exactly these in flight
         self.vmops, self.vm_done, self.vm_at = 0, 0, {}
         self.mfmas, self.mfma_at = 0, {}
@@ -281,10 +280,9 @@ def trickle_program(epi):
             if item[2] == "store":
                 groups.append(cur)
                 cur = []
-        if cur:
-            groups[-1] += cur
-        if not work or SPREAD == 0:
+        if not work or not groups:  # (no store to space: the nostore ablation)
             return work + st
+        groups[-1] += cur
         out, n = [], len(work)
         cuts = [n * g // len(groups) for g in range(len(groups))]
         for idx, item in enumerate(work):
@@ -511,12 +509,13 @@ def qk_program():
 
 # ------------------------------------------------------------------------------------------------------------------ the K loop
 def ktile(emit, g, first=False, dma_w=True, dma_a=True, last=False, trick=None):
+    """K-tile t (stage g = t & 1) of the two-stage loop: W pieces of K-tile t+1 -> stage g^1 in step 0, s_waitcnt + barrier at step 3, then
+    A pieces of K-tile t+2 -> stage g; every step's first 8 MFMA slots carry the fragment reads of the next step.  trick: the previous
+    tile's epilogue, pulled TPS issue slots at a time behind each MFMA."""
     for s in range(4):
         cur, nxt = s & 1, (s & 1) ^ 1
         if s == 3 and not last:
-            young = trick.young_stores if (trick and COUNTED) else 0
-            emit(f"s_waitcnt vmcnt({young}) lgkmcnt(0)")
-            emit("s_barrier")
+            emit(f"s_waitcnt vmcnt({trick.young_stores if trick else 0}) lgkmcnt(0)", "s_barrier")
             if trick:
                 trick.vm_done = trick.vmops - trick.young_stores   # everything but the young stores has landed
                 trick.young_stores = 0
@@ -527,39 +526,24 @@ def ktile(emit, g, first=False, dma_w=True, dma_a=True, last=False, trick=None):
         for k in range(16):
             i, j = k >> 2, k & 3
             acc = ar(64 * i + 16 * j, 16)
-            c = "0" if (first and s == 0) else acc
-            emit(f"v_mfma_f32_32x32x16_bf16 {acc}, {vr(wf(cur, i), 4)}, {vr(af(cur, j), 4)}, {c}")
+            emit(f"v_mfma_f32_32x32x16_bf16 {acc}, {vr(wf(cur, i), 4)}, {vr(af(cur, j), 4)}, {'0' if (first and s == 0) else acc}")
             if trick:
                 trick.mfmas += 1
             if k < 8 and not (last and s == 3):
-                gs, ss = (g, s + 1) if s < 3 else (g ^ 1, 0)
-                if k < 4:
-                    emit(f"ds_read_b128 {vr(wf(nxt, k), 4)}, {vr(vaddr(True, gs, ss))} offset:{k * 4096}")
-                else:
-                    emit(f"ds_read_b128 {vr(af(nxt, k - 4), 4)}, {vr(vaddr(False, gs, ss))} offset:{(k - 4) * 4096}")
+                emit(frag(nxt, k, g, s + 1) if s < 3 else frag(nxt, k, g ^ 1, 0))
             p = k >> 1
             if s == 0 and dma_w:
-                if k & 1 == 0:
-                    emit(f"s_add_u32 m0, s{S_M0W}, {(g ^ 1) * 65536 + 32768 + p * 4096}")
-                else:
-                    emit(f"global_load_lds_dwordx4 {vr(VOFF + 8 + p)}, s[{S_W}:{S_W + 1}]")
-                    if trick:
-                        trick.vmops += 1
+                emit(m0_piece(S_M0W, (g ^ 1) * W_STRIDE + W_BASE + p * 4096) if k & 1 == 0 else lds_dma(VOFF + 8 + p, S_W))
             if s == 3 and dma_a:
-                if k & 1 == 0:
-                    emit(f"s_add_u32 m0, s{S_M0W}, {g * A_STRIDE + p * 4096}")
-                else:
-                    emit(f"global_load_lds_dwordx4 {vr(VOFF + p)}, s[{S_A}:{S_A + 1}]")
-                    if trick:
-                        trick.vmops += 1
+                emit(m0_piece(S_M0W, g * A_STRIDE + p * 4096) if k & 1 == 0 else lds_dma(VOFF + p, S_A))
+            if trick and k & 1 and ((s == 0 and dma_w) or (s == 3 and dma_a)):
+                trick.vmops += 1    # the LDS-DMA piece just emitted: vmcnt counts it with the trickle's loads and stores
             if trick and not trick.done():
-                trick.pull(emit, s, trick.tps if hasattr(trick, 'tps') else TPS)
+                trick.pull(emit, s, trick.tps)
         if s == 0 and dma_w:
-            emit(f"s_add_u32 s{S_W}, s{S_W}, 128")
-            emit(f"s_addc_u32 s{S_W + 1}, s{S_W + 1}, 0")
+            emit(*ptr_advance(S_W))
         if s == 3 and dma_a:
-            emit(f"s_add_u32 s{S_A}, s{S_A}, 128")
-            emit(f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0")
+            emit(*ptr_advance(S_A))
 
 
 def drain(emit):
@@ -585,19 +569,11 @@ def drain(emit):
 
 def frag_reads(emit):
     for n in range(8):
-        if n < 4:
-            emit(f"ds_read_b128 {vr(wf(0, n), 4)}, {vr(vaddr(True, 0, 0))} offset:{n * 4096}")
-        else:
-            emit(f"ds_read_b128 {vr(af(0, n - 4), 4)}, {vr(vaddr(False, 0, 0))} offset:{(n - 4) * 4096}")
+        emit(frag(0, n, 0, 0))
 
 
 def gen(epi):
-    L = []
-
-    def emit(ln):
-        if ln:
-            L.append(ln)
-
+    L, emit = emitter()
     emit(f"; ---- gemm_g4t<{epi}>: persistent tile walk with trickled epilogue (generated by gen_gemm_g4t.py; do not edit)")
     emit(f"s_mov_b32 s{S_HAVE}, 0")
     emit(f"s_mov_b32 s{S_MASK}, 0xffff0000")
@@ -645,23 +621,13 @@ def gen(epi):
     # 3. barrier + prologue DMA
     emit("s_barrier")
     for p in range(8):
-        emit(f"s_add_u32 m0, s{S_M0W}, {p * 4096}")
-        emit("s_nop 0")
-        emit(f"global_load_lds_dwordx4 {vr(VOFF + p)}, s[{S_A}:{S_A + 1}]")
+        emit(m0_piece(S_M0W, p * 4096), "s_nop 0", lds_dma(VOFF + p, S_A))
     for p in range(8):
-        emit(f"s_add_u32 m0, s{S_M0W}, {W_BASE + p * 4096}")
-        emit("s_nop 0")
-        emit(f"global_load_lds_dwordx4 {vr(VOFF + 8 + p)}, s[{S_W}:{S_W + 1}]")
-    emit(f"s_add_u32 s{S_A}, s{S_A}, 128")
-    emit(f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0")
-    emit(f"s_add_u32 s{S_W}, s{S_W}, 128")
-    emit(f"s_addc_u32 s{S_W + 1}, s{S_W + 1}, 0")
+        emit(m0_piece(S_M0W, W_BASE + p * 4096), "s_nop 0", lds_dma(VOFF + 8 + p, S_W))
+    emit(*ptr_advance(S_A), *ptr_advance(S_W))
     for p in range(8):
-        emit(f"s_add_u32 m0, s{S_M0W}, {A_STRIDE + p * 4096}")
-        emit("s_nop 0")
-        emit(f"global_load_lds_dwordx4 {vr(VOFF + p)}, s[{S_A}:{S_A + 1}]")
-    emit(f"s_add_u32 s{S_A}, s{S_A}, 128")
-    emit(f"s_addc_u32 s{S_A + 1}, s{S_A + 1}, 0")
+        emit(m0_piece(S_M0W, A_STRIDE + p * 4096), "s_nop 0", lds_dma(VOFF + p, S_A))
+    emit(*ptr_advance(S_A))
     emit(f"s_cmp_eq_u32 s{S_HAVE}, 0")
     emit("s_cbranch_scc1 L_t_first_%=")
     # 4. drain under the DMA latency
@@ -673,8 +639,7 @@ def gen(epi):
     frag_reads(emit)
     # 5. K-tiles 0 .. TK with the trickle
     def unrolled(prog, tps):
-        trick = Trickle(prog if "notrickle" not in ABLATE else [])
-        trick.tps = tps
+        trick = Trickle(prog if "notrickle" not in ABLATE else [], tps)
         ktile(emit, 0, first=True, trick=trick)
         tk = 0
         while not trick.done() or tk % 2:
@@ -723,30 +688,28 @@ def gen(epi):
 
 
 def main():
-    here = os.environ.get("S2V_GEN_OUT") or os.path.dirname(os.path.abspath(__file__))  # S2V_GEN_OUT: tests/test_host_cpu.py regenerates into a scratch directory
+    here = out_dir(__file__)
     tks = {}
     for epi in EPI:
-        body, tk = gen(epi)
-        tks[epi] = tk
-        with open(os.path.join(here, f"gemm_g4t_body_{epi}.inc"), "w") as f:
-            for ln in body:
-                f.write('"' + ln + '\\n\\t"\n')
+        body, tks[epi] = gen(epi)
+        write_inc(os.path.join(here, f"gemm_g4t_body_{epi}.inc"), body)
     vclob = [f"v{r}" for r in range(0, 64)] + [f"v{r}" for r in range(E0, 256) if r != V_TAB]
     sclob = [f"s{r}" for r in (S_CNT, S_HAVE, S_ST, S_ST + 1, S_MASK, S_C, S_C + 1, S_CB, S_CB + 1, S_TMP)] + [f"s{S_REC + k}" for k in range(8)] + [f"s{S_PB + k}" for k in range(4)]
     sclob_qk = [f"s{S_CS + k}" for k in range(8)]
     with open(os.path.join(here, "gemm_g4t_regs.h"), "w") as f:
         f.write("// generated by gen_gemm_g4t.py: register constraints, LDS map and unroll depth of gemm_g4t\n#pragma once\n")
         f.write(f"#define G4T_LDS_BYTES {TABLE_BASE + TABLE_BYTES}\n#define G4T_PATCH_BASE {PATCH_BASE}\n#define G4T_PATCH_WAVE {PATCH_WAVE}\n#define G4T_TABLE_BASE {TABLE_BASE}\n#define G4T_TABLE_RECORDS {TABLE_BYTES // 32}\n")
-        f.write(f"#define G4T_A_STRIDE {A_STRIDE}\n#define G4T_W_BASE {W_BASE}\n#define G4T_W_STRIDE 65536\n")
+        f.write(f"#define G4T_A_STRIDE {A_STRIDE}\n#define G4T_W_BASE {W_BASE}\n#define G4T_W_STRIDE {W_STRIDE}\n")
         for epi, tk in tks.items():
             f.write(f"#define G4T_TK_{epi.upper()} {tk}  // K-tiles (after K-tile 0) that carry the trickle: nT >= TK + 4\n")
         for k in range(8):
-            f.write(f'#define G4T_ACC{k} "{{a[{32 * k}:{32 * k + 31}]}}"\n')
-        f.write(f'#define G4T_VADDR "{{v[{VADDR}:{VADDR + 15}]}}"\n#define G4T_VOFF "{{v[{VOFF}:{VOFF + 15}]}}"\n#define G4T_VLANE "{{v[{V_ST}:{V_BOFF}]}}"\n#define G4T_VTAB "{{v{V_TAB}}}"\n')
-        f.write(f'#define G4T_SIN0 "{{s{S_M0W}}}"\n#define G4T_SIN1 "{{s[{S_CNT0}:{S_TILES}]}}"\n#define G4T_SIN2 "{{s{S_LDC8}}}"\n#define G4T_SIN3 "{{s[{S_WCOFF}:{S_WBOFF}]}}"\n#define G4T_SIN4 "{{s[{S_BIAS}:{S_BIAS + 1}]}}"\n#define G4T_PTR "{{s[{S_A}:{S_A + 3}]}}"\n')
-        f.write("#define G4T_CLOBBERS " + ", ".join(f'"{c}"' for c in vclob + sclob) + ', "vcc", "scc", "m0", "memory"\n')
-        f.write(f'#define G4T_QK_CB "{{s{S_CB0}}}"\n#define G4T_QK_CONST_BASE {TABLE_BASE + TABLE_BYTES}\n#define G4T_QK_CONST_BYTES {QK_CONST_BYTES}\n#define G4T_QK_LN_OFF {QK_LN_OFF}\n')
-        f.write("#define G4T_QK_CLOBBERS " + ", ".join(f'"{c}"' for c in sclob_qk) + "\n")
+            f.write(define_regs(f"G4T_ACC{k}", "a", 32 * k, 32))
+        f.write(define_regs("G4T_VADDR", "v", VADDR, 16) + define_regs("G4T_VOFF", "v", VOFF, 16) + define_regs("G4T_VLANE", "v", V_ST, V_BOFF - V_ST + 1) + define_regs("G4T_VTAB", "v", V_TAB))
+        f.write(define_regs("G4T_SIN0", "s", S_M0W) + define_regs("G4T_SIN1", "s", S_CNT0, 2) + define_regs("G4T_SIN2", "s", S_LDC8) + define_regs("G4T_SIN3", "s", S_WCOFF, 2)
+                + define_regs("G4T_SIN4", "s", S_BIAS, 2) + define_regs("G4T_PTR", "s", S_A, 4))
+        f.write(define_clobbers("G4T_CLOBBERS", vclob + sclob))
+        f.write(define_regs("G4T_QK_CB", "s", S_CB0) + f"#define G4T_QK_CONST_BASE {TABLE_BASE + TABLE_BYTES}\n#define G4T_QK_CONST_BYTES {QK_CONST_BYTES}\n#define G4T_QK_LN_OFF {QK_LN_OFF}\n")
+        f.write(define_clobbers("G4T_QK_CLOBBERS", sclob_qk, ()))
     if "-v" in sys.argv:
         for epi in EPI:
             print(epi, "TK", tks[epi], "trickle instructions", len(trickle_program(epi)))

@@ -302,3 +302,42 @@ def test_generator_reproduces_the_committed_outputs(gen, tmp_path):
     assert sorted(os.listdir(tmp_path)) == sorted(outs)
     for o in outs:
         assert open(os.path.join(tmp_path, o), "rb").read() == open(os.path.join(b.CSRC, o), "rb").read(), f"{o} differs from what {gen} writes"
+
+
+def _drain_block(lines):
+    """gemm_g4t: the drain is what stands between the first `s_waitcnt vmcnt(24)` of a body (the 24 prologue pieces are in flight; the
+    q/k-norm trickle may count to the same number later) and the `s_waitcnt vmcnt(8)` that follows it"""
+    first = next(i for i, ln in enumerate(lines) if ln.startswith('"s_waitcnt vmcnt(24)'))
+    end = next(i for i in range(first + 1, len(lines)) if lines[i].startswith('"s_waitcnt vmcnt(8)'))
+    assert end - first - 1 == 4 * (16 + 4 * (16 + 16 + 8)), "not the drain: per i, 16 bias unpacks + 4 blocks of 16 reads, 16 adds and 8 packs"
+    return set(range(first + 1, end))
+
+
+@pytest.mark.parametrize("gen,knob,gone", [("gen_gemm_g4.py", "G4_ABLATE=nodma", "global_load_lds_dwordx4"), ("gen_attn_q4.py", "Q4_ABLATE=noread", "ds_read_b128"),
+                                           ("gen_gemm_g4t.py", "G4T_ABLATE=nodrain", _drain_block)])
+def test_ablation_knob_only_deletes_lines_from_the_finished_stream(gen, knob, gone, tmp_path):
+    """the one kind of switch the generators keep (tools/*_ablate.sh, tools/stall_*.py): an ablation removes instructions from the stream
+    the product schedule emits and changes nothing else -- every body is the committed one without exactly those lines, every other
+    output (the *_regs.h, the split-K sum) is the committed file.  G4_ABLATE and Q4_ABLATE drop by opcode; the G4T_ABLATE values are
+    decided inside the trickle's program (nostore changes the loop's counted vmcnt, nogelu / notrickle the unroll depth), the one
+    that is a pure deletion is nodrain: the block that moves the previous tile's accumulators into the packed registers."""
+    import subprocess
+    import sys
+
+    b = _builder()
+    outs = dict(b.GENERATORS)[gen]
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("Q4_", "G4_", "G4T_", "G4F_"))}
+    env["S2V_GEN_OUT"] = str(tmp_path)
+    env.update([knob.split("=")])
+    subprocess.check_call([sys.executable, os.path.join(b.CSRC, gen)], env=env, stdout=subprocess.DEVNULL)
+    assert sorted(os.listdir(tmp_path)) == sorted(outs)
+    bodies = 0
+    for o in outs:
+        want = open(os.path.join(b.CSRC, o)).read().splitlines()
+        if "_body" in o:
+            drop = gone(want) if callable(gone) else {i for i, ln in enumerate(want) if ln[1:].split()[0] == gone}
+            assert drop, f"{o}: nothing to ablate"
+            want = [ln for i, ln in enumerate(want) if i not in drop]
+            bodies += 1
+        assert open(os.path.join(tmp_path, o)).read().splitlines() == want, f"{o} under {knob}"
+    assert bodies >= 1

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Timing experiments on the generated gemm_g4 K loop (G4_ABLATE: nodma / noread / nobar -- results are wrong by construction).
+# Timing experiments on the generated gemm_g4 K loop: G4_ABLATE = nodma / noread / nobar (comma-separated) drops those instructions from the
+# finished stream -- results are wrong by construction.  The generator has one schedule and no other switch.
 # One diagnostics library per experiment in tools/g4abl/<name>/:  bash tools/g4_ablate.sh build "<name>=<ENV ...>" ...   then on the GPU
 # box:  bash tools/g4_ablate.sh run
 set -u

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Timing experiments on the generated gemm_g4t body (G4T_TPS = trickle slots per MFMA; G4T_ABLATE: nogelu / nostore / nodrain / notrickle --
-# results are wrong by construction under an ablation).  One diagnostics library per experiment in tools/g4tabl/<name>/:
+# Timing experiments on the generated gemm_g4t body: G4T_ABLATE = nogelu / nostore / nodrain / notrickle / qk_noload / qk_nocompute
+# (comma-separated) -- results are wrong by construction.  The trickle's tuning values are constants of the generator.  One diagnostics library per experiment in tools/g4tabl/<name>/:
 #   bash tools/g4t_ablate.sh build "<name>=<ENV ...>" ...     then on the GPU box:   bash tools/g4t_ablate.sh run
 set -u
 PKG=disentangled-subject-to-vid_amd

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Timing experiments on the generated attn_q4 / attn_q8 bodies: ablations (Q4_ABLATE: results are wrong by construction) and placement
-# variants (Q4_ORDER, Q4_READPOS: results stay right).  One diagnostics library per experiment in tools/q4abl/<name>/ (git-ignored, travels
+# Timing experiments on the generated attn_q4 / attn_q8 bodies: Q4_ABLATE = nodma / noread / nosoft / movexp / nobar / nowait / nomfma
+# (comma-separated) drops or cheapens those instructions in the finished stream -- results are wrong by construction.  The generator has one
+# schedule and no other switch (the placement variants: HISTORY.md section 12).  One diagnostics library per experiment in tools/q4abl/<name>/ (git-ignored, travels
 # to the GPU box):   bash tools/q4_ablate.sh build "<name>=<ENV ...>" ...      then on the GPU box:   bash tools/q4_ablate.sh run
 set -u
 PKG=disentangled-subject-to-vid_amd
