@@ -13,6 +13,9 @@ TORCH_DTYPE = {DTYPE_F32: torch.float32, DTYPE_BF16: torch.bfloat16, DTYPE_F16: 
 DTYPE_OF = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}
 # ModelConfigC.reserved[0]: the kind of context s2v_create makes (include/s2v_hip.h, S2V_CTX_*)
 CTX_MODEL, CTX_ATTN_WEIGHTS, CTX_ATTN_WORKSPACE = 0, 1, 2
+# ModelConfigC.reserved[1]: lora_runtime_rank in the low 16 bits; bit 16 asks an fp8 weight_format for the 16-bit adapter branch beside its
+# e4m3 weights (include/s2v_hip.h, S2V_LORA_RANK_MASK / S2V_LORA_FP8_BRANCH)
+LORA_RANK_MASK, LORA_FP8_BRANCH = 0xFFFF, 1 << 16
 
 
 class ModelConfigC(ctypes.Structure):
@@ -81,6 +84,8 @@ _SIGS = {
     "s2v_op_attention_fp8qk": [_P, _P, _P, _I64, _P, _I32, _I32, _I32, _P],
     "s2v_op_attention_fp8qk_p16": [_P, _P, _P, _I64, _P, _I32, _I32, _I32, _P],
     "s2v_op_linear_fp8": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P],
+    "s2v_op_linear_fp8_lora": [_P, _P, _P, _P, _P, _I32, _F, _P, _I32, _I32, _I32, _I32, _P, _I64, _P],
+    "s2v_op_ff_fp8_lora": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _F, _P, _I32, _I32, _I32, _I32, _P, _I64, _P],
 }
 # replicas over RCCL behind the C ABI (csrc/rccl.hip); RCCL itself is bound at first use
 _SIGS.update({

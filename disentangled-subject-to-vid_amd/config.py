@@ -43,6 +43,11 @@ class TransformerConfig:
     # reference's unmerged PEFT model does, and S2VEngine.attach_lora / set_lora_scale / detach_lora swap, rescale and remove the adapter
     # after the weights are finalized
     lora_runtime_rank: int = 0
+    # fp8 weight formats only, with lora_runtime_rank > 0.  False (default): the fp8 engines take a LoRA only merged into the weights before
+    # the e4m3 quantisation (attach_lora refuses; W + s B A is rounded to three mantissa bits as one number, which keeps the base and loses
+    # most of a subject-sized delta).  True: a 16-bit adapter branch runs beside the e4m3 weights (include/s2v_hip.h, S2V_LORA_FP8_BRANCH) and
+    # attach_lora / set_lora_scale / detach_lora / checkpoint.swap_lora work as on a model-dtype engine
+    lora_runtime_fp8: bool = False
 
     @property
     def inner_dim(self):

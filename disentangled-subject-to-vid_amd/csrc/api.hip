@@ -32,6 +32,8 @@ struct Slot {
     int lora = 0;
     char* lora_a = nullptr;
     int64_t tail_col = 0;
+    // fp8 weight formats with lora_runtime_fp8: e4m3 rows take no 16-bit tail, so rnd(s * B) goes into an array of its own, rows lr_fp8 apart
+    char* lora_bs = nullptr;
 };
 enum { LORA_NONE = 0, LORA_BRANCH = 1, LORA_REMERGE = 2 };
 
@@ -41,6 +43,8 @@ struct LayerW {
     char *w1, *b1, *w2, *b2;
     // runtime LoRA: the A stacks of the four adapted linears, model dtype, zero without an adapter: [3 lr][D] (q | k | v), [lr][D], [lr][D], [lr][4 D]
     char *a_qkv = nullptr, *a_o = nullptr, *a_1 = nullptr, *a_2 = nullptr;
+    // runtime LoRA beside e4m3 weights (s2v_ctx::flr > 0): Bs = rnd(s * B) of the four adapted linears, model dtype, [N_pad][flr], zero without an adapter
+    char *bs_qkv = nullptr, *bs_o = nullptr, *bs_1 = nullptr, *bs_2 = nullptr;
     // weight_format 1: e4m3 copies [N_pad][K] of the four big linears + per-output-channel scales (quantised at finalize)
     char *q_qkv = nullptr, *q_o = nullptr, *q_1 = nullptr, *q_2 = nullptr;
     float *s_qkv = nullptr, *s_o = nullptr, *s_1 = nullptr, *s_2 = nullptr;
@@ -80,6 +84,11 @@ struct s2v_ctx {
     // attached every adapted GEMM runs with K' = K + R after a down-projection (lora.hip) has written T
     int lora_cap = 0;            // the rank asked for (0: mode off)
     int lr = 0;                  // lora_cap padded to what the GEMM dispatch needs (64, or 128 when D % 128 == 0); 0 with the mode off / fp8
+    // fp8 weight formats with S2V_LORA_FP8_BRANCH: the branch runs beside the e4m3 GEMM (GemmArgs::lora_bs).  flr = lora_cap padded to 64 (the
+    // down-projection's column tile; the up-projection steps by 16); the A stacks are carved with flr rows per adapter, the Bs arrays
+    // (LayerW::bs_*) [N_pad][flr], and the workspace holds T [Mpad][3 flr].  lr stays 0: nothing of the bf16 operand layout changes.
+    int flr = 0;
+    char* Tl = nullptr;          // workspace (flr): T = rnd(x . A^T) of the adapted GEMM being fed, rows 3 flr apart
     std::unordered_map<std::string, int> lora_names;   // attached: weight name -> rank
     int lora_rank = 0; float lora_scale = 0.f;          // of the last attach / rescale (s2v_lora_state)
     int64_t graph_captures = 0;
@@ -215,7 +224,11 @@ static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
     sq[1] = add_slot(c, NM("attn1.to_k.weight"), w.wqkv + D * ldq * E, D, D, ldq);
     sq[2] = add_slot(c, NM("attn1.to_v.weight"), w.wqkv + 2 * D * ldq * E, D, D, ldq);
     // block-diagonal tail of the fused QKV: part p keeps s * B_p in the tail columns [p lr, (p + 1) lr) of its own rows, zeros elsewhere
-    for (int p = 0; lr && p < 3; ++p) { sq[p]->lora = LORA_BRANCH; sq[p]->lora_a = w.a_qkv + p * lr * D * E; sq[p]->tail_col = D + p * lr; }
+    const int64_t fl = c->flr, la = lr + fl;  // fp8 branch: part p's rnd(s * B_p) sits in its own rows of the Bs array
+    for (int p = 0; la && p < 3; ++p) {
+        sq[p]->lora = LORA_BRANCH; sq[p]->lora_a = w.a_qkv + p * la * D * E; sq[p]->tail_col = D + p * lr;
+        if (fl) sq[p]->lora_bs = w.bs_qkv + p * D * fl * E;
+    }
     add_slot(c, NM("attn1.to_q.bias"), w.bqkv, 1, D, D);
     add_slot(c, NM("attn1.to_k.bias"), w.bqkv + D * E, 1, D, D);
     add_slot(c, NM("attn1.to_v.bias"), w.bqkv + 2 * D * E, 1, D, D);
@@ -224,17 +237,19 @@ static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
     add_slot(c, NM("attn1.norm_k.weight"), w.nk_w, 1, 64, 64);
     add_slot(c, NM("attn1.norm_k.bias"), w.nk_b, 1, 64, 64);
     Slot* so = add_slot(c, NM("attn1.to_out.0.weight"), w.wo, D, D, ldo);
-    if (lr) { so->lora = LORA_BRANCH; so->lora_a = w.a_o; so->tail_col = D; }
+    if (la) { so->lora = LORA_BRANCH; so->lora_a = w.a_o; so->tail_col = D; so->lora_bs = fl ? w.bs_o : nullptr; }
     add_slot(c, NM("attn1.to_out.0.bias"), w.bo, 1, D, D);
 #undef NM
 }
 
 // lora_runtime_rank (cfg.reserved[1], 0 .. 128: s2v_create) -> the padded rank the layout is carved for
 static void lora_setup(s2v_ctx* c) {
-    c->lora_cap = c->cfg.reserved[1];
-    // the fp8 weight formats keep no 16-bit operand for a branch to extend: nothing is carved, s2v_lora_attach refuses
+    c->lora_cap = c->cfg.reserved[1] & S2V_LORA_RANK_MASK;
+    // the fp8 weight formats keep no 16-bit operand for a branch to extend: without S2V_LORA_FP8_BRANCH nothing is carved and s2v_lora_attach
+    // refuses; with it the branch gets operands of its own beside the e4m3 GEMM (s2v_ctx::flr)
     const bool fp8 = c->cfg.weight_format != 0;
     c->lr = (c->lora_cap > 0 && !fp8) ? (int)rup(c->lora_cap, c->D % 128 == 0 ? 128 : 64) : 0;
+    c->flr = (c->lora_cap > 0 && fp8 && (c->cfg.reserved[1] & S2V_LORA_FP8_BRANCH)) ? (int)rup(c->lora_cap, 64) : 0;
 }
 
 // S2V_CTX_ATTN_WEIGHTS: an arena of num_layers x the attn1 weights, carved exactly as a model carves them (zero pad rows included), so that a
@@ -289,7 +304,8 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     S2V_REQUIRE(cfg->num_layers > 0 && cfg->num_heads > 0, "s2v_create: bad model size");
     S2V_REQUIRE(cfg->in_channels * 4 <= 4096 && cfg->out_channels > 0, "s2v_create: bad channel count");
     // everything that depends on the configuration alone is refused here, before anything is allocated
-    S2V_REQUIRE(cfg->reserved[1] >= 0 && cfg->reserved[1] <= 128, "s2v_create: lora_runtime_rank (reserved[1]) must be 0 .. 128");
+    S2V_REQUIRE(cfg->reserved[1] >= 0 && (cfg->reserved[1] & ~(S2V_LORA_RANK_MASK | S2V_LORA_FP8_BRANCH)) == 0 && (cfg->reserved[1] & S2V_LORA_RANK_MASK) <= 128,
+                "s2v_create: lora_runtime_rank (reserved[1]) must be 0 .. 128, optionally with the flag S2V_LORA_FP8_BRANCH");
     const int Dc = cfg->num_heads * 64;
     const bool mfma = cfg->dtype == S2V_DTYPE_BF16 && !cfg->force_simple;
     if (kind == S2V_CTX_ATTN_WEIGHTS) {
@@ -347,10 +363,11 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     // two passes: size, then carve
     int64_t off = 0;
     auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
-    struct Offs { int64_t ln1_w, ln1_b, ln2_w, ln2_b, wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, w1, b1, w2, b2, a_qkv, a_o, a_1, a_2; };
+    struct Offs { int64_t ln1_w, ln1_b, ln2_w, ln2_b, wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, w1, b1, w2, b2, a_qkv, a_o, a_1, a_2, bs_qkv, bs_o, bs_1, bs_2; };
     std::vector<Offs> lo(L);
     const int64_t Dp = rup(D, 256);  // weight rows are padded to the 256-column GEMM tile (zero rows)
     const int64_t lr = c->lr;        // runtime LoRA: the adapted weights get lr (QKV: 3 lr) zero tail columns, ld = K + R
+    const int64_t fl = c->flr, la = lr + fl;  // fp8 branch: no tail columns; A stacks of fl rows per adapter and the Bs arrays [N_pad][fl] instead
     for (int l = 0; l < L; ++l) {
         Offs& o = lo[l];
         o.ln1_w = carve(D); o.ln1_b = carve(D); o.ln2_w = carve(D); o.ln2_b = carve(D);
@@ -359,7 +376,8 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         o.wo = carve(Dp * (D + lr)); o.bo = carve(D);
         o.w1 = carve(rup(4 * D, 256) * (D + lr)); o.b1 = carve(4 * D);
         o.w2 = carve(Dp * (4 * D + lr)); o.b2 = carve(D);
-        o.a_qkv = carve(3 * lr * D); o.a_o = carve(lr * D); o.a_1 = carve(lr * D); o.a_2 = carve(lr * 4 * D);
+        o.a_qkv = carve(3 * la * D); o.a_o = carve(la * D); o.a_1 = carve(la * D); o.a_2 = carve(la * 4 * D);
+        o.bs_qkv = carve(rup(3 * D, 256) * fl); o.bs_o = carve(Dp * fl); o.bs_1 = carve(rup(4 * D, 256) * fl); o.bs_2 = carve(Dp * fl);
     }
     const int64_t o_patch_w = carve(Dp * Kp), o_patch_b = carve(D);
     const int64_t o_text_w = carve(Dp * TX), o_text_b = carve(D);
@@ -372,9 +390,9 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     const int64_t o_mod_w = carve(c->mod_rows * TE), o_mod_b = carve(c->mod_rows);
     // runtime LoRA: base copies of the weights an attach re-merges (every norm{1,2}.linear of the modulation stack, patch_embed.proj,
     // patch_embed.text_proj), filled by s2v_finalize_weights
-    c->base_mod_bytes = lr ? c->mod_rows * TE * E : 0; c->base_patch_bytes = lr ? Dp * Kp * E : 0; c->base_text_bytes = lr ? Dp * TX * E : 0;
-    const int64_t o_base_mod = carve(lr ? c->mod_rows * TE : 0), o_base_patch = carve(lr ? Dp * Kp : 0), o_base_text = carve(lr ? Dp * TX : 0);
-    const int64_t o_lora_hdr = carve(lr ? 128 : 0);
+    c->base_mod_bytes = la ? c->mod_rows * TE * E : 0; c->base_patch_bytes = la ? Dp * Kp * E : 0; c->base_text_bytes = la ? Dp * TX * E : 0;
+    const int64_t o_base_mod = carve(la ? c->mod_rows * TE : 0), o_base_patch = carve(la ? Dp * Kp : 0), o_base_text = carve(la ? Dp * TX : 0);
+    const int64_t o_lora_hdr = carve(la ? 128 : 0);
     // fp8 copies live in the same arena (one broadcast replicates everything a replica needs)
     c->fp8 = cfg->weight_format >= 1 && cfg->weight_format <= 3;
     c->fp8_qk = cfg->weight_format == 2;
@@ -406,6 +424,7 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         w.nk_w = A + o.nk_w; w.nk_b = A + o.nk_b; w.wo = A + o.wo; w.bo = A + o.bo;
         w.w1 = A + o.w1; w.b1 = A + o.b1; w.w2 = A + o.w2; w.b2 = A + o.b2;
         w.a_qkv = A + o.a_qkv; w.a_o = A + o.a_o; w.a_1 = A + o.a_1; w.a_2 = A + o.a_2;
+        if (fl) { w.bs_qkv = A + o.bs_qkv; w.bs_o = A + o.bs_o; w.bs_1 = A + o.bs_1; w.bs_2 = A + o.bs_2; }
         if (c->fp8) {
             const QOffs& q = qo[l];
             w.q_qkv = A + q.q_qkv; w.q_o = A + q.q_o; w.q_1 = A + q.q_1; w.q_2 = A + q.q_2;
@@ -421,10 +440,11 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
         add_slot(c, NM("ff.net.0.proj.bias"), w.b1, 1, 4 * D, 4 * D);
         Slot* s2 = add_slot(c, NM("ff.net.2.weight"), w.w2, D, 4 * D, 4 * D + lr);
         add_slot(c, NM("ff.net.2.bias"), w.b2, 1, D, D);
-        if (lr) { s1->lora = LORA_BRANCH; s1->lora_a = w.a_1; s1->tail_col = D; s2->lora = LORA_BRANCH; s2->lora_a = w.a_2; s2->tail_col = 4 * D; }
-        add_slot(c, NM("norm1.linear.weight"), A + o_mod_w + (int64_t)(2 * l) * MC * D * TE * E, 6 * D, TE, TE)->lora = lr ? LORA_REMERGE : LORA_NONE;
+        if (la) { s1->lora = LORA_BRANCH; s1->lora_a = w.a_1; s1->tail_col = D; s2->lora = LORA_BRANCH; s2->lora_a = w.a_2; s2->tail_col = 4 * D; }
+        if (fl) { s1->lora_bs = w.bs_1; s2->lora_bs = w.bs_2; }
+        add_slot(c, NM("norm1.linear.weight"), A + o_mod_w + (int64_t)(2 * l) * MC * D * TE * E, 6 * D, TE, TE)->lora = la ? LORA_REMERGE : LORA_NONE;
         add_slot(c, NM("norm1.linear.bias"), A + o_mod_b + (int64_t)(2 * l) * MC * D * E, 1, 6 * D, 6 * D);
-        add_slot(c, NM("norm2.linear.weight"), A + o_mod_w + (int64_t)(2 * l + 1) * MC * D * TE * E, 6 * D, TE, TE)->lora = lr ? LORA_REMERGE : LORA_NONE;
+        add_slot(c, NM("norm2.linear.weight"), A + o_mod_w + (int64_t)(2 * l + 1) * MC * D * TE * E, 6 * D, TE, TE)->lora = la ? LORA_REMERGE : LORA_NONE;
         add_slot(c, NM("norm2.linear.bias"), A + o_mod_b + (int64_t)(2 * l + 1) * MC * D * E, 1, 6 * D, 6 * D);
 #undef NM
     }
@@ -432,10 +452,10 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
     c->te1_w = A + o_te1_w; c->te1_b = A + o_te1_b; c->te2_w = A + o_te2_w; c->te2_b = A + o_te2_b;
     c->nf_w = A + o_nf_w; c->nf_b = A + o_nf_b; c->no_w = A + o_no_w; c->no_b = A + o_no_b;
     c->po_w = A + o_po_w; c->po_b = A + o_po_b; c->mod_w = A + o_mod_w; c->mod_b = A + o_mod_b;
-    if (lr) { c->base_mod = A + o_base_mod; c->base_patch = A + o_base_patch; c->base_text = A + o_base_text; c->lora_hdr = A + o_lora_hdr; }
-    add_slot(c, "patch_embed.proj.weight", c->patch_w, D, Kp, Kp)->lora = lr ? LORA_REMERGE : LORA_NONE;
+    if (la) { c->base_mod = A + o_base_mod; c->base_patch = A + o_base_patch; c->base_text = A + o_base_text; c->lora_hdr = A + o_lora_hdr; }
+    add_slot(c, "patch_embed.proj.weight", c->patch_w, D, Kp, Kp)->lora = la ? LORA_REMERGE : LORA_NONE;
     add_slot(c, "patch_embed.proj.bias", c->patch_b, 1, D, D);
-    add_slot(c, "patch_embed.text_proj.weight", c->text_w, D, TX, TX)->lora = lr ? LORA_REMERGE : LORA_NONE;
+    add_slot(c, "patch_embed.text_proj.weight", c->text_w, D, TX, TX)->lora = la ? LORA_REMERGE : LORA_NONE;
     add_slot(c, "patch_embed.text_proj.bias", c->text_b, 1, D, D);
     add_slot(c, "time_embedding.linear_1.weight", c->te1_w, TE, D, D);
     add_slot(c, "time_embedding.linear_1.bias", c->te1_b, 1, TE, TE);
@@ -578,7 +598,7 @@ extern "C" int s2v_finalize_weights(s2v_ctx* c, s2v_stream stream) {
         c->lora_tmp = nullptr;
         c->lora_tmp_bytes = 0;
     }
-    if (c->lr && c->kind == S2V_CTX_MODEL) {
+    if ((c->lr || c->flr) && c->kind == S2V_CTX_MODEL) {
         // runtime LoRA: what the re-merged weights hold now is their base (a LoRA merged before this call stays part of it)
         hipStream_t st = (hipStream_t)stream;
         S2V_CHECK_HIP(hipMemcpyAsync(c->base_mod, c->mod_w, (size_t)c->base_mod_bytes, hipMemcpyDeviceToDevice, st));
@@ -701,6 +721,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     // runtime LoRA: the rows of Xn and Hb have room for T = x . A^T behind column K (3 lr / lr columns)
     const int64_t oX = carve(c->Mpad * D * E), oXn = carve(c->Mpad * (D + 3 * c->lr) * E), oQKV = carve(c->Mpad * 3 * D * E);
     const int64_t oH = carve(c->Mpad * (4 * D + c->lr) * E);
+    const int64_t oTl = carve(c->Mpad * 3 * c->flr * E);  // fp8 branch: T has a buffer of its own (it cannot ride behind column K of an e4m3 / MX image)
     const int64_t oVT = carve((int64_t)B * (c->cfg.num_heads / c->sp) * 64 * c->ntok_pad * 2);
     const int64_t oe0 = carve(rup((int64_t)B * T + 128, 128) * D * E), oe1 = carve(rup(c->gR + 128, 128) * D * E);
     const int64_t opat = carve(BVg * Cin4 * E), otail = carve(BVp * D * E), oproj = carve(BVp * Cout4 * E);
@@ -745,6 +766,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     c->emb = w + oemb; c->noise_pred = w + onp; c->rope_cos = (float*)(w + ocos); c->rope_sin = (float*)(w + osin);
     c->pos_tab = w + opos; c->rope_pk = (float*)(w + opk); c->rope_paired = false;
     c->aq = w + oaq; c->aq_scale = (float*)(w + oaqs);
+    c->Tl = c->flr ? w + oTl : nullptr;
     c->hq = (unsigned char*)(w + ohq); c->hs = (unsigned char*)(w + ohs);
     c->q8 = (unsigned char*)(w + oq8); c->q8s = (unsigned short*)(w + oq8s); c->k8 = (unsigned char*)(w + ok8); c->k8s = (unsigned*)(w + ok8s);
     c->sk_ws = (float*)(w + osk); c->sk_cnt = (unsigned*)(w + oskc);
@@ -977,6 +999,21 @@ static int lora_down(s2v_ctx* c, char* x, int ldx, const char* A, int N, int K, 
     return launch_lora_down(a, c->dtype, (c->mfma || c->h16) && K % 64 == 0, st);
 }
 
+// runtime LoRA beside e4m3 weights (s2v_ctx::flr): T = rnd(x^ . A^T) into the context's T buffer, x^ = the operand the base GEMM sees at the
+// best precision in which it exists -- bf16 rows (mx_s null: Xn, or Hb without the MX form), or an MX image dequantised exactly (lora.hip)
+static int lora_down_fp8(s2v_ctx* c, const void* x, int ldx, const unsigned char* mx_s, const char* A, int N, int K, hipStream_t st) {
+    LoraDownArgs a{};
+    a.x = x; a.ldx = ldx; a.A = A; a.lda = K; a.out = c->Tl; a.ldo = 3 * c->flr; a.M = (int)c->M; a.N = N; a.K = K;
+    ProfScope ps(c, PK_LORA, st);
+    if (!mx_s) return launch_lora_down(a, c->dtype, true, st);
+    a.mx_s = mx_s; a.mx_rows = (int)c->Mpad;
+    return launch_lora_down_mx(a, st);
+}
+// ... and the GEMM's side of it: the branch operands of GemmArgs (seg: output columns per adapter, 0 = one adapter)
+static void lora_branch_fp8(const s2v_ctx* c, GemmArgs& g, const char* bs, int seg) {
+    g.lora_t = c->Tl; g.lora_ldt = 3 * c->flr; g.lora_bs = bs; g.lora_r = c->flr; g.lora_seg = seg;
+}
+
 // ---- attention: one QKV projection and one core for the single engine (run_attention) and the Ulysses shard (shard_front, shard_attention) ----
 // May the per-head LayerNorm + rotary embedding of q and k ride in the QKV projection's epilogue (EPI_BIAS_QKNORM), on the rounded projection
 // as the stand-alone kernel does?  The matrix-core kernels only, and rotary tables in the paired form (s2v_set_rope).  g_fused_qk is the A/B
@@ -1005,10 +1042,13 @@ static QkNormRopeArgs qk_norm_args(const s2v_ctx* c, const LayerW& w) {
 // GEMM runs with K = pX behind the down-projection; qk_epi: EPI_BIAS_QKNORM; prequant: linear_fp8
 static int qkv_proj(s2v_ctx* c, const LayerW& w, int pX, bool lora, bool qk_epi, bool prequant, hipStream_t st) {
     const int D = c->D;
-    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_qkv, 3 * c->lr, D, st));
+    const bool lora8 = lora && c->flr > 0;  // the branch beside the e4m3 GEMM: Xn holds the bf16 rows also under prequant (block_norm)
+    if (lora8) S2V_TRY(lora_down_fp8(c, c->Xn, pX, nullptr, w.a_qkv, 3 * c->flr, D, st));
+    else if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_qkv, 3 * c->lr, D, st));
     GemmArgs g{};
     g.A = c->Xn; g.lda = pX; g.W = w.wqkv; g.ldw = pX; g.bias = w.bqkv;
     g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = lora ? pX : D;
+    if (lora8) lora_branch_fp8(c, g, w.bs_qkv, D);
     if (qk_epi) set_qk_epilogue(c, w, g);
     ProfScope ps(c, PK_QKV, st);
     const int epi = qk_epi ? EPI_BIAS_QKNORM : EPI_BIAS;
@@ -1098,7 +1138,7 @@ static int block_norm(s2v_ctx* c, int l, int half, const char* mod_base /* [B][m
 #ifdef S2V_DIAG
     prequant = prequant && g_fused_q8;
 #endif
-    if (prequant) { n.q8 = c->aq; n.q8_scale = c->aq_scale; }
+    if (prequant) { n.q8 = c->aq; n.q8_scale = c->aq_scale; n.q8_keep_y = (c->flr > 0 && c->lora_on()) ? 1 : 0; }
     *prequant_out = prequant;
     ProfScope ps(c, PK_LNMOD, st);
     return launch_ln_modulate(n, c->dtype, st);
@@ -1121,7 +1161,14 @@ static GemmArgs block_gate(const s2v_ctx* c, int half, const char* mod_base, int
 // AttnProcessor seam)
 static int out_proj(s2v_ctx* c, const LayerW& w, bool lora, GemmArgs g, int epi, bool timed, hipStream_t st) {
     const int D = c->D, pX = D + 3 * c->lr;
-    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
+    const bool lora8 = lora && c->flr > 0;
+    if (lora8) {
+        if (attn_mx_out(c)) S2V_TRY(lora_down_fp8(c, c->aq, D, c->hs, w.a_o, c->flr, D, st));
+        else S2V_TRY(lora_down_fp8(c, c->Xn, pX, nullptr, w.a_o, c->flr, D, st));
+        lora_branch_fp8(c, g, w.bs_o, 0);
+    } else if (lora) {
+        S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
+    }
     g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.M = (int)c->M; g.N = D; g.K = lora ? D + c->lr : D;
     if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
     auto gemm = [&]() { return c->fp8 ? linear_fp8(c, g, epi, w.q_o, w.s_o, st) : linear(c, g, epi, st); };
@@ -1133,9 +1180,14 @@ static int out_proj(s2v_ctx* c, const LayerW& w, bool lora, GemmArgs g, int epi,
 static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st) {
     const LayerW& w = c->layers[l];
     const int D = c->D, pX = D + 3 * c->lr, pH = 4 * D + c->lr;
-    const bool lora = c->lora_on();
-    if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_1, c->lr, D, st));
+    const bool lora = c->lora_on(), lora8 = lora && c->flr > 0;
     GemmArgs f{};
+    if (lora8) {
+        S2V_TRY(lora_down_fp8(c, c->Xn, pX, nullptr, w.a_1, c->flr, D, st));
+        lora_branch_fp8(c, f, w.bs_1, 0);
+    } else if (lora) {
+        S2V_TRY(lora_down(c, c->Xn, pX, w.a_1, c->lr, D, st));
+    }
     f.A = c->Xn; f.lda = pX; f.W = w.w1; f.ldw = D + c->lr; f.bias = w.b1; f.C = c->Hb; f.ldc = pH;
     f.M = (int)c->M; f.N = 4 * D; f.K = lora ? D + c->lr : D;
     bool mx = c->fp8 && (4 * D) % 128 == 0;
@@ -1148,7 +1200,13 @@ static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st
         if (c->fp8) S2V_TRY(linear_fp8(c, f, EPI_BIAS_GELU, w.q_1, w.s_1, st, prequant));
         else S2V_TRY(linear(c, f, EPI_BIAS_GELU, st));
     }
-    if (lora) S2V_TRY(lora_down(c, c->Hb, pH, w.a_2, c->lr, 4 * D, st));
+    if (lora8) {  // FF2: the operand is the FF1 epilogue's MX image (or, without the MX form, the bf16 rows in Hb)
+        if (mx) S2V_TRY(lora_down_fp8(c, c->hq, 4 * D, c->hs, w.a_2, c->flr, 4 * D, st));
+        else S2V_TRY(lora_down_fp8(c, c->Hb, pH, nullptr, w.a_2, c->flr, 4 * D, st));
+        lora_branch_fp8(c, g, w.bs_2, 0);
+    } else if (lora) {
+        S2V_TRY(lora_down(c, c->Hb, pH, w.a_2, c->lr, 4 * D, st));
+    }
     g.A = c->Hb; g.lda = pH; g.W = w.w2; g.ldw = pH; g.bias = w.b2; g.K = lora ? pH : 4 * D;
     if (mx) { g.A = c->hq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
     ProfScope ps(c, PK_FF2, st);
@@ -1321,7 +1379,9 @@ static int lora_checks(s2v_ctx* c, const char* fn) {
     static thread_local std::string m;
     auto fail = [&](const char* why) { m = std::string(fn) + ": " + why; return s2v_fail(__FILE__, __LINE__, m.c_str(), -1); };
     if (c->lora_cap == 0) return fail("the runtime adapter mode is off (lora_runtime_rank = 0: this context merges LoRA at load time, s2v_merge_lora)");
-    if (c->cfg.weight_format != 0) return fail("fp8 weight formats have no runtime adapter branch (weight_format must be 0, the model dtype)");
+    if (c->cfg.weight_format != 0 && c->flr == 0)
+        return fail("fp8 weight formats run a runtime adapter branch only when the context was created for it (lora_runtime_fp8 / S2V_LORA_FP8_BRANCH in "
+                    "reserved[1]); without the flag weight_format must be 0, the model dtype");
     if (c->shard) return fail("a shard context (s2v_set_shard) does not support runtime adapters");
     if (c->kind == S2V_CTX_ATTN_WORKSPACE) return fail("a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
     if (!c->finalized) return fail("the weights are not finalized (before s2v_finalize_weights use s2v_merge_lora)");
@@ -1341,7 +1401,8 @@ static char* lora_base_of(s2v_ctx* c, const char* live) {
 static int lora_write(s2v_ctx* c, const char* name, Slot& s, const float* A, const float* B, int rank, float scale, bool with_a, hipStream_t st) {
     const int64_t E = c->esz;
     if (s.lora == LORA_BRANCH) {
-        if (with_a) S2V_TRY(launch_lora_pack_a(A, rank, c->lr, (int)s.cols, s.lora_a, s.cols, c->dtype, st));
+        if (with_a) S2V_TRY(launch_lora_pack_a(A, rank, c->lr + c->flr, (int)s.cols, s.lora_a, s.cols, c->dtype, st));
+        if (s.lora_bs) return launch_lora_pack_b(B, rank, c->flr, (int)s.rows, scale, s.lora_bs, c->flr, c->dtype, st);  // beside e4m3 weights
         return launch_lora_pack_b(B, rank, c->lr, (int)s.rows, scale, s.dst + s.tail_col * E, s.ld, c->dtype, st);
     }
     char* base = lora_base_of(c, s.dst);
@@ -1417,7 +1478,20 @@ extern "C" int s2v_lora_detach(s2v_ctx* c, s2v_stream stream) {
     if (!c->lora_on()) return 0;
     const int64_t D = c->D, E = c->esz, lr = c->lr, Dp = rup(D, 256);
     const bool model = c->kind == S2V_CTX_MODEL;
+    for (auto& w : c->layers) {  // fp8 branch: zero Bs arrays and A stacks
+        if (!c->flr) break;
+        const int64_t fl = c->flr;
+        S2V_CHECK_HIP(hipMemsetAsync(w.bs_qkv, 0, (size_t)(rup(3 * D, 256) * fl * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.bs_o, 0, (size_t)(Dp * fl * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.bs_1, 0, (size_t)(rup(4 * D, 256) * fl * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.bs_2, 0, (size_t)(Dp * fl * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_qkv, 0, (size_t)(3 * fl * D * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_o, 0, (size_t)(fl * D * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_1, 0, (size_t)(fl * D * E), st));
+        S2V_CHECK_HIP(hipMemsetAsync(w.a_2, 0, (size_t)(fl * 4 * D * E), st));
+    }
     for (auto& w : c->layers) {  // zero tails and A stacks: a later attach of fewer names must not meet these values
+        if (c->flr) break;
         S2V_CHECK_HIP(hipMemset2DAsync(w.wqkv + D * E, (size_t)((D + 3 * lr) * E), 0, (size_t)(3 * lr * E), (size_t)rup(3 * D, 256), st));
         S2V_CHECK_HIP(hipMemset2DAsync(w.wo + D * E, (size_t)((D + lr) * E), 0, (size_t)(lr * E), (size_t)Dp, st));
         S2V_CHECK_HIP(hipMemsetAsync(w.a_qkv, 0, (size_t)(3 * lr * D * E), st));
@@ -2038,6 +2112,104 @@ extern "C" int s2v_op_ff_fp8(const void* x, const void* w1, const void* b1, cons
     hipStreamSynchronize(st);
     hipFree(p);
     return rc;
+}
+
+// One adapted linear as the fp8 engines run it with S2V_LORA_FP8_BRANCH: s2v_op_linear_fp8's quantisation and GEMM with the adapter branch beside
+// it -- A into a stack, rnd(scale * B) into a Bs array (the attach-time kernels), T = rnd(x . A^T) from the bf16 rows of x (the down-projection
+// kernel), and T . Bs^T added to the dequantised accumulator before bias / GELU (GemmArgs::lora_bs).  Everything lives in `scratch`; asynchronous.
+extern "C" int s2v_op_linear_fp8_lora(const void* x, const void* W, const void* bias, const float* A, const float* B, int32_t rank, float scale, void* C,
+                                      int32_t M, int32_t N, int32_t K, int32_t epilogue, void* scratch, int64_t scratch_bytes, s2v_stream stream) {
+    S2V_REQUIRE(x && W && A && B && C && scratch, "s2v_op_linear_fp8_lora: null argument");
+    S2V_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU, "s2v_op_linear_fp8_lora: epilogue must be 0 or 1");
+    S2V_REQUIRE(M > 0 && N > 0 && K > 0 && M % 256 == 0 && N % 256 == 0 && K % 128 == 0, "s2v_op_linear_fp8_lora: M, N multiples of 256 and K of 128");
+    S2V_REQUIRE(rank > 0 && rank <= 128, "s2v_op_linear_fp8_lora: rank must be 1 .. 128");
+    const int64_t R = rup(rank, 64);
+    const int64_t o_q = rup((int64_t)M * K + (int64_t)N * K + 4 * ((int64_t)M + N), 256);
+    const int64_t need = o_q + 2 * R * ((int64_t)K + N + M);
+    S2V_REQUIRE(scratch_bytes >= need, "s2v_op_linear_fp8_lora: scratch too small (M*K + N*K + 4*(M+N) rounded up to 256, + 2*R*(K+N+M) bytes, R = rank rounded up to 64)");
+    hipStream_t st = (hipStream_t)stream;
+    char* aq = (char*)scratch;
+    char* wq = aq + (int64_t)M * K;
+    float* as = (float*)(wq + (int64_t)N * K);
+    float* ws = as + M;
+    char* a_st = (char*)scratch + o_q;          // A stack [R][K]
+    char* bs = a_st + 2 * R * K;                // Bs [N][R]
+    char* t = bs + 2 * R * N;                   // T [M][R]
+    S2V_TRY(launch_quant_rows_fp8(x, K, M, K, aq, as, st));
+    S2V_TRY(launch_quant_rows_fp8(W, K, N, K, wq, ws, st));
+    S2V_TRY(launch_lora_pack_a(A, rank, (int)R, K, a_st, K, S2V_BF16, st));
+    S2V_TRY(launch_lora_pack_b(B, rank, (int)R, N, scale, bs, R, S2V_BF16, st));
+    LoraDownArgs d{};
+    d.x = x; d.ldx = K; d.A = a_st; d.lda = K; d.out = t; d.ldo = (int)R; d.M = M; d.N = (int)R; d.K = K;
+    S2V_TRY(launch_lora_down(d, S2V_BF16, true, st));
+    GemmArgs g{};
+    g.A = aq; g.lda = K; g.W = wq; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K;
+    g.a_rows_padded = M; g.w_rows_padded = N; g.a_scale = as; g.w_scale = ws;
+    g.lora_t = t; g.lora_ldt = (int)R; g.lora_bs = bs; g.lora_r = (int)R; g.lora_seg = 0;
+    return launch_gemm_fp8(g, epilogue, st);
+}
+
+// s2v_op_ff_fp8 with an adapter on both linears, as the fp8 engines run a block's FeedForward with S2V_LORA_FP8_BRANCH: FF1's branch reads the
+// bf16 rows of x; FF2's reads (mx = 1) the MX image the FF1 epilogue left, dequantised exactly, or (mx = 0) the bf16 h.  `scratch` starts with
+// what a test wants to look at: the image bytes [M][F], its block scales (GemmArgs::mx_a_s: [F / 128][M] dwords, rows permuted by mx_perm_row,
+// byte b = block 4 kt + b) and, from the next multiple of 256 bytes on, FF2's T [M][R] bf16 (R = rank rounded up to 64).  Asynchronous.
+extern "C" int s2v_op_ff_fp8_lora(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, const float* A1, const float* B1,
+                                  const float* A2, const float* B2, int32_t rank, float scale, void* out, int32_t M, int32_t D, int32_t F, int32_t mx,
+                                  void* scratch, int64_t scratch_bytes, s2v_stream stream) {
+    S2V_REQUIRE(x && w1 && w2 && out && A1 && B1 && A2 && B2 && scratch, "s2v_op_ff_fp8_lora: null argument");
+    S2V_REQUIRE(M > 0 && D > 0 && F > 0 && M % 256 == 0 && D % 256 == 0 && F % 256 == 0, "s2v_op_ff_fp8_lora: M, D, F must be multiples of 256");
+    S2V_REQUIRE(rank > 0 && rank <= 128, "s2v_op_ff_fp8_lora: rank must be 1 .. 128");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t R = rup(rank, 64), m = M, dd = D, f = F;
+    int64_t off = 0;
+    auto carve = [&](int64_t bytes) { int64_t o = off; off += rup(bytes, 256); return o; };
+    off = m * f + m * f / 32;                          // image bytes + block scales, back to back
+    off = rup(off, 256);
+    const int64_t o_t2 = carve(m * R * 2), o_t1 = carve(m * R * 2);
+    const int64_t o_xq = carve(m * dd), o_w1q = carve(f * dd), o_w2q = carve(dd * f);
+    const int64_t o_xs = carve(m * 4), o_hrow = carve(m * 4), o_w1s = carve(f * 4), o_w2s = carve(dd * 4);
+    const int64_t o_hb = carve(m * f * 2);
+    const int64_t o_a1 = carve(R * dd * 2), o_bs1 = carve(f * R * 2), o_a2 = carve(R * f * 2), o_bs2 = carve(dd * R * 2);
+    S2V_REQUIRE(scratch_bytes >= off, "s2v_op_ff_fp8_lora: scratch too small (4*M*F + M*D + 2*D*F + 2*R*(2*M + 2*D + 2*F) + 8*M + 4*(D + F) + 8192 bytes suffice)");
+    char* p = (char*)scratch;
+    unsigned char* hq = (unsigned char*)p;
+    unsigned char* hsc = hq + m * f;
+    char *t2 = p + o_t2, *t1 = p + o_t1, *xq = p + o_xq, *w1q = p + o_w1q, *w2q = p + o_w2q, *hb = p + o_hb;
+    float *xs = (float*)(p + o_xs), *hs_row = (float*)(p + o_hrow), *w1s = (float*)(p + o_w1s), *w2s = (float*)(p + o_w2s);
+    char *a1 = p + o_a1, *bs1 = p + o_bs1, *a2 = p + o_a2, *bs2 = p + o_bs2;
+    S2V_TRY(launch_quant_rows_fp8(x, D, M, D, xq, xs, st));
+    S2V_TRY(launch_quant_rows_fp8(w1, D, F, D, w1q, w1s, st));
+    S2V_TRY(launch_quant_rows_fp8(w2, F, D, F, w2q, w2s, st));
+    S2V_TRY(launch_lora_pack_a(A1, rank, (int)R, D, a1, D, S2V_BF16, st));
+    S2V_TRY(launch_lora_pack_b(B1, rank, (int)R, F, scale, bs1, R, S2V_BF16, st));
+    S2V_TRY(launch_lora_pack_a(A2, rank, (int)R, F, a2, F, S2V_BF16, st));
+    S2V_TRY(launch_lora_pack_b(B2, rank, (int)R, D, scale, bs2, R, S2V_BF16, st));
+    LoraDownArgs d1{};
+    d1.x = x; d1.ldx = D; d1.A = a1; d1.lda = D; d1.out = t1; d1.ldo = (int)R; d1.M = M; d1.N = (int)R; d1.K = D;
+    S2V_TRY(launch_lora_down(d1, S2V_BF16, true, st));
+    GemmArgs g1{};
+    g1.A = xq; g1.lda = D; g1.W = w1q; g1.ldw = D; g1.bias = b1; g1.C = hb; g1.ldc = F; g1.M = M; g1.N = F; g1.K = D;
+    g1.a_rows_padded = M; g1.w_rows_padded = F; g1.a_scale = xs; g1.w_scale = w1s;
+    g1.lora_t = t1; g1.lora_ldt = (int)R; g1.lora_bs = bs1; g1.lora_r = (int)R;
+    if (mx) { g1.mx_out_q = hq; g1.mx_out_s = hsc; g1.mx_rows = M; }
+    S2V_TRY(launch_gemm_fp8(g1, EPI_BIAS_GELU, st));
+    LoraDownArgs d2{};
+    d2.A = a2; d2.lda = F; d2.out = t2; d2.ldo = (int)R; d2.M = M; d2.N = (int)R; d2.K = F;
+    GemmArgs g2{};
+    g2.A = hq; g2.lda = F; g2.W = w2q; g2.ldw = F; g2.bias = b2; g2.C = out; g2.ldc = D; g2.M = M; g2.N = D; g2.K = F;
+    g2.a_rows_padded = M; g2.w_rows_padded = D; g2.w_scale = w2s;
+    g2.lora_t = t2; g2.lora_ldt = (int)R; g2.lora_bs = bs2; g2.lora_r = (int)R;
+    if (mx) {
+        g2.mx_a_s = hsc; g2.mx_rows = M;
+        d2.x = hq; d2.ldx = F; d2.mx_s = hsc; d2.mx_rows = M;
+        S2V_TRY(launch_lora_down_mx(d2, st));
+    } else {
+        S2V_TRY(launch_quant_rows_fp8(hb, F, M, F, hq, hs_row, st));
+        g2.a_scale = hs_row;
+        d2.x = hb; d2.ldx = F;
+        S2V_TRY(launch_lora_down(d2, S2V_BF16, true, st));
+    }
+    return launch_gemm_fp8(g2, EPI_BIAS, st);
 }
 
 // Census of the attention kernel's deferred-maximum slow path since the last reset: slow = slow paths taken, total = (wave, KV tile) pairs run by

@@ -87,7 +87,7 @@ __device__ __forceinline__ void row_modulate_store(float* v, int D, int lane, co
 // arithmetic of quant_rows_fp8_k on values that never leave the registers
 template <int NR>
 __device__ __forceinline__ void row_modulate_quant_store(float* v, int D, int lane, const bf16_t* shift, const bf16_t* scale, unsigned char* q,
-                                                         float* qscale) {
+                                                         float* qscale, bf16_t* y = nullptr /* LnModArgs::q8_keep_y: the bf16 row as well */) {
     const int chunks = D / 8;
     float amax = 0.f;
 #pragma unroll
@@ -120,6 +120,7 @@ __device__ __forceinline__ void row_modulate_quant_store(float* v, int D, int la
         w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[i * 8 + 4] * inv, v[i * 8 + 5] * inv, w1, false);
         w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[i * 8 + 6] * inv, v[i * 8 + 7] * inv, w1, true);
         if (c < chunks) *(u32x2*)(q + c * 8) = u32x2{(unsigned)w0, (unsigned)w1};
+        if (y != nullptr && c < chunks) Vec16<bf16_t>::st(y + c * 8, v + i * 8);
     }
 }
 // The same three steps with the parameter vectors (LayerNorm weight / bias, modulation scale / shift) REQUESTED WITH THE ROW: as written
@@ -229,7 +230,8 @@ __global__ __launch_bounds__(256) void ln_modulate_k(const LnModArgs a) {
         if (a.q8 != nullptr) {  // fp8 engine: per-row e4m3 image instead of the bf16 store
             row_load<T, NR>((const T*)a.x + (size_t)row * a.ldx, a.D, lane, v);
             row_layernorm<T, NR>(v, a.D, lane, (const T*)a.w, (const T*)a.b, a.eps);
-            row_modulate_quant_store<NR>(v, a.D, lane, shift, scale, (unsigned char*)a.q8 + (size_t)row * a.D, a.q8_scale + row);
+            row_modulate_quant_store<NR>(v, a.D, lane, shift, scale, (unsigned char*)a.q8 + (size_t)row * a.D, a.q8_scale + row,
+                                         a.q8_keep_y ? (bf16_t*)a.y + (size_t)row * a.ldy : nullptr);
             return;
         }
     }
@@ -299,7 +301,8 @@ __global__ __launch_bounds__(256) void ln_modulate_lds_k(const LnModArgs a) {
         row_layernorm<T, NR>(v, a.D, lane, pw, pb, a.eps);
         if constexpr (std::is_same<T, bf16_t>::value) {
             if (a.q8 != nullptr) {
-                row_modulate_quant_store<NR>(v, a.D, lane, psh, psc, (unsigned char*)a.q8 + (size_t)row * a.D, a.q8_scale + row);
+                row_modulate_quant_store<NR>(v, a.D, lane, psh, psc, (unsigned char*)a.q8 + (size_t)row * a.D, a.q8_scale + row,
+                                             a.q8_keep_y ? (bf16_t*)a.y + (size_t)row * a.ldy : nullptr);
                 continue;
             }
         }

@@ -532,7 +532,8 @@ __device__ __forceinline__ i32x8v cat16(bf16x8 lo, bf16x8 hi) {
     const i32x4v a = __builtin_bit_cast(i32x4v, lo), b = __builtin_bit_cast(i32x4v, hi);
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-template <int EPI, int ABL = 0, bool FP8 = false, typename T16 = bf16_t>
+// LORA (FP8 only): the runtime adapter branch of GemmArgs::lora_bs between the K loop and the epilogue (gemm_epi.h, lora_up_wave)
+template <int EPI, int ABL = 0, bool FP8 = false, typename T16 = bf16_t, bool LORA = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_pp64(const GemmArgs a, int tiles_m, int tiles_n) {
     constexpr int ES = FP8 ? 1 : 2;         // bytes per operand element
     constexpr int BKE = 128 / ES;           // elements per 128-byte K-tile
@@ -719,7 +720,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pp64(const GemmArgs a, int t
 
     char* patch = smem + wave * 16384;
     if (epi_vec_ok(a, EPI)) {
-        epilogue_wave<EPI, 4, FP8, T16>(a, acc, m0 + wm * 128, n0 + wn * 64, patch, lane);
+        if constexpr (LORA) {
+            lora_up_wave<4>(a, acc, m0 + wm * 128, n0 + wn * 64, lane);
+            epilogue_wave<EPI, 4, false, T16>(a, acc, m0 + wm * 128, n0 + wn * 64, patch, lane);
+        } else {
+            epilogue_wave<EPI, 4, FP8, T16>(a, acc, m0 + wm * 128, n0 + wn * 64, patch, lane);
+        }
         if ((ABL >= 4)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             tacc[3] = now() - te0;  // epilogue incl. store drain (replaces the vmcnt slot)
@@ -1242,11 +1248,11 @@ static constexpr int g_gemm_impl = 9;  // 9: gemm_g4 where it qualifies, gemm_bf
 static constexpr int g_gemm_g4t = 1;
 #endif
 
-template <int EPI>
+template <int EPI, bool LORA = false>
 static int launch_fp8_t(const GemmArgs& a, hipStream_t st) {
     const int tiles_m = (a.M + WBM - 1) / WBM, tiles_n = (a.N + WBN - 1) / WBN;
-    S2V_TRY(ensure_lds_attr((const void*)gemm_bf16_pp64<EPI, 0, true>, 131072 + 2048));  // + two stages of A block scales (MX)
-    hipLaunchKernelGGL((gemm_bf16_pp64<EPI, 0, true>), dim3(tiles_m * tiles_n), dim3(512), 131072 + 2048, st, a, tiles_m, tiles_n);
+    S2V_TRY(ensure_lds_attr((const void*)gemm_bf16_pp64<EPI, 0, true, bf16_t, LORA>, 131072 + 2048));  // + two stages of A block scales (MX)
+    hipLaunchKernelGGL((gemm_bf16_pp64<EPI, 0, true, bf16_t, LORA>), dim3(tiles_m * tiles_n), dim3(512), 131072 + 2048, st, a, tiles_m, tiles_n);
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1343,9 +1349,15 @@ int launch_gemm_fp8(const GemmArgs& a, int epi, hipStream_t st) {
     S2V_REQUIRE(a.a_rows_padded >= ((a.M + WBM - 1) / WBM) * WBM && a.w_rows_padded >= ((a.N + WBN - 1) / WBN) * WBN,
                 "gemm_fp8: operands must be padded to whole 256-row tiles");
     S2V_REQUIRE(epi_vec_ok(a, epi), "gemm_fp8: output rows must be 16-byte aligned and N a multiple of 8");
+    S2V_REQUIRE(!a.lora_bs || (a.lora_t && a.lora_r > 0 && a.lora_r % 16 == 0 && a.lora_r <= 128 && a.lora_ldt % 8 == 0 && a.lora_seg % 64 == 0 &&
+                               a.lora_ldt >= (a.lora_seg > 0 ? (a.N + a.lora_seg - 1) / a.lora_seg : 1) * a.lora_r),
+                "gemm_fp8: the adapter branch needs T and Bs with a rank of 16 .. 128 in steps of 16, 16-byte aligned rows of T and whole 64-column segments");
     if (gemm_kernel(a, epi, 0) == GEMM_G4F) return launch_gemm_g4f(a, epi, st);  // (the fp8 choice counts no CUs)
     return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_QKNORM>(epi, "gemm_fp8: bad epilogue",
-                                                                                   [&](auto e) { return launch_fp8_t<decltype(e)::value>(a, st); });
+                                                                                   [&](auto e) {
+                                                                                       if (a.lora_bs) return launch_fp8_t<decltype(e)::value, true>(a, st);
+                                                                                       return launch_fp8_t<decltype(e)::value>(a, st);
+                                                                                   });
 }
 
 int launch_gemm_bf16(const GemmArgs& a0, int epi, hipStream_t st) {

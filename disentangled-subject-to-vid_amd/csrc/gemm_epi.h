@@ -321,6 +321,43 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& a, const f32x16 (&
     load_bias64(a, nw, lane >> 5, bvec);
     epilogue_wave_b<EPI, MB, SC, 4, T16>(a, acc, mw, nw, patch, lane, bvec);
 }
+// Runtime LoRA beside e4m3 weights (GemmArgs::lora_bs): the wave's 64(n) x MB*32(m) accumulator tile of an fp8 GEMM is dequantised IN PLACE --
+// acc * (a_scale[row] * w_scale[column]), the product the SC epilogue forms -- and the adapter's up-projection T . Bs^T is accumulated onto it
+// in the same registers on v_mfma_f32_32x32x16_bf16 (the 32 x 32 C layout is shared by the fp8 and the bf16 instruction): one fp32
+// accumulator per output, rounded once by the epilogue, which then runs with SC = false.  Fragments come straight from global memory in
+// MFMA layout (16 bytes per lane: row fr, K elements 8 hi .. 8 hi + 7 of the 16-step); Bs and a tile's rows of T are L2-resident.
+// Rows of T and Bs exist up to the padded tiles, so no address is clamped.  At most lora_r / 16 = 8 steps of 2 * MB MFMAs.
+template <int MB>
+__device__ __forceinline__ void lora_up_wave(const GemmArgs& a, f32x16 (&acc)[2][MB], int mw, int nw, int lane) {
+    const int fr = lane & 31, hi = lane >> 5;
+    float sa[MB];
+#pragma unroll
+    for (int j = 0; j < MB; ++j) sa[j] = a.a_scale ? a.a_scale[min(mw + j * 32 + fr, a.M - 1)] : 1.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+            const f32x4 sw = *(const f32x4*)(a.w_scale + nw + i * 32 + 8 * rq + 4 * hi);
+#pragma unroll
+            for (int j = 0; j < MB; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[i][j][rq * 4 + e] = acc[i][j][rq * 4 + e] * (sa[j] * sw[e]);
+        }
+    const int seg = a.lora_seg > 0 ? min(nw, a.N - 1) / a.lora_seg : 0;  // (a wave tile past N in the padded last column tile stays inside T)
+    const bf16_t* tp = (const bf16_t*)a.lora_t + (size_t)(mw + fr) * a.lora_ldt + seg * a.lora_r + 8 * hi;
+    const bf16_t* bp = (const bf16_t*)a.lora_bs + (size_t)(nw + fr) * a.lora_r + 8 * hi;
+    for (int k = 0; k < a.lora_r; k += 16) {
+        bf16x8 bf[2], tf[MB];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) bf[i] = *(const bf16x8*)(bp + (size_t)i * 32 * a.lora_r + k);
+#pragma unroll
+        for (int j = 0; j < MB; ++j) tf[j] = *(const bf16x8*)(tp + (size_t)j * 32 * a.lora_ldt + k);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < MB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[i], tf[j], acc[i][j], 0, 0, 0);  // D[i = n][j = m]
+    }
+}
 template <int EPI>
 __device__ __forceinline__ void epilogue_wave64(const GemmArgs& a, const f32x16 (&acc)[2][2], int mw, int nw, char* patch,
                                                 int lane) {

@@ -15,7 +15,9 @@
 typedef __attribute__((ext_vector_type(32))) float f32x32;
 typedef __attribute__((ext_vector_type(16))) unsigned int u32x16;
 
-template <int EPI, bool MX>
+// LORA: the runtime adapter branch (GemmArgs::lora_bs) -- after the K loop each 64-column half is dequantised in place and takes T . Bs^T on the
+// bf16 MFMA (gemm_epi.h, lora_up_wave) before the epilogue, which then applies no scales.  LORA = false is the kernel without the branch.
+template <int EPI, bool MX, bool LORA = false>
 __global__ __launch_bounds__(256, 1) void gemm_g4f(const GemmArgs a, int tiles_m, int tiles_n) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int A_STRIDE = G4F_A3_A_STRIDE, W_BASE = G4F_A3_W_BASE, W_STRIDE = G4F_A3_W_STRIDE;
@@ -105,18 +107,23 @@ __global__ __launch_bounds__(256, 1) void gemm_g4f(const GemmArgs a, int tiles_m
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = AC[2 * (2 * h + i) + (j >> 1)][(j & 1) * 16 + e];
-        epilogue_wave<EPI, 4, true>(a, acc, m0 + wm * 128, n0 + wn * 128 + h * 64, patch, lane);
+        if constexpr (LORA) {
+            lora_up_wave<4>(a, acc, m0 + wm * 128, n0 + wn * 128 + h * 64, lane);
+            epilogue_wave<EPI, 4, false>(a, acc, m0 + wm * 128, n0 + wn * 128 + h * 64, patch, lane);
+        } else {
+            epilogue_wave<EPI, 4, true>(a, acc, m0 + wm * 128, n0 + wn * 128 + h * 64, patch, lane);
+        }
     }
     clk_stamp(a.clk, gridDim.x >> 1, 1);
 }
 
-template <int EPI, bool MX>
+template <int EPI, bool MX, bool LORA = false>
 static int launch_g4f_t(const GemmArgs& a_in, hipStream_t st) {
     GemmArgs a = a_in;
     const int tiles_m = (a.M + 255) / 256, tiles_n = (a.N + 255) / 256;
     if (a.gm <= 0) a.gm = (tiles_n <= 16 && tiles_m >= 32 && a.K >= 16384) ? 1 : 4;  // as gemm_g4, K in bytes
     const int lds = MX ? G4F_MX_LDS_BYTES : G4F_A3_LDS_BYTES;
-    const void* fn = (const void*)gemm_g4f<EPI, MX>;
+    const void* fn = (const void*)gemm_g4f<EPI, MX, LORA>;
     S2V_TRY(ensure_lds_attr(fn, lds));
     void* args[] = {(void*)&a, (void*)&tiles_m, (void*)&tiles_n};
     S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(tiles_m * tiles_n), dim3(256), args, lds, st));
@@ -138,8 +145,8 @@ int launch_gemm_g4f(const GemmArgs& a, int epi, hipStream_t st) {
     return epi_dispatch<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_QKNORM>(epi, "gemm_g4f: bad epilogue", [&](auto e) {
         constexpr int E = decltype(e)::value;
         if constexpr (E == EPI_BIAS || E == EPI_BIAS_GATE_RES) {  // the epilogues with an MX form
-            if (a.mx_a_s) return launch_g4f_t<E, true>(a, st);
+            if (a.mx_a_s) return a.lora_bs ? launch_g4f_t<E, true, true>(a, st) : launch_g4f_t<E, true>(a, st);
         }
-        return launch_g4f_t<E, false>(a, st);
+        return a.lora_bs ? launch_g4f_t<E, false, true>(a, st) : launch_g4f_t<E, false>(a, st);
     });
 }

@@ -79,6 +79,13 @@ struct GemmArgs {
     unsigned char* mx_out_q; unsigned char* mx_out_s;
     const unsigned char* mx_a_s;
     int mx_rows;
+    // fp8 GEMMs only, runtime LoRA (lora_runtime_fp8): the adapter's up-projection rides behind the K loop as 16-bit matrix work,
+    //   C = epilogue(a_scale[m] * w_scale[n] * acc + T . Bs^T + bias),   T = rnd(x . A^T) [M_pad][lora_ldt],   Bs = rnd(s * B) [N_pad][lora_r],
+    // both bf16, lora_r a multiple of 16 (pad columns zero), rows present up to the padded 256-row tiles.  Output columns
+    // [j * lora_seg, (j + 1) * lora_seg) read the columns [j * lora_r, (j + 1) * lora_r) of T (the fused QKV: q | k | v have an adapter
+    // each; lora_seg = 0: one adapter, lora_seg % 64 == 0 otherwise).  lora_bs null: no branch -- the instantiation without it runs.
+    const void* lora_t; int lora_ldt;
+    const void* lora_bs; int lora_r, lora_seg;
 };
 // fp8 x fp8 -> bf16 GEMM on v_mfma_scale_f32_32x32x64_f8f6f4 (unit block scales; the per-row scales above in the epilogue): the
 // 256 x 256 ping-pong schedule of gemm_bf16_pp64 on K-tiles of 128 bytes.  Plain mode only (no conv), K % 128 == 0, N_pad % 256 == 0.
@@ -146,9 +153,15 @@ struct LoraDownArgs {
     const void* A; int lda;
     void* out; int ldo;
     int M, N, K;
+    // launch_lora_down_mx only: the block scales of x (GemmArgs::mx_a_s: K-tile major dwords, rows permuted) and the rows of that array
+    const unsigned char* mx_s; int mx_rows;
 };
 // mfma: the 16-bit model dtypes on v_mfma_f32_32x32x16_{bf16,f16} (N % 64 == 0, N <= 384, K % 64 == 0); otherwise the generic kernel
 int launch_lora_down(const LoraDownArgs& a, int dtype, bool mfma, hipStream_t st);
+// the same product with x given as an MX e4m3 image (bytes [M][K], ldx in bytes, block scales a.mx_s): every element is dequantised
+// exactly -- e4m3(byte) * 2^(scale - 127) is a bf16 value -- and multiplied on v_mfma_f32_32x32x16_bf16; A and out are bf16.
+// N % 64 == 0, N <= 128, K % 128 == 0
+int launch_lora_down_mx(const LoraDownArgs& a, hipStream_t st);
 // attach time: A [rank][K] fp32 -> `rows` rows of the stack (rows past rank zero); scale * B [N][rank] fp32 -> `cols` tail columns (past rank zero)
 int launch_lora_pack_a(const float* A, int rank, int rows, int K, void* dst, int64_t ldd, int dtype, hipStream_t st);
 int launch_lora_pack_b(const float* B, int rank, int cols, int N, float scale, void* dst, int64_t ldd, int dtype, hipStream_t st);
@@ -243,6 +256,7 @@ struct LnModArgs {
     // quant_rows_fp8_k would quantise its bf16 image -- e4m3 bytes [row][D] and scale[row] = amax / 448 -- for the projection that
     // consumes it (one read + one write pass over the activations less per LayerNorm)
     void* q8; float* q8_scale;
+    int q8_keep_y;  // with q8: the bf16 rows are stored to y as well (the fp8 engine's runtime LoRA reads them for its down-projection)
 };
 int launch_ln_modulate(const LnModArgs& a, int dtype, hipStream_t st);
 

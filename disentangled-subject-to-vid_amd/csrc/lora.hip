@@ -157,6 +157,120 @@ int launch_lora_down(const LoraDownArgs& a, int dtype, bool mfma, hipStream_t st
     return 0;
 }
 
+// ---- down-projection from an MX e4m3 image (the fp8 engine: attention output -> out-projection, GELU(FF1) -> FF2) ------------------------------
+// The same tiling and the same v_mfma_f32_32x32x16_bf16 as lora_down_mfma_k, but x arrives as one byte per element plus one E8M0 scale per
+// (row, 32 elements) in the K-tile-major layout of GemmArgs::mx_a_s -- dword (kt, mx_perm_row(m)), byte b = block 4 kt + b -- so the kernel reads
+// half the bytes of the bf16 one.  A thread owns 16 consecutive elements of a row per K chunk (half an MX block: one scale byte), converts them
+// with v_cvt_pk_f32_fp8, multiplies by 2^(scale - 127) and packs bf16 pairs: e4m3 has four significant bits, so every product is a bf16 value and
+// the operand the MFMA sees is the image dequantised exactly.  N <= 128 (one adapter's padded rank): two 32-column tiles per wave at most.
+template <int NTW>
+__global__ __launch_bounds__(LD_THREADS, 2) void lora_down_mx_k(const LoraDownArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* tX = smem;                       // [128][64] of x, bf16
+    char* tA = smem + LD_BM * LD_BK * 2;   // [N][64] of the A stack
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave & 3, wn = wave >> 2;
+    const int fr = lane & 31, hi = lane >> 5;
+    const int m0 = blockIdx.x * LD_BM;
+    const int ntw = a.N >> 6;
+    const unsigned char* X = (const unsigned char*)a.x;
+    const char* A = (const char*)a.A;
+    // x: 128 rows x 4 pieces of 16 bytes per K chunk, one per thread
+    const int xrow = tid >> 2, xq = tid & 3;
+    const bool xok = m0 + xrow < a.M;
+    const unsigned char* xp = X + (int64_t)(m0 + xrow) * a.ldx + xq * 16;
+    const unsigned char* sp = a.mx_s + mx_perm_row(m0 + xrow) * 4;
+
+    u32x4 rx, ra[NTW];
+    unsigned rs = 0;
+    auto fetch = [&](int k0) {
+        rx = u32x4{0u, 0u, 0u, 0u};
+        rs = 127;
+        if (xok) {
+            rx = *(const u32x4*)(xp + k0);
+            rs = sp[(int64_t)(k0 >> 7) * a.mx_rows * 4 + (((k0 & 127) + xq * 16) >> 5)];
+        }
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {
+            const int p = i * LD_THREADS + tid, row = p >> 3, ch = p & 7;
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (row < a.N) v = *(const u32x4*)(A + 2 * ((int64_t)row * a.lda + k0 + ch * 8));
+            ra[i] = v;
+        }
+    };
+    auto commit = [&]() {
+        const float sc = __uint_as_float(rs ? rs << 23 : 0x00400000u);   // 2^(rs - 127)
+        u32x4 o[2];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)rx[w], false), up = __builtin_amdgcn_cvt_pk_f32_fp8((int)rx[w], true);
+            o[w >> 1][(w & 1) * 2] = pack2bf(lo[0] * sc, lo[1] * sc);
+            o[w >> 1][(w & 1) * 2 + 1] = pack2bf(up[0] * sc, up[1] * sc);
+        }
+        *(u32x4*)(tX + lora_swz(xrow, xq * 2)) = o[0];
+        *(u32x4*)(tX + lora_swz(xrow, xq * 2 + 1)) = o[1];
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {
+            const int p = i * LD_THREADS + tid;
+            if ((p >> 3) < a.N) *(u32x4*)(tA + lora_swz(p >> 3, p & 7)) = ra[i];
+        }
+    };
+
+    f32x16 acc[NTW];
+#pragma unroll
+    for (int i = 0; i < NTW; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+
+    const int nt = a.K / LD_BK;
+    fetch(0);
+    for (int t = 0; t < nt; ++t) {
+        commit();
+        __syncthreads();
+        if (t + 1 < nt) fetch((t + 1) * LD_BK);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const bf16x8 xf = *(const bf16x8*)(tX + lora_swz(wm * 32 + fr, kk * 2 + hi));
+#pragma unroll
+            for (int i = 0; i < NTW; ++i) {
+                if (i < ntw) {
+                    const bf16x8 af = *(const bf16x8*)(tA + lora_swz((wn * ntw + i) * 32 + fr, kk * 2 + hi));
+                    acc[i] = lora_mfma<bf16_t>(af, xf, acc[i]);   // D[i = column of T][j = row of x]
+                }
+            }
+        }
+        __syncthreads();
+    }
+    const int m = m0 + wm * 32 + fr;
+    if (m >= a.M) return;
+    bf16_t* out = (bf16_t*)a.out + (int64_t)m * a.ldo;
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) {
+        if (i < ntw) {
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const int n = (wn * ntw + i) * 32 + 8 * rq + 4 * hi;
+                u32x2 w;
+                w[0] = pack2bf(acc[i][rq * 4 + 0], acc[i][rq * 4 + 1]);
+                w[1] = pack2bf(acc[i][rq * 4 + 2], acc[i][rq * 4 + 3]);
+                *(u32x2*)(out + n) = w;
+            }
+        }
+    }
+}
+
+int launch_lora_down_mx(const LoraDownArgs& a, hipStream_t st) {
+    S2V_REQUIRE(a.x && a.A && a.out && a.mx_s && a.M > 0 && a.N > 0 && a.K > 0, "lora_down_mx: bad argument");
+    S2V_REQUIRE(a.N % 64 == 0 && a.N <= 128 && a.K % 128 == 0 && a.ldx % 16 == 0 && a.lda % 8 == 0 && a.ldo % 4 == 0,
+                "lora_down_mx: N must be 64 or 128, K a multiple of 128, rows 16-byte aligned");
+    S2V_REQUIRE(a.mx_rows % 128 == 0 && a.mx_rows >= (a.M + 127) / 128 * 128, "lora_down_mx: the block scales must cover M padded to 128 rows");
+    const int grid = (a.M + LD_BM - 1) / LD_BM, lds = LD_LDS(a.N);
+    S2V_TRY(ensure_lds_attr((const void*)lora_down_mx_k<2>, LD_LDS(128)));
+    hipLaunchKernelGGL((lora_down_mx_k<2>), dim3(grid), dim3(LD_THREADS), lds, st, a);
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- attach time --------------------------------------------------------------------------------------------------------------------
 // dst[j][k] = rnd(A[j][k]) for j < rank, 0 for rank <= j < rows: the adapter's A [rank][K] (fp32) into its rows of the layer's A stack
 template <typename T>

@@ -46,7 +46,11 @@ class S2VEngine:
             raise _lib.S2VError(f"unknown attn_p_format {cfg.attn_p_format!r} ('bf16', 'f16' or 'auto')")
         c.attn_p_format = 0 if cfg.attn_p_format == "bf16" else 1
         c.reserved[0] = kind
+        # reserved[1]: the rank in the low 16 bits, S2V_LORA_FP8_BRANCH above it (include/s2v_hip.h): cfg.lora_runtime_fp8 asks an fp8
+        # weight_format for the 16-bit adapter branch beside its e4m3 weights
         c.reserved[1] = int(getattr(cfg, "lora_runtime_rank", 0) or 0)
+        if c.reserved[1] > 0 and c.weight_format != 0 and getattr(cfg, "lora_runtime_fp8", False):
+            c.reserved[1] |= _lib.LORA_FP8_BRANCH
         self.kind = kind
         # runtime adapter mode: the attached adapter's fp32 device copies {name: (A2, B2)} (set_lora_scale re-reads them), and the last
         # adapter attached with its current scale, kept across detach_lora so that enable_lora can put it back (lora_kept_bytes counts it)
@@ -131,8 +135,9 @@ class S2VEngine:
         """the library's own refusals, taken before anything is changed (attach_lora detaches first): the state stays as it was"""
         if self.cfg.lora_runtime_rank <= 0:
             raise _lib.S2VError(f"{what}: the runtime adapter mode is off (lora_runtime_rank = 0: this engine merges LoRA at load time)")
-        if self.cfg.weight_format is not None:
-            raise _lib.S2VError(f"{what}: fp8 weight formats have no runtime adapter branch (weight_format {self.cfg.weight_format!r})")
+        if self.cfg.weight_format is not None and not getattr(self.cfg, "lora_runtime_fp8", False):
+            raise _lib.S2VError(f"{what}: fp8 weight formats have no runtime adapter branch (weight_format {self.cfg.weight_format!r}) unless the "
+                                f"engine is created with TransformerConfig.lora_runtime_fp8 = True")
         if self.shard is not None:
             raise _lib.S2VError(f"{what}: a shard engine (set_shard) does not support runtime adapters")
         if rank > self.cfg.lora_runtime_rank:

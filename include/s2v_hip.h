@@ -81,8 +81,12 @@ typedef struct s2v_model_config {
                                * reserved[1] = lora_runtime_rank: 0 = LoRA exists only as the load-time merge (s2v_merge_lora; the default: it costs
                                *     nothing per step); r in 1 .. 128 = the runtime adapter mode with room for adapters of rank <= r per layer
                                *     (s2v_lora_attach below): the arena and the workspace are carved larger, the arithmetic without an adapter is
-                               *     unchanged */
+                               *     unchanged.  The rank sits in the low 16 bits (S2V_LORA_RANK_MASK); bit 16, S2V_LORA_FP8_BRANCH, asks an fp8
+                               *     weight_format (1 / 2 / 3) for the 16-bit adapter branch beside its e4m3 weights (below); without the flag an fp8
+                               *     context carves nothing and s2v_lora_attach refuses it; weight_format 0 ignores the flag */
 } s2v_model_config;
+/* flag bits of reserved[1] above the rank */
+enum { S2V_LORA_RANK_MASK = 0xffff, S2V_LORA_FP8_BRANCH = 1 << 16 };
 
 /* reserved[0] of s2v_model_config.  The AttnProcessor seam installed on every Attention module of a model
  * keeps each module's attention weights in an S2V_CTX_ATTN_WEIGHTS context and runs all of them with ONE S2V_CTX_ATTN_WORKSPACE
@@ -139,15 +143,26 @@ S2V_API int s2v_weight_slot(s2v_ctx* ctx, const char* name, int64_t* offset_byte
  * arithmetic, so their bytes equal a merged context's (lora_adaln_scope 1 included).  Tails, A stacks and base copies live inside the weight
  * arena: s2v_weight_arena, s2v_bcast_weights and the replica path carry an attached adapter; s2v_weight_slot keeps returning the base
  * [rows, cols] with the larger ld; s2v_device_bytes counts all of it.
+ * fp8 weight formats (weight_format 1 / 2 / 3) created with S2V_LORA_FP8_BRANCH run the same adapters beside e4m3 weights.  Merged before the
+ * quantisation, W + s B A is rounded to three mantissa bits as one number and most of a subject-sized delta is lost; here the base stays the
+ * quantised W and the branch stays 16-bit:
+ *     y  = epilogue((q_a . q_w^T) * a_scale[m] * w_scale[n] + T . Bs^T + b)      one fp32 accumulator, one rounding at the epilogue
+ *     T  = rnd16(x^ . A^T), x^ = the operand the base GEMM sees at the best precision in which it exists: the bf16 LayerNorm-modulate rows for
+ *          the QKV and FF1 projections, the attention's / the FF1 epilogue's MX e4m3 image dequantised exactly (e4m3(byte) * 2^(scale - 127))
+ *          for the out-projection and FF2
+ * The fp8 GEMM kernels dequantise their accumulator tile in place after the K loop and accumulate T . Bs^T onto it on the bf16 matrix
+ * instruction, before bias, GELU, gate + residual, q/k-norm + RoPE and FF1's MX output quantisation.  e4m3 rows cannot take 16-bit tail columns:
+ * the arena holds a Bs array [N_pad][R] per adapted linear and the A stacks (R = the rank padded to 64), the workspace a T buffer [M_pad][3 R].
+ * Attach / rescale / detach, the re-merged targets, hipGraph handling, replicas and the refusals are the ones described here; shards stay refused.
  * s2v_lora_attach: the arguments of s2v_merge_lora (fp32 device pointers, the reference's weight name, conv A as [r, C * 2 * 2]), legal AFTER
  *   s2v_finalize_weights; replaces what is attached under `name`.  Refused, with a message that says which: the mode off, an fp8
- *   weight_format, a shard context, a rank over lora_runtime_rank, a name that is unknown or no LoRA target of the context (an
+ *   weight_format created without S2V_LORA_FP8_BRANCH, a shard context, a rank over lora_runtime_rank, a name that is unknown or no LoRA target of the context (an
  *   S2V_CTX_ATTN_WEIGHTS context takes the four attn1 names).  hipGraph: an attach or a detach changes K' and drops the captured step (as
  *   s2v_set_rope does; it is re-captured at its next use).
  * s2v_lora_set_scale: the same A and B under another scale; the result equals, bit for bit, attaching them at that scale.  It rewrites
  *   values only (the tail of a branch weight, a re-merged weight) and KEEPS a captured step.  The caller keeps A and B (the library keeps no
  *   fp32 copy).
- * s2v_lora_detach: the base model; zeroes every tail and A stack, restores the re-merged weights.
+ * s2v_lora_detach: the base model; zeroes every tail (fp8 branch: every Bs array) and A stack, restores the re-merged weights.
  * Conditioning: patch_embed.proj and patch_embed.text_proj made the hoisted conditioning, so after an attach, rescale or detach that
  *   reaches them the forward entry points ask for s2v_set_conditioning again (a captured step reads the buffers it rewrites and stays valid).
  * Replicas: the attached state (names attached, rank, scale) is kept inside the arena too; s2v_mark_weights_loaded on a context whose arena was
@@ -509,6 +524,20 @@ S2V_API int s2v_op_linear_fp8(const void* A, const void* W, const void* bias, vo
  * reference arithmetic exists for fp8 (parity unpinned): tests/test_gpu_fp8.py states the contract against a torch emulation. */
 S2V_API int s2v_op_ff_fp8(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* out, int32_t M,
                           int32_t D, int32_t F, int32_t mx, s2v_stream stream);
+/* One adapted linear as an fp8 context created with S2V_LORA_FP8_BRANCH computes it: s2v_op_linear_fp8 (same operands, quantisation, shapes and
+ * epilogues) with the adapter branch beside it, C = epilogue(scale_a[m] * scale_w[n] * acc + T . rnd(scale * B)^T + bias), T = rnd(x . A^T) from
+ * the bf16 rows of x.  A [rank, K], B [N, rank] fp32, rank <= 128.  scratch >= M*K + N*K + 4*(M+N) rounded up to 256, + 2*R*(K+N+M) bytes with
+ * R = rank rounded up to 64.  scale = 0 or B = 0 returns the bytes of s2v_op_linear_fp8.  tests/test_gpu_lora_runtime_fp8.py. */
+S2V_API int s2v_op_linear_fp8_lora(const void* x, const void* W, const void* bias, const float* A, const float* B, int32_t rank, float scale, void* C,
+                                   int32_t M, int32_t N, int32_t K, int32_t epilogue, void* scratch, int64_t scratch_bytes, s2v_stream stream);
+/* s2v_op_ff_fp8 with an adapter (A1 [rank, D], B1 [F, rank]; A2 [rank, F], B2 [D, rank]; fp32, one scale) on both linears.  FF1's branch reads
+ * the bf16 rows of x; FF2's reads, mx = 1, the MX image of GELU(h) dequantised exactly, or, mx = 0, the bf16 h.  The caller's scratch
+ * (4*M*F + M*D + 2*D*F + 2*R*(2*M + 2*D + 2*F) + 8*M + 4*(D + F) + 8192 bytes suffice) starts with the image bytes [M][F], then its block scales
+ * [F / 128][M] dwords (dword (kt, m) at row (m & ~127) | (m & 31) << 2 | (m >> 5) & 3, byte b = the E8M0 scale of columns 128 kt + 32 b ..),
+ * then, at the next multiple of 256 bytes, FF2's T [M][R] bf16 (R = rank rounded up to 64, pad columns zero).  Asynchronous. */
+S2V_API int s2v_op_ff_fp8_lora(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, const float* A1, const float* B1,
+                               const float* A2, const float* B2, int32_t rank, float scale, void* out, int32_t M, int32_t D, int32_t F, int32_t mx,
+                               void* scratch, int64_t scratch_bytes, s2v_stream stream);
 /* out[b][r] = silu(emb[b]) . W[r] + bias[r] for the stacked AdaLN modulation linears of a step (every
  * CogVideoXLayerNormZero.linear and norm_out.linear on silu(temb), normalization.py / cogvideox_transformer_3d.py:122-186);
  * emb [B, temb_dim], W [rows, temb_dim], out [B, rows], B <= 4; impl 0 = the product dispatch, 1 = one wave per row */

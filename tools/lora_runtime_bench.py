@@ -11,7 +11,13 @@ One process, one GPU, the headline geometry (CogVideoX-5B, 49 x 480 x 720, bf16,
   * the wall time of attach_lora on the loaded runtime engine (reading a checkpoint directory is not timed here).
 Acceptance (printed, not enforced here): overhead <= 2 x floor, down-projection >= 0.5 of its byte floor.
 
-    python tools/lora_runtime_bench.py [--layers 42] [--rank 128] [--rounds 5] [--steps 3] [--out profiles/...txt]
+--weight-format fp8 | fp8-qk | fp8-auto: A = the fp8 engine with the adapter merged BEFORE the e4m3 quantisation, B = the fp8 engine created with
+lora_runtime_fp8 and the same adapter attached as a 16-bit branch beside the e4m3 weights.  The floor then is: the bytes each down-projection
+must read (bf16 rows for QKV / FF1, one byte per element for the out-projection and FF2 from their MX images) and write (T), the bf16 rows
+LayerNorm-modulate now stores beside its e4m3 image, plus 2 R / K of each base GEMM's time -- R / K extra matrix work at the bf16 MFMA rate,
+half the fp8 rate the base runs at.  No acceptance line is printed for fp8: the ratio measured / derived is reported.
+
+    python tools/lora_runtime_bench.py [--layers 42] [--rank 128] [--rounds 5] [--steps 3] [--weight-format fp8] [--geometry 49x720x1280] [--out profiles/...txt]
 """
 import argparse
 import ctypes
@@ -52,10 +58,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--weight-format", default=None, choices=["fp8", "fp8-qk", "fp8-auto"])
+    ap.add_argument("--geometry", default="49x480x720", help="frames x height x width in pixels (49x480x720, 49x720x1280)")
     a = ap.parse_args()
     s2v = importlib.import_module("disentangled-subject-to-vid_amd")
     dev, dt = "cuda:0", torch.bfloat16
-    F, H, W, T = 13, 60, 90, 226
+    gf, gh, gw = (int(v) for v in a.geometry.split("x"))
+    F, H, W, T = (gf - 1) // 4 + 1, gh // 8, gw // 8, 226
+    fp8 = a.weight_format is not None
     lines = []
 
     def say(s):
@@ -66,6 +76,8 @@ def main():
         cfg = s2v.cogvideox_5b()
         cfg.num_layers = a.layers
         cfg.lora_runtime_rank = rank
+        cfg.weight_format = a.weight_format
+        cfg.lora_runtime_fp8 = fp8 and rank > 0
         return cfg
 
     lora = s2v.weights.synthetic_lora(mk(0), rank=a.rank, seed=99, device=dev, std=0.02)
@@ -101,7 +113,7 @@ def main():
         eng.prepare_tables(H * 8, W * 8)
         eng.set_conditioning(text, ref)
         engines[name] = (eng, lat0.clone())
-    say(f"# runtime LoRA at the headline geometry: 5B x {a.layers} layers, 49 x 480 x 720, bf16, B = 2, rank {a.rank}, hipGraph; one process, one GPU")
+    say(f"# runtime LoRA: 5B x {a.layers} layers, {a.geometry.replace('x', ' x ')}, {a.weight_format or 'bf16'}, B = 2, rank {a.rank}, hipGraph; one process, one GPU")
     for name in engines:
         ar, ws = engines[name][0].device_bytes()
         say(f"device_bytes {name}: arena {ar / 2**30:.3f} GiB workspace {ws / 2**30:.3f} GiB")
@@ -146,23 +158,36 @@ def main():
 
     # the floor
     D, E, M = 3072, 2, 2 * (T + (F + 1) * (H // 2) * (W // 2))
-    R = (a.rank + 127) // 128 * 128
+    R = (a.rank + 63) // 64 * 64 if fp8 else (a.rank + 127) // 128 * 128
     pa = prof["merged"][0]
-    extra = {"qkv": 3 * R / D, "out_proj": R / D, "ff1": R / D, "ff2": R / (4 * D)}
+    if fp8:  # R / K extra matrix work at the bf16 MFMA rate = 2 R / K of the fp8 GEMM's time; every QKV column meets ONE adapter
+        extra = {"qkv": 2 * R / D, "out_proj": 2 * R / D, "ff1": 2 * R / D, "ff2": 2 * R / (4 * D)}
+    else:
+        extra = {"qkv": 3 * R / D, "out_proj": R / D, "ff1": R / D, "ff2": R / (4 * D)}
     mfma_floor = sum(pa[CLASSES.index(k)] * f for k, f in extra.items())
     ln_ms, ln_n = pa[5], prof["merged"][1][5]
-    ln_gbs = 2 * M * D * E * ln_n / (ln_ms * 1e-3) / 1e9
-    down_bytes = a.layers * ((3 * M * D + M * 4 * D) * E + M * 6 * R * E)
+    ln_gbs = (M * D * E + M * D) * ln_n / (ln_ms * 1e-3) / 1e9 if fp8 else 2 * M * D * E * ln_n / (ln_ms * 1e-3) / 1e9
+    if fp8:  # x: bf16 rows twice (QKV, FF1), bytes + block scales for the out-projection (K = D) and FF2 (K = 4 D); T written four times;
+        # and the bf16 rows LayerNorm-modulate stores beside its e4m3 image, twice per block
+        down_bytes = a.layers * (2 * M * D * E + (M * D + M * 4 * D) * 33 // 32 + M * 6 * R * E + 2 * M * D * E)
+    else:
+        down_bytes = a.layers * ((3 * M * D + M * 4 * D) * E + M * 6 * R * E)
     bytes_floor = down_bytes / (ln_gbs * 1e9) * 1e3
     floor = mfma_floor + bytes_floor
     say(f"floor: extra MFMA work {mfma_floor:.2f} ms (" + ", ".join(f"{k} +{100 * f:.1f} %" for k, f in extra.items()) + f") + down-projection bytes "
         f"{down_bytes / 1e9:.2f} GB at LayerNorm-modulate's {ln_gbs:.0f} GB/s = {bytes_floor:.2f} ms -> {floor:.2f} ms per step")
-    say(f"acceptance 1: overhead {over:.1f} ms <= 2 x floor {2 * floor:.1f} ms: {'MET' if over <= 2 * floor else 'MISSED'}")
+    if fp8:
+        say(f"measured / derived: overhead {over:.1f} ms against the floor {floor:.2f} ms = {over / floor:.2f} x")
+    else:
+        say(f"acceptance 1: overhead {over:.1f} ms <= 2 x floor {2 * floor:.1f} ms: {'MET' if over <= 2 * floor else 'MISSED'}")
     dn_ms = prof["runtime"][0][9]
+    if fp8:
+        down_bytes -= a.layers * 2 * M * D * E   # the kernels' own bytes: without LayerNorm-modulate's extra store
     dn_gbs = down_bytes / (dn_ms * 1e-3) / 1e9 if dn_ms > 0 else 0.0
     say(f"down-projection kernel: {dn_ms:.2f} ms per step over {prof['runtime'][1][9]} launches = {dn_gbs:.0f} GB/s = {dn_gbs / PEAK_HBM_GBS:.3f} of the "
         f"{PEAK_HBM_GBS:.0f} GB/s HBM peak (LayerNorm-modulate: {ln_gbs / PEAK_HBM_GBS:.3f})")
-    say(f"acceptance 2: down-projection rate against its byte floor >= 0.5: {'MET' if dn_gbs / PEAK_HBM_GBS >= 0.5 else 'MISSED'}")
+    if not fp8:
+        say(f"acceptance 2: down-projection rate against its byte floor >= 0.5: {'MET' if dn_gbs / PEAK_HBM_GBS >= 0.5 else 'MISSED'}")
     pb = prof["runtime"][0]
     say("where the overhead goes (eager ms, runtime - merged): " + ", ".join(f"{c} {pb[i] - pa[i]:+.2f}" for i, c in enumerate(CLASSES) if prof["runtime"][1][i]))
     if a.out:
