@@ -37,17 +37,37 @@ struct Slot {
 };
 enum { LORA_NONE = 0, LORA_BRANCH = 1, LORA_REMERGE = 2 };
 
+// the four big linears of a block.  What any site needs to know about one of them -- its shape, how many adapters share it, its state-dict
+// names -- is lin_shape()'s; what a layer stores for it is a LinW
+enum { LIN_QKV, LIN_OUT, LIN_FF1, LIN_FF2, LIN_NUM };
+struct LinShape {
+    int64_t N, K;          // output rows, depth
+    int parts;             // adapters side by side in the output columns (q | k | v of the fused QKV), N / parts rows each
+    const char* stem[3];   // state-dict name of each part, inside "transformer_blocks.<l>."
+    int64_t n_pad() const { return rup(N, 256); }                    // weight rows are padded to the 256-column GEMM tile (zero rows)
+    int64_t pitch(int64_t lr) const { return K + parts * lr; }       // runtime LoRA: every part gets lr zero tail columns, ld = K + R
+    int lora_seg() const { return parts > 1 ? (int)(N / parts) : 0; }  // GemmArgs::lora_seg: output columns per adapter, 0 = one adapter
+};
+static LinShape lin_shape(int which, int64_t D) {
+    switch (which) {
+    case LIN_QKV: return {3 * D, D, 3, {"attn1.to_q", "attn1.to_k", "attn1.to_v"}};
+    case LIN_OUT: return {D, D, 1, {"attn1.to_out.0"}};
+    case LIN_FF1: return {4 * D, D, 1, {"ff.net.0.proj"}};
+    default: return {D, 4 * D, 1, {"ff.net.2"}};
+    }
+}
+struct LinW {
+    char *w = nullptr, *b = nullptr;   // weight [n_pad][pitch] and bias [N], model dtype
+    char* a = nullptr;                 // runtime LoRA: the A stack, model dtype, zero without an adapter: [parts (lr + flr)][K]
+    char* bs = nullptr;                // runtime LoRA beside e4m3 weights (s2v_ctx::flr > 0): Bs = rnd(s * B), model dtype, [n_pad][flr], zero without an adapter
+    char* q = nullptr;                 // weight_format 1: the e4m3 copy [n_pad][K] + per-output-channel scales (quantised at finalize)
+    float* s = nullptr;
+};
+
 struct LayerW {
     char *ln1_w, *ln1_b, *ln2_w, *ln2_b;
-    char *wqkv, *bqkv, *nq_w, *nq_b, *nk_w, *nk_b, *wo, *bo;
-    char *w1, *b1, *w2, *b2;
-    // runtime LoRA: the A stacks of the four adapted linears, model dtype, zero without an adapter: [3 lr][D] (q | k | v), [lr][D], [lr][D], [lr][4 D]
-    char *a_qkv = nullptr, *a_o = nullptr, *a_1 = nullptr, *a_2 = nullptr;
-    // runtime LoRA beside e4m3 weights (s2v_ctx::flr > 0): Bs = rnd(s * B) of the four adapted linears, model dtype, [N_pad][flr], zero without an adapter
-    char *bs_qkv = nullptr, *bs_o = nullptr, *bs_1 = nullptr, *bs_2 = nullptr;
-    // weight_format 1: e4m3 copies [N_pad][K] of the four big linears + per-output-channel scales (quantised at finalize)
-    char *q_qkv = nullptr, *q_o = nullptr, *q_1 = nullptr, *q_2 = nullptr;
-    float *s_qkv = nullptr, *s_o = nullptr, *s_1 = nullptr, *s_2 = nullptr;
+    char *nq_w, *nq_b, *nk_w, *nk_b;
+    LinW lin[LIN_NUM];
 };
 
 struct GraphKey {
@@ -86,7 +106,7 @@ struct s2v_ctx {
     int lr = 0;                  // lora_cap padded to what the GEMM dispatch needs (64, or 128 when D % 128 == 0); 0 with the mode off / fp8
     // fp8 weight formats with S2V_LORA_FP8_BRANCH: the branch runs beside the e4m3 GEMM (GemmArgs::lora_bs).  flr = lora_cap padded to 64 (the
     // down-projection's column tile; the up-projection steps by 16); the A stacks are carved with flr rows per adapter, the Bs arrays
-    // (LayerW::bs_*) [N_pad][flr], and the workspace holds T [Mpad][3 flr].  lr stays 0: nothing of the bf16 operand layout changes.
+    // (LinW::bs) [N_pad][flr], and the workspace holds T [Mpad][3 flr].  lr stays 0: nothing of the bf16 operand layout changes.
     int flr = 0;
     char* Tl = nullptr;          // workspace (flr): T = rnd(x . A^T) of the adapted GEMM being fed, rows 3 flr apart
     std::unordered_map<std::string, int> lora_names;   // attached: weight name -> rank
@@ -214,31 +234,30 @@ static Slot* add_slot(s2v_ctx* c, const std::string& name, char* dst, int64_t ro
     return &c->slots[name];
 }
 
-// the attn1 keys of layer l: fused QKV [rup(3D, 256)][D] + bias [3D], per-head LayerNorm(64) of q and k, out-projection [Dp][D] + bias
-static void add_attn_slots(s2v_ctx* c, int l, const LayerW& w) {
-    const int64_t D = c->D, E = c->esz, lr = c->lr, ldq = D + 3 * lr, ldo = D + lr;
-    char nm[160];
-#define NM(fmt) (snprintf(nm, sizeof(nm), "transformer_blocks.%d." fmt, l), std::string(nm))
-    Slot* sq[3];
-    sq[0] = add_slot(c, NM("attn1.to_q.weight"), w.wqkv, D, D, ldq);
-    sq[1] = add_slot(c, NM("attn1.to_k.weight"), w.wqkv + D * ldq * E, D, D, ldq);
-    sq[2] = add_slot(c, NM("attn1.to_v.weight"), w.wqkv + 2 * D * ldq * E, D, D, ldq);
-    // block-diagonal tail of the fused QKV: part p keeps s * B_p in the tail columns [p lr, (p + 1) lr) of its own rows, zeros elsewhere
+// the keys of the first nlin linears of layer l, and with the QKV the per-head LayerNorm(64) of q and k.  A linear of several parts (the fused
+// QKV) is one weight [rup(N, 256)][K + R] whose parts own N / parts rows each
+static void add_linear_slots(s2v_ctx* c, int l, const LayerW& w, int nlin) {
+    const int64_t E = c->esz, lr = c->lr;
     const int64_t fl = c->flr, la = lr + fl;  // fp8 branch: part p's rnd(s * B_p) sits in its own rows of the Bs array
-    for (int p = 0; la && p < 3; ++p) {
-        sq[p]->lora = LORA_BRANCH; sq[p]->lora_a = w.a_qkv + p * la * D * E; sq[p]->tail_col = D + p * lr;
-        if (fl) sq[p]->lora_bs = w.bs_qkv + p * D * fl * E;
+    char nm[160];
+#define NM(fmt, ...) (snprintf(nm, sizeof(nm), "transformer_blocks.%d." fmt, l, ##__VA_ARGS__), std::string(nm))
+    for (int i = 0; i < nlin; ++i) {
+        const LinShape s = lin_shape(i, c->D);
+        const LinW& x = w.lin[i];
+        const int64_t n = s.N / s.parts, ld = s.pitch(lr);
+        for (int p = 0; p < s.parts; ++p) {
+            Slot* sl = add_slot(c, NM("%s.weight", s.stem[p]), x.w + p * n * ld * E, n, s.K, ld);
+            add_slot(c, NM("%s.bias", s.stem[p]), x.b + p * n * E, 1, n, n);
+            if (!la) continue;
+            // block-diagonal tail: part p keeps s * B_p in the tail columns [p lr, (p + 1) lr) of its own rows, zeros elsewhere
+            sl->lora = LORA_BRANCH; sl->lora_a = x.a + p * la * s.K * E; sl->tail_col = s.K + p * lr;
+            if (fl) sl->lora_bs = x.bs + p * n * fl * E;
+        }
     }
-    add_slot(c, NM("attn1.to_q.bias"), w.bqkv, 1, D, D);
-    add_slot(c, NM("attn1.to_k.bias"), w.bqkv + D * E, 1, D, D);
-    add_slot(c, NM("attn1.to_v.bias"), w.bqkv + 2 * D * E, 1, D, D);
     add_slot(c, NM("attn1.norm_q.weight"), w.nq_w, 1, 64, 64);
     add_slot(c, NM("attn1.norm_q.bias"), w.nq_b, 1, 64, 64);
     add_slot(c, NM("attn1.norm_k.weight"), w.nk_w, 1, 64, 64);
     add_slot(c, NM("attn1.norm_k.bias"), w.nk_b, 1, 64, 64);
-    Slot* so = add_slot(c, NM("attn1.to_out.0.weight"), w.wo, D, D, ldo);
-    if (la) { so->lora = LORA_BRANCH; so->lora_a = w.a_o; so->tail_col = D; so->lora_bs = fl ? w.bs_o : nullptr; }
-    add_slot(c, NM("attn1.to_out.0.bias"), w.bo, 1, D, D);
 #undef NM
 }
 
@@ -252,35 +271,43 @@ static void lora_setup(s2v_ctx* c) {
     c->flr = (c->lora_cap > 0 && fp8 && (c->cfg.reserved[1] & S2V_LORA_FP8_BRANCH)) ? (int)rup(c->lora_cap, 64) : 0;
 }
 
+// The arena's layout is one sequence of carve calls, run twice: with no arena yet (A null) a pass only adds up the sizes, with the arena it hands out
+// the same pieces.  Every piece starts on a multiple of 256 bytes; a piece of no bytes is null
+struct Carver {
+    char* A; int64_t E; int64_t off = 0;
+    char* bytes(int64_t n) { const int64_t o = off; off += rup(n, 256); return A && n ? A + o : nullptr; }
+    char* operator()(int64_t elems) { return bytes(elems * E); }   // elements of the model dtype
+};
+
+// the first nlin linears of one layer: each weight followed directly by its bias, the two q/k LayerNorm pairs between bqkv and wo, then the A
+// stacks and (fp8 branch) the Bs arrays.  lr: the weights get lr zero tail columns per part; flr: no tail columns, A stacks of flr rows per adapter
+// and the Bs arrays instead
+static void carve_linears(const s2v_ctx* c, Carver& cv, LayerW& w, int nlin) {
+    const int64_t la = c->lr + c->flr;
+    for (int i = 0; i < nlin; ++i) {
+        const LinShape s = lin_shape(i, c->D);
+        w.lin[i].w = cv(s.n_pad() * s.pitch(c->lr)); w.lin[i].b = cv(s.N);
+        if (i == LIN_QKV) { w.nq_w = cv(64); w.nq_b = cv(64); w.nk_w = cv(64); w.nk_b = cv(64); }
+    }
+    for (int i = 0; i < nlin; ++i) { const LinShape s = lin_shape(i, c->D); w.lin[i].a = cv(s.parts * la * s.K); }
+    for (int i = 0; i < nlin; ++i) w.lin[i].bs = cv(lin_shape(i, c->D).n_pad() * c->flr);
+}
+
 // S2V_CTX_ATTN_WEIGHTS: an arena of num_layers x the attn1 weights, carved exactly as a model carves them (zero pad rows included), so that a
 // workspace context runs them through the same GEMM tiles; no stream, event, scratch or workspace of its own
 static int create_attn_weights(s2v_ctx* c) {
-    const int64_t D = c->D, E = c->esz, Dp = rup(D, 256), lr = c->lr;
-    int64_t off = 0;
-    auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
-    struct Offs { int64_t wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, a_qkv, a_o; };
-    std::vector<Offs> lo(c->L);
-    for (Offs& o : lo) {
-        o.wqkv = carve(rup(3 * D, 256) * (D + 3 * lr)); o.bqkv = carve(3 * D);
-        o.nq_w = carve(64); o.nq_b = carve(64); o.nk_w = carve(64); o.nk_b = carve(64);
-        o.wo = carve(Dp * (D + lr)); o.bo = carve(D);
-        o.a_qkv = carve(3 * lr * D); o.a_o = carve(lr * D);
-    }
-    const int64_t o_lora_hdr = carve(lr ? 128 : 0);
-    c->arena_bytes = off;
+    c->layers.assign(c->L, LayerW{});
+    auto layout = [&]() {
+        Carver cv{c->arena, c->esz};
+        for (LayerW& w : c->layers) carve_linears(c, cv, w, LIN_OUT + 1);
+        c->lora_hdr = cv(c->lr ? 128 : 0);
+        return cv.off;
+    };
+    c->arena_bytes = layout();
     S2V_CHECK_HIP(hipMalloc((void**)&c->arena, c->arena_bytes));
     S2V_CHECK_HIP(hipMemset(c->arena, 0, c->arena_bytes));
-    char* A = c->arena;
-    if (lr) c->lora_hdr = A + o_lora_hdr;
-    c->layers.assign(c->L, LayerW{});
-    for (int l = 0; l < c->L; ++l) {
-        const Offs& o = lo[l];
-        LayerW& w = c->layers[l];
-        w.wqkv = A + o.wqkv; w.bqkv = A + o.bqkv; w.nq_w = A + o.nq_w; w.nq_b = A + o.nq_b;
-        w.nk_w = A + o.nk_w; w.nk_b = A + o.nk_b; w.wo = A + o.wo; w.bo = A + o.bo;
-        w.a_qkv = A + o.a_qkv; w.a_o = A + o.a_o;
-        add_attn_slots(c, l, w);
-    }
+    layout();
+    for (int l = 0; l < c->L; ++l) add_linear_slots(c, l, c->layers[l], LIN_OUT + 1);
     return 0;
 }
 
@@ -360,99 +387,66 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
 
     const int64_t D = c->D, E = c->esz, L = c->L, TE = c->temb;
     const int64_t Kp = cfg->in_channels * 4, Cout = cfg->out_channels * 4, TX = cfg->text_embed_dim;
-    // two passes: size, then carve
-    int64_t off = 0;
-    auto carve = [&](int64_t elems) { int64_t o = off; off += rup(elems * E, 256); return o; };
-    struct Offs { int64_t ln1_w, ln1_b, ln2_w, ln2_b, wqkv, bqkv, nq_w, nq_b, nk_w, nk_b, wo, bo, w1, b1, w2, b2, a_qkv, a_o, a_1, a_2, bs_qkv, bs_o, bs_1, bs_2; };
-    std::vector<Offs> lo(L);
     const int64_t Dp = rup(D, 256);  // weight rows are padded to the 256-column GEMM tile (zero rows)
-    const int64_t lr = c->lr;        // runtime LoRA: the adapted weights get lr (QKV: 3 lr) zero tail columns, ld = K + R
-    const int64_t fl = c->flr, la = lr + fl;  // fp8 branch: no tail columns; A stacks of fl rows per adapter and the Bs arrays [N_pad][fl] instead
-    for (int l = 0; l < L; ++l) {
-        Offs& o = lo[l];
-        o.ln1_w = carve(D); o.ln1_b = carve(D); o.ln2_w = carve(D); o.ln2_b = carve(D);
-        o.wqkv = carve(rup(3 * D, 256) * (D + 3 * lr)); o.bqkv = carve(3 * D);
-        o.nq_w = carve(64); o.nq_b = carve(64); o.nk_w = carve(64); o.nk_b = carve(64);
-        o.wo = carve(Dp * (D + lr)); o.bo = carve(D);
-        o.w1 = carve(rup(4 * D, 256) * (D + lr)); o.b1 = carve(4 * D);
-        o.w2 = carve(Dp * (4 * D + lr)); o.b2 = carve(D);
-        o.a_qkv = carve(3 * la * D); o.a_o = carve(la * D); o.a_1 = carve(la * D); o.a_2 = carve(la * 4 * D);
-        o.bs_qkv = carve(rup(3 * D, 256) * fl); o.bs_o = carve(Dp * fl); o.bs_1 = carve(rup(4 * D, 256) * fl); o.bs_2 = carve(Dp * fl);
-    }
-    const int64_t o_patch_w = carve(Dp * Kp), o_patch_b = carve(D);
-    const int64_t o_text_w = carve(Dp * TX), o_text_b = carve(D);
-    const int64_t o_te1_w = carve(TE * D), o_te1_b = carve(TE), o_te2_w = carve(TE * TE), o_te2_b = carve(TE);
-    const int64_t o_nf_w = carve(D), o_nf_b = carve(D), o_no_w = carve(D), o_no_b = carve(D);
-    const int64_t o_po_w = carve(rup(Cout, 256) * D), o_po_b = carve(Cout);
+    const int64_t la = c->lr + c->flr;
     c->mc = cfg->lora_adaln_scope ? 9 : 6;
     const int64_t MC = c->mc;
     c->mod_rows = 2 * L * MC * D + 2 * D;
-    const int64_t o_mod_w = carve(c->mod_rows * TE), o_mod_b = carve(c->mod_rows);
-    // runtime LoRA: base copies of the weights an attach re-merges (every norm{1,2}.linear of the modulation stack, patch_embed.proj,
-    // patch_embed.text_proj), filled by s2v_finalize_weights
     c->base_mod_bytes = la ? c->mod_rows * TE * E : 0; c->base_patch_bytes = la ? Dp * Kp * E : 0; c->base_text_bytes = la ? Dp * TX * E : 0;
-    const int64_t o_base_mod = carve(la ? c->mod_rows * TE : 0), o_base_patch = carve(la ? Dp * Kp : 0), o_base_text = carve(la ? Dp * TX : 0);
-    const int64_t o_lora_hdr = carve(la ? 128 : 0);
-    // fp8 copies live in the same arena (one broadcast replicates everything a replica needs)
     c->fp8 = cfg->weight_format >= 1 && cfg->weight_format <= 3;
     c->fp8_qk = cfg->weight_format == 2;
     c->attn_p16 = cfg->attn_p_format == 1;
-    struct QOffs { int64_t q_qkv, q_o, q_1, q_2, s_qkv, s_o, s_1, s_2; };
-    std::vector<QOffs> qo(c->fp8 ? L : 0);
-    auto carve_b = [&](int64_t bytes) { int64_t o = off; off += rup(bytes, 256); return o; };
-    for (auto& q : qo) {
-        q.q_qkv = carve_b(rup(3 * D, 256) * D); q.q_o = carve_b(Dp * D); q.q_1 = carve_b(rup(4 * D, 256) * D); q.q_2 = carve_b(Dp * 4 * D);
-        q.s_qkv = carve_b(rup(3 * D, 256) * 4); q.s_o = carve_b(Dp * 4); q.s_1 = carve_b(rup(4 * D, 256) * 4); q.s_2 = carve_b(Dp * 4);
-    }
     if (kind == S2V_CTX_ATTN_WORKSPACE) {  // no arena: the weights come from another context (s2v_attn_forward_with)
         if (!create_tail(c)) return fail("s2v_create: allocation failed");
         *out = c;
         return 0;
     }
-    c->arena_bytes = off;
+    c->layers.assign(L, LayerW{});
+    // two passes: size, then carve
+    auto layout = [&]() {
+        Carver cv{c->arena, E};
+        for (LayerW& w : c->layers) {
+            w.ln1_w = cv(D); w.ln1_b = cv(D); w.ln2_w = cv(D); w.ln2_b = cv(D);
+            carve_linears(c, cv, w, LIN_NUM);
+        }
+        c->patch_w = cv(Dp * Kp); c->patch_b = cv(D);
+        c->text_w = cv(Dp * TX); c->text_b = cv(D);
+        c->te1_w = cv(TE * D); c->te1_b = cv(TE); c->te2_w = cv(TE * TE); c->te2_b = cv(TE);
+        c->nf_w = cv(D); c->nf_b = cv(D); c->no_w = cv(D); c->no_b = cv(D);
+        c->po_w = cv(rup(Cout, 256) * D); c->po_b = cv(Cout);
+        c->mod_w = cv(c->mod_rows * TE); c->mod_b = cv(c->mod_rows);
+        // runtime LoRA: base copies of the weights an attach re-merges (every norm{1,2}.linear of the modulation stack, patch_embed.proj,
+        // patch_embed.text_proj), filled by s2v_finalize_weights
+        c->base_mod = cv(c->base_mod_bytes / E); c->base_patch = cv(c->base_patch_bytes / E); c->base_text = cv(c->base_text_bytes / E);
+        c->lora_hdr = cv(la ? 128 : 0);
+        // fp8 copies live in the same arena (one broadcast replicates everything a replica needs)
+        for (LayerW& w : c->layers) {
+            if (!c->fp8) break;
+            for (int i = 0; i < LIN_NUM; ++i) { const LinShape s = lin_shape(i, D); w.lin[i].q = cv.bytes(s.n_pad() * s.K); }
+            for (int i = 0; i < LIN_NUM; ++i) w.lin[i].s = (float*)cv.bytes(lin_shape(i, D).n_pad() * 4);
+        }
+        return cv.off;
+    };
+    c->arena_bytes = layout();
     hipError_t e = hipMalloc((void**)&c->arena, c->arena_bytes);
     if (e == hipSuccess) e = hipMemset(c->arena, 0, c->arena_bytes);
     if (e != hipSuccess) return fail(hipGetErrorString(e));
-    char* A = c->arena;
-    c->layers.resize(L);
+    layout();
     char nm[160];
     for (int l = 0; l < L; ++l) {
-        const Offs& o = lo[l];
-        LayerW& w = c->layers[l];
-        w.ln1_w = A + o.ln1_w; w.ln1_b = A + o.ln1_b; w.ln2_w = A + o.ln2_w; w.ln2_b = A + o.ln2_b;
-        w.wqkv = A + o.wqkv; w.bqkv = A + o.bqkv; w.nq_w = A + o.nq_w; w.nq_b = A + o.nq_b;
-        w.nk_w = A + o.nk_w; w.nk_b = A + o.nk_b; w.wo = A + o.wo; w.bo = A + o.bo;
-        w.w1 = A + o.w1; w.b1 = A + o.b1; w.w2 = A + o.w2; w.b2 = A + o.b2;
-        w.a_qkv = A + o.a_qkv; w.a_o = A + o.a_o; w.a_1 = A + o.a_1; w.a_2 = A + o.a_2;
-        if (fl) { w.bs_qkv = A + o.bs_qkv; w.bs_o = A + o.bs_o; w.bs_1 = A + o.bs_1; w.bs_2 = A + o.bs_2; }
-        if (c->fp8) {
-            const QOffs& q = qo[l];
-            w.q_qkv = A + q.q_qkv; w.q_o = A + q.q_o; w.q_1 = A + q.q_1; w.q_2 = A + q.q_2;
-            w.s_qkv = (float*)(A + q.s_qkv); w.s_o = (float*)(A + q.s_o); w.s_1 = (float*)(A + q.s_1); w.s_2 = (float*)(A + q.s_2);
-        }
+        const LayerW& w = c->layers[l];
 #define NM(fmt) (snprintf(nm, sizeof(nm), "transformer_blocks.%d." fmt, l), std::string(nm))
         add_slot(c, NM("norm1.norm.weight"), w.ln1_w, 1, D, D);
         add_slot(c, NM("norm1.norm.bias"), w.ln1_b, 1, D, D);
         add_slot(c, NM("norm2.norm.weight"), w.ln2_w, 1, D, D);
         add_slot(c, NM("norm2.norm.bias"), w.ln2_b, 1, D, D);
-        add_attn_slots(c, l, w);
-        Slot* s1 = add_slot(c, NM("ff.net.0.proj.weight"), w.w1, 4 * D, D, D + lr);
-        add_slot(c, NM("ff.net.0.proj.bias"), w.b1, 1, 4 * D, 4 * D);
-        Slot* s2 = add_slot(c, NM("ff.net.2.weight"), w.w2, D, 4 * D, 4 * D + lr);
-        add_slot(c, NM("ff.net.2.bias"), w.b2, 1, D, D);
-        if (la) { s1->lora = LORA_BRANCH; s1->lora_a = w.a_1; s1->tail_col = D; s2->lora = LORA_BRANCH; s2->lora_a = w.a_2; s2->tail_col = 4 * D; }
-        if (fl) { s1->lora_bs = w.bs_1; s2->lora_bs = w.bs_2; }
-        add_slot(c, NM("norm1.linear.weight"), A + o_mod_w + (int64_t)(2 * l) * MC * D * TE * E, 6 * D, TE, TE)->lora = la ? LORA_REMERGE : LORA_NONE;
-        add_slot(c, NM("norm1.linear.bias"), A + o_mod_b + (int64_t)(2 * l) * MC * D * E, 1, 6 * D, 6 * D);
-        add_slot(c, NM("norm2.linear.weight"), A + o_mod_w + (int64_t)(2 * l + 1) * MC * D * TE * E, 6 * D, TE, TE)->lora = la ? LORA_REMERGE : LORA_NONE;
-        add_slot(c, NM("norm2.linear.bias"), A + o_mod_b + (int64_t)(2 * l + 1) * MC * D * E, 1, 6 * D, 6 * D);
+        add_linear_slots(c, l, w, LIN_NUM);
+        add_slot(c, NM("norm1.linear.weight"), c->mod_w + (int64_t)(2 * l) * MC * D * TE * E, 6 * D, TE, TE)->lora = la ? LORA_REMERGE : LORA_NONE;
+        add_slot(c, NM("norm1.linear.bias"), c->mod_b + (int64_t)(2 * l) * MC * D * E, 1, 6 * D, 6 * D);
+        add_slot(c, NM("norm2.linear.weight"), c->mod_w + (int64_t)(2 * l + 1) * MC * D * TE * E, 6 * D, TE, TE)->lora = la ? LORA_REMERGE : LORA_NONE;
+        add_slot(c, NM("norm2.linear.bias"), c->mod_b + (int64_t)(2 * l + 1) * MC * D * E, 1, 6 * D, 6 * D);
 #undef NM
     }
-    c->patch_w = A + o_patch_w; c->patch_b = A + o_patch_b; c->text_w = A + o_text_w; c->text_b = A + o_text_b;
-    c->te1_w = A + o_te1_w; c->te1_b = A + o_te1_b; c->te2_w = A + o_te2_w; c->te2_b = A + o_te2_b;
-    c->nf_w = A + o_nf_w; c->nf_b = A + o_nf_b; c->no_w = A + o_no_w; c->no_b = A + o_no_b;
-    c->po_w = A + o_po_w; c->po_b = A + o_po_b; c->mod_w = A + o_mod_w; c->mod_b = A + o_mod_b;
-    if (la) { c->base_mod = A + o_base_mod; c->base_patch = A + o_base_patch; c->base_text = A + o_base_text; c->lora_hdr = A + o_lora_hdr; }
     add_slot(c, "patch_embed.proj.weight", c->patch_w, D, Kp, Kp)->lora = la ? LORA_REMERGE : LORA_NONE;
     add_slot(c, "patch_embed.proj.bias", c->patch_b, 1, D, D);
     add_slot(c, "patch_embed.text_proj.weight", c->text_w, D, TX, TX)->lora = la ? LORA_REMERGE : LORA_NONE;
@@ -582,14 +576,12 @@ extern "C" int s2v_finalize_weights(s2v_ctx* c, s2v_stream stream) {
     }
     if (c->fp8) {
         // per-output-channel e4m3 quantisation of the (LoRA-merged) bf16 weights; the zero pad rows get scale 1, bytes 0
-        const int64_t D = c->D, Dp = rup(D, 256);
         hipStream_t st = (hipStream_t)stream;
-        for (auto& w : c->layers) {
-            S2V_TRY(launch_quant_rows_fp8(w.wqkv, D, rup(3 * D, 256), (int)D, w.q_qkv, w.s_qkv, st));
-            S2V_TRY(launch_quant_rows_fp8(w.wo, D, Dp, (int)D, w.q_o, w.s_o, st));
-            S2V_TRY(launch_quant_rows_fp8(w.w1, D, rup(4 * D, 256), (int)D, w.q_1, w.s_1, st));
-            S2V_TRY(launch_quant_rows_fp8(w.w2, 4 * D, Dp, (int)(4 * D), w.q_2, w.s_2, st));
-        }
+        for (auto& w : c->layers)
+            for (int i = 0; i < LIN_NUM; ++i) {
+                const LinShape s = lin_shape(i, c->D);
+                S2V_TRY(launch_quant_rows_fp8(w.lin[i].w, s.pitch(c->lr), s.n_pad(), (int)s.K, w.lin[i].q, w.lin[i].s, st));
+            }
         S2V_CHECK_HIP(hipStreamSynchronize(st));
     }
     if (c->lora_tmp) {
@@ -1014,6 +1006,37 @@ static void lora_branch_fp8(const s2v_ctx* c, GemmArgs& g, const char* bs, int s
     g.lora_t = c->Tl; g.lora_ldt = 3 * c->flr; g.lora_bs = bs; g.lora_r = c->flr; g.lora_seg = seg;
 }
 
+// where the operand of an adapted linear lives: the 16-bit rows with their pitch and, if its producer left one, the MX image (bytes [rows][K],
+// block scales) the fp8 GEMM reads in place of them
+struct LinIn {
+    char* x; int ldx;
+    const void* mx_q = nullptr; const unsigned char* mx_s = nullptr;
+};
+static const int PK_UNTIMED = -1;
+
+// One of the four big linears of a layer, on the context's rows: lora: the weights carry an attached adapter (their context's lora_names is not
+// empty), so the down-projection for the mode in force runs first -- beside e4m3 weights from the best-precision operand into the T buffer, the
+// GEMM taking the branch operands; otherwise in place behind column K of the 16-bit rows, the GEMM running with K' = K + R.  g carries the
+// destination and the epilogue's own fields; pk: the class the GEMM is timed as (PK_UNTIMED: not at all); prequant: linear_fp8
+static int adapted_linear(s2v_ctx* c, const LayerW& w, int which, const LinIn& in, bool lora, GemmArgs g, int epi, bool prequant, int pk, hipStream_t st) {
+    const LinShape s = lin_shape(which, c->D);
+    const LinW& x = w.lin[which];
+    const int K = (int)s.K, Kx = (int)s.pitch(c->lr);
+    if (lora && c->flr > 0) {
+        if (in.mx_s) S2V_TRY(lora_down_fp8(c, in.mx_q, K, in.mx_s, x.a, s.parts * c->flr, K, st));
+        else S2V_TRY(lora_down_fp8(c, in.x, in.ldx, nullptr, x.a, s.parts * c->flr, K, st));
+        lora_branch_fp8(c, g, x.bs, s.lora_seg());
+    } else if (lora) {
+        S2V_TRY(lora_down(c, in.x, in.ldx, x.a, s.parts * c->lr, K, st));
+    }
+    g.A = in.x; g.lda = in.ldx; g.W = x.w; g.ldw = Kx; g.bias = x.b; g.M = (int)c->M; g.N = (int)s.N; g.K = lora ? Kx : K;
+    if (in.mx_s) { g.A = in.mx_q; g.mx_a_s = in.mx_s; g.mx_rows = (int)c->Mpad; }
+    auto gemm = [&]() { return c->fp8 ? linear_fp8(c, g, epi, x.q, x.s, st, prequant) : linear(c, g, epi, st); };
+    if (pk == PK_UNTIMED) return gemm();
+    ProfScope ps(c, pk, st);
+    return gemm();
+}
+
 // ---- attention: one QKV projection and one core for the single engine (run_attention) and the Ulysses shard (shard_front, shard_attention) ----
 // May the per-head LayerNorm + rotary embedding of q and k ride in the QKV projection's epilogue (EPI_BIAS_QKNORM), on the rounded projection
 // as the stand-alone kernel does?  The matrix-core kernels only, and rotary tables in the paired form (s2v_set_rope).  g_fused_qk is the A/B
@@ -1041,19 +1064,11 @@ static QkNormRopeArgs qk_norm_args(const s2v_ctx* c, const LayerW& w) {
 // Xn (row pitch pX) -> QKV on the context's rows.  lora: the weights carry an attached adapter (their context's lora_names is not empty) and the
 // GEMM runs with K = pX behind the down-projection; qk_epi: EPI_BIAS_QKNORM; prequant: linear_fp8
 static int qkv_proj(s2v_ctx* c, const LayerW& w, int pX, bool lora, bool qk_epi, bool prequant, hipStream_t st) {
-    const int D = c->D;
-    const bool lora8 = lora && c->flr > 0;  // the branch beside the e4m3 GEMM: Xn holds the bf16 rows also under prequant (block_norm)
-    if (lora8) S2V_TRY(lora_down_fp8(c, c->Xn, pX, nullptr, w.a_qkv, 3 * c->flr, D, st));
-    else if (lora) S2V_TRY(lora_down(c, c->Xn, pX, w.a_qkv, 3 * c->lr, D, st));
     GemmArgs g{};
-    g.A = c->Xn; g.lda = pX; g.W = w.wqkv; g.ldw = pX; g.bias = w.bqkv;
-    g.C = c->QKV; g.ldc = 3 * D; g.M = (int)c->M; g.N = 3 * D; g.K = lora ? pX : D;
-    if (lora8) lora_branch_fp8(c, g, w.bs_qkv, D);
+    g.C = c->QKV; g.ldc = 3 * c->D;
     if (qk_epi) set_qk_epilogue(c, w, g);
-    ProfScope ps(c, PK_QKV, st);
-    const int epi = qk_epi ? EPI_BIAS_QKNORM : EPI_BIAS;
-    if (c->fp8) return linear_fp8(c, g, epi, w.q_qkv, w.s_qkv, st, prequant);
-    return linear(c, g, epi, st);
+    // the branch beside the e4m3 GEMM: Xn holds the bf16 rows also under prequant (block_norm)
+    return adapted_linear(c, w, LIN_QKV, {c->Xn, pX}, lora, g, qk_epi ? EPI_BIAS_QKNORM : EPI_BIAS, prequant, PK_QKV, st);
 }
 
 // what the callers of attn_core differ in: the q | k | v rows, heads and tokens per sample (the kernel and its formats are chosen on Ntok), the
@@ -1156,62 +1171,30 @@ static GemmArgs block_gate(const s2v_ctx* c, int half, const char* mod_base, int
     return g;
 }
 
-// the out-projection of what run_attention / the shard's O exchange left: Xn, or (attn_mx_out) the MX image in aq / hs, against w.wo behind the
-// adapter's down-projection.  g carries the destination and the epilogue's own fields; timed: the GEMM counts as PK_OUT (the block, not the
+// the out-projection of what run_attention / the shard's O exchange left: Xn, or (attn_mx_out) the MX image in aq / hs, against the layer's LIN_OUT behind
+// the adapter's down-projection.  g carries the destination and the epilogue's own fields; timed: the GEMM counts as PK_OUT (the block, not the
 // AttnProcessor seam)
 static int out_proj(s2v_ctx* c, const LayerW& w, bool lora, GemmArgs g, int epi, bool timed, hipStream_t st) {
-    const int D = c->D, pX = D + 3 * c->lr;
-    const bool lora8 = lora && c->flr > 0;
-    if (lora8) {
-        if (attn_mx_out(c)) S2V_TRY(lora_down_fp8(c, c->aq, D, c->hs, w.a_o, c->flr, D, st));
-        else S2V_TRY(lora_down_fp8(c, c->Xn, pX, nullptr, w.a_o, c->flr, D, st));
-        lora_branch_fp8(c, g, w.bs_o, 0);
-    } else if (lora) {
-        S2V_TRY(lora_down(c, c->Xn, pX, w.a_o, c->lr, D, st));
-    }
-    g.A = c->Xn; g.lda = pX; g.W = w.wo; g.ldw = D + c->lr; g.bias = w.bo; g.M = (int)c->M; g.N = D; g.K = lora ? D + c->lr : D;
-    if (attn_mx_out(c)) { g.A = c->aq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
-    auto gemm = [&]() { return c->fp8 ? linear_fp8(c, g, epi, w.q_o, w.s_o, st) : linear(c, g, epi, st); };
-    if (!timed) return gemm();
-    ProfScope ps(c, PK_OUT, st);
-    return gemm();
+    LinIn in{c->Xn, c->D + 3 * c->lr};
+    if (attn_mx_out(c)) { in.mx_q = c->aq; in.mx_s = c->hs; }
+    return adapted_linear(c, w, LIN_OUT, in, lora, g, epi, false, timed ? PK_OUT : PK_UNTIMED, st);
 }
 
 static int block_ff(s2v_ctx* c, int l, GemmArgs g, bool prequant, hipStream_t st) {
     const LayerW& w = c->layers[l];
     const int D = c->D, pX = D + 3 * c->lr, pH = 4 * D + c->lr;
-    const bool lora = c->lora_on(), lora8 = lora && c->flr > 0;
+    const bool lora = c->lora_on();
     GemmArgs f{};
-    if (lora8) {
-        S2V_TRY(lora_down_fp8(c, c->Xn, pX, nullptr, w.a_1, c->flr, D, st));
-        lora_branch_fp8(c, f, w.bs_1, 0);
-    } else if (lora) {
-        S2V_TRY(lora_down(c, c->Xn, pX, w.a_1, c->lr, D, st));
-    }
-    f.A = c->Xn; f.lda = pX; f.W = w.w1; f.ldw = D + c->lr; f.bias = w.b1; f.C = c->Hb; f.ldc = pH;
-    f.M = (int)c->M; f.N = 4 * D; f.K = lora ? D + c->lr : D;
+    f.C = c->Hb; f.ldc = pH;
     bool mx = c->fp8 && (4 * D) % 128 == 0;
 #ifdef S2V_DIAG
     mx = mx && g_fp8_mx;
 #endif
     if (mx) { f.mx_out_q = c->hq; f.mx_out_s = c->hs; f.mx_rows = (int)c->Mpad; }
-    {
-        ProfScope ps(c, PK_FF1, st);
-        if (c->fp8) S2V_TRY(linear_fp8(c, f, EPI_BIAS_GELU, w.q_1, w.s_1, st, prequant));
-        else S2V_TRY(linear(c, f, EPI_BIAS_GELU, st));
-    }
-    if (lora8) {  // FF2: the operand is the FF1 epilogue's MX image (or, without the MX form, the bf16 rows in Hb)
-        if (mx) S2V_TRY(lora_down_fp8(c, c->hq, 4 * D, c->hs, w.a_2, c->flr, 4 * D, st));
-        else S2V_TRY(lora_down_fp8(c, c->Hb, pH, nullptr, w.a_2, c->flr, 4 * D, st));
-        lora_branch_fp8(c, g, w.bs_2, 0);
-    } else if (lora) {
-        S2V_TRY(lora_down(c, c->Hb, pH, w.a_2, c->lr, 4 * D, st));
-    }
-    g.A = c->Hb; g.lda = pH; g.W = w.w2; g.ldw = pH; g.bias = w.b2; g.K = lora ? pH : 4 * D;
-    if (mx) { g.A = c->hq; g.mx_a_s = c->hs; g.mx_rows = (int)c->Mpad; }
-    ProfScope ps(c, PK_FF2, st);
-    if (c->fp8) return linear_fp8(c, g, EPI_BIAS_GATE_RES, w.q_2, w.s_2, st);
-    return linear(c, g, EPI_BIAS_GATE_RES, st);
+    S2V_TRY(adapted_linear(c, w, LIN_FF1, {c->Xn, pX}, lora, f, EPI_BIAS_GELU, prequant, PK_FF1, st));
+    LinIn h{c->Hb, pH};  // FF2: the operand is the FF1 epilogue's MX image (or, without the MX form, the bf16 rows in Hb)
+    if (mx) { h.mx_q = c->hq; h.mx_s = c->hs; }
+    return adapted_linear(c, w, LIN_FF2, h, lora, g, EPI_BIAS_GATE_RES, false, PK_FF2, st);
 }
 
 static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] rows of this layer's norm1 */,
@@ -1476,32 +1459,18 @@ extern "C" int s2v_lora_detach(s2v_ctx* c, s2v_stream stream) {
     S2V_TRY(lora_checks(c, "s2v_lora_detach"));
     hipStream_t st = (hipStream_t)stream;
     if (!c->lora_on()) return 0;
-    const int64_t D = c->D, E = c->esz, lr = c->lr, Dp = rup(D, 256);
+    const int64_t E = c->esz, lr = c->lr, fl = c->flr;
     const bool model = c->kind == S2V_CTX_MODEL;
-    for (auto& w : c->layers) {  // fp8 branch: zero Bs arrays and A stacks
-        if (!c->flr) break;
-        const int64_t fl = c->flr;
-        S2V_CHECK_HIP(hipMemsetAsync(w.bs_qkv, 0, (size_t)(rup(3 * D, 256) * fl * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.bs_o, 0, (size_t)(Dp * fl * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.bs_1, 0, (size_t)(rup(4 * D, 256) * fl * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.bs_2, 0, (size_t)(Dp * fl * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_qkv, 0, (size_t)(3 * fl * D * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_o, 0, (size_t)(fl * D * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_1, 0, (size_t)(fl * D * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_2, 0, (size_t)(fl * 4 * D * E), st));
-    }
-    for (auto& w : c->layers) {  // zero tails and A stacks: a later attach of fewer names must not meet these values
-        if (c->flr) break;
-        S2V_CHECK_HIP(hipMemset2DAsync(w.wqkv + D * E, (size_t)((D + 3 * lr) * E), 0, (size_t)(3 * lr * E), (size_t)rup(3 * D, 256), st));
-        S2V_CHECK_HIP(hipMemset2DAsync(w.wo + D * E, (size_t)((D + lr) * E), 0, (size_t)(lr * E), (size_t)Dp, st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_qkv, 0, (size_t)(3 * lr * D * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_o, 0, (size_t)(lr * D * E), st));
-        if (!model) continue;
-        S2V_CHECK_HIP(hipMemset2DAsync(w.w1 + D * E, (size_t)((D + lr) * E), 0, (size_t)(lr * E), (size_t)rup(4 * D, 256), st));
-        S2V_CHECK_HIP(hipMemset2DAsync(w.w2 + 4 * D * E, (size_t)((4 * D + lr) * E), 0, (size_t)(lr * E), (size_t)Dp, st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_1, 0, (size_t)(lr * D * E), st));
-        S2V_CHECK_HIP(hipMemsetAsync(w.a_2, 0, (size_t)(lr * 4 * D * E), st));
-    }
+    // zero what an attach wrote beside the base weights -- fp8 branch: the Bs arrays, otherwise the tail columns -- and the A stacks: a later
+    // attach of fewer names must not meet these values.  An attention-weights context holds the first two linears only
+    for (auto& w : c->layers)
+        for (int i = 0; i < (model ? LIN_NUM : LIN_OUT + 1); ++i) {
+            const LinShape s = lin_shape(i, c->D);
+            const LinW& x = w.lin[i];
+            if (fl) S2V_CHECK_HIP(hipMemsetAsync(x.bs, 0, (size_t)(s.n_pad() * fl * E), st));
+            else S2V_CHECK_HIP(hipMemset2DAsync(x.w + s.K * E, (size_t)(s.pitch(lr) * E), 0, (size_t)(s.parts * lr * E), (size_t)s.n_pad(), st));
+            S2V_CHECK_HIP(hipMemsetAsync(x.a, 0, (size_t)(s.parts * (lr + fl) * s.K * E), st));
+        }
     if (model) {
         // the modulation stack interleaves, under lora_adaln_scope 1, the reference-image copies with the six chunks: rebuild slot by slot
         for (auto& kv : c->slots) {
@@ -2049,6 +2018,58 @@ extern "C" int s2v_op_linear_lora(const void* x, const void* W, const void* bias
     return rc;
 }
 
+// An fp8 linear on scratch, with or without an adapter, as the s2v_op_*fp8* entry points run it: x [M][K] and W [N][K] (bf16, rows K apart) are
+// quantised per row to e4m3 into xq / wq with their scales in xs / ws, and the product runs on the fp8 matrix cores.  mx_s set: x is not
+// quantised -- xq already holds the operand as an MX image with these block scales.  mx_out_q set: the epilogue leaves its output as an MX image
+// as well.  A set: the adapter branch beside it, as the fp8 engines run it with S2V_LORA_FP8_BRANCH -- A into a stack, rnd(scale * B) into a Bs
+// array (the attach-time kernels), T = rnd(x^ . A^T) from the best-precision operand (the bf16 rows of x, or the MX image dequantised exactly:
+// the down-projection kernels), and T . Bs^T added to the dequantised accumulator before bias / GELU (GemmArgs::lora_bs)
+struct Fp8Op {
+    const void *x, *W, *bias; void* C; int M, N, K;
+    char *xq, *wq; float *xs, *ws;
+    const unsigned char* mx_s; unsigned char *mx_out_q, *mx_out_s;
+    const float *A, *B; int rank; float scale;
+    char *a_st, *bs, *t;   // A stack [R][K], Bs [N][R], T [M][R], bf16, R = rank rounded up to 64
+};
+static Fp8Op fp8_op(const void* x, const void* W, const void* bias, void* C, int M, int N, int K, char* xq, char* wq, float* xs, float* ws) {
+    Fp8Op o{};
+    o.x = x; o.W = W; o.bias = bias; o.C = C; o.M = M; o.N = N; o.K = K; o.xq = xq; o.wq = wq; o.xs = xs; o.ws = ws;
+    return o;
+}
+// ... on the scratch of s2v_op_linear_fp8, which s2v_op_linear_fp8_lora's starts with: xq [M][K], wq [N][K], xs [M], ws [N]
+static Fp8Op fp8_op(const void* x, const void* W, const void* bias, void* C, int M, int N, int K, void* scratch) {
+    char *xq = (char*)scratch, *wq = xq + (int64_t)M * K;
+    float* xs = (float*)(wq + (int64_t)N * K);
+    return fp8_op(x, W, bias, C, M, N, K, xq, wq, xs, xs + M);
+}
+static void fp8_op_adapter(Fp8Op& o, const float* A, const float* B, int rank, float scale, char* a_st, char* bs, char* t) {
+    o.A = A; o.B = B; o.rank = rank; o.scale = scale; o.a_st = a_st; o.bs = bs; o.t = t;
+}
+static int launch_fp8_op(const Fp8Op& o, int epi, hipStream_t st) {
+    const int M = o.M, N = o.N, K = o.K, R = (int)rup(o.rank, 64);
+    if (!o.mx_s) S2V_TRY(launch_quant_rows_fp8(o.x, K, M, K, o.xq, o.xs, st));
+    S2V_TRY(launch_quant_rows_fp8(o.W, K, N, K, o.wq, o.ws, st));
+    GemmArgs g{};
+    g.A = o.xq; g.lda = K; g.W = o.wq; g.ldw = K; g.bias = o.bias; g.C = o.C; g.ldc = N; g.M = M; g.N = N; g.K = K;
+    g.a_rows_padded = M; g.w_rows_padded = N; g.a_scale = o.mx_s ? nullptr : o.xs; g.w_scale = o.ws;
+    if (o.mx_s) { g.mx_a_s = o.mx_s; g.mx_rows = M; }
+    if (o.mx_out_q) { g.mx_out_q = o.mx_out_q; g.mx_out_s = o.mx_out_s; g.mx_rows = M; }
+    if (o.A) {
+        S2V_TRY(launch_lora_pack_a(o.A, o.rank, R, K, o.a_st, K, S2V_BF16, st));
+        S2V_TRY(launch_lora_pack_b(o.B, o.rank, R, N, o.scale, o.bs, R, S2V_BF16, st));
+        LoraDownArgs d{};
+        d.x = o.x; d.ldx = K; d.A = o.a_st; d.lda = K; d.out = o.t; d.ldo = R; d.M = M; d.N = R; d.K = K;
+        if (o.mx_s) {
+            d.x = o.xq; d.mx_s = o.mx_s; d.mx_rows = M;
+            S2V_TRY(launch_lora_down_mx(d, st));
+        } else {
+            S2V_TRY(launch_lora_down(d, S2V_BF16, true, st));
+        }
+        g.lora_t = o.t; g.lora_ldt = R; g.lora_bs = o.bs; g.lora_r = R; g.lora_seg = 0;
+    }
+    return launch_gemm_fp8(g, epi, st);
+}
+
 // C = epilogue(dequant(quant_rows(A) . quant_rows(W)^T) + bias): both bf16 operands are quantised per row to e4m3 (dynamic
 // per-token / per-output-channel scales) into `scratch` and multiplied on the fp8 matrix cores.  M, N multiples of 256, K of 128.
 extern "C" int s2v_op_linear_fp8(const void* A, const void* W, const void* bias, void* C, int32_t M, int32_t N, int32_t K,
@@ -2058,17 +2079,7 @@ extern "C" int s2v_op_linear_fp8(const void* A, const void* W, const void* bias,
     S2V_REQUIRE(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, "s2v_op_linear_fp8: M, N multiples of 256 and K of 128");
     const int64_t need = (int64_t)M * K + (int64_t)N * K + 4 * ((int64_t)M + N);
     S2V_REQUIRE(scratch_bytes >= need, "s2v_op_linear_fp8: scratch too small (M*K + N*K + 4*(M+N) bytes)");
-    hipStream_t st = (hipStream_t)stream;
-    char* aq = (char*)scratch;
-    char* wq = aq + (int64_t)M * K;
-    float* as = (float*)(wq + (int64_t)N * K);
-    float* ws = as + M;
-    S2V_TRY(launch_quant_rows_fp8(A, K, M, K, aq, as, st));
-    S2V_TRY(launch_quant_rows_fp8(W, K, N, K, wq, ws, st));
-    GemmArgs g{};
-    g.A = aq; g.lda = K; g.W = wq; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K;
-    g.a_rows_padded = M; g.w_rows_padded = N; g.a_scale = as; g.w_scale = ws;
-    return launch_gemm_fp8(g, epilogue, st);
+    return launch_fp8_op(fp8_op(A, W, bias, C, M, N, K, scratch), epilogue, (hipStream_t)stream);
 }
 
 // FeedForward (attention.py:1237-1243) on the fp8 matrix cores as the fp8 engine runs it: x, W1, W2 quantised per row (e4m3, amax / 448);
@@ -2088,35 +2099,17 @@ extern "C" int s2v_op_ff_fp8(const void* x, const void* w1, const void* b1, cons
     char* hb = (char*)(w2s + D);                 // bf16 h (mx = 0)
     char* hq = hb + (size_t)M * F * 2;           // e4m3 h
     unsigned char* hsc = (unsigned char*)hq + (size_t)M * F;  // MX block scales
-    int rc = 0;
-    auto run = [&]() -> int {
-        S2V_TRY(launch_quant_rows_fp8(x, D, M, D, xq, xs, st));
-        S2V_TRY(launch_quant_rows_fp8(w1, D, F, D, w1q, w1s, st));
-        S2V_TRY(launch_quant_rows_fp8(w2, F, D, F, w2q, w2s, st));
-        GemmArgs f{};
-        f.A = xq; f.lda = D; f.W = w1q; f.ldw = D; f.bias = b1; f.C = hb; f.ldc = F; f.M = M; f.N = F; f.K = D;
-        f.a_rows_padded = M; f.w_rows_padded = F; f.a_scale = xs; f.w_scale = w1s;
-        if (mx) { f.mx_out_q = (unsigned char*)hq; f.mx_out_s = hsc; f.mx_rows = M; }
-        S2V_TRY(launch_gemm_fp8(f, EPI_BIAS_GELU, st));
-        GemmArgs g{};
-        g.A = hq; g.lda = F; g.W = w2q; g.ldw = F; g.bias = b2; g.C = out; g.ldc = D; g.M = M; g.N = D; g.K = F;
-        g.a_rows_padded = M; g.w_rows_padded = D; g.w_scale = w2s;
-        if (mx) { g.mx_a_s = hsc; g.mx_rows = M; }
-        else {
-            S2V_TRY(launch_quant_rows_fp8(hb, F, M, F, hq, hs_row, st));
-            g.a_scale = hs_row;
-        }
-        return launch_gemm_fp8(g, EPI_BIAS, st);
-    };
-    rc = run();
+    Fp8Op f1 = fp8_op(x, w1, b1, hb, M, F, D, xq, w1q, xs, w1s), f2 = fp8_op(hb, w2, b2, out, M, D, F, hq, w2q, hs_row, w2s);
+    if (mx) { f1.mx_out_q = (unsigned char*)hq; f1.mx_out_s = hsc; f2.mx_s = hsc; }
+    int rc = launch_fp8_op(f1, EPI_BIAS_GELU, st);
+    if (!rc) rc = launch_fp8_op(f2, EPI_BIAS, st);
     hipStreamSynchronize(st);
     hipFree(p);
     return rc;
 }
 
 // One adapted linear as the fp8 engines run it with S2V_LORA_FP8_BRANCH: s2v_op_linear_fp8's quantisation and GEMM with the adapter branch beside
-// it -- A into a stack, rnd(scale * B) into a Bs array (the attach-time kernels), T = rnd(x . A^T) from the bf16 rows of x (the down-projection
-// kernel), and T . Bs^T added to the dequantised accumulator before bias / GELU (GemmArgs::lora_bs).  Everything lives in `scratch`; asynchronous.
+// it (Fp8Op), T from the bf16 rows of x.  Everything lives in `scratch`; asynchronous.
 extern "C" int s2v_op_linear_fp8_lora(const void* x, const void* W, const void* bias, const float* A, const float* B, int32_t rank, float scale, void* C,
                                       int32_t M, int32_t N, int32_t K, int32_t epilogue, void* scratch, int64_t scratch_bytes, s2v_stream stream) {
     S2V_REQUIRE(x && W && A && B && C && scratch, "s2v_op_linear_fp8_lora: null argument");
@@ -2127,26 +2120,12 @@ extern "C" int s2v_op_linear_fp8_lora(const void* x, const void* W, const void* 
     const int64_t o_q = rup((int64_t)M * K + (int64_t)N * K + 4 * ((int64_t)M + N), 256);
     const int64_t need = o_q + 2 * R * ((int64_t)K + N + M);
     S2V_REQUIRE(scratch_bytes >= need, "s2v_op_linear_fp8_lora: scratch too small (M*K + N*K + 4*(M+N) rounded up to 256, + 2*R*(K+N+M) bytes, R = rank rounded up to 64)");
-    hipStream_t st = (hipStream_t)stream;
-    char* aq = (char*)scratch;
-    char* wq = aq + (int64_t)M * K;
-    float* as = (float*)(wq + (int64_t)N * K);
-    float* ws = as + M;
     char* a_st = (char*)scratch + o_q;          // A stack [R][K]
     char* bs = a_st + 2 * R * K;                // Bs [N][R]
     char* t = bs + 2 * R * N;                   // T [M][R]
-    S2V_TRY(launch_quant_rows_fp8(x, K, M, K, aq, as, st));
-    S2V_TRY(launch_quant_rows_fp8(W, K, N, K, wq, ws, st));
-    S2V_TRY(launch_lora_pack_a(A, rank, (int)R, K, a_st, K, S2V_BF16, st));
-    S2V_TRY(launch_lora_pack_b(B, rank, (int)R, N, scale, bs, R, S2V_BF16, st));
-    LoraDownArgs d{};
-    d.x = x; d.ldx = K; d.A = a_st; d.lda = K; d.out = t; d.ldo = (int)R; d.M = M; d.N = (int)R; d.K = K;
-    S2V_TRY(launch_lora_down(d, S2V_BF16, true, st));
-    GemmArgs g{};
-    g.A = aq; g.lda = K; g.W = wq; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K;
-    g.a_rows_padded = M; g.w_rows_padded = N; g.a_scale = as; g.w_scale = ws;
-    g.lora_t = t; g.lora_ldt = (int)R; g.lora_bs = bs; g.lora_r = (int)R; g.lora_seg = 0;
-    return launch_gemm_fp8(g, epilogue, st);
+    Fp8Op o = fp8_op(x, W, bias, C, M, N, K, scratch);
+    fp8_op_adapter(o, A, B, rank, scale, a_st, bs, t);
+    return launch_fp8_op(o, epilogue, (hipStream_t)stream);
 }
 
 // s2v_op_ff_fp8 with an adapter on both linears, as the fp8 engines run a block's FeedForward with S2V_LORA_FP8_BRANCH: FF1's branch reads the
@@ -2174,42 +2153,14 @@ extern "C" int s2v_op_ff_fp8_lora(const void* x, const void* w1, const void* b1,
     char* p = (char*)scratch;
     unsigned char* hq = (unsigned char*)p;
     unsigned char* hsc = hq + m * f;
-    char *t2 = p + o_t2, *t1 = p + o_t1, *xq = p + o_xq, *w1q = p + o_w1q, *w2q = p + o_w2q, *hb = p + o_hb;
-    float *xs = (float*)(p + o_xs), *hs_row = (float*)(p + o_hrow), *w1s = (float*)(p + o_w1s), *w2s = (float*)(p + o_w2s);
-    char *a1 = p + o_a1, *bs1 = p + o_bs1, *a2 = p + o_a2, *bs2 = p + o_bs2;
-    S2V_TRY(launch_quant_rows_fp8(x, D, M, D, xq, xs, st));
-    S2V_TRY(launch_quant_rows_fp8(w1, D, F, D, w1q, w1s, st));
-    S2V_TRY(launch_quant_rows_fp8(w2, F, D, F, w2q, w2s, st));
-    S2V_TRY(launch_lora_pack_a(A1, rank, (int)R, D, a1, D, S2V_BF16, st));
-    S2V_TRY(launch_lora_pack_b(B1, rank, (int)R, F, scale, bs1, R, S2V_BF16, st));
-    S2V_TRY(launch_lora_pack_a(A2, rank, (int)R, F, a2, F, S2V_BF16, st));
-    S2V_TRY(launch_lora_pack_b(B2, rank, (int)R, D, scale, bs2, R, S2V_BF16, st));
-    LoraDownArgs d1{};
-    d1.x = x; d1.ldx = D; d1.A = a1; d1.lda = D; d1.out = t1; d1.ldo = (int)R; d1.M = M; d1.N = (int)R; d1.K = D;
-    S2V_TRY(launch_lora_down(d1, S2V_BF16, true, st));
-    GemmArgs g1{};
-    g1.A = xq; g1.lda = D; g1.W = w1q; g1.ldw = D; g1.bias = b1; g1.C = hb; g1.ldc = F; g1.M = M; g1.N = F; g1.K = D;
-    g1.a_rows_padded = M; g1.w_rows_padded = F; g1.a_scale = xs; g1.w_scale = w1s;
-    g1.lora_t = t1; g1.lora_ldt = (int)R; g1.lora_bs = bs1; g1.lora_r = (int)R;
-    if (mx) { g1.mx_out_q = hq; g1.mx_out_s = hsc; g1.mx_rows = M; }
-    S2V_TRY(launch_gemm_fp8(g1, EPI_BIAS_GELU, st));
-    LoraDownArgs d2{};
-    d2.A = a2; d2.lda = F; d2.out = t2; d2.ldo = (int)R; d2.M = M; d2.N = (int)R; d2.K = F;
-    GemmArgs g2{};
-    g2.A = hq; g2.lda = F; g2.W = w2q; g2.ldw = F; g2.bias = b2; g2.C = out; g2.ldc = D; g2.M = M; g2.N = D; g2.K = F;
-    g2.a_rows_padded = M; g2.w_rows_padded = D; g2.w_scale = w2s;
-    g2.lora_t = t2; g2.lora_ldt = (int)R; g2.lora_bs = bs2; g2.lora_r = (int)R;
-    if (mx) {
-        g2.mx_a_s = hsc; g2.mx_rows = M;
-        d2.x = hq; d2.ldx = F; d2.mx_s = hsc; d2.mx_rows = M;
-        S2V_TRY(launch_lora_down_mx(d2, st));
-    } else {
-        S2V_TRY(launch_quant_rows_fp8(hb, F, M, F, hq, hs_row, st));
-        g2.a_scale = hs_row;
-        d2.x = hb; d2.ldx = F;
-        S2V_TRY(launch_lora_down(d2, S2V_BF16, true, st));
-    }
-    return launch_gemm_fp8(g2, EPI_BIAS, st);
+    char* hb = p + o_hb;
+    Fp8Op f1 = fp8_op(x, w1, b1, hb, M, F, D, p + o_xq, p + o_w1q, (float*)(p + o_xs), (float*)(p + o_w1s));
+    Fp8Op f2 = fp8_op(hb, w2, b2, out, M, D, F, (char*)hq, p + o_w2q, (float*)(p + o_hrow), (float*)(p + o_w2s));
+    fp8_op_adapter(f1, A1, B1, rank, scale, p + o_a1, p + o_bs1, p + o_t1);
+    fp8_op_adapter(f2, A2, B2, rank, scale, p + o_a2, p + o_bs2, p + o_t2);
+    if (mx) { f1.mx_out_q = hq; f1.mx_out_s = hsc; f2.mx_s = hsc; }
+    S2V_TRY(launch_fp8_op(f1, EPI_BIAS_GELU, st));
+    return launch_fp8_op(f2, EPI_BIAS, st);
 }
 
 // Census of the attention kernel's deferred-maximum slow path since the last reset: slow = slow paths taken, total = (wave, KV tile) pairs run by
