@@ -58,7 +58,9 @@ _SIGS = {
     "s2v_set_rope": [_P, _P, _P, _P],
     "s2v_set_pos_embed": [_P, _P, _P],
     "s2v_set_conditioning": [_P, _P, _P, _P],
+    "s2v_set_conditioning_refs": [_P, _P, _P, _I32, _P],
     "s2v_transformer_forward": [_P, _P, _I64, _P, _P, _P],
+    "s2v_transformer_forward_videos": [_P, _P, _I32, _P, _P, _P],
     "s2v_block_forward": [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "s2v_attn_forward": [_P, _I32, _P, _P, _P, _P, _P],
     "s2v_attn_forward_with": [_P, _P, _I32, _P, _P, _P, _P, _P],

@@ -147,10 +147,15 @@ struct s2v_ctx {
     bool rope_paired = false;                // (get_3d_rotary_pos_embed: repeat_interleave(2)); the fused QKV epilogue needs it
     char* pos_tab;
     bool have_rope = false, have_pos = false, have_cond = false;
+    // one reference per video (s2v_set_conditioning_refs): sample j reads the tokens of reference j mod n_ref at e1_cur + (j mod n_ref) * e1_stride.
+    // n_ref = 1 is the workspace's e1; more references sit in e1x, allocated by that set-up call and freed with the workspace
+    int n_ref = 1;
+    char *e1_cur = nullptr, *e1x = nullptr;
+    int64_t e1_stride = 0, e1x_bytes = 0;
     float* t_dev = nullptr;
     SchedCoef* coef_dev = nullptr;
     // pinned staging ring for per-step scalars
-    struct Stage { float t[4]; SchedCoef c; };
+    struct Stage { float t[S2V_MAX_BATCH]; SchedCoef c; };
     Stage* ring = nullptr;
     int ring_pos = 0;
     // graph
@@ -313,7 +318,7 @@ static int create_attn_weights(s2v_ctx* c) {
 
 // the host-side scratch every context that runs launches needs: step scalars, the pinned staging ring, the capture stream
 static bool create_tail(s2v_ctx* c) {
-    hipMalloc((void**)&c->t_dev, 4 * sizeof(float));
+    hipMalloc((void**)&c->t_dev, S2V_MAX_BATCH * sizeof(float));
     hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef));
     hipHostMalloc((void**)&c->ring, sizeof(s2v_ctx::Stage) * RING);
     hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
@@ -479,6 +484,7 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->coef_dev) hipFree(c->coef_dev);
     if (c->t_dev) hipFree(c->t_dev);
     if (c->ws) hipFree(c->ws);
+    if (c->e1x) hipFree(c->e1x);
     if (c->attn_queue) hipFree(c->attn_queue);
     if (c->vt_amax) hipFree(c->vt_amax);
     if (c->attn_stats) hipFree(c->attn_stats);
@@ -491,6 +497,12 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
 // the captured step bakes in what it was captured under: whoever changes that drops the graph, and the next graph step captures again
 static void drop_graph(s2v_ctx* c) {
     if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+}
+
+// the references beyond the first (s2v_set_conditioning_refs) go with the workspace they were projected for
+static void drop_refs(s2v_ctx* c) {
+    if (c->e1x) hipFree(c->e1x);
+    c->e1x = nullptr; c->e1x_bytes = 0; c->n_ref = 1; c->e1_cur = nullptr;
 }
 
 // "transformer_blocks.<l>.norm{1,2}.linear.{weight,bias}"
@@ -663,6 +675,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     S2V_CHECK_HIP(hipDeviceSynchronize());
     drop_graph(c);
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
+    drop_refs(c);
     c->B = 0;
     c->shard = true; c->sp = world; c->sr = rank;
     c->sh_pending = 0;
@@ -674,13 +687,14 @@ static bool attn_mx_out(const s2v_ctx* c);
 extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int32_t H, int32_t W) {
     S2V_REQUIRE(c, "null context");
     S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WEIGHTS, "s2v_set_geometry: an attention-weights context (S2V_CTX_ATTN_WEIGHTS) never carves a workspace");
-    S2V_REQUIRE(B >= 1 && B <= 4, "s2v_set_geometry: batch must be 1..4");
+    S2V_REQUIRE(B >= 1 && B <= S2V_MAX_BATCH, "s2v_set_geometry: batch must be 1..8 (S2V_MAX_BATCH: the CFG pairs of at most four videos per call)");
     S2V_REQUIRE(T >= 0 && F >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "s2v_set_geometry: bad geometry");
     if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
     if (c->shard) S2V_REQUIRE(F * (H / 2) * (W / 2) >= c->sp, "s2v_set_geometry: every rank of a shard needs at least one video row");
     S2V_CHECK_HIP(hipDeviceSynchronize());
     drop_graph(c);
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }
+    drop_refs(c);
     c->B = B; c->T = T; c->F = F; c->H = H; c->W = W;
     c->R = (H / 2) * (W / 2);
     c->V = F * c->R;
@@ -754,6 +768,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     S2V_CHECK_HIP(hipMemset(c->ws, 0, c->ws_bytes));
     char* w = c->ws;
     c->X = w + oX; c->Xn = w + oXn; c->QKV = w + oQKV; c->Hb = w + oH; c->VT = w + oVT; c->e0 = w + oe0; c->e1 = w + oe1;
+    c->e1_cur = c->e1; c->e1_stride = rup(c->gR + 128, 128) * D * E;
     c->patches = w + opat; c->tailn = w + otail; c->proj = w + oproj; c->mod = w + omod; c->tmp_te = w + ote;
     c->emb = w + oemb; c->noise_pred = w + onp; c->rope_cos = (float*)(w + ocos); c->rope_sin = (float*)(w + osin);
     c->pos_tab = w + opos; c->rope_pk = (float*)(w + opk); c->rope_paired = false;
@@ -917,36 +932,86 @@ static int linear_fp8(s2v_ctx* c, const GemmArgs& g0, int epi, const char* wq, c
     return launch_gemm_fp8(g, epi, st);
 }
 
-extern "C" int s2v_set_conditioning(s2v_ctx* c, const void* text_dev, const void* ref_latent_dev, s2v_stream stream) {
-    S2V_REQUIRE(c && c->ws && c->finalized, "s2v_set_conditioning: geometry and weights must be set first");
-    S2V_REQUIRE(text_dev && ref_latent_dev, "s2v_set_conditioning: null input");
+extern "C" int s2v_set_conditioning_refs(s2v_ctx* c, const void* text_dev, const void* ref_latents_dev, int32_t n_ref, s2v_stream stream) {
+    S2V_REQUIRE(c && c->ws && c->finalized, "s2v_set_conditioning_refs: geometry and weights must be set first");
+    S2V_REQUIRE(text_dev && ref_latents_dev, "s2v_set_conditioning_refs: null input");
+    const int B = c->B;
+    S2V_REQUIRE(n_ref == 1 || n_ref == B || (B % 2 == 0 && n_ref == B / 2),
+                "s2v_set_conditioning_refs: n_ref must be 1 (one reference for every sample), B / 2 (one per video of [negative x b | positive x b]) "
+                "or B (one per sample): sample j takes reference j mod n_ref");
     hipStream_t st = (hipStream_t)stream;
     const int D = c->D;
+    const int64_t E = c->esz;
+    // where the reference tokens live: the workspace's e1 for one reference, a buffer of n_ref of them otherwise.  The captured step reads
+    // the address and the mapping: a change of either drops it
+    char* e1 = c->e1;
+    if (n_ref > 1) {
+        const int64_t need = n_ref * c->e1_stride;
+        if (c->e1x_bytes < need) {
+            S2V_CHECK_HIP(hipDeviceSynchronize());
+            if (c->e1x) hipFree(c->e1x);
+            c->e1x = nullptr; c->e1x_bytes = 0;
+            if (c->e1_cur != c->e1) { c->e1_cur = c->e1; c->n_ref = 1; c->have_cond = false; drop_graph(c); }
+            S2V_CHECK_HIP(hipMalloc((void**)&c->e1x, need));
+            S2V_CHECK_HIP(hipMemset(c->e1x, 0, need));
+            c->e1x_bytes = need;
+        }
+        e1 = c->e1x;
+    }
+    if (e1 != c->e1_cur || n_ref != c->n_ref) drop_graph(c);
+    c->e1_cur = e1; c->n_ref = n_ref;
+    c->have_cond = false;
     // text_proj (cogvideox_transformer_3d.py:494).  The MFMA kernel stages 128-row tiles, so the operand is first
     // copied into the (padded, zero-initialised) Hb scratch.
     const int TX = c->cfg.text_embed_dim;
     if (c->T > 0) {
-        if (c->shard) {  // the full [B][gT] embeddings in, this rank's T_r rows of each sample kept
-            for (int b = 0; b < c->B; ++b)
-                S2V_TRY(launch_convert2d((const char*)text_dev + ((int64_t)b * c->gT + c->t0) * TX * c->esz, c->dtype, TX,
-                                         c->Hb + (int64_t)b * c->T * TX * c->esz, c->dtype, TX, c->T, TX, st));
-        } else {
-            S2V_TRY(launch_convert2d(text_dev, c->dtype, TX, c->Hb, c->dtype, TX, (int64_t)c->B * c->T, TX, st));
-        }
         GemmArgs g{};
         g.A = c->Hb; g.lda = TX; g.W = c->text_w; g.ldw = TX; g.bias = c->text_b;
-        g.C = c->e0; g.ldc = D; g.M = c->B * c->T; g.N = D; g.K = TX;
-        S2V_TRY(linear(c, g, EPI_BIAS, st));
+        g.C = c->e0; g.ldc = D; g.N = D; g.K = TX;
+        if (B > 2 && B % 2 == 0 && !c->shard) {
+            // several videos: the [negative | positive] pair of each video is projected by a launch of a one-video call's shape (M = 2 T
+            // rows: tile and row tail do not depend on how many videos share the call), into X as scratch, then moved to its two places of
+            // e0.  Split K is the one thing the shape does not settle: gemm_plan splits only where the GEOMETRY carved a split-K workspace
+            // (sk_tiles, from B * Ntok), so at a size where the one-video geometry has one and the batched one has none (configs[0]) this
+            // K = text_embed_dim projection sums in another order than it does alone; everywhere else the bits are the one-video call's
+            const int b = B / 2;
+            const int64_t tb = (int64_t)c->T * TX * E, eb = (int64_t)c->T * D * E;
+            g.C = c->X; g.M = 2 * c->T;
+            for (int v = 0; v < b; ++v) {
+                for (int h = 0; h < 2; ++h)
+                    S2V_TRY(launch_convert2d((const char*)text_dev + (int64_t)(v + h * b) * tb, c->dtype, TX, c->Hb + h * tb, c->dtype, TX, c->T, TX, st));
+                S2V_TRY(linear(c, g, EPI_BIAS, st));
+                for (int h = 0; h < 2; ++h)
+                    S2V_TRY(launch_copy_rows(c->X + h * eb, D, nullptr, 0, c->e0 + (int64_t)(v + h * b) * eb, D, c->T, D, c->dtype, st));
+            }
+        } else {
+            if (c->shard) {  // the full [B][gT] embeddings in, this rank's T_r rows of each sample kept
+                for (int b = 0; b < B; ++b)
+                    S2V_TRY(launch_convert2d((const char*)text_dev + ((int64_t)b * c->gT + c->t0) * TX * c->esz, c->dtype, TX,
+                                             c->Hb + (int64_t)b * c->T * TX * c->esz, c->dtype, TX, c->T, TX, st));
+            } else {
+                S2V_TRY(launch_convert2d(text_dev, c->dtype, TX, c->Hb, c->dtype, TX, (int64_t)B * c->T, TX, st));
+            }
+            g.M = B * c->T;
+            S2V_TRY(linear(c, g, EPI_BIAS, st));
+        }
     }
-    // reference image latent -> patch tokens (cogvideox_transformer_3d.py:496-501); identical for every sample
+    // reference image latents -> patch tokens (cogvideox_transformer_3d.py:496-501), one launch per reference: what a one-video call runs
     const int K = c->cfg.in_channels * 4;
-    S2V_TRY(launch_patchify(ref_latent_dev, 0, 1, 1, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st));
-    GemmArgs g{};
-    g.A = c->patches + (int64_t)c->r0 * K * c->esz; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;  // shard: this rank's R_r patches
-    g.C = c->e1; g.ldc = D; g.M = c->R; g.N = D; g.K = K;
-    if (c->R > 0) S2V_TRY(linear(c, g, EPI_BIAS, st));
+    const int64_t ref_elems = (int64_t)c->cfg.in_channels * c->H * c->W;
+    for (int r = 0; r < n_ref; ++r) {
+        S2V_TRY(launch_patchify((const char*)ref_latents_dev + r * ref_elems * E, 0, 1, 1, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st));
+        GemmArgs g{};
+        g.A = c->patches + (int64_t)c->r0 * K * c->esz; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;  // shard: this rank's R_r patches
+        g.C = e1 + r * c->e1_stride; g.ldc = D; g.M = c->R; g.N = D; g.K = K;
+        if (c->R > 0) S2V_TRY(linear(c, g, EPI_BIAS, st));
+    }
     c->have_cond = true;
     return 0;
+}
+
+extern "C" int s2v_set_conditioning(s2v_ctx* c, const void* text_dev, const void* ref_latent_dev, s2v_stream stream) {
+    return s2v_set_conditioning_refs(c, text_dev, ref_latent_dev, 1, stream);
 }
 
 // ---- one transformer block on the packed residual buffer X ------------------------------------------------
@@ -1215,7 +1280,8 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
 
 // time embedding, every modulation of the step, and the residual streams [text | ref | video] of each sample in X (a shard: this rank's rows
 // [T_r | R_r | V_r]; the latent is patchified whole and the rank's V_r patch rows embedded)
-static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* t_dev, hipStream_t st) {
+// latents: sample b reads the latent at (b mod n_lat) * lat_bstride elements (n_lat = 0: at b * lat_bstride)
+static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, hipStream_t st) {
     const int D = c->D, B = c->B;
     const int64_t E = c->esz;
     // 1. timestep embedding + every AdaLN modulation of the step in one batched GEMV (temb is block-invariant)
@@ -1226,11 +1292,11 @@ static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, c
     }
     // 2. residual streams: [text | ref | video] per sample
     const int K = c->cfg.in_channels * 4;
-    S2V_TRY(launch_patchify(latents, lat_bstride, B, c->F, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st));
+    S2V_TRY(launch_patchify(latents, lat_bstride, B, c->F, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st, n_lat));
     for (int b = 0; b < B; ++b) {
         char* xb = c->X + (int64_t)b * c->Ntok * D * E;
         S2V_TRY(launch_copy_rows(c->e0 + (int64_t)b * c->T * D * E, D, nullptr, 0, xb, D, c->T, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows(c->e1, D, nullptr, 0, xb + (int64_t)c->T * D * E, D, c->R, D, c->dtype, st));
+        S2V_TRY(launch_copy_rows(c->e1_cur + (b % c->n_ref) * c->e1_stride, D, nullptr, 0, xb + (int64_t)c->T * D * E, D, c->R, D, c->dtype, st));
         char* xv = xb + (int64_t)(c->T + c->R) * D * E;
         GemmArgs g{};
         g.A = c->patches + ((int64_t)b * c->gV + c->v0) * K * E; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;
@@ -1258,7 +1324,7 @@ static int tail_proj(s2v_ctx* c, hipStream_t st) {
     return linear(c, g, EPI_BIAS, st);
 }
 
-static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* t_dev, void* out,
+static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, void* out,
                         hipStream_t st) {
     S2V_REQUIRE(c->ws && c->finalized && c->have_cond, "transformer_forward: geometry, weights and conditioning required");
     S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "transformer_forward: RoPE tables missing (s2v_set_rope)");
@@ -1266,7 +1332,7 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, co
     S2V_REQUIRE(!c->shard, "transformer_forward: a shard context (s2v_set_shard) runs the staged step only (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     const int D = c->D;
     const int64_t E = c->esz;
-    S2V_TRY(embed_streams(c, latents, lat_bstride, t_dev, st));
+    S2V_TRY(embed_streams(c, latents, lat_bstride, n_lat, t_dev, st));
     // 3. blocks
     for (int l = 0; l < c->L; ++l)
         S2V_TRY(run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st));
@@ -1280,7 +1346,14 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, co
 extern "C" int s2v_transformer_forward(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* timesteps_dev,
                                        void* out, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward: null argument");
-    return forward_impl(c, latents, lat_bstride, timesteps_dev, out, (hipStream_t)stream);
+    return forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream);
+}
+
+extern "C" int s2v_transformer_forward_videos(s2v_ctx* c, const void* latents, int32_t n_lat, const float* timesteps_dev, void* out,
+                                              s2v_stream stream) {
+    S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward_videos: null argument");
+    S2V_REQUIRE(c->ws && n_lat >= 1 && c->B % n_lat == 0, "s2v_transformer_forward_videos: n_lat must divide the geometry's batch (sample j embeds latent j mod n_lat)");
+    return forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream);
 }
 
 // the residual streams of every sample between the caller's dense tensors (s0: n0 rows, s1: n1 rows, video: V rows per sample; n0 + n1 = T + R)
@@ -1500,7 +1573,7 @@ extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, floa
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
     S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
     *arena = c->arena ? c->arena_bytes : 0;
-    *workspace = c->ws ? c->ws_bytes : 0;
+    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes : 0;
     return 0;
 }
 
@@ -1538,9 +1611,9 @@ extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const
 static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_host, hipStream_t st) {
     s2v_ctx::Stage& sg = c->ring[c->ring_pos];
     c->ring_pos = (c->ring_pos + 1) % RING;
-    for (int i = 0; i < 4; ++i) sg.t[i] = timestep;
+    for (int i = 0; i < S2V_MAX_BATCH; ++i) sg.t[i] = timestep;
     fill_coef(sg.c, *coef_host);
-    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * 4, hipMemcpyHostToDevice, st));
+    S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * S2V_MAX_BATCH, hipMemcpyHostToDevice, st));
     S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
     return 0;
 }
@@ -1567,23 +1640,26 @@ static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body
     return 0;
 }
 
-// (CFG +) scheduler step on the context's noise_pred with the coefficients stage_step uploaded, latents updated in place
-static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, int cfg_flag, hipStream_t st) {
+// (CFG +) scheduler step on the context's noise_pred with the coefficients stage_step uploaded, latents updated in place.  nvid videos:
+// latents / x0_hist / noise [nvid][F,C,H,W] and noise_pred [negative x nvid | positive x nvid], so the conditional half starts n elements in
+static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, int cfg_flag, hipStream_t st, int nvid = 1) {
     SchedArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
-    a.n = (int64_t)c->F * c->cfg.out_channels * c->H * c->W; a.cfg = cfg_flag; a.coef = c->coef_dev;
+    a.n = (int64_t)nvid * c->F * c->cfg.out_channels * c->H * c->W; a.cfg = cfg_flag; a.coef = c->coef_dev;
     return launch_sched_step(a, c->dtype, st);
 }
 
 static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
-    S2V_TRY(forward_impl(c, latents, 0, c->t_dev, c->noise_pred, st));
-    return sched_on_pair(c, latents, x0_hist, noise, c->B == 2 ? 1 : 0, st);
+    // b videos: sample j of [negative x b | positive x b] embeds video j mod b straight from `latents` (one video: the stride of 0 it always had)
+    const int b = c->B >= 2 ? c->B / 2 : 1;
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st));
+    return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b);
 }
 
 extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
                                 float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
     S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_step: null argument");
-    S2V_REQUIRE(c->ws && (c->B == 1 || c->B == 2), "s2v_denoise_step: geometry with B = 1 or 2 (CFG pair) required");
+    S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
     S2V_REQUIRE(coef_host->kind == 0 || (noise && x0_hist), "s2v_denoise_step: DPM needs noise and x0_hist");
     S2V_REQUIRE(!c->shard, use_graph ? "s2v_denoise_step: hipGraph capture is not supported for a shard context (s2v_set_shard): its step is staged around "
@@ -1610,14 +1686,14 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
     // a begin is pending only once its forward is on the stream: whatever fails below, s2v_denoise_split_end finds none
     if (c) c->split_kind = -1;
     S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_split_begin: null argument");
-    S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required");
+    S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required; a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_split_begin: in/out channels must match");
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timestep, coef_host, st));
     char* out = c->noise_pred + (int64_t)slot * pair_half_bytes(c);
-    auto forward = [&](hipStream_t s) { return forward_impl(c, latents, 0, c->t_dev, out, s); };
+    auto forward = [&](hipStream_t s) { return forward_impl(c, latents, 0, 0, c->t_dev, out, s); };
     S2V_TRY(use_graph ? launch_captured(c, GraphKey{(void*)latents, nullptr, nullptr, slot}, st, forward) : forward(st));
     c->split_kind = coef_host->kind;
     return 0;
@@ -1632,7 +1708,7 @@ extern "C" int s2v_cfg_pair(s2v_ctx* c, void** dev_ptr, int64_t* bytes_per_half)
 
 extern "C" int s2v_denoise_split_end(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, s2v_stream stream) {
     S2V_REQUIRE(c && latents, "s2v_denoise_split_end: null argument");
-    S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_end: a geometry with B = 1 is required (s2v_denoise_split_begin ran before)");
+    S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_end: a geometry with B = 1 is required (s2v_denoise_split_begin ran before); a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     // the step's coefficients live on the device since s2v_denoise_split_begin: one end per begin, and a DPM step brings its noise and x0 history
     S2V_REQUIRE(c->split_kind >= 0, "s2v_denoise_split_end: no s2v_denoise_split_begin is pending (its coefficients are the step's)");
     S2V_REQUIRE(c->split_kind == 0 || (noise && x0_hist), "s2v_denoise_split_end: DPM needs noise and x0_hist");
@@ -1795,7 +1871,7 @@ extern "C" int s2v_shard_step_begin(s2v_ctx* c, const void* latents, float times
                                     s2v_stream stream) {
     S2V_REQUIRE(c && latents && coef_host && pending, "s2v_shard_step_begin: null argument");
     S2V_REQUIRE(c->shard, "s2v_shard_step_begin: not a shard context (s2v_set_shard)");
-    S2V_REQUIRE(c->ws && (c->B == 1 || c->B == 2), "s2v_shard_step_begin: geometry with B = 1 or 2 (CFG pair) required");
+    S2V_REQUIRE(c->ws && (c->B == 1 || c->B == 2), "s2v_shard_step_begin: geometry with B = 1 or 2 (CFG pair) required; a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(c->finalized && c->have_cond, "s2v_shard_step_begin: weights and conditioning required");
     S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "s2v_shard_step_begin: RoPE tables missing (s2v_set_rope)");
     S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "s2v_shard_step_begin: sincos table missing (s2v_set_pos_embed)");
@@ -1803,7 +1879,7 @@ extern "C" int s2v_shard_step_begin(s2v_ctx* c, const void* latents, float times
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timestep, coef_host, st));
     c->sh_pending = 0;
-    S2V_TRY(embed_streams(c, latents, 0, c->t_dev, st));
+    S2V_TRY(embed_streams(c, latents, 0, 0, c->t_dev, st));
     S2V_TRY(shard_front(c, 0, st));
     c->split_kind = coef_host->kind;
     c->sh_layer = 0;

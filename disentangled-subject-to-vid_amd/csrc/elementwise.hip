@@ -806,8 +806,13 @@ static int gemv_rows_reg(const void* in, int B, const void* W, const void* bias,
 template <typename T>
 static int gemv_rows(const void* in, int B, int K, const void* W, const void* bias, int64_t rows, void* out,
                      bool pre_silu, hipStream_t st, bool rowwise = false) {
-    S2V_REQUIRE(B <= 4, "gemv_rows: batch must be <= 4");
     S2V_REQUIRE(K % Vec16<T>::N == 0, "gemv_rows: K must be a multiple of the 16-byte vector width");
+    if (B > GEMV_MAX_B) {  // the kernels hold GEMV_MAX_B accumulators per row: more samples run as chunks, in [b][K] -> out [b][rows]
+        for (int b0 = 0; b0 < B; b0 += GEMV_MAX_B)
+            S2V_TRY(gemv_rows<T>((const T*)in + (size_t)b0 * K, std::min(GEMV_MAX_B, B - b0), K, W, bias, rows, (T*)out + (size_t)b0 * rows,
+                                 pre_silu, st, rowwise));
+        return 0;
+    }
     if (pre_silu && rows >= 4096 && !rowwise) {  // the modulation stack (K = time_embed_dim): one or two chunks per lane
         if (K == 64 * Vec16<T>::N) return gemv_rows_reg<T, true, 1>(in, B, W, bias, rows, out, st);
         if (K == 128 * Vec16<T>::N) return gemv_rows_reg<T, true, 2>(in, B, W, bias, rows, out, st);
@@ -846,7 +851,7 @@ int launch_mod_gemv(const void* emb, int B, int temb_dim, const void* W, const v
 
 // ---------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ void patchify_k(const T* lat, int64_t lat_bstride, int Bn, int F, int C, int H, int W, T* out) {
+__global__ void patchify_k(const T* lat, int64_t lat_bstride, int n_lat, int Bn, int F, int C, int H, int W, T* out) {
     // out[(((b*F + f)*hp + y)*wp + x)][c*4 + py*2 + px] = lat[b][f][c][2y+py][2x+px]
     // (the im2col operand of the 2x2 stride-2 patch conv, embeddings.py:414-419)
     const int hp = H / 2, wp = W / 2, K = C * 4;
@@ -859,14 +864,15 @@ __global__ void patchify_k(const T* lat, int64_t lat_bstride, int Bn, int F, int
     const int y = (int)((tok / wp) % hp);
     const int f = (int)((tok / ((int64_t)wp * hp)) % F);
     const int64_t b = tok / ((int64_t)wp * hp * F);
+    const int64_t bl = n_lat > 0 ? b % n_lat : b;  // n_lat videos shared by Bn samples
     const int c = k >> 2, py = (k >> 1) & 1, px = k & 1;
-    out[i] = lat[b * lat_bstride + (((int64_t)f * C + c) * H + 2 * y + py) * W + 2 * x + px];
+    out[i] = lat[bl * lat_bstride + (((int64_t)f * C + c) * H + 2 * y + py) * W + 2 * x + px];
 }
 int launch_patchify(const void* lat, int64_t lat_bstride, int Bn, int F, int C, int H, int W, void* out, int dtype,
-                    hipStream_t st) {
+                    hipStream_t st, int n_lat) {
     const int64_t total = (int64_t)Bn * F * (H / 2) * (W / 2) * C * 4;
     dim3 grid((unsigned)((total + 255) / 256));
-    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(patchify_k<T>, grid, dim3(256), 0, st, (const T*)lat, lat_bstride, Bn, F, C, H, W, (T*)out))
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(patchify_k<T>, grid, dim3(256), 0, st, (const T*)lat, lat_bstride, n_lat, Bn, F, C, H, W, (T*)out))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

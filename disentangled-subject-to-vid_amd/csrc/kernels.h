@@ -279,13 +279,16 @@ int launch_v_transpose(const void* qkv, int ld_qkv, int B, int H, int Ntok, void
 int launch_time_embed(const float* t_dev, int B, int D, const void* w1, const void* b1, const void* w2, const void* b2,
                       int temb_dim, void* tmp /*[B,temb]*/, void* emb_out /*[B,temb]*/, int dtype, hipStream_t st);
 // out[j][b][:] = W_j . silu(emb[b]) + bias_j for a batch of stacked linears: W [rows_total, temb], bias [rows_total]
+// (a batch over GEMV_MAX_B runs in chunks of at most GEMV_MAX_B samples, each sample's sum the chain it is alone)
+#define GEMV_MAX_B 4
 int launch_mod_gemv(const void* emb, int B, int temb_dim, const void* W, const void* bias, int64_t rows_total,
                     void* out /*[B][rows_total]*/, int dtype, hipStream_t st, bool rowwise = false);
 
 // latents [Bn, F, C, H, W] -> patches [Bn*F*(H/2)*(W/2), C*4] with feature order (c, py, px);
-// lat_bstride = elements between samples (0 => every sample reads the same latent: the CFG pair)
+// lat_bstride = elements between samples (0 => every sample reads the same latent: the CFG pair); n_lat > 0: sample b reads latent
+// b mod n_lat (the CFG pairs of n_lat videos, [negative x n_lat | positive x n_lat], straight from the [n_lat] latents)
 int launch_patchify(const void* lat, int64_t lat_bstride, int Bn, int F, int C, int H, int W, void* out, int dtype,
-                    hipStream_t st);
+                    hipStream_t st, int n_lat = 0);
 // y [B*V, C*4] (feature c*4+py*2+px) -> out [B, F, C, H, W]; rows of y start at y_row0 with batch stride y_bstride rows
 int launch_unpatchify(const void* y, int ldy, int64_t y_bstride, void* out, int B, int F, int C, int H, int W, int dtype,
                       hipStream_t st);

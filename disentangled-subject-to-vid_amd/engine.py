@@ -275,6 +275,8 @@ class S2VEngine:
         _lib.check(_lib.lib().s2v_fp8_qk_active(self._h, ctypes.byref(on)))
         return bool(on.value)
 
+    MAX_BATCH = 8   # S2V_MAX_BATCH (include/s2v_hip.h): the CFG pairs of at most four videos per call
+
     def set_geometry(self, B, T, F, H, W):
         new = self.geometry != (B, T, F, H, W)
         _lib.check(_lib.lib().s2v_set_geometry(self._h, B, T, F, H, W))
@@ -341,14 +343,24 @@ class S2VEngine:
             self.set_pos_embed(torch.from_numpy(pe))
 
     def set_conditioning(self, text, ref_latent):
+        """text [B,T,text_embed_dim]; ref_latent [n_ref,1,C,H,W] with n_ref in {1, B/2, B}: sample j of the batch takes reference j mod n_ref
+        (1: one subject for every sample; B/2: the reference's eval=True duplication over [negative x b | positive x b]; B: one per sample)"""
         text = text.to(self.device, self.dtype).contiguous()
         ref = ref_latent.to(self.device, self.dtype).contiguous()
         B, T, F, H, W = self.geometry
         if tuple(text.shape) != (B, T, self.cfg.text_embed_dim):
             raise _lib.S2VError(f"text embeddings must be [{B},{T},{self.cfg.text_embed_dim}], got {tuple(text.shape)}")
-        if ref.numel() != self.cfg.in_channels * H * W:
-            raise _lib.S2VError("ref_img_states must be [1,1,C,H,W] with the geometry's H, W")
-        _lib.check(_lib.lib().s2v_set_conditioning(self._h, _lib.ptr(text), _lib.ptr(ref), _lib.stream_ptr()))
+        per_ref = self.cfg.in_channels * H * W
+        if ref.numel() % per_ref != 0 or (ref.numel() != per_ref and (ref.ndim != 5 or ref.shape[0] * per_ref != ref.numel())):
+            raise _lib.S2VError("ref_img_states must be [n_ref,1,C,H,W] with the geometry's H, W")
+        n_ref = ref.numel() // per_ref
+        if n_ref not in {1, B} | ({B // 2} if B % 2 == 0 else set()):
+            raise _lib.S2VError(f"ref_img_states has {n_ref} rows: n_ref must be 1, B/2 or B for a batch of {B} samples "
+                                f"(sample j takes reference j mod n_ref)")
+        if n_ref == 1:
+            _lib.check(_lib.lib().s2v_set_conditioning(self._h, _lib.ptr(text), _lib.ptr(ref), _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib().s2v_set_conditioning_refs(self._h, _lib.ptr(text), _lib.ptr(ref), n_ref, _lib.stream_ptr()))
         torch.cuda.current_stream().synchronize()
         self._cond_args = (text, ref) if self.cfg.lora_runtime_rank > 0 else None
         self._bump("cond")
@@ -363,13 +375,21 @@ class S2VEngine:
 
     # ---- compute -------------------------------------------------------------------------------------------
     def forward(self, latents, timesteps, shared_latent=False):
-        """CogVideoXTransformer3DModel.forward seam: latents [B,F,C,H,W] (or [1,F,C,H,W] with shared_latent)."""
+        """CogVideoXTransformer3DModel.forward seam: latents [B,F,C,H,W]; with shared_latent [n,F,C,H,W], n dividing B: sample j embeds latent
+        j mod n (n = 1: every sample the same latent; n = B/2: the CFG batch cat([latents] * 2) of B/2 videos without the copy)."""
         B, T, F, H, W = self.geometry
         lat = latents.to(self.device, self.dtype).contiguous()
+        n_lat = lat.numel() // (F * self.cfg.in_channels * H * W)
+        if lat.numel() != n_lat * F * self.cfg.in_channels * H * W or n_lat < 1 or (B % n_lat if shared_latent else n_lat != B):
+            raise _lib.S2VError(f"latents {tuple(lat.shape)} do not fit the geometry: [{B},{F},{self.cfg.in_channels},{H},{W}]"
+                                + (f", or with shared_latent [n,...] with n dividing {B}" if shared_latent else ""))
         t = timesteps.to(self.device, torch.float32).contiguous()
         if t.numel() != B:
             t = t.reshape(-1)[:1].expand(B).contiguous()
         out = torch.empty((B, F, self.cfg.out_channels, H, W), dtype=self.dtype, device=self.device)
+        if shared_latent and n_lat > 1:
+            _lib.check(_lib.lib().s2v_transformer_forward_videos(self._h, _lib.ptr(lat), n_lat, _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr()))
+            return out
         stride = 0 if shared_latent else F * self.cfg.in_channels * H * W
         _lib.check(_lib.lib().s2v_transformer_forward(self._h, _lib.ptr(lat), stride, _lib.ptr(t), _lib.ptr(out),
                                                       _lib.stream_ptr()))
@@ -414,9 +434,18 @@ class S2VEngine:
         self.attn_p_format = fmt
 
     def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
-        """one iteration of the denoise loop, latents [1,F,C,H,W] (model dtype) updated in place"""
+        """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
+        [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
+        B, T, F, H, W = self.geometry
+        if B > 2:
+            if B % 2:
+                raise _lib.S2VError(f"denoise_step: a geometry of {B} samples is no whole number of CFG pairs")
+            want = (B // 2, F, self.cfg.in_channels, H, W)
+            for name, x in (("latents", latents), ("x0_hist", x0_hist), ("noise", noise)):
+                if x is not None and (tuple(x.shape) != want or not x.is_contiguous()):
+                    raise _lib.S2VError(f"denoise_step: {name} must be contiguous {list(want)} for {B // 2} videos per call, got {list(x.shape)}")
         auto = self._attn_auto_pending
         if auto:
             self.attn_slow_stats(reset=True)

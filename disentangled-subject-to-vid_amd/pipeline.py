@@ -18,7 +18,21 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .schedulers import CogVideoXDPMScheduler
+from .schedulers import CogVideoXDPMScheduler, randn_videos  # noqa: F401
+
+
+MAX_VIDEOS = 4   # videos per call: the library runs at most S2V_MAX_BATCH = 8 samples, the CFG pairs of four videos
+
+
+def expand_prompts(embeds, num_videos_per_prompt=1):
+    """[P,T,D] -> [P * num_videos_per_prompt,T,D], prompt-major, as _get_t5_prompt_embeds does (pipeline_cogvideox.py:230-233)"""
+    P, T, _ = embeds.shape
+    return embeds.repeat(1, num_videos_per_prompt, 1).view(P * num_videos_per_prompt, T, -1)
+
+
+def cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt=1):
+    """the transformer's text batch [negative x b | positive x b] (custom_cogvideox_pipe.py:196), b = P * num_videos_per_prompt"""
+    return torch.cat([expand_prompts(negative_prompt_embeds, num_videos_per_prompt), expand_prompts(prompt_embeds, num_videos_per_prompt)], dim=0)
 
 
 class S2VPipeline:
@@ -44,15 +58,42 @@ class S2VPipeline:
             raise ValueError("`prompt_embeds` and `negative_prompt_embeds` must have the same shape when passed "
                              f"directly, but got {prompt_embeds.shape} != {negative_prompt_embeds.shape}.")
 
-    def prepare_latents(self, num_frames, height, width, dtype, device, generator, latents=None):
-        shape = (1, (num_frames - 1) // self.vae_scale_factor_temporal + 1, self.transformer.config.in_channels,
+    def prepare_latents(self, num_frames, height, width, dtype, device, generator, latents=None, batch=1):
+        shape = (batch, (num_frames - 1) // self.vae_scale_factor_temporal + 1, self.transformer.config.in_channels,
                  height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
         if latents is None:
-            gdev = generator.device if generator is not None else device
-            latents = torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
+            latents = randn_videos(shape, generator, device, dtype)
         else:
             latents = latents.to(device)
         return latents * self.scheduler.init_noise_sigma
+
+    @staticmethod
+    def check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents=None, generator=None, video=None, cfg_parallel=None,
+                    ulysses=None):
+        """the number of videos b = prompts x num_videos_per_prompt of a call, after everything that limits it has been checked (no device
+        is touched): 1 <= b <= MAX_VIDEOS, ref_img_states with 1 or b rows, latents with b rows, a generator list of b, and the paths that
+        stay one video per call"""
+        if prompt_embeds.ndim != 3:
+            raise ValueError(f"`prompt_embeds` must be [prompts, tokens, dim], got {tuple(prompt_embeds.shape)}")
+        if num_videos_per_prompt < 1:
+            raise ValueError(f"`num_videos_per_prompt` must be >= 1, got {num_videos_per_prompt}")
+        b = prompt_embeds.shape[0] * num_videos_per_prompt
+        if b > MAX_VIDEOS:
+            raise ValueError(f"{prompt_embeds.shape[0]} prompts x {num_videos_per_prompt} videos per prompt = {b} videos: at most {MAX_VIDEOS} videos "
+                             f"per call (the fused step runs the CFG pairs of up to {MAX_VIDEOS} videos, {2 * MAX_VIDEOS} samples)")
+        if ref_img_states.ndim != 5 or ref_img_states.shape[0] not in (1, b):
+            raise ValueError(f"`ref_img_states` must have one row per video ({b}) or one row shared by all videos, got {tuple(ref_img_states.shape)}")
+        if latents is not None and latents.shape[0] != b:
+            raise ValueError(f"`latents` has {latents.shape[0]} rows for {b} videos")
+        if isinstance(generator, (list, tuple)) and len(generator) != b:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {b}. "
+                             f"Make sure the batch size matches the length of the generators.")
+        if b > 1:
+            for name, arg in (("video", video), ("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+                if arg is not None:
+                    raise ValueError(f"`{name}` with {b} videos per call: several videos per call run as one batched step on one GPU; "
+                                     f"video-to-video, CFG-parallel and Ulysses stay one video per call")
+        return b
 
     @staticmethod
     def get_timesteps(num_inference_steps, timesteps, strength, order=1):
@@ -78,8 +119,13 @@ class S2VPipeline:
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
-                 video=None, strength=0.8):
-        """cfg_parallel: a dist.CfgPair -- this process runs ONE sample of the CFG pair (slot 0: negative prompt, slot 1: prompt) on its GPU and its
+                 video=None, strength=0.8, num_videos_per_prompt=1):
+        """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
+        make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
+        one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
+        generator k alone).  Every step runs the transformer on [negative x b | positive x b]; the result is [b,...].  video=, cfg_parallel=
+        and ulysses= stay one video per call.
+        cfg_parallel: a dist.CfgPair -- this process runs ONE sample of the CFG pair (slot 0: negative prompt, slot 1: prompt) on its GPU and its
         peer the other; every rank of the pair passes the SAME arguments (embeddings, reference latent, latents or an equally seeded generator) and
         returns the same latents / video bit for bit.  fused mode only.
         ulysses: a dist.UlyssesGroup -- the group's ranks share every step of this video (both samples of the CFG pair, the rows of each stream
@@ -90,6 +136,8 @@ class S2VPipeline:
         if strength < 0 or strength > 1:
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if video is not None:
+            if prompt_embeds is not None and prompt_embeds.ndim == 3 and ref_img_states is not None:  # several videos: refused before the VAE is asked for
+                self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, None, None, video)
             if latents is not None:
                 raise ValueError("Only one of `video` or `latents` should be provided")
             if self.vae is None:
@@ -112,14 +160,12 @@ class S2VPipeline:
                              "(video_generate.inference does it)")
         if ref_img_states is None:
             raise ValueError("Provide `ref_img_states` (the VAE latent of the reference image, [1, 1, C, H/8, W/8])")
-        if prompt_embeds.shape[0] != 1:
-            raise RuntimeError("one prompt per call: the transformer duplicates the reference tokens exactly x2 "
-                               "(cogvideox_transformer_3d.py:503-504)")
         if guidance_scale <= 1.0:
             raise RuntimeError("guidance_scale must be > 1: eval=True duplicates the reference tokens for the CFG pair")
+        b = self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents, generator, video, cfg_parallel, ulysses)
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
-        text = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(dev, dt)
+        text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)  # [negative x b | positive x b] (:196)
         sch.set_timesteps(num_inference_steps, device="cpu")
         timesteps = sch.timesteps
         if video is not None:
@@ -128,9 +174,11 @@ class S2VPipeline:
                 raise ValueError(f"strength {strength} keeps none of the {sch.num_inference_steps} timesteps")
             latents = self.prepare_video_latents(video, dt, dev, generator, timesteps[:1]).to(dt).contiguous()
         else:
-            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents).to(dt).contiguous()
+            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b).to(dt).contiguous()
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
         ref = ref_img_states.to(dev, dt)
+        # the seam's eval=True wants one reference row per video (:503-504); one shared row is repeated (the engine maps it itself)
+        ref_seam = ref if ref.shape[0] == b else ref.expand(b, -1, -1, -1, -1).contiguous()
         is_dpm = isinstance(sch, CogVideoXDPMScheduler)
         rope = ref_rope = None
         if tr.config.use_rotary_positional_embeddings:
@@ -153,7 +201,7 @@ class S2VPipeline:
         if fused:
             # CFG-parallel: B = 1 with this rank's half of [negative | positive] (custom_cogvideox_pipe.py:196) and the un-duplicated reference tokens
             my_text = text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1]
-            eng.set_geometry(2 if cfg_parallel is None else 1, text.shape[1], F, H, W)
+            eng.set_geometry(2 * b if cfg_parallel is None else 1, text.shape[1], F, H, W)
             eng.prepare_tables(height, width)
             eng.set_conditioning(my_text, ref)
             x0_hist = torch.zeros(latents.shape, dtype=torch.float32, device=dev) if is_dpm else None
@@ -183,8 +231,8 @@ class S2VPipeline:
             else:
                 x = torch.cat([latents] * 2)
                 x = sch.scale_model_input(x, t)
-                noise_pred = tr(hidden_states=x, encoder_hidden_states=text, ref_img_states=ref,
-                                timestep=t.expand(2), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
+                noise_pred = tr(hidden_states=x, encoder_hidden_states=text, ref_img_states=ref_seam,
+                                timestep=t.expand(2 * b), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
                                 return_dict=False, eval=True)[0].float()
                 u, c = noise_pred.chunk(2)
                 noise_pred = u + g * (c - u)
@@ -233,6 +281,9 @@ class S2VPipeline:
 
     @staticmethod
     def _draw(buf, generator):
+        if isinstance(generator, (list, tuple)):  # video k's draw comes from generator k alone
+            buf.copy_(randn_videos(buf.shape, generator, buf.device, buf.dtype))
+            return
         gdev = generator.device.type if generator is not None else buf.device.type
         if gdev == "cpu":
             buf.copy_(torch.randn(buf.shape, generator=generator, dtype=buf.dtype))
@@ -240,5 +291,7 @@ class S2VPipeline:
             buf.normal_(generator=generator)
 
     def decode_latents(self, latents):
-        """pipeline_cogvideox.py:346-351"""
-        return self.vae.decode_latents(latents)
+        """pipeline_cogvideox.py:346-351; the VAE decodes one video per call: several videos are decoded one after the other"""
+        if latents.shape[0] == 1:
+            return self.vae.decode_latents(latents)
+        return torch.cat([self.vae.decode_latents(latents[k:k + 1].contiguous()) for k in range(latents.shape[0])], dim=0)

@@ -28,6 +28,18 @@ def _as_model(x, dtype):
     return float(t.to(dtype).to(torch.float32))
 
 
+def randn_videos(shape, generator, device, dtype):
+    """diffusers' randn_tensor, the ONE place a batch of videos is drawn: a list of generators draws every video [1,...] from its own
+    generator, one generator (or None) draws the whole [b,...] tensor at once; on the generator's device, returned on `device`"""
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != shape[0]:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of "
+                             f"{shape[0]}. Make sure the batch size matches the length of the generators.")
+        return torch.cat([randn_videos((1,) + tuple(shape[1:]), g, device, dtype) for g in generator], dim=0)
+    gdev = generator.device if generator is not None else device
+    return torch.randn(tuple(shape), generator=generator, device=gdev, dtype=dtype).to(device)
+
+
 class _SchedulerBase:
     order = 1
     init_noise_sigma = 1.0
@@ -165,11 +177,10 @@ class CogVideoXDPMScheduler(_SchedulerBase):
         c = self.coef(timestep, timestep_back, first, sample.dtype)
         # the reference draws randn once, and a second time on multistep steps (the first draw is then discarded)
         shape, dev = sample.shape, sample.device
-        gdev = generator.device.type if generator is not None else dev.type
-        noise = torch.randn(shape, generator=generator, device=gdev if gdev == "cpu" else dev, dtype=sample.dtype)
+
+        noise = randn_videos(shape, generator, dev, sample.dtype)
         if c.kind == 2:
-            noise = torch.randn(shape, generator=generator, device=gdev if gdev == "cpu" else dev, dtype=sample.dtype)
-        noise = noise.to(dev)
+            noise = randn_videos(shape, generator, dev, sample.dtype)
         hist = old_pred_original_sample.float().clone() if not first else None
         prev, x0 = self._run(c, model_output, sample, hist, noise)
         return (prev, x0)

@@ -103,8 +103,11 @@ class HipCogVideoXTransformer3DModel:
         if eval and B != 2 * ref_img_states.shape[0]:
             raise RuntimeError(f"Sizes of tensors must match: eval=True duplicates ref_img_states exactly x2 "
                                f"(:503-504) but hidden_states has batch {B}")
-        if ref_img_states.shape[0] != 1:
-            raise NotImplementedError("one reference image per call (what src/video_generate.py:35-38 provides)")
+        if B > S2VEngine.MAX_BATCH:
+            raise NotImplementedError(f"a batch of {B} samples: at most {S2VEngine.MAX_BATCH} per call (the CFG pairs of "
+                                      f"{S2VEngine.MAX_BATCH // 2} videos)")
+        # eval=True: ref_img_states [b] is duplicated over [negative x b | positive x b], sample j sees reference j mod b (:503-504);
+        # eval=False: one row per sample.  The engine maps sample j to reference j mod n_ref in both cases
         use_rope = self.config.use_rotary_positional_embeddings
         if use_rope and image_rotary_emb is None:
             raise TypeError("'NoneType' object is not subscriptable: a RoPE model needs image_rotary_emb")

@@ -45,7 +45,8 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
               video_uint8=None, strength=0.8, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
-    `output_type` selects ("latent" / "pt").
+    `output_type` selects ("latent" / "pt").  A batch of prompt ids [P, T] (with num_videos_per_prompt through **pipe_kwargs: up to four
+    videos per call) shares the one reference image and returns one video per row, [b, F, H, W, 3].
 
     Random draws.  The reference creates and seeds a `torch.Generator` (video_generate.py:21-23) and then never passes it anywhere:
     `.latent_dist.sample()` (:37) and the pipeline call (:44-56) carry no generator, so BOTH draws -- the posterior sample of the reference
@@ -76,6 +77,8 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
     ref = reference_latents(pipe.vae, ref_image_uint8, generator)
     pe = prompt_embeddings(text_encoder, prompt_ids, pipe.transformer.dtype)
     ne = prompt_embeddings(text_encoder, negative_prompt_ids, pipe.transformer.dtype)
+    if ne.shape[0] == 1 and pe.shape[0] > 1:  # one negative prompt for a batch of prompts
+        ne = ne.expand(pe.shape[0], -1, -1)
     if video_uint8 is not None:
         pipe_kwargs = dict(pipe_kwargs, video=_video_tensor(pipe.vae, video_uint8), strength=strength)
         num_frames = np.asarray(video_uint8).shape[0]
@@ -84,7 +87,7 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
                use_dynamic_cfg=use_dynamic_cfg, generator=generator, latents=latents, output_type=output_type,
                return_dict=True, **pipe_kwargs)
     video = out["frames"]
-    return video[0] if output_type == "np" else video
+    return video[0] if output_type == "np" and len(video) == 1 else video
 
 
 def _write_mjpeg_avi(frames, path, fps, quality=95):

@@ -175,9 +175,11 @@ S2V_API int s2v_lora_set_scale(s2v_ctx* ctx, const char* name, const float* A, c
 S2V_API int s2v_lora_detach(s2v_ctx* ctx, s2v_stream stream);
 S2V_API int s2v_lora_state(s2v_ctx* ctx, int32_t* attached, int32_t* rank, float* scale, int64_t* graph_captures);
 
-/* Token geometry of the next calls: batch B (2 = CFG pair), text tokens T, latent frames F and latent H x W
+/* Token geometry of the next calls: batch B (2 = the CFG pair of one video, 2b = the pairs of b videos in the reference's order
+ * [negative x b | positive x b], custom_cogvideox_pipe.py:196,246-248; 1 <= B <= S2V_MAX_BATCH), text tokens T, latent frames F and latent H x W
  * (R = (H/2)(W/2) reference-image tokens, V = F*R video tokens, sequence order [text | ref | video]).
  * Allocates the activation workspace (no allocation happens inside the compute calls). */
+#define S2V_MAX_BATCH 8   /* samples per call: the CFG pairs of at most four videos */
 S2V_API int s2v_set_geometry(s2v_ctx* ctx, int32_t B, int32_t T, int32_t F, int32_t H, int32_t W);
 
 /* whether QK^T of the attention runs in MX e4m3 at the current geometry: weight_format 2 always, 3 from its token threshold on (the decision
@@ -194,14 +196,27 @@ S2V_API int s2v_set_rope(s2v_ctx* ctx, const float* cos_dev, const float* sin_de
 S2V_API int s2v_set_pos_embed(s2v_ctx* ctx, const void* table_dev, s2v_stream stream);
 
 /* Step-invariant conditioning: text [B,T,text_embed_dim] -> patch_embed.text_proj; ref image latent [1,1,C,H,W] ->
- * patch_embed.proj, duplicated over the batch (cogvideox_transformer_3d.py:494-504). */
+ * patch_embed.proj, duplicated over the batch (cogvideox_transformer_3d.py:494-504).  The n_ref = 1 case of s2v_set_conditioning_refs. */
 S2V_API int s2v_set_conditioning(s2v_ctx* ctx, const void* text_dev, const void* ref_latent_dev, s2v_stream stream);
+/* One reference image per video: ref_latents [n_ref,1,C,H,W] contiguous, n_ref in {1, B/2, B}; sample j of the batch takes reference j mod n_ref.
+ * 1 = one subject for every sample; B/2 = the reference's eval=True duplication `cat([ref, ref])` over [negative x b | positive x b]
+ * (cogvideox_transformer_3d.py:503-504); B = eval=False, one row per sample.  The hoisted projections run per video -- the text projection on the
+ * [negative | positive] pair of each video, the patch embedding on each reference -- with launches of a one-video call's shape, so a sample's
+ * conditioning holds the bits it gets alone wherever the two geometries agree on split K: the split-K workspace is carved per geometry from
+ * B * Ntok, and at a size where one video has it and the batch has not (configs[0]: 2500 against 5000 rows) the text projection (K =
+ * text_embed_dim) sums in another order -- within bf16 rounding, not bitwise.  References beyond the first live in a buffer allocated here (a set-up call) and counted by
+ * s2v_device_bytes as workspace; a change of n_ref drops a captured step. */
+S2V_API int s2v_set_conditioning_refs(s2v_ctx* ctx, const void* text_dev, const void* ref_latents_dev, int32_t n_ref, s2v_stream stream);
 
 /* CogVideoXTransformer3DModel.forward (cogvideox_transformer_3d.py:450-560) with eval=True.
  * latents [B,F,C,H,W] (lat_bstride = elements between samples, 0 = all samples share one latent), timesteps fp32
  * DEVICE [B]; out [B,F,C,H,W]. */
 S2V_API int s2v_transformer_forward(s2v_ctx* ctx, const void* latents, int64_t lat_bstride, const float* timesteps_dev,
                             void* out, s2v_stream stream);
+/* the same on latents [n_lat,F,C,H,W] contiguous that the B samples share: sample j embeds latent j mod n_lat (n_lat divides B; n_lat = B/2 is the
+ * CFG batch `cat([latents] * 2)` of b videos, custom_cogvideox_pipe.py:246-248, without the copy) */
+S2V_API int s2v_transformer_forward_videos(s2v_ctx* ctx, const void* latents, int32_t n_lat, const float* timesteps_dev, void* out,
+                                   s2v_stream stream);
 
 /* CogVideoXBlock.forward (cogvideox_transformer_3d.py:122-186) for layer `layer`: three residual streams in/out,
  * hidden [B,V,D], enc0 (text) [B,T,D], enc1 (ref) [B,R,D], temb [B,time_embed_dim]. */
@@ -251,6 +266,10 @@ S2V_API int s2v_add_noise(const void* sample, const void* noise, int64_t n, floa
 
 /* One iteration of the denoise loop (custom_cogvideox_pipe.py:241-296): transformer on the CFG pair sharing
  * `latents` [1,F,C,H,W], fp32 CFG, scheduler step, round to the model dtype; latents updated IN PLACE.
+ * Several videos per call: with a geometry of B = 2b samples (b <= S2V_MAX_BATCH / 2) `latents`, `x0_hist` and `noise` are [b][F,C,H,W] contiguous,
+ * sample j embeds video j mod b (no staged copy), the model output is [2b] = [negative x b | positive x b] and the CFG + scheduler step runs on
+ * n = b F C H W elements with one timestep, guidance and coefficient set.  B = 1 is one sample without CFG.  A batched call runs on one GPU: the
+ * CFG-parallel and Ulysses entry points below keep requiring B = 1 or 2.
  * use_graph != 0 captures the launch sequence into a hipGraph on first use and replays it afterwards
  * (timestep and coefficients live in device memory, so one graph serves all steps). */
 S2V_API int s2v_denoise_step(s2v_ctx* ctx, void* latents, float timestep, const s2v_sched_coef* coef_host, float* x0_hist,
