@@ -2042,6 +2042,69 @@ extern "C" int s2v_op_linear(const void* A, const void* W, const void* bias, voi
     return launch_gemm_simple(g, epilogue, dtype, (hipStream_t)stream);
 }
 
+// The plan-and-launch of linear() for the operator entries: gemm_plan at this device's CU count (split K where the caller brought a workspace
+// of sk_tiles partial tiles, GemmArgs::tile, the row tail), main and tail launch on the same stream
+static int launch_planned(const GemmArgs& g0, int epi, int64_t sk_tiles, float* sk_ws, unsigned* sk_cnt, hipStream_t st) {
+    GemmArgs g = g0;
+    const GemmPlan p = gemm_plan(g, epi, device_cus(), sk_tiles);
+    g.tile = p.tile;
+    if (p.splitk > 1) { g.splitk = p.splitk; g.sk_ws = sk_ws; g.sk_cnt = sk_cnt; }
+    if (p.tail != GEMM_NONE) {
+        GemmArgs gm = g, gt = g;
+        gm.M = p.m_main; gt.m_begin = p.m_main;
+        S2V_TRY(launch_gemm_bf16(gm, epi, st));
+        return launch_gemm_bf16(gt, epi, st);
+    }
+    return launch_gemm_bf16(g, epi, st);
+}
+
+// One linear as a context's linear() runs it, on the caller's operands (include/s2v_hip.h).  With a split-K workspace the launch runs twice
+// where the epilogue allows it (as s2v_op_linear impl 2: the second launch starts from the counters the first one left), and the counters are
+// read back: anything but zero is an error
+extern "C" int s2v_op_linear_planned(const void* A, int32_t lda, const void* W, int32_t ldw, const void* bias, void* C, int32_t ldc, int32_t M, int32_t N,
+                                     int32_t K, int32_t epilogue, int32_t dtype, const void* gate_txt, const void* gate_ref, const void* gate_vid,
+                                     int32_t gate_stride, int32_t tok_per_batch, int32_t text_len, int32_t ref_len, const void* R, int32_t ldr,
+                                     int32_t tile, int64_t sk_tiles, s2v_stream stream) {
+    S2V_REQUIRE(A && W && C && M > 0 && N > 0 && K > 0, "s2v_op_linear_planned: bad argument");
+    S2V_REQUIRE(dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_linear_planned: bf16 or fp16 (the dtypes whose linears run on the matrix cores)");
+    S2V_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GATE_RES || epilogue == EPI_BIAS_ADD,
+                "s2v_op_linear_planned: epilogue must be 0 (bias), 1 (GELU), 2 (gate + residual) or 3 (residual add)");
+    S2V_REQUIRE(K % 64 == 0 && lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K && ldc >= N,
+                "s2v_op_linear_planned: K a multiple of 64, lda and ldw multiples of 8 and >= K, ldc >= N (what linear() sends to the matrix cores)");
+    S2V_REQUIRE(tile >= 0 && tile <= 2, "s2v_op_linear_planned: tile must be 0 (the plan's), 1 (256 x 128) or 2 (128 x 128)");
+    S2V_REQUIRE(epilogue != EPI_BIAS_GATE_RES || (gate_txt && gate_vid && tok_per_batch > 0 && text_len >= 0 && ref_len >= 0),
+                "s2v_op_linear_planned: epilogue 2 needs the text and video gates and tok_per_batch > 0 (C is the residual, updated in place)");
+    S2V_REQUIRE(epilogue != EPI_BIAS_ADD || (R && ldr >= N), "s2v_op_linear_planned: epilogue 3 needs R with ldr >= N");
+    S2V_REQUIRE(sk_tiles >= 0 && sk_tiles <= 1024 && (sk_tiles == 0 || dtype == S2V_DTYPE_BF16),
+                "s2v_op_linear_planned: a split-K workspace holds at most 1024 partial tiles and is bf16 only");
+    hipStream_t st = (hipStream_t)stream;
+    GemmArgs g{};
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    g.a_rows_padded = (int)rup(M, 256); g.w_rows_padded = (int)rup(N, 256); g.f16 = dtype == S2V_DTYPE_F16 ? 1 : 0;
+    g.tile = tile;
+    g.tok_per_batch = tok_per_batch > 0 ? tok_per_batch : M; g.text_len = text_len; g.ref_len = ref_len;
+    if (epilogue == EPI_BIAS_GATE_RES) { g.X = C; g.ldx = ldc; g.gate_txt = gate_txt; g.gate_ref = gate_ref; g.gate_vid = gate_vid; g.gate_stride = gate_stride; }
+    if (epilogue == EPI_BIAS_ADD) { g.R = R; g.ldr = ldr; }
+    if (sk_tiles == 0) return launch_planned(g, epilogue, 0, nullptr, nullptr, st);
+    char* ws = nullptr;
+    const size_t pb = (size_t)sk_tiles * 262144, cb = (size_t)sk_tiles * 4;
+    S2V_CHECK_HIP(hipMalloc((void**)&ws, pb + cb));
+    std::vector<unsigned> cnt((size_t)sk_tiles, 0u);
+    auto run = [&]() -> int {
+        S2V_CHECK_HIP(hipMemsetAsync(ws + pb, 0, cb, st));
+        S2V_TRY(launch_planned(g, epilogue, sk_tiles, (float*)ws, (unsigned*)(ws + pb), st));
+        if (epilogue != EPI_BIAS_GATE_RES) S2V_TRY(launch_planned(g, epilogue, sk_tiles, (float*)ws, (unsigned*)(ws + pb), st));  // (in place: once)
+        S2V_CHECK_HIP(hipMemcpyAsync(cnt.data(), ws + pb, cb, hipMemcpyDeviceToHost, st));
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    if (rc != 0) return rc;
+    for (unsigned v : cnt) S2V_REQUIRE(v == 0, "s2v_op_linear_planned: a split-K arrival counter did not return to zero");
+    return 0;
+}
+
 // One adapted linear as the runtime adapter mode runs it (s2v_lora_attach), on operands of its own: x and W are copied into scratch rows with room
 // for the K extension, A goes into a stack and rnd(scale * B) into W's tail (the attach-time kernels), the down-projection writes T behind x, and
 // the GEMM the engine's linear() would launch for this shape runs with K' = K + R.  Allocates its scratch; synchronous.
@@ -2078,15 +2141,7 @@ extern "C" int s2v_op_linear_lora(const void* x, const void* W, const void* bias
             g.qk_w[0] = aux0; g.qk_w[1] = (const char*)aux0 + 64 * E; g.qk_b[0] = aux1; g.qk_b[1] = (const char*)aux1 + 64 * E;
             g.qk_cs = nullptr; g.qk_D = N / 3; g.qk_eps = 1e-6f;
         }
-        const GemmPlan p = gemm_plan(g, epilogue, device_cus(), 0);  // the choice linear() makes, the row tail on the same stream
-        g.tile = p.tile;
-        if (p.tail != GEMM_NONE) {
-            GemmArgs gm = g, gt = g;
-            gm.M = p.m_main; gt.m_begin = p.m_main;
-            S2V_TRY(launch_gemm_bf16(gm, epilogue, st));
-            return launch_gemm_bf16(gt, epilogue, st);
-        }
-        return launch_gemm_bf16(g, epilogue, st);
+        return launch_planned(g, epilogue, 0, nullptr, nullptr, st);
     };
     const int rc = run();
     (void)hipStreamSynchronize(st);

@@ -1221,7 +1221,9 @@ extern "C" __attribute__((visibility("default"))) int s2v_set_gemm_impl(int impl
 // gemm_plan of one GEMM as the engine issues it, without a device (tests/test_gemm_dispatch_cpu.py): M x N x K with the operands of linear()
 // (rows padded to 256, a bias, the gate + residual of the out-projection / FF2, the q/k-norm parameters).  flags: 1 fp16 operands, 2 a rotary
 // table (EPI_BIAS_QKNORM), 4 e4m3 operands (launch_gemm_fp8) with per-token scales of A, 8 (with 4) an MX image as A instead, 16 a VAE
-// convolution (kt = 3 over cin = K / 27 channels, launch_gemm_bf16 directly).  out = {splitk, tile, m_main, main, tail} (GemmPlan)
+// convolution (kt = 3 over cin = K / 27 channels, launch_gemm_bf16 directly); bits 8 .. 9: GemmArgs::tile as a caller forces it (s2v_op_linear_planned); 32: no plan --
+// the kernel of ONE launch of M x N x K as given, operands exactly M and N rows (s2v_op_linear impl 0 / 4).  out = {splitk, tile, m_main, main, tail} (GemmPlan)
+static int gemm_kernel(const GemmArgs& a, int epi, int ncu);
 extern "C" __attribute__((visibility("default"))) int s2v_diag_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t flags, int32_t ncu,
                                                                           int64_t sk_tiles, int32_t* out) {
     S2V_REQUIRE(out && M > 0 && N > 0 && K > 0 && ncu > 0, "s2v_diag_gemm_plan: bad argument");
@@ -1232,12 +1234,18 @@ extern "C" __attribute__((visibility("default"))) int s2v_diag_gemm_plan(int32_t
     g.X = p; g.ldx = N; g.gate_vid = p; g.gate_txt = p; g.gate_stride = N; g.R = p; g.ldr = N;
     g.tok_per_batch = M; g.qk_w[0] = g.qk_w[1] = g.qk_b[0] = g.qk_b[1] = p; g.qk_D = N / 3; g.qk_cs = (flags & 2) ? (const float*)p : nullptr;
     g.f16 = flags & 1;
+    g.tile = (flags >> 8) & 3;
     if (flags & 4) {
         g.w_scale = (const float*)p;
         if (flags & 8) { g.mx_a_s = (const unsigned char*)p; g.mx_rows = g.a_rows_padded; }
         else g.a_scale = (const float*)p;
     }
     if (flags & 16) { g.conv = 1; g.kt = 3; g.cin = K / 27; g.lda = 0; g.a_rows_padded = 0; }
+    if (flags & 32) {
+        g.a_rows_padded = M; g.w_rows_padded = N;
+        out[0] = 0; out[1] = 0; out[2] = M; out[3] = gemm_kernel(g, epi, ncu); out[4] = GEMM_NONE;
+        return 0;
+    }
     const GemmPlan pl = gemm_plan(g, epi, ncu, sk_tiles);
     out[0] = pl.splitk; out[1] = pl.tile; out[2] = pl.m_main; out[3] = pl.main; out[4] = pl.tail;
     return 0;

@@ -516,6 +516,19 @@ S2V_API int s2v_t5_encode(s2v_t5* t5, const int64_t* input_ids_dev, int32_t B, i
  * reduction (M, N multiples of 256; fails if the shape does not qualify; allocates its workspace, synchronous) */
 S2V_API int s2v_op_linear(const void* A, const void* W, const void* bias, void* C, int32_t M, int32_t N, int32_t K,
                   int32_t epilogue, int32_t dtype, int32_t impl, s2v_stream stream);
+/* One linear as a context runs it (api.hip linear()): the kernel plan of gemm.hip at this device's CU count -- split K, tile, the partial last
+ * 256-row tile as a tail launch -- on the caller's operands, bf16 or fp16.  A [M rounded up to 256][lda] and W [N rounded up to 256][ldw]: the pad
+ * rows are READ (any finite values; they reach no element m < M, n < N), K a multiple of 64, lda / ldw multiples of 8.  epilogue 0 = bias,
+ * 1 = bias + GELU(tanh): C [M][ldc] out;  2 = gate + residual: C [M][ldc] is the residual, updated in place as C + rnd(gate * rnd(acc + bias)) with
+ * the gate of row m taken from sample b = m / tok_per_batch, r = m % tok_per_batch: gate_txt for r < text_len, gate_ref (may be null: gate_vid)
+ * for r < text_len + ref_len, gate_vid otherwise, each at + b * gate_stride elements;  3 = residual add: C = rnd(rnd(acc + bias) + R[m][n]), R
+ * rows ldr apart.  tile 0 = the plan's choice, 1 / 2 force 256 x 128 / 128 x 128 tiles (GemmArgs::tile).  sk_tiles > 0 (bf16): a split-K workspace
+ * of that many partial tiles is allocated and the plan may split K as it does in a context whose geometry carved one; the launch then runs twice
+ * (epilogue 2: once) and fails unless every arrival counter is zero afterwards; synchronous.  tests/test_gpu_gemm_exact.py. */
+S2V_API int s2v_op_linear_planned(const void* A, int32_t lda, const void* W, int32_t ldw, const void* bias, void* C, int32_t ldc, int32_t M, int32_t N,
+                                  int32_t K, int32_t epilogue, int32_t dtype, const void* gate_txt, const void* gate_ref, const void* gate_vid,
+                                  int32_t gate_stride, int32_t tok_per_batch, int32_t text_len, int32_t ref_len, const void* R, int32_t ldr,
+                                  int32_t tile, int64_t sk_tiles, s2v_stream stream);
 /* One adapted linear as the runtime adapter mode computes it (s2v_lora_attach): y = epilogue([x | T] . [W | rnd(scale * B)]^T + bias) with
  * T = rnd(x . A^T) from the down-projection kernel -- the attach-time packing, the down-projection and the K-extended GEMM that a context's
  * linear would launch for this shape, on the caller's operands.  x [M, K], W [N, K], bias [N] in `dtype` (bf16 or fp16); A [rank, K], B [N, rank]
