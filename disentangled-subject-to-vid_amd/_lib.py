@@ -68,6 +68,7 @@ _SIGS = {
     "s2v_sched_step": [_P, ctypes.POINTER(SchedCoefC), _P, _I32, _P, _P, _P, _P, _I64, _I32, _P],
     "s2v_add_noise": [_P, _P, _I64, _F, _F, _P, _I32, _P],
     "s2v_denoise_step": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],
+    "s2v_denoise_step_videos": [_P, _P, ctypes.POINTER(_F), ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],
     "s2v_last_noise_pred": [_P, ctypes.POINTER(_P)],
     "s2v_denoise_split_begin": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _I32, _I32, _P],
     "s2v_cfg_pair": [_P, ctypes.POINTER(_P), ctypes.POINTER(_I64)],

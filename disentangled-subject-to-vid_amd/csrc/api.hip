@@ -155,7 +155,7 @@ struct s2v_ctx {
     float* t_dev = nullptr;
     SchedCoef* coef_dev = nullptr;
     // pinned staging ring for per-step scalars
-    struct Stage { float t[S2V_MAX_BATCH]; SchedCoef c; };
+    struct Stage { float t[S2V_MAX_BATCH]; SchedCoef c[S2V_MAX_BATCH / 2]; };   // a timestep per sample, a coefficient set per video
     Stage* ring = nullptr;
     int ring_pos = 0;
     // graph
@@ -319,7 +319,7 @@ static int create_attn_weights(s2v_ctx* c) {
 // the host-side scratch every context that runs launches needs: step scalars, the pinned staging ring, the capture stream
 static bool create_tail(s2v_ctx* c) {
     hipMalloc((void**)&c->t_dev, S2V_MAX_BATCH * sizeof(float));
-    hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef));
+    hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef) * (S2V_MAX_BATCH / 2));
     hipHostMalloc((void**)&c->ring, sizeof(s2v_ctx::Stage) * RING);
     hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
     return c->t_dev && c->coef_dev && c->ring && c->cap_stream;
@@ -1600,22 +1600,26 @@ extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const
     (void)c;
     SchedArgs a{};
     a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
-    a.noise = noise; a.n = n; a.cfg = flags & 1; a.np_f32 = (flags >> 1) & 1; a.out_f32 = (flags >> 2) & 1;
+    a.noise = noise; a.n = n; a.nvid = 1; a.n_vid = n; a.cfg = flags & 1; a.np_f32 = (flags >> 1) & 1; a.out_f32 = (flags >> 2) & 1;
     a.coef = nullptr;
     fill_coef(a.cval, *coef_host);
     return launch_sched_step(a, dtype, (hipStream_t)stream);
 }
 
-// the step's scalars to the device: timestep and scheduler coefficients through the next slot of the pinned ring (the uploads are
-// asynchronous: a slot must outlive its copies, RING steps ahead of the device are allowed)
-static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_host, hipStream_t st) {
+// the step's scalars to the device through the next slot of the pinned ring (the uploads are asynchronous: a slot must outlive its copies, RING
+// steps ahead of the device are allowed): b videos, sample j of the S2V_MAX_BATCH slots at timesteps[j mod b], video k's coefficient set coefs[k]
+// (the sets past b repeat the last one).  Whatever b is, the timesteps go up in one copy and the coefficient sets in one
+static int stage_step(s2v_ctx* c, const float* timesteps, const s2v_sched_coef* coefs, int b, hipStream_t st) {
     s2v_ctx::Stage& sg = c->ring[c->ring_pos];
     c->ring_pos = (c->ring_pos + 1) % RING;
-    for (int i = 0; i < S2V_MAX_BATCH; ++i) sg.t[i] = timestep;
-    fill_coef(sg.c, *coef_host);
+    for (int i = 0; i < S2V_MAX_BATCH; ++i) sg.t[i] = timesteps[i % b];
+    for (int k = 0; k < S2V_MAX_BATCH / 2; ++k) fill_coef(sg.c[k], coefs[k < b ? k : b - 1]);
     S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * S2V_MAX_BATCH, hipMemcpyHostToDevice, st));
-    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, &sg.c, sizeof(SchedCoef), hipMemcpyHostToDevice, st));
+    S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, sg.c, sizeof(SchedCoef) * (S2V_MAX_BATCH / 2), hipMemcpyHostToDevice, st));
     return 0;
+}
+static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_host, hipStream_t st) {
+    return stage_step(c, &timestep, coef_host, 1, st);
 }
 
 // the graph cache: replay the captured `body` on st; a first use or another key captures body(cap_stream) anew.  A body that fails ends the
@@ -1641,11 +1645,13 @@ static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body
 }
 
 // (CFG +) scheduler step on the context's noise_pred with the coefficients stage_step uploaded, latents updated in place.  nvid videos:
-// latents / x0_hist / noise [nvid][F,C,H,W] and noise_pred [negative x nvid | positive x nvid], so the conditional half starts n elements in
+// latents / x0_hist / noise [nvid][F,C,H,W] and noise_pred [negative x nvid | positive x nvid], so the conditional half starts n elements in;
+// video k is stepped with the k-th uploaded coefficient set
 static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, int cfg_flag, hipStream_t st, int nvid = 1) {
     SchedArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
-    a.n = (int64_t)nvid * c->F * c->cfg.out_channels * c->H * c->W; a.cfg = cfg_flag; a.coef = c->coef_dev;
+    a.nvid = nvid; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
+    a.n = nvid * a.n_vid; a.cfg = cfg_flag; a.coef = c->coef_dev;
     return launch_sched_step(a, c->dtype, st);
 }
 
@@ -1656,19 +1662,34 @@ static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* 
     return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b);
 }
 
-extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
-                                float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
-    S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_step: null argument");
+// the whole step of b = B/2 videos (b = 1 for B = 1 or 2) at timesteps[b] and coefs[b]; s2v_denoise_step's wording serves both entries
+static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist, const void* noise,
+                             int32_t use_graph, hipStream_t st) {
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
-    S2V_REQUIRE(coef_host->kind == 0 || (noise && x0_hist), "s2v_denoise_step: DPM needs noise and x0_hist");
+    const int b = c->B >= 2 ? c->B / 2 : 1;
+    for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step: DPM needs noise and x0_hist");
     S2V_REQUIRE(!c->shard, use_graph ? "s2v_denoise_step: hipGraph capture is not supported for a shard context (s2v_set_shard): its step is staged around "
                                        "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
                                      : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
-    hipStream_t st = (hipStream_t)stream;
-    S2V_TRY(stage_step(c, timestep, coef_host, st));
+    S2V_TRY(stage_step(c, timesteps, coefs, b, st));
     if (!use_graph) return step_launches(c, latents, x0_hist, noise, st);
     return launch_captured(c, GraphKey{latents, x0_hist, noise, -1}, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s); });
+}
+
+extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
+                                float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
+    S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_step: null argument");
+    float t[S2V_MAX_BATCH / 2];
+    s2v_sched_coef k[S2V_MAX_BATCH / 2];
+    for (int i = 0; i < S2V_MAX_BATCH / 2; ++i) { t[i] = timestep; k[i] = *coef_host; }   // the scalar repeated for every video
+    return denoise_step_impl(c, latents, t, k, x0_hist, noise, use_graph, (hipStream_t)stream);
+}
+
+extern "C" int s2v_denoise_step_videos(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist,
+                                       const void* noise, int32_t use_graph, s2v_stream stream) {
+    S2V_REQUIRE(c && latents && timesteps && coefs, "s2v_denoise_step_videos: null argument");
+    return denoise_step_impl(c, latents, timesteps, coefs, x0_hist, noise, use_graph, (hipStream_t)stream);
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------

@@ -930,9 +930,10 @@ int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void
 template <typename T>
 __global__ void sched_step_k(const SchedArgs a) {
 #pragma clang fp contract(off)  // hipcc defaults to -ffp-contract=fast and __fmul_rn is a plain multiply in HIP
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    const SchedCoef k = a.coef ? *a.coef : a.cval;
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // within video blockIdx.y
+    if (j >= a.n_vid) return;
+    const int64_t i = (int64_t)blockIdx.y * a.n_vid + j;
+    const SchedCoef k = a.coef ? a.coef[blockIdx.y] : a.cval;
     float v;
     if (a.np_f32) {
         const float* np = (const float*)a.noise_pred;
@@ -962,7 +963,9 @@ __global__ void sched_step_k(const SchedArgs a) {
     else ET<T>::st((T*)a.latents_out + i, prev);
 }
 int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st) {
-    dim3 grid((unsigned)((a.n + 255) / 256));
+    S2V_REQUIRE(a.nvid >= 1 && a.n_vid >= 1 && (int64_t)a.nvid * a.n_vid == a.n, "sched_step: n must be nvid videos of n_vid elements");
+    S2V_REQUIRE(a.coef || a.nvid == 1, "sched_step: several videos take their coefficient sets from device memory");
+    dim3 grid((unsigned)((a.n_vid + 255) / 256), (unsigned)a.nvid);
     S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(sched_step_k<T>, grid, dim3(256), 0, st, a))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;

@@ -334,19 +334,22 @@ int launch_tail_norm(const TailNormArgs& a, int dtype, hipStream_t st);
 //   kind 0 (DDIM)          : out = rnd(a_t * x) + b_t * x0
 //   kind 1 (DPM first/last): out = (rnd(m1 * x) - m2 * x0) + rnd(mn * noise)
 //   kind 2 (DPM multistep) : d = m3 * x0 - m4 * x0_old ; out = (rnd(m1 * x) - m2 * d) + rnd(mn * noise)
+// nvid videos per launch, video v = blockIdx.y with its own coefficient set coef[v] (kind and guidance included): the set is chosen per
+// workgroup, so its load stays uniform and no workgroup runs across two videos.
 struct SchedCoef {
     int kind; float guidance;
     float c_x0_x, c_x0_v, a_t, b_t, m1, m2, m3, m4, mn;
     float pad;
 };
 struct SchedArgs {
-    const void* noise_pred;   // [2, n] model dtype (uncond, cond) or [1, n] when !cfg
-    const void* latents_in;   // [n] model dtype
+    const void* noise_pred;   // [2, n] model dtype (uncond, cond) or [1, n] when !cfg; n = nvid * n_vid, the conditional half n elements in
+    const void* latents_in;   // [n] model dtype: nvid videos of n_vid elements
     void* latents_out;        // [n] model dtype (may alias latents_in)
     float* x0_hist;           // [n] fp32: read as x0_old (kind 2), overwritten with this step's x0 (may be null for DDIM)
     const void* noise;        // [n] model dtype, DPM only
     int64_t n; int cfg;
-    const SchedCoef* coef;    // device pointer, or null => use cval
+    int nvid; int64_t n_vid;  // videos in this launch and the elements of one (n = nvid * n_vid)
+    const SchedCoef* coef;    // device pointer to nvid consecutive sets, or null => use cval (nvid = 1)
     SchedCoef cval;
     int np_f32;               // noise_pred is fp32 (the scheduler-object seam: model_output after .float())
     int out_f32;              // latents_out is fp32 and un-rounded (scheduler.step's return value)

@@ -16,6 +16,20 @@ class _ArenaView:
         self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
 
 
+def _is_seq(x):
+    return isinstance(x, (list, tuple)) or (isinstance(x, (torch.Tensor, np.ndarray)) and x.ndim > 0)
+
+
+def _per_video(name, x, b):
+    """x as a list of b entries: a sequence of b, or one value repeated"""
+    xs = list(x) if _is_seq(x) else [x]
+    if len(xs) == 1 and not _is_seq(x):
+        xs = xs * b
+    if len(xs) != b:
+        raise _lib.S2VError(f"denoise_step: `{name}` has {len(xs)} entries for b = {b} videos (one per video, or a scalar for all)")
+    return xs
+
+
 class S2VEngine:
     def __init__(self, cfg: TransformerConfig, dtype=torch.bfloat16, device="cuda:0", force_simple=False, kind=_lib.CTX_MODEL):
         """kind: _lib.CTX_MODEL (a whole model), or one of the two halves of the model-wide AttnProcessor (include/s2v_hip.h, S2V_CTX_*):
@@ -435,7 +449,9 @@ class S2VEngine:
 
     def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
-        [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents"""
+        [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
+        (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
+        coef[k] -- its own kind, guidance and scalars (s2v_denoise_step_videos); a scalar beside a sequence is repeated"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
@@ -446,11 +462,22 @@ class S2VEngine:
             for name, x in (("latents", latents), ("x0_hist", x0_hist), ("noise", noise)):
                 if x is not None and (tuple(x.shape) != want or not x.is_contiguous()):
                     raise _lib.S2VError(f"denoise_step: {name} must be contiguous {list(want)} for {B // 2} videos per call, got {list(x.shape)}")
+        per_video = not isinstance(coef, _lib.SchedCoefC) or _is_seq(timestep)
+        if per_video:
+            b = B // 2 if B >= 2 else 1
+            ts = _per_video("timestep", timestep, b)
+            cs = _per_video("coef", coef, b)
+            t_arr = (ctypes.c_float * b)(*[float(t) for t in ts])
+            c_arr = (_lib.SchedCoefC * b)(*cs)
         auto = self._attn_auto_pending
         if auto:
             self.attn_slow_stats(reset=True)
-        _lib.check(_lib.lib().s2v_denoise_step(self._h, _lib.ptr(latents), float(timestep), ctypes.byref(coef),
-                                               _lib.ptr(x0_hist), _lib.ptr(noise), int(use_graph and not auto), _lib.stream_ptr()))
+        if per_video:
+            _lib.check(_lib.lib().s2v_denoise_step_videos(self._h, _lib.ptr(latents), t_arr, c_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
+                                                          int(use_graph and not auto), _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib().s2v_denoise_step(self._h, _lib.ptr(latents), float(timestep), ctypes.byref(coef),
+                                                   _lib.ptr(x0_hist), _lib.ptr(noise), int(use_graph and not auto), _lib.stream_ptr()))
         if auto:  # the first step of an "auto" engine runs eagerly; its census decides the format of every later step
             slow, total = self.attn_slow_stats()
             self.attn_slow_fraction = slow / total if total else 0.0

@@ -71,8 +71,8 @@ class S2VPipeline:
     def check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents=None, generator=None, video=None, cfg_parallel=None,
                     ulysses=None):
         """the number of videos b = prompts x num_videos_per_prompt of a call, after everything that limits it has been checked (no device
-        is touched): 1 <= b <= MAX_VIDEOS, ref_img_states with 1 or b rows, latents with b rows, a generator list of b, and the paths that
-        stay one video per call"""
+        is touched): 1 <= b <= MAX_VIDEOS, ref_img_states with 1 or b rows, latents with b rows, a generator list of b, a video with 1 or b
+        rows, and the paths that stay one video per call"""
         if prompt_embeds.ndim != 3:
             raise ValueError(f"`prompt_embeds` must be [prompts, tokens, dim], got {tuple(prompt_embeds.shape)}")
         if num_videos_per_prompt < 1:
@@ -89,11 +89,89 @@ class S2VPipeline:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {b}. "
                              f"Make sure the batch size matches the length of the generators.")
         if b > 1:
-            for name, arg in (("video", video), ("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+            for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
                 if arg is not None:
                     raise ValueError(f"`{name}` with {b} videos per call: several videos per call run as one batched step on one GPU; "
-                                     f"video-to-video, CFG-parallel and Ulysses stay one video per call")
+                                     f"CFG-parallel and Ulysses stay one video per call")
+            if video is not None and (video.ndim != 5 or video.shape[0] not in (1, b)):
+                raise ValueError(f"`video` must be [v, 3, F, H, W] with v = 1 (one input video shared by all {b} videos) or v = b = {b} "
+                                 f"(video k starts from row k), got {tuple(video.shape)}")
         return b
+
+    @staticmethod
+    def check_per_video(b, guidance_scale, num_inference_steps, strength, video=None, cfg_parallel=None, ulysses=None):
+        """guidance_scale, num_inference_steps and strength of a call as three lists of b entries (a scalar is repeated; lists are prompt-major
+        as generator lists are), after every refusal that needs no scheduler: a list whose length is not b, a guidance scale <= 1, a strength
+        outside [0, 1], a strength list without a video, a list on the paths that stay one video per call with scalars"""
+        out = []
+        for name, x in (("guidance_scale", guidance_scale), ("num_inference_steps", num_inference_steps), ("strength", strength)):
+            if isinstance(x, (list, tuple)):
+                for other, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+                    if arg is not None:
+                        raise ValueError(f"`{name}` as a list together with `{other}`: CFG-parallel and Ulysses stay one video per call with scalars")
+                if len(x) != b:
+                    raise ValueError(f"`{name}` is a list of {len(x)} entries for b = {b} videos: one entry per video (prompt-major), or a scalar for all")
+                if name == "strength" and video is None:
+                    raise ValueError("`strength` as a list applies only together with `video` (text-to-video calls run every timestep)")
+                out.append(list(x))
+            else:
+                out.append([x] * b)
+        for k, g in enumerate(out[0]):
+            if g <= 1.0:
+                raise ValueError(f"guidance_scale[{k}] = {g}: every guidance scale must be > 1 (eval=True duplicates the reference tokens for the CFG pair)")
+        for k, n in enumerate(out[1]):
+            if int(n) != n or n < 1:
+                raise ValueError(f"num_inference_steps[{k}] = {n}: every step count must be an integer >= 1")
+        for st in out[2]:
+            if st < 0 or st > 1:
+                raise ValueError(f"The value of strength should in [0.0, 1.0] but is {st}")
+        return tuple(out)
+
+    @classmethod
+    def video_plan(cls, scheduler, num_inference_steps, strength, guidance_scale, use_dynamic_cfg, dtype):
+        """everything the one-video call with these arguments does per step, in its order: {"num_inference_steps": the scheduler's count,
+        "timesteps": its timesteps (strength: the last int(n * strength) of them; None: text-to-video, all), "steps": per step {"t",
+        "t_back", "first" (DPM: no x0 history yet), "guidance" (the dynamic-CFG curve runs on the video's own index and count), "coef",
+        "draws" (noise draws from the video's generator: DPM draws once, twice on a multistep step)}}.  No device is touched"""
+        n = int(num_inference_steps)
+        ts = scheduler.timesteps_for(n)
+        n_loop = n
+        if strength is not None:
+            ts, n_loop = cls.get_timesteps(n, ts, strength, scheduler.order)
+            if len(ts) == 0:
+                raise ValueError(f"strength {strength} keeps none of the {n} timesteps")
+        is_dpm = isinstance(scheduler, CogVideoXDPMScheduler)
+        steps = []
+        for i, t in enumerate(ts):
+            g = guidance_scale
+            if use_dynamic_cfg:
+                g = 1 + guidance_scale * ((1 - math.cos(math.pi * ((n_loop - i) / n_loop) ** 5.0)) / 2)
+            t_back = ts[i - 1] if is_dpm and i > 0 else None
+            if is_dpm:
+                coef = scheduler.coef(t, t_back, i == 0, dtype, g, num_inference_steps=n)
+            else:
+                coef = scheduler.coef(t, dtype, g, num_inference_steps=n)
+            steps.append(dict(t=t, t_back=t_back, first=i == 0, guidance=g, coef=coef, draws=(2 if coef.kind == 2 else 1) if is_dpm else 0))
+        return dict(num_inference_steps=n, timesteps=ts, steps=steps)
+
+    @staticmethod
+    def plan_order(plans):
+        """(order, inverse): the internal order of the videos, longest plan first and stable, so the videos that still have a step are always
+        a prefix; order[p] is the caller's index of the video at internal position p and inverse[k] the position of the caller's video k"""
+        order = sorted(range(len(plans)), key=lambda k: -len(plans[k]["steps"]))
+        inverse = [0] * len(order)
+        for p, k in enumerate(order):
+            inverse[k] = p
+        return order, inverse
+
+    @staticmethod
+    def check_plans(plans, scheduler, generator):
+        """one random stream cannot be dealt out to videos that draw different numbers of times"""
+        if isinstance(scheduler, CogVideoXDPMScheduler) and not isinstance(generator, (list, tuple)):
+            draws = [[s["draws"] for s in p["steps"]] for p in plans]
+            if any(d != draws[0] for d in draws):
+                raise ValueError(f"plans of {[len(d) for d in draws]} steps under the DPM scheduler with a single generator (or none): one random "
+                                 f"stream cannot be dealt out to videos that draw different numbers of times; pass a list of {len(plans)} generators")
 
     @staticmethod
     def get_timesteps(num_inference_steps, timesteps, strength, order=1):
@@ -123,27 +201,39 @@ class S2VPipeline:
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
-        generator k alone).  Every step runs the transformer on [negative x b | positive x b]; the result is [b,...].  video=, cfg_parallel=
-        and ulysses= stay one video per call.
+        generator k alone).  Every step runs the transformer on [negative x b | positive x b]; the result is [b,...].  cfg_parallel= and
+        ulysses= stay one video per call.
+        Per video: guidance_scale, num_inference_steps and strength each take a scalar (one value for all, the path below) or a list with one
+        entry per video, prompt-major as generator lists are; video may have b rows, or one row shared by all b videos.  Video k then equals
+        the one-video call made with its own prompt, reference row, video row, generator, guidance scale, step count and strength: every video
+        runs the plan of that call (_call_videos), the batch shrinks as the shortest plans end, results come back in the caller's order.  The
+        step-end callback sees all b videos in the caller's order; its `t` is a [b] tensor once the active videos' timesteps differ (a
+        finished video keeps its last one).  Plans of different lengths under the DPM scheduler need a generator list.
         cfg_parallel: a dist.CfgPair -- this process runs ONE sample of the CFG pair (slot 0: negative prompt, slot 1: prompt) on its GPU and its
         peer the other; every rank of the pair passes the SAME arguments (embeddings, reference latent, latents or an equally seeded generator) and
         returns the same latents / video bit for bit.  fused mode only.
         ulysses: a dist.UlyssesGroup -- the group's ranks share every step of this video (both samples of the CFG pair, the rows of each stream
         split over the ranks, attention sharded by heads); same arguments on every rank, same latents back.  fused mode only, not with cfg_parallel.
-        video: video-to-video (pipeline_cogvideox_video2video.py): [1,3,F,H,W] in [-1,1] with F = 1 or 8k + 1 and H x W = height x width.  The
+        video: video-to-video (pipeline_cogvideox_video2video.py): [1,3,F,H,W] (or [b,3,F,H,W]) in [-1,1] with F = 1 or 8k + 1 and H x W = height x width.  The
         loop starts from the encoded video noised to the first of the last int(num_inference_steps * strength) timesteps; num_frames comes
         from the video.  strength applies only together with a video (text-to-video calls run every timestep, as before)."""
-        if strength < 0 or strength > 1:
+        per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength))
+        if not isinstance(strength, (list, tuple)) and (strength < 0 or strength > 1):
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if video is not None:
-            if prompt_embeds is not None and prompt_embeds.ndim == 3 and ref_img_states is not None:  # several videos: refused before the VAE is asked for
-                self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, None, None, video)
+            nv = 1
+            if prompt_embeds is not None and prompt_embeds.ndim == 3 and ref_img_states is not None:  # the rows of `video`: refused before the VAE is asked for
+                nv = self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, None, None, video)
             if latents is not None:
                 raise ValueError("Only one of `video` or `latents` should be provided")
             if self.vae is None:
+                if nv > 1:
+                    raise ValueError(f"`video` with {nv} videos per call: video-to-video encodes every input video with the VAE, one video per call "
+                                     f"of its encoder: construct the pipeline with a `vae`")
                 raise ValueError("video-to-video encodes the video: construct the pipeline with a `vae`")
-            if video.ndim != 5 or video.shape[0] != 1 or video.shape[1] != 3:
-                raise ValueError(f"`video` must be [1, 3, F, H, W], got {tuple(video.shape)}")
+            if video.ndim != 5 or video.shape[0] not in (1, nv) or video.shape[1] != 3:
+                raise ValueError(f"`video` must be [1, 3, F, H, W]" + (f" or [{nv}, 3, F, H, W] (one row per video)" if nv > 1 else "")
+                                 + f", got {tuple(video.shape)}")
             if (video.shape[3], video.shape[4]) != (height, width):
                 raise ValueError(f"`video` is {video.shape[3]}x{video.shape[4]} but height x width is {height}x{width}: resizing stays "
                                  "with the caller")
@@ -160,9 +250,14 @@ class S2VPipeline:
                              "(video_generate.inference does it)")
         if ref_img_states is None:
             raise ValueError("Provide `ref_img_states` (the VAE latent of the reference image, [1, 1, C, H/8, W/8])")
-        if guidance_scale <= 1.0:
+        if not isinstance(guidance_scale, (list, tuple)) and guidance_scale <= 1.0:
             raise RuntimeError("guidance_scale must be > 1: eval=True duplicates the reference tokens for the CFG pair")
         b = self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents, generator, video, cfg_parallel, ulysses)
+        if per_video or (video is not None and b > 1):   # every video on its own plan; scalars and one input video stay on the path below
+            lists = self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)
+            return self._call_videos(b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg,
+                                     generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
+                                     callback_on_step_end_tensor_inputs, video, num_videos_per_prompt)
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)  # [negative x b | positive x b] (:196)
@@ -261,6 +356,10 @@ class S2VPipeline:
                     if fused:  # the hoisted text projection follows the new embeddings
                         eng.set_conditioning(text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1], ref)
                 negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
+        return self._finish(latents, fused, output_type, return_dict)
+
+    def _finish(self, latents, fused, output_type, return_dict):
+        tr = self.transformer
         # attn_p_format "auto" settled on the census of the FIRST step; the whole run's census is kept for the caller and, should later (less
         # noisy, sharper) steps have taken the fp16 kernel's slow path too often, the next video of this engine runs on bf16 probabilities
         self.attn_slow_fraction = None
@@ -278,6 +377,150 @@ class S2VPipeline:
             video = self.decode_latents(latents)
             video = self.vae.postprocess_video(video, output_type)
         return (video,) if not return_dict else {"frames": video}
+
+    def prepare_videos_latents(self, video, dtype, device, generator, first_timesteps):
+        """pipeline_cogvideox_video2video.py:374-392 for b = len(first_timesteps) videos: video [v,3,F,H,W], v = b or one row shared by all.
+        One generator (or none): one posterior sample per video row in order, then the noise of all b videos in one draw.  A list: video k's
+        posterior sample and noise both come from generator k (a shared row is encoded once and sampled per generator).  add_noise at every
+        video's own first timestep; the VAE encodes one video at a time -> [b,Fl,C,h,w]"""
+        vae, b, v = self.vae, len(first_timesteps), video.shape[0]
+        scaled = lambda z: vae.config.scaling_factor * z.to(dtype).permute(0, 2, 1, 3, 4).contiguous()   # as prepare_video_latents writes it
+        if isinstance(generator, (list, tuple)):
+            z0, noise, dist = [], [], None
+            for k, g in enumerate(generator):
+                if dist is None or v > 1:
+                    dist = vae.encode(video[k:k + 1]).latent_dist
+                z0.append(scaled(dist.sample(g)))
+                noise.append(torch.randn(z0[-1].shape, generator=g, device=g.device, dtype=dtype).to(device))
+            z0, noise = torch.cat(z0, dim=0), torch.cat(noise, dim=0)
+        else:
+            z0 = scaled(torch.cat([vae.encode(video[r:r + 1]).latent_dist.sample(generator) for r in range(v)], dim=0))
+            if v != b:
+                z0 = z0.expand(b, -1, -1, -1, -1).contiguous()
+            gdev = generator.device if generator is not None else device
+            noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
+        latents = self.scheduler.add_noise(z0.to(device), noise, torch.stack([torch.as_tensor(t) for t in first_timesteps]))
+        return latents * self.scheduler.init_noise_sigma
+
+    def _call_videos(self, b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg, generator,
+                     latents, output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, video,
+                     num_videos_per_prompt):
+        """b videos, each on the plan of its one-video call (video_plan): iteration i applies step i of every video that still has one.  The
+        videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers; when
+        the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
+        latents stay where they are.  Results, and everything the callback sees, are in the caller's order"""
+        tr, sch = self.transformer, self.scheduler
+        dt, dev = tr.dtype, tr.device
+        guidance, counts, strengths = lists
+        plans = [self.video_plan(sch, counts[k], strengths[k] if video is not None else None, guidance[k], use_dynamic_cfg, dt) for k in range(b)]
+        self.check_plans(plans, sch, generator)
+        order, inverse = self.plan_order(plans)
+        eng = tr.engine
+        is_dpm = isinstance(sch, CogVideoXDPMScheduler)
+        gen_list = isinstance(generator, (list, tuple))
+        text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)   # caller's order, what the callback sees
+        if video is not None:
+            latents = self.prepare_videos_latents(video, dt, dev, generator, [p["timesteps"][0] for p in plans])
+        else:
+            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b)
+        latents = latents.to(dt)[order].contiguous()   # internal order from here on
+        F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
+        ref = ref_img_states.to(dev, dt)
+        if ref.shape[0] > 1:
+            ref = ref[order].contiguous()
+        gens = [generator[k] for k in order] if gen_list else None
+        rope = ref_rope = None
+        if tr.config.use_rotary_positional_embeddings:
+            cos, sin = tables.rope_tables(height, width, F)
+            n = (H // 2) * (W // 2)
+            cos, sin = torch.from_numpy(cos).to(dev), torch.from_numpy(sin).to(dev)
+            ref_rope, rope = (cos[:n], sin[:n]), (cos[n:], sin[n:])
+
+        def active_text(a):   # [negative x a | positive x a] of the first a videos
+            neg, pos = text.chunk(2)
+            return torch.cat([neg[order[:a]], pos[order[:a]]], dim=0).contiguous()
+
+        def active_ref(a, rows):   # the engine maps one shared row itself; the seam's eval=True wants a rows
+            if ref.shape[0] > 1:
+                return ref[:a]
+            return ref.expand(a, -1, -1, -1, -1).contiguous() if rows else ref
+
+        def set_active(a):
+            eng.set_geometry(2 * a, text.shape[1], F, H, W)
+            eng.prepare_tables(height, width)
+            eng.set_conditioning(active_text(a), active_ref(a, False))
+
+        lens = [len(plans[k]["steps"]) for k in order]
+        active = b
+        if fused:
+            set_active(b)
+            x0_hist = torch.zeros(latents.shape, dtype=torch.float32, device=dev) if is_dpm else None
+            noise = torch.empty_like(latents) if is_dpm else None
+        old = [None] * b
+        last_t = [plans[k]["timesteps"][0] for k in order]
+        seam_key = seam_text = seam_ref = None   # the seam re-conditions when its tensors change: new ones only when the rows or the text do
+        for i in range(lens[0]):
+            if self.interrupt:
+                break
+            a = sum(1 for n_k in lens if n_k > i)
+            if a != active:   # the shortest plans have ended: the batch shrinks to the videos that go on
+                active = a
+                if fused:
+                    set_active(a)
+            steps = [plans[order[p]]["steps"][i] for p in range(a)]
+            for p, st in enumerate(steps):
+                last_t[p] = st["t"]
+            self._guidance_scale = [plans[k]["steps"][min(i, len(plans[k]["steps"]) - 1)]["guidance"] for k in range(b)]
+            if fused:
+                if is_dpm and gen_list:   # video p draws from its own generator, as often as its one-video call does at this step
+                    for p, st in enumerate(steps):
+                        for _ in range(st["draws"]):
+                            self._draw(noise[p:p + 1], gens[p])
+                elif is_dpm:
+                    for _ in range(steps[0]["draws"]):
+                        self._draw(noise[:a], generator)
+                eng.denoise_step(latents[:a], [float(st["t"]) for st in steps], [st["coef"] for st in steps],
+                                 x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph)
+            else:
+                x = torch.cat([latents[:a]] * 2)
+                if seam_key is None or seam_key[0] != a or seam_key[1] is not text:
+                    seam_key, seam_text, seam_ref = (a, text), active_text(a), active_ref(a, True)
+                noise_pred = tr(hidden_states=x, encoder_hidden_states=seam_text, ref_img_states=seam_ref,
+                                timestep=torch.stack([st["t"] for st in steps]).repeat(2), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
+                                return_dict=False, eval=True)[0].float()
+                u, c = noise_pred.chunk(2)
+                drawn = None
+                if is_dpm and not gen_list:   # one stream: the noise of all videos in one draw, the last of this step's draws
+                    for _ in range(steps[0]["draws"]):
+                        drawn = randn_videos(latents[:a].shape, generator, dev, dt)
+                for p, st in enumerate(steps):   # the one-video call's own sequence on video p
+                    n_k = plans[order[p]]["num_inference_steps"]
+                    np_p = u[p:p + 1] + st["guidance"] * (c[p:p + 1] - u[p:p + 1])
+                    if not is_dpm:
+                        new = sch.step(np_p, st["t"], latents[p:p + 1], return_dict=False, num_inference_steps=n_k)[0]
+                    else:
+                        new, old[p] = sch.step(np_p, old[p], st["t"], st["t_back"], latents[p:p + 1], generator=gens[p] if gen_list else None,
+                                               variance_noise=None if drawn is None else drawn[p:p + 1], return_dict=False,
+                                               num_inference_steps=n_k)
+                    latents[p:p + 1] = new.to(dt)
+            if callback_on_step_end is not None:
+                # the contract of the scalar path over all b videos in the caller's order; `t` is the 0-dim timestep while the active videos
+                # share it, otherwise [b] timesteps (a finished video keeps its last one)
+                t_cb = steps[0]["t"] if all(int(st["t"]) == int(steps[0]["t"]) for st in steps) else torch.stack([last_t[inverse[k]] for k in range(b)])
+                shown = latents[inverse]
+                avail = {"latents": shown, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
+                outs = callback_on_step_end(self, i, t_cb, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
+                new_lat = outs.get("latents", shown)
+                if new_lat is not shown:   # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
+                    latents.copy_(new_lat.to(dev, dt).reshape(shown.shape)[order])
+                new_text = outs.get("prompt_embeds", text)
+                if new_text is not text:
+                    text = new_text.to(dev, dt)
+                    if fused:  # the hoisted text projection of the active rows follows the new embeddings
+                        eng.set_conditioning(active_text(active), active_ref(active, False))
+                negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
+        sch.set_timesteps(plans[order[0]]["num_inference_steps"], device="cpu")   # the object is left on the longest video's count
+        return self._finish(latents[inverse].contiguous(), fused, output_type, return_dict)
 
     @staticmethod
     def _draw(buf, generator):

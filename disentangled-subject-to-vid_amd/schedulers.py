@@ -87,26 +87,39 @@ class _SchedulerBase:
         return float(a**0.5), float((1 - a) ** 0.5)
 
     def add_noise(self, original_samples, noise, timesteps):
-        """scheduler.add_noise (scheduling_ddim_cogvideox.py:405-431; scheduling_dpm_cogvideox.py:442) for one timestep, in the HIP
-        kernel of s2v_add_noise"""
+        """scheduler.add_noise (scheduling_ddim_cogvideox.py:405-431; scheduling_dpm_cogvideox.py:442) in the HIP kernel of s2v_add_noise:
+        one timestep for the whole tensor, or b timesteps for [b, ...] samples, row k noised at timesteps[k] (one launch per row: this
+        runs once per call, outside the step loop)"""
         t = torch.as_tensor(timesteps).reshape(-1)
-        if t.numel() != 1:
-            raise NotImplementedError("add_noise: one timestep (batch 1)")
         if original_samples.shape != noise.shape or original_samples.dtype != noise.dtype:
             raise ValueError("add_noise: original_samples and noise must have the same shape and dtype")
+        if t.numel() != 1 and (original_samples.ndim < 1 or t.numel() != original_samples.shape[0]):
+            raise ValueError(f"add_noise: {t.numel()} timesteps for samples of shape {tuple(original_samples.shape)}: one timestep, or one per row")
         x = original_samples.contiguous()
         n = noise.to(x.device).contiguous()
-        sa, sb = self.add_noise_scalars(int(t[0]), x.dtype, x.device)
         out = torch.empty_like(x)
-        _lib.check(_lib.lib().s2v_add_noise(_lib.ptr(x), _lib.ptr(n), x.numel(), sa, sb, _lib.ptr(out),
-                                            _lib.DTYPE_OF[x.dtype], _lib.stream_ptr()))
+        rows = [(x, n, out)] if t.numel() == 1 else [(x[k], n[k], out[k]) for k in range(x.shape[0])]
+        for (xk, nk, ok), tk in zip(rows, t):
+            sa, sb = self.add_noise_scalars(int(tk), x.dtype, x.device)
+            _lib.check(_lib.lib().s2v_add_noise(_lib.ptr(xk), _lib.ptr(nk), xk.numel(), sa, sb, _lib.ptr(ok),
+                                                _lib.DTYPE_OF[x.dtype], _lib.stream_ptr()))
         return out
 
-    def _alphas(self, timestep):
-        if self.num_inference_steps is None:
+    def timesteps_for(self, num_inference_steps):
+        """the timesteps set_timesteps(num_inference_steps) would leave, without touching the object: a batched call plans every video on its
+        own step count (coef / step take the count as `num_inference_steps`)"""
+        n_train = self.config["num_train_timesteps"]
+        if num_inference_steps > n_train:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than {n_train}")
+        return torch.from_numpy(tables.trailing_timesteps(num_inference_steps, n_train))
+
+    def _alphas(self, timestep, num_inference_steps=None):
+        """num_inference_steps: the step count the timestep belongs to; None: the one set_timesteps left"""
+        n = self.num_inference_steps if num_inference_steps is None else num_inference_steps
+        if n is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' first")
         t = int(timestep)
-        prev_t = t - self.config["num_train_timesteps"] // self.num_inference_steps
+        prev_t = t - self.config["num_train_timesteps"] // n
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         return t, prev_t, a_t, a_prev
@@ -127,9 +140,9 @@ class _SchedulerBase:
 
 
 class CogVideoXDDIMScheduler(_SchedulerBase):
-    def coef(self, timestep, dtype, guidance=1.0):
+    def coef(self, timestep, dtype, guidance=1.0, num_inference_steps=None):
         """scalars of scheduling_ddim_cogvideox.py:364-394 for one step"""
-        _, _, a_t, a_prev = self._alphas(timestep)
+        _, _, a_t, a_prev = self._alphas(timestep, num_inference_steps)
         b_t = 1 - a_t
         at = ((1 - a_prev) / (1 - a_t)) ** 0.5
         bt = a_prev**0.5 - a_t**0.5 * at
@@ -140,17 +153,17 @@ class CogVideoXDDIMScheduler(_SchedulerBase):
         return c
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
-             variance_noise=None, return_dict=True):
-        prev, x0 = self._run(self.coef(timestep, sample.dtype), model_output, sample, None, None)
+             variance_noise=None, return_dict=True, num_inference_steps=None):
+        prev, x0 = self._run(self.coef(timestep, sample.dtype, num_inference_steps=num_inference_steps), model_output, sample, None, None)
         if not return_dict:
             return (prev, x0)
         return dict(prev_sample=prev, pred_original_sample=x0)
 
 
 class CogVideoXDPMScheduler(_SchedulerBase):
-    def coef(self, timestep, timestep_back, first, dtype, guidance=1.0):
+    def coef(self, timestep, timestep_back, first, dtype, guidance=1.0, num_inference_steps=None):
         """scalars of scheduling_dpm_cogvideox.py:391-434; `first` = no old_pred_original_sample yet"""
-        _, prev_t, a_t, a_prev = self._alphas(timestep)
+        _, prev_t, a_t, a_prev = self._alphas(timestep, num_inference_steps)
         b_t = 1 - a_t
         lamb = ((a_t / (1 - a_t)) ** 0.5).log()
         lamb_next = ((a_prev / (1 - a_prev)) ** 0.5).log()
@@ -172,15 +185,20 @@ class CogVideoXDPMScheduler(_SchedulerBase):
         return c
 
     def step(self, model_output, old_pred_original_sample, timestep, timestep_back, sample, eta=0.0,
-             use_clipped_model_output=False, generator=None, variance_noise=None, return_dict=False):
+             use_clipped_model_output=False, generator=None, variance_noise=None, return_dict=False, num_inference_steps=None):
+        """variance_noise: the noise this step adds, already drawn (a batched call draws one generator's noise for all videos at once and
+        steps every video on its own coefficients); None: drawn here from `generator` as the reference draws it"""
         first = old_pred_original_sample is None
-        c = self.coef(timestep, timestep_back, first, sample.dtype)
+        c = self.coef(timestep, timestep_back, first, sample.dtype, num_inference_steps=num_inference_steps)
         # the reference draws randn once, and a second time on multistep steps (the first draw is then discarded)
         shape, dev = sample.shape, sample.device
 
-        noise = randn_videos(shape, generator, dev, sample.dtype)
-        if c.kind == 2:
+        if variance_noise is not None:
+            noise = variance_noise.to(dev, sample.dtype).contiguous()
+        else:
             noise = randn_videos(shape, generator, dev, sample.dtype)
+            if c.kind == 2:
+                noise = randn_videos(shape, generator, dev, sample.dtype)
         hist = old_pred_original_sample.float().clone() if not first else None
         prev, x0 = self._run(c, model_output, sample, hist, noise)
         return (prev, x0)

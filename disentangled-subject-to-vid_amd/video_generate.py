@@ -27,8 +27,10 @@ def video_latents(vae, video_uint8, generator=None):
 
 
 def _video_tensor(vae, video_uint8):
-    """uint8 [F, H, W, 3] -> [1, 3, F, H, W] in [-1, 1] on the VAE's device and dtype"""
+    """uint8 [F, H, W, 3] -> [1, 3, F, H, W] in [-1, 1] on the VAE's device and dtype; [b, F, H, W, 3] -> [b, 3, F, H, W], one row per video"""
     v = np.asarray(video_uint8)
+    if v.ndim == 5:
+        return torch.cat([_video_tensor(vae, row) for row in v], dim=0)
     if v.ndim != 4 or v.shape[3] != 3:
         raise ValueError("video must be [F, H, W, 3]")
     x = torch.from_numpy(np.ascontiguousarray(v)).float() / 255.0 * 2.0 - 1.0  # [F,H,W,3]
@@ -62,11 +64,15 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
 
     Video-to-video: video_uint8 [F, H, W, 3] (F = 1 or 8k + 1, H x W = height x width) starts the loop from that video at `strength`
     (pipeline_cogvideox_video2video.py).  Draw order: the reference image's posterior sample, the video's posterior sample, the noise.
-    The video's frame count replaces num_frames."""
+    The video's frame count replaces num_frames.
+
+    Per video: guidance_scale, num_inference_steps and strength may each be a list with one entry per video (prompt-major), and video_uint8
+    [b, F, H, W, 3] gives every video its own input video ([F, H, W, 3]: one shared by all); S2VPipeline.__call__ runs every video on the plan
+    of its one-video call."""
     if video_uint8 is not None:
-        vs = np.asarray(video_uint8).shape
-        if len(vs) != 4 or vs[3] != 3:
-            raise ValueError("video_uint8 must be [F, H, W, 3]")
+        vs = np.asarray(video_uint8).shape[-4:]
+        if np.asarray(video_uint8).ndim not in (4, 5) or vs[3] != 3:
+            raise ValueError("video_uint8 must be [F, H, W, 3] or [b, F, H, W, 3]")
         if (vs[1], vs[2]) != (height, width):
             raise ValueError(f"video is {vs[1]}x{vs[2]} but the requested size is {height}x{width}: resize it first (preprocess_video)")
     dev = pipe.transformer.device
@@ -81,7 +87,9 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
         ne = ne.expand(pe.shape[0], -1, -1)
     if video_uint8 is not None:
         pipe_kwargs = dict(pipe_kwargs, video=_video_tensor(pipe.vae, video_uint8), strength=strength)
-        num_frames = np.asarray(video_uint8).shape[0]
+        num_frames = vs[0]
+    elif isinstance(strength, (list, tuple)):   # the pipeline refuses a strength list without a video
+        pipe_kwargs = dict(pipe_kwargs, strength=strength)
     out = pipe(prompt_embeds=pe, negative_prompt_embeds=ne, ref_img_states=ref, height=height, width=width,
                num_frames=num_frames, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                use_dynamic_cfg=use_dynamic_cfg, generator=generator, latents=latents, output_type=output_type,

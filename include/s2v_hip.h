@@ -268,12 +268,21 @@ S2V_API int s2v_add_noise(const void* sample, const void* noise, int64_t n, floa
  * `latents` [1,F,C,H,W], fp32 CFG, scheduler step, round to the model dtype; latents updated IN PLACE.
  * Several videos per call: with a geometry of B = 2b samples (b <= S2V_MAX_BATCH / 2) `latents`, `x0_hist` and `noise` are [b][F,C,H,W] contiguous,
  * sample j embeds video j mod b (no staged copy), the model output is [2b] = [negative x b | positive x b] and the CFG + scheduler step runs on
- * n = b F C H W elements with one timestep, guidance and coefficient set.  B = 1 is one sample without CFG.  A batched call runs on one GPU: the
+ * n = b F C H W elements with one timestep, guidance and coefficient set (per video: s2v_denoise_step_videos).  B = 1 is one sample without CFG.  A batched call runs on one GPU: the
  * CFG-parallel and Ulysses entry points below keep requiring B = 1 or 2.
  * use_graph != 0 captures the launch sequence into a hipGraph on first use and replays it afterwards
  * (timestep and coefficients live in device memory, so one graph serves all steps). */
 S2V_API int s2v_denoise_step(s2v_ctx* ctx, void* latents, float timestep, const s2v_sched_coef* coef_host, float* x0_hist,
                      const void* noise, int32_t use_graph, s2v_stream stream);
+/* The same iteration with the step's scalars PER VIDEO: on a geometry of B = 2b samples [negative x b | positive x b] (B = 1 or 2: b = 1)
+ * `timesteps` and `coefs` are HOST arrays of b entries; sample j runs at timesteps[j mod b] (time embedding and every AdaLN modulation are per
+ * sample) and video k is stepped with coefs[k] -- its own kind, guidance scale and scalars, so a video on its first DPM step (kind 1) may sit
+ * beside videos on multistep steps (kind 2), and DDIM beside DPM.  x0_hist and noise are required as soon as one kind is not 0.  The timesteps
+ * and the coefficient sets each go up in one asynchronous copy; the captured graph does not depend on their values, so one graph serves every
+ * step.  s2v_denoise_step is this call with its scalar repeated b times, bit for bit.  Shard contexts are refused as s2v_denoise_step refuses
+ * them; the CFG-parallel and Ulysses entry points stay single-scalar. */
+S2V_API int s2v_denoise_step_videos(s2v_ctx* ctx, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist,
+                            const void* noise, int32_t use_graph, s2v_stream stream);
 /* pointer to the [B,F,C,H,W] model output of the last s2v_denoise_step (context-owned, model dtype) */
 S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 
