@@ -73,7 +73,10 @@ struct LayerW {
 struct GraphKey {
     void* latents; float* x0; const void* noise;
     int slot;   // -1: the whole step (s2v_denoise_step); 0 / 1: the forward-only graph of s2v_denoise_split_begin writing that half of the CFG pair
-    bool operator==(const GraphKey& o) const { return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot; }
+    const void *z0 = nullptr, *noise0 = nullptr, *mask = nullptr;   // the blend operands of the masked step (s2v_denoise_step_masked); null: unmasked
+    bool operator==(const GraphKey& o) const {
+        return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask;
+    }
 };
 
 // kernel classes of the per-class timing (ProfScope, s2v_profile_*): 8 = the Ulysses packs / unpacks, 9 = the LoRA down-projections
@@ -154,8 +157,13 @@ struct s2v_ctx {
     int64_t e1_stride = 0, e1x_bytes = 0;
     float* t_dev = nullptr;
     SchedCoef* coef_dev = nullptr;
-    // pinned staging ring for per-step scalars
-    struct Stage { float t[S2V_MAX_BATCH]; SchedCoef c[S2V_MAX_BATCH / 2]; };   // a timestep per sample, a coefficient set per video
+    SchedBlend* blend_dev = nullptr;   // the masked step's blend record per video, uploaded beside the coefficient sets
+    // masked video-to-video (s2v_set_blend): the call's clean latents, start noise and latent masks of blend_b videos; held, not copied
+    const void *blend_z0 = nullptr, *blend_noise0 = nullptr;
+    const unsigned char* blend_mask = nullptr;
+    int blend_b = 0;
+    // pinned staging ring for per-step scalars: a timestep per sample, a coefficient set and (masked step) a blend record per video
+    struct Stage { float t[S2V_MAX_BATCH]; SchedCoef c[S2V_MAX_BATCH / 2]; SchedBlend bl[S2V_MAX_BATCH / 2]; };
     Stage* ring = nullptr;
     int ring_pos = 0;
     // graph
@@ -320,9 +328,10 @@ static int create_attn_weights(s2v_ctx* c) {
 static bool create_tail(s2v_ctx* c) {
     hipMalloc((void**)&c->t_dev, S2V_MAX_BATCH * sizeof(float));
     hipMalloc((void**)&c->coef_dev, sizeof(SchedCoef) * (S2V_MAX_BATCH / 2));
+    hipMalloc((void**)&c->blend_dev, sizeof(SchedBlend) * (S2V_MAX_BATCH / 2));
     hipHostMalloc((void**)&c->ring, sizeof(s2v_ctx::Stage) * RING);
     hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking);
-    return c->t_dev && c->coef_dev && c->ring && c->cap_stream;
+    return c->t_dev && c->coef_dev && c->blend_dev && c->ring && c->cap_stream;
 }
 
 extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
@@ -482,6 +491,7 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->ev_join) hipEventDestroy(c->ev_join);
     if (c->ring) hipHostFree(c->ring);
     if (c->coef_dev) hipFree(c->coef_dev);
+    if (c->blend_dev) hipFree(c->blend_dev);
     if (c->t_dev) hipFree(c->t_dev);
     if (c->ws) hipFree(c->ws);
     if (c->e1x) hipFree(c->e1x);
@@ -1583,6 +1593,8 @@ static void fill_coef(SchedCoef& d, const s2v_sched_coef& s) {
     d.m1 = s.m1; d.m2 = s.m2; d.m3 = s.m3; d.m4 = s.m4; d.mn = s.mn; d.pad = 0.f;
 }
 
+static SchedBlend fill_blend(const s2v_blend& s) { return SchedBlend{s.sqrt_alpha, s.sqrt_one_minus_alpha, s.last != 0, 0}; }
+
 extern "C" int s2v_add_noise(const void* sample, const void* noise, int64_t n, float sqrt_alpha, float sqrt_one_minus_alpha, void* out,
                              int32_t dtype, s2v_stream stream) {
     S2V_REQUIRE(sample && noise && out && n > 0, "s2v_add_noise: bad argument");
@@ -1606,16 +1618,48 @@ extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const
     return launch_sched_step(a, dtype, (hipStream_t)stream);
 }
 
+extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
+                                     const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0,
+                                     const void* noise0, const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype,
+                                     s2v_stream stream) {
+    S2V_REQUIRE(coef_host && blend_host && noise_pred && latents_in && latents_out && z0 && noise0 && latent_mask, "s2v_sched_step_masked: null argument");
+    S2V_REQUIRE(F >= 1 && C >= 1 && H >= 1 && W >= 1, "s2v_sched_step_masked: the latent is [F, C, H, W]");
+    S2V_REQUIRE(coef_host->kind == 0 || noise, "s2v_sched_step_masked: DPM step needs a noise tensor");
+    S2V_REQUIRE(coef_host->kind != 2 || x0_hist, "s2v_sched_step_masked: DPM multistep needs x0_hist");
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_sched_step_masked: unsupported dtype");
+    S2V_REQUIRE(!(flags & 4), "s2v_sched_step_masked: the blend runs on the latents rounded to `dtype` (flags bit2, fp32 output, is refused)");
+    (void)c;
+    SchedMaskArgs a{};
+    a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
+    a.noise = noise; a.n = (int64_t)F * C * H * W; a.nvid = 1; a.n_vid = a.n; a.cfg = flags & 1; a.np_f32 = (flags >> 1) & 1;
+    a.coef = nullptr;
+    fill_coef(a.cval, *coef_host);
+    a.z0 = z0; a.noise0 = noise0; a.mask = latent_mask; a.chw = C * H * W; a.hw = H * W; a.mask_vid = F * H * W;
+    a.blend = nullptr; a.bval = fill_blend(*blend_host);
+    return launch_sched_step_masked(a, dtype, (hipStream_t)stream);
+}
+
+extern "C" int s2v_mask_to_latent(const void* mask, int32_t mask_dtype, int32_t F, int32_t H, int32_t W, uint8_t* latent_mask, uint8_t* pixel_mask,
+                                  s2v_stream stream) {
+    S2V_REQUIRE(mask && latent_mask, "s2v_mask_to_latent: null argument");
+    return launch_mask_to_latent(mask, mask_dtype, F, H, W, latent_mask, pixel_mask, (hipStream_t)stream);
+}
+
 // the step's scalars to the device through the next slot of the pinned ring (the uploads are asynchronous: a slot must outlive its copies, RING
 // steps ahead of the device are allowed): b videos, sample j of the S2V_MAX_BATCH slots at timesteps[j mod b], video k's coefficient set coefs[k]
 // (the sets past b repeat the last one).  Whatever b is, the timesteps go up in one copy and the coefficient sets in one
-static int stage_step(s2v_ctx* c, const float* timesteps, const s2v_sched_coef* coefs, int b, hipStream_t st) {
+// The masked step's blend records (blends != null: b of them) ride in the same slot and go up in a third copy
+static int stage_step(s2v_ctx* c, const float* timesteps, const s2v_sched_coef* coefs, int b, hipStream_t st, const s2v_blend* blends = nullptr) {
     s2v_ctx::Stage& sg = c->ring[c->ring_pos];
     c->ring_pos = (c->ring_pos + 1) % RING;
     for (int i = 0; i < S2V_MAX_BATCH; ++i) sg.t[i] = timesteps[i % b];
     for (int k = 0; k < S2V_MAX_BATCH / 2; ++k) fill_coef(sg.c[k], coefs[k < b ? k : b - 1]);
     S2V_CHECK_HIP(hipMemcpyAsync(c->t_dev, sg.t, sizeof(float) * S2V_MAX_BATCH, hipMemcpyHostToDevice, st));
     S2V_CHECK_HIP(hipMemcpyAsync(c->coef_dev, sg.c, sizeof(SchedCoef) * (S2V_MAX_BATCH / 2), hipMemcpyHostToDevice, st));
+    if (blends) {
+        for (int k = 0; k < S2V_MAX_BATCH / 2; ++k) sg.bl[k] = fill_blend(blends[k < b ? k : b - 1]);
+        S2V_CHECK_HIP(hipMemcpyAsync(c->blend_dev, sg.bl, sizeof(SchedBlend) * (S2V_MAX_BATCH / 2), hipMemcpyHostToDevice, st));
+    }
     return 0;
 }
 static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_host, hipStream_t st) {
@@ -1690,6 +1734,49 @@ extern "C" int s2v_denoise_step_videos(s2v_ctx* c, void* latents, const float* t
                                        const void* noise, int32_t use_graph, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps && coefs, "s2v_denoise_step_videos: null argument");
     return denoise_step_impl(c, latents, timesteps, coefs, x0_hist, noise, use_graph, (hipStream_t)stream);
+}
+
+// ---- masked video-to-video: the step with the blend in its last kernel ----------------------------------------------------------------
+extern "C" int s2v_set_blend(s2v_ctx* c, const void* z0, const void* noise0, const uint8_t* latent_mask, int32_t b) {
+    S2V_REQUIRE(c, "s2v_set_blend: null context");
+    const bool clear = !z0 && !noise0 && !latent_mask && b == 0;
+    S2V_REQUIRE(clear || (z0 && noise0 && latent_mask && b >= 1 && b <= S2V_MAX_BATCH / 2),
+                "s2v_set_blend: z0, noise0 and the latent mask of 1 <= b <= 4 videos, or all null with b = 0 to clear");
+    c->blend_z0 = z0; c->blend_noise0 = noise0; c->blend_mask = latent_mask; c->blend_b = b;
+    drop_graph(c);   // the captured step bakes the operands in (they are part of its key)
+    return 0;
+}
+
+static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
+    const int b = c->B / 2;
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st));
+    SchedMaskArgs a{};
+    a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
+    a.nvid = b; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
+    a.n = b * a.n_vid; a.cfg = 1; a.coef = c->coef_dev;
+    a.z0 = c->blend_z0; a.noise0 = c->blend_noise0; a.mask = c->blend_mask;
+    a.chw = c->cfg.out_channels * c->H * c->W; a.hw = c->H * c->W; a.mask_vid = c->F * a.hw; a.blend = c->blend_dev;
+    return launch_sched_step_masked(a, c->dtype, st);
+}
+
+extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
+                                       float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
+    S2V_REQUIRE(c && latents && timesteps && coefs && blends, "s2v_denoise_step_masked: null argument");
+    S2V_REQUIRE(!c->shard, "s2v_denoise_step_masked: a shard context (s2v_set_shard) has no masked step: masked video-to-video runs on one GPU");
+    S2V_REQUIRE(c->ws && c->B != 1, "s2v_denoise_step_masked: a geometry with B = 1 is one sample of a CFG-parallel pair, and the split entries "
+                                    "(s2v_denoise_split_begin / _end, s2v_denoise_step_cfg_parallel) have no masked form: masked video-to-video runs the "
+                                    "CFG pairs of b videos, B = 2b, on one GPU");
+    S2V_REQUIRE(c->B % 2 == 0, "s2v_denoise_step_masked: an even B = 2b (the CFG pairs of b videos) is required");
+    S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step_masked: in/out channels must match");
+    const int b = c->B / 2;
+    S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_masked: s2v_set_blend has not set the blend operands of this geometry's b = B/2 videos");
+    for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step_masked: DPM needs noise and x0_hist");
+    hipStream_t st = (hipStream_t)stream;
+    S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
+    if (!use_graph) return masked_step_launches(c, latents, x0_hist, noise, st);
+    GraphKey key{latents, x0_hist, noise, -1};
+    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask;
+    return launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s); });
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------

@@ -355,6 +355,30 @@ struct SchedArgs {
     int out_f32;              // latents_out is fp32 and un-rounded (scheduler.step's return value)
 };
 int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st);
+// Masked video-to-video (pipeline_stable_diffusion_inpaint.py:1271-1285, the 4-channel branch, as a select): after the step has produced
+// `prev` rounded to T, an element whose latent cell has mask 0 is overwritten -- with add_noise(z0, noise0) at the video's NEXT timestep
+// (add_noise_k's arithmetic: rnd(rnd(sqrt_a * z0) + rnd(sqrt_1ma * noise0))), or on the video's last step with z0's own bits.  x0_hist
+// keeps the unblended x0.  The records sit beside the coefficient sets in device memory, so the captured graph serves every step.
+struct SchedBlend {
+    float sqrt_a, sqrt_1ma;   // Scheduler.add_noise_scalars(t_next, T): already taken in T by the host
+    int last;                 // the video's last step: kept elements are z0, bit for bit (coefficients (1, 0) would turn -0 into +0)
+    int pad;
+};
+struct SchedMaskArgs : SchedArgs {     // latents_out is T (out_f32 is refused)
+    const void* z0;            // [n] model dtype: the clean input latents, scaled
+    const void* noise0;        // [n] model dtype: the noise that started the loop
+    const unsigned char* mask; // [nvid][F * hw]: 1 repaint, 0 keep; one plane for all channels of a video [F][C][hw]
+    int chw, hw;               // C * H * W and H * W of the latent: element j of a video is frame j / chw, cell j % hw of the plane
+    int mask_vid;              // F * H * W: the cells of one video's plane
+    const SchedBlend* blend;   // device pointer to nvid consecutive records, or null => use bval (nvid = 1)
+    SchedBlend bval;
+};
+int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st);
+// pixel mask [F][H][W] (mdtype: S2V_F32 / S2V_BF16 / S2V_F16 binarised at 0.5, or S2V_MASK_U8: non-zero) -> latent mask uint8 [Fl][H/8][W/8],
+// a cell 1 if ANY pixel it covers is 1: the 8 x 8 block of pixel frame 0 (latent frame 0) or of pixel frames 4j-3 .. 4j (latent frame j >= 1),
+// the causal grouping of the VAE encode; Fl = (F - 1) / 4 + 1.  pixel_out (may be null): the binarised pixel mask, uint8 [F][H][W]
+#define S2V_MASK_U8 3
+int launch_mask_to_latent(const void* mask, int mdtype, int F, int H, int W, unsigned char* latent_out, unsigned char* pixel_out, hipStream_t st);
 int launch_add_noise(const void* x, const void* noise, int64_t n, float sqrt_a, float sqrt_1ma, void* out, int dtype, hipStream_t st);
 // dst[i] = (Tdst) src[i]
 int launch_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t st);

@@ -771,6 +771,44 @@ __global__ void postprocess_u8_k(const T* v, int C, int F, int H, int W, unsigne
         out[i] = (unsigned char)(int)x;
     }
 }
+// Paste-back of masked video-to-video: the same two post-processes as a select per frame and pixel, for all C channels -- of the decoded
+// video v (T) where the binarised pixel mask [F][H][W] is 1, of the input video `keep` (its own dtype kdt) where it is 0.  Each side is
+// post-processed in its own dtype, so a kept pixel is exactly what the unmasked kernel makes of the input video.
+template <typename T>
+__device__ __forceinline__ float postprocess_one(const T* v, int64_t idx) {
+    const float x = ET<T>::rnd(ET<T>::rnd(ET<T>::ld(v + idx) / 2.0f) + 0.5f);
+    return fminf(fmaxf(x, 0.f), 1.f);
+}
+__device__ __forceinline__ float postprocess_any(const void* v, int dt, int64_t idx) {
+    if (dt == S2V_BF16) return postprocess_one((const bf16_t*)v, idx);
+    if (dt == S2V_F16) return postprocess_one((const f16_t*)v, idx);
+    return postprocess_one((const float*)v, idx);
+}
+template <typename T, typename O>
+__global__ void postprocess_masked_k(const T* v, const void* keep, int kdt, const unsigned char* mask, int C, int F, int H, int W, O* out) {
+    const int64_t total = (int64_t)C * F * H * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        const int64_t p = i / C;  // (f, y, x)
+        const int64_t idx = (int64_t)c * F * H * W + p;
+        const float x = mask[p] ? postprocess_one(v, idx) : postprocess_any(keep, kdt, idx);
+        if constexpr (std::is_same<O, unsigned char>::value) out[i] = (unsigned char)(int)(x * 255.0f);   // as postprocess_u8_k
+        else out[i] = x;
+    }
+}
+int launch_postprocess_masked(const void* v, const void* keep, int keep_dtype, const unsigned char* mask, int C, int F, int H, int W, void* out,
+                              int out_u8, int dtype, hipStream_t st) {
+    const int64_t total = (int64_t)C * F * H * W;
+    if (out_u8) {
+        S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((postprocess_masked_k<T, unsigned char>), dim3(grid_for(total)), dim3(256), 0, st, (const T*)v, keep,
+                           keep_dtype, mask, C, F, H, W, (unsigned char*)out))
+    } else {
+        S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((postprocess_masked_k<T, float>), dim3(grid_for(total)), dim3(256), 0, st, (const T*)v, keep,
+                           keep_dtype, mask, C, F, H, W, (float*)out))
+    }
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 int launch_postprocess_u8(const void* v, int C, int F, int H, int W, unsigned char* out, int dtype, hipStream_t st) {
     const int64_t total = (int64_t)C * F * H * W;
     S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(postprocess_u8_k<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)v, C, F, H, W, out))

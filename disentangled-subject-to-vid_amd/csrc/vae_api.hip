@@ -775,6 +775,26 @@ extern "C" int s2v_vae_postprocess_u8(const void* video, int32_t C, int32_t F, i
     return launch_postprocess_u8(video, C, F, H, W, out, dtype, (hipStream_t)stream);
 }
 
+static int postprocess_masked(const char* fn, const void* video, const void* keep, int32_t keep_dtype, const uint8_t* mask, int32_t C, int32_t F,
+                              int32_t H, int32_t W, void* out, int out_u8, int32_t dtype, s2v_stream stream) {
+    static thread_local std::string m;
+    auto bad = [&](const char* why) { m = std::string(fn) + ": " + why; return m.c_str(); };
+    S2V_REQUIRE(video && keep && mask && out, bad("null argument"));
+    S2V_REQUIRE(C >= 1 && F >= 1 && H >= 1 && W >= 1, bad("bad shape"));
+    for (int dt : {dtype, keep_dtype}) S2V_REQUIRE(dt == S2V_F32 || dt == S2V_BF16 || dt == S2V_F16, bad("unsupported dtype"));
+    return launch_postprocess_masked(video, keep, keep_dtype, mask, C, F, H, W, out, out_u8, dtype, (hipStream_t)stream);
+}
+
+extern "C" int s2v_vae_postprocess_masked(const void* video, const void* keep, int32_t keep_dtype, const uint8_t* mask, int32_t C, int32_t F,
+                                          int32_t H, int32_t W, float* out, int32_t dtype, s2v_stream stream) {
+    return postprocess_masked("s2v_vae_postprocess_masked", video, keep, keep_dtype, mask, C, F, H, W, out, 0, dtype, stream);
+}
+
+extern "C" int s2v_vae_postprocess_u8_masked(const void* video, const void* keep, int32_t keep_dtype, const uint8_t* mask, int32_t C, int32_t F,
+                                             int32_t H, int32_t W, uint8_t* out, int32_t dtype, s2v_stream stream) {
+    return postprocess_masked("s2v_vae_postprocess_u8_masked", video, keep, keep_dtype, mask, C, F, H, W, out, 1, dtype, stream);
+}
+
 extern "C" int s2v_vae_postprocess(const void* video, int32_t C, int32_t F, int32_t H, int32_t W, float* out, int32_t dtype,
                                    s2v_stream stream) {
     S2V_REQUIRE(video && out, "s2v_vae_postprocess: null argument");

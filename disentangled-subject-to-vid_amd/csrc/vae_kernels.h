@@ -35,4 +35,7 @@ int launch_paste(const void* tile, int Ht, int Wt, int ch, int cw, void* out, in
                  int dtype, hipStream_t st);
 int launch_postprocess(const void* v, int C, int F, int H, int W, float* out, int dtype, hipStream_t st);
 int launch_postprocess_u8(const void* v, int C, int F, int H, int W, unsigned char* out, int dtype, hipStream_t st);
+// the two above as a select: decoded video v where mask [F][H][W] (uint8, 0 / 1) is 1, the input video `keep` (dtype keep_dtype) where it is 0
+int launch_postprocess_masked(const void* v, const void* keep, int keep_dtype, const unsigned char* mask, int C, int F, int H, int W, void* out,
+                              int out_u8, int dtype, hipStream_t st);
 int launch_conv_w_repack(const void* src, int sdt, int cout, int cin, int taps, void* dst, int ddt, hipStream_t st);

@@ -30,6 +30,29 @@ def _per_video(name, x, b):
     return xs
 
 
+def mask_to_latent(mask, device=None):
+    """pixel masks [r,F,H,W] (uint8 / bool: non-zero repaints; float32 / bfloat16 / float16: binarised at 0.5 as image_processor.py:535-536
+    does; anything else goes through float32) -> (latent mask uint8 [r,(F-1)/4+1,H/8,W/8], binarised pixel mask uint8 [r,F,H,W]), one
+    s2v_mask_to_latent launch per row: a latent cell repaints if ANY pixel it covers does (include/s2v_hip.h)"""
+    if mask.ndim != 4:
+        raise _lib.S2VError(f"mask_to_latent: the masks must be [rows, F, H, W], got {tuple(mask.shape)}")
+    r, F, H, W = mask.shape
+    if (F - 1) % 4 or H % 8 or W % 8 or min(r, H, W) < 1:
+        raise _lib.S2VError(f"mask_to_latent: F = 4k + 1 frames of H x W pixels, both multiples of 8, got {tuple(mask.shape)}")
+    m = mask.to(device or mask.device)
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8) if m.is_contiguous() else m.to(torch.uint8)
+    elif m.dtype != torch.uint8 and m.dtype not in _lib.DTYPE_OF:
+        m = m.float()
+    m = m.contiguous()
+    md = _lib.MASK_DTYPE_U8 if m.dtype == torch.uint8 else _lib.DTYPE_OF[m.dtype]
+    lat = torch.empty((r, (F - 1) // 4 + 1, H // 8, W // 8), dtype=torch.uint8, device=m.device)
+    pix = torch.empty((r, F, H, W), dtype=torch.uint8, device=m.device)
+    for k in range(r):
+        _lib.check(_lib.lib().s2v_mask_to_latent(_lib.ptr(m[k]), md, F, H, W, _lib.ptr(lat[k]), _lib.ptr(pix[k]), _lib.stream_ptr()))
+    return lat, pix
+
+
 class S2VEngine:
     def __init__(self, cfg: TransformerConfig, dtype=torch.bfloat16, device="cuda:0", force_simple=False, kind=_lib.CTX_MODEL):
         """kind: _lib.CTX_MODEL (a whole model), or one of the two halves of the model-wide AttnProcessor (include/s2v_hip.h, S2V_CTX_*):
@@ -447,11 +470,36 @@ class S2VEngine:
         _lib.check(_lib.lib().s2v_set_attn_p_format(self._h, 1 if fmt == "f16" else 0))
         self.attn_p_format = fmt
 
-    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
+    # ---- masked video-to-video (include/s2v_hip.h: s2v_set_blend, s2v_denoise_step_masked) ---------------------------------------------
+    _blend = None
+
+    def set_blend(self, z0, noise0, latent_mask):
+        """the blend operands of a masked call for the b = B/2 videos of the geometry: z0 and noise0 [b,F,C,H,W] in the model dtype, latent_mask
+        uint8 [b,F,H,W] (mask_to_latent); the tensors are held until clear_blend or the next set_blend.  Drops a captured step"""
+        B, T, F, H, W = self.geometry
+        b = B // 2
+        want = (b, F, self.cfg.in_channels, H, W)
+        for name, x in (("z0", z0), ("noise0", noise0)):
+            if x.dtype != self.dtype or tuple(x.shape) != want or not x.is_contiguous():
+                raise _lib.S2VError(f"set_blend: {name} must be contiguous {list(want)} in the model dtype for the b = B/2 videos of the geometry, "
+                                    f"got {list(x.shape)} {x.dtype}")
+        if latent_mask.dtype != torch.uint8 or tuple(latent_mask.shape) != (b, F, H, W) or not latent_mask.is_contiguous():
+            raise _lib.S2VError(f"set_blend: latent_mask must be contiguous uint8 {[b, F, H, W]}, got {list(latent_mask.shape)} {latent_mask.dtype}")
+        _lib.check(_lib.lib().s2v_set_blend(self._h, _lib.ptr(z0), _lib.ptr(noise0), _lib.ptr(latent_mask), b))
+        self._blend = (z0, noise0, latent_mask)
+
+    def clear_blend(self):
+        if self._blend is not None:
+            torch.cuda.current_stream().synchronize()   # the last masked step still reads the tensors about to be released
+            _lib.check(_lib.lib().s2v_set_blend(self._h, None, None, None, 0))
+            self._blend = None
+
+    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
         [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
         (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
-        coef[k] -- its own kind, guidance and scalars (s2v_denoise_step_videos); a scalar beside a sequence is repeated"""
+        coef[k] -- its own kind, guidance and scalars (s2v_denoise_step_videos); a scalar beside a sequence is repeated.
+        blend: the masked step (s2v_denoise_step_masked, after set_blend): one _lib.BlendC, or a sequence of b, video k blended with blend[k]"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
@@ -462,17 +510,22 @@ class S2VEngine:
             for name, x in (("latents", latents), ("x0_hist", x0_hist), ("noise", noise)):
                 if x is not None and (tuple(x.shape) != want or not x.is_contiguous()):
                     raise _lib.S2VError(f"denoise_step: {name} must be contiguous {list(want)} for {B // 2} videos per call, got {list(x.shape)}")
-        per_video = not isinstance(coef, _lib.SchedCoefC) or _is_seq(timestep)
+        per_video = blend is not None or not isinstance(coef, _lib.SchedCoefC) or _is_seq(timestep)
         if per_video:
             b = B // 2 if B >= 2 else 1
             ts = _per_video("timestep", timestep, b)
             cs = _per_video("coef", coef, b)
             t_arr = (ctypes.c_float * b)(*[float(t) for t in ts])
             c_arr = (_lib.SchedCoefC * b)(*cs)
+            if blend is not None:
+                b_arr = (_lib.BlendC * b)(*_per_video("blend", blend, b))
         auto = self._attn_auto_pending
         if auto:
             self.attn_slow_stats(reset=True)
-        if per_video:
+        if blend is not None:
+            _lib.check(_lib.lib().s2v_denoise_step_masked(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
+                                                          int(use_graph and not auto), _lib.stream_ptr()))
+        elif per_video:
             _lib.check(_lib.lib().s2v_denoise_step_videos(self._h, _lib.ptr(latents), t_arr, c_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                           int(use_graph and not auto), _lib.stream_ptr()))
         else:

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
+from .engine import mask_to_latent
 from .schedulers import CogVideoXDPMScheduler, randn_videos  # noqa: F401
 
 
@@ -180,9 +181,44 @@ class S2VPipeline:
         t_start = max(num_inference_steps - init_timestep, 0)
         return timesteps[t_start * order:], num_inference_steps - t_start
 
-    def prepare_video_latents(self, video, dtype, device, generator, timestep):
+    @staticmethod
+    def check_mask(mask, video, b, cfg_parallel=None, ulysses=None):
+        """the pixel masks of a masked video-to-video call as [1 | b, F, H, W] (one row: shared by all b videos), after every refusal (no
+        device is touched): a mask without a video, on the paths that stay unmasked, of another size than the video, with a row count that
+        is neither 1 nor b"""
+        if video is None:
+            raise ValueError("`mask` applies only together with `video`: masked video-to-video keeps the input video outside the mask "
+                             "(a mask on a text-to-video call has nothing to keep)")
+        for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+            if arg is not None:
+                raise ValueError(f"`mask` together with `{name}`: the masked step runs on one GPU; CFG-parallel and Ulysses stay unmasked")
+        m = mask[:, 0] if mask.ndim == 5 and mask.shape[1] == 1 else mask
+        F, H, W = video.shape[2:]
+        if m.ndim != 4 or tuple(m.shape[1:]) != (F, H, W):
+            raise ValueError(f"`mask` must be [rows, 1, F, H, W] or [rows, F, H, W] with the video's F x H x W = {F} x {H} x {W} (one value per "
+                             f"frame and pixel), got {tuple(mask.shape)}")
+        if m.shape[0] not in (1, b):
+            raise ValueError(f"`mask` has {m.shape[0]} rows for b = {b} videos: one mask per video, or one row shared by all")
+        return m
+
+    @staticmethod
+    def blend_plan(scheduler, plan, dtype, device="cpu"):
+        """the masked step's record (scheduler.blend_record) for every step of a video_plan: step i blends at the video's NEXT timestep
+        t[i + 1], the last step is flagged and keeps the clean latents"""
+        ts = plan["timesteps"]
+        return [scheduler.blend_record(ts[i + 1] if i + 1 < len(ts) else None, dtype, device) for i in range(len(ts))]
+
+    @staticmethod
+    def _blend_torch(scheduler, latents, z0, noise0, keep, next_timestep):
+        """the blend of fused=False on latents [n,...] after the step: where keep (bool, broadcast over the channels) the input's latents
+        noised to next_timestep with the noise that started the loop, or, after the last step (None), the clean ones"""
+        proper = z0 if next_timestep is None else scheduler.add_noise(z0, noise0, next_timestep)
+        return torch.where(keep, proper, latents)
+
+    def prepare_video_latents(self, video, dtype, device, generator, timestep, parts=False):
         """pipeline_cogvideox_video2video.py:345-398 for one video: the posterior sample of the encoded video, then the noise, both drawn
-        from `generator` in that order; add_noise(scaling_factor * z0, noise, timestep) * init_noise_sigma -> [1,Fl,C,h,w]"""
+        from `generator` in that order; add_noise(scaling_factor * z0, noise, timestep) * init_noise_sigma -> [1,Fl,C,h,w]; parts: also the
+        scaled z0 and the noise (what a masked call keeps)"""
         vae = self.vae
         z0 = vae.encode(video).latent_dist.sample(generator)              # [1,C,Fl,h,w]
         # the scaling as the reference writes it (and as video_generate.reference_latents does): torch's scalar semantics for the dtype
@@ -190,6 +226,8 @@ class S2VPipeline:
         gdev = generator.device if generator is not None else device
         noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
         latents = self.scheduler.add_noise(z0.to(device), noise, timestep)
+        if parts:
+            return latents * self.scheduler.init_noise_sigma, z0.to(device), noise
         return latents * self.scheduler.init_noise_sigma
 
     @torch.no_grad()
@@ -197,7 +235,7 @@ class S2VPipeline:
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
-                 video=None, strength=0.8, num_videos_per_prompt=1):
+                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -216,7 +254,15 @@ class S2VPipeline:
         split over the ranks, attention sharded by heads); same arguments on every rank, same latents back.  fused mode only, not with cfg_parallel.
         video: video-to-video (pipeline_cogvideox_video2video.py): [1,3,F,H,W] (or [b,3,F,H,W]) in [-1,1] with F = 1 or 8k + 1 and H x W = height x width.  The
         loop starts from the encoded video noised to the first of the last int(num_inference_steps * strength) timesteps; num_frames comes
-        from the video.  strength applies only together with a video (text-to-video calls run every timestep, as before)."""
+        from the video.  strength applies only together with a video (text-to-video calls run every timestep, as before).
+        mask: masked video-to-video -- [1 | b, 1, F, H, W] or [1 | b, F, H, W] over the input video's frames and pixels (b rows: one mask per
+        video; one row: shared), binarised at 0.5: 1 repaints, 0 keeps the input.  A latent cell repaints if any pixel it covers does.  The
+        start is video-to-video's; after every step the kept latents are the input's, noised to the video's next timestep with the noise that
+        started the loop, and after the last step the clean ones (pipeline_stable_diffusion_inpaint.py:1271-1285); a step-end callback sees
+        the blended latents.  paste_back (frames only): where the PIXEL mask is 0 the frames are the post-processed input video, exactly.
+        Only with `video`; not with cfg_parallel= or ulysses=."""
+        if mask is not None and video is None:
+            self.check_mask(mask, None, 1)
         per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength))
         if not isinstance(strength, (list, tuple)) and (strength < 0 or strength > 1):
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
@@ -253,11 +299,13 @@ class S2VPipeline:
         if not isinstance(guidance_scale, (list, tuple)) and guidance_scale <= 1.0:
             raise RuntimeError("guidance_scale must be > 1: eval=True duplicates the reference tokens for the CFG pair")
         b = self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents, generator, video, cfg_parallel, ulysses)
+        if mask is not None:
+            mask = self.check_mask(mask, video, b, cfg_parallel, ulysses)
         if per_video or (video is not None and b > 1):   # every video on its own plan; scalars and one input video stay on the path below
             lists = self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)
             return self._call_videos(b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg,
                                      generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
-                                     callback_on_step_end_tensor_inputs, video, num_videos_per_prompt)
+                                     callback_on_step_end_tensor_inputs, video, num_videos_per_prompt, mask, paste_back)
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)  # [negative x b | positive x b] (:196)
@@ -267,7 +315,8 @@ class S2VPipeline:
             timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, timesteps, strength, sch.order)
             if len(timesteps) == 0:
                 raise ValueError(f"strength {strength} keeps none of the {sch.num_inference_steps} timesteps")
-            latents = self.prepare_video_latents(video, dt, dev, generator, timesteps[:1]).to(dt).contiguous()
+            latents, z0, noise0 = self.prepare_video_latents(video, dt, dev, generator, timesteps[:1], parts=True)
+            latents = latents.to(dt).contiguous()
         else:
             latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b).to(dt).contiguous()
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
@@ -281,6 +330,13 @@ class S2VPipeline:
             n = (H // 2) * (W // 2)
             cos, sin = torch.from_numpy(cos).to(dev), torch.from_numpy(sin).to(dev)
             ref_rope, rope = (cos[:n], sin[:n]), (cos[n:], sin[n:])
+        paste = None
+        if mask is not None:   # one video (several go through _call_videos): its blend operands, held for the whole call
+            lat_mask, pix_mask = mask_to_latent(mask, dev)
+            z0, noise0 = z0.to(dt).contiguous(), noise0.to(dt).contiguous()
+            keep = (lat_mask == 0)[:, :, None]   # [1,Fl,1,h,w]: fused=False's select
+            nexts = [timesteps[i + 1] if i + 1 < len(timesteps) else None for i in range(len(timesteps))]
+            paste = (video, pix_mask) if paste_back else None
 
         if ulysses is not None and cfg_parallel is not None:
             raise ValueError("ulysses and cfg_parallel do not compose yet: a Ulysses group runs both samples of the CFG pair on every rank")
@@ -301,64 +357,74 @@ class S2VPipeline:
             eng.set_conditioning(my_text, ref)
             x0_hist = torch.zeros(latents.shape, dtype=torch.float32, device=dev) if is_dpm else None
             noise = torch.empty_like(latents) if is_dpm else None
+            if mask is not None:
+                eng.set_blend(z0, noise0, lat_mask)
         old = None
-        for i, t in enumerate(timesteps):
-            if self.interrupt:
-                break
-            g = guidance_scale
-            if use_dynamic_cfg:
-                g = 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - i) / num_inference_steps) ** 5.0)) / 2)
-            self._guidance_scale = g
-            if fused:
-                if is_dpm:
-                    coef = sch.coef(t, timesteps[i - 1] if i > 0 else None, i == 0, dt, g)
-                    self._draw(noise, generator)
-                    if coef.kind == 2:
-                        self._draw(noise, generator)  # the reference discards its first draw on multistep steps
-                else:
-                    coef = sch.coef(t, dt, g)
-                if ulysses is not None:
-                    ulysses.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
-                elif cfg_parallel is None:
-                    eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph)
-                else:
-                    cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
-            else:
-                x = torch.cat([latents] * 2)
-                x = sch.scale_model_input(x, t)
-                noise_pred = tr(hidden_states=x, encoder_hidden_states=text, ref_img_states=ref_seam,
-                                timestep=t.expand(2 * b), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
-                                return_dict=False, eval=True)[0].float()
-                u, c = noise_pred.chunk(2)
-                noise_pred = u + g * (c - u)
-                if not is_dpm:
-                    latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
-                else:
-                    latents, old = sch.step(noise_pred, old, t, timesteps[i - 1] if i > 0 else None, latents,
-                                            generator=generator, return_dict=False)
-                latents = latents.to(dt)
-            if callback_on_step_end is not None:
-                # custom_cogvideox_pipe.py:298-305: the callback sees the requested tensors -- `prompt_embeds` is, at that point of
-                # the reference loop, the CONCATENATED [negative | positive] pair (:196) -- and what it returns replaces them for
-                # the following steps (a returned `negative_prompt_embeds` is rebound there too, but nothing reads it after :196).
-                # A callback that returns nothing keeps everything (the reference would raise on `None.get`).
-                avail = {"latents": latents, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
-                outs = callback_on_step_end(self, i, t, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
-                new_lat = outs.get("latents", latents)
-                if new_lat is not latents:
-                    if fused:  # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
-                        latents.copy_(new_lat.to(dev, dt).reshape(latents.shape))
+        try:
+            for i, t in enumerate(timesteps):
+                if self.interrupt:
+                    break
+                g = guidance_scale
+                if use_dynamic_cfg:
+                    g = 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - i) / num_inference_steps) ** 5.0)) / 2)
+                self._guidance_scale = g
+                if fused:
+                    if is_dpm:
+                        coef = sch.coef(t, timesteps[i - 1] if i > 0 else None, i == 0, dt, g)
+                        self._draw(noise, generator)
+                        if coef.kind == 2:
+                            self._draw(noise, generator)  # the reference discards its first draw on multistep steps
                     else:
-                        latents = new_lat.to(dev, dt)
-                new_text = outs.get("prompt_embeds", text)
-                if new_text is not text:
-                    text = new_text.to(dev, dt)
-                    if fused:  # the hoisted text projection follows the new embeddings
-                        eng.set_conditioning(text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1], ref)
-                negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
-        return self._finish(latents, fused, output_type, return_dict)
+                        coef = sch.coef(t, dt, g)
+                    if ulysses is not None:
+                        ulysses.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
+                    elif cfg_parallel is None:
+                        eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph,
+                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev))
+                    else:
+                        cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
+                else:
+                    x = torch.cat([latents] * 2)
+                    x = sch.scale_model_input(x, t)
+                    noise_pred = tr(hidden_states=x, encoder_hidden_states=text, ref_img_states=ref_seam,
+                                    timestep=t.expand(2 * b), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
+                                    return_dict=False, eval=True)[0].float()
+                    u, c = noise_pred.chunk(2)
+                    noise_pred = u + g * (c - u)
+                    if not is_dpm:
+                        latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
+                    else:
+                        latents, old = sch.step(noise_pred, old, t, timesteps[i - 1] if i > 0 else None, latents,
+                                                generator=generator, return_dict=False)
+                    latents = latents.to(dt)
+                    if mask is not None:
+                        latents = self._blend_torch(sch, latents, z0, noise0, keep, nexts[i])
+                if callback_on_step_end is not None:
+                    # custom_cogvideox_pipe.py:298-305: the callback sees the requested tensors -- `prompt_embeds` is, at that point of
+                    # the reference loop, the CONCATENATED [negative | positive] pair (:196) -- and what it returns replaces them for
+                    # the following steps (a returned `negative_prompt_embeds` is rebound there too, but nothing reads it after :196).
+                    # A callback that returns nothing keeps everything (the reference would raise on `None.get`).
+                    avail = {"latents": latents, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
+                    outs = callback_on_step_end(self, i, t, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
+                    new_lat = outs.get("latents", latents)
+                    if new_lat is not latents:
+                        if fused:  # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
+                            latents.copy_(new_lat.to(dev, dt).reshape(latents.shape))
+                        else:
+                            latents = new_lat.to(dev, dt)
+                    new_text = outs.get("prompt_embeds", text)
+                    if new_text is not text:
+                        text = new_text.to(dev, dt)
+                        if fused:  # the hoisted text projection follows the new embeddings
+                            eng.set_conditioning(text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1], ref)
+                    negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
+        finally:
+            if fused and mask is not None:
+                eng.clear_blend()
+        return self._finish(latents, fused, output_type, return_dict, paste)
 
-    def _finish(self, latents, fused, output_type, return_dict):
+    def _finish(self, latents, fused, output_type, return_dict, paste=None):
+        """paste (masked video-to-video's paste-back): (the input videos [1 | b,3,F,H,W], the binarised pixel masks [1 | b,F,H,W])"""
         tr = self.transformer
         # attn_p_format "auto" settled on the census of the FIRST step; the whole run's census is kept for the caller and, should later (less
         # noisy, sharper) steps have taken the fp16 kernel's slow path too often, the next video of this engine runs on bf16 probabilities
@@ -375,14 +441,17 @@ class S2VPipeline:
             if self.vae is None:
                 raise ValueError("a VAE object is needed for output_type != 'latent'")
             video = self.decode_latents(latents)
-            video = self.vae.postprocess_video(video, output_type)
+            if paste is None:
+                video = self.vae.postprocess_video(video, output_type)
+            else:
+                video = self.vae.postprocess_video(video, output_type, keep=paste[0], pixel_mask=paste[1])
         return (video,) if not return_dict else {"frames": video}
 
-    def prepare_videos_latents(self, video, dtype, device, generator, first_timesteps):
+    def prepare_videos_latents(self, video, dtype, device, generator, first_timesteps, parts=False):
         """pipeline_cogvideox_video2video.py:374-392 for b = len(first_timesteps) videos: video [v,3,F,H,W], v = b or one row shared by all.
         One generator (or none): one posterior sample per video row in order, then the noise of all b videos in one draw.  A list: video k's
         posterior sample and noise both come from generator k (a shared row is encoded once and sampled per generator).  add_noise at every
-        video's own first timestep; the VAE encodes one video at a time -> [b,Fl,C,h,w]"""
+        video's own first timestep; the VAE encodes one video at a time -> [b,Fl,C,h,w]; parts: also the scaled z0 and the noise of the b videos"""
         vae, b, v = self.vae, len(first_timesteps), video.shape[0]
         scaled = lambda z: vae.config.scaling_factor * z.to(dtype).permute(0, 2, 1, 3, 4).contiguous()   # as prepare_video_latents writes it
         if isinstance(generator, (list, tuple)):
@@ -400,15 +469,19 @@ class S2VPipeline:
             gdev = generator.device if generator is not None else device
             noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
         latents = self.scheduler.add_noise(z0.to(device), noise, torch.stack([torch.as_tensor(t) for t in first_timesteps]))
+        if parts:
+            return latents * self.scheduler.init_noise_sigma, z0.to(device), noise
         return latents * self.scheduler.init_noise_sigma
 
     def _call_videos(self, b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg, generator,
                      latents, output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, video,
-                     num_videos_per_prompt):
+                     num_videos_per_prompt, mask=None, paste_back=True):
         """b videos, each on the plan of its one-video call (video_plan): iteration i applies step i of every video that still has one.  The
         videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers; when
         the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
-        latents stay where they are.  Results, and everything the callback sees, are in the caller's order"""
+        latents stay where they are.  Results, and everything the callback sees, are in the caller's order.
+        mask [1 | b,F,H,W] (check_mask): z0, noise0 and the latent masks follow the internal order and the shrinking prefix exactly as the latents
+        do; video k blends at the next timestep of its own plan and is flagged on its own last step"""
         tr, sch = self.transformer, self.scheduler
         dt, dev = tr.dtype, tr.device
         guidance, counts, strengths = lists
@@ -420,11 +493,22 @@ class S2VPipeline:
         gen_list = isinstance(generator, (list, tuple))
         text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)   # caller's order, what the callback sees
         if video is not None:
-            latents = self.prepare_videos_latents(video, dt, dev, generator, [p["timesteps"][0] for p in plans])
+            latents = self.prepare_videos_latents(video, dt, dev, generator, [p["timesteps"][0] for p in plans], parts=mask is not None)
+            if mask is not None:
+                latents, z0, noise0 = latents
         else:
             latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b)
         latents = latents.to(dt)[order].contiguous()   # internal order from here on
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
+        paste = None
+        if mask is not None:
+            lat_mask, pix_mask = mask_to_latent(mask, dev)
+            paste = (video, pix_mask) if paste_back else None
+            if lat_mask.shape[0] != b:
+                lat_mask = lat_mask.expand(b, -1, -1, -1)
+            z0, noise0, lat_mask = z0.to(dt)[order].contiguous(), noise0.to(dt)[order].contiguous(), lat_mask[order].contiguous()
+            keep = (lat_mask == 0)[:, :, None]   # [b,Fl,1,h,w]: fused=False's select
+            blends = [self.blend_plan(sch, plans[k], dt, dev) for k in order]
         ref = ref_img_states.to(dev, dt)
         if ref.shape[0] > 1:
             ref = ref[order].contiguous()
@@ -449,6 +533,8 @@ class S2VPipeline:
             eng.set_geometry(2 * a, text.shape[1], F, H, W)
             eng.prepare_tables(height, width)
             eng.set_conditioning(active_text(a), active_ref(a, False))
+            if mask is not None:   # prefixes of the same buffers, as latents[:a] is
+                eng.set_blend(z0[:a], noise0[:a], lat_mask[:a])
 
         lens = [len(plans[k]["steps"]) for k in order]
         active = b
@@ -459,68 +545,77 @@ class S2VPipeline:
         old = [None] * b
         last_t = [plans[k]["timesteps"][0] for k in order]
         seam_key = seam_text = seam_ref = None   # the seam re-conditions when its tensors change: new ones only when the rows or the text do
-        for i in range(lens[0]):
-            if self.interrupt:
-                break
-            a = sum(1 for n_k in lens if n_k > i)
-            if a != active:   # the shortest plans have ended: the batch shrinks to the videos that go on
-                active = a
+        try:
+            for i in range(lens[0]):
+                if self.interrupt:
+                    break
+                a = sum(1 for n_k in lens if n_k > i)
+                if a != active:   # the shortest plans have ended: the batch shrinks to the videos that go on
+                    active = a
+                    if fused:
+                        set_active(a)
+                steps = [plans[order[p]]["steps"][i] for p in range(a)]
+                for p, st in enumerate(steps):
+                    last_t[p] = st["t"]
+                self._guidance_scale = [plans[k]["steps"][min(i, len(plans[k]["steps"]) - 1)]["guidance"] for k in range(b)]
                 if fused:
-                    set_active(a)
-            steps = [plans[order[p]]["steps"][i] for p in range(a)]
-            for p, st in enumerate(steps):
-                last_t[p] = st["t"]
-            self._guidance_scale = [plans[k]["steps"][min(i, len(plans[k]["steps"]) - 1)]["guidance"] for k in range(b)]
-            if fused:
-                if is_dpm and gen_list:   # video p draws from its own generator, as often as its one-video call does at this step
-                    for p, st in enumerate(steps):
-                        for _ in range(st["draws"]):
-                            self._draw(noise[p:p + 1], gens[p])
-                elif is_dpm:
-                    for _ in range(steps[0]["draws"]):
-                        self._draw(noise[:a], generator)
-                eng.denoise_step(latents[:a], [float(st["t"]) for st in steps], [st["coef"] for st in steps],
-                                 x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph)
-            else:
-                x = torch.cat([latents[:a]] * 2)
-                if seam_key is None or seam_key[0] != a or seam_key[1] is not text:
-                    seam_key, seam_text, seam_ref = (a, text), active_text(a), active_ref(a, True)
-                noise_pred = tr(hidden_states=x, encoder_hidden_states=seam_text, ref_img_states=seam_ref,
-                                timestep=torch.stack([st["t"] for st in steps]).repeat(2), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
-                                return_dict=False, eval=True)[0].float()
-                u, c = noise_pred.chunk(2)
-                drawn = None
-                if is_dpm and not gen_list:   # one stream: the noise of all videos in one draw, the last of this step's draws
-                    for _ in range(steps[0]["draws"]):
-                        drawn = randn_videos(latents[:a].shape, generator, dev, dt)
-                for p, st in enumerate(steps):   # the one-video call's own sequence on video p
-                    n_k = plans[order[p]]["num_inference_steps"]
-                    np_p = u[p:p + 1] + st["guidance"] * (c[p:p + 1] - u[p:p + 1])
-                    if not is_dpm:
-                        new = sch.step(np_p, st["t"], latents[p:p + 1], return_dict=False, num_inference_steps=n_k)[0]
-                    else:
-                        new, old[p] = sch.step(np_p, old[p], st["t"], st["t_back"], latents[p:p + 1], generator=gens[p] if gen_list else None,
-                                               variance_noise=None if drawn is None else drawn[p:p + 1], return_dict=False,
-                                               num_inference_steps=n_k)
-                    latents[p:p + 1] = new.to(dt)
-            if callback_on_step_end is not None:
-                # the contract of the scalar path over all b videos in the caller's order; `t` is the 0-dim timestep while the active videos
-                # share it, otherwise [b] timesteps (a finished video keeps its last one)
-                t_cb = steps[0]["t"] if all(int(st["t"]) == int(steps[0]["t"]) for st in steps) else torch.stack([last_t[inverse[k]] for k in range(b)])
-                shown = latents[inverse]
-                avail = {"latents": shown, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
-                outs = callback_on_step_end(self, i, t_cb, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
-                new_lat = outs.get("latents", shown)
-                if new_lat is not shown:   # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
-                    latents.copy_(new_lat.to(dev, dt).reshape(shown.shape)[order])
-                new_text = outs.get("prompt_embeds", text)
-                if new_text is not text:
-                    text = new_text.to(dev, dt)
-                    if fused:  # the hoisted text projection of the active rows follows the new embeddings
-                        eng.set_conditioning(active_text(active), active_ref(active, False))
-                negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
+                    if is_dpm and gen_list:   # video p draws from its own generator, as often as its one-video call does at this step
+                        for p, st in enumerate(steps):
+                            for _ in range(st["draws"]):
+                                self._draw(noise[p:p + 1], gens[p])
+                    elif is_dpm:
+                        for _ in range(steps[0]["draws"]):
+                            self._draw(noise[:a], generator)
+                    eng.denoise_step(latents[:a], [float(st["t"]) for st in steps], [st["coef"] for st in steps],
+                                     x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph,
+                                     blend=None if mask is None else [blends[p][i] for p in range(a)])
+                else:
+                    x = torch.cat([latents[:a]] * 2)
+                    if seam_key is None or seam_key[0] != a or seam_key[1] is not text:
+                        seam_key, seam_text, seam_ref = (a, text), active_text(a), active_ref(a, True)
+                    noise_pred = tr(hidden_states=x, encoder_hidden_states=seam_text, ref_img_states=seam_ref,
+                                    timestep=torch.stack([st["t"] for st in steps]).repeat(2), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
+                                    return_dict=False, eval=True)[0].float()
+                    u, c = noise_pred.chunk(2)
+                    drawn = None
+                    if is_dpm and not gen_list:   # one stream: the noise of all videos in one draw, the last of this step's draws
+                        for _ in range(steps[0]["draws"]):
+                            drawn = randn_videos(latents[:a].shape, generator, dev, dt)
+                    for p, st in enumerate(steps):   # the one-video call's own sequence on video p
+                        n_k = plans[order[p]]["num_inference_steps"]
+                        np_p = u[p:p + 1] + st["guidance"] * (c[p:p + 1] - u[p:p + 1])
+                        if not is_dpm:
+                            new = sch.step(np_p, st["t"], latents[p:p + 1], return_dict=False, num_inference_steps=n_k)[0]
+                        else:
+                            new, old[p] = sch.step(np_p, old[p], st["t"], st["t_back"], latents[p:p + 1], generator=gens[p] if gen_list else None,
+                                                   variance_noise=None if drawn is None else drawn[p:p + 1], return_dict=False,
+                                                   num_inference_steps=n_k)
+                        new = new.to(dt)
+                        if mask is not None:
+                            ts_p = plans[order[p]]["timesteps"]
+                            new = self._blend_torch(sch, new, z0[p:p + 1], noise0[p:p + 1], keep[p:p + 1], ts_p[i + 1] if i + 1 < len(ts_p) else None)
+                        latents[p:p + 1] = new
+                if callback_on_step_end is not None:
+                    # the contract of the scalar path over all b videos in the caller's order; `t` is the 0-dim timestep while the active videos
+                    # share it, otherwise [b] timesteps (a finished video keeps its last one)
+                    t_cb = steps[0]["t"] if all(int(st["t"]) == int(steps[0]["t"]) for st in steps) else torch.stack([last_t[inverse[k]] for k in range(b)])
+                    shown = latents[inverse]
+                    avail = {"latents": shown, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
+                    outs = callback_on_step_end(self, i, t_cb, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
+                    new_lat = outs.get("latents", shown)
+                    if new_lat is not shown:   # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
+                        latents.copy_(new_lat.to(dev, dt).reshape(shown.shape)[order])
+                    new_text = outs.get("prompt_embeds", text)
+                    if new_text is not text:
+                        text = new_text.to(dev, dt)
+                        if fused:  # the hoisted text projection of the active rows follows the new embeddings
+                            eng.set_conditioning(active_text(active), active_ref(active, False))
+                    negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
+        finally:
+            if fused and mask is not None:
+                eng.clear_blend()
         sch.set_timesteps(plans[order[0]]["num_inference_steps"], device="cpu")   # the object is left on the longest video's count
-        return self._finish(latents[inverse].contiguous(), fused, output_type, return_dict)
+        return self._finish(latents[inverse].contiguous(), fused, output_type, return_dict, paste)
 
     @staticmethod
     def _draw(buf, generator):

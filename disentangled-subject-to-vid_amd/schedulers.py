@@ -86,6 +86,14 @@ class _SchedulerBase:
         a = torch.as_tensor(self.alphas_cumprod[int(timestep)], dtype=torch.float64).to(device).to(dtype)
         return float(a**0.5), float((1 - a) ** 0.5)
 
+    def blend_record(self, next_timestep, dtype, device="cpu"):
+        """the masked step's record (_lib.BlendC) of a video whose NEXT timestep is next_timestep: add_noise's scalars there; None: this is
+        the video's last step (the kept elements become the clean latents, the scalars are not read)"""
+        if next_timestep is None:
+            return _lib.BlendC(1.0, 0.0, 1, 0)
+        sa, sb = self.add_noise_scalars(int(next_timestep), dtype, device)
+        return _lib.BlendC(sa, sb, 0, 0)
+
     def add_noise(self, original_samples, noise, timesteps):
         """scheduler.add_noise (scheduling_ddim_cogvideox.py:405-431; scheduling_dpm_cogvideox.py:442) in the HIP kernel of s2v_add_noise:
         one timestep for the whole tensor, or b timesteps for [b, ...] samples, row k noised at timesteps[k] (one launch per row: this

@@ -35,6 +35,8 @@ _lib.register_sigs({
     "s2v_vae_decode": [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P],
     "s2v_vae_postprocess": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P],
     "s2v_vae_postprocess_u8": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P],
+    "s2v_vae_postprocess_masked": [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _I32, _P],
+    "s2v_vae_postprocess_u8_masked": [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _I32, _P],
     "s2v_vae_enc_create": [ctypes.POINTER(VaeConfigC), ctypes.POINTER(_P)],
     "s2v_vae_encode_shape": [_P, _I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
     "s2v_vae_encode": [_P, _P, _I32, _I32, _I32, _P, _P],
@@ -285,28 +287,60 @@ class HipAutoencoderKLCogVideoX:
             return (dec,)
         return SimpleNamespace(sample=dec)
 
-    def frames_uint8(self, video):
+    def _paste_args(self, what, video, keep, pixel_mask):
+        """the input video row [3,F,H,W] (its own dtype) and the binarised pixel mask [F,H,W] of a masked post-process of video [1,3,F,H,W]"""
+        if keep is None or pixel_mask is None:
+            raise ValueError(f"{what}: paste-back takes both `keep` (the input video) and `pixel_mask`")
+        _, C, F, H, W = video.shape
+        k = keep.to(video.device)
+        if k.dtype not in _lib.DTYPE_OF:
+            k = k.float()
+        m = pixel_mask.to(video.device)
+        if tuple(k.shape) != (1, C, F, H, W) or tuple(m.shape) != (1, F, H, W) or m.dtype != torch.uint8:
+            raise ValueError(f"{what}: `keep` must be {[1, C, F, H, W]} and `pixel_mask` uint8 {[1, F, H, W]} for a decoded video of "
+                             f"{list(video.shape)}, got {list(k.shape)} and {list(m.shape)} {m.dtype}")
+        return k[0].contiguous(), m[0].contiguous()
+
+    def frames_uint8(self, video, keep=None, pixel_mask=None):
         """decoded video [1,3,F,H,W] -> uint8 [F,H,W,3]: postprocess_video(..., "np")[0] followed by export_to_video's
-        `(frame * 255).astype(np.uint8)` (utils/export_utils.py:175), converted on the device"""
+        `(frame * 255).astype(np.uint8)` (utils/export_utils.py:175), converted on the device.
+        keep / pixel_mask (masked video-to-video's paste-back): the input video [1,3,F,H,W] and the binarised pixel mask uint8 [1,F,H,W]
+        (engine.mask_to_latent): the frames of `keep` where the mask is 0, for all three channels -- exactly its own frames_uint8"""
         if video.shape[0] != 1:
             raise NotImplementedError("one video per call")
         _, C, F, H, W = video.shape
         v = video[0].contiguous()
         o = torch.empty((F, H, W, C), dtype=torch.uint8, device=v.device)
+        if keep is not None or pixel_mask is not None:
+            k, m = self._paste_args("frames_uint8", video, keep, pixel_mask)
+            _lib.check(_lib.lib().s2v_vae_postprocess_u8_masked(_lib.ptr(v), _lib.ptr(k), _lib.DTYPE_OF[k.dtype], _lib.ptr(m), C, F, H, W,
+                                                                _lib.ptr(o), _lib.DTYPE_OF[v.dtype], _lib.stream_ptr()))
+            return o
         _lib.check(_lib.lib().s2v_vae_postprocess_u8(_lib.ptr(v), C, F, H, W, _lib.ptr(o), _lib.DTYPE_OF[v.dtype], _lib.stream_ptr()))
         return o
 
-    def postprocess_video(self, video, output_type="np"):
-        """VideoProcessor.postprocess_video: [B,3,F,H,W] -> np float32 [B,F,H,W,3] (or 'pt' [B,F,3,H,W])"""
+    def postprocess_video(self, video, output_type="np", keep=None, pixel_mask=None):
+        """VideoProcessor.postprocess_video: [B,3,F,H,W] -> np float32 [B,F,H,W,3] (or 'pt' [B,F,3,H,W]).
+        keep / pixel_mask (masked video-to-video's paste-back): the input videos [1 | B,3,F,H,W] and the binarised pixel masks uint8
+        [1 | B,F,H,W] (one row: shared by all B): where the mask is 0 the result is the post-processed input video, exactly"""
         if output_type not in ("np", "pt"):
             raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt']")
         B, C, F, H, W = video.shape
+        paste = keep is not None or pixel_mask is not None
+        if paste and (keep is None or pixel_mask is None or keep.shape[0] not in (1, B) or pixel_mask.shape[0] not in (1, B)):
+            raise ValueError("postprocess_video: paste-back takes `keep` and `pixel_mask` with one row, or one row per video")
         outs = []
         for b in range(B):
             v = video[b].contiguous()
             o = torch.empty((F, H, W, C), dtype=torch.float32, device=v.device)
-            _lib.check(_lib.lib().s2v_vae_postprocess(_lib.ptr(v), C, F, H, W, _lib.ptr(o), _lib.DTYPE_OF[v.dtype],
-                                                      _lib.stream_ptr()))
+            if paste:
+                kb, mb = min(b, keep.shape[0] - 1), min(b, pixel_mask.shape[0] - 1)
+                k, m = self._paste_args("postprocess_video", video[b:b + 1], keep[kb:kb + 1], pixel_mask[mb:mb + 1])
+                _lib.check(_lib.lib().s2v_vae_postprocess_masked(_lib.ptr(v), _lib.ptr(k), _lib.DTYPE_OF[k.dtype], _lib.ptr(m), C, F, H, W,
+                                                                 _lib.ptr(o), _lib.DTYPE_OF[v.dtype], _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().s2v_vae_postprocess(_lib.ptr(v), C, F, H, W, _lib.ptr(o), _lib.DTYPE_OF[v.dtype],
+                                                          _lib.stream_ptr()))
             outs.append(o)
         res = torch.stack(outs)
         if output_type == "np":

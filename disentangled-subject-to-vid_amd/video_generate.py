@@ -45,7 +45,7 @@ def prompt_embeddings(text_encoder, input_ids, dtype=None):
 
 def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_ids, height=480, width=720, num_frames=49,
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
-              video_uint8=None, strength=0.8, **pipe_kwargs):
+              video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
     `output_type` selects ("latent" / "pt").  A batch of prompt ids [P, T] (with num_videos_per_prompt through **pipe_kwargs: up to four
     videos per call) shares the one reference image and returns one video per row, [b, F, H, W, 3].
@@ -68,13 +68,27 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
 
     Per video: guidance_scale, num_inference_steps and strength may each be a list with one entry per video (prompt-major), and video_uint8
     [b, F, H, W, 3] gives every video its own input video ([F, H, W, 3]: one shared by all); S2VPipeline.__call__ runs every video on the plan
-    of its one-video call."""
+    of its one-video call.
+
+    Masked video-to-video: mask_uint8 [F, H, W] (one mask shared by all videos) or [b, F, H, W] over the input video's frames and pixels,
+    >= 128 repaints, below keeps the input video (S2VPipeline.__call__'s `mask`); paste_back returns the input video's own pixels outside
+    the mask."""
     if video_uint8 is not None:
         vs = np.asarray(video_uint8).shape[-4:]
         if np.asarray(video_uint8).ndim not in (4, 5) or vs[3] != 3:
             raise ValueError("video_uint8 must be [F, H, W, 3] or [b, F, H, W, 3]")
         if (vs[1], vs[2]) != (height, width):
             raise ValueError(f"video is {vs[1]}x{vs[2]} but the requested size is {height}x{width}: resize it first (preprocess_video)")
+    if mask_uint8 is not None:
+        m = np.asarray(mask_uint8)
+        if m.dtype != np.uint8 or m.ndim not in (3, 4):
+            raise ValueError("mask_uint8 must be uint8 [F, H, W] or [b, F, H, W] (>= 128 repaints)")
+        if video_uint8 is None:
+            raise ValueError("mask_uint8 applies only together with video_uint8")
+        if tuple(m.shape[-3:]) != tuple(vs[:3]):
+            raise ValueError(f"mask_uint8 is {m.shape[-3:]} (frames, height, width) but the video is {tuple(vs[:3])}")
+        mask = torch.from_numpy(np.ascontiguousarray(m >= 128).view(np.uint8))
+        pipe_kwargs = dict(pipe_kwargs, mask=mask[None] if mask.ndim == 3 else mask, paste_back=paste_back)
     dev = pipe.transformer.device
     generator = None
     if seed is not None:

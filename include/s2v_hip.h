@@ -283,6 +283,44 @@ S2V_API int s2v_denoise_step(s2v_ctx* ctx, void* latents, float timestep, const 
  * them; the CFG-parallel and Ulysses entry points stay single-scalar. */
 S2V_API int s2v_denoise_step_videos(s2v_ctx* ctx, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist,
                             const void* noise, int32_t use_graph, s2v_stream stream);
+/* ---- masked video-to-video: repaint inside a mask, keep the rest (pipeline_stable_diffusion_inpaint.py:1271-1285, the 4-channel branch) ------
+ * After every scheduler step the latents OUTSIDE the mask are overwritten with the input video's latents noised to the video's next timestep
+ * -- with the noise that started the loop -- and after its last step with the clean input latents.  The mask is exactly 0 or 1, so the
+ * reference's (1 - m) * proper + m * latents is a select on the step's result as it is stored today (rounded to the model dtype T):
+ *   m = 1:             the step's result
+ *   m = 0, not last:   rnd_T(rnd_T(sqrt_alpha * z0) + rnd_T(sqrt_one_minus_alpha * noise0))      (s2v_add_noise's arithmetic, no fma)
+ *   m = 0, last:       z0, bit for bit (a flag, not the coefficients (1, 0), which would turn -0 into +0)
+ * x0_hist keeps the unblended x0: the scheduler's state is left alone, as in the reference. */
+typedef struct s2v_blend {
+    float sqrt_alpha, sqrt_one_minus_alpha;   /* of the video's NEXT timestep, taken in T by the host as for s2v_add_noise */
+    int32_t last;                             /* != 0: this is the video's last step */
+    int32_t pad;
+} s2v_blend;
+#define S2V_MASK_DTYPE_U8 3   /* s2v_mask_to_latent: a uint8 mask, non-zero = repaint (beside S2V_DTYPE_*: binarised at 0.5) */
+/* The pixel mask of one video [F,H,W] (F = 4k + 1; H, W multiples of 8; mask_dtype S2V_DTYPE_* -- value < 0.5 -> 0, >= 0.5 -> 1 as
+ * image_processor.py:535-536 binarises -- or S2V_MASK_DTYPE_U8) -> latent_mask uint8 [(F-1)/4+1, H/8, W/8], one plane for all latent channels:
+ * a cell is 1 (repaint) if ANY pixel it covers is 1 -- its 8 x 8 block of pixel frame 0 for latent frame 0, of pixel frames 4j-3 .. 4j for latent
+ * frame j >= 1, the causal grouping of the VAE encode.  (Beyond the reference, whose prepare_mask_latents :747-760 takes the nearest pixel and
+ * has no time axis: a latent any of whose pixels the caller asked to change is never kept.)  pixel_mask, when not NULL, receives the
+ * binarised pixel mask uint8 [F,H,W] (what the masked post-processes take).  One launch. */
+S2V_API int s2v_mask_to_latent(const void* mask, int32_t mask_dtype, int32_t F, int32_t H, int32_t W, uint8_t* latent_mask, uint8_t* pixel_mask,
+                               s2v_stream stream);
+/* The blend operands of the call on the context: z0 (the clean input latents, scaled) and noise0 (the noise that started the loop), both
+ * [b,F,C,H,W] in the model dtype, and latent_mask uint8 [b,F,H,W], for the b = B/2 videos of the geometry.  The pointers are HELD, nothing is
+ * copied: they must stay valid until they are replaced or cleared (all NULL, b = 0).  Setting or clearing drops a captured step (the operands
+ * are part of its key).  s2v_denoise_step / s2v_denoise_step_videos never read them. */
+S2V_API int s2v_set_blend(s2v_ctx* ctx, const void* z0, const void* noise0, const uint8_t* latent_mask, int32_t b);
+/* s2v_denoise_step_videos with the blend in the step's last kernel: `blends` is a HOST array of b records, video k blended with blends[k]
+ * (its own next timestep and last-step flag, so a video on its last step may sit beside videos that go on).  The records go up beside the
+ * coefficient sets, so one captured graph serves every step of a masked call.  Refused: a geometry with B = 1 (one sample of a CFG-parallel
+ * pair: the split entries have no masked form), a shard context, operands not set for b = B/2. */
+S2V_API int s2v_denoise_step_masked(s2v_ctx* ctx, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
+                            float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream);
+/* s2v_sched_step followed by the blend, for ONE video whose latent is [F,C,H,W]: latents_out in `dtype` (flags bit2 is refused: the blend runs
+ * on the rounded result), z0 / noise0 [F,C,H,W] in `dtype`, latent_mask uint8 [F,H,W]; ctx may be NULL. */
+S2V_API int s2v_sched_step_masked(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
+                          const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0, const void* noise0,
+                          const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype, s2v_stream stream);
 /* pointer to the [B,F,C,H,W] model output of the last s2v_denoise_step (context-owned, model dtype) */
 S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 
@@ -452,6 +490,13 @@ S2V_API int s2v_vae_postprocess(const void* video, int32_t C, int32_t F, int32_t
  * src/video_generate.py:65-66): video [C,F,H,W] -> uint8 [F,H,W,C], what the mp4 writer consumes (4x less D2H traffic) */
 S2V_API int s2v_vae_postprocess_u8(const void* video, int32_t C, int32_t F, int32_t H, int32_t W, uint8_t* out, int32_t dtype,
                            s2v_stream stream);
+/* Paste-back of masked video-to-video: s2v_vae_postprocess / s2v_vae_postprocess_u8 as a select per frame and pixel, for all C channels: of
+ * `video` (the decoded video, `dtype`) where pixel_mask uint8 [F,H,W] (0 / 1: s2v_mask_to_latent's pixel_mask) is 1, of `keep` (the input video
+ * [C,F,H,W], its own keep_dtype) where it is 0.  A kept pixel is exactly what the unmasked entry makes of the input video. */
+S2V_API int s2v_vae_postprocess_masked(const void* video, const void* keep, int32_t keep_dtype, const uint8_t* pixel_mask, int32_t C, int32_t F,
+                               int32_t H, int32_t W, float* out, int32_t dtype, s2v_stream stream);
+S2V_API int s2v_vae_postprocess_u8_masked(const void* video, const void* keep, int32_t keep_dtype, const uint8_t* pixel_mask, int32_t C, int32_t F,
+                                  int32_t H, int32_t W, uint8_t* out, int32_t dtype, s2v_stream stream);
 
 /* ---- reference-image encode (the step in front of the denoise loop) ------------------------------------------
  * Replaces pipe.vae.encode(ref_image).latent_dist.sample() of src/video_generate.py:35-37
