@@ -95,6 +95,10 @@ _SIGS = {
     "s2v_op_linear_lora": [_P, _P, _P, _P, _P, _I32, _F, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P],
     "s2v_op_ff_fp8": [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P],
     "s2v_op_mod_gemv": [_P, _P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P],
+    "s2v_op_ln_modulate": [_P, _I32, _P, _I32, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P],
+    "s2v_op_tail_norm": [_P, _I32, _P, _I32, _P, _P, _P, _P, _F, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "s2v_op_qk_norm_rope": [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _I32, _P],
+    "s2v_op_v_transpose": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P],
     "s2v_op_attention": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
     "s2v_attn_slow_stats": [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _I32],
     "s2v_set_attn_p_format": [_P, _I32],

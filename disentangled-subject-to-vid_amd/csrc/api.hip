@@ -2436,6 +2436,72 @@ extern "C" int s2v_op_mod_gemv(const void* emb, const void* W, const void* bias,
     return launch_mod_gemv(emb, B, temb_dim, W, bias, rows, out, dtype, (hipStream_t)stream, impl == 1);
 }
 
+// The HBM-bound row kernels as operators (tests/test_gpu_norm_exact.py): each entry validates, fills the launcher's args struct and calls the
+// launcher a context calls.  A row pitch or a parameter stride must keep every row 16-byte aligned: a multiple of `per16` elements.
+static bool op_dtype_ok(int32_t dtype) { return dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_F16; }
+static int per16(int32_t dtype) { return dtype == S2V_DTYPE_F32 ? 4 : 8; }
+extern "C" int s2v_op_ln_modulate(const void* x, int32_t ldx, void* y, int32_t ldy, const void* w, const void* b, float eps, const void* shift_vid,
+                                  const void* scale_vid, const void* shift_txt, const void* scale_txt, const void* shift_ref, const void* scale_ref,
+                                  int32_t mod_stride, int32_t B, int32_t Ntok, int32_t text_len, int32_t ref_len, int32_t D, void* q8, float* q8_scale,
+                                  int32_t q8_keep_y, int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(op_dtype_ok(dtype), "s2v_op_ln_modulate: dtype must be f32, bf16 or f16");
+    S2V_REQUIRE(x && w && b && shift_vid && scale_vid && shift_txt && scale_txt, "s2v_op_ln_modulate: null argument");
+    S2V_REQUIRE((shift_ref == nullptr) == (scale_ref == nullptr), "s2v_op_ln_modulate: the reference set is a shift AND a scale, or neither");
+    S2V_REQUIRE(q8 == nullptr || (dtype == S2V_DTYPE_BF16 && q8_scale != nullptr), "s2v_op_ln_modulate: the fp8 output needs bf16 rows and a scale vector");
+    S2V_REQUIRE(y != nullptr || (q8 != nullptr && !q8_keep_y), "s2v_op_ln_modulate: y may be null only where the fp8 form does not keep the rows");
+    S2V_REQUIRE(B > 0 && Ntok > 0 && (int64_t)B * Ntok <= INT32_MAX && text_len >= 0 && ref_len >= 0 && text_len + (int64_t)ref_len <= Ntok,
+                "s2v_op_ln_modulate: B, Ntok > 0 and text_len + ref_len <= Ntok");
+    const int v = per16(dtype);
+    S2V_REQUIRE(D > 0 && D <= 4096 && D % 8 == 0, "s2v_op_ln_modulate: D must be <= 4096 and a multiple of 8");
+    S2V_REQUIRE(ldx >= D && ldy >= D && mod_stride >= D && ldx % v == 0 && ldy % v == 0 && mod_stride % v == 0,
+                "s2v_op_ln_modulate: ldx, ldy and mod_stride must cover D and keep rows 16-byte aligned");
+    LnModArgs n{};
+    n.x = x; n.ldx = ldx; n.y = y; n.ldy = ldy; n.w = w; n.b = b; n.eps = eps;
+    n.shift_vid = shift_vid; n.scale_vid = scale_vid; n.shift_txt = shift_txt; n.scale_txt = scale_txt; n.mod_stride = mod_stride;
+    n.B = B; n.Ntok = Ntok; n.text_len = text_len; n.D = D;
+    n.shift_ref = shift_ref; n.scale_ref = scale_ref; n.ref_len = ref_len;
+    n.q8 = q8; n.q8_scale = q8_scale; n.q8_keep_y = q8 != nullptr && q8_keep_y ? 1 : 0;
+    return launch_ln_modulate(n, dtype, (hipStream_t)stream);
+}
+extern "C" int s2v_op_tail_norm(const void* x, int32_t ldx, void* y, int32_t ldy, const void* w1, const void* b1, const void* w2, const void* b2,
+                                float eps, const void* shift, const void* scale, int32_t mod_stride, int32_t B, int32_t Ntok, int32_t row0, int32_t V,
+                                int32_t D, int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(op_dtype_ok(dtype), "s2v_op_tail_norm: dtype must be f32, bf16 or f16");
+    S2V_REQUIRE(x && y && w1 && b1 && w2 && b2 && shift && scale, "s2v_op_tail_norm: null argument");
+    S2V_REQUIRE(B > 0 && Ntok > 0 && (int64_t)B * Ntok <= INT32_MAX && row0 >= 0 && V > 0 && row0 + (int64_t)V <= Ntok,
+                "s2v_op_tail_norm: B, Ntok, V > 0 and rows [row0, row0 + V) inside a sample");
+    const int v = per16(dtype);
+    S2V_REQUIRE(D > 0 && D <= 4096 && D % 8 == 0, "s2v_op_tail_norm: D must be <= 4096 and a multiple of 8");
+    S2V_REQUIRE(ldx >= D && ldy >= D && mod_stride >= D && ldx % v == 0 && ldy % v == 0 && mod_stride % v == 0,
+                "s2v_op_tail_norm: ldx, ldy and mod_stride must cover D and keep rows 16-byte aligned");
+    TailNormArgs t{};
+    t.x = x; t.ldx = ldx; t.y = y; t.ldy = ldy; t.w1 = w1; t.b1 = b1; t.w2 = w2; t.b2 = b2; t.eps = eps;
+    t.shift = shift; t.scale = scale; t.mod_stride = mod_stride; t.B = B; t.Ntok = Ntok; t.row0 = row0; t.V = V; t.D = D;
+    return launch_tail_norm(t, dtype, (hipStream_t)stream);
+}
+extern "C" int s2v_op_qk_norm_rope(void* qkv, int32_t ld_qkv, int32_t B, int32_t H, int32_t Ntok, int32_t text_len, const void* nq_w, const void* nq_b,
+                                   const void* nk_w, const void* nk_b, float eps, const float* cos_tab, const float* sin_tab, int32_t dtype,
+                                   s2v_stream stream) {
+    S2V_REQUIRE(op_dtype_ok(dtype), "s2v_op_qk_norm_rope: dtype must be f32, bf16 or f16");
+    S2V_REQUIRE(qkv && nq_w && nq_b && nk_w && nk_b, "s2v_op_qk_norm_rope: null argument");
+    S2V_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr), "s2v_op_qk_norm_rope: the rotary tables are a cosine AND a sine table, or neither");
+    S2V_REQUIRE(B > 0 && H > 0 && H <= 4096 && Ntok > 0 && (int64_t)B * Ntok <= INT32_MAX && text_len >= 0 && text_len <= Ntok,
+                "s2v_op_qk_norm_rope: B, H, Ntok > 0 and text_len <= Ntok");
+    S2V_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % per16(dtype) == 0, "s2v_op_qk_norm_rope: ld_qkv must cover 3 * H * 64 and keep rows 16-byte aligned");
+    QkNormRopeArgs q{};
+    q.qkv = qkv; q.ld_qkv = ld_qkv; q.B = B; q.H = H; q.Ntok = Ntok; q.text_len = text_len;
+    q.nq_w = nq_w; q.nq_b = nq_b; q.nk_w = nk_w; q.nk_b = nk_b; q.eps = eps; q.cos = cos_tab; q.sin = sin_tab;
+    return launch_qk_norm_rope(q, dtype, (hipStream_t)stream);  // q.vt stays null: no V^T
+}
+extern "C" int s2v_op_v_transpose(const void* qkv, int32_t ld_qkv, int32_t B, int32_t H, int32_t Ntok, void* vt, int32_t ntok_pad, uint32_t* vt_amax,
+                                  s2v_stream stream) {
+    S2V_REQUIRE(qkv && vt, "s2v_op_v_transpose: null argument");
+    S2V_REQUIRE(B > 0 && B <= 65535 && H > 0 && H <= 65535 && Ntok > 0, "s2v_op_v_transpose: B, H (<= 65535 each) and Ntok must be positive");
+    S2V_REQUIRE(ld_qkv >= 3 * H * 64 && ld_qkv % 8 == 0, "s2v_op_v_transpose: ld_qkv must cover 3 * H * 64 and be a multiple of 8");
+    S2V_REQUIRE(ntok_pad % 64 == 0 && ntok_pad >= Ntok, "s2v_op_v_transpose: ntok_pad must be a multiple of 64 covering Ntok");
+    return launch_v_transpose(qkv, ld_qkv, B, H, Ntok, vt, ntok_pad, (hipStream_t)stream, vt_amax);
+}
+
 // attention with QK^T on the scaled fp8 MFMA as weight_format 2 runs it: q (times scale * log2 e) and k of the bf16 qkv rows become MX e4m3
 // images in `scratch` (also returned to the caller for inspection: layout in kernels.h AttnArgs::q8 ... k8s, offsets below), V^T and P.V stay bf16.
 static int op_attention_fp8qk(const void* qkv, void* vt_scratch, void* scratch, int64_t scratch_bytes, void* out, int32_t B, int32_t H,

@@ -201,8 +201,8 @@ template <typename T> static int ln_rounds(int D) {
         if (r >= need) return r;
     return -1;
 }
-#define S2V_LN_DISPATCH(T, D, ...)                                                   \
-    switch (ln_rounds<T>(D)) {                                                        \
+#define S2V_LN_DISPATCH_NR(T, nr, ...)                                                \
+    switch (nr) {                                                                     \
         case 1: { constexpr int NR = 1; __VA_ARGS__; } break;                                \
         case 2: { constexpr int NR = 2; __VA_ARGS__; } break;                                \
         case 3: { constexpr int NR = 3; __VA_ARGS__; } break;                                \
@@ -213,6 +213,7 @@ template <typename T> static int ln_rounds(int D) {
         case 16: if constexpr (sizeof(T) == 4) { constexpr int NR = 16; __VA_ARGS__; } break; \
         default: return s2v_fail(__FILE__, __LINE__, "layer norm: row too long", -1); \
     }
+#define S2V_LN_DISPATCH(T, D, ...) S2V_LN_DISPATCH_NR(T, ln_rounds<T>(D), __VA_ARGS__)
 
 // CogVideoXLayerNormZero.forward (normalization.py:467-484): LN(x)*(1+scale)+shift, three token ranges
 template <typename T, int NR>
@@ -309,30 +310,49 @@ __global__ __launch_bounds__(256) void ln_modulate_lds_k(const LnModArgs a) {
         row_modulate_store<T, NR>(v, a.D, lane, psh, psc, (T*)a.y + (size_t)row * a.ldy);
     }
 }
+// many rows (at least four workgroups of sixteen rows per CU): parameters staged in LDS per workgroup (bf16 only)
+LnPlan ln_modulate_plan(int rows, int D, int dtype, int lds_rows) {
+    LnPlan p;
+    p.kernel = dtype == S2V_BF16 && lds_rows > 0 && rows >= lds_rows ? LN_KERNEL_LDS : LN_KERNEL_REG;
+    p.nr = dtype == S2V_BF16 ? ln_rounds<bf16_t>(D) : dtype == S2V_F16 ? ln_rounds<f16_t>(D) : ln_rounds<float>(D);
+    if (dtype != S2V_F32 && p.nr > 8) p.nr = -1;  // 12 and 16 rounds are instantiated for fp32 only
+    return p;
+}
+static int ln_lds_rows() {
+#ifdef S2V_DIAG
+    if (const char* e = getenv("S2V_LN_LDS_ROWS")) return atoi(e);  // tools/ln_lds_probe.py (diagnostics library): 0 = never
+#endif
+    return LN_LDS_ROWS;
+}
+#ifdef S2V_DIAG
+// ln_modulate_plan without a device: out = {kernel (LN_KERNEL_*), NR}; lds_rows < 0: the launcher's own threshold (S2V_LN_LDS_ROWS included)
+extern "C" __attribute__((visibility("default"))) int s2v_diag_ln_plan(int32_t rows, int32_t D, int32_t dtype, int32_t lds_rows, int32_t* out) {
+    S2V_REQUIRE(out && rows > 0 && D > 0 && (dtype == S2V_F32 || dtype == S2V_BF16 || dtype == S2V_F16), "s2v_diag_ln_plan: bad argument");
+    const LnPlan p = ln_modulate_plan(rows, D, dtype, lds_rows < 0 ? ln_lds_rows() : lds_rows);
+    out[0] = p.kernel; out[1] = p.nr;
+    return 0;
+}
+#endif
 int launch_ln_modulate(const LnModArgs& a, int dtype, hipStream_t st) {
     S2V_REQUIRE(a.D <= 4096 && a.D % 8 == 0, "ln_modulate: D must be <= 4096 and a multiple of 8");
     S2V_REQUIRE(a.q8 == nullptr || (dtype == S2V_BF16 && a.q8_scale != nullptr), "ln_modulate: the fp8 output needs bf16 rows and a scale vector");
     const int rows = a.B * a.Ntok;
     dim3 grid((rows + 3) / 4);
-    // many rows (at least four workgroups of sixteen rows per CU): parameters staged in LDS per workgroup
-    int lds_rows = 16384;
-#ifdef S2V_DIAG
-    if (const char* e = getenv("S2V_LN_LDS_ROWS")) lds_rows = atoi(e);  // tools/ln_lds_probe.py (diagnostics library): 0 = never
-#endif
-    if (dtype == S2V_BF16 && lds_rows > 0 && rows >= lds_rows) {
+    const LnPlan pl = ln_modulate_plan(rows, a.D, dtype, ln_lds_rows());
+    if (pl.kernel == LN_KERNEL_LDS) {
         constexpr int RPW = 4;
         dim3 g16((rows + 4 * RPW - 1) / (4 * RPW));
         const size_t lds = (size_t)4 * a.D * 2;
-        S2V_LN_DISPATCH(bf16_t, a.D, hipLaunchKernelGGL((ln_modulate_lds_k<bf16_t, NR, RPW>), g16, dim3(256), lds, st, a))
+        S2V_LN_DISPATCH_NR(bf16_t, pl.nr, hipLaunchKernelGGL((ln_modulate_lds_k<bf16_t, NR, RPW>), g16, dim3(256), lds, st, a))
         S2V_CHECK_HIP(hipGetLastError());
         return 0;
     }
     if (dtype == S2V_BF16) {
-        S2V_LN_DISPATCH(bf16_t, a.D, hipLaunchKernelGGL((ln_modulate_k<bf16_t, NR>), grid, dim3(256), 0, st, a))
+        S2V_LN_DISPATCH_NR(bf16_t, pl.nr, hipLaunchKernelGGL((ln_modulate_k<bf16_t, NR>), grid, dim3(256), 0, st, a))
     } else if (dtype == S2V_F16) {
-        S2V_LN_DISPATCH(f16_t, a.D, hipLaunchKernelGGL((ln_modulate_k<f16_t, NR>), grid, dim3(256), 0, st, a))
+        S2V_LN_DISPATCH_NR(f16_t, pl.nr, hipLaunchKernelGGL((ln_modulate_k<f16_t, NR>), grid, dim3(256), 0, st, a))
     } else {
-        S2V_LN_DISPATCH(float, a.D, hipLaunchKernelGGL((ln_modulate_k<float, NR>), grid, dim3(256), 0, st, a))
+        S2V_LN_DISPATCH_NR(float, pl.nr, hipLaunchKernelGGL((ln_modulate_k<float, NR>), grid, dim3(256), 0, st, a))
     }
     S2V_CHECK_HIP(hipGetLastError());
     return 0;

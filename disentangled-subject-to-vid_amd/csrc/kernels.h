@@ -259,6 +259,13 @@ struct LnModArgs {
     int q8_keep_y;  // with q8: the bf16 rows are stored to y as well (the fp8 engine's runtime LoRA reads them for its down-projection)
 };
 int launch_ln_modulate(const LnModArgs& a, int dtype, hipStream_t st);
+// which kernel launch_ln_modulate runs for rows x D of `dtype`, and with how many rounds of 64 lanes x 16 bytes (NR; -1: row too long): pure host
+// arithmetic, the launcher's own choice (the diagnostics build exports it as s2v_diag_ln_plan).  lds_rows: from this many rows on bf16 rows take
+// ln_modulate_lds_k (0 = never); the product's value is LN_LDS_ROWS
+enum { LN_KERNEL_REG = 0, LN_KERNEL_LDS = 1 };
+#define LN_LDS_ROWS 16384  // at least four workgroups of sixteen rows per CU
+struct LnPlan { int kernel, nr; };
+LnPlan ln_modulate_plan(int rows, int D, int dtype, int lds_rows);
 
 // per-head LayerNorm(64, eps 1e-6, affine) on q,k (in place in qkv) + interleaved-pair RoPE on rows >= text_len,
 // optional V^T production (bf16 path).  cos/sin: [Ntok - text_len, 64] fp32 (ref rows then video rows), null => no RoPE.

@@ -629,6 +629,33 @@ S2V_API int s2v_op_ff_fp8_lora(const void* x, const void* w1, const void* b1, co
  * emb [B, temb_dim], W [rows, temb_dim], out [B, rows], B <= 4; impl 0 = the product dispatch, 1 = one wave per row */
 S2V_API int s2v_op_mod_gemv(const void* emb, const void* W, const void* bias, void* out, int32_t B, int32_t temb_dim,
                             int64_t rows, int32_t dtype, int32_t impl, s2v_stream stream);
+/* The HBM-bound row kernels between the GEMMs and the attention, one launch each as a context issues it (tests/test_gpu_norm_exact.py holds
+ * them to expected bits).  Row pitches and mod_stride are in elements, cover D and keep every row 16-byte aligned; asynchronous.
+ * s2v_op_ln_modulate (CogVideoXLayerNormZero): y[r] = rnd(rnd(LN(x[r]; w, b, eps) * rnd(1 + scale)) + shift) on rows [B * Ntok][D], D <= 4096 and
+ * a multiple of 8; row r of sample b takes (shift, scale)_txt[b] for r < text_len, _ref[b] for the next ref_len rows when that set is given
+ * (null: they are video rows), _vid[b] otherwise; the sets are [B][mod_stride].  q8 (bf16 only): the row leaves as e4m3 bytes [row][D] with
+ * q8_scale[row] = amax / 448 (1 for a zero row) instead of y; q8_keep_y: y is written as well. */
+S2V_API int s2v_op_ln_modulate(const void* x, int32_t ldx, void* y, int32_t ldy, const void* w, const void* b, float eps, const void* shift_vid,
+                               const void* scale_vid, const void* shift_txt, const void* scale_txt, const void* shift_ref, const void* scale_ref,
+                               int32_t mod_stride, int32_t B, int32_t Ntok, int32_t text_len, int32_t ref_len, int32_t D, void* q8, float* q8_scale,
+                               int32_t q8_keep_y, int32_t dtype, s2v_stream stream);
+/* norm_final then norm_out on the video rows: y[b * V + i] = rnd(rnd(LN(LN(x[b * Ntok + row0 + i]; w1, b1); w2, b2) * rnd(1 + scale[b])) + shift[b]),
+ * i < V, row0 + V <= Ntok; shift / scale [B][mod_stride] */
+S2V_API int s2v_op_tail_norm(const void* x, int32_t ldx, void* y, int32_t ldy, const void* w1, const void* b1, const void* w2, const void* b2,
+                             float eps, const void* shift, const void* scale, int32_t mod_stride, int32_t B, int32_t Ntok, int32_t row0, int32_t V,
+                             int32_t D, int32_t dtype, s2v_stream stream);
+/* Per-head LayerNorm(64) of the q and k thirds of qkv [B * Ntok][ld_qkv] in place (columns < 2 * H * 64; weights and biases [64]), then on rows
+ * r >= text_len of a sample the rotation of the pairs (2 i, 2 i + 1): (x0 cos[2i] - x1 sin[2i], x1 cos[2i+1] + x0 sin[2i+1]) with the fp32 tables
+ * cos / sin [Ntok - text_len][64] (both null: no rotation).  The v third is not touched and no V^T is produced. */
+S2V_API int s2v_op_qk_norm_rope(void* qkv, int32_t ld_qkv, int32_t B, int32_t H, int32_t Ntok, int32_t text_len, const void* nq_w, const void* nq_b,
+                                const void* nk_w, const void* nk_b, float eps, const float* cos_tab, const float* sin_tab, int32_t dtype,
+                                s2v_stream stream);
+/* The v third of bf16 qkv [B * Ntok][ld_qkv] (columns 2 * H * 64 + h * 64 + d) -> vt [B][H][64][ntok_pad], token order [0-3, 8-11, 4-7, 12-15] inside
+ * every 16 tokens, zeros from Ntok up to the next multiple of 64 -- positions beyond that multiple are NOT written (ntok_pad is that multiple in
+ * every launch of a context).  vt_amax ([B * H] words): V^T as fp16, each (batch, head) times the power of two that puts its largest magnitude
+ * into [2^14, 2^15); the word receives the bf16 bits of that magnitude; a head holding Inf / NaN is not scaled and Inf saturates to 65504. */
+S2V_API int s2v_op_v_transpose(const void* qkv, int32_t ld_qkv, int32_t B, int32_t H, int32_t Ntok, void* vt, int32_t ntok_pad, uint32_t* vt_amax,
+                               s2v_stream stream);
 /* Census of the deferred-maximum slow path of the four-wave attention kernels since the last reset (device counters; the call synchronises):
  * slow = slow paths taken, total = (wave, KV tile) pairs run.  attn_p_format 1 lowers the threshold from 2^64 to 2^14; a caller whose data
  * take the slow path in more than a fraction of a percent of the pairs switches back with s2v_set_attn_p_format (the engine's "auto"

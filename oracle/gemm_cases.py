@@ -389,8 +389,10 @@ def ulp16(v16):
     return (mag + 1).view(v16.dtype).double() - mag.view(v16.dtype).double()
 
 
-def qknorm_reference(y16, D, ln, cs, tok, text_len, eps, dt):
-    """(expected [M][3 D] in dt, bar [M][2 D] fp64).  fp64 with the kernel's two rounding points: per 64-column head of the q and k ranges
+def qknorm_reference(y16, D, ln, cs, tok, text_len, eps, dt, tabs=None):
+    """(expected [M][3 D] in dt, bar [M][2 D] fp64).  tabs = (cos, sin), each [positions][64] fp32, instead of cs: the tables as the stand-alone
+    pass qk_norm_rope_k reads them, an entry per (position, dim) -- (x0 cos[2k] - x1 sin[2k], x1 cos[2k+1] + x0 sin[2k+1]), no pair structure
+    assumed; the bar is the same form with each element's own |cos| + |sin|.  fp64 with the kernel's two rounding points: per 64-column head of the q and k ranges
     LayerNorm + affine on the rounded projection, rounded; then, on rows with m % tok >= text_len and with a table, the rotation of the pairs
     (2 k, 2 k + 1) by cs[m % tok - text_len] = [32 cos | 32 sin], rounded.  The v range is the projection itself.
     bar: one ulp of the output value plus (|cos| + |sin|) times one ulp of the larger normalised value of the pair, for every element -- a row
@@ -422,6 +424,14 @@ def qknorm_reference(y16, D, ln, cs, tok, text_len, eps, dt):
         o16 = torch.stack([x0 * c - x1 * s, x1 * c + x0 * s], dim=-1).view(M, H2, 64).to(dt)
         out = torch.where(rot, o16, n16)
         extra = torch.where(rot, ((c.abs() + s.abs()) * ulp16(big)).repeat_interleave(2, dim=-1), extra)
+    elif tabs is not None:
+        r = torch.arange(M, device=y16.device) % tok
+        rot = (r >= text_len)[:, None, None]
+        pos = (r - text_len).clamp_min(0)
+        c, s = tabs[0][pos].double()[:, None, :], tabs[1][pos].double()[:, None, :]
+        o16 = torch.stack([x0 * c[..., 0::2] - x1 * s[..., 0::2], x1 * c[..., 1::2] + x0 * s[..., 1::2]], dim=-1).view(M, H2, 64).to(dt)
+        out = torch.where(rot, o16, n16)
+        extra = torch.where(rot, (c.abs() + s.abs()) * ulp16(big).repeat_interleave(2, dim=-1), extra)
     bar = ulp16(out) + extra
     # a row that is not rotated has ONE stage: one ulp, wherever the premise of the derivation holds (no cancellation beyond 2^-10 in w n + b)
     premise = n16.double().abs() >= 2.0 ** -10 * torch.maximum(wn.abs(), b.abs().expand_as(wn))
