@@ -6,7 +6,7 @@ from .config import TransformerConfig, VAEConfig, cogvideox_2b, cogvideox_5b, ti
 from .engine import S2VEngine, mask_to_latent  # noqa: F401
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler  # noqa: F401
 from .transformer import HipCogVideoXAttnProcessor2_0, HipCogVideoXBlock, HipCogVideoXTransformer3DModel  # noqa: F401
-from .pipeline import S2VPipeline  # noqa: F401
+from .pipeline import S2VPipeline, StepCache, step_cache_plan  # noqa: F401
 from .vae import HipAutoencoderKLCogVideoX  # noqa: F401
 from . import dist  # noqa: F401
 from . import checkpoint  # noqa: F401

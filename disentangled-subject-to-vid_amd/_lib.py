@@ -108,6 +108,16 @@ _SIGS = {
     "s2v_op_linear_fp8_lora": [_P, _P, _P, _P, _P, _I32, _F, _P, _I32, _I32, _I32, _I32, _P, _I64, _P],
     "s2v_op_ff_fp8_lora": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _F, _P, _I32, _I32, _I32, _I32, _P, _I64, _P],
 }
+# step cache (include/s2v_hip.h: s2v_step_cache_*, s2v_time_embedding)
+STEP_FULL, STEP_CAPTURE, STEP_REUSE = 0, 1, 2
+_SIGS.update({
+    "s2v_step_cache_enable": [_P, _I32],
+    "s2v_step_cache_arm": [_P, _I32],
+    "s2v_step_cache_state": [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64)],
+    "s2v_step_cache_read": [_P, _I32, _P, _P],
+    "s2v_time_embedding": [_P, ctypes.POINTER(_F), _I32, _P, _P],
+    "s2v_op_step_cache": [_I32, _P, _I64, _P, _I32, _I64, _I32, _P],
+})
 # replicas over RCCL behind the C ABI (csrc/rccl.hip); RCCL itself is bound at first use
 _SIGS.update({
     "s2v_rccl_available": [],

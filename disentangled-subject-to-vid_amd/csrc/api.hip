@@ -74,9 +74,11 @@ struct GraphKey {
     void* latents; float* x0; const void* noise;
     int slot;   // -1: the whole step (s2v_denoise_step); 0 / 1: the forward-only graph of s2v_denoise_split_begin writing that half of the CFG pair
     const void *z0 = nullptr, *noise0 = nullptr, *mask = nullptr;   // the blend operands of the masked step (s2v_denoise_step_masked); null: unmasked
-    bool operator==(const GraphKey& o) const {
+    int mode = 0;   // S2V_STEP_*: the step-cache mode the forward was captured in; every mode has an executable of its own (launch_captured)
+    bool same_but_mode(const GraphKey& o) const {
         return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask;
     }
+    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode; }
 };
 
 // kernel classes of the per-class timing (ProfScope, s2v_profile_*): 8 = the Ulysses packs / unpacks, 9 = the LoRA down-projections
@@ -168,8 +170,16 @@ struct s2v_ctx {
     int ring_pos = 0;
     // graph
     hipStream_t cap_stream = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    GraphKey gkey{nullptr, nullptr, nullptr, -1};
+    // one executable per step-cache mode (GraphKey::mode); the held ones differ in nothing but the mode
+    hipGraphExec_t gexec[3] = {nullptr, nullptr, nullptr};
+    GraphKey gkey[3] = {{nullptr, nullptr, nullptr, -1}, {nullptr, nullptr, nullptr, -1}, {nullptr, nullptr, nullptr, -1}};
+    bool any_graph() const { return gexec[0] || gexec[1] || gexec[2]; }
+    // step cache (include/s2v_hip.h): sc_delta holds IN between the two extra launches of a CAPTURE forward and the residual after it
+    int sc_on = 0;               // s2v_step_cache_enable: 0 off, 1 the cache, 2 the cache + sc_in (IN of every forward, for the read-out)
+    int sc_arm = 0;              // S2V_STEP_*: the mode of the next forward
+    bool sc_valid = false;       // sc_delta is the residual of this geometry / conditioning / weights
+    char *sc_delta = nullptr, *sc_in = nullptr;   // dense [B][V][D], model dtype; allocated beside the workspace, not carved from it
+    int64_t sc_bytes = 0;        // of both buffers
     int split_kind = -1;         // scheduler kind of the s2v_denoise_split_begin that has not met its s2v_denoise_split_end yet (-1: none pending)
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's live roofline figure)
     // + shader-clock stamps (s_memtime / s_memrealtime pairs written by a one-lane kernel right before and right after every profiled launch)
@@ -484,7 +494,9 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
 
 extern "C" void s2v_destroy(s2v_ctx* c) {
     if (!c) return;
-    if (c->gexec) hipGraphExecDestroy(c->gexec);
+    for (hipGraphExec_t g : c->gexec) if (g) hipGraphExecDestroy(g);
+    if (c->sc_delta) hipFree(c->sc_delta);
+    if (c->sc_in) hipFree(c->sc_in);
     if (c->cap_stream) hipStreamDestroy(c->cap_stream);
     if (c->side) hipStreamDestroy(c->side);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -506,7 +518,27 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
 
 // the captured step bakes in what it was captured under: whoever changes that drops the graph, and the next graph step captures again
 static void drop_graph(s2v_ctx* c) {
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+    for (hipGraphExec_t& g : c->gexec) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+}
+
+// step cache: whatever makes the stored residual belong to another computation clears its validity, and with it a pending arm (the next
+// forward then runs FULL: time, never correctness)
+static void sc_invalidate(s2v_ctx* c) { c->sc_valid = false; c->sc_arm = S2V_STEP_FULL; }
+static void sc_free(s2v_ctx* c) {
+    if (c->sc_delta) hipFree(c->sc_delta);
+    if (c->sc_in) hipFree(c->sc_in);
+    c->sc_delta = c->sc_in = nullptr; c->sc_bytes = 0; c->sc_on = 0;
+    sc_invalidate(c);
+}
+// the buffers of level `on` for the current geometry (the caller has synchronised the device and dropped the graphs)
+static int sc_alloc(s2v_ctx* c, int on) {
+    sc_free(c);
+    if (!on) return 0;
+    const int64_t bytes = (int64_t)c->B * c->V * c->D * c->esz;
+    S2V_CHECK_HIP(hipMalloc((void**)&c->sc_delta, bytes));
+    if (on == 2 && hipMalloc((void**)&c->sc_in, bytes) != hipSuccess) { sc_free(c); return s2v_fail(__FILE__, __LINE__, "s2v_step_cache_enable: out of device memory", -2); }
+    c->sc_bytes = on == 2 ? 2 * bytes : bytes; c->sc_on = on;
+    return 0;
 }
 
 // the references beyond the first (s2v_set_conditioning_refs) go with the workspace they were projected for
@@ -525,6 +557,7 @@ extern "C" int s2v_load_weight(s2v_ctx* c, const char* name, const void* dev_ptr
                                int32_t src_dtype, s2v_stream stream) {
     S2V_REQUIRE(c && name && dev_ptr && shape, "s2v_load_weight: null argument");
     S2V_REQUIRE(!c->finalized, "s2v_load_weight: weights already finalized");
+    sc_invalidate(c);
     S2V_REQUIRE(src_dtype == S2V_DTYPE_F32 || src_dtype == S2V_DTYPE_BF16 || src_dtype == S2V_DTYPE_F16, "s2v_load_weight: unsupported source dtype");
     auto it = c->slots.find(name);
     if (it == c->slots.end()) {
@@ -580,6 +613,7 @@ extern "C" int s2v_merge_lora(s2v_ctx* c, const char* name, const float* A, cons
                               s2v_stream stream) {
     S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_merge_lora: bad argument");
     S2V_REQUIRE(!c->finalized, "s2v_merge_lora: weights already finalized");
+    sc_invalidate(c);
     auto it = c->slots.find(name);
     S2V_REQUIRE(it != c->slots.end(), "s2v_merge_lora: unknown tensor name");
     Slot& s = it->second;
@@ -590,6 +624,7 @@ extern "C" int s2v_merge_lora(s2v_ctx* c, const char* name, const float* A, cons
 extern "C" int s2v_finalize_weights(s2v_ctx* c, s2v_stream stream) {
     S2V_REQUIRE(c, "s2v_finalize_weights: null context");
     S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_finalize_weights: a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
+    sc_invalidate(c);
     for (auto& kv : c->slots) {
         if (!kv.second.loaded) {
             std::string m = std::string("s2v_finalize_weights: tensor was never loaded: ") + kv.first;
@@ -648,6 +683,7 @@ extern "C" int s2v_mark_weights_loaded(s2v_ctx* c) {
     S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_mark_weights_loaded: a workspace context (S2V_CTX_ATTN_WORKSPACE) holds no weights");
     for (auto& kv : c->slots) kv.second.loaded = true;
     c->finalized = true;
+    sc_invalidate(c);
     if (c->lora_hdr) {  // the arena may carry an attached adapter: run it
         S2V_CHECK_HIP(hipDeviceSynchronize());
         S2V_CHECK_HIP(hipMemcpy(c->lora_hdr_host, c->lora_hdr, sizeof(c->lora_hdr_host), hipMemcpyDeviceToHost));
@@ -681,9 +717,11 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
                 "s2v_set_shard: fp8 weight formats need an even number of heads per rank, (inner_dim / world) % 128 == 0 (the MX block-scale dwords of "
                 "the attention output hold two heads each)");
     S2V_REQUIRE(c->cfg.out_channels * 4 * c->esz % 16 == 0, "s2v_set_shard: the projected rows must be a multiple of 16 bytes (out_channels * 4 * element size)");
+    sc_invalidate(c);
     if (c->shard && c->sp == world && c->sr == rank) return 0;
     S2V_CHECK_HIP(hipDeviceSynchronize());
     drop_graph(c);
+    sc_free(c);   // a shard context has no step cache
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
     drop_refs(c);
     c->B = 0;
@@ -699,6 +737,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     S2V_REQUIRE(c->kind != S2V_CTX_ATTN_WEIGHTS, "s2v_set_geometry: an attention-weights context (S2V_CTX_ATTN_WEIGHTS) never carves a workspace");
     S2V_REQUIRE(B >= 1 && B <= S2V_MAX_BATCH, "s2v_set_geometry: batch must be 1..8 (S2V_MAX_BATCH: the CFG pairs of at most four videos per call)");
     S2V_REQUIRE(T >= 0 && F >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "s2v_set_geometry: bad geometry");
+    sc_invalidate(c);
     if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
     if (c->shard) S2V_REQUIRE(F * (H / 2) * (W / 2) >= c->sp, "s2v_set_geometry: every rank of a shard needs at least one video row");
     S2V_CHECK_HIP(hipDeviceSynchronize());
@@ -830,6 +869,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
         }
         if (omx) S2V_CHECK_HIP(hipMemcpy(c->omap, omap.data(), omap.size() * 4, hipMemcpyHostToDevice));
     }
+    if (c->sc_on) S2V_TRY(sc_alloc(c, c->sc_on));   // the step cache follows the geometry
     return 0;
 }
 
@@ -841,6 +881,7 @@ extern "C" int s2v_fp8_qk_active(s2v_ctx* c, int32_t* active) {
 
 extern "C" int s2v_set_rope(s2v_ctx* c, const float* cos_dev, const float* sin_dev, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws, "s2v_set_rope: call s2v_set_geometry first");
+    sc_invalidate(c);
     // the captured step bakes in have_rope and the fused-epilogue decision (rope_paired): a change of either drops the graph
     if (!cos_dev || !sin_dev) {
         if (c->have_rope) drop_graph(c);
@@ -886,6 +927,7 @@ extern "C" int s2v_set_rope(s2v_ctx* c, const float* cos_dev, const float* sin_d
 
 extern "C" int s2v_set_pos_embed(s2v_ctx* c, const void* table_dev, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws, "s2v_set_pos_embed: call s2v_set_geometry first");
+    sc_invalidate(c);
     if (!table_dev) { c->have_pos = false; return 0; }
     // shard: the full [V][D] table in, this rank's V_r rows kept
     S2V_CHECK_HIP(hipMemcpyAsync(c->pos_tab, (const char*)table_dev + (size_t)c->v0 * c->D * c->esz, (size_t)c->V * c->D * c->esz,
@@ -945,6 +987,7 @@ static int linear_fp8(s2v_ctx* c, const GemmArgs& g0, int epi, const char* wq, c
 extern "C" int s2v_set_conditioning_refs(s2v_ctx* c, const void* text_dev, const void* ref_latents_dev, int32_t n_ref, s2v_stream stream) {
     S2V_REQUIRE(c && c->ws && c->finalized, "s2v_set_conditioning_refs: geometry and weights must be set first");
     S2V_REQUIRE(text_dev && ref_latents_dev, "s2v_set_conditioning_refs: null input");
+    sc_invalidate(c);
     const int B = c->B;
     S2V_REQUIRE(n_ref == 1 || n_ref == B || (B % 2 == 0 && n_ref == B / 2),
                 "s2v_set_conditioning_refs: n_ref must be 1 (one reference for every sample), B / 2 (one per video of [negative x b | positive x b]) "
@@ -1291,22 +1334,28 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
 // time embedding, every modulation of the step, and the residual streams [text | ref | video] of each sample in X (a shard: this rank's rows
 // [T_r | R_r | V_r]; the latent is patchified whole and the rank's V_r patch rows embedded)
 // latents: sample b reads the latent at (b mod n_lat) * lat_bstride elements (n_lat = 0: at b * lat_bstride)
-static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, hipStream_t st) {
+// video_only (the step cache's REUSE forward): of the modulations only the norm_out rows -- the last 2 D rows of the stack, left compact as
+// [B][2 D] at the start of c->mod -- and of the streams only the video rows; the text and reference rows of X are not written
+static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, hipStream_t st, bool video_only = false) {
     const int D = c->D, B = c->B;
     const int64_t E = c->esz;
     // 1. timestep embedding + every AdaLN modulation of the step in one batched GEMV (temb is block-invariant)
     S2V_TRY(launch_time_embed(t_dev, B, D, c->te1_w, c->te1_b, c->te2_w, c->te2_b, c->temb, c->tmp_te, c->emb, c->dtype, st));
     {
         ProfScope ps(c, PK_OTHER, st);  // the step's modulation GEMV: every norm1 / norm2 / norm_out linear in one launch
-        S2V_TRY(launch_mod_gemv(c->emb, B, c->temb, c->mod_w, c->mod_b, c->mod_rows, c->mod, c->dtype, st));
+        const int64_t r0 = c->mod_rows - 2 * D;   // norm_out's rows
+        if (video_only) S2V_TRY(launch_mod_gemv(c->emb, B, c->temb, c->mod_w + r0 * c->temb * E, c->mod_b + r0 * E, 2 * D, c->mod, c->dtype, st));
+        else S2V_TRY(launch_mod_gemv(c->emb, B, c->temb, c->mod_w, c->mod_b, c->mod_rows, c->mod, c->dtype, st));
     }
     // 2. residual streams: [text | ref | video] per sample
     const int K = c->cfg.in_channels * 4;
     S2V_TRY(launch_patchify(latents, lat_bstride, B, c->F, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st, n_lat));
     for (int b = 0; b < B; ++b) {
         char* xb = c->X + (int64_t)b * c->Ntok * D * E;
-        S2V_TRY(launch_copy_rows(c->e0 + (int64_t)b * c->T * D * E, D, nullptr, 0, xb, D, c->T, D, c->dtype, st));
-        S2V_TRY(launch_copy_rows(c->e1_cur + (b % c->n_ref) * c->e1_stride, D, nullptr, 0, xb + (int64_t)c->T * D * E, D, c->R, D, c->dtype, st));
+        if (!video_only) {
+            S2V_TRY(launch_copy_rows(c->e0 + (int64_t)b * c->T * D * E, D, nullptr, 0, xb, D, c->T, D, c->dtype, st));
+            S2V_TRY(launch_copy_rows(c->e1_cur + (b % c->n_ref) * c->e1_stride, D, nullptr, 0, xb + (int64_t)c->T * D * E, D, c->R, D, c->dtype, st));
+        }
         char* xv = xb + (int64_t)(c->T + c->R) * D * E;
         GemmArgs g{};
         g.A = c->patches + ((int64_t)b * c->gV + c->v0) * K * E; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;
@@ -1318,13 +1367,14 @@ static int embed_streams(s2v_ctx* c, const void* latents, int64_t lat_bstride, i
 }
 
 // final norms + projection on the video rows of X -> c->proj [B * V][Cout]
-static int tail_proj(s2v_ctx* c, hipStream_t st) {
+// compact_mod: norm_out's modulation sits as [B][2 D] at the start of c->mod (embed_streams with video_only), not at its place in the stack
+static int tail_proj(s2v_ctx* c, hipStream_t st, bool compact_mod = false) {
     const int D = c->D, B = c->B;
     const int64_t E = c->esz;
-    const char* mo = c->mod + (int64_t)2 * c->L * c->mc * D * E;
+    const char* mo = compact_mod ? c->mod : c->mod + (int64_t)2 * c->L * c->mc * D * E;
     TailNormArgs t{};
     t.x = c->X; t.ldx = D; t.y = c->tailn; t.ldy = D; t.w1 = c->nf_w; t.b1 = c->nf_b; t.w2 = c->no_w; t.b2 = c->no_b;
-    t.eps = c->cfg.norm_eps; t.shift = mo; t.scale = mo + D * E; t.mod_stride = (int)c->mod_rows;
+    t.eps = c->cfg.norm_eps; t.shift = mo; t.scale = mo + D * E; t.mod_stride = compact_mod ? 2 * D : (int)c->mod_rows;
     t.B = B; t.Ntok = c->Ntok; t.row0 = c->T + c->R; t.V = c->V; t.D = D;
     S2V_TRY(launch_tail_norm(t, c->dtype, st));
     const int Co = c->cfg.out_channels * 4;
@@ -1334,20 +1384,47 @@ static int tail_proj(s2v_ctx* c, hipStream_t st) {
     return linear(c, g, EPI_BIAS, st);
 }
 
+// the step cache's launch on the video rows of X (rows [T + R, T + R + V) of every sample) against a dense buffer
+static int sc_launch(s2v_ctx* c, int op, char* cache, char* keep2, hipStream_t st) {
+    return launch_step_cache(op, c->X + (int64_t)(c->T + c->R) * c->D * c->esz, (int64_t)c->Ntok * c->D, cache, keep2, c->B, (int64_t)c->V * c->D, c->dtype, st);
+}
+// the mode armed for the forward that is about to run (s2v_step_cache_arm): taken once per entry call, outside any capture
+static int sc_take_arm(s2v_ctx* c) {
+    const int m = c->sc_on ? c->sc_arm : S2V_STEP_FULL;
+    c->sc_arm = S2V_STEP_FULL;
+    if (m == S2V_STEP_CAPTURE) c->sc_valid = false;   // valid again once the forward is on the stream (sc_done)
+    return m;
+}
+static int sc_done(s2v_ctx* c, int mode, int r) {
+    if (r == 0 && mode == S2V_STEP_CAPTURE) c->sc_valid = true;
+    return r;
+}
+
+// mode: S2V_STEP_* (include/s2v_hip.h); FULL is the forward as it is without a step cache
 static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, void* out,
-                        hipStream_t st) {
+                        hipStream_t st, int mode = S2V_STEP_FULL) {
     S2V_REQUIRE(c->ws && c->finalized && c->have_cond, "transformer_forward: geometry, weights and conditioning required");
     S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "transformer_forward: RoPE tables missing (s2v_set_rope)");
     S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "transformer_forward: sincos table missing (s2v_set_pos_embed)");
     S2V_REQUIRE(!c->shard, "transformer_forward: a shard context (s2v_set_shard) runs the staged step only (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     const int D = c->D;
     const int64_t E = c->esz;
-    S2V_TRY(embed_streams(c, latents, lat_bstride, n_lat, t_dev, st));
-    // 3. blocks
-    for (int l = 0; l < c->L; ++l)
-        S2V_TRY(run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st));
+    const bool reuse = mode == S2V_STEP_REUSE;
+    S2V_REQUIRE(mode == S2V_STEP_FULL || (c->sc_on && c->sc_delta), "transformer_forward: a step-cache mode without s2v_step_cache_enable");
+    S2V_REQUIRE(!reuse || c->sc_valid, "transformer_forward: S2V_STEP_REUSE without a captured residual");
+    S2V_TRY(embed_streams(c, latents, lat_bstride, n_lat, t_dev, st, reuse));
+    if (mode == S2V_STEP_CAPTURE) S2V_TRY(sc_launch(c, SC_KEEP, c->sc_delta, c->sc_in, st));   // IN
+    else if (c->sc_in) S2V_TRY(sc_launch(c, SC_KEEP, c->sc_in, nullptr, st));                  // enable 2: IN of every forward, for the read-out
+    if (reuse) {
+        S2V_TRY(sc_launch(c, SC_ADD, c->sc_delta, nullptr, st));                               // X_video = rnd(IN' + delta)
+    } else {
+        // 3. blocks
+        for (int l = 0; l < c->L; ++l)
+            S2V_TRY(run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st));
+        if (mode == S2V_STEP_CAPTURE) S2V_TRY(sc_launch(c, SC_SUB, c->sc_delta, nullptr, st)); // delta = rnd(OUT - IN)
+    }
     // 4. tail
-    S2V_TRY(tail_proj(c, st));
+    S2V_TRY(tail_proj(c, st, reuse));
     const int Co = c->cfg.out_channels * 4;
     S2V_TRY(launch_unpatchify(c->proj, Co, c->V, out, c->B, c->F, c->cfg.out_channels, c->H, c->W, c->dtype, st));
     return 0;
@@ -1356,14 +1433,16 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, in
 extern "C" int s2v_transformer_forward(s2v_ctx* c, const void* latents, int64_t lat_bstride, const float* timesteps_dev,
                                        void* out, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward: null argument");
-    return forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream);
+    const int mode = sc_take_arm(c);
+    return sc_done(c, mode, forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream, mode));
 }
 
 extern "C" int s2v_transformer_forward_videos(s2v_ctx* c, const void* latents, int32_t n_lat, const float* timesteps_dev, void* out,
                                               s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward_videos: null argument");
+    const int mode = sc_take_arm(c);
     S2V_REQUIRE(c->ws && n_lat >= 1 && c->B % n_lat == 0, "s2v_transformer_forward_videos: n_lat must divide the geometry's batch (sample j embeds latent j mod n_lat)");
-    return forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream);
+    return sc_done(c, mode, forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream, mode));
 }
 
 // the residual streams of every sample between the caller's dense tensors (s0: n0 rows, s1: n1 rows, video: V rows per sample; n0 + n1 = T + R)
@@ -1507,13 +1586,14 @@ static int lora_write_hdr(s2v_ctx* c, hipStream_t st) {
 }
 
 static void lora_drop_graph(s2v_ctx* c) {
-    if (c->gexec) (void)hipDeviceSynchronize();  // the graph may still be replaying
+    if (c->any_graph()) (void)hipDeviceSynchronize();  // the graph may still be replaying
     drop_graph(c);
 }
 
 extern "C" int s2v_lora_attach(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream) {
     S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_lora_attach: bad argument");
     S2V_TRY(lora_checks(c, "s2v_lora_attach"));
+    sc_invalidate(c);
     Slot* s = nullptr;
     S2V_TRY(lora_find(c, "s2v_lora_attach", name, rank, &s));
     S2V_TRY(lora_write(c, name, *s, A, B, rank, scale, true, (hipStream_t)stream));
@@ -1527,6 +1607,7 @@ extern "C" int s2v_lora_attach(s2v_ctx* c, const char* name, const float* A, con
 extern "C" int s2v_lora_set_scale(s2v_ctx* c, const char* name, const float* A, const float* B, int32_t rank, float scale, s2v_stream stream) {
     S2V_REQUIRE(c && name && A && B && rank > 0, "s2v_lora_set_scale: bad argument");
     S2V_TRY(lora_checks(c, "s2v_lora_set_scale"));
+    sc_invalidate(c);
     Slot* s = nullptr;
     S2V_TRY(lora_find(c, "s2v_lora_set_scale", name, rank, &s));
     auto it = c->lora_names.find(name);
@@ -1540,6 +1621,7 @@ extern "C" int s2v_lora_set_scale(s2v_ctx* c, const char* name, const float* A, 
 extern "C" int s2v_lora_detach(s2v_ctx* c, s2v_stream stream) {
     S2V_REQUIRE(c, "s2v_lora_detach: null context");
     S2V_TRY(lora_checks(c, "s2v_lora_detach"));
+    sc_invalidate(c);
     hipStream_t st = (hipStream_t)stream;
     if (!c->lora_on()) return 0;
     const int64_t E = c->esz, lr = c->lr, fl = c->flr;
@@ -1583,7 +1665,7 @@ extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, floa
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
     S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
     *arena = c->arena ? c->arena_bytes : 0;
-    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes : 0;
+    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes : 0;
     return 0;
 }
 
@@ -1668,23 +1750,28 @@ static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_hos
 
 // the graph cache: replay the captured `body` on st; a first use or another key captures body(cap_stream) anew.  A body that fails ends the
 // capture and returns its code with no graph held
+// One executable per step-cache mode (key.mode): a plan that alternates between modes captures each kind once.  A key that differs from a
+// held one in anything but the mode drops every executable, as the single one was dropped before modes existed
 template <class Body>
 static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body body) {
-    if (!c->gexec || !(c->gkey == key)) {
-        drop_graph(c);
+    for (int m = 0; m < 3; ++m)
+        if (c->gexec[m] && !c->gkey[m].same_but_mode(key)) { drop_graph(c); break; }
+    hipGraphExec_t& gexec = c->gexec[key.mode];
+    if (!gexec) {
         hipGraph_t graph = nullptr;
         S2V_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
         const int r = body(c->cap_stream);
         hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
         if (r != 0) { if (graph) hipGraphDestroy(graph); return r; }
         S2V_CHECK_HIP(e);
-        e = hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0);
+        e = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
         hipGraphDestroy(graph);
+        if (e != hipSuccess) gexec = nullptr;
         S2V_CHECK_HIP(e);
         c->graph_captures++;
-        c->gkey = key;
+        c->gkey[key.mode] = key;
     }
-    S2V_CHECK_HIP(hipGraphLaunch(c->gexec, st));
+    S2V_CHECK_HIP(hipGraphLaunch(gexec, st));
     return 0;
 }
 
@@ -1699,16 +1786,17 @@ static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* 
     return launch_sched_step(a, c->dtype, st);
 }
 
-static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
+static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode) {
     // b videos: sample j of [negative x b | positive x b] embeds video j mod b straight from `latents` (one video: the stride of 0 it always had)
     const int b = c->B >= 2 ? c->B / 2 : 1;
-    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st));
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode));
     return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b);
 }
 
 // the whole step of b = B/2 videos (b = 1 for B = 1 or 2) at timesteps[b] and coefs[b]; s2v_denoise_step's wording serves both entries
 static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist, const void* noise,
                              int32_t use_graph, hipStream_t st) {
+    const int mode = sc_take_arm(c);
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
     const int b = c->B >= 2 ? c->B / 2 : 1;
@@ -1717,8 +1805,10 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
                                        "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
                                      : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     S2V_TRY(stage_step(c, timesteps, coefs, b, st));
-    if (!use_graph) return step_launches(c, latents, x0_hist, noise, st);
-    return launch_captured(c, GraphKey{latents, x0_hist, noise, -1}, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s); });
+    if (!use_graph) return sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode));
+    GraphKey key{latents, x0_hist, noise, -1};
+    key.mode = mode;
+    return sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode); }));
 }
 
 extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
@@ -1747,9 +1837,9 @@ extern "C" int s2v_set_blend(s2v_ctx* c, const void* z0, const void* noise0, con
     return 0;
 }
 
-static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
+static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode) {
     const int b = c->B / 2;
-    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st));
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode));
     SchedMaskArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
     a.nvid = b; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
@@ -1762,6 +1852,7 @@ static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const
 extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
                                        float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps && coefs && blends, "s2v_denoise_step_masked: null argument");
+    const int mode = sc_take_arm(c);
     S2V_REQUIRE(!c->shard, "s2v_denoise_step_masked: a shard context (s2v_set_shard) has no masked step: masked video-to-video runs on one GPU");
     S2V_REQUIRE(c->ws && c->B != 1, "s2v_denoise_step_masked: a geometry with B = 1 is one sample of a CFG-parallel pair, and the split entries "
                                     "(s2v_denoise_split_begin / _end, s2v_denoise_step_cfg_parallel) have no masked form: masked video-to-video runs the "
@@ -1773,10 +1864,10 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step_masked: DPM needs noise and x0_hist");
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
-    if (!use_graph) return masked_step_launches(c, latents, x0_hist, noise, st);
+    if (!use_graph) return sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask;
-    return launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s); });
+    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode;
+    return sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode); }));
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------
@@ -1794,6 +1885,8 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
     // a begin is pending only once its forward is on the stream: whatever fails below, s2v_denoise_split_end finds none
     if (c) c->split_kind = -1;
     S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_split_begin: null argument");
+    S2V_REQUIRE(sc_take_arm(c) == S2V_STEP_FULL, "s2v_denoise_split_begin: a step-cache mode (s2v_step_cache_arm: CAPTURE / REUSE) is armed, and CFG-parallel "
+                                                 "has its own forward per rank: the step cache runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required; a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");
@@ -2106,6 +2199,77 @@ extern "C" int s2v_last_noise_pred(s2v_ctx* c, void** dev_ptr) {
 }
 
 // ------------------------------------------------------------------------------------------------------
+// ---- step cache (include/s2v_hip.h) -------------------------------------------------------------------------------------------------
+extern "C" int s2v_step_cache_enable(s2v_ctx* c, int32_t on) {
+    S2V_REQUIRE(c, "s2v_step_cache_enable: null context");
+    S2V_REQUIRE(on >= 0 && on <= 2, "s2v_step_cache_enable: 0 (off), 1 (the cache) or 2 (the cache and the IN buffer of the read-out)");
+    S2V_REQUIRE(!on || c->kind == S2V_CTX_MODEL, "s2v_step_cache_enable: attention-only contexts (S2V_CTX_ATTN_*) run no forward");
+    S2V_REQUIRE(!on || !c->shard, "s2v_step_cache_enable: a shard context (s2v_set_shard) has no step cache: it runs on one GPU");
+    S2V_REQUIRE(!on || c->ws, "s2v_step_cache_enable: call s2v_set_geometry first (the cache is [B][V][D] of the current geometry)");
+    if (on == c->sc_on) { sc_invalidate(c); return 0; }
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    drop_graph(c);   // a captured step bakes in the buffers and (enable 2) the IN copy
+    return sc_alloc(c, on);
+}
+
+extern "C" int s2v_step_cache_arm(s2v_ctx* c, int32_t mode) {
+    S2V_REQUIRE(c, "s2v_step_cache_arm: null context");
+    S2V_REQUIRE(mode == S2V_STEP_FULL || mode == S2V_STEP_CAPTURE || mode == S2V_STEP_REUSE, "s2v_step_cache_arm: S2V_STEP_FULL, S2V_STEP_CAPTURE or S2V_STEP_REUSE");
+    if (mode != S2V_STEP_FULL) {
+        S2V_REQUIRE(!c->shard, "s2v_step_cache_arm: a shard context (s2v_set_shard) runs the staged step, which has no cached form: the step cache runs on one GPU");
+        S2V_REQUIRE(c->sc_on && c->sc_delta, "s2v_step_cache_arm: the step cache is not enabled (s2v_step_cache_enable)");
+        S2V_REQUIRE(mode != S2V_STEP_REUSE || c->sc_valid, "s2v_step_cache_arm: no captured residual for this geometry / conditioning / weights");
+    }
+    c->sc_arm = mode;
+    return 0;
+}
+
+extern "C" int s2v_step_cache_state(s2v_ctx* c, int32_t* enabled, int32_t* valid, int64_t* bytes) {
+    S2V_REQUIRE(c && enabled && valid && bytes, "s2v_step_cache_state: null argument");
+    *enabled = c->sc_on; *valid = c->sc_valid ? 1 : 0; *bytes = c->sc_bytes;
+    return 0;
+}
+
+extern "C" int s2v_step_cache_read(s2v_ctx* c, int32_t which, void* out_dev, s2v_stream stream) {
+    S2V_REQUIRE(c && out_dev, "s2v_step_cache_read: null argument");
+    S2V_REQUIRE(which >= 0 && which <= 2, "s2v_step_cache_read: which is 0 (IN), 1 (OUT) or 2 (the residual)");
+    S2V_REQUIRE(c->ws && !c->shard, "s2v_step_cache_read: a geometry on an unsharded context is required");
+    S2V_REQUIRE(which != 0 || c->sc_in, "s2v_step_cache_read: IN is kept only under s2v_step_cache_enable(ctx, 2)");
+    S2V_REQUIRE(which != 2 || (c->sc_delta && c->sc_valid), "s2v_step_cache_read: no captured residual for this geometry / conditioning / weights");
+    hipStream_t st = (hipStream_t)stream;
+    if (which == 1) return sc_launch(c, SC_KEEP, (char*)out_dev, nullptr, st);
+    S2V_CHECK_HIP(hipMemcpyAsync(out_dev, which == 0 ? c->sc_in : c->sc_delta, (size_t)c->B * c->V * c->D * c->esz, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+extern "C" int s2v_op_step_cache(int32_t op, void* x, int64_t x_bstride, void* cache, int32_t B, int64_t n, int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(x && cache && B >= 1 && n >= 1 && x_bstride >= n, "s2v_op_step_cache: null argument, or samples that overlap (x_bstride < n)");
+    S2V_REQUIRE(dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_F16, "s2v_op_step_cache: dtype must be f32, bf16 or f16");
+    return launch_step_cache(op, x, x_bstride, cache, nullptr, B, n, dtype, (hipStream_t)stream);
+}
+
+extern "C" int s2v_time_embedding(s2v_ctx* c, const float* timesteps_host, int32_t n, void* out_dev, s2v_stream stream) {
+    S2V_REQUIRE(c && timesteps_host && out_dev && n >= 1, "s2v_time_embedding: null argument");
+    S2V_REQUIRE(c->kind == S2V_CTX_MODEL && c->finalized, "s2v_time_embedding: a model context with finalized weights is required");
+    hipStream_t st = (hipStream_t)stream;
+    // scratch of its own (no geometry needed): the timesteps, then launch_time_embed's [chunk][D] sinusoid and [chunk][temb] hidden
+    const int64_t E = c->esz, tmp_bytes = (int64_t)S2V_MAX_BATCH * (c->D + c->temb) * E;
+    char* buf = nullptr;
+    S2V_CHECK_HIP(hipMalloc((void**)&buf, 256 + tmp_bytes));
+    int r = 0;
+    for (int i0 = 0; i0 < n && !r; i0 += S2V_MAX_BATCH) {
+        const int nb = std::min<int>(S2V_MAX_BATCH, n - i0);
+        hipError_t e = hipStreamSynchronize(st);   // the previous chunk has read the scratch
+        if (e == hipSuccess) e = hipMemcpy(buf, timesteps_host + i0, sizeof(float) * nb, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { r = s2v_fail(__FILE__, __LINE__, hipGetErrorString(e), -2); break; }
+        r = launch_time_embed((const float*)buf, nb, c->D, c->te1_w, c->te1_b, c->te2_w, c->te2_b, c->temb, buf + 256, (char*)out_dev + (int64_t)i0 * c->temb * E,
+                              c->dtype, st);
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    return r;
+}
+
 extern "C" int s2v_op_linear(const void* A, const void* W, const void* bias, void* C, int32_t M, int32_t N, int32_t K,
                              int32_t epilogue, int32_t dtype, int32_t impl, s2v_stream stream) {
     S2V_REQUIRE(A && W && C, "s2v_op_linear: null argument");
@@ -2421,6 +2585,7 @@ extern "C" int s2v_attn_slow_stats(s2v_ctx* c, uint64_t* slow, uint64_t* total, 
 extern "C" int s2v_set_attn_p_format(s2v_ctx* c, int32_t fmt) {
     S2V_REQUIRE(c, "s2v_set_attn_p_format: null context");
     S2V_REQUIRE(fmt == 0 || fmt == 1, "s2v_set_attn_p_format: 0 (bf16) or 1 (fp16)");
+    sc_invalidate(c);
     if (c->attn_p16 != (fmt == 1)) {
         S2V_CHECK_HIP(hipDeviceSynchronize());
         c->attn_p16 = fmt == 1;

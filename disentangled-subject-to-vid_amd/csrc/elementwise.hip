@@ -1189,3 +1189,51 @@ int launch_quant_rows_fp8(const void* src, int64_t ld, int64_t M, int K, void* d
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Step cache (include/s2v_hip.h): the video rows of the packed residual buffer -- sample b's n = V * D elements start at x + b * x_bstride
+// and are contiguous, rows being D apart -- against the dense cache [B][n].  Streaming kernels: every lane moves 16 bytes per operand and
+// round, blockIdx.y is the sample, the grid strides over the sample's n / Vec16<T>::N vectors (any count: no multiple of the block is assumed).
+//   SC_KEEP: cache = x (and keep2 = x when given)      SC_SUB: cache = rnd(float(x) - float(cache))      SC_ADD: x = rnd(float(x) + float(cache))
+// The sums are single fp32 operations rounded once to T (round to nearest even); this translation unit is built without fma contraction.
+template <typename T, int OP>
+__global__ __launch_bounds__(256) void step_cache_k(T* x, int64_t x_bstride, T* cache, T* keep2, int64_t nvec) {
+    constexpr int VN = Vec16<T>::N;
+    T* xs = x + (int64_t)blockIdx.y * x_bstride;
+    T* cs = cache + (int64_t)blockIdx.y * nvec * VN;
+    T* ks = keep2 ? keep2 + (int64_t)blockIdx.y * nvec * VN : nullptr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+        if (OP == SC_KEEP) {
+            const typename Vec16<T>::raw_t v = Vec16<T>::ldraw(xs + i * VN);
+            *(typename Vec16<T>::raw_t*)(cs + i * VN) = v;
+            if (ks) *(typename Vec16<T>::raw_t*)(ks + i * VN) = v;
+        } else {
+            float a[VN], d[VN], o[VN];
+            Vec16<T>::ld(xs + i * VN, a);
+            Vec16<T>::ld(cs + i * VN, d);
+#pragma unroll
+            for (int e = 0; e < VN; ++e) o[e] = OP == SC_SUB ? a[e] - d[e] : a[e] + d[e];
+            Vec16<T>::st(OP == SC_SUB ? cs + i * VN : xs + i * VN, o);
+        }
+    }
+}
+int launch_step_cache(int op, void* x, int64_t x_bstride, void* cache, void* keep2, int B, int64_t n, int dtype, hipStream_t st) {
+    const int esz = dtype == S2V_F32 ? 4 : 2, vn = 16 / esz;
+    S2V_REQUIRE(op == SC_KEEP || op == SC_SUB || op == SC_ADD, "step_cache: unknown operation");
+    S2V_REQUIRE(n % vn == 0 && x_bstride % vn == 0 && ((uintptr_t)x | (uintptr_t)cache | (uintptr_t)keep2) % 16 == 0,
+                "step_cache: the rows must be whole 16-byte vectors on 16-byte boundaries");
+    if (B <= 0 || n <= 0) return 0;
+    const int64_t nvec = n / vn;
+    // at most ~2048 workgroups in all (eight per CU); the rest of a sample is taken by the grid stride
+    const int64_t cap = std::max<int64_t>(1, 2048 / B);
+    dim3 grid((unsigned)std::min<int64_t>((nvec + 255) / 256, cap), (unsigned)B);
+#define S2V_SC_OP(OP) hipLaunchKernelGGL((step_cache_k<T, OP>), grid, dim3(256), 0, st, (T*)x, x_bstride, (T*)cache, (T*)keep2, nvec)
+    S2V_DT_DISPATCH(dtype, {
+        if (op == SC_KEEP) S2V_SC_OP(SC_KEEP);
+        else if (op == SC_SUB) S2V_SC_OP(SC_SUB);
+        else S2V_SC_OP(SC_ADD);
+    })
+#undef S2V_SC_OP
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}

@@ -326,6 +326,10 @@ int launch_shard_scales(const ShardScaleArgs& a, hipStream_t st);
 // dst[r][:] = rnd(src[r][:] (+ add[r][:]))
 int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void* dst, int ldd, int rows, int D,
                      int dtype, hipStream_t st);
+// step cache (include/s2v_hip.h): sample b's n contiguous elements at x + b * x_bstride against the dense cache [B][n]
+//   SC_KEEP: cache = x (and keep2 = x when non-null)   SC_SUB: cache = rnd(x - cache)   SC_ADD: x = rnd(x + cache)
+enum { SC_KEEP = 0, SC_SUB = 1, SC_ADD = 2 };
+int launch_step_cache(int op, void* x, int64_t x_bstride, void* cache, void* keep2, int B, int64_t n, int dtype, hipStream_t st);
 // final: y = LN2(LN1(x)) * (1+scale[b]) + shift[b]   on video rows  (cogvideox_transformer_3d.py:536-542)
 struct TailNormArgs {
     const void* x; int ldx; void* y; int ldy;

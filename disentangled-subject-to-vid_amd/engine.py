@@ -410,10 +410,49 @@ class S2VEngine:
         if self.kind == _lib.CTX_MODEL and self._cond_args is not None and self.geometry is not None:
             self.set_conditioning(*self._cond_args)
 
+    # ---- step cache (include/s2v_hip.h: s2v_step_cache_*) ------------------------------------------------------------------------------
+    _CACHE_MODES = {None: _lib.STEP_FULL, "full": _lib.STEP_FULL, "capture": _lib.STEP_CAPTURE, "reuse": _lib.STEP_REUSE}
+
+    def step_cache_enable(self, on=True):
+        """after set_geometry: True / 1 allocates the residual cache [B,V,D] of the current geometry, 2 additionally the buffer that keeps the
+        embedded video rows of every forward for step_cache_read(0) (diagnostics), False / 0 frees both"""
+        _lib.check(_lib.lib().s2v_step_cache_enable(self._h, int(on)))
+
+    def step_cache_state(self):
+        """{"enabled": 0 / 1 / 2, "valid": a residual is held, "bytes": device bytes of the cache buffers}"""
+        e, v, n = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        _lib.check(_lib.lib().s2v_step_cache_state(self._h, ctypes.byref(e), ctypes.byref(v), ctypes.byref(n)))
+        return {"enabled": e.value, "valid": bool(v.value), "bytes": n.value}
+
+    def step_cache_read(self, which):
+        """[B,V,D] in the model dtype: 0 the video rows as the last forward embedded them (enable 2 only), 1 the video rows as its tail read
+        them, 2 the residual"""
+        B, T, F, H, W = self.geometry
+        out = torch.empty((B, F * (H // 2) * (W // 2), self.D), dtype=self.dtype, device=self.device)
+        _lib.check(_lib.lib().s2v_step_cache_read(self._h, int(which), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def time_embedding(self, timesteps):
+        """[n, time_embed_dim] in the model dtype: row i is the timestep embedding a step at timesteps[i] computes (s2v_time_embedding): the
+        indicator of step_cache_plan.  Needs finalized weights only"""
+        ts = [float(t) for t in (timesteps.reshape(-1).tolist() if isinstance(timesteps, (torch.Tensor, np.ndarray)) else timesteps)]
+        out = torch.empty((len(ts), self.cfg.time_embed_dim), dtype=self.dtype, device=self.device)
+        _lib.check(_lib.lib().s2v_time_embedding(self._h, (ctypes.c_float * len(ts))(*ts), len(ts), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def _arm(self, cache):
+        """the step-cache mode of the next forward: None / "full", "capture" (a full step that also stores the block stack's contribution to
+        the video rows) or "reuse" (embed, add the stored contribution, tail)"""
+        if cache not in self._CACHE_MODES:
+            raise _lib.S2VError(f"unknown cache mode {cache!r} (None, 'capture' or 'reuse')")
+        if self._CACHE_MODES[cache] != _lib.STEP_FULL:
+            _lib.check(_lib.lib().s2v_step_cache_arm(self._h, self._CACHE_MODES[cache]))
+
     # ---- compute -------------------------------------------------------------------------------------------
-    def forward(self, latents, timesteps, shared_latent=False):
+    def forward(self, latents, timesteps, shared_latent=False, cache=None):
         """CogVideoXTransformer3DModel.forward seam: latents [B,F,C,H,W]; with shared_latent [n,F,C,H,W], n dividing B: sample j embeds latent
-        j mod n (n = 1: every sample the same latent; n = B/2: the CFG batch cat([latents] * 2) of B/2 videos without the copy)."""
+        j mod n (n = 1: every sample the same latent; n = B/2: the CFG batch cat([latents] * 2) of B/2 videos without the copy).
+        cache: the step-cache mode of this forward (_arm; after step_cache_enable)"""
         B, T, F, H, W = self.geometry
         lat = latents.to(self.device, self.dtype).contiguous()
         n_lat = lat.numel() // (F * self.cfg.in_channels * H * W)
@@ -424,6 +463,7 @@ class S2VEngine:
         if t.numel() != B:
             t = t.reshape(-1)[:1].expand(B).contiguous()
         out = torch.empty((B, F, self.cfg.out_channels, H, W), dtype=self.dtype, device=self.device)
+        self._arm(cache)
         if shared_latent and n_lat > 1:
             _lib.check(_lib.lib().s2v_transformer_forward_videos(self._h, _lib.ptr(lat), n_lat, _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr()))
             return out
@@ -494,12 +534,13 @@ class S2VEngine:
             _lib.check(_lib.lib().s2v_set_blend(self._h, None, None, None, 0))
             self._blend = None
 
-    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None):
+    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
         [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
         (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
         coef[k] -- its own kind, guidance and scalars (s2v_denoise_step_videos); a scalar beside a sequence is repeated.
-        blend: the masked step (s2v_denoise_step_masked, after set_blend): one _lib.BlendC, or a sequence of b, video k blended with blend[k]"""
+        blend: the masked step (s2v_denoise_step_masked, after set_blend): one _lib.BlendC, or a sequence of b, video k blended with blend[k]
+        cache: the step-cache mode of this step's forward (_arm; after step_cache_enable): "capture", "reuse" or None"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
@@ -522,6 +563,7 @@ class S2VEngine:
         auto = self._attn_auto_pending
         if auto:
             self.attn_slow_stats(reset=True)
+        self._arm(cache)
         if blend is not None:
             _lib.check(_lib.lib().s2v_denoise_step_masked(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                           int(use_graph and not auto), _lib.stream_ptr()))

@@ -36,6 +36,40 @@ def cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt=1):
     return torch.cat([expand_prompts(negative_prompt_embeds, num_videos_per_prompt), expand_prompts(prompt_embeds, num_videos_per_prompt)], dim=0)
 
 
+class StepCache:
+    """the arguments of step_cache_plan as one object (S2VPipeline.__call__(step_cache=...))"""
+
+    def __init__(self, threshold, coefficients=(1.0, 0.0), keep_first=1, keep_last=1):
+        self.threshold, self.coefficients, self.keep_first, self.keep_last = threshold, tuple(coefficients), keep_first, keep_last
+
+
+def step_cache_plan(emb, threshold, coefficients=(1.0, 0.0), keep_first=1, keep_last=1):
+    """which steps of a call run the block stack: [n] booleans, True = a full step, from the timestep embeddings emb [n, time_embed_dim] of
+    the call's timesteps (S2VEngine.time_embedding), taken to float64.  Pure host arithmetic: the indicator depends on the timesteps and the
+    weights only, so the whole plan exists before the loop.
+    Step 0 and the first keep_first steps are full, and so are the last keep_last.  In between d_i = mean|e_i - e_(i-1)| / mean|e_(i-1)| and
+    acc += polyval(coefficients, d_i): the step reuses the stored contribution while acc < threshold, otherwise it is full and acc = 0.  Any
+    full step resets acc.  coefficients (highest power first, as numpy.polyval takes them) default to the identity: a rescaling polynomial
+    fitted to a model is the caller's to bring"""
+    if threshold < 0:
+        raise ValueError(f"step cache: the threshold must be >= 0, got {threshold}")
+    e = np.asarray(emb.detach().double().cpu() if isinstance(emb, torch.Tensor) else emb, dtype=np.float64)
+    if e.ndim != 2:
+        raise ValueError(f"step cache: the embeddings must be [steps, time_embed_dim], got {e.shape}")
+    n = e.shape[0]
+    plan, acc = [], 0.0
+    for i in range(n):
+        full = i == 0 or i < keep_first or i >= n - keep_last
+        if not full:
+            d = np.abs(e[i] - e[i - 1]).mean() / np.abs(e[i - 1]).mean()
+            acc += float(np.polyval(coefficients, d))
+            full = not acc < threshold
+        if full:
+            acc = 0.0
+        plan.append(bool(full))
+    return plan
+
+
 class S2VPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]  # pipeline_cogvideox.py:166-170
 
@@ -202,6 +236,36 @@ class S2VPipeline:
         return m
 
     @staticmethod
+    def check_step_cache(step_cache, per_video=False, cfg_parallel=None, ulysses=None, fused=True, videos_path=False):
+        """every refusal of a step-cache call that needs no step count (no device is touched); returns the argument as a StepCache or a list"""
+        if per_video or videos_path:
+            raise ValueError("`step_cache` together with per-video lists (or several input videos, which run per-video plans): videos on different "
+                             "timesteps have different plans of full and reuse steps, and the batch runs one launch sequence")
+        for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+            if arg is not None:
+                raise ValueError(f"`step_cache` together with `{name}`: the step cache runs on one GPU; CFG-parallel and Ulysses have their own forward")
+        if not fused:
+            raise ValueError("`step_cache` together with fused=False: the cache lives in the fused step; fused=False is the reference's seam sequence")
+        if isinstance(step_cache, StepCache):
+            sc = step_cache
+        elif isinstance(step_cache, (list, tuple)):
+            if len(step_cache) > 0 and not step_cache[0]:
+                raise ValueError("`step_cache` as a list: step 0 cannot be a reuse (nothing has been captured yet)")
+            return [bool(x) for x in step_cache]
+        else:
+            sc = StepCache(float(step_cache))
+        if sc.threshold < 0:
+            raise ValueError(f"`step_cache`: the threshold must be >= 0, got {sc.threshold}")
+        return sc
+
+    @staticmethod
+    def check_step_cache_length(sc, n):
+        if isinstance(sc, list) and len(sc) != n:
+            raise ValueError(f"`step_cache` is a list of {len(sc)} entries for the {n} steps this call runs: one boolean per step actually run")
+
+    step_cache_report = None
+
+    @staticmethod
     def blend_plan(scheduler, plan, dtype, device="cpu"):
         """the masked step's record (scheduler.blend_record) for every step of a video_plan: step i blends at the video's NEXT timestep
         t[i + 1], the last step is flagged and keeps the clean latents"""
@@ -235,7 +299,7 @@ class S2VPipeline:
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
-                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True):
+                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -260,7 +324,15 @@ class S2VPipeline:
         start is video-to-video's; after every step the kept latents are the input's, noised to the video's next timestep with the noise that
         started the loop, and after the last step the clean ones (pipeline_stable_diffusion_inpaint.py:1271-1285); a step-end callback sees
         the blended latents.  paste_back (frames only): where the PIXEL mask is 0 the frames are the post-processed input video, exactly.
-        Only with `video`; not with cfg_parallel= or ulysses=."""
+        Only with `video`; not with cfg_parallel= or ulysses=.
+        step_cache: skip the block stack on steps whose timestep embedding barely moved since the last full step -- a threshold (float), a
+        StepCache(threshold, coefficients, keep_first, keep_last), or a list of booleans, one per step actually run (True = full).  The plan
+        (step_cache_plan) comes from the call's own timesteps before the loop; a full step that a reuse follows stores the block stack's
+        contribution to the video rows, a reuse step embeds its latents, adds it and runs the tail.  CFG, the scheduler step, the DPM draws and
+        the mask's select run on every step.  A planned reuse runs full when the stored contribution is no longer valid (a callback replaced
+        `prompt_embeds`).  After the call `step_cache_report` holds {"plan", "full", "reused", "ran_full"}.  Scalars only (b > 1 videos share
+        the timesteps); refused with per-video lists, several input videos, cfg_parallel=, ulysses= and fused=False."""
+        self.step_cache_report = None
         if mask is not None and video is None:
             self.check_mask(mask, None, 1)
         per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength))
@@ -301,6 +373,8 @@ class S2VPipeline:
         b = self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents, generator, video, cfg_parallel, ulysses)
         if mask is not None:
             mask = self.check_mask(mask, video, b, cfg_parallel, ulysses)
+        if step_cache is not None:
+            step_cache = self.check_step_cache(step_cache, per_video, cfg_parallel, ulysses, fused, video is not None and b > 1)
         if per_video or (video is not None and b > 1):   # every video on its own plan; scalars and one input video stay on the path below
             lists = self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)
             return self._call_videos(b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg,
@@ -315,9 +389,11 @@ class S2VPipeline:
             timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, timesteps, strength, sch.order)
             if len(timesteps) == 0:
                 raise ValueError(f"strength {strength} keeps none of the {sch.num_inference_steps} timesteps")
+            self.check_step_cache_length(step_cache, len(timesteps))
             latents, z0, noise0 = self.prepare_video_latents(video, dt, dev, generator, timesteps[:1], parts=True)
             latents = latents.to(dt).contiguous()
         else:
+            self.check_step_cache_length(step_cache, len(timesteps))
             latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b).to(dt).contiguous()
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
         ref = ref_img_states.to(dev, dt)
@@ -359,8 +435,18 @@ class S2VPipeline:
             noise = torch.empty_like(latents) if is_dpm else None
             if mask is not None:
                 eng.set_blend(z0, noise0, lat_mask)
+        sc_plan = None
+        if step_cache is not None:   # the whole plan on the host, before the loop: no read-back inside it, a captured step stays a replay
+            if isinstance(step_cache, list):
+                sc_plan = step_cache
+            else:
+                sc_plan = step_cache_plan(eng.time_embedding([float(t) for t in timesteps]), step_cache.threshold, step_cache.coefficients,
+                                          step_cache.keep_first, step_cache.keep_last)
+            self.step_cache_report = {"plan": list(sc_plan), "full": 0, "reused": 0, "ran_full": []}
         old = None
         try:
+            if sc_plan is not None:
+                eng.step_cache_enable(True)
             for i, t in enumerate(timesteps):
                 if self.interrupt:
                     break
@@ -379,8 +465,18 @@ class S2VPipeline:
                     if ulysses is not None:
                         ulysses.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
                     elif cfg_parallel is None:
+                        cache = None
+                        if sc_plan is not None:
+                            rep = self.step_cache_report
+                            if not sc_plan[i] and eng.step_cache_state()["valid"]:
+                                cache = "reuse"
+                            elif i + 1 < len(sc_plan) and not sc_plan[i + 1]:
+                                cache = "capture"   # a reuse follows: store the contribution; otherwise the step runs as it does without a cache
+                            if not sc_plan[i] and cache != "reuse":
+                                rep["ran_full"].append(i)
+                            rep["reused" if cache == "reuse" else "full"] += 1
                         eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph,
-                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev))
+                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev), cache=cache)
                     else:
                         cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
                 else:
@@ -421,6 +517,8 @@ class S2VPipeline:
         finally:
             if fused and mask is not None:
                 eng.clear_blend()
+            if sc_plan is not None:
+                eng.step_cache_enable(False)
         return self._finish(latents, fused, output_type, return_dict, paste)
 
     def _finish(self, latents, fused, output_type, return_dict, paste=None):

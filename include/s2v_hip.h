@@ -324,6 +324,45 @@ S2V_API int s2v_sched_step_masked(s2v_ctx* ctx, const s2v_sched_coef* coef_host,
 /* pointer to the [B,F,C,H,W] model output of the last s2v_denoise_step (context-owned, model dtype) */
 S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 
+/* ---- Step cache: a step whose timestep embedding barely moved skips the block stack ---------------------------------------------------------
+ * Opt-in state on a model context.  X is the packed residual buffer [B][Ntok][D]; its video rows are rows [T + R, T + R + V) of each sample.
+ * The cache is dense [B][V][D] in the model dtype T.  Every forward (s2v_transformer_forward*, s2v_denoise_step, _videos, _masked) runs in the
+ * mode that was armed for it:
+ *   S2V_STEP_FULL     the launches the entry runs without a cache, not one more.
+ *   S2V_STEP_CAPTURE  those launches plus two: after the streams are embedded the video rows IN are copied to the cache, and after the last
+ *                     block the cache becomes  delta = rnd_T(float(OUT) - float(IN))  (round to nearest even; a plain subtraction in fp32),
+ *                     OUT being the video rows the tail is about to read.  The residual is valid from then on.
+ *   S2V_STEP_REUSE    time embedding; the modulation GEMV of the norm_out rows only (the last 2 D rows of the stack, the ones the tail
+ *                     reads); patchify; the patch-embed linear of every sample (plus the sincos table where the model has no RoPE) -- text
+ *                     and reference rows are not copied, nothing reads them; X_video = rnd_T(float(IN') + float(delta)); the tail
+ *                     (norm_final, norm_out, proj_out); unpatchify.  The residual and its validity stay as they are.
+ * s2v_step_cache_enable: after s2v_set_geometry; on = 1 allocates the cache for the current geometry (B V D elements), on = 2 additionally a
+ * second buffer of the same size that keeps IN of EVERY forward for s2v_step_cache_read (diagnostics: one more copy launch per forward, FULL
+ * included), on = 0 frees both.  While off, s2v_device_bytes reports what it reports without this feature; while on, the buffers count as
+ * workspace.  A new geometry re-sizes the buffers.  Refused on a shard context.  A change of `on` drops a captured step.
+ * s2v_step_cache_arm: the mode of the NEXT forward only; after it (or after anything that clears the validity) the mode is S2V_STEP_FULL
+ * again, so a forgotten arm costs time, never correctness.  Refused by name: CAPTURE / REUSE on a shard context, without enable, and REUSE
+ * without a valid residual; a s2v_denoise_split_begin that finds CAPTURE / REUSE armed refuses (CFG-parallel has its own forward per rank: the
+ * step cache runs on one GPU).
+ * The validity is cleared by everything that makes the stored residual belong to another computation: s2v_set_geometry, s2v_set_conditioning
+ * / _refs, s2v_load_weight, s2v_merge_lora, s2v_finalize_weights, s2v_mark_weights_loaded, s2v_lora_attach / _set_scale / _detach,
+ * s2v_set_rope, s2v_set_pos_embed, s2v_set_attn_p_format, s2v_set_shard, s2v_step_cache_enable.
+ * A captured step is kept per mode: a plan that alternates captures each kind once. */
+#define S2V_STEP_FULL 0
+#define S2V_STEP_CAPTURE 1
+#define S2V_STEP_REUSE 2
+S2V_API int s2v_step_cache_enable(s2v_ctx* ctx, int32_t on);
+S2V_API int s2v_step_cache_arm(s2v_ctx* ctx, int32_t mode);
+/* enabled: 0 / 1 / 2 as given to s2v_step_cache_enable; valid: a residual is held; bytes: device bytes of the cache buffers */
+S2V_API int s2v_step_cache_state(s2v_ctx* ctx, int32_t* enabled, int32_t* valid, int64_t* bytes);
+/* diagnostics read-out into out_dev [B][V][D] (model dtype): which = 0 IN, the video rows as the last forward embedded them (enable 2 only);
+ * 1 OUT, the video rows of X as the last forward's tail read them; 2 the residual (valid only) */
+S2V_API int s2v_step_cache_read(s2v_ctx* ctx, int32_t which, void* out_dev, s2v_stream stream);
+/* the timestep embedding of n HOST timesteps -> out_dev [n][time_embed_dim] (model dtype), in chunks of at most S2V_MAX_BATCH: row i is exactly
+ * what a step at timesteps_host[i] holds as its embedding (the indicator of the step-cache plan).  Finalized weights only, no geometry;
+ * synchronises the stream */
+S2V_API int s2v_time_embedding(s2v_ctx* ctx, const float* timesteps_host, int32_t n, void* out_dev, s2v_stream stream);
+
 /* Live per-kernel timing for the roofline report (bench.py): HIP events are recorded on the launch stream around
  * every launch of a class; classes 0 qkv GEMM, 1 attention, 2 out-proj GEMM, 3 FF1 GEMM, 4 FF2 GEMM,
  * 5 LN-modulate, 6 qk-norm/rope/V^T, 7 the modulation GEMV, 8 the Ulysses packs, 9 the runtime-LoRA down-projections.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
@@ -560,6 +599,11 @@ S2V_API int s2v_t5_rel_table(s2v_t5* t5, void** dev_ptr);
 S2V_API int s2v_t5_set_position_bias(s2v_t5* t5, const void* bias_dev, int32_t B, int32_t T, s2v_stream stream);
 /* input_ids int64 [B, T] -> last_hidden_state [B, T, d_model] (model dtype) */
 S2V_API int s2v_t5_encode(s2v_t5* t5, const int64_t* input_ids_dev, int32_t B, int32_t T, void* out, s2v_stream stream);
+
+/* the step cache's streaming kernels on their own (tools/step_cache_bench.py): sample b's n contiguous elements at x + b * x_bstride (elements)
+ * against the dense cache [B][n]; op 0: cache = x; 1: cache = rnd(float(x) - float(cache)); 2: x = rnd(float(x) + float(cache)).  n, x_bstride
+ * and the pointers in whole 16-byte vectors */
+S2V_API int s2v_op_step_cache(int32_t op, void* x, int64_t x_bstride, void* cache, int32_t B, int64_t n, int32_t dtype, s2v_stream stream);
 
 /* ---- operator-level entry points (used by the parity tests and micro-benchmarks) ------------------------- */
 /* C[M,N] = A[M,K] . W[N,K]^T + bias, epilogue 0 = bias, 1 = bias + GELU(tanh); impl 0 = MFMA bf16, 1 = generic (VALU),
