@@ -3,10 +3,10 @@ Host side (Python) mirrors the reference's plug-in objects; all arithmetic lives
 from . import _lib, config, tables, weights  # noqa: F401
 from ._lib import S2VError, lib  # noqa: F401
 from .config import TransformerConfig, VAEConfig, cogvideox_2b, cogvideox_5b, tiny  # noqa: F401
-from .engine import S2VEngine, mask_to_latent  # noqa: F401
+from .engine import S2VEngine, map_to_latent, mask_to_latent  # noqa: F401
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler  # noqa: F401
 from .transformer import HipCogVideoXAttnProcessor2_0, HipCogVideoXBlock, HipCogVideoXTransformer3DModel  # noqa: F401
-from .pipeline import S2VPipeline, StepCache, step_cache_plan  # noqa: F401
+from .pipeline import S2VPipeline, StepCache, change_map_plan, step_cache_plan  # noqa: F401
 from .vae import HipAutoencoderKLCogVideoX  # noqa: F401
 from . import dist  # noqa: F401
 from . import checkpoint  # noqa: F401

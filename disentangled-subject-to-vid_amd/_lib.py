@@ -35,11 +35,12 @@ class SchedCoefC(ctypes.Structure):
 
 
 class BlendC(ctypes.Structure):
-    """s2v_blend: the masked step's record per video (add_noise scalars of its next timestep, last-step flag)"""
-    _fields_ = [("sqrt_alpha", ctypes.c_float), ("sqrt_one_minus_alpha", ctypes.c_float), ("last", ctypes.c_int32), ("pad", ctypes.c_int32)]
+    """s2v_blend: the masked step's record per video (add_noise scalars of its next timestep, last-step flag, the level up to which cells
+    are kept: 0 for a 0 / 1 mask)"""
+    _fields_ = [("sqrt_alpha", ctypes.c_float), ("sqrt_one_minus_alpha", ctypes.c_float), ("last", ctypes.c_int32), ("keep_max", ctypes.c_int32)]
 
 
-MASK_DTYPE_U8 = 3   # S2V_MASK_DTYPE_U8: a uint8 pixel mask, non-zero = repaint
+MASK_DTYPE_U8 = 3   # S2V_MASK_DTYPE_U8: a uint8 pixel mask, non-zero = repaint; for s2v_map_to_latent: levels 0..255
 
 
 class S2VError(RuntimeError):
@@ -78,6 +79,7 @@ _SIGS = {
     "s2v_denoise_step": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],
     "s2v_denoise_step_videos": [_P, _P, ctypes.POINTER(_F), ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],
     "s2v_mask_to_latent": [_P, _I32, _I32, _I32, _I32, _P, _P, _P],
+    "s2v_map_to_latent": [_P, _I32, _I32, _I32, _I32, _P, _P, _P],
     "s2v_set_blend": [_P, _P, _P, _P, _I32],
     "s2v_denoise_step_masked": [_P, _P, ctypes.POINTER(_F), ctypes.POINTER(SchedCoefC), ctypes.POINTER(BlendC), _P, _P, _I32, _P],
     "s2v_sched_step_masked": [_P, ctypes.POINTER(SchedCoefC), ctypes.POINTER(BlendC), _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32,

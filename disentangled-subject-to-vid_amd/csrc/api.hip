@@ -160,7 +160,7 @@ struct s2v_ctx {
     float* t_dev = nullptr;
     SchedCoef* coef_dev = nullptr;
     SchedBlend* blend_dev = nullptr;   // the masked step's blend record per video, uploaded beside the coefficient sets
-    // masked video-to-video (s2v_set_blend): the call's clean latents, start noise and latent masks of blend_b videos; held, not copied
+    // masked video-to-video (s2v_set_blend): the call's clean latents, start noise and latent masks (levels) of blend_b videos; held, not copied
     const void *blend_z0 = nullptr, *blend_noise0 = nullptr;
     const unsigned char* blend_mask = nullptr;
     int blend_b = 0;
@@ -1675,7 +1675,7 @@ static void fill_coef(SchedCoef& d, const s2v_sched_coef& s) {
     d.m1 = s.m1; d.m2 = s.m2; d.m3 = s.m3; d.m4 = s.m4; d.mn = s.mn; d.pad = 0.f;
 }
 
-static SchedBlend fill_blend(const s2v_blend& s) { return SchedBlend{s.sqrt_alpha, s.sqrt_one_minus_alpha, s.last != 0, 0}; }
+static SchedBlend fill_blend(const s2v_blend& s) { return SchedBlend{s.sqrt_alpha, s.sqrt_one_minus_alpha, s.last != 0, s.keep_max}; }
 
 extern "C" int s2v_add_noise(const void* sample, const void* noise, int64_t n, float sqrt_alpha, float sqrt_one_minus_alpha, void* out,
                              int32_t dtype, s2v_stream stream) {
@@ -1710,6 +1710,7 @@ extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host
     S2V_REQUIRE(coef_host->kind != 2 || x0_hist, "s2v_sched_step_masked: DPM multistep needs x0_hist");
     S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_sched_step_masked: unsupported dtype");
     S2V_REQUIRE(!(flags & 4), "s2v_sched_step_masked: the blend runs on the latents rounded to `dtype` (flags bit2, fp32 output, is refused)");
+    S2V_REQUIRE(blend_host->keep_max >= 0 && blend_host->keep_max <= 255, "s2v_sched_step_masked: keep_max must be a level 0..255");
     (void)c;
     SchedMaskArgs a{};
     a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
@@ -1725,6 +1726,12 @@ extern "C" int s2v_mask_to_latent(const void* mask, int32_t mask_dtype, int32_t 
                                   s2v_stream stream) {
     S2V_REQUIRE(mask && latent_mask, "s2v_mask_to_latent: null argument");
     return launch_mask_to_latent(mask, mask_dtype, F, H, W, latent_mask, pixel_mask, (hipStream_t)stream);
+}
+
+extern "C" int s2v_map_to_latent(const void* map, int32_t map_dtype, int32_t F, int32_t H, int32_t W, uint8_t* latent_level, uint8_t* pixel_mask,
+                                 s2v_stream stream) {
+    S2V_REQUIRE(map && latent_level, "s2v_map_to_latent: null argument");
+    return launch_map_to_latent(map, map_dtype, F, H, W, latent_level, pixel_mask, (hipStream_t)stream);
 }
 
 // the step's scalars to the device through the next slot of the pinned ring (the uploads are asynchronous: a slot must outlive its copies, RING
@@ -1862,6 +1869,7 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     const int b = c->B / 2;
     S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_masked: s2v_set_blend has not set the blend operands of this geometry's b = B/2 videos");
     for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step_masked: DPM needs noise and x0_hist");
+    for (int k = 0; k < b; ++k) S2V_REQUIRE(blends[k].keep_max >= 0 && blends[k].keep_max <= 255, "s2v_denoise_step_masked: keep_max must be a level 0..255");
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
     if (!use_graph) return sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode));

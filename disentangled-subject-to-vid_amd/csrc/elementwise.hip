@@ -947,7 +947,8 @@ int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void
 // arrive already rounded to the model dtype by the host: torch rounds a 0-dim fp64 scalar to the tensor dtype
 // before the multiply (pinned by tests/golden/sched_*.npz).  __f*_rn keep the reference's separate roundings
 // (no fma contraction), so the fp32 arithmetic is bit-identical to the CPU reference.
-// A = SchedArgs: the step.  A = SchedMaskArgs: the step, then the masked video-to-video select on its rounded result (kernels.h); the
+// A = SchedArgs: the step.  A = SchedMaskArgs: the step, then the masked video-to-video select on its rounded result (kernels.h): a cell is
+// kept iff its level is <= the record's keep_max (a 0 / 1 mask: keep_max = 0; a change map: the video's threshold of this step).  The
 // SchedArgs instantiation is the kernel it was before the masked form existed, kernel arguments included.
 template <typename T, typename A>
 __global__ void sched_step_k(const A a) {
@@ -987,8 +988,10 @@ __global__ void sched_step_k(const A a) {
         const unsigned ju = (unsigned)j, chw = (unsigned)a.chw, hw = (unsigned)a.hw;
         const int64_t cell = (int64_t)blockIdx.y * a.mask_vid + (ju / chw) * hw + ju % hw;
         T* out = (T*)a.latents_out + i;
-        if (a.mask[cell]) { ET<T>::st(out, prev); return; }
+        // the plane holds levels 0..255 as unsigned bytes; the record is the workgroup's own (uniform), loaded before the branch.  A 0 / 1 mask
+        // with keep_max = 0 is the test `mask != 0`
         const SchedBlend bl = a.blend ? a.blend[blockIdx.y] : a.bval;
+        if ((int)a.mask[cell] > bl.keep_max) { ET<T>::st(out, prev); return; }
         const T* z0 = (const T*)a.z0 + i;
         if (bl.last) { *out = *z0; return; }   // the bits of z0, -0 included
         const float s = ET<T>::rnd(__fmul_rn(bl.sqrt_a, ET<T>::ld(z0)));                       // add_noise_k's arithmetic
@@ -1015,8 +1018,7 @@ int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st) 
     S2V_TRY(sched_step_checks(a));
     S2V_REQUIRE(a.z0 && a.noise0 && a.mask, "sched_step_masked: z0, noise0 and the latent mask are required");
     S2V_REQUIRE(a.blend || a.nvid == 1, "sched_step_masked: several videos take their blend records from device memory");
-    S2V_REQUIRE(!a.out_f32, "sched_step_masked: the blend runs on the latents rounded to the model dtype (no fp32 output)");
-    S2V_REQUIRE(a.hw >= 1 && a.chw >= a.hw && a.chw % a.hw == 0 && a.n_vid % a.chw == 0,
+    S2V_REQUIRE(!a.out_f32, "sched_step_masked: the blend runs on the latents rounded to the model dtype (no fp32 output)");    S2V_REQUIRE(a.hw >= 1 && a.chw >= a.hw && a.chw % a.hw == 0 && a.n_vid % a.chw == 0,
                 "sched_step_masked: a video is [F][C][H * W] elements over a mask plane of [F][H * W] cells");
     S2V_REQUIRE(a.n_vid < ((int64_t)1 << 31) && a.mask_vid == a.n_vid / a.chw * a.hw, "sched_step_masked: a video of fewer than 2^31 elements, mask_vid = F * H * W cells");
     dim3 grid((unsigned)((a.n_vid + 255) / 256), (unsigned)a.nvid);
@@ -1029,12 +1031,12 @@ int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st) 
 // The pixel mask of masked video-to-video -> the latent mask (kernels.h).  One thread per latent cell: its 8 x 8 pixels of 1 or 4 frames,
 // a row of 8 mask values per load; with pixel_out the binarised rows are written on the way (8 bytes per store).
 template <typename M> struct MaskRow;   // the 8 mask values at p, binarised: byte k of the result is 0 or 1
+// byte != 0 -> 1: the high bit of (b & 0x7f) + 0x7f is set when the low seven bits are non-zero, b's own high bit covers the rest
+__device__ __forceinline__ unsigned long long nonzero_bytes(unsigned long long v) {
+    return ((((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) >> 7) & 0x0101010101010101ull;
+}
 template <> struct MaskRow<unsigned char> {
-    static __device__ __forceinline__ unsigned long long ld(const unsigned char* p) {
-        const unsigned long long v = *(const unsigned long long*)p;
-        // byte != 0 -> 1: the high bit of (b & 0x7f) + 0x7f is set when the low seven bits are non-zero, b's own high bit covers the rest
-        return ((((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) >> 7) & 0x0101010101010101ull;
-    }
+    static __device__ __forceinline__ unsigned long long ld(const unsigned char* p) { return nonzero_bytes(*(const unsigned long long*)p); }
 };
 template <> struct MaskRow<float> {
     static __device__ __forceinline__ unsigned long long ld(const float* p) {
@@ -1086,6 +1088,75 @@ int launch_mask_to_latent(const void* mask, int mdtype, int F, int H, int W, uns
         hipLaunchKernelGGL(mask_to_latent_k<unsigned char>, grid, dim3(256), 0, st, (const unsigned char*)mask, F, H, W, latent_out, pixel_out);
     } else {
         S2V_DT_DISPATCH(mdtype, hipLaunchKernelGGL(mask_to_latent_k<T>, grid, dim3(256), 0, st, (const T*)mask, F, H, W, latent_out, pixel_out))
+    }
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The change map of video-to-video -> the latent levels (kernels.h).  mask_to_latent_k's walk -- one thread per latent cell, its 8 x 8 pixels
+// of 1 or 4 frames, a row of 8 map values per load -- with every value quantised to a level 0..255 and the running MAXIMUM in place of "any";
+// with pixel_out the rows of `level > 0` are written on the way (8 bytes per store).
+// float maps: level = floor(clamp(v, 0, 1) * 255 + 0.5) in fp32, the multiply and the add rounded separately; NaN -> 0 (no compare holds)
+__device__ __forceinline__ unsigned long long quantise_row(const float* v) {
+#pragma clang fp contract(off)  // hipcc defaults to -ffp-contract=fast
+    unsigned long long r = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float c = v[k] > 0.f ? (v[k] < 1.f ? v[k] : 1.f) : 0.f;
+        r |= (unsigned long long)(unsigned)__fadd_rn(__fmul_rn(c, 255.f), 0.5f) << (8 * k);   // 0.5 <= the sum <= 255.5: truncation is floor
+    }
+    return r;
+}
+template <typename M> struct MapRow;   // the 8 map values at p as levels: byte k of the result is 0..255
+template <> struct MapRow<unsigned char> {
+    static __device__ __forceinline__ unsigned long long ld(const unsigned char* p) { return *(const unsigned long long*)p; }
+};
+template <> struct MapRow<float> {
+    static __device__ __forceinline__ unsigned long long ld(const float* p) {
+        float v[8];
+        Vec16<float>::ld(p, v);
+        Vec16<float>::ld(p + 4, v + 4);
+        return quantise_row(v);
+    }
+};
+template <typename M> struct MapRow {   // bf16_t / f16_t: eight values in one 16-byte load
+    static __device__ __forceinline__ unsigned long long ld(const M* p) {
+        float v[8];
+        Vec16<M>::ld(p, v);
+        return quantise_row(v);
+    }
+};
+template <typename M>
+__global__ void map_to_latent_k(const M* map, int F, int H, int W, unsigned char* lat, unsigned char* pix) {
+    const int h = H / 8, w = W / 8, Fl = (F - 1) / 4 + 1;
+    const int64_t total = (int64_t)Fl * h * w;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % w), y = (int)((i / w) % h), fl = (int)(i / ((int64_t)w * h));
+        const int f0 = fl == 0 ? 0 : 4 * fl - 3, f1 = fl == 0 ? 0 : 4 * fl;   // pixel frames f0 .. f1 (F = 4 (Fl - 1) + 1: all inside)
+        unsigned level = 0;
+        for (int f = f0; f <= f1; ++f)
+            for (int r = 0; r < 8; ++r) {
+                const int64_t p = ((int64_t)f * H + 8 * y + r) * W + 8 * x;
+                const unsigned long long row = MapRow<M>::ld(map + p);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) level = max(level, (unsigned)(row >> (8 * k)) & 0xffu);
+                if (pix) *(unsigned long long*)(pix + p) = nonzero_bytes(row);
+            }
+        lat[i] = (unsigned char)level;
+    }
+}
+int launch_map_to_latent(const void* map, int mdtype, int F, int H, int W, unsigned char* level_out, unsigned char* pixel_out, hipStream_t st) {
+    S2V_REQUIRE(map && level_out, "map_to_latent: null argument");
+    S2V_REQUIRE(F >= 1 && (F - 1) % 4 == 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0,
+                "map_to_latent: F = 4k + 1 frames of H x W pixels, both multiples of 8");
+    S2V_REQUIRE(mdtype == S2V_F32 || mdtype == S2V_BF16 || mdtype == S2V_F16 || mdtype == S2V_MASK_U8, "map_to_latent: unknown map dtype");
+    const int64_t total = (int64_t)((F - 1) / 4 + 1) * (H / 8) * (W / 8);
+    const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 16));
+    if (mdtype == S2V_MASK_U8) {
+        hipLaunchKernelGGL(map_to_latent_k<unsigned char>, grid, dim3(256), 0, st, (const unsigned char*)map, F, H, W, level_out, pixel_out);
+    } else {
+        S2V_DT_DISPATCH(mdtype, hipLaunchKernelGGL(map_to_latent_k<T>, grid, dim3(256), 0, st, (const T*)map, F, H, W, level_out, pixel_out))
     }
     S2V_CHECK_HIP(hipGetLastError());
     return 0;

@@ -370,15 +370,19 @@ int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st);
 // `prev` rounded to T, an element whose latent cell has mask 0 is overwritten -- with add_noise(z0, noise0) at the video's NEXT timestep
 // (add_noise_k's arithmetic: rnd(rnd(sqrt_a * z0) + rnd(sqrt_1ma * noise0))), or on the video's last step with z0's own bits.  x0_hist
 // keeps the unblended x0.  The records sit beside the coefficient sets in device memory, so the captured graph serves every step.
+// The plane holds LEVELS 0..255 (unsigned bytes) and a cell is kept iff level <= keep_max, the video's threshold of this step: a 0 / 1 mask is
+// the case keep_max = 0, and a change map (differential diffusion: pipeline_stable_diffusion_xl_differential_img2img.py:1316-1347, whose
+// `map` is 1 - level / 255) lowers keep_max step by step, so a cell of level L is released at the step its level asks for.  Every step is
+// still a select: no latent is ever multiplied by the map.
 struct SchedBlend {
     float sqrt_a, sqrt_1ma;   // Scheduler.add_noise_scalars(t_next, T): already taken in T by the host
     int last;                 // the video's last step: kept elements are z0, bit for bit (coefficients (1, 0) would turn -0 into +0)
-    int pad;
+    int keep_max;             // 0..255: cells whose level is <= keep_max are kept
 };
 struct SchedMaskArgs : SchedArgs {     // latents_out is T (out_f32 is refused)
     const void* z0;            // [n] model dtype: the clean input latents, scaled
     const void* noise0;        // [n] model dtype: the noise that started the loop
-    const unsigned char* mask; // [nvid][F * hw]: 1 repaint, 0 keep; one plane for all channels of a video [F][C][hw]
+    const unsigned char* mask; // [nvid][F * hw]: levels, kept where <= keep_max (a mask: 1 repaint, 0 keep); one plane for all channels of a video [F][C][hw]
     int chw, hw;               // C * H * W and H * W of the latent: element j of a video is frame j / chw, cell j % hw of the plane
     int mask_vid;              // F * H * W: the cells of one video's plane
     const SchedBlend* blend;   // device pointer to nvid consecutive records, or null => use bval (nvid = 1)
@@ -390,6 +394,10 @@ int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st);
 // the causal grouping of the VAE encode; Fl = (F - 1) / 4 + 1.  pixel_out (may be null): the binarised pixel mask, uint8 [F][H][W]
 #define S2V_MASK_U8 3
 int launch_mask_to_latent(const void* mask, int mdtype, int F, int H, int W, unsigned char* latent_out, unsigned char* pixel_out, hipStream_t st);
+// change map [F][H][W] -> latent levels uint8 [Fl][H/8][W/8]: every value becomes a level 0..255 (S2V_MASK_U8: the byte itself; S2V_F32 / S2V_BF16 /
+// S2V_F16: floor(clamp(v, 0, 1) * 255 + 0.5) in fp32, one multiply and one add, no fma; NaN -> 0) and a cell takes the MAXIMUM level of the block
+// launch_mask_to_latent reduces with "any".  pixel_out (may be null): level > 0 as uint8 0 / 1 [F][H][W], what the masked post-processes take
+int launch_map_to_latent(const void* map, int mdtype, int F, int H, int W, unsigned char* level_out, unsigned char* pixel_out, hipStream_t st);
 int launch_add_noise(const void* x, const void* noise, int64_t n, float sqrt_a, float sqrt_1ma, void* out, int dtype, hipStream_t st);
 // dst[i] = (Tdst) src[i]
 int launch_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t st);

@@ -53,6 +53,27 @@ def mask_to_latent(mask, device=None):
     return lat, pix
 
 
+def map_to_latent(change_map, device=None):
+    """change maps [r,F,H,W] (uint8: levels 0..255; float32 / bfloat16 / float16: values in [0, 1], level = floor(clamp(v, 0, 1) * 255 + 0.5),
+    NaN -> 0; anything else goes through float32) -> (latent levels uint8 [r,(F-1)/4+1,H/8,W/8], pixel mask `level > 0` uint8 [r,F,H,W]), one
+    s2v_map_to_latent launch per row: a latent cell takes the MAXIMUM level of the pixels it covers (include/s2v_hip.h)"""
+    if change_map.ndim != 4:
+        raise _lib.S2VError(f"map_to_latent: the maps must be [rows, F, H, W], got {tuple(change_map.shape)}")
+    r, F, H, W = change_map.shape
+    if (F - 1) % 4 or H % 8 or W % 8 or min(r, H, W) < 1:
+        raise _lib.S2VError(f"map_to_latent: F = 4k + 1 frames of H x W pixels, both multiples of 8, got {tuple(change_map.shape)}")
+    m = change_map.to(device or change_map.device)
+    if m.dtype != torch.uint8 and m.dtype not in _lib.DTYPE_OF:
+        m = m.float()
+    m = m.contiguous()
+    md = _lib.MASK_DTYPE_U8 if m.dtype == torch.uint8 else _lib.DTYPE_OF[m.dtype]
+    lat = torch.empty((r, (F - 1) // 4 + 1, H // 8, W // 8), dtype=torch.uint8, device=m.device)
+    pix = torch.empty((r, F, H, W), dtype=torch.uint8, device=m.device)
+    for k in range(r):
+        _lib.check(_lib.lib().s2v_map_to_latent(_lib.ptr(m[k]), md, F, H, W, _lib.ptr(lat[k]), _lib.ptr(pix[k]), _lib.stream_ptr()))
+    return lat, pix
+
+
 class S2VEngine:
     def __init__(self, cfg: TransformerConfig, dtype=torch.bfloat16, device="cuda:0", force_simple=False, kind=_lib.CTX_MODEL):
         """kind: _lib.CTX_MODEL (a whole model), or one of the two halves of the model-wide AttnProcessor (include/s2v_hip.h, S2V_CTX_*):
@@ -515,7 +536,7 @@ class S2VEngine:
 
     def set_blend(self, z0, noise0, latent_mask):
         """the blend operands of a masked call for the b = B/2 videos of the geometry: z0 and noise0 [b,F,C,H,W] in the model dtype, latent_mask
-        uint8 [b,F,H,W] (mask_to_latent); the tensors are held until clear_blend or the next set_blend.  Drops a captured step"""
+        uint8 [b,F,H,W] (mask_to_latent's 0 / 1, or map_to_latent's levels: a cell is kept where it is <= the record's keep_max); the tensors are held until clear_blend or the next set_blend.  Drops a captured step"""
         B, T, F, H, W = self.geometry
         b = B // 2
         want = (b, F, self.cfg.in_channels, H, W)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .engine import mask_to_latent
+from .engine import map_to_latent, mask_to_latent
 from .schedulers import CogVideoXDPMScheduler, randn_videos  # noqa: F401
 
 
@@ -68,6 +68,18 @@ def step_cache_plan(emb, threshold, coefficients=(1.0, 0.0), keep_first=1, keep_
             acc = 0.0
         plan.append(bool(full))
     return plan
+
+
+def change_map_plan(n):
+    """the keep thresholds of a change-map call whose plan runs n steps (the number actually run, after `strength`): after step j (0-based) a
+    latent cell of level L (0..255, 255 = repaint from the first step) is kept iff L <= plan[j], with
+        plan[j] = max(0, (255 * (n - j - 1) - 1) // n)
+    For j < n - 1 that is exactly L * n < 255 * (n - j - 1): the reference's `map > (j + 1) / n` with map = 1 - L / 255
+    (pipeline_stable_diffusion_xl_differential_img2img.py:1316-1347) in integers.  The last entry is 0: only level-0 cells are kept there, as
+    the clean input latents, which is what `mask=` does (the reference keeps nothing after its last step).  Host integers only"""
+    if n < 1:
+        raise ValueError(f"change_map_plan: a plan of n >= 1 steps, got {n}")
+    return [max(0, (255 * (n - j - 1) - 1) // n) for j in range(n)]
 
 
 class S2VPipeline:
@@ -216,23 +228,23 @@ class S2VPipeline:
         return timesteps[t_start * order:], num_inference_steps - t_start
 
     @staticmethod
-    def check_mask(mask, video, b, cfg_parallel=None, ulysses=None):
+    def check_mask(mask, video, b, cfg_parallel=None, ulysses=None, what="mask"):
         """the pixel masks of a masked video-to-video call as [1 | b, F, H, W] (one row: shared by all b videos), after every refusal (no
         device is touched): a mask without a video, on the paths that stay unmasked, of another size than the video, with a row count that
-        is neither 1 nor b"""
+        is neither 1 nor b.  what="change_map": the same checks for a change map, named as such"""
         if video is None:
-            raise ValueError("`mask` applies only together with `video`: masked video-to-video keeps the input video outside the mask "
-                             "(a mask on a text-to-video call has nothing to keep)")
+            raise ValueError(f"`{what}` applies only together with `video`: masked video-to-video keeps the input video outside the mask "
+                             f"(a {what} on a text-to-video call has nothing to keep)")
         for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
             if arg is not None:
-                raise ValueError(f"`mask` together with `{name}`: the masked step runs on one GPU; CFG-parallel and Ulysses stay unmasked")
+                raise ValueError(f"`{what}` together with `{name}`: the masked step runs on one GPU; CFG-parallel and Ulysses stay unmasked")
         m = mask[:, 0] if mask.ndim == 5 and mask.shape[1] == 1 else mask
         F, H, W = video.shape[2:]
         if m.ndim != 4 or tuple(m.shape[1:]) != (F, H, W):
-            raise ValueError(f"`mask` must be [rows, 1, F, H, W] or [rows, F, H, W] with the video's F x H x W = {F} x {H} x {W} (one value per "
+            raise ValueError(f"`{what}` must be [rows, 1, F, H, W] or [rows, F, H, W] with the video's F x H x W = {F} x {H} x {W} (one value per "
                              f"frame and pixel), got {tuple(mask.shape)}")
         if m.shape[0] not in (1, b):
-            raise ValueError(f"`mask` has {m.shape[0]} rows for b = {b} videos: one mask per video, or one row shared by all")
+            raise ValueError(f"`{what}` has {m.shape[0]} rows for b = {b} videos: one {what} per video, or one row shared by all")
         return m
 
     @staticmethod
@@ -266,11 +278,13 @@ class S2VPipeline:
     step_cache_report = None
 
     @staticmethod
-    def blend_plan(scheduler, plan, dtype, device="cpu"):
+    def blend_plan(scheduler, plan, dtype, device="cpu", keep_max=None):
         """the masked step's record (scheduler.blend_record) for every step of a video_plan: step i blends at the video's NEXT timestep
-        t[i + 1], the last step is flagged and keeps the clean latents"""
+        t[i + 1], the last step is flagged and keeps the clean latents.  keep_max: the level up to which step i keeps a cell, one per step
+        (a change map: change_map_plan(len(timesteps))); None: 0 on every step, a 0 / 1 mask"""
         ts = plan["timesteps"]
-        return [scheduler.blend_record(ts[i + 1] if i + 1 < len(ts) else None, dtype, device) for i in range(len(ts))]
+        km = [0] * len(ts) if keep_max is None else keep_max
+        return [scheduler.blend_record(ts[i + 1] if i + 1 < len(ts) else None, dtype, device, km[i]) for i in range(len(ts))]
 
     @staticmethod
     def _blend_torch(scheduler, latents, z0, noise0, keep, next_timestep):
@@ -299,7 +313,7 @@ class S2VPipeline:
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
-                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None):
+                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -325,6 +339,13 @@ class S2VPipeline:
         started the loop, and after the last step the clean ones (pipeline_stable_diffusion_inpaint.py:1271-1285); a step-end callback sees
         the blended latents.  paste_back (frames only): where the PIXEL mask is 0 the frames are the post-processed input video, exactly.
         Only with `video`; not with cfg_parallel= or ulysses=.
+        change_map: a strength per pixel (differential diffusion, pipeline_stable_diffusion_xl_differential_img2img.py:1316-1347, whose `map` is
+        1 - level / 255) -- the shapes and rows of `mask`; uint8 levels 0..255, or floats in [0, 1] quantised to level = floor(v * 255 + 0.5):
+        255 repaints from the first step, 0 keeps the input.  A latent cell takes the largest level of the pixels it covers.  The map never
+        multiplies a latent: a cell of level L is overwritten like a kept cell of `mask` after step j while L <= change_map_plan(n)[j] (n: the
+        steps this video actually runs, after `strength`) and runs free afterwards, so it sees roughly L / 255 of the video's strength; level 0
+        ends as the clean input latents.  A map of 0 and 255 alone is `mask` with the same cells.  paste_back: pixels whose OWN level is 0 are
+        the input video's.  Only with `video`; not with `mask`, cfg_parallel= or ulysses=.
         step_cache: skip the block stack on steps whose timestep embedding barely moved since the last full step -- a threshold (float), a
         StepCache(threshold, coefficients, keep_first, keep_last), or a list of booleans, one per step actually run (True = full).  The plan
         (step_cache_plan) comes from the call's own timesteps before the loop; a full step that a reuse follows stores the block stack's
@@ -333,8 +354,14 @@ class S2VPipeline:
         `prompt_embeds`).  After the call `step_cache_report` holds {"plan", "full", "reused", "ran_full"}.  Scalars only (b > 1 videos share
         the timesteps); refused with per-video lists, several input videos, cfg_parallel=, ulysses= and fused=False."""
         self.step_cache_report = None
+        if change_map is not None and mask is not None:
+            raise ValueError("`change_map` together with `mask`: both say which cells are kept; a change map of 0 and 255 alone is that mask")
+        levels = change_map is not None   # from here on `mask` is the call's plane, read as levels 0..255 when `levels`
+        what = "change_map" if levels else "mask"
+        if levels:
+            mask = change_map
         if mask is not None and video is None:
-            self.check_mask(mask, None, 1)
+            self.check_mask(mask, None, 1, what=what)
         per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength))
         if not isinstance(strength, (list, tuple)) and (strength < 0 or strength > 1):
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
@@ -372,14 +399,14 @@ class S2VPipeline:
             raise RuntimeError("guidance_scale must be > 1: eval=True duplicates the reference tokens for the CFG pair")
         b = self.check_batch(prompt_embeds, num_videos_per_prompt, ref_img_states, latents, generator, video, cfg_parallel, ulysses)
         if mask is not None:
-            mask = self.check_mask(mask, video, b, cfg_parallel, ulysses)
+            mask = self.check_mask(mask, video, b, cfg_parallel, ulysses, what)
         if step_cache is not None:
             step_cache = self.check_step_cache(step_cache, per_video, cfg_parallel, ulysses, fused, video is not None and b > 1)
         if per_video or (video is not None and b > 1):   # every video on its own plan; scalars and one input video stay on the path below
             lists = self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)
             return self._call_videos(b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg,
                                      generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
-                                     callback_on_step_end_tensor_inputs, video, num_videos_per_prompt, mask, paste_back)
+                                     callback_on_step_end_tensor_inputs, video, num_videos_per_prompt, mask, paste_back, levels)
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)  # [negative x b | positive x b] (:196)
@@ -408,9 +435,9 @@ class S2VPipeline:
             ref_rope, rope = (cos[:n], sin[:n]), (cos[n:], sin[n:])
         paste = None
         if mask is not None:   # one video (several go through _call_videos): its blend operands, held for the whole call
-            lat_mask, pix_mask = mask_to_latent(mask, dev)
+            lat_mask, pix_mask = (map_to_latent if levels else mask_to_latent)(mask, dev)
             z0, noise0 = z0.to(dt).contiguous(), noise0.to(dt).contiguous()
-            keep = (lat_mask == 0)[:, :, None]   # [1,Fl,1,h,w]: fused=False's select
+            keep_max = change_map_plan(len(timesteps)) if levels else [0] * len(timesteps)   # step i keeps the cells of level <= keep_max[i]
             nexts = [timesteps[i + 1] if i + 1 < len(timesteps) else None for i in range(len(timesteps))]
             paste = (video, pix_mask) if paste_back else None
 
@@ -476,7 +503,7 @@ class S2VPipeline:
                                 rep["ran_full"].append(i)
                             rep["reused" if cache == "reuse" else "full"] += 1
                         eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph,
-                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev), cache=cache)
+                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev, keep_max[i]), cache=cache)
                     else:
                         cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
                 else:
@@ -494,6 +521,7 @@ class S2VPipeline:
                                                 generator=generator, return_dict=False)
                     latents = latents.to(dt)
                     if mask is not None:
+                        keep = (lat_mask <= keep_max[i])[:, :, None]   # [1,Fl,1,h,w]: fused=False's select
                         latents = self._blend_torch(sch, latents, z0, noise0, keep, nexts[i])
                 if callback_on_step_end is not None:
                     # custom_cogvideox_pipe.py:298-305: the callback sees the requested tensors -- `prompt_embeds` is, at that point of
@@ -573,13 +601,14 @@ class S2VPipeline:
 
     def _call_videos(self, b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg, generator,
                      latents, output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, video,
-                     num_videos_per_prompt, mask=None, paste_back=True):
+                     num_videos_per_prompt, mask=None, paste_back=True, levels=False):
         """b videos, each on the plan of its one-video call (video_plan): iteration i applies step i of every video that still has one.  The
         videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers; when
         the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
         latents stay where they are.  Results, and everything the callback sees, are in the caller's order.
         mask [1 | b,F,H,W] (check_mask): z0, noise0 and the latent masks follow the internal order and the shrinking prefix exactly as the latents
-        do; video k blends at the next timestep of its own plan and is flagged on its own last step"""
+        do; video k blends at the next timestep of its own plan and is flagged on its own last step.  levels: the mask is a change map, and
+        video k keeps the cells of level <= change_map_plan(n_k)[i] after its step i, n_k the steps of its own plan"""
         tr, sch = self.transformer, self.scheduler
         dt, dev = tr.dtype, tr.device
         guidance, counts, strengths = lists
@@ -600,13 +629,13 @@ class S2VPipeline:
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
         paste = None
         if mask is not None:
-            lat_mask, pix_mask = mask_to_latent(mask, dev)
+            lat_mask, pix_mask = (map_to_latent if levels else mask_to_latent)(mask, dev)
             paste = (video, pix_mask) if paste_back else None
             if lat_mask.shape[0] != b:
                 lat_mask = lat_mask.expand(b, -1, -1, -1)
             z0, noise0, lat_mask = z0.to(dt)[order].contiguous(), noise0.to(dt)[order].contiguous(), lat_mask[order].contiguous()
-            keep = (lat_mask == 0)[:, :, None]   # [b,Fl,1,h,w]: fused=False's select
-            blends = [self.blend_plan(sch, plans[k], dt, dev) for k in order]
+            keep_max = [change_map_plan(len(plans[k]["timesteps"])) if levels else [0] * len(plans[k]["timesteps"]) for k in order]
+            blends = [self.blend_plan(sch, plans[k], dt, dev, keep_max[p]) for p, k in enumerate(order)]
         ref = ref_img_states.to(dev, dt)
         if ref.shape[0] > 1:
             ref = ref[order].contiguous()
@@ -691,7 +720,8 @@ class S2VPipeline:
                         new = new.to(dt)
                         if mask is not None:
                             ts_p = plans[order[p]]["timesteps"]
-                            new = self._blend_torch(sch, new, z0[p:p + 1], noise0[p:p + 1], keep[p:p + 1], ts_p[i + 1] if i + 1 < len(ts_p) else None)
+                            keep = (lat_mask[p:p + 1] <= keep_max[p][i])[:, :, None]   # [1,Fl,1,h,w]: fused=False's select
+                            new = self._blend_torch(sch, new, z0[p:p + 1], noise0[p:p + 1], keep, ts_p[i + 1] if i + 1 < len(ts_p) else None)
                         latents[p:p + 1] = new
                 if callback_on_step_end is not None:
                     # the contract of the scalar path over all b videos in the caller's order; `t` is the 0-dim timestep while the active videos

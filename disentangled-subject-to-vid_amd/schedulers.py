@@ -86,13 +86,14 @@ class _SchedulerBase:
         a = torch.as_tensor(self.alphas_cumprod[int(timestep)], dtype=torch.float64).to(device).to(dtype)
         return float(a**0.5), float((1 - a) ** 0.5)
 
-    def blend_record(self, next_timestep, dtype, device="cpu"):
+    def blend_record(self, next_timestep, dtype, device="cpu", keep_max=0):
         """the masked step's record (_lib.BlendC) of a video whose NEXT timestep is next_timestep: add_noise's scalars there; None: this is
-        the video's last step (the kept elements become the clean latents, the scalars are not read)"""
+        the video's last step (the kept elements become the clean latents, the scalars are not read).  keep_max: cells whose level is
+        <= keep_max are kept (0: a 0 / 1 mask; a change map passes pipeline.change_map_plan(n)[step])"""
         if next_timestep is None:
-            return _lib.BlendC(1.0, 0.0, 1, 0)
+            return _lib.BlendC(1.0, 0.0, 1, keep_max)
         sa, sb = self.add_noise_scalars(int(next_timestep), dtype, device)
-        return _lib.BlendC(sa, sb, 0, 0)
+        return _lib.BlendC(sa, sb, 0, keep_max)
 
     def add_noise(self, original_samples, noise, timesteps):
         """scheduler.add_noise (scheduling_ddim_cogvideox.py:405-431; scheduling_dpm_cogvideox.py:442) in the HIP kernel of s2v_add_noise:

@@ -45,7 +45,7 @@ def prompt_embeddings(text_encoder, input_ids, dtype=None):
 
 def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_ids, height=480, width=720, num_frames=49,
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
-              video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, **pipe_kwargs):
+              video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, change_map_uint8=None, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
     `output_type` selects ("latent" / "pt").  A batch of prompt ids [P, T] (with num_videos_per_prompt through **pipe_kwargs: up to four
     videos per call) shares the one reference image and returns one video per row, [b, F, H, W, 3].
@@ -72,7 +72,11 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
 
     Masked video-to-video: mask_uint8 [F, H, W] (one mask shared by all videos) or [b, F, H, W] over the input video's frames and pixels,
     >= 128 repaints, below keeps the input video (S2VPipeline.__call__'s `mask`); paste_back returns the input video's own pixels outside
-    the mask."""
+    the mask.
+
+    Change map: change_map_uint8 [F, H, W] or [b, F, H, W], levels 0..255 over the input video's frames and pixels -- a strength per pixel
+    (S2VPipeline.__call__'s `change_map`): 255 repaints from the first step, 0 keeps the input video, a level in between is released
+    part-way through the steps.  Not together with mask_uint8."""
     if video_uint8 is not None:
         vs = np.asarray(video_uint8).shape[-4:]
         if np.asarray(video_uint8).ndim not in (4, 5) or vs[3] != 3:
@@ -89,6 +93,18 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
             raise ValueError(f"mask_uint8 is {m.shape[-3:]} (frames, height, width) but the video is {tuple(vs[:3])}")
         mask = torch.from_numpy(np.ascontiguousarray(m >= 128).view(np.uint8))
         pipe_kwargs = dict(pipe_kwargs, mask=mask[None] if mask.ndim == 3 else mask, paste_back=paste_back)
+    if change_map_uint8 is not None:
+        m = np.asarray(change_map_uint8)
+        if m.dtype != np.uint8 or m.ndim not in (3, 4):
+            raise ValueError("change_map_uint8 must be uint8 [F, H, W] or [b, F, H, W] (levels 0..255)")
+        if mask_uint8 is not None:
+            raise ValueError("change_map_uint8 together with mask_uint8: both say which pixels are kept")
+        if video_uint8 is None:
+            raise ValueError("change_map_uint8 applies only together with video_uint8")
+        if tuple(m.shape[-3:]) != tuple(vs[:3]):
+            raise ValueError(f"change_map_uint8 is {m.shape[-3:]} (frames, height, width) but the video is {tuple(vs[:3])}")
+        cmap = torch.from_numpy(np.ascontiguousarray(m))
+        pipe_kwargs = dict(pipe_kwargs, change_map=cmap[None] if cmap.ndim == 3 else cmap, paste_back=paste_back)
     dev = pipe.transformer.device
     generator = None
     if seed is not None:

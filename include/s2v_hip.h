@@ -290,13 +290,22 @@ S2V_API int s2v_denoise_step_videos(s2v_ctx* ctx, void* latents, const float* ti
  *   m = 1:             the step's result
  *   m = 0, not last:   rnd_T(rnd_T(sqrt_alpha * z0) + rnd_T(sqrt_one_minus_alpha * noise0))      (s2v_add_noise's arithmetic, no fma)
  *   m = 0, last:       z0, bit for bit (a flag, not the coefficients (1, 0), which would turn -0 into +0)
- * x0_hist keeps the unblended x0: the scheduler's state is left alone, as in the reference. */
+ * x0_hist keeps the unblended x0: the scheduler's state is left alone, as in the reference.
+ * Change map (differential diffusion, e.g. pipeline_stable_diffusion_xl_differential_img2img.py:1316-1347): the plane holds LEVELS 0..255
+ * (unsigned bytes; 255 = repaint from the first step, 0 = keep the input -- the reference's `map` is 1 - level / 255) and the test is
+ *   kept  <=>  level <= keep_max
+ * with keep_max the video's threshold of this step.  A 0 / 1 mask is the case keep_max = 0.  For a video whose plan runs n steps the pipeline
+ * passes, after step j (0-based), keep_max_j = max(0, (255 (n - j - 1) - 1) / n) (integer division): for j < n - 1 exactly
+ * level * n < 255 (n - j - 1), the reference's map > (j + 1) / n in integers; 0 on the last step, where only level-0 cells are kept, as the
+ * clean z0.  The map never multiplies a latent: every step is still the select above.  Two deliberate differences from the reference's loop:
+ * it keeps nothing after its last step (here level 0 stays the input, as a mask's 0 does), and with strength < 1 it divides by the full
+ * schedule without offsetting the step index (here n and j count the steps actually run). */
 typedef struct s2v_blend {
     float sqrt_alpha, sqrt_one_minus_alpha;   /* of the video's NEXT timestep, taken in T by the host as for s2v_add_noise */
     int32_t last;                             /* != 0: this is the video's last step */
-    int32_t pad;
+    int32_t keep_max;                         /* 0..255: cells whose level is <= keep_max are kept; 0 for a 0 / 1 mask */
 } s2v_blend;
-#define S2V_MASK_DTYPE_U8 3   /* s2v_mask_to_latent: a uint8 mask, non-zero = repaint (beside S2V_DTYPE_*: binarised at 0.5) */
+#define S2V_MASK_DTYPE_U8 3   /* s2v_mask_to_latent: a uint8 mask, non-zero = repaint (beside S2V_DTYPE_*: binarised at 0.5); s2v_map_to_latent: levels */
 /* The pixel mask of one video [F,H,W] (F = 4k + 1; H, W multiples of 8; mask_dtype S2V_DTYPE_* -- value < 0.5 -> 0, >= 0.5 -> 1 as
  * image_processor.py:535-536 binarises -- or S2V_MASK_DTYPE_U8) -> latent_mask uint8 [(F-1)/4+1, H/8, W/8], one plane for all latent channels:
  * a cell is 1 (repaint) if ANY pixel it covers is 1 -- its 8 x 8 block of pixel frame 0 for latent frame 0, of pixel frames 4j-3 .. 4j for latent
@@ -305,19 +314,28 @@ typedef struct s2v_blend {
  * binarised pixel mask uint8 [F,H,W] (what the masked post-processes take).  One launch. */
 S2V_API int s2v_mask_to_latent(const void* mask, int32_t mask_dtype, int32_t F, int32_t H, int32_t W, uint8_t* latent_mask, uint8_t* pixel_mask,
                                s2v_stream stream);
+/* The change map of one video [F,H,W] (same sizes as s2v_mask_to_latent) -> latent_level uint8 [(F-1)/4+1, H/8, W/8].  Every value becomes a
+ * level 0..255: map_dtype S2V_MASK_DTYPE_U8 means LEVELS here, the byte itself (not "non-zero"); S2V_DTYPE_F32 / _BF16 / _F16 are values in
+ * [0, 1] quantised as level = floor(clamp(v, 0, 1) * 255 + 0.5) in fp32, one multiply and one add, no fma; NaN gives 0.  A cell takes the
+ * MAXIMUM level over the pixels it covers, the block s2v_mask_to_latent reduces with "any": a cell any of whose pixels asked for more change is
+ * never changed less.  pixel_mask, when not NULL, receives level > 0 as uint8 0 / 1 [F,H,W] (what the masked post-processes take: a pixel whose
+ * own level is 0 is the input video's).  One launch. */
+S2V_API int s2v_map_to_latent(const void* map, int32_t map_dtype, int32_t F, int32_t H, int32_t W, uint8_t* latent_level, uint8_t* pixel_mask,
+                              s2v_stream stream);
 /* The blend operands of the call on the context: z0 (the clean input latents, scaled) and noise0 (the noise that started the loop), both
- * [b,F,C,H,W] in the model dtype, and latent_mask uint8 [b,F,H,W], for the b = B/2 videos of the geometry.  The pointers are HELD, nothing is
+ * [b,F,C,H,W] in the model dtype, and latent_mask uint8 [b,F,H,W] (a 0 / 1 mask, or the levels of s2v_map_to_latent), for the b = B/2 videos of the geometry.  The pointers are HELD, nothing is
  * copied: they must stay valid until they are replaced or cleared (all NULL, b = 0).  Setting or clearing drops a captured step (the operands
  * are part of its key).  s2v_denoise_step / s2v_denoise_step_videos never read them. */
 S2V_API int s2v_set_blend(s2v_ctx* ctx, const void* z0, const void* noise0, const uint8_t* latent_mask, int32_t b);
 /* s2v_denoise_step_videos with the blend in the step's last kernel: `blends` is a HOST array of b records, video k blended with blends[k]
  * (its own next timestep and last-step flag, so a video on its last step may sit beside videos that go on).  The records go up beside the
  * coefficient sets, so one captured graph serves every step of a masked call.  Refused: a geometry with B = 1 (one sample of a CFG-parallel
- * pair: the split entries have no masked form), a shard context, operands not set for b = B/2. */
+ * pair: the split entries have no masked form), a shard context, operands not set for b = B/2, a keep_max outside 0..255. */
 S2V_API int s2v_denoise_step_masked(s2v_ctx* ctx, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
                             float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream);
 /* s2v_sched_step followed by the blend, for ONE video whose latent is [F,C,H,W]: latents_out in `dtype` (flags bit2 is refused: the blend runs
- * on the rounded result), z0 / noise0 [F,C,H,W] in `dtype`, latent_mask uint8 [F,H,W]; ctx may be NULL. */
+ * on the rounded result), z0 / noise0 [F,C,H,W] in `dtype`, latent_mask uint8 [F,H,W] (mask or levels); a keep_max outside 0..255 is refused;
+ * ctx may be NULL. */
 S2V_API int s2v_sched_step_masked(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
                           const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0, const void* noise0,
                           const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype, s2v_stream stream);
