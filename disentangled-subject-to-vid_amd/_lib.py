@@ -120,6 +120,15 @@ _SIGS.update({
     "s2v_time_embedding": [_P, ctypes.POINTER(_F), _I32, _P, _P],
     "s2v_op_step_cache": [_I32, _P, _I64, _P, _I32, _I64, _I32, _P],
 })
+# attention map (include/s2v_hip.h: s2v_attn_map_*, s2v_op_attn_mass)
+_SIGS.update({
+    "s2v_attn_map_enable": [_P, _I32, ctypes.POINTER(_I32), _I32],
+    "s2v_attn_map_arm": [_P, ctypes.c_uint64],
+    "s2v_attn_map_read": [_P, _I32, _P, ctypes.POINTER(_I64), _P],
+    "s2v_attn_map_reset": [_P],
+    "s2v_op_attn_mass": [_P, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P, _I32, _I32, _I32, _P],
+    "s2v_op_attn_mass_mean": [_P, _I32, _I32, _I32, _I32, _I64, _P, _P],
+})
 # replicas over RCCL behind the C ABI (csrc/rccl.hip); RCCL itself is bound at first use
 _SIGS.update({
     "s2v_rccl_available": [],

@@ -7,12 +7,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libs2v_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_g4.hip", "gemm_g4t.hip", "gemm_g4f.hip", "gemm_f32m.hip", "attention.hip", "attention_f32m.hip", "attention_q4.hip", "elementwise.hip", "vae.hip", "vae_api.hip", "t5.hip", "rccl.hip", "ulysses.hip", "lora.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_g4.hip", "gemm_g4t.hip", "gemm_g4f.hip", "gemm_f32m.hip", "attention.hip", "attention_f32m.hip", "attention_q4.hip", "attn_mass.hip", "elementwise.hip", "vae.hip", "vae_api.hip", "t5.hip", "rccl.hip", "ulysses.hip", "lora.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result", "-Wno-unused-value", "-Wno-inline-asm"]
 # the HBM-bound kernels mirror the reference's separately-rounded elementwise ops: no fma contraction there
 # (hipcc defaults to -ffp-contract=fast); the scheduler step is bit-exact against the CPU reference because of it
 EXTRA = {"attention_q4.hip": ["-fno-slp-vectorize"], "gemm_g4.hip": ["-fno-slp-vectorize"], "gemm_g4t.hip": ["-fno-slp-vectorize"], "gemm_g4f.hip": ["-fno-slp-vectorize"], "elementwise.hip": ["-ffp-contract=off", "-DS2V_TU_FP_CONTRACT_OFF"], "vae.hip": ["-ffp-contract=off", "-DS2V_TU_FP_CONTRACT_OFF"],
-         "t5.hip": ["-ffp-contract=off", "-DS2V_TU_FP_CONTRACT_OFF"]}
+         "t5.hip": ["-ffp-contract=off", "-DS2V_TU_FP_CONTRACT_OFF"],
+         # accumulate is ONE fp32 add of a finished product (out + sum * rcp): a contracted fma would break "two accumulated launches = a + b"
+         "attn_mass.hip": ["-ffp-contract=off"]}
 
 
 def _stale(out, deps):

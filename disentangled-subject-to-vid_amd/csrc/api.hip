@@ -75,10 +75,11 @@ struct GraphKey {
     int slot;   // -1: the whole step (s2v_denoise_step); 0 / 1: the forward-only graph of s2v_denoise_split_begin writing that half of the CFG pair
     const void *z0 = nullptr, *noise0 = nullptr, *mask = nullptr;   // the blend operands of the masked step (s2v_denoise_step_masked); null: unmasked
     int mode = 0;   // S2V_STEP_*: the step-cache mode the forward was captured in; every mode has an executable of its own (launch_captured)
+    uint64_t amask = 0;   // s2v_attn_map_arm: the layers whose attention the mass kernel follows in this step; every mask has an executable of its own
     bool same_but_mode(const GraphKey& o) const {
         return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask;
     }
-    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode; }
+    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask; }
 };
 
 // kernel classes of the per-class timing (ProfScope, s2v_profile_*): 8 = the Ulysses packs / unpacks, 9 = the LoRA down-projections
@@ -173,7 +174,18 @@ struct s2v_ctx {
     // one executable per step-cache mode (GraphKey::mode); the held ones differ in nothing but the mode
     hipGraphExec_t gexec[3] = {nullptr, nullptr, nullptr};
     GraphKey gkey[3] = {{nullptr, nullptr, nullptr, -1}, {nullptr, nullptr, nullptr, -1}, {nullptr, nullptr, nullptr, -1}};
-    bool any_graph() const { return gexec[0] || gexec[1] || gexec[2]; }
+    // ... and one per (mode, layer mask) of an armed step (s2v_attn_map_arm), which is another launch sequence: never replayed for an un-armed step
+    std::vector<std::pair<GraphKey, hipGraphExec_t>> gexec_armed;
+    bool any_graph() const { return gexec[0] || gexec[1] || gexec[2] || !gexec_armed.empty(); }
+    // attention map (include/s2v_hip.h): raw sums of the mass kernel over the armed layer launches, [am_n][B][H][V] fp32, beside the workspace
+    bool am_on = false;
+    int am_n = 0;                // 1 + text spans: range 0 is the reference stream [T, T + R)
+    int am_k0[AM_MAX_RANGES] = {}, am_k1[AM_MAX_RANGES] = {};
+    int am_spans[2 * (AM_MAX_RANGES - 1)] = {};   // the text spans as given: the ranges are re-derived when the geometry changes
+    float* am_acc = nullptr;
+    int64_t am_bytes = 0, am_count = 0;
+    uint64_t am_arm = 0;         // the layers of the NEXT forward; am_run: of the forward that is running (run_block reads it)
+    uint64_t am_run = 0;
     // step cache (include/s2v_hip.h): sc_delta holds IN between the two extra launches of a CAPTURE forward and the residual after it
     int sc_on = 0;               // s2v_step_cache_enable: 0 off, 1 the cache, 2 the cache + sc_in (IN of every forward, for the read-out)
     int sc_arm = 0;              // S2V_STEP_*: the mode of the next forward
@@ -495,6 +507,8 @@ extern "C" int s2v_create(const s2v_model_config* cfg, s2v_ctx** out) {
 extern "C" void s2v_destroy(s2v_ctx* c) {
     if (!c) return;
     for (hipGraphExec_t g : c->gexec) if (g) hipGraphExecDestroy(g);
+    for (auto& kg : c->gexec_armed) hipGraphExecDestroy(kg.second);
+    if (c->am_acc) hipFree(c->am_acc);
     if (c->sc_delta) hipFree(c->sc_delta);
     if (c->sc_in) hipFree(c->sc_in);
     if (c->cap_stream) hipStreamDestroy(c->cap_stream);
@@ -519,6 +533,29 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
 // the captured step bakes in what it was captured under: whoever changes that drops the graph, and the next graph step captures again
 static void drop_graph(s2v_ctx* c) {
     for (hipGraphExec_t& g : c->gexec) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+    for (auto& kg : c->gexec_armed) hipGraphExecDestroy(kg.second);
+    c->gexec_armed.clear();
+}
+
+// attention map: the buffer follows the geometry as the step cache's does (the caller has synchronised the device and dropped the graphs)
+static void am_free(s2v_ctx* c) {
+    if (c->am_acc) hipFree(c->am_acc);
+    c->am_acc = nullptr; c->am_bytes = 0; c->am_count = 0; c->am_arm = 0; c->am_on = false;
+}
+static int am_alloc(s2v_ctx* c) {
+    const int n = c->am_n;
+    am_free(c);
+    c->am_k0[0] = c->T; c->am_k1[0] = c->T + c->R;
+    for (int r = 1; r < n; ++r) {
+        c->am_k0[r] = c->am_spans[2 * (r - 1)]; c->am_k1[r] = c->am_spans[2 * (r - 1) + 1];
+        S2V_REQUIRE(c->am_k0[r] >= 0 && c->am_k0[r] <= c->am_k1[r] && c->am_k1[r] <= c->T,
+                    "s2v_attn_map_enable: a text span must be a token range inside [0, T) of the current geometry");
+    }
+    const int64_t bytes = (int64_t)n * c->B * c->cfg.num_heads * c->V * 4;
+    S2V_CHECK_HIP(hipMalloc((void**)&c->am_acc, bytes));
+    S2V_CHECK_HIP(hipMemset(c->am_acc, 0, bytes));
+    c->am_bytes = bytes; c->am_on = true; c->am_n = n;
+    return 0;
 }
 
 // step cache: whatever makes the stored residual belong to another computation clears its validity, and with it a pending arm (the next
@@ -722,6 +759,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     S2V_CHECK_HIP(hipDeviceSynchronize());
     drop_graph(c);
     sc_free(c);   // a shard context has no step cache
+    am_free(c);   // ... and no attention map
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
     drop_refs(c);
     c->B = 0;
@@ -870,6 +908,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
         if (omx) S2V_CHECK_HIP(hipMemcpy(c->omap, omap.data(), omap.size() * 4, hipMemcpyHostToDevice));
     }
     if (c->sc_on) S2V_TRY(sc_alloc(c, c->sc_on));   // the step cache follows the geometry
+    if (c->am_on) S2V_TRY(am_alloc(c));             // ... and so does the attention map: re-sized, zeroed, the count at 0
     return 0;
 }
 
@@ -1242,7 +1281,20 @@ static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w,
 
 // Xn -> QKV -> (qk-norm, rope, V^T) -> attention -> Xn (reused as the attention output buffer; fp8 engine: MX e4m3 in aq / hs)
 // w: the layer's weights -- c's own, or another context's of the same dtype / heads / weight_format (s2v_attn_forward_with)
-static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false) {
+// mass: an armed layer of the attention map -- the mass kernel follows the attention launch on the same stream.  c->QKV then holds q and k normed
+// and rotated (QK_DONE: by the projection's epilogue; QK_STANDALONE: by the core's own pass) and nothing has written it since: V^T, the attention
+// kernels and the MX output of the fp8 engine only read it.  QK_IN_QUANT (fp8 QK^T) leaves q and k un-normed in c->QKV: s2v_attn_map_arm refuses it
+static int am_launch(s2v_ctx* c, hipStream_t st) {
+    S2V_REQUIRE(c->am_on && c->am_acc && !c->fp8_qk, "attention map: an armed layer without s2v_attn_map_enable, or under fp8 QK^T");
+    AttnMassArgs a{};
+    a.qkv = c->QKV; a.ld_qkv = 3 * c->D; a.B = c->B; a.H = c->cfg.num_heads; a.Ntok = c->Ntok;
+    a.q0 = c->T + c->R; a.nq = c->V; a.n = c->am_n;
+    for (int r = 0; r < c->am_n; ++r) { a.k0[r] = c->am_k0[r]; a.k1[r] = c->am_k1[r]; }
+    a.out = c->am_acc; a.accumulate = 1;
+    return launch_attn_mass(a, c->dtype, (c->mfma || c->h16) ? 0 : 1, st);
+}
+
+static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false, bool mass = false) {
     const int D = c->D, pX = D + 3 * c->lr;
     // fp8 QK^T (weight_format 2 / 3 beyond its token threshold): q and k reach the attention kernel only as MX e4m3 images, so their LayerNorm + rotary
     // embedding ride in the pass that makes the images (qk_norm_quant_mx_k: the same bytes moved, the same bits produced) and the projection keeps the plain
@@ -1250,7 +1302,8 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
     const bool epi_ok = qk_epilogue_ok(c), norm_in_quant = epi_ok && c->fp8_qk && g_fused_qk != 3;
     S2V_TRY(qkv_proj(c, w, pX, lora, epi_ok && !norm_in_quant, prequant, st));
     const AttnOperands o{c->QKV, 3 * D, c->cfg.num_heads, c->Ntok, c->Xn, pX, (unsigned char*)c->aq, c->hs, c->Mpad};
-    return attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st);
+    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st));
+    return mass ? am_launch(c, st) : 0;
 }
 
 // the pieces of a block on the packed residual buffer X (rows: the context's M), in the order run_block launches them
@@ -1322,7 +1375,7 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
         S2V_TRY(block_norm(c, l, half, mod_base, mod_stride, st, &prequant));
         const GemmArgs g = block_gate(c, half, mod_base, mod_stride);
         if (half == 0) {
-            S2V_TRY(run_attention(c, c->layers[l], st, prequant, c->lora_on()));
+            S2V_TRY(run_attention(c, c->layers[l], st, prequant, c->lora_on(), (c->am_run >> l) & 1));
             S2V_TRY(out_proj(c, c->layers[l], c->lora_on(), g, EPI_BIAS_GATE_RES, true, st));
         } else {
             S2V_TRY(block_ff(c, l, g, prequant, st));
@@ -1399,10 +1452,22 @@ static int sc_done(s2v_ctx* c, int mode, int r) {
     if (r == 0 && mode == S2V_STEP_CAPTURE) c->sc_valid = true;
     return r;
 }
+// the layer mask armed for the forward that is about to run (s2v_attn_map_arm): one-shot, taken once per entry call, outside any capture
+static uint64_t am_take_arm(s2v_ctx* c) {
+    const uint64_t m = c->am_on ? c->am_arm : 0;
+    c->am_arm = 0;
+    return m;
+}
+// the host count: one per armed layer launch of a forward that is on the stream (a replayed graph runs them without running this code's body)
+static int am_done(s2v_ctx* c, uint64_t am, int r) {
+    if (r == 0) c->am_count += __builtin_popcountll(am);
+    return r;
+}
 
 // mode: S2V_STEP_* (include/s2v_hip.h); FULL is the forward as it is without a step cache
+// am: the layers whose attention the mass kernel follows (s2v_attn_map_arm; 0: the launches of a forward without the feature)
 static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, void* out,
-                        hipStream_t st, int mode = S2V_STEP_FULL) {
+                        hipStream_t st, int mode = S2V_STEP_FULL, uint64_t am = 0) {
     S2V_REQUIRE(c->ws && c->finalized && c->have_cond, "transformer_forward: geometry, weights and conditioning required");
     S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "transformer_forward: RoPE tables missing (s2v_set_rope)");
     S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "transformer_forward: sincos table missing (s2v_set_pos_embed)");
@@ -1412,6 +1477,8 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, in
     const bool reuse = mode == S2V_STEP_REUSE;
     S2V_REQUIRE(mode == S2V_STEP_FULL || (c->sc_on && c->sc_delta), "transformer_forward: a step-cache mode without s2v_step_cache_enable");
     S2V_REQUIRE(!reuse || c->sc_valid, "transformer_forward: S2V_STEP_REUSE without a captured residual");
+    S2V_REQUIRE(!am || !reuse, "transformer_forward: an attention map is armed (s2v_attn_map_arm) together with S2V_STEP_REUSE: the block stack does not run");
+    S2V_REQUIRE(!am || (c->am_on && !c->fp8_qk), "transformer_forward: an attention map is armed without s2v_attn_map_enable, or while fp8 QK^T is active");
     S2V_TRY(embed_streams(c, latents, lat_bstride, n_lat, t_dev, st, reuse));
     if (mode == S2V_STEP_CAPTURE) S2V_TRY(sc_launch(c, SC_KEEP, c->sc_delta, c->sc_in, st));   // IN
     else if (c->sc_in) S2V_TRY(sc_launch(c, SC_KEEP, c->sc_in, nullptr, st));                  // enable 2: IN of every forward, for the read-out
@@ -1419,8 +1486,12 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, in
         S2V_TRY(sc_launch(c, SC_ADD, c->sc_delta, nullptr, st));                               // X_video = rnd(IN' + delta)
     } else {
         // 3. blocks
-        for (int l = 0; l < c->L; ++l)
-            S2V_TRY(run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st));
+        c->am_run = am;
+        for (int l = 0; l < c->L; ++l) {
+            const int r = run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st);
+            if (r != 0) { c->am_run = 0; return r; }
+        }
+        c->am_run = 0;
         if (mode == S2V_STEP_CAPTURE) S2V_TRY(sc_launch(c, SC_SUB, c->sc_delta, nullptr, st)); // delta = rnd(OUT - IN)
     }
     // 4. tail
@@ -1434,15 +1505,17 @@ extern "C" int s2v_transformer_forward(s2v_ctx* c, const void* latents, int64_t 
                                        void* out, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward: null argument");
     const int mode = sc_take_arm(c);
-    return sc_done(c, mode, forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream, mode));
+    const uint64_t am = am_take_arm(c);
+    return am_done(c, am, sc_done(c, mode, forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream, mode, am)));
 }
 
 extern "C" int s2v_transformer_forward_videos(s2v_ctx* c, const void* latents, int32_t n_lat, const float* timesteps_dev, void* out,
                                               s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward_videos: null argument");
     const int mode = sc_take_arm(c);
+    const uint64_t am = am_take_arm(c);
     S2V_REQUIRE(c->ws && n_lat >= 1 && c->B % n_lat == 0, "s2v_transformer_forward_videos: n_lat must divide the geometry's batch (sample j embeds latent j mod n_lat)");
-    return sc_done(c, mode, forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream, mode));
+    return am_done(c, am, sc_done(c, mode, forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream, mode, am)));
 }
 
 // the residual streams of every sample between the caller's dense tensors (s0: n0 rows, s1: n1 rows, video: V rows per sample; n0 + n1 = T + R)
@@ -1665,7 +1738,7 @@ extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, floa
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
     S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
     *arena = c->arena ? c->arena_bytes : 0;
-    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes : 0;
+    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes : 0;
     return 0;
 }
 
@@ -1761,9 +1834,15 @@ static int stage_step(s2v_ctx* c, float timestep, const s2v_sched_coef* coef_hos
 // held one in anything but the mode drops every executable, as the single one was dropped before modes existed
 template <class Body>
 static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body body) {
-    for (int m = 0; m < 3; ++m)
-        if (c->gexec[m] && !c->gkey[m].same_but_mode(key)) { drop_graph(c); break; }
-    hipGraphExec_t& gexec = c->gexec[key.mode];
+    bool other = false;
+    for (int m = 0; m < 3; ++m) other = other || (c->gexec[m] && !c->gkey[m].same_but_mode(key));
+    for (auto& kg : c->gexec_armed) other = other || !kg.first.same_but_mode(key);
+    if (other) drop_graph(c);
+    hipGraphExec_t fresh = nullptr;
+    hipGraphExec_t* slot = key.amask ? &fresh : &c->gexec[key.mode];   // an armed step: its own executable per (mode, layer mask)
+    if (key.amask)
+        for (auto& kg : c->gexec_armed) if (kg.first == key) slot = &kg.second;
+    hipGraphExec_t& gexec = *slot;
     if (!gexec) {
         hipGraph_t graph = nullptr;
         S2V_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
@@ -1776,7 +1855,8 @@ static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body
         if (e != hipSuccess) gexec = nullptr;
         S2V_CHECK_HIP(e);
         c->graph_captures++;
-        c->gkey[key.mode] = key;
+        if (key.amask) c->gexec_armed.emplace_back(key, gexec);
+        else c->gkey[key.mode] = key;
     }
     S2V_CHECK_HIP(hipGraphLaunch(gexec, st));
     return 0;
@@ -1793,10 +1873,10 @@ static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* 
     return launch_sched_step(a, c->dtype, st);
 }
 
-static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode) {
+static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am) {
     // b videos: sample j of [negative x b | positive x b] embeds video j mod b straight from `latents` (one video: the stride of 0 it always had)
     const int b = c->B >= 2 ? c->B / 2 : 1;
-    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode));
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am));
     return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b);
 }
 
@@ -1804,6 +1884,7 @@ static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* 
 static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist, const void* noise,
                              int32_t use_graph, hipStream_t st) {
     const int mode = sc_take_arm(c);
+    const uint64_t am = am_take_arm(c);
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
     const int b = c->B >= 2 ? c->B / 2 : 1;
@@ -1812,10 +1893,10 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
                                        "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
                                      : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     S2V_TRY(stage_step(c, timesteps, coefs, b, st));
-    if (!use_graph) return sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode));
+    if (!use_graph) return am_done(c, am, sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode, am)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.mode = mode;
-    return sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode); }));
+    key.mode = mode; key.amask = am;
+    return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode, am); })));
 }
 
 extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
@@ -1844,9 +1925,9 @@ extern "C" int s2v_set_blend(s2v_ctx* c, const void* z0, const void* noise0, con
     return 0;
 }
 
-static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode) {
+static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am) {
     const int b = c->B / 2;
-    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode));
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am));
     SchedMaskArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
     a.nvid = b; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
@@ -1860,6 +1941,7 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
                                        float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps && coefs && blends, "s2v_denoise_step_masked: null argument");
     const int mode = sc_take_arm(c);
+    const uint64_t am = am_take_arm(c);
     S2V_REQUIRE(!c->shard, "s2v_denoise_step_masked: a shard context (s2v_set_shard) has no masked step: masked video-to-video runs on one GPU");
     S2V_REQUIRE(c->ws && c->B != 1, "s2v_denoise_step_masked: a geometry with B = 1 is one sample of a CFG-parallel pair, and the split entries "
                                     "(s2v_denoise_split_begin / _end, s2v_denoise_step_cfg_parallel) have no masked form: masked video-to-video runs the "
@@ -1872,10 +1954,10 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     for (int k = 0; k < b; ++k) S2V_REQUIRE(blends[k].keep_max >= 0 && blends[k].keep_max <= 255, "s2v_denoise_step_masked: keep_max must be a level 0..255");
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
-    if (!use_graph) return sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode));
+    if (!use_graph) return am_done(c, am, sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode, am)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode;
-    return sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode); }));
+    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am;
+    return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode, am); })));
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------
@@ -1895,6 +1977,8 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
     S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_split_begin: null argument");
     S2V_REQUIRE(sc_take_arm(c) == S2V_STEP_FULL, "s2v_denoise_split_begin: a step-cache mode (s2v_step_cache_arm: CAPTURE / REUSE) is armed, and CFG-parallel "
                                                  "has its own forward per rank: the step cache runs on one GPU (s2v_denoise_step)");
+    S2V_REQUIRE(am_take_arm(c) == 0, "s2v_denoise_split_begin: an attention map is armed (s2v_attn_map_arm), and a CFG-parallel split holds one sample of the pair "
+                                     "per rank: the attention map runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required; a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");
@@ -2206,6 +2290,87 @@ extern "C" int s2v_last_noise_pred(s2v_ctx* c, void** dev_ptr) {
     return 0;
 }
 
+// ---- attention map (include/s2v_hip.h) ---------------------------------------------------------------------------------------------------
+extern "C" int s2v_attn_map_enable(s2v_ctx* c, int32_t on, const int32_t* text_spans_host, int32_t n_spans) {
+    S2V_REQUIRE(c, "s2v_attn_map_enable: null context");
+    if (!on) {
+        if (c->am_on) { S2V_CHECK_HIP(hipDeviceSynchronize()); drop_graph(c); }
+        am_free(c);
+        return 0;
+    }
+    S2V_REQUIRE(c->kind == S2V_CTX_MODEL, "s2v_attn_map_enable: attention-only contexts (S2V_CTX_ATTN_*) run no forward");
+    S2V_REQUIRE(!c->shard, "s2v_attn_map_enable: a shard context (s2v_set_shard) has no attention map: its attention sees a head group of all ranks' rows; the map runs on one GPU");
+    S2V_REQUIRE(c->ws, "s2v_attn_map_enable: call s2v_set_geometry first (the sums are [1 + spans][B][H][V] of the current geometry)");
+    S2V_REQUIRE(n_spans >= 0 && n_spans <= AM_MAX_RANGES - 1 && (n_spans == 0 || text_spans_host), "s2v_attn_map_enable: 0..3 text spans (2 ints each) are accepted");
+    for (int i = 0; i < n_spans; ++i)
+        S2V_REQUIRE(text_spans_host[2 * i] >= 0 && text_spans_host[2 * i] <= text_spans_host[2 * i + 1] && text_spans_host[2 * i + 1] <= c->T,
+                    "s2v_attn_map_enable: a text span must be a token range inside [0, T) of the current geometry");
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    drop_graph(c);
+    for (int i = 0; i < 2 * n_spans; ++i) c->am_spans[i] = text_spans_host[i];
+    c->am_n = 1 + n_spans;
+    return am_alloc(c);
+}
+
+extern "C" int s2v_attn_map_arm(s2v_ctx* c, uint64_t layer_mask) {
+    S2V_REQUIRE(c, "s2v_attn_map_arm: null context");
+    if (layer_mask) {
+        S2V_REQUIRE(!c->shard, "s2v_attn_map_arm: a shard context (s2v_set_shard) has no attention map: the map runs on one GPU");
+        S2V_REQUIRE(c->am_on && c->am_acc, "s2v_attn_map_arm: the attention map is not enabled (s2v_attn_map_enable)");
+        S2V_REQUIRE(!c->fp8_qk, "s2v_attn_map_arm: fp8 QK^T is active at this geometry (q and k exist normed only as MX e4m3 images): the attention map "
+                                "runs with 16-bit attention (the plain \"fp8\" weight format included)");
+        S2V_REQUIRE(c->L >= 64 || (layer_mask >> c->L) == 0, "s2v_attn_map_arm: a layer bit at or beyond num_layers is set");
+        S2V_REQUIRE(c->sc_arm != S2V_STEP_REUSE, "s2v_attn_map_arm: S2V_STEP_REUSE is armed for the next forward (s2v_step_cache_arm): the block stack does not run, "
+                                                 "there is no attention to follow");
+    }
+    c->am_arm = layer_mask;
+    return 0;
+}
+
+extern "C" int s2v_attn_map_reset(s2v_ctx* c) {
+    S2V_REQUIRE(c && c->am_on && c->am_acc, "s2v_attn_map_reset: the attention map is not enabled (s2v_attn_map_enable)");
+    S2V_CHECK_HIP(hipDeviceSynchronize());   // launches of any stream may still add to the sums
+    S2V_CHECK_HIP(hipMemset(c->am_acc, 0, c->am_bytes));
+    c->am_count = 0;
+    return 0;
+}
+
+extern "C" int s2v_attn_map_read(s2v_ctx* c, int32_t per_head, void* out_dev, int64_t* count, s2v_stream stream) {
+    S2V_REQUIRE(c && count, "s2v_attn_map_read: null argument");
+    S2V_REQUIRE(c->am_on && c->am_acc, "s2v_attn_map_read: the attention map is not enabled (s2v_attn_map_enable)");
+    S2V_REQUIRE(out_dev, "s2v_attn_map_read: null argument");
+    *count = c->am_count;
+    hipStream_t st = (hipStream_t)stream;
+    if (per_head) {
+        S2V_CHECK_HIP(hipMemcpyAsync(out_dev, c->am_acc, (size_t)c->am_bytes, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    S2V_REQUIRE(c->am_count >= 1, "s2v_attn_map_read: the head mean needs at least one armed layer launch (the count is 0)");
+    return launch_attn_mass_mean(c->am_acc, c->am_n, c->B, c->cfg.num_heads, c->V, c->am_count, (float*)out_dev, st);
+}
+
+extern "C" int s2v_op_attn_mass(const void* qkv, int32_t B, int32_t H, int32_t Ntok, int32_t q0, int32_t nq, const int32_t* ranges_host, int32_t n,
+                                float* out, int32_t accumulate, int32_t dtype, int32_t impl, s2v_stream stream) {
+    S2V_REQUIRE(qkv && ranges_host && out, "s2v_op_attn_mass: null argument");
+    S2V_REQUIRE(n >= 1 && n <= AM_MAX_RANGES, "s2v_op_attn_mass: the number of key ranges must be 1..4");
+    S2V_REQUIRE(B >= 1 && H >= 1 && Ntok >= 1, "s2v_op_attn_mass: bad shape");
+    for (int r = 0; r < n; ++r)
+        S2V_REQUIRE(ranges_host[2 * r] >= 0 && ranges_host[2 * r] <= ranges_host[2 * r + 1] && ranges_host[2 * r + 1] <= Ntok,
+                    "s2v_op_attn_mass: a key range must lie inside [0, Ntok] with k0 <= k1");
+    S2V_REQUIRE(q0 >= 0 && nq >= 1 && (int64_t)q0 + nq <= Ntok, "s2v_op_attn_mass: the query rows [q0, q0 + nq) must lie inside the sample (q0 + nq <= Ntok)");
+    S2V_REQUIRE(impl == 0 || impl == 1, "s2v_op_attn_mass: impl is 0 (matrix pipe) or 1 (generic)");
+    S2V_REQUIRE(impl != 0 || dtype != S2V_DTYPE_F32, "s2v_op_attn_mass: impl 0 (matrix pipe) runs bf16 / fp16 storage; fp32 runs impl 1");
+    AttnMassArgs a{};
+    a.qkv = qkv; a.ld_qkv = 3 * H * 64; a.B = B; a.H = H; a.Ntok = Ntok; a.q0 = q0; a.nq = nq; a.n = n;
+    for (int r = 0; r < n; ++r) { a.k0[r] = ranges_host[2 * r]; a.k1[r] = ranges_host[2 * r + 1]; }
+    a.out = out; a.accumulate = accumulate ? 1 : 0;
+    return launch_attn_mass(a, dtype, impl, (hipStream_t)stream);
+}
+
+extern "C" int s2v_op_attn_mass_mean(const float* acc, int32_t n, int32_t B, int32_t H, int32_t nq, int64_t count, float* out, s2v_stream stream) {
+    return launch_attn_mass_mean(acc, n, B, H, nq, count, out, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------------
 // ---- step cache (include/s2v_hip.h) -------------------------------------------------------------------------------------------------
 extern "C" int s2v_step_cache_enable(s2v_ctx* c, int32_t on) {
@@ -2227,6 +2392,8 @@ extern "C" int s2v_step_cache_arm(s2v_ctx* c, int32_t mode) {
         S2V_REQUIRE(!c->shard, "s2v_step_cache_arm: a shard context (s2v_set_shard) runs the staged step, which has no cached form: the step cache runs on one GPU");
         S2V_REQUIRE(c->sc_on && c->sc_delta, "s2v_step_cache_arm: the step cache is not enabled (s2v_step_cache_enable)");
         S2V_REQUIRE(mode != S2V_STEP_REUSE || c->sc_valid, "s2v_step_cache_arm: no captured residual for this geometry / conditioning / weights");
+        S2V_REQUIRE(mode != S2V_STEP_REUSE || !c->am_arm, "s2v_step_cache_arm: S2V_STEP_REUSE while an attention map is armed for the next forward (s2v_attn_map_arm): "
+                                                          "the block stack does not run, there is no attention to follow");
     }
     c->sc_arm = mode;
     return 0;

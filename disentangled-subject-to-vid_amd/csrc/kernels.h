@@ -404,3 +404,19 @@ int launch_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int
 // strided 2-D convert-copy: dst[r*ldd + c] = src[r*lds + c]
 int launch_convert2d(const void* src, int src_dtype, int64_t lds_, void* dst, int dst_dtype, int64_t ldd, int64_t rows,
                      int64_t cols, hipStream_t st);
+
+// Attention mass (attn_mass.hip): the softmax weight a query of qkv [B * Ntok][ld_qkv] (q | k | v, head_dim 64, scores q . k / 8 over the
+// sample's own Ntok keys) puts on n <= 4 key ranges [k0_r, k1_r) -> out [n][B][H][nq] fp32 for the query rows [q0, q0 + nq) of every sample.
+// accumulate: out + mass in one fp32 add by the owning thread.  impl 0: v_mfma_f32_32x32x16 (bf16 / fp16 storage; q * 0.125 * log2 e rounded
+// to the storage type, exp2, v_rcp_f32); impl 1: the VALU (any dtype; q * 0.125, expf, a division)
+#define AM_MAX_RANGES 4
+struct AttnMassArgs {
+    const void* qkv; int ld_qkv;
+    int B, H, Ntok;
+    int q0, nq;
+    int n; int k0[AM_MAX_RANGES], k1[AM_MAX_RANGES];
+    float* out; int accumulate;
+};
+int launch_attn_mass(const AttnMassArgs& a, int dtype, int impl, hipStream_t st);
+// head mean of raw sums acc [n][B][H][nq] -> out [n][B][nq]: (acc[.][.][0][i] + ... + acc[.][.][H-1][i], in that order) * (1.0f / (H * count))
+int launch_attn_mass_mean(const float* acc, int n, int B, int H, int nq, int64_t count, float* out, hipStream_t st);

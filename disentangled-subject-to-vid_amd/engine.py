@@ -469,11 +469,51 @@ class S2VEngine:
         if self._CACHE_MODES[cache] != _lib.STEP_FULL:
             _lib.check(_lib.lib().s2v_step_cache_arm(self._h, self._CACHE_MODES[cache]))
 
+    # ---- attention map (include/s2v_hip.h: s2v_attn_map_*) -----------------------------------------------------------------------------
+    _attn_map_n = 0
+
+    def attn_map_enable(self, on=True, text_spans=()):
+        """after set_geometry: allocates (and zeroes) the sums [1 + spans, B, H, V] fp32 of the current geometry; range 0 is the reference
+        stream, text_spans up to three (k0, k1) token ranges inside [0, T).  False frees them"""
+        spans = [int(x) for s in text_spans for x in s]
+        if len(spans) != 2 * len(text_spans):
+            raise _lib.S2VError("attn_map_enable: every text span is a pair (k0, k1)")
+        arr = (ctypes.c_int32 * max(1, len(spans)))(*spans)
+        _lib.check(_lib.lib().s2v_attn_map_enable(self._h, int(bool(on)), arr, len(text_spans)))
+        self._attn_map_n = 1 + len(text_spans) if on else 0
+
+    def attn_map_reset(self):
+        """zero the sums and the count"""
+        _lib.check(_lib.lib().s2v_attn_map_reset(self._h))
+
+    def attn_map_read(self, per_head=False):
+        """(sums, count): per_head the raw sums [n, B, H, V] fp32 over the armed layer launches since the last reset; otherwise their head mean
+        [n, B, V] divided by the count (count >= 1).  n = 1 + text spans, row 0 the reference stream"""
+        B, T, F, H, W = self.geometry
+        V, nh = F * (H // 2) * (W // 2), self.cfg.num_attention_heads
+        shape = (self._attn_map_n, B, nh, V) if per_head else (self._attn_map_n, B, V)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        count = ctypes.c_int64()
+        _lib.check(_lib.lib().s2v_attn_map_read(self._h, int(bool(per_head)), _lib.ptr(out), ctypes.byref(count), _lib.stream_ptr()))
+        return out, count.value
+
+    def _arm_attn(self, attn_layers):
+        """the layers whose attention the mass kernel follows in the next forward (one-shot; after attn_map_enable)"""
+        if attn_layers is None:
+            return
+        mask = 0
+        for l in attn_layers:
+            if int(l) != l or l < 0 or l >= 64:
+                raise _lib.S2VError(f"attn_layers: {l!r} is no block index")
+            mask |= 1 << int(l)
+        _lib.check(_lib.lib().s2v_attn_map_arm(self._h, mask))
+
     # ---- compute -------------------------------------------------------------------------------------------
-    def forward(self, latents, timesteps, shared_latent=False, cache=None):
+    def forward(self, latents, timesteps, shared_latent=False, cache=None, attn_layers=None):
         """CogVideoXTransformer3DModel.forward seam: latents [B,F,C,H,W]; with shared_latent [n,F,C,H,W], n dividing B: sample j embeds latent
         j mod n (n = 1: every sample the same latent; n = B/2: the CFG batch cat([latents] * 2) of B/2 videos without the copy).
-        cache: the step-cache mode of this forward (_arm; after step_cache_enable)"""
+        cache: the step-cache mode of this forward (_arm; after step_cache_enable)
+        attn_layers: the block indices whose attention mass is added to the attention map by this forward (after attn_map_enable)"""
         B, T, F, H, W = self.geometry
         lat = latents.to(self.device, self.dtype).contiguous()
         n_lat = lat.numel() // (F * self.cfg.in_channels * H * W)
@@ -485,6 +525,7 @@ class S2VEngine:
             t = t.reshape(-1)[:1].expand(B).contiguous()
         out = torch.empty((B, F, self.cfg.out_channels, H, W), dtype=self.dtype, device=self.device)
         self._arm(cache)
+        self._arm_attn(attn_layers)
         if shared_latent and n_lat > 1:
             _lib.check(_lib.lib().s2v_transformer_forward_videos(self._h, _lib.ptr(lat), n_lat, _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr()))
             return out
@@ -555,13 +596,14 @@ class S2VEngine:
             _lib.check(_lib.lib().s2v_set_blend(self._h, None, None, None, 0))
             self._blend = None
 
-    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None):
+    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
         [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
         (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
         coef[k] -- its own kind, guidance and scalars (s2v_denoise_step_videos); a scalar beside a sequence is repeated.
         blend: the masked step (s2v_denoise_step_masked, after set_blend): one _lib.BlendC, or a sequence of b, video k blended with blend[k]
-        cache: the step-cache mode of this step's forward (_arm; after step_cache_enable): "capture", "reuse" or None"""
+        cache: the step-cache mode of this step's forward (_arm; after step_cache_enable): "capture", "reuse" or None
+        attn_layers: the block indices whose attention mass this step adds to the attention map (after attn_map_enable; not with "reuse")"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
@@ -585,6 +627,7 @@ class S2VEngine:
         if auto:
             self.attn_slow_stats(reset=True)
         self._arm(cache)
+        self._arm_attn(attn_layers)
         if blend is not None:
             _lib.check(_lib.lib().s2v_denoise_step_masked(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                           int(use_graph and not auto), _lib.stream_ptr()))

@@ -82,6 +82,49 @@ def change_map_plan(n):
     return [max(0, (255 * (n - j - 1) - 1) // n) for j in range(n)]
 
 
+class AttentionMap:
+    """what S2VPipeline.__call__(attention_map=...) collects: `layers` the block indices whose attention is followed (an explicit list: no
+    default is recommended), `steps` the step indices of the call that collect (None: every step that runs the block stack), `text_spans` up
+    to three (k0, k1) token ranges of the prompt, each giving a map of its own beside the subject's"""
+
+    def __init__(self, layers, steps=None, text_spans=()):
+        self.layers = layers
+        self.steps = steps
+        self.text_spans = tuple(tuple(s) for s in text_spans)
+
+
+def attention_map_plan(am, n_steps, sc_plan=None):
+    """(collect, skipped): the step indices of a call of n_steps steps on which the layers of `am` are armed, and the requested ones that are
+    not because the step-cache plan sc_plan (True = full) reuses them: a reuse step does not run the block stack.  Host integers only"""
+    want = list(range(n_steps)) if am.steps is None else sorted(set(int(i) for i in am.steps))
+    for i in want:
+        if i < 0 or i >= n_steps:
+            raise ValueError(f"`attention_map`: step {i} is outside the {n_steps} steps this call runs")
+    skipped = [i for i in want if sc_plan is not None and not sc_plan[i]]
+    return [i for i in want if i not in skipped], skipped
+
+
+def attention_map_to_change_map(m, lo, hi, num_frames):
+    """an attention map [b, F_lat, h, w] (S2VPipeline.attention_maps["subject"], or one text map) -> change-map levels uint8
+    [b, num_frames, 16 h, 16 w] for a second call's `change_map=`: level = floor(clamp((m - lo) / (hi - lo), 0, 1) * 255 + 0.5) in fp32
+    (NaN -> 0), every patch repeated 16 x 16 in space, latent frame 0 to frame 0 and latent frame f >= 1 to frames 4f - 3 .. 4f -- the
+    cells s2v_map_to_latent reduces, so every latent cell gets the level of its own patch back.  Plain torch, on the map's device; lo and hi
+    are the caller's to choose"""
+    if m.ndim != 4:
+        raise ValueError(f"attention_map_to_change_map: the map must be [b, F_lat, h, w], got {tuple(m.shape)}")
+    if not hi > lo:
+        raise ValueError(f"attention_map_to_change_map: need lo < hi, got lo = {lo}, hi = {hi}")
+    b, Fl, h, w = m.shape
+    if num_frames != 4 * (Fl - 1) + 1:
+        raise ValueError(f"attention_map_to_change_map: {Fl} latent frames are {4 * (Fl - 1) + 1} frames, not num_frames = {num_frames}")
+    x = (m.to(torch.float32) - lo) / (hi - lo)
+    x = torch.nan_to_num(x, nan=0.0).clamp(0.0, 1.0)
+    level = torch.floor(x * 255.0 + 0.5).to(torch.uint8)
+    level = level.repeat_interleave(16, dim=2).repeat_interleave(16, dim=3)
+    reps = torch.tensor([1] + [4] * (Fl - 1), device=m.device)
+    return level.repeat_interleave(reps, dim=1).contiguous()
+
+
 class S2VPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]  # pipeline_cogvideox.py:166-170
 
@@ -276,6 +319,41 @@ class S2VPipeline:
             raise ValueError(f"`step_cache` is a list of {len(sc)} entries for the {n} steps this call runs: one boolean per step actually run")
 
     step_cache_report = None
+    attention_maps = None
+
+    @staticmethod
+    def check_attention_map(am, num_layers, weight_format=None, per_video=False, cfg_parallel=None, ulysses=None, fused=True, videos_path=False):
+        """every refusal of an attention-map call that needs no step count and no geometry (no device is touched)"""
+        if not isinstance(am, AttentionMap):
+            raise ValueError("`attention_map` must be an AttentionMap(layers, steps=None, text_spans=())")
+        if per_video or videos_path:
+            raise ValueError("`attention_map` together with per-video lists (or several input videos, which run per-video plans): the maps are "
+                             "collected on one plan of steps for the whole batch")
+        for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+            if arg is not None:
+                raise ValueError(f"`attention_map` together with `{name}`: the map is collected on one GPU; CFG-parallel and Ulysses split the "
+                                 f"attention it reads")
+        if not fused:
+            raise ValueError("`attention_map` together with fused=False: the map is collected inside the fused step; fused=False is the reference's "
+                             "seam sequence")
+        if weight_format == "fp8-qk":
+            raise ValueError("`attention_map` with weight_format 'fp8-qk': q and k reach the attention only as MX e4m3 images; the map needs 16-bit "
+                             "attention (None or 'fp8')")
+        if not isinstance(am.layers, (list, tuple)) or len(am.layers) == 0:
+            raise ValueError("`attention_map`: `layers` is an explicit, non-empty list of block indices (no default is recommended)")
+        for l in am.layers:
+            if int(l) != l or l < 0 or l >= num_layers:
+                raise ValueError(f"`attention_map`: layer {l!r} is no block index of a model of {num_layers} blocks")
+        if len(set(int(l) for l in am.layers)) != len(am.layers):
+            raise ValueError("`attention_map`: a layer is listed twice")
+        if am.steps is not None and (not isinstance(am.steps, (list, tuple)) or any(int(i) != i for i in am.steps)):
+            raise ValueError("`attention_map`: `steps` is a list of step indices, or None for every step that runs the block stack")
+        if len(am.text_spans) > 3:
+            raise ValueError(f"`attention_map`: at most three text spans (four key ranges with the reference stream), got {len(am.text_spans)}")
+        for sp in am.text_spans:
+            if len(sp) != 2 or int(sp[0]) != sp[0] or int(sp[1]) != sp[1] or sp[0] < 0 or sp[1] < sp[0]:
+                raise ValueError(f"`attention_map`: a text span is a token range (k0, k1) with 0 <= k0 <= k1, got {sp!r}")
+        return am
 
     @staticmethod
     def blend_plan(scheduler, plan, dtype, device="cpu", keep_max=None):
@@ -313,7 +391,8 @@ class S2VPipeline:
                  num_frames=49, num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, generator=None,
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
-                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None):
+                 video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None,
+                 attention_map=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -352,8 +431,16 @@ class S2VPipeline:
         contribution to the video rows, a reuse step embeds its latents, adds it and runs the tail.  CFG, the scheduler step, the DPM draws and
         the mask's select run on every step.  A planned reuse runs full when the stored contribution is no longer valid (a callback replaced
         `prompt_embeds`).  After the call `step_cache_report` holds {"plan", "full", "reused", "ran_full"}.  Scalars only (b > 1 videos share
-        the timesteps); refused with per-video lists, several input videos, cfg_parallel=, ulysses= and fused=False."""
+        the timesteps); refused with per-video lists, several input videos, cfg_parallel=, ulysses= and fused=False.
+        attention_map: an AttentionMap(layers, steps=None, text_spans=()) -- on the listed steps (None: every step that runs the block stack; with
+        `step_cache` the planned reuse steps are skipped and reported) the attention of the listed blocks is followed by the mass kernel, which
+        sums the softmax weight every video query puts on the reference-image keys and on each text span.  After the call `attention_maps` holds
+        {"subject": [b, F_lat, H/16, W/16] fp32, "text": [n_spans, b, F_lat, H/16, W/16], "count", "layers", "steps", "skipped_steps"}: the
+        positive halves of the CFG pairs, head mean, then the mean over the collected (layer, step) launches.  The latents are those of the call
+        without it, bit for bit.  Scalars only; refused with per-video lists, several input videos, cfg_parallel=, ulysses=, fused=False and
+        fp8 QK^T ('fp8-qk', and 'fp8-auto' where it is active)."""
         self.step_cache_report = None
+        self.attention_maps = None
         if change_map is not None and mask is not None:
             raise ValueError("`change_map` together with `mask`: both say which cells are kept; a change map of 0 and 255 alone is that mask")
         levels = change_map is not None   # from here on `mask` is the call's plane, read as levels 0..255 when `levels`
@@ -402,6 +489,10 @@ class S2VPipeline:
             mask = self.check_mask(mask, video, b, cfg_parallel, ulysses, what)
         if step_cache is not None:
             step_cache = self.check_step_cache(step_cache, per_video, cfg_parallel, ulysses, fused, video is not None and b > 1)
+        if attention_map is not None:
+            attention_map = self.check_attention_map(attention_map, self.transformer.config.num_layers,
+                                                     getattr(self.transformer.config, "weight_format", None), per_video, cfg_parallel, ulysses,
+                                                     fused, video is not None and b > 1)
         if per_video or (video is not None and b > 1):   # every video on its own plan; scalars and one input video stay on the path below
             lists = self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)
             return self._call_videos(b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg,
@@ -470,10 +561,22 @@ class S2VPipeline:
                 sc_plan = step_cache_plan(eng.time_embedding([float(t) for t in timesteps]), step_cache.threshold, step_cache.coefficients,
                                           step_cache.keep_first, step_cache.keep_last)
             self.step_cache_report = {"plan": list(sc_plan), "full": 0, "reused": 0, "ran_full": []}
+        am_steps = am_skipped = None
+        am_ran = []   # the steps that did collect (an interrupted call ends early)
+        if attention_map is not None:   # the steps that collect, on the host, before the loop
+            am_steps, am_skipped = attention_map_plan(attention_map, len(timesteps), sc_plan)
+            for sp in attention_map.text_spans:
+                if sp[1] > text.shape[1]:
+                    raise ValueError(f"`attention_map`: the text span {sp!r} reaches beyond the {text.shape[1]} prompt tokens")
+            if eng.fp8_qk_active:
+                raise ValueError("`attention_map` while fp8 QK^T is active at this geometry ('fp8-auto' beyond its token threshold): the map needs "
+                                 "16-bit attention (None or 'fp8')")
         old = None
         try:
             if sc_plan is not None:
                 eng.step_cache_enable(True)
+            if attention_map is not None:
+                eng.attn_map_enable(True, attention_map.text_spans)
             for i, t in enumerate(timesteps):
                 if self.interrupt:
                     break
@@ -502,8 +605,12 @@ class S2VPipeline:
                             if not sc_plan[i] and cache != "reuse":
                                 rep["ran_full"].append(i)
                             rep["reused" if cache == "reuse" else "full"] += 1
+                        collect = am_steps is not None and i in am_steps and cache != "reuse"
                         eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph,
-                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev, keep_max[i]), cache=cache)
+                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev, keep_max[i]), cache=cache,
+                                         attn_layers=attention_map.layers if collect else None)
+                        if collect:
+                            am_ran.append(i)
                     else:
                         cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
                 else:
@@ -542,12 +649,29 @@ class S2VPipeline:
                         if fused:  # the hoisted text projection follows the new embeddings
                             eng.set_conditioning(text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1], ref)
                     negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
+            if attention_map is not None:
+                self.attention_maps = self._read_attention_maps(eng, attention_map, b, am_ran, am_skipped)
         finally:
             if fused and mask is not None:
                 eng.clear_blend()
             if sc_plan is not None:
                 eng.step_cache_enable(False)
+            if attention_map is not None and eng.geometry is not None:
+                eng.attn_map_enable(False)
         return self._finish(latents, fused, output_type, return_dict, paste)
+
+    @staticmethod
+    def _read_attention_maps(eng, am, b, steps, skipped):
+        """the positive halves (rows b .. 2b - 1 of [negative x b | positive x b]) of the head mean over the collected launches"""
+        B, T, F, H, W = eng.geometry
+        n = 1 + len(am.text_spans)
+        if steps:
+            mean, count = eng.attn_map_read(per_head=False)
+        else:   # nothing was collected (every requested step is a planned reuse, or an empty list)
+            mean, count = torch.zeros((n, B, F * (H // 2) * (W // 2)), dtype=torch.float32, device=eng.device), 0
+        maps = mean[:, b:2 * b].reshape(n, b, F, H // 2, W // 2)
+        return {"subject": maps[0].contiguous(), "text": maps[1:].contiguous(), "count": count, "layers": [int(l) for l in am.layers],
+                "steps": list(steps), "skipped_steps": list(skipped)}
 
     def _finish(self, latents, fused, output_type, return_dict, paste=None):
         """paste (masked video-to-video's paste-back): (the input videos [1 | b,3,F,H,W], the binarised pixel masks [1 | b,F,H,W])"""

@@ -45,7 +45,7 @@ def prompt_embeddings(text_encoder, input_ids, dtype=None):
 
 def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_ids, height=480, width=720, num_frames=49,
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
-              video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, change_map_uint8=None, **pipe_kwargs):
+              video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, change_map_uint8=None, attention_map=None, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
     `output_type` selects ("latent" / "pt").  A batch of prompt ids [P, T] (with num_videos_per_prompt through **pipe_kwargs: up to four
     videos per call) shares the one reference image and returns one video per row, [b, F, H, W, 3].
@@ -76,7 +76,12 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
 
     Change map: change_map_uint8 [F, H, W] or [b, F, H, W], levels 0..255 over the input video's frames and pixels -- a strength per pixel
     (S2VPipeline.__call__'s `change_map`): 255 repaints from the first step, 0 keeps the input video, a level in between is released
-    part-way through the steps.  Not together with mask_uint8."""
+    part-way through the steps.  Not together with mask_uint8.
+
+    Attention map: attention_map=AttentionMap(layers, steps, text_spans) is passed through to S2VPipeline.__call__; the maps are in
+    pipe.attention_maps after the call, and attention_map_to_change_map turns one into the change_map_uint8 of a second call."""
+    if attention_map is not None:
+        pipe_kwargs = dict(pipe_kwargs, attention_map=attention_map)
     if video_uint8 is not None:
         vs = np.asarray(video_uint8).shape[-4:]
         if np.asarray(video_uint8).ndim not in (4, 5) or vs[3] != 3:

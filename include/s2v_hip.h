@@ -381,6 +381,34 @@ S2V_API int s2v_step_cache_read(s2v_ctx* ctx, int32_t which, void* out_dev, s2v_
  * synchronises the stream */
 S2V_API int s2v_time_embedding(s2v_ctx* ctx, const float* timesteps_host, int32_t n, void* out_dev, s2v_stream stream);
 
+/* ---- Attention map: the softmax mass a video query puts on the reference-image keys (and on text-token spans) ---------------------------------
+ * Every block runs joint attention over [text T | reference R | video V].  With q_i, k_j the normed and rotated rows of one (sample, head),
+ * s_ij = q_i . k_j / 8 over the sample's own Ntok keys and  mass_r(b, h, i) = sum over j in range r of softmax_j(s_i.)  in fp32.  Opt-in state
+ * on a model context; while off every entry runs the launches it runs without this feature and s2v_device_bytes reports what it reports
+ * without it.
+ * s2v_attn_map_enable: after s2v_set_geometry; on != 0 allocates the raw sums acc [1 + n_spans][B][H][V] fp32 (zeroed, counted as workspace
+ * while on), on = 0 frees them.  Range 0 is always the reference stream [T, T + R); text_spans_host holds n_spans <= 3 pairs (k0, k1), token
+ * ranges inside [0, T); the queries are the video rows [T + R, Ntok).  A new geometry re-sizes and zeroes the buffer (a span that no longer fits
+ * refuses the geometry call and leaves the map off).  Refused on a shard context and on attention-only contexts.  Drops a captured step.
+ * s2v_attn_map_arm: the layers (bit l = block l) of the NEXT forward only (s2v_transformer_forward*, s2v_denoise_step, _videos, _masked); after
+ * it the mask is 0 again.  After the attention launch of every armed layer the forward launches the mass kernel (csrc/attn_mass.hip) on the
+ * same stream, which adds mass to acc in one fp32 add per element (no atomics: two armed forwards hold the fp32 sum of each alone, bit for bit),
+ * and the host count goes up by one per armed layer launch.  The kernel only reads the forward's q / k buffer: an armed step returns the bits of
+ * the un-armed step.  Refused by name: on a shard context, without enable, while fp8 QK^T is active at the geometry (weight_format 2, or 3 beyond
+ * its token threshold: q and k exist normed only as MX e4m3 images; the plain fp8 weight format with its 16-bit attention is allowed), together
+ * with S2V_STEP_REUSE (either order of the two arms: the block stack does not run), a bit at or beyond num_layers; a s2v_denoise_split_begin
+ * that finds a mask armed refuses (a CFG-parallel split holds one sample of the pair per rank).
+ * An armed step is another launch sequence: a captured step (use_graph) is kept per (step-cache mode, layer mask), and an un-armed step never
+ * replays an armed executable nor the reverse.
+ * s2v_attn_map_read: per_head != 0 copies the raw sums [n][B][H][V] to out_dev; per_head = 0 writes the head mean [n][B][V],
+ * (acc[.][.][0][i] + ... + acc[.][.][H-1][i], in that order, fp32) * (1.0f / (H * count)), which needs count >= 1.  *count: the armed layer
+ * launches since the last reset.  s2v_attn_map_reset zeroes the sums and the count (synchronises the device).
+ * Engines whose attention runs on the matrix pipe (bf16, fp16) run the MFMA form (impl 0 of s2v_op_attn_mass), an fp32 engine the generic one. */
+S2V_API int s2v_attn_map_enable(s2v_ctx* ctx, int32_t on, const int32_t* text_spans_host, int32_t n_spans);
+S2V_API int s2v_attn_map_arm(s2v_ctx* ctx, uint64_t layer_mask);
+S2V_API int s2v_attn_map_read(s2v_ctx* ctx, int32_t per_head, void* out_dev, int64_t* count, s2v_stream stream);
+S2V_API int s2v_attn_map_reset(s2v_ctx* ctx);
+
 /* Live per-kernel timing for the roofline report (bench.py): HIP events are recorded on the launch stream around
  * every launch of a class; classes 0 qkv GEMM, 1 attention, 2 out-proj GEMM, 3 FF1 GEMM, 4 FF2 GEMM,
  * 5 LN-modulate, 6 qk-norm/rope/V^T, 7 the modulation GEMV, 8 the Ulysses packs, 9 the runtime-LoRA down-projections.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
@@ -622,6 +650,15 @@ S2V_API int s2v_t5_encode(s2v_t5* t5, const int64_t* input_ids_dev, int32_t B, i
  * against the dense cache [B][n]; op 0: cache = x; 1: cache = rnd(float(x) - float(cache)); 2: x = rnd(float(x) + float(cache)).  n, x_bstride
  * and the pointers in whole 16-byte vectors */
 S2V_API int s2v_op_step_cache(int32_t op, void* x, int64_t x_bstride, void* cache, int32_t B, int64_t n, int32_t dtype, s2v_stream stream);
+/* the attention-mass kernel on its own: qkv [B * Ntok][3 * H * 64] (q | k | v as s2v_op_attention takes them, 16-byte aligned; nothing past row
+ * B * Ntok - 1 is read), query rows [q0, q0 + nq) of every sample, ranges_host n pairs (k0, k1) -> out [n][B][H][nq] fp32; accumulate != 0: out + mass
+ * in one fp32 add.  An empty range gives exactly 0.  impl 0: v_mfma_f32_32x32x16 on bf16 / fp16 storage, q * 0.125 * log2 e rounded to the
+ * storage type, exp2, v_rcp_f32; impl 1: the VALU on any dtype, q * 0.125, expf, a division.  Refused by name: n outside 1..4, a range outside
+ * [0, Ntok] or with k1 < k0, q0 + nq > Ntok, impl 0 with fp32 */
+S2V_API int s2v_op_attn_mass(const void* qkv, int32_t B, int32_t H, int32_t Ntok, int32_t q0, int32_t nq, const int32_t* ranges_host, int32_t n,
+                     float* out, int32_t accumulate, int32_t dtype, int32_t impl, s2v_stream stream);
+/* the head mean of s2v_attn_map_read on caller-owned sums: acc [n][B][H][nq] -> out [n][B][nq] = (sum over h = 0 .. H-1 in that order) * (1.0f / (H * count)) */
+S2V_API int s2v_op_attn_mass_mean(const float* acc, int32_t n, int32_t B, int32_t H, int32_t nq, int64_t count, float* out, s2v_stream stream);
 
 /* ---- operator-level entry points (used by the parity tests and micro-benchmarks) ------------------------- */
 /* C[M,N] = A[M,K] . W[N,K]^T + bias, epilogue 0 = bias, 1 = bias + GELU(tanh); impl 0 = MFMA bf16, 1 = generic (VALU),
