@@ -2,6 +2,10 @@
 (src/custom_cogvideox_pipe.py:125-326) from step 4 on: prompt embeddings are inputs (the T5 encoder is a caller-side
 step), everything after them runs here.
 
+S2VPipeline.__call__ checks the arguments, plans every video's steps on the host (video_plan: a call with scalars is one plan shared by all
+its videos) and runs them in ONE loop (_denoise), whatever the call combines of several videos, per-video lists, video-to-video, masks,
+change maps, the step cache, the attention map, CFG-parallel and Ulysses.
+
 Two execution modes with identical results:
   fused=True  (default) one s2v_denoise_step per iteration: transformer on the CFG pair, fp32 CFG, scheduler step
                and the round to the model dtype in one (optionally hipGraph-captured) launch sequence;
@@ -125,6 +129,13 @@ def attention_map_to_change_map(m, lo, hi, num_frames):
     return level.repeat_interleave(reps, dim=1).contiguous()
 
 
+def _one_gpu_only(cfg_parallel, ulysses, message):
+    """the refusal of a feature that does not run under cfg_parallel= / ulysses=: message(name) for whichever was passed, cfg_parallel first"""
+    for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
+        if arg is not None:
+            raise ValueError(message(name))
+
+
 class S2VPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]  # pipeline_cogvideox.py:166-170
 
@@ -179,10 +190,8 @@ class S2VPipeline:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {b}. "
                              f"Make sure the batch size matches the length of the generators.")
         if b > 1:
-            for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
-                if arg is not None:
-                    raise ValueError(f"`{name}` with {b} videos per call: several videos per call run as one batched step on one GPU; "
-                                     f"CFG-parallel and Ulysses stay one video per call")
+            _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`{name}` with {b} videos per call: several videos per call run as one batched step on "
+                                                              f"one GPU; CFG-parallel and Ulysses stay one video per call")
             if video is not None and (video.ndim != 5 or video.shape[0] not in (1, b)):
                 raise ValueError(f"`video` must be [v, 3, F, H, W] with v = 1 (one input video shared by all {b} videos) or v = b = {b} "
                                  f"(video k starts from row k), got {tuple(video.shape)}")
@@ -196,9 +205,8 @@ class S2VPipeline:
         out = []
         for name, x in (("guidance_scale", guidance_scale), ("num_inference_steps", num_inference_steps), ("strength", strength)):
             if isinstance(x, (list, tuple)):
-                for other, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
-                    if arg is not None:
-                        raise ValueError(f"`{name}` as a list together with `{other}`: CFG-parallel and Ulysses stay one video per call with scalars")
+                _one_gpu_only(cfg_parallel, ulysses, lambda other: f"`{name}` as a list together with `{other}`: CFG-parallel and Ulysses stay one video "
+                                                                   f"per call with scalars")
                 if len(x) != b:
                     raise ValueError(f"`{name}` is a list of {len(x)} entries for b = {b} videos: one entry per video (prompt-major), or a scalar for all")
                 if name == "strength" and video is None:
@@ -278,9 +286,8 @@ class S2VPipeline:
         if video is None:
             raise ValueError(f"`{what}` applies only together with `video`: masked video-to-video keeps the input video outside the mask "
                              f"(a {what} on a text-to-video call has nothing to keep)")
-        for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
-            if arg is not None:
-                raise ValueError(f"`{what}` together with `{name}`: the masked step runs on one GPU; CFG-parallel and Ulysses stay unmasked")
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`{what}` together with `{name}`: the masked step runs on one GPU; CFG-parallel and Ulysses "
+                                                          f"stay unmasked")
         m = mask[:, 0] if mask.ndim == 5 and mask.shape[1] == 1 else mask
         F, H, W = video.shape[2:]
         if m.ndim != 4 or tuple(m.shape[1:]) != (F, H, W):
@@ -296,9 +303,8 @@ class S2VPipeline:
         if per_video or videos_path:
             raise ValueError("`step_cache` together with per-video lists (or several input videos, which run per-video plans): videos on different "
                              "timesteps have different plans of full and reuse steps, and the batch runs one launch sequence")
-        for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
-            if arg is not None:
-                raise ValueError(f"`step_cache` together with `{name}`: the step cache runs on one GPU; CFG-parallel and Ulysses have their own forward")
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`step_cache` together with `{name}`: the step cache runs on one GPU; CFG-parallel and "
+                                                          f"Ulysses have their own forward")
         if not fused:
             raise ValueError("`step_cache` together with fused=False: the cache lives in the fused step; fused=False is the reference's seam sequence")
         if isinstance(step_cache, StepCache):
@@ -313,11 +319,6 @@ class S2VPipeline:
             raise ValueError(f"`step_cache`: the threshold must be >= 0, got {sc.threshold}")
         return sc
 
-    @staticmethod
-    def check_step_cache_length(sc, n):
-        if isinstance(sc, list) and len(sc) != n:
-            raise ValueError(f"`step_cache` is a list of {len(sc)} entries for the {n} steps this call runs: one boolean per step actually run")
-
     step_cache_report = None
     attention_maps = None
 
@@ -329,10 +330,8 @@ class S2VPipeline:
         if per_video or videos_path:
             raise ValueError("`attention_map` together with per-video lists (or several input videos, which run per-video plans): the maps are "
                              "collected on one plan of steps for the whole batch")
-        for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
-            if arg is not None:
-                raise ValueError(f"`attention_map` together with `{name}`: the map is collected on one GPU; CFG-parallel and Ulysses split the "
-                                 f"attention it reads")
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`attention_map` together with `{name}`: the map is collected on one GPU; CFG-parallel and "
+                                                          f"Ulysses split the attention it reads")
         if not fused:
             raise ValueError("`attention_map` together with fused=False: the map is collected inside the fused step; fused=False is the reference's "
                              "seam sequence")
@@ -364,27 +363,31 @@ class S2VPipeline:
         km = [0] * len(ts) if keep_max is None else keep_max
         return [scheduler.blend_record(ts[i + 1] if i + 1 < len(ts) else None, dtype, device, km[i]) for i in range(len(ts))]
 
-    @staticmethod
-    def _blend_torch(scheduler, latents, z0, noise0, keep, next_timestep):
-        """the blend of fused=False on latents [n,...] after the step: where keep (bool, broadcast over the channels) the input's latents
-        noised to next_timestep with the noise that started the loop, or, after the last step (None), the clean ones"""
-        proper = z0 if next_timestep is None else scheduler.add_noise(z0, noise0, next_timestep)
-        return torch.where(keep, proper, latents)
-
-    def prepare_video_latents(self, video, dtype, device, generator, timestep, parts=False):
-        """pipeline_cogvideox_video2video.py:345-398 for one video: the posterior sample of the encoded video, then the noise, both drawn
-        from `generator` in that order; add_noise(scaling_factor * z0, noise, timestep) * init_noise_sigma -> [1,Fl,C,h,w]; parts: also the
-        scaled z0 and the noise (what a masked call keeps)"""
-        vae = self.vae
-        z0 = vae.encode(video).latent_dist.sample(generator)              # [1,C,Fl,h,w]
+    def prepare_video_latents(self, video, dtype, device, generator, first_timesteps):
+        """pipeline_cogvideox_video2video.py:345-398 for b = len(first_timesteps) videos: video [v,3,F,H,W], v = b or one row shared by all.
+        One generator (or none): one posterior sample per video row in order, then the noise of all b videos in one draw.  A list: video k's
+        posterior sample and noise both come from generator k (a shared row is encoded once and sampled per generator).  The VAE encodes one
+        video at a time.  -> (add_noise(z0, noise, every video's own first timestep) * init_noise_sigma, z0, noise), each [b,Fl,C,h,w]: the
+        start of the loop, and the scaled clean latents and the noise that a masked call keeps"""
+        vae, b, v = self.vae, len(first_timesteps), video.shape[0]
         # the scaling as the reference writes it (and as video_generate.reference_latents does): torch's scalar semantics for the dtype
-        z0 = vae.config.scaling_factor * z0.to(dtype).permute(0, 2, 1, 3, 4).contiguous()  # [1,Fl,C,h,w]
-        gdev = generator.device if generator is not None else device
-        noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
-        latents = self.scheduler.add_noise(z0.to(device), noise, timestep)
-        if parts:
-            return latents * self.scheduler.init_noise_sigma, z0.to(device), noise
-        return latents * self.scheduler.init_noise_sigma
+        scaled = lambda z: vae.config.scaling_factor * z.to(dtype).permute(0, 2, 1, 3, 4).contiguous()   # [.,C,Fl,h,w] -> [.,Fl,C,h,w]
+        if isinstance(generator, (list, tuple)):
+            z0, noise, dist = [], [], None
+            for k, g in enumerate(generator):
+                if dist is None or v > 1:
+                    dist = vae.encode(video[k:k + 1]).latent_dist
+                z0.append(scaled(dist.sample(g)))
+                noise.append(torch.randn(z0[-1].shape, generator=g, device=g.device, dtype=dtype).to(device))
+            z0, noise = torch.cat(z0, dim=0), torch.cat(noise, dim=0)
+        else:
+            z0 = scaled(torch.cat([vae.encode(video[r:r + 1]).latent_dist.sample(generator) for r in range(v)], dim=0))
+            if v != b:
+                z0 = z0.expand(b, -1, -1, -1, -1).contiguous()
+            gdev = generator.device if generator is not None else device
+            noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
+        latents = self.scheduler.add_noise(z0.to(device), noise, torch.stack([torch.as_tensor(t) for t in first_timesteps]))
+        return latents * self.scheduler.init_noise_sigma, z0.to(device), noise
 
     @torch.no_grad()
     def __call__(self, prompt_embeds=None, negative_prompt_embeds=None, ref_img_states=None, height=480, width=720,
@@ -398,12 +401,13 @@ class S2VPipeline:
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
         generator k alone).  Every step runs the transformer on [negative x b | positive x b]; the result is [b,...].  cfg_parallel= and
         ulysses= stay one video per call.
-        Per video: guidance_scale, num_inference_steps and strength each take a scalar (one value for all, the path below) or a list with one
-        entry per video, prompt-major as generator lists are; video may have b rows, or one row shared by all b videos.  Video k then equals
-        the one-video call made with its own prompt, reference row, video row, generator, guidance scale, step count and strength: every video
-        runs the plan of that call (_call_videos), the batch shrinks as the shortest plans end, results come back in the caller's order.  The
-        step-end callback sees all b videos in the caller's order; its `t` is a [b] tensor once the active videos' timesteps differ (a
-        finished video keeps its last one).  Plans of different lengths under the DPM scheduler need a generator list.
+        Per video: guidance_scale, num_inference_steps and strength each take a scalar (one value for all) or a list with one entry per
+        video, prompt-major as generator lists are; video may have b rows, or one row shared by all b videos.  Video k then equals the
+        one-video call made with its own prompt, reference row, video row, generator, guidance scale, step count and strength: every video
+        runs the plan of that call (video_plan) in the one loop (_denoise), the batch shrinks as the shortest plans end, results come back in
+        the caller's order; scalars are b times one plan.  The step-end callback sees all b videos in the caller's order; its `t` is a [b]
+        tensor once the active videos' timesteps differ (a finished video keeps its last one).  `guidance_scale` reads as a list of b on a
+        call with a list or several input videos.  Plans of different lengths under the DPM scheduler need a generator list.
         cfg_parallel: a dist.CfgPair -- this process runs ONE sample of the CFG pair (slot 0: negative prompt, slot 1: prompt) on its GPU and its
         peer the other; every rank of the pair passes the SAME arguments (embeddings, reference latent, latents or an equally seeded generator) and
         returns the same latents / video bit for bit.  fused mode only.
@@ -493,44 +497,89 @@ class S2VPipeline:
             attention_map = self.check_attention_map(attention_map, self.transformer.config.num_layers,
                                                      getattr(self.transformer.config, "weight_format", None), per_video, cfg_parallel, ulysses,
                                                      fused, video is not None and b > 1)
-        if per_video or (video is not None and b > 1):   # every video on its own plan; scalars and one input video stay on the path below
-            lists = self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)
-            return self._call_videos(b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg,
-                                     generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
-                                     callback_on_step_end_tensor_inputs, video, num_videos_per_prompt, mask, paste_back, levels)
+        own_plans = per_video or (video is not None and b > 1)   # every video on the plan of its own one-video call
+        per = [(guidance_scale, num_inference_steps, strength)]   # a call with scalars: one plan, built once and shared by all b videos
+        if own_plans:
+            per = list(zip(*self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)))
+        plans = [self.video_plan(self.scheduler, n, st if video is not None else None, g, use_dynamic_cfg, self.transformer.dtype) for g, n, st in per]
+        self.check_plans(plans, self.scheduler, generator)
+        return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
+                             num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
+                             callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
+                             step_cache, attention_map)
+
+    def _denoise(self, plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator, latents,
+                 output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video,
+                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map):
+        """the one denoise loop: b = len(plans) videos, each on its video_plan; iteration i applies step i of every video that still has one.
+        The videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers;
+        when the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
+        latents stay where they are.  Results, and everything the callback sees, are in the caller's order.  A call with scalars is b times
+        the same plan: the order is the caller's and the batch never shrinks.
+        own_plans: the call asked for per-video plans -- `guidance_scale` then reads as a list of b; step_cache and attention_map, which
+        follow ONE plan of steps, and cfg_parallel / ulysses, which run one video, were refused with it.
+        mask [1 | b,F,H,W] (check_mask): z0, noise0 and the latent masks follow the internal order and the shrinking prefix exactly as the
+        latents do; video k blends at the next timestep of its own plan and is flagged on its own last step.  levels: the mask is a change
+        map, and video k keeps the cells of level <= change_map_plan(n_k)[i] after its step i, n_k the steps of its own plan"""
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
-        text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)  # [negative x b | positive x b] (:196)
-        sch.set_timesteps(num_inference_steps, device="cpu")
-        timesteps = sch.timesteps
+        b = len(plans)
+        order, inverse = self.plan_order(plans)
+        lens = [len(plans[k]["steps"]) for k in order]
+        if isinstance(step_cache, list) and len(step_cache) != lens[0]:
+            raise ValueError(f"`step_cache` is a list of {len(step_cache)} entries for the {lens[0]} steps this call runs: one boolean per step "
+                             f"actually run")
+        moved = order != list(range(b))
+        internal = lambda x: x[order].contiguous() if moved else x.contiguous()   # caller's order -> internal order
+        callers = lambda x: x[inverse] if moved else x                            # and back
+        is_dpm = isinstance(sch, CogVideoXDPMScheduler)
+        gen_list = isinstance(generator, (list, tuple))
+        gens = [generator[k] for k in order] if gen_list else None
+        text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)  # [negative x b | positive x b] (:196), caller's order
+        sch.set_timesteps(plans[order[0]]["num_inference_steps"], device="cpu")   # the object is left on the longest video's count
         if video is not None:
-            timesteps, num_inference_steps = self.get_timesteps(num_inference_steps, timesteps, strength, sch.order)
-            if len(timesteps) == 0:
-                raise ValueError(f"strength {strength} keeps none of the {sch.num_inference_steps} timesteps")
-            self.check_step_cache_length(step_cache, len(timesteps))
-            latents, z0, noise0 = self.prepare_video_latents(video, dt, dev, generator, timesteps[:1], parts=True)
-            latents = latents.to(dt).contiguous()
+            latents, z0, noise0 = self.prepare_video_latents(video, dt, dev, generator, [p["timesteps"][0] for p in plans])
         else:
-            self.check_step_cache_length(step_cache, len(timesteps))
-            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b).to(dt).contiguous()
+            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b)
+        latents = internal(latents.to(dt))   # internal order from here on
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
         ref = ref_img_states.to(dev, dt)
-        # the seam's eval=True wants one reference row per video (:503-504); one shared row is repeated (the engine maps it itself)
-        ref_seam = ref if ref.shape[0] == b else ref.expand(b, -1, -1, -1, -1).contiguous()
-        is_dpm = isinstance(sch, CogVideoXDPMScheduler)
+        if ref.shape[0] > 1:
+            ref = internal(ref)
         rope = ref_rope = None
         if tr.config.use_rotary_positional_embeddings:
             cos, sin = tables.rope_tables(height, width, F)
             n = (H // 2) * (W // 2)
             cos, sin = torch.from_numpy(cos).to(dev), torch.from_numpy(sin).to(dev)
             ref_rope, rope = (cos[:n], sin[:n]), (cos[n:], sin[n:])
-        paste = None
-        if mask is not None:   # one video (several go through _call_videos): its blend operands, held for the whole call
+        paste = blends = None
+        if mask is not None:   # the blend operands, held for the whole call
             lat_mask, pix_mask = (map_to_latent if levels else mask_to_latent)(mask, dev)
-            z0, noise0 = z0.to(dt).contiguous(), noise0.to(dt).contiguous()
-            keep_max = change_map_plan(len(timesteps)) if levels else [0] * len(timesteps)   # step i keeps the cells of level <= keep_max[i]
-            nexts = [timesteps[i + 1] if i + 1 < len(timesteps) else None for i in range(len(timesteps))]
             paste = (video, pix_mask) if paste_back else None
+            if lat_mask.shape[0] != b:
+                lat_mask = lat_mask.expand(b, -1, -1, -1)
+            z0, noise0, lat_mask = internal(z0.to(dt)), internal(noise0.to(dt)), internal(lat_mask)
+            # step i of the video at position p keeps the cells of level <= keep_max[p][i]
+            keep_max = [change_map_plan(len(plans[k]["timesteps"])) if levels else [0] * len(plans[k]["timesteps"]) for k in order]
+            blends = [self.blend_plan(sch, plans[k], dt, dev, keep_max[p]) for p, k in enumerate(order)]
+
+        def active_text(a):   # [negative x a | positive x a] of the first a videos; CFG-parallel: this rank's half of the one pair
+            neg, pos = text.chunk(2)
+            pair = torch.cat([neg[order[:a]], pos[order[:a]]], dim=0).contiguous()
+            return pair if cfg_parallel is None else pair[cfg_parallel.slot:cfg_parallel.slot + 1]
+
+        def active_ref(a, rows):   # the engine maps one shared row itself; the seam's eval=True wants a rows (:503-504)
+            if ref.shape[0] > 1:
+                return ref[:a]
+            return ref.expand(a, -1, -1, -1, -1).contiguous() if rows else ref
+
+        def set_active(a):
+            # CFG-parallel: B = 1 with this rank's half of [negative | positive] (custom_cogvideox_pipe.py:196) and the un-duplicated reference tokens
+            eng.set_geometry(2 * a if cfg_parallel is None else 1, text.shape[1], F, H, W)
+            eng.prepare_tables(height, width)
+            eng.set_conditioning(active_text(a), active_ref(a, False))
+            if mask is not None:   # prefixes of the same buffers, as latents[:a] is
+                eng.set_blend(z0[:a], noise0[:a], lat_mask[:a])
 
         if ulysses is not None and cfg_parallel is not None:
             raise ValueError("ulysses and cfg_parallel do not compose yet: a Ulysses group runs both samples of the CFG pair on every rank")
@@ -543,58 +592,67 @@ class S2VPipeline:
             raise ValueError("cfg_parallel runs the fused step (one sample of the CFG pair per rank); fused=False is the reference's seam sequence")
         if cfg_parallel is not None:  # both ranks compute from the same inputs or the video is garbage: checked once, collectively
             cfg_parallel.assert_same(latents=latents, ref_img_states=ref, text=text)
+        x0_hist = noise = None
         if fused:
-            # CFG-parallel: B = 1 with this rank's half of [negative | positive] (custom_cogvideox_pipe.py:196) and the un-duplicated reference tokens
-            my_text = text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1]
-            eng.set_geometry(2 * b if cfg_parallel is None else 1, text.shape[1], F, H, W)
-            eng.prepare_tables(height, width)
-            eng.set_conditioning(my_text, ref)
-            x0_hist = torch.zeros(latents.shape, dtype=torch.float32, device=dev) if is_dpm else None
-            noise = torch.empty_like(latents) if is_dpm else None
-            if mask is not None:
-                eng.set_blend(z0, noise0, lat_mask)
+            set_active(b)
+            if is_dpm:
+                x0_hist, noise = torch.zeros(latents.shape, dtype=torch.float32, device=dev), torch.empty_like(latents)
         sc_plan = None
         if step_cache is not None:   # the whole plan on the host, before the loop: no read-back inside it, a captured step stays a replay
             if isinstance(step_cache, list):
                 sc_plan = step_cache
             else:
-                sc_plan = step_cache_plan(eng.time_embedding([float(t) for t in timesteps]), step_cache.threshold, step_cache.coefficients,
-                                          step_cache.keep_first, step_cache.keep_last)
+                sc_plan = step_cache_plan(eng.time_embedding([float(t) for t in plans[0]["timesteps"]]), step_cache.threshold,
+                                          step_cache.coefficients, step_cache.keep_first, step_cache.keep_last)
             self.step_cache_report = {"plan": list(sc_plan), "full": 0, "reused": 0, "ran_full": []}
         am_steps = am_skipped = None
         am_ran = []   # the steps that did collect (an interrupted call ends early)
         if attention_map is not None:   # the steps that collect, on the host, before the loop
-            am_steps, am_skipped = attention_map_plan(attention_map, len(timesteps), sc_plan)
+            am_steps, am_skipped = attention_map_plan(attention_map, lens[0], sc_plan)
             for sp in attention_map.text_spans:
                 if sp[1] > text.shape[1]:
                     raise ValueError(f"`attention_map`: the text span {sp!r} reaches beyond the {text.shape[1]} prompt tokens")
             if eng.fp8_qk_active:
                 raise ValueError("`attention_map` while fp8 QK^T is active at this geometry ('fp8-auto' beyond its token threshold): the map needs "
                                  "16-bit attention (None or 'fp8')")
-        old = None
+        active = b
+        old = [None] * b   # fused=False under DPM: every video's x0 of its last step
+        last_t = [plans[k]["timesteps"][0] for k in order]
+        seam_key = seam_text = seam_ref = None   # the seam re-conditions when its tensors change: new ones only when the rows or the text do
         try:
             if sc_plan is not None:
                 eng.step_cache_enable(True)
             if attention_map is not None:
                 eng.attn_map_enable(True, attention_map.text_spans)
-            for i, t in enumerate(timesteps):
+            for i in range(lens[0]):
                 if self.interrupt:
                     break
-                g = guidance_scale
-                if use_dynamic_cfg:
-                    g = 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - i) / num_inference_steps) ** 5.0)) / 2)
-                self._guidance_scale = g
+                a = sum(1 for n_k in lens if n_k > i)
+                if a != active:   # the shortest plans have ended: the batch shrinks to the videos that go on
+                    active = a
+                    if fused:
+                        set_active(a)
+                steps = [plans[order[p]]["steps"][i] for p in range(a)]
+                for p, st in enumerate(steps):
+                    last_t[p] = st["t"]
+                if own_plans:   # a finished video keeps its last value
+                    self._guidance_scale = [plans[k]["steps"][min(i, len(plans[k]["steps"]) - 1)]["guidance"] for k in range(b)]
+                else:
+                    self._guidance_scale = steps[0]["guidance"]
                 if fused:
-                    if is_dpm:
-                        coef = sch.coef(t, timesteps[i - 1] if i > 0 else None, i == 0, dt, g)
-                        self._draw(noise, generator)
-                        if coef.kind == 2:
-                            self._draw(noise, generator)  # the reference discards its first draw on multistep steps
-                    else:
-                        coef = sch.coef(t, dt, g)
+                    if is_dpm and gen_list:   # video p draws from its own generator, as often as its one-video call does at this step
+                        for p, st in enumerate(steps):
+                            for _ in range(st["draws"]):   # the reference discards its first draw on multistep steps
+                                self._draw(noise[p:p + 1], gens[p])
+                    elif is_dpm:
+                        for _ in range(steps[0]["draws"]):
+                            self._draw(noise[:a], generator)
+                    ts, coefs = [float(st["t"]) for st in steps], [st["coef"] for st in steps]
                     if ulysses is not None:
-                        ulysses.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
-                    elif cfg_parallel is None:
+                        ulysses.step(eng, latents, ts[0], coefs[0], x0_hist, noise, use_graph)
+                    elif cfg_parallel is not None:
+                        cfg_parallel.step(eng, latents, ts[0], coefs[0], x0_hist, noise, use_graph)
+                    else:
                         cache = None
                         if sc_plan is not None:
                             rep = self.step_cache_report
@@ -606,48 +664,58 @@ class S2VPipeline:
                                 rep["ran_full"].append(i)
                             rep["reused" if cache == "reuse" else "full"] += 1
                         collect = am_steps is not None and i in am_steps and cache != "reuse"
-                        eng.denoise_step(latents, float(t), coef, x0_hist, noise, use_graph,
-                                         blend=None if mask is None else sch.blend_record(nexts[i], dt, dev, keep_max[i]), cache=cache,
+                        eng.denoise_step(latents[:a], ts, coefs, x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph,
+                                         blend=None if mask is None else [blends[p][i] for p in range(a)], cache=cache,
                                          attn_layers=attention_map.layers if collect else None)
                         if collect:
                             am_ran.append(i)
-                    else:
-                        cfg_parallel.step(eng, latents, float(t), coef, x0_hist, noise, use_graph)
                 else:
-                    x = torch.cat([latents] * 2)
-                    x = sch.scale_model_input(x, t)
-                    noise_pred = tr(hidden_states=x, encoder_hidden_states=text, ref_img_states=ref_seam,
-                                    timestep=t.expand(2 * b), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
+                    x = torch.cat([latents[:a]] * 2)
+                    if seam_key is None or seam_key[0] != a or seam_key[1] is not text:
+                        seam_key, seam_text, seam_ref = (a, text), active_text(a), active_ref(a, True)
+                    noise_pred = tr(hidden_states=x, encoder_hidden_states=seam_text, ref_img_states=seam_ref,
+                                    timestep=torch.stack([st["t"] for st in steps]).repeat(2), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
                                     return_dict=False, eval=True)[0].float()
                     u, c = noise_pred.chunk(2)
-                    noise_pred = u + g * (c - u)
-                    if not is_dpm:
-                        latents = sch.step(noise_pred, t, latents, return_dict=False)[0]
-                    else:
-                        latents, old = sch.step(noise_pred, old, t, timesteps[i - 1] if i > 0 else None, latents,
-                                                generator=generator, return_dict=False)
-                    latents = latents.to(dt)
-                    if mask is not None:
-                        keep = (lat_mask <= keep_max[i])[:, :, None]   # [1,Fl,1,h,w]: fused=False's select
-                        latents = self._blend_torch(sch, latents, z0, noise0, keep, nexts[i])
-                if callback_on_step_end is not None:
-                    # custom_cogvideox_pipe.py:298-305: the callback sees the requested tensors -- `prompt_embeds` is, at that point of
-                    # the reference loop, the CONCATENATED [negative | positive] pair (:196) -- and what it returns replaces them for
-                    # the following steps (a returned `negative_prompt_embeds` is rebound there too, but nothing reads it after :196).
-                    # A callback that returns nothing keeps everything (the reference would raise on `None.get`).
-                    avail = {"latents": latents, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
-                    outs = callback_on_step_end(self, i, t, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
-                    new_lat = outs.get("latents", latents)
-                    if new_lat is not latents:
-                        if fused:  # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
-                            latents.copy_(new_lat.to(dev, dt).reshape(latents.shape))
+                    drawn = None
+                    if is_dpm and not gen_list:   # one stream: the noise of all videos in one draw, the last of this step's draws
+                        for _ in range(steps[0]["draws"]):
+                            drawn = randn_videos(latents[:a].shape, generator, dev, dt)
+                    for p, st in enumerate(steps):   # the one-video call's own sequence on video p
+                        n_k = plans[order[p]]["num_inference_steps"]
+                        np_p = u[p:p + 1] + st["guidance"] * (c[p:p + 1] - u[p:p + 1])
+                        if not is_dpm:
+                            new = sch.step(np_p, st["t"], latents[p:p + 1], return_dict=False, num_inference_steps=n_k)[0]
                         else:
-                            latents = new_lat.to(dev, dt)
+                            new, old[p] = sch.step(np_p, old[p], st["t"], st["t_back"], latents[p:p + 1], generator=gens[p] if gen_list else None,
+                                                   variance_noise=None if drawn is None else drawn[p:p + 1], return_dict=False,
+                                                   num_inference_steps=n_k)
+                        new = new.to(dt)
+                        if mask is not None:   # fused=False's select: where kept, the input's latents noised to the video's next timestep with
+                            # the noise that started the loop, or, after its last step, the clean ones
+                            ts_p = plans[order[p]]["timesteps"]
+                            keep = (lat_mask[p:p + 1] <= keep_max[p][i])[:, :, None]   # [1,Fl,1,h,w], broadcast over the channels
+                            proper = z0[p:p + 1] if i + 1 == len(ts_p) else sch.add_noise(z0[p:p + 1], noise0[p:p + 1], ts_p[i + 1])
+                            new = torch.where(keep, proper, new)
+                        latents[p:p + 1] = new
+                if callback_on_step_end is not None:
+                    # custom_cogvideox_pipe.py:298-305 over all b videos in the caller's order: the callback sees the requested tensors --
+                    # `prompt_embeds` is, at that point of the reference loop, the CONCATENATED [negative | positive] pair (:196) -- and what it
+                    # returns replaces them for the following steps (a returned `negative_prompt_embeds` is rebound there too, but nothing reads
+                    # it after :196).  A callback that returns nothing keeps everything (the reference would raise on `None.get`).  `t` is the
+                    # 0-dim timestep while the active videos share it, otherwise [b] timesteps (a finished video keeps its last one)
+                    t_cb = steps[0]["t"] if all(int(st["t"]) == int(steps[0]["t"]) for st in steps) else torch.stack([last_t[inverse[k]] for k in range(b)])
+                    shown = callers(latents)
+                    avail = {"latents": shown, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
+                    outs = callback_on_step_end(self, i, t_cb, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
+                    new_lat = outs.get("latents", shown)
+                    if new_lat is not shown:   # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
+                        latents.copy_(internal(new_lat.to(dev, dt).reshape(shown.shape)))
                     new_text = outs.get("prompt_embeds", text)
                     if new_text is not text:
                         text = new_text.to(dev, dt)
-                        if fused:  # the hoisted text projection follows the new embeddings
-                            eng.set_conditioning(text if cfg_parallel is None else text[cfg_parallel.slot:cfg_parallel.slot + 1], ref)
+                        if fused:  # the hoisted text projection of the active rows follows the new embeddings
+                            eng.set_conditioning(active_text(active), active_ref(active, False))
                     negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
             if attention_map is not None:
                 self.attention_maps = self._read_attention_maps(eng, attention_map, b, am_ran, am_skipped)
@@ -658,7 +726,7 @@ class S2VPipeline:
                 eng.step_cache_enable(False)
             if attention_map is not None and eng.geometry is not None:
                 eng.attn_map_enable(False)
-        return self._finish(latents, fused, output_type, return_dict, paste)
+        return self._finish(callers(latents), fused, output_type, return_dict, paste)
 
     @staticmethod
     def _read_attention_maps(eng, am, b, steps, skipped):
@@ -696,178 +764,6 @@ class S2VPipeline:
             else:
                 video = self.vae.postprocess_video(video, output_type, keep=paste[0], pixel_mask=paste[1])
         return (video,) if not return_dict else {"frames": video}
-
-    def prepare_videos_latents(self, video, dtype, device, generator, first_timesteps, parts=False):
-        """pipeline_cogvideox_video2video.py:374-392 for b = len(first_timesteps) videos: video [v,3,F,H,W], v = b or one row shared by all.
-        One generator (or none): one posterior sample per video row in order, then the noise of all b videos in one draw.  A list: video k's
-        posterior sample and noise both come from generator k (a shared row is encoded once and sampled per generator).  add_noise at every
-        video's own first timestep; the VAE encodes one video at a time -> [b,Fl,C,h,w]; parts: also the scaled z0 and the noise of the b videos"""
-        vae, b, v = self.vae, len(first_timesteps), video.shape[0]
-        scaled = lambda z: vae.config.scaling_factor * z.to(dtype).permute(0, 2, 1, 3, 4).contiguous()   # as prepare_video_latents writes it
-        if isinstance(generator, (list, tuple)):
-            z0, noise, dist = [], [], None
-            for k, g in enumerate(generator):
-                if dist is None or v > 1:
-                    dist = vae.encode(video[k:k + 1]).latent_dist
-                z0.append(scaled(dist.sample(g)))
-                noise.append(torch.randn(z0[-1].shape, generator=g, device=g.device, dtype=dtype).to(device))
-            z0, noise = torch.cat(z0, dim=0), torch.cat(noise, dim=0)
-        else:
-            z0 = scaled(torch.cat([vae.encode(video[r:r + 1]).latent_dist.sample(generator) for r in range(v)], dim=0))
-            if v != b:
-                z0 = z0.expand(b, -1, -1, -1, -1).contiguous()
-            gdev = generator.device if generator is not None else device
-            noise = torch.randn(z0.shape, generator=generator, device=gdev, dtype=dtype).to(device)
-        latents = self.scheduler.add_noise(z0.to(device), noise, torch.stack([torch.as_tensor(t) for t in first_timesteps]))
-        if parts:
-            return latents * self.scheduler.init_noise_sigma, z0.to(device), noise
-        return latents * self.scheduler.init_noise_sigma
-
-    def _call_videos(self, b, lists, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, use_dynamic_cfg, generator,
-                     latents, output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, video,
-                     num_videos_per_prompt, mask=None, paste_back=True, levels=False):
-        """b videos, each on the plan of its one-video call (video_plan): iteration i applies step i of every video that still has one.  The
-        videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers; when
-        the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
-        latents stay where they are.  Results, and everything the callback sees, are in the caller's order.
-        mask [1 | b,F,H,W] (check_mask): z0, noise0 and the latent masks follow the internal order and the shrinking prefix exactly as the latents
-        do; video k blends at the next timestep of its own plan and is flagged on its own last step.  levels: the mask is a change map, and
-        video k keeps the cells of level <= change_map_plan(n_k)[i] after its step i, n_k the steps of its own plan"""
-        tr, sch = self.transformer, self.scheduler
-        dt, dev = tr.dtype, tr.device
-        guidance, counts, strengths = lists
-        plans = [self.video_plan(sch, counts[k], strengths[k] if video is not None else None, guidance[k], use_dynamic_cfg, dt) for k in range(b)]
-        self.check_plans(plans, sch, generator)
-        order, inverse = self.plan_order(plans)
-        eng = tr.engine
-        is_dpm = isinstance(sch, CogVideoXDPMScheduler)
-        gen_list = isinstance(generator, (list, tuple))
-        text = cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt).to(dev, dt)   # caller's order, what the callback sees
-        if video is not None:
-            latents = self.prepare_videos_latents(video, dt, dev, generator, [p["timesteps"][0] for p in plans], parts=mask is not None)
-            if mask is not None:
-                latents, z0, noise0 = latents
-        else:
-            latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b)
-        latents = latents.to(dt)[order].contiguous()   # internal order from here on
-        F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
-        paste = None
-        if mask is not None:
-            lat_mask, pix_mask = (map_to_latent if levels else mask_to_latent)(mask, dev)
-            paste = (video, pix_mask) if paste_back else None
-            if lat_mask.shape[0] != b:
-                lat_mask = lat_mask.expand(b, -1, -1, -1)
-            z0, noise0, lat_mask = z0.to(dt)[order].contiguous(), noise0.to(dt)[order].contiguous(), lat_mask[order].contiguous()
-            keep_max = [change_map_plan(len(plans[k]["timesteps"])) if levels else [0] * len(plans[k]["timesteps"]) for k in order]
-            blends = [self.blend_plan(sch, plans[k], dt, dev, keep_max[p]) for p, k in enumerate(order)]
-        ref = ref_img_states.to(dev, dt)
-        if ref.shape[0] > 1:
-            ref = ref[order].contiguous()
-        gens = [generator[k] for k in order] if gen_list else None
-        rope = ref_rope = None
-        if tr.config.use_rotary_positional_embeddings:
-            cos, sin = tables.rope_tables(height, width, F)
-            n = (H // 2) * (W // 2)
-            cos, sin = torch.from_numpy(cos).to(dev), torch.from_numpy(sin).to(dev)
-            ref_rope, rope = (cos[:n], sin[:n]), (cos[n:], sin[n:])
-
-        def active_text(a):   # [negative x a | positive x a] of the first a videos
-            neg, pos = text.chunk(2)
-            return torch.cat([neg[order[:a]], pos[order[:a]]], dim=0).contiguous()
-
-        def active_ref(a, rows):   # the engine maps one shared row itself; the seam's eval=True wants a rows
-            if ref.shape[0] > 1:
-                return ref[:a]
-            return ref.expand(a, -1, -1, -1, -1).contiguous() if rows else ref
-
-        def set_active(a):
-            eng.set_geometry(2 * a, text.shape[1], F, H, W)
-            eng.prepare_tables(height, width)
-            eng.set_conditioning(active_text(a), active_ref(a, False))
-            if mask is not None:   # prefixes of the same buffers, as latents[:a] is
-                eng.set_blend(z0[:a], noise0[:a], lat_mask[:a])
-
-        lens = [len(plans[k]["steps"]) for k in order]
-        active = b
-        if fused:
-            set_active(b)
-            x0_hist = torch.zeros(latents.shape, dtype=torch.float32, device=dev) if is_dpm else None
-            noise = torch.empty_like(latents) if is_dpm else None
-        old = [None] * b
-        last_t = [plans[k]["timesteps"][0] for k in order]
-        seam_key = seam_text = seam_ref = None   # the seam re-conditions when its tensors change: new ones only when the rows or the text do
-        try:
-            for i in range(lens[0]):
-                if self.interrupt:
-                    break
-                a = sum(1 for n_k in lens if n_k > i)
-                if a != active:   # the shortest plans have ended: the batch shrinks to the videos that go on
-                    active = a
-                    if fused:
-                        set_active(a)
-                steps = [plans[order[p]]["steps"][i] for p in range(a)]
-                for p, st in enumerate(steps):
-                    last_t[p] = st["t"]
-                self._guidance_scale = [plans[k]["steps"][min(i, len(plans[k]["steps"]) - 1)]["guidance"] for k in range(b)]
-                if fused:
-                    if is_dpm and gen_list:   # video p draws from its own generator, as often as its one-video call does at this step
-                        for p, st in enumerate(steps):
-                            for _ in range(st["draws"]):
-                                self._draw(noise[p:p + 1], gens[p])
-                    elif is_dpm:
-                        for _ in range(steps[0]["draws"]):
-                            self._draw(noise[:a], generator)
-                    eng.denoise_step(latents[:a], [float(st["t"]) for st in steps], [st["coef"] for st in steps],
-                                     x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph,
-                                     blend=None if mask is None else [blends[p][i] for p in range(a)])
-                else:
-                    x = torch.cat([latents[:a]] * 2)
-                    if seam_key is None or seam_key[0] != a or seam_key[1] is not text:
-                        seam_key, seam_text, seam_ref = (a, text), active_text(a), active_ref(a, True)
-                    noise_pred = tr(hidden_states=x, encoder_hidden_states=seam_text, ref_img_states=seam_ref,
-                                    timestep=torch.stack([st["t"] for st in steps]).repeat(2), image_rotary_emb=rope, ref_image_rotary_emb=ref_rope,
-                                    return_dict=False, eval=True)[0].float()
-                    u, c = noise_pred.chunk(2)
-                    drawn = None
-                    if is_dpm and not gen_list:   # one stream: the noise of all videos in one draw, the last of this step's draws
-                        for _ in range(steps[0]["draws"]):
-                            drawn = randn_videos(latents[:a].shape, generator, dev, dt)
-                    for p, st in enumerate(steps):   # the one-video call's own sequence on video p
-                        n_k = plans[order[p]]["num_inference_steps"]
-                        np_p = u[p:p + 1] + st["guidance"] * (c[p:p + 1] - u[p:p + 1])
-                        if not is_dpm:
-                            new = sch.step(np_p, st["t"], latents[p:p + 1], return_dict=False, num_inference_steps=n_k)[0]
-                        else:
-                            new, old[p] = sch.step(np_p, old[p], st["t"], st["t_back"], latents[p:p + 1], generator=gens[p] if gen_list else None,
-                                                   variance_noise=None if drawn is None else drawn[p:p + 1], return_dict=False,
-                                                   num_inference_steps=n_k)
-                        new = new.to(dt)
-                        if mask is not None:
-                            ts_p = plans[order[p]]["timesteps"]
-                            keep = (lat_mask[p:p + 1] <= keep_max[p][i])[:, :, None]   # [1,Fl,1,h,w]: fused=False's select
-                            new = self._blend_torch(sch, new, z0[p:p + 1], noise0[p:p + 1], keep, ts_p[i + 1] if i + 1 < len(ts_p) else None)
-                        latents[p:p + 1] = new
-                if callback_on_step_end is not None:
-                    # the contract of the scalar path over all b videos in the caller's order; `t` is the 0-dim timestep while the active videos
-                    # share it, otherwise [b] timesteps (a finished video keeps its last one)
-                    t_cb = steps[0]["t"] if all(int(st["t"]) == int(steps[0]["t"]) for st in steps) else torch.stack([last_t[inverse[k]] for k in range(b)])
-                    shown = latents[inverse]
-                    avail = {"latents": shown, "prompt_embeds": text, "negative_prompt_embeds": negative_prompt_embeds}
-                    outs = callback_on_step_end(self, i, t_cb, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}
-                    new_lat = outs.get("latents", shown)
-                    if new_lat is not shown:   # the step (and its captured graph) updates ONE buffer in place: keep it, take the values
-                        latents.copy_(new_lat.to(dev, dt).reshape(shown.shape)[order])
-                    new_text = outs.get("prompt_embeds", text)
-                    if new_text is not text:
-                        text = new_text.to(dev, dt)
-                        if fused:  # the hoisted text projection of the active rows follows the new embeddings
-                            eng.set_conditioning(active_text(active), active_ref(active, False))
-                    negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
-        finally:
-            if fused and mask is not None:
-                eng.clear_blend()
-        sch.set_timesteps(plans[order[0]]["num_inference_steps"], device="cpu")   # the object is left on the longest video's count
-        return self._finish(latents[inverse].contiguous(), fused, output_type, return_dict, paste)
 
     @staticmethod
     def _draw(buf, generator):

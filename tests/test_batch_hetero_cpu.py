@@ -23,7 +23,7 @@ def _coef_bytes(c):
 
 
 def _one_video_sequence(s2v, kind, n, strength, guidance, dynamic):
-    """what S2VPipeline.__call__ does for ONE video with scalars (pipeline.py, the scalar path), written out on a scheduler of its own"""
+    """what S2VPipeline.__call__ does for ONE video with scalars (the reference's loop, custom_cogvideox_pipe.py:237-296), written out on a scheduler of its own"""
     sch = _sched(s2v, kind)
     sch.set_timesteps(n, device="cpu")
     ts, n_loop = sch.timesteps, n

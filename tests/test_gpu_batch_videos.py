@@ -284,6 +284,50 @@ def test_pipeline_two_prompts_two_videos_each_equal_four_single_calls_bitwise(s2
     pipe.transformer.engine.close()
 
 
+_LOOP = {}
+
+
+def _two_videos_one_stream_written_out(s2v):
+    """what a call with scalars, two videos, the DPM scheduler and ONE generator does, written out: prepare_latents once for both videos, then
+    per step the coefficients, as many draws of the whole [2,...] noise as the step's kind says (the last one counts) and one scalar step"""
+    if not _LOOP:
+        pos, neg, ref = _pipe_inputs(s2v)
+        dt = torch.bfloat16
+        pipe = _pipe(s2v, "dpm", dt)
+        sch, eng = pipe.scheduler, pipe.transformer.engine
+        g = torch.Generator().manual_seed(977)
+        lat = pipe.prepare_latents(PF, PH, PW, dt, DEV, g, None, 2).to(dt).contiguous()
+        sch.set_timesteps(4)
+        eng.set_geometry(4, PT, lat.shape[1], PH // 8, PW // 8)
+        eng.prepare_tables(PH, PW)
+        eng.set_conditioning(torch.cat([neg, pos]), ref[:2])
+        x0, kinds = torch.zeros(lat.shape, dtype=torch.float32, device=DEV), []
+        for i, t in enumerate(sch.timesteps):
+            coef = sch.coef(t, sch.timesteps[i - 1] if i > 0 else None, i == 0, dt, 6.0)
+            kinds.append(coef.kind)
+            for _ in range(2 if coef.kind == 2 else 1):
+                noise = s2v.pipeline.randn_videos(lat.shape, g, DEV, dt).contiguous()
+            eng.denoise_step(lat, float(t), coef, x0, noise, use_graph=False)
+        torch.cuda.synchronize()
+        assert kinds == [1, 2, 2, 1], "the two multistep steps draw twice and discard the first draw"
+        eng.close()
+        _LOOP["latents"] = lat.clone()
+    return _LOOP["latents"]
+
+
+@pytest.mark.parametrize("mode", ["fused-graph", "seams"])
+def test_pipeline_two_videos_with_scalars_and_one_dpm_stream_equal_the_written_out_loop_bitwise(s2v, mode):
+    pos, neg, ref = _pipe_inputs(s2v)
+    exp = _two_videos_one_stream_written_out(s2v)
+    pipe = _pipe(s2v, "dpm", torch.bfloat16)
+    out = pipe(prompt_embeds=pos, negative_prompt_embeds=neg, ref_img_states=ref[:2], generator=torch.Generator().manual_seed(977), height=PH,
+               width=PW, num_frames=PF, num_inference_steps=4, guidance_scale=6.0, fused=mode != "seams", use_graph=mode != "seams")["frames"]
+    assert pipe.guidance_scale == 6.0 and isinstance(pipe.guidance_scale, float)
+    assert tuple(out.shape) == (2, 2, 16, PH // 8, PW // 8) and torch.equal(out, exp)
+    assert not torch.equal(out[0], out[1])
+    pipe.transformer.engine.close()
+
+
 def test_pipeline_callback_on_one_video_leaves_the_others_alone_and_frames_are_decoded_per_video(s2v):
     pos, neg, ref = _pipe_inputs(s2v)
     dt = torch.bfloat16

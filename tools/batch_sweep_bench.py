@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""What a sweep costs as ONE batched call against one call per video (S2VPipeline with per-video lists: pipeline.py, _call_videos).
+"""What a sweep costs as ONE batched call against one call per video (S2VPipeline with per-video lists: every video on its own plan in the one loop of pipeline.py).
 
 The sweep: one input video at strength 0.4 / 0.6 / 0.8 / 1.0 and `--steps` (50) inference steps, DDIM, bf16, hipGraph -- plans of 20 / 30 / 40 / 50
 steps, 140 video-steps.  The one call holds 4 videos for 20 steps, then 3, 2 and 1 for 10 steps each, and re-sets geometry, tables and
