@@ -111,17 +111,21 @@ static int make_conv(s2v_vae* v, ConvL& c, const std::string& name, int cin, int
     v->slots[name + ".bias"] = VSlot{0, c.b, cout, 1, 1, false};
     return 0;
 }
-static int make_snorm(s2v_vae* v, SNormL& n, const std::string& name, int C) {
+// decoder: CogVideoXSpatialNorm3D (GroupNorm under ".norm_layer." and the conv_y / conv_b tables over zq); encoder: nn.GroupNorm alone
+static int make_norm(s2v_vae* v, SNormL& n, const std::string& name, int C) {
     n.C = C;
+    const bool spatial = !v->encoder;
     const int Cz = v->Cz;
     S2V_TRY(wmalloc(v, &n.gn_w, (int64_t)C * v->esz));
     S2V_TRY(wmalloc(v, &n.gn_b, (int64_t)C * v->esz));
+    const std::string gn = name + (spatial ? ".norm_layer" : "");
+    v->slots[gn + ".weight"] = VSlot{0, n.gn_w, C, 1, 1, false};
+    v->slots[gn + ".bias"] = VSlot{0, n.gn_b, C, 1, 1, false};
+    if (!spatial) return 0;
     S2V_TRY(wmalloc(v, &n.wy, (int64_t)C * Cz * 4));
     S2V_TRY(wmalloc(v, &n.wb, (int64_t)C * Cz * 4));
     S2V_TRY(wmalloc(v, &n.by, (int64_t)C * 4));
     S2V_TRY(wmalloc(v, &n.bb, (int64_t)C * 4));
-    v->slots[name + ".norm_layer.weight"] = VSlot{0, n.gn_w, C, 1, 1, false};
-    v->slots[name + ".norm_layer.bias"] = VSlot{0, n.gn_b, C, 1, 1, false};
     v->slots[name + ".conv_y.conv.weight"] = VSlot{2, n.wy, C, Cz, 1, false};
     v->slots[name + ".conv_b.conv.weight"] = VSlot{2, n.wb, C, Cz, 1, false};
     v->slots[name + ".conv_y.conv.bias"] = VSlot{3, n.by, C, 1, 1, false};
@@ -130,21 +134,19 @@ static int make_snorm(s2v_vae* v, SNormL& n, const std::string& name, int C) {
 }
 static int make_resnet(s2v_vae* v, ResnetL& r, const std::string& name, int cin, int cout, int level) {
     r.cin = cin; r.cout = cout; r.has_sc = cin != cout;
-    S2V_TRY(make_snorm(v, r.n1, name + ".norm1", cin));
+    S2V_TRY(make_norm(v, r.n1, name + ".norm1", cin));
     S2V_TRY(make_conv(v, r.c1, name + ".conv1.conv", cin, cout, 3, level));
-    S2V_TRY(make_snorm(v, r.n2, name + ".norm2", cout));
+    S2V_TRY(make_norm(v, r.n2, name + ".norm2", cout));
     S2V_TRY(make_conv(v, r.c2, name + ".conv2.conv", cout, cout, 3, level));
     if (r.has_sc) S2V_TRY(make_conv(v, r.sc, name + ".conv_shortcut", cin, cout, 0, level));
     return 0;
 }
 
 extern "C" void s2v_vae_destroy(s2v_vae* v) {
-    if (v) {
-        for (auto st_ : v->side) (void)hipStreamDestroy(st_);
-        for (auto e : v->ev_side) (void)hipEventDestroy(e);
-        if (v->ev_fork) (void)hipEventDestroy(v->ev_fork);
-    }
     if (!v) return;
+    for (auto st_ : v->side) (void)hipStreamDestroy(st_);
+    for (auto e : v->ev_side) (void)hipEventDestroy(e);
+    if (v->ev_fork) (void)hipEventDestroy(v->ev_fork);
     (void)hipDeviceSynchronize();
     for (void* p : v->allocs) (void)hipFree(p);
     for (void* p : v->geo_allocs) (void)hipFree(p);
@@ -202,15 +204,57 @@ static int build_decoder(s2v_vae* v) {
             level++;
         }
     }
-    if (!r) r = make_snorm(v, v->norm_out, "decoder.norm_out", rc[nb - 1]);
+    if (!r) r = make_norm(v, v->norm_out, "decoder.norm_out", rc[nb - 1]);
     if (!r) r = make_conv(v, v->conv_out, "decoder.conv_out.conv", rc[nb - 1], cfg->out_channels, 3, level);
     return r;
 }
 
-extern "C" int s2v_vae_create(const s2v_vae_config* cfg, s2v_vae** out) {
-    S2V_REQUIRE(cfg && out, "s2v_vae_create: null argument");
-    S2V_REQUIRE(cfg->dtype == S2V_DTYPE_F32 || cfg->dtype == S2V_DTYPE_BF16 || cfg->dtype == S2V_DTYPE_F16, "s2v_vae_create: unsupported dtype");
-    S2V_REQUIRE(cfg->num_blocks >= 1 && cfg->num_blocks <= 6, "s2v_vae_create: 1..6 blocks");
+// The encoder's plan (CogVideoXEncoder3D, autoencoder_kl_cogvideox.py:755-814: conv_in, DownBlock3D x4 of plain-GroupNorm resnets +
+// CogVideoXDownsample3D, MidBlock3D, norm_out, conv_out): stages[0 .. nb-1] = down blocks (StageL::up is the stride-2 downsampler conv),
+// stages[nb] = mid block; ConvL::level l works at (tile height >> l) x (tile width >> l).
+static int build_encoder(s2v_vae* v) {
+    const s2v_vae_config* cfg = &v->cfg;
+    const int nb = cfg->num_blocks;
+    const int tlevel = (int)std::lround(std::log2((double)cfg->temporal_compression_ratio));
+    int r = make_conv(v, v->conv_in, "encoder.conv_in.conv", cfg->out_channels, cfg->block_out_channels[0], 3, 0);
+    v->stages.resize(nb + 1);
+    char nm[128];
+    int prev = cfg->block_out_channels[0], level = 0;
+    for (int b = 0; b < nb && !r; ++b) {
+        StageL& s = v->stages[b];
+        const int co = cfg->block_out_channels[b];
+        s.res.resize(cfg->layers_per_block);
+        for (int i = 0; i < cfg->layers_per_block && !r; ++i) {
+            snprintf(nm, sizeof(nm), "encoder.down_blocks.%d.resnets.%d", b, i);
+            r = make_resnet(v, s.res[i], nm, i == 0 ? prev : co, co, level);
+        }
+        prev = co;
+        s.has_up = b != nb - 1;  // here: has a downsampler
+        s.compress_time = b < tlevel;
+        if (s.has_up && !r) {
+            snprintf(nm, sizeof(nm), "encoder.down_blocks.%d.downsamplers.0.conv", b);
+            r = make_conv(v, s.up, nm, co, co, 1, level);  // operand at the level it reads; output one level down
+            level++;
+        }
+    }
+    if (!r) {
+        v->stages[nb].res.resize(2);
+        for (int i = 0; i < 2 && !r; ++i) {
+            snprintf(nm, sizeof(nm), "encoder.mid_block.resnets.%d", i);
+            r = make_resnet(v, v->stages[nb].res[i], nm, prev, prev, level);
+        }
+    }
+    if (!r) r = make_norm(v, v->norm_out, "encoder.norm_out", prev);
+    if (!r) r = make_conv(v, v->conv_out, "encoder.conv_out.conv", prev, 2 * v->Cz, 3, level);
+    return r;
+}
+
+static int vae_create(const char* fn, const s2v_vae_config* cfg, s2v_vae** out, bool encoder) {
+    static thread_local std::string m;
+    auto bad = [&](const char* why) { m = std::string(fn) + ": " + why; return m.c_str(); };
+    S2V_REQUIRE(cfg && out, bad("null argument"));
+    S2V_REQUIRE(cfg->dtype == S2V_DTYPE_F32 || cfg->dtype == S2V_DTYPE_BF16 || cfg->dtype == S2V_DTYPE_F16, bad("unsupported dtype"));
+    S2V_REQUIRE(cfg->num_blocks >= 1 && cfg->num_blocks <= 6, bad("1..6 blocks"));
     s2v_vae* v = new s2v_vae();
     v->cfg = *cfg;
     v->dtype = cfg->dtype;
@@ -219,11 +263,16 @@ extern "C" int s2v_vae_create(const s2v_vae_config* cfg, s2v_vae** out) {
     v->Cz = cfg->latent_channels;
     v->mfma = cfg->dtype == S2V_DTYPE_BF16 && !cfg->force_simple;
     v->h16 = cfg->dtype == S2V_DTYPE_F16 && !cfg->force_simple;  // fp16: convolutions / shortcuts with cin % 64 == 0 on v_mfma_f32_32x32x16_f16 (gemm_f16)
-    const int r = build_two_pass(v, build_decoder);
+    v->encoder = encoder;
+    const int r = build_two_pass(v, encoder ? build_encoder : build_decoder);
     if (r) { s2v_vae_destroy(v); return r; }
     *out = v;
     return 0;
 }
+extern "C" int s2v_vae_create(const s2v_vae_config* cfg, s2v_vae** out) { return vae_create("s2v_vae_create", cfg, out, false); }
+// The reference-image / video ENCODE handle (src/video_generate.py:26-38): weights load through s2v_vae_load_weight
+// under the reference's "encoder.*" names and it is destroyed by s2v_vae_destroy.
+extern "C" int s2v_vae_enc_create(const s2v_vae_config* cfg, s2v_vae** out) { return vae_create("s2v_vae_enc_create", cfg, out, true); }
 
 /* One device range holding every weight of the handle (decoder or encoder), for the replica broadcast; a replica that
  * received it calls s2v_vae_mark_weights_loaded instead of s2v_vae_load_weight + s2v_vae_finalize. */
@@ -347,21 +396,36 @@ static void ws_activate(s2v_vae* v, int k) {
     ws_load(v, k);
 }
 
-// one workspace set (every operand / cache / scratch buffer of a decode at window th x tw) into the live members
-static int alloc_workspace_set(s2v_vae* v, int th, int tw, int fz_max) {
+// Conv c's operand at window th x tw (latents for the decoder, pixels for the encoder): the window at c's level (the decoder works up,
+// the encoder down) and fl[level] frames (the largest frame batch at that level), plus the two cache frames of a causal convolution
+struct Operand {
+    int64_t H, W, F, frames;  // F: frames with the cache
+    int64_t padded_bytes(const s2v_vae* v, const ConvL& c) const { return F * (H + 2) * (W + 2) * c.cin * v->esz; }
+    int64_t dense_bytes(const s2v_vae* v, const ConvL& c) const { return frames * H * W * std::max(c.cin, c.cout) * v->esz; }
+};
+static Operand operand_extent(const s2v_vae* v, const ConvL& c, int th, int tw, const int* fl) {
+    const int64_t H = v->encoder ? th >> c.level : (int64_t)th << c.level, W = v->encoder ? tw >> c.level : (int64_t)tw << c.level;
+    return {H, W, fl[c.level] + (c.kt == 3 ? 2 : 0), fl[c.level]};
+}
+// every conv's operand buffer and the three dense buffers for windows up to th x tw, into the live members
+static int alloc_operands(s2v_vae* v, int th, int tw, const int* fl) {
     int rc = 0;
     int64_t dmax = 0;
     for_each_conv(v, [&](ConvL& c) {
-        const int64_t H = (int64_t)th << c.level, W = (int64_t)tw << c.level;
-        const int F = v->fmax[c.level] + (c.kt == 3 ? 2 : 0);
-        c.pad_bytes = (int64_t)F * (H + 2) * (W + 2) * c.cin * v->esz + 1024;
+        const Operand o = operand_extent(v, c, th, tw, fl);
+        c.pad_bytes = o.padded_bytes(v, c) + 1024;
         if (!rc) rc = dmalloc(v, &c.pad, c.pad_bytes, true);
-        const int64_t d = (int64_t)v->fmax[c.level] * H * W * (c.cin > c.cout ? c.cin : c.cout) * v->esz;
-        dmax = d > dmax ? d : dmax;
+        dmax = std::max(dmax, o.dense_bytes(v, c));
     });
     if (rc) return rc;
     v->dense_bytes = dmax + (int64_t)256 * 1024 * v->esz;  // + one 128-row MFMA tile of slack
     for (int i = 0; i < 3; ++i) S2V_TRY(dmalloc(v, &v->dense[i], v->dense_bytes, true));
+    return 0;
+}
+
+// one workspace set (every operand / cache / scratch buffer of a decode at window th x tw) into the live members
+static int alloc_workspace_set(s2v_vae* v, int th, int tw, int fz_max) {
+    S2V_TRY(alloc_operands(v, th, tw, v->fmax));
     S2V_TRY(dmalloc(v, &v->zq, (int64_t)fz_max * th * tw * v->Cz * v->esz + 64, true));
     int cmax = 0;
     for_each_conv(v, [&](ConvL& c) { cmax = c.cin > cmax ? c.cin : cmax; });
@@ -410,9 +474,9 @@ static int prepare_tile_capacity(s2v_vae* v, int th, int tw, int fz_max, int nws
     {  // as many sets as 70 % of the free memory (and the optional byte cap) hold, never fewer than one
         int64_t set_bytes = 0, dmax = 0;
         for_each_conv(v, [&](ConvL& c) {
-            const int64_t H = (int64_t)th << c.level, W = (int64_t)tw << c.level;
-            set_bytes += (int64_t)(v->fmax[c.level] + (c.kt == 3 ? 2 : 0)) * (H + 2) * (W + 2) * c.cin * v->esz;
-            dmax = std::max(dmax, (int64_t)v->fmax[c.level] * H * W * std::max(c.cin, c.cout) * v->esz);
+            const Operand o = operand_extent(v, c, th, tw, v->fmax);
+            set_bytes += o.padded_bytes(v, c);
+            dmax = std::max(dmax, o.dense_bytes(v, c));
         });
         set_bytes += 3 * dmax;
         v->set_bytes = set_bytes;
@@ -479,7 +543,8 @@ static int set_layout(s2v_vae* v, int h, int w, hipStream_t st, bool ring_only =
     int rc = 0;
     for_each_conv(v, [&](ConvL& c) {
         if (rc) return;
-        if (ring_only) rc = launch_zero_border(c.pad, v->fmax[c.level] + (c.kt == 3 ? 2 : 0), h << c.level, w << c.level, c.cin, v->esz, st);
+        const Operand o = operand_extent(v, c, h, w, v->fmax);
+        if (ring_only) rc = launch_zero_border(c.pad, (int)o.F, (int)o.H, (int)o.W, c.cin, v->esz, st);
         else if (hipMemsetAsync(c.pad, 0, (size_t)c.pad_bytes, st) != hipSuccess) rc = -2;
     });
     if (rc) return vfail("clearing the operand borders failed");
@@ -497,6 +562,15 @@ static void vae_gemm_log(const GemmArgs& g, int epi, bool mfma, const char* kind
         if (FILE* f = fopen(lg, "a")) { fprintf(f, "%d %d %d %d %d %s\n", g.M, g.N, g.K, epi, (int)mfma, kind); fclose(f); }
 }
 #endif
+// the GEMM kernel of a convolution or a 1 x 1 shortcut: bf16 MFMA when the channel count fills its K tiles, fp16 MFMA where gemm_f16 takes
+// the shape, the generic kernel otherwise
+static bool gemm_is_bf16_mfma(const s2v_vae* v, const GemmArgs& g) { return v->mfma && (g.conv ? g.cin : g.K) % 64 == 0; }
+static int launch_gemm(s2v_vae* v, GemmArgs& g, int epi, hipStream_t st) {
+    if (gemm_is_bf16_mfma(v, g)) return launch_gemm_bf16(g, epi, st);  // cout = 3 (conv_out) without the direct kernel: one padded 128-column tile
+    if (v->h16 && gemm_f16_ok(g, epi)) return launch_gemm_f16(g, epi, st);
+    g.valu_only = v->cfg.force_simple;
+    return launch_gemm_simple(g, epi, v->dtype, st);
+}
 // direct_dst (conv_out only): the [C][Ftot][H][W] tile output -- when the direct small-N kernel qualifies (launch_conv_out_direct) it writes there
 // and *did_direct is set; otherwise the implicit GEMM writes `out` and the caller converts the layout
 static int run_conv(s2v_vae* v, ConvL& c, int F, int H, int W, bool first, int epi, const void* resid, void* out,
@@ -529,12 +603,9 @@ static int run_conv(s2v_vae* v, ConvL& c, int F, int H, int W, bool first, int e
         if (epi == EPI_BIAS_ADD && atoi(e) == 1) { epi = EPI_BIAS; g.R = nullptr; }
         if (epi == EPI_BIAS_ADD && atoi(e) == 2) g.R = (const char*)c.pad;  // some other resident buffer of at least M x cout elements
     }
-    if (!direct) vae_gemm_log(g, epi, v->mfma && c.cin % 64 == 0, "conv");
+    if (!direct) vae_gemm_log(g, epi, gemm_is_bf16_mfma(v, g), "conv");
 #endif
-    if (direct) {}  // conv_out ran as the direct kernel
-    else if (v->mfma && c.cin % 64 == 0) S2V_TRY(launch_gemm_bf16(g, epi, st));  // cout = 3 (conv_out) without the direct kernel: one padded 128-column tile
-    else if (v->h16 && gemm_f16_ok(g, epi)) S2V_TRY(launch_gemm_f16(g, epi, st));
-    else { g.valu_only = v->cfg.force_simple; S2V_TRY(launch_gemm_simple(g, epi, v->dtype, st)); }
+    if (!direct) S2V_TRY(launch_gemm(v, g, epi, st));  // otherwise conv_out ran as the direct kernel
     if (c.kt == 3) {  // conv cache: the last two frames of the operand become frames 0, 1 of the next batch (adjacent on both sides: one copy unless they overlap)
         if (F >= 2) S2V_CHECK_HIP(hipMemcpyAsync(c.pad, c.pad + (int64_t)F * fb, 2 * fb, hipMemcpyDeviceToDevice, st));
         else {
@@ -545,14 +616,37 @@ static int run_conv(s2v_vae* v, ConvL& c, int F, int H, int W, bool first, int e
     return 0;
 }
 
-static int run_snorm(s2v_vae* v, const SNormL& n, const void* x, int F, int H, int W, int Fz, int hz, int wz, void* out_pad,
-                     int f_off, hipStream_t st) {
+// GroupNorm statistics over the frame batch, then normalise + SiLU into the next conv's operand (frames 2.. of out_pad).  The decoder's handle
+// has the yt / bt tables of the spatial norm and passes the zq window (Fz, hz, wz); the encoder's has none (the kernel then applies plain
+// GroupNorm) and passes 1, 1, 1.
+struct ZqWin { int F, h, w; };
+static int run_norm(s2v_vae* v, const SNormL& n, const void* x, int F, int H, int W, ZqWin z, void* out_pad, hipStream_t st) {
     S2V_TRY(launch_gn_stats(x, (int64_t)F * H * W, n.C, v->G, v->sums, v->gn_part, v->dtype, st));
     SNormArgs a{};
     a.x = x; a.F = F; a.H = H; a.W = W; a.C = n.C; a.G = v->G; a.sums = v->sums; a.eps = v->cfg.norm_eps;
     a.gn_w = n.gn_w; a.gn_b = n.gn_b; a.wy = n.wy; a.by = n.by; a.wb = n.wb; a.bb = n.bb;
-    a.zq = v->zq; a.Fz = Fz; a.hz = hz; a.wz = wz; a.Cz = v->Cz; a.out = out_pad; a.f_off = f_off; a.silu = 1; a.yt = v->yt; a.bt = v->bt;
+    a.zq = v->zq; a.Fz = z.F; a.hz = z.h; a.wz = z.w; a.Cz = v->Cz; a.out = out_pad; a.f_off = 2; a.silu = 1; a.yt = v->yt; a.bt = v->bt;
     return launch_snorm_apply(a, v->dtype, st);
+}
+
+// one resnet on dense[cur] (scratch dense[t1], dense[t2]): norm, conv, norm, the 1 x 1 shortcut GEMM where the channel count changes, conv +
+// add; the result is in dense[cur] again (with a shortcut cur and t2 trade places)
+static int run_resnet(s2v_vae* v, ResnetL& r, int F, int H, int W, ZqWin z, bool first, int& cur, int t1, int& t2, hipStream_t st) {
+    S2V_TRY(run_norm(v, r.n1, v->dense[cur], F, H, W, z, r.c1.pad, st));
+    S2V_TRY(run_conv(v, r.c1, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st));
+    S2V_TRY(run_norm(v, r.n2, v->dense[t1], F, H, W, z, r.c2.pad, st));
+    if (!r.has_sc) return run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[cur], v->dense[cur], st);
+    GemmArgs g{};
+    g.A = v->dense[cur]; g.lda = r.cin; g.W = r.sc.w; g.ldw = r.cin; g.bias = r.sc.b;
+    g.C = v->dense[t2]; g.ldc = r.cout; g.M = F * H * W; g.N = r.cout; g.K = r.cin;
+    g.a_rows_padded = (int)rup64(g.M, 256);  // dense buffers carry a 256-row slack
+#ifdef S2V_DIAG
+    vae_gemm_log(g, EPI_BIAS, gemm_is_bf16_mfma(v, g), "shortcut");
+#endif
+    S2V_TRY(launch_gemm(v, g, EPI_BIAS, st));
+    S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[t2], v->dense[t2], st));
+    std::swap(cur, t2);
+    return 0;
 }
 
 // one decoder pass over a frame batch of `Fz` latent frames of an (h x w) latent window; writes its output frames
@@ -560,30 +654,11 @@ static int decode_batch(s2v_vae* v, int Fz, int h, int w, bool first, char* dst,
                         hipStream_t st) {
     int cur = 0, t1 = 1, t2 = 2;
     int F = Fz, H = h, W = w;
+    const ZqWin z{Fz, h, w};
     S2V_TRY(launch_dense_to_padded(v->zq, Fz, h, w, v->Cz, v->conv_in.pad, 2, v->dtype, st));
     S2V_TRY(run_conv(v, v->conv_in, F, H, W, first, EPI_BIAS, nullptr, v->dense[cur], st));
     for (auto& s : v->stages) {
-        for (auto& r : s.res) {
-            S2V_TRY(run_snorm(v, r.n1, v->dense[cur], F, H, W, Fz, h, w, r.c1.pad, 2, st));
-            S2V_TRY(run_conv(v, r.c1, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st));
-            S2V_TRY(run_snorm(v, r.n2, v->dense[t1], F, H, W, Fz, h, w, r.c2.pad, 2, st));
-            if (r.has_sc) {
-                GemmArgs g{};
-                g.A = v->dense[cur]; g.lda = r.cin; g.W = r.sc.w; g.ldw = r.cin; g.bias = r.sc.b;
-                g.C = v->dense[t2]; g.ldc = r.cout; g.M = F * H * W; g.N = r.cout; g.K = r.cin;
-                g.a_rows_padded = (int)rup64(g.M, 256);  // dense buffers carry a 256-row slack
-#ifdef S2V_DIAG
-                vae_gemm_log(g, EPI_BIAS, v->mfma && r.cin % 64 == 0, "shortcut");
-#endif
-                if (v->mfma && r.cin % 64 == 0) S2V_TRY(launch_gemm_bf16(g, EPI_BIAS, st));
-                else if (v->h16 && gemm_f16_ok(g, EPI_BIAS)) S2V_TRY(launch_gemm_f16(g, EPI_BIAS, st));
-                else { g.valu_only = v->cfg.force_simple; S2V_TRY(launch_gemm_simple(g, EPI_BIAS, v->dtype, st)); }
-                S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[t2], v->dense[t2], st));
-                std::swap(cur, t2);
-            } else {
-                S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[cur], v->dense[cur], st));
-            }
-        }
+        for (auto& r : s.res) S2V_TRY(run_resnet(v, r, F, H, W, z, first, cur, t1, t2, st));
         if (s.has_up) {
             S2V_TRY(launch_upsample(v->dense[cur], F, H, W, s.up.cin, s.compress_time, s.up.pad, v->dtype, st));
             F = up_frames(F, s.compress_time); H *= 2; W *= 2;
@@ -591,7 +666,7 @@ static int decode_batch(s2v_vae* v, int Fz, int h, int w, bool first, char* dst,
             std::swap(cur, t1);
         }
     }
-    S2V_TRY(run_snorm(v, v->norm_out, v->dense[cur], F, H, W, Fz, h, w, v->conv_out.pad, 2, st));
+    S2V_TRY(run_norm(v, v->norm_out, v->dense[cur], F, H, W, z, v->conv_out.pad, st));
     bool direct = false;
     S2V_TRY(run_conv(v, v->conv_out, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st, dst, Ftot, f0, &direct));
     if (!direct) S2V_TRY(launch_to_ncfhw(v->dense[t1], F, H, W, v->cfg.out_channels, dst, Ftot, f0, v->dtype, st));
@@ -599,9 +674,11 @@ static int decode_batch(s2v_vae* v, int Fz, int h, int w, bool first, char* dst,
     return 0;
 }
 
+// Frame batches of the reference (autoencoder_kl_cogvideox.py:1237-1245 decode, num_latent_frames_batch_size = 2; :1177-1202 _encode,
+// num_sample_frames_batch_size = 8): the first batch takes fbs + F % fbs frames, every later batch fbs; fewer than 2 fbs frames are one batch
+enum { DEC_FRAME_BATCH = 2, ENC_FRAME_BATCH = 8 };
 struct Batch { int s, e; };
-static std::vector<Batch> frame_batches(int F) {  // autoencoder_kl_cogvideox.py:1237-1245 (num_latent_frames_batch_size = 2)
-    const int fbs = 2;
+static std::vector<Batch> frame_batches(int F, int fbs) {
     const int nb = F / fbs > 1 ? F / fbs : 1, rem = F % fbs;
     std::vector<Batch> b;
     for (int i = 0; i < nb; ++i) b.push_back({fbs * i + (i == 0 ? 0 : rem), std::min(fbs * (i + 1) + rem, F)});
@@ -609,7 +686,7 @@ static std::vector<Batch> frame_batches(int F) {  // autoencoder_kl_cogvideox.py
 }
 static int out_frames_of(s2v_vae* v, int F) {
     int tot = 0;
-    for (auto b : frame_batches(F)) {
+    for (auto b : frame_batches(F, DEC_FRAME_BATCH)) {
         int f = b.e - b.s;
         for (size_t s = 1; s < v->stages.size(); ++s)
             if (v->stages[s].has_up) f = up_frames(f, v->stages[s].compress_time);
@@ -619,20 +696,72 @@ static int out_frames_of(s2v_vae* v, int F) {
 }
 static int spatial_scale(s2v_vae* v) { return 1 << (v->cfg.num_blocks - 1); }
 
-struct TileGeo { int tl_h, tl_w, ov_h, ov_w, bl_h, bl_w, lim_h, lim_w; };
-static TileGeo tile_geo(s2v_vae* v) {  // :1102-1114, 1400-1406 incl. the int() truncations
-    TileGeo t;
-    const int ts_h = v->cfg.sample_height / 2, ts_w = v->cfg.sample_width / 2, sc = spatial_scale(v);
-    t.tl_h = (int)((double)ts_h / sc); t.tl_w = (int)((double)ts_w / sc);
-    t.ov_h = (int)(t.tl_h * (1.0 - 1.0 / 6.0)); t.ov_w = (int)(t.tl_w * (1.0 - 1.0 / 5.0));
-    t.bl_h = (int)(ts_h * (1.0 / 6.0)); t.bl_w = (int)(ts_w * (1.0 / 5.0));
-    t.lim_h = ts_h - t.bl_h; t.lim_w = ts_w - t.bl_w;
-    return t;
+// The tiling of the reference's tiled_decode / tiled_encode (autoencoder_kl_cogvideox.py:1102-1114 the tile sizes, :1400-1406 / :1317-1323
+// overlap, blend extent and crop limit with their int() truncations, :1437-1450 / :1354-1367 the raster-order blend, crop and concatenation) --
+// one rule with input and output swapped.  Tiles are sample_size / 2 pixels = that / 2^(blocks - 1) latents; the decoder cuts latents and
+// pastes pixels, the encoder cuts pixels and pastes latents.  Tile origins step by the overlap, a fraction (5/6, 4/5) of the INPUT-side tile;
+// blend extent (1/6, 1/5) and crop limit (the rest) are fractions of the OUTPUT-side tile; edge tiles are whatever is left of the input, so a
+// blend takes no more rows than either neighbour has.  Pure arithmetic: no handle, no device (tests/test_vae_tile_plan_cpu.py).
+struct Tile {
+    int y, x, h, w;  // input window
+    int oh, ow;      // its output: h * scale decoding, h / scale encoding
+    int bv, bh;      // rows blended with the tile above, columns with the tile to the left (0: first row / column)
+    int ch, cw;      // crop of the blended output
+    int py, px;      // where the crop lands in the whole output
+};
+struct TilePlan { bool tiled = false; int rows = 1, cols = 1, out_h = 0, out_w = 0; std::vector<Tile> tiles; };  // tiles in raster order
+static bool vae_tile_plan(int sample_h, int sample_w, int num_blocks, bool encode, int H, int W, int tiling, TilePlan* p) {  // false: degenerate overlap
+    const int sc = 1 << (num_blocks - 1), ts_h = sample_h / 2, ts_w = sample_w / 2;
+    const int tl_h = (int)((double)ts_h / sc), tl_w = (int)((double)ts_w / sc);
+    const int in_h = encode ? ts_h : tl_h, in_w = encode ? ts_w : tl_w, to_h = encode ? tl_h : ts_h, to_w = encode ? tl_w : ts_w;
+    const int ov_h = (int)(in_h * (1.0 - 1.0 / 6.0)), ov_w = (int)(in_w * (1.0 - 1.0 / 5.0));
+    const int bl_h = (int)(to_h * (1.0 / 6.0)), bl_w = (int)(to_w * (1.0 / 5.0));
+    const int lim_h = to_h - bl_h, lim_w = to_w - bl_w;
+    auto out = [&](int n) { return encode ? n / sc : n * sc; };
+    *p = TilePlan();
+    p->tiled = tiling && (W > in_w || H > in_h);
+    if (!p->tiled) {
+        p->out_h = out(H); p->out_w = out(W);
+        p->tiles.push_back({0, 0, H, W, p->out_h, p->out_w, 0, 0, p->out_h, p->out_w, 0, 0});
+        return true;
+    }
+    if (ov_h <= 0 || ov_w <= 0) return false;
+    p->rows = (H + ov_h - 1) / ov_h; p->cols = (W + ov_w - 1) / ov_w;
+    for (int i = 0; i < H; i += ov_h) {
+        p->out_w = 0;
+        for (int j = 0; j < W; j += ov_w) {
+            Tile t{i, j, std::min(in_h, H - i), std::min(in_w, W - j)};
+            t.oh = out(t.h); t.ow = out(t.w);
+            t.bv = i > 0 ? std::min(std::min(p->tiles[p->tiles.size() - p->cols].oh, t.oh), bl_h) : 0;
+            t.bh = j > 0 ? std::min(std::min(p->tiles.back().ow, t.ow), bl_w) : 0;
+            t.ch = std::min(t.oh, lim_h); t.cw = std::min(t.ow, lim_w);
+            t.py = p->out_h; t.px = p->out_w;
+            p->out_w += t.cw;
+            p->tiles.push_back(t);
+        }
+        p->out_h += p->tiles.back().ch;
+    }
+    return true;
 }
-static bool use_tiles(s2v_vae* v, int h, int w, int tiling) {
-    TileGeo t = tile_geo(v);
-    return tiling && (w > t.tl_w || h > t.tl_h);
+static bool tile_plan_of(const s2v_vae* v, bool encode, int H, int W, int tiling, TilePlan* p) {
+    return vae_tile_plan(v->cfg.sample_height, v->cfg.sample_width, v->cfg.num_blocks, encode, H, W, tiling, p);
 }
+#ifdef S2V_DIAG
+// vae_tile_plan without a handle: head = {tiled, rows, cols, out_h, out_w}; tiles = the twelve fields of Tile, tile after tile, for at most max_tiles
+extern "C" __attribute__((visibility("default"))) int s2v_diag_vae_tile_plan(int32_t sample_h, int32_t sample_w, int32_t num_blocks, int32_t encode,
+                                                                              int32_t H, int32_t W, int32_t tiling, int32_t* head, int32_t* tiles,
+                                                                              int32_t max_tiles) {
+    S2V_REQUIRE(head && tiles && sample_h > 0 && sample_w > 0 && num_blocks >= 1 && num_blocks <= 6 && H >= 1 && W >= 1, "s2v_diag_vae_tile_plan: bad argument");
+    TilePlan p;
+    S2V_REQUIRE(vae_tile_plan(sample_h, sample_w, num_blocks, encode != 0, H, W, tiling, &p), "s2v_diag_vae_tile_plan: degenerate tile overlap");
+    S2V_REQUIRE((int64_t)p.tiles.size() <= max_tiles, "s2v_diag_vae_tile_plan: more tiles than the caller has room for");
+    const int32_t h5[5] = {p.tiled, p.rows, p.cols, p.out_h, p.out_w};
+    std::copy(h5, h5 + 5, head);
+    static_assert(sizeof(Tile) == 12 * sizeof(int32_t), "Tile is twelve ints");
+    std::copy((const int32_t*)p.tiles.data(), (const int32_t*)(p.tiles.data() + p.tiles.size()), tiles);
+    return 0;
+}
+#endif
 
 extern "C" int s2v_vae_workspace_info(s2v_vae* v, int32_t* sets, int64_t* bytes_per_set) {
     S2V_REQUIRE(v && sets && bytes_per_set, "s2v_vae_workspace_info: null argument");
@@ -645,14 +774,40 @@ extern "C" int s2v_vae_out_shape(s2v_vae* v, int32_t F, int32_t h, int32_t w, in
                                  int32_t* Wo) {
     S2V_REQUIRE(v && Fo && Ho && Wo && F >= 1 && h >= 1 && w >= 1, "s2v_vae_out_shape: bad argument");
     *Fo = out_frames_of(v, F);
-    const int sc = spatial_scale(v);
-    if (!use_tiles(v, h, w, tiling)) { *Ho = h * sc; *Wo = w * sc; return 0; }
-    TileGeo t = tile_geo(v);
-    S2V_REQUIRE(t.ov_h > 0 && t.ov_w > 0, "s2v_vae_out_shape: degenerate tile overlap");
-    int H = 0, W = 0;
-    for (int i = 0; i < h; i += t.ov_h) H += std::min(std::min(t.tl_h, h - i) * sc, t.lim_h);
-    for (int j = 0; j < w; j += t.ov_w) W += std::min(std::min(t.tl_w, w - j) * sc, t.lim_w);
-    *Ho = H; *Wo = W;
+    TilePlan p;
+    S2V_REQUIRE(tile_plan_of(v, false, h, w, tiling, &p), "s2v_vae_out_shape: degenerate tile overlap");
+    *Ho = p.out_h; *Wo = p.out_w;
+    return 0;
+}
+
+// per-tile outputs [C][Fo][oh][ow] of a tiled call (re-allocated only when the tiling or the output frame count changes)
+static int ensure_tile_buffers(s2v_vae* v, const TilePlan& p, int C, int Fo) {
+    const size_t nt = p.tiles.size();
+    bool same = v->tiles.size() == nt && v->tiles_F == Fo;
+    for (size_t k = 0; same && k < nt; ++k) same = v->tile_h[k] == p.tiles[k].oh && v->tile_w[k] == p.tiles[k].ow;
+    if (same) return 0;
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    for (char* q : v->tiles) (void)hipFree(q);
+    v->tiles.assign(nt, nullptr); v->tile_h.assign(nt, 0); v->tile_w.assign(nt, 0);
+    for (size_t k = 0; k < nt; ++k) {
+        v->tile_h[k] = p.tiles[k].oh; v->tile_w[k] = p.tiles[k].ow;
+        S2V_CHECK_HIP(hipMalloc((void**)&v->tiles[k], (size_t)C * Fo * v->tile_h[k] * v->tile_w[k] * v->esz + 16));
+    }
+    v->tiles_F = Fo;
+    return 0;
+}
+// raster-order in-place blends (neighbours are read already blended), then crop + paste into the whole output; a tile is CF planes of oh x ow
+static int blend_and_paste(s2v_vae* v, const TilePlan& p, int CF, void* out, hipStream_t st) {
+    for (size_t k = 0; k < p.tiles.size(); ++k) {
+        const Tile& t = p.tiles[k];
+        for (int vertical = 1; vertical >= 0; --vertical) {
+            const int E = vertical ? t.bv : t.bh;
+            if (E <= 0) continue;
+            const size_t ka = vertical ? k - p.cols : k - 1;
+            S2V_TRY(launch_blend(v->tiles[ka], p.tiles[ka].oh, p.tiles[ka].ow, v->tiles[k], t.oh, t.ow, CF, E, vertical, v->dtype, st));
+        }
+        S2V_TRY(launch_paste(v->tiles[k], t.oh, t.ow, t.ch, t.cw, out, p.out_h, p.out_w, t.py, t.px, CF, v->dtype, st));
+    }
     return 0;
 }
 
@@ -662,7 +817,7 @@ static int decode_window(s2v_vae* v, const char* lat, int F, int h, int w, int y
     const float inv_sf = scaled ? (float)(1.0 / (double)v->cfg.scaling_factor) : 1.0f;
     int f0 = 0;
     bool first = true;
-    for (auto b : frame_batches(F)) {
+    for (auto b : frame_batches(F, DEC_FRAME_BATCH)) {
         const int Fz = b.e - b.s;
         S2V_TRY(launch_latent_to_zq(lat + (int64_t)b.s * v->Cz * h * w * v->esz, Fz, v->Cz, h, w, inv_sf, v->zq, y0, x0, th,
                                     tw, v->dtype, st));
@@ -681,47 +836,27 @@ extern "C" int s2v_vae_decode(s2v_vae* v, const void* latents, int32_t F, int32_
     S2V_REQUIRE(v->finalized, "s2v_vae_decode: weights not finalized");
     S2V_REQUIRE(F >= 1 && h >= 1 && w >= 1, "s2v_vae_decode: bad geometry");
     hipStream_t st = (hipStream_t)stream;
-    const int sc = spatial_scale(v);
     const int Ftot = out_frames_of(v, F);
     int fz_max = 0;
-    for (auto b : frame_batches(F)) fz_max = std::max(fz_max, b.e - b.s);
-    if (!use_tiles(v, h, w, tiling)) {
+    for (auto b : frame_batches(F, DEC_FRAME_BATCH)) fz_max = std::max(fz_max, b.e - b.s);
+    TilePlan p;
+    S2V_REQUIRE(tile_plan_of(v, false, h, w, tiling, &p), "s2v_vae_decode: degenerate tile overlap");
+    if (!p.tiled) {
         S2V_TRY(prepare_tile_capacity(v, h, w, fz_max));
         ws_activate(v, 0);
         return decode_window(v, (const char*)latents, F, h, w, 0, 0, h, w, (char*)out, Ftot, scaled, st);
     }
-    TileGeo t = tile_geo(v);
-    S2V_REQUIRE(t.ov_h > 0 && t.ov_w > 0, "s2v_vae_decode: degenerate tile overlap");
-    std::vector<int> is, js;
-    for (int i = 0; i < h; i += t.ov_h) is.push_back(i);
-    for (int j = 0; j < w; j += t.ov_w) js.push_back(j);
-    const size_t nt = is.size() * js.size();
+    const size_t nt = p.tiles.size();
     // tiles in flight: 49 x 480 x 720 at the real widths measured 928 / 684 / 602 / 605 / 554 / 590 ms with 1 / 2 / 3 / 4 / 6 / 9 sets
     // (profiles/r03_vae_tiles_in_flight.txt; round 6: 505-510 ms with six); up to six, as many as the byte cap of prepare_tile_capacity holds (a set
     // sized for a 30 x 45-latent tile is 5.5 GB: all six)
     int nws_cap = 6;
     if (const char* e = getenv("S2V_VAE_TILES_IN_FLIGHT")) nws_cap = std::max(1, atoi(e));
     int nws = (int)std::min<size_t>(nt, (size_t)nws_cap);
-    S2V_TRY(prepare_tile_capacity(v, std::min(t.tl_h, h), std::min(t.tl_w, w), fz_max, nws));
+    S2V_TRY(prepare_tile_capacity(v, p.tiles[0].h, p.tiles[0].w, fz_max, nws));  // the first tile is the largest
     nws = std::min(nws, (int)v->ws.size());
     const int C = v->cfg.out_channels;
-    // per-tile outputs [C][Ftot][8 th][8 tw] (re-allocated only when the tiling changes)
-    bool realloc_tiles = v->tiles.size() != nt || v->tiles_F != Ftot;
-    for (size_t k = 0; !realloc_tiles && k < nt; ++k) {
-        const int th = std::min(t.tl_h, h - is[k / js.size()]), tw = std::min(t.tl_w, w - js[k % js.size()]);
-        if (v->tile_h[k] != th * sc || v->tile_w[k] != tw * sc) realloc_tiles = true;
-    }
-    if (realloc_tiles) {
-        S2V_CHECK_HIP(hipDeviceSynchronize());
-        for (char* p : v->tiles) (void)hipFree(p);
-        v->tiles.assign(nt, nullptr); v->tile_h.assign(nt, 0); v->tile_w.assign(nt, 0);
-        for (size_t k = 0; k < nt; ++k) {
-            const int th = std::min(t.tl_h, h - is[k / js.size()]), tw = std::min(t.tl_w, w - js[k % js.size()]);
-            v->tile_h[k] = th * sc; v->tile_w[k] = tw * sc;
-            S2V_CHECK_HIP(hipMalloc((void**)&v->tiles[k], (size_t)C * Ftot * th * sc * tw * sc * v->esz));
-        }
-        v->tiles_F = Ftot;
-    }
+    S2V_TRY(ensure_tile_buffers(v, p, C, Ftot));
     // tile k runs on workspace set k mod nws: set 0 on the caller's stream, the others on side streams forked from it and joined
     // before the blends (tiles of one set serialise on its stream: they share its buffers)
     if (nws > 1) S2V_CHECK_HIP(hipEventRecord(v->ev_fork, st));
@@ -729,44 +864,17 @@ extern "C" int s2v_vae_decode(s2v_vae* v, const void* latents, int32_t F, int32_
     // raster order, round-robin over the sets (largest-tile-first onto the least loaded set measured the same at 3-4 sets and 18 % worse
     // at 6: what overlaps well is a big tile's chip-filling GEMMs with a small tile's latency-bound ones, which raster order pairs up)
     for (size_t k = 0; k < nt; ++k) {
-        const int i = is[k / js.size()], j = js[k % js.size()];
+        const Tile& t = p.tiles[k];
         const int q = (int)(k % nws);
         ws_activate(v, q);
-        S2V_TRY(decode_window(v, (const char*)latents, F, h, w, i, j, v->tile_h[k] / sc, v->tile_w[k] / sc, v->tiles[k], Ftot, scaled,
-                              q == 0 ? st : v->side[q - 1]));
+        S2V_TRY(decode_window(v, (const char*)latents, F, h, w, t.y, t.x, t.h, t.w, v->tiles[k], Ftot, scaled, q == 0 ? st : v->side[q - 1]));
     }
     ws_activate(v, 0);
     for (int q = 1; q < nws; ++q) {
         S2V_CHECK_HIP(hipEventRecord(v->ev_side[q - 1], v->side[q - 1]));
         S2V_CHECK_HIP(hipStreamWaitEvent(st, v->ev_side[q - 1], 0));
     }
-    // raster-order in-place blends, then crop + concatenate (:1437-1450)
-    int32_t Fo, Ho, Wo;
-    S2V_TRY(s2v_vae_out_shape(v, F, h, w, 1, &Fo, &Ho, &Wo));
-    int y0 = 0;
-    for (size_t r = 0; r < is.size(); ++r) {
-        int x0 = 0, ch = 0;
-        for (size_t c = 0; c < js.size(); ++c) {
-            const size_t k = r * js.size() + c;
-            const int Ht = v->tile_h[k], Wt = v->tile_w[k];
-            if (r > 0) {
-                const size_t ka = (r - 1) * js.size() + c;
-                const int E = std::min(std::min(v->tile_h[ka], Ht), t.bl_h);
-                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, C * Ftot, E, 1, v->dtype, st));
-            }
-            if (c > 0) {
-                const size_t ka = k - 1;
-                const int E = std::min(std::min(v->tile_w[ka], Wt), t.bl_w);
-                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, C * Ftot, E, 0, v->dtype, st));
-            }
-            ch = std::min(Ht, t.lim_h);
-            const int cw = std::min(Wt, t.lim_w);
-            S2V_TRY(launch_paste(v->tiles[k], Ht, Wt, ch, cw, out, Ho, Wo, y0, x0, C * Ftot, v->dtype, st));
-            x0 += cw;
-        }
-        y0 += ch;
-    }
-    return 0;
+    return blend_and_paste(v, p, C * Ftot, out, st);
 }
 
 extern "C" int s2v_vae_postprocess_u8(const void* video, int32_t C, int32_t F, int32_t H, int32_t W, uint8_t* out, int32_t dtype,
@@ -802,96 +910,9 @@ extern "C" int s2v_vae_postprocess(const void* video, int32_t C, int32_t F, int3
 }
 
 // =====================================================================================================================
-// Reference-image ENCODE (src/video_generate.py:26-38): one frame through CogVideoXEncoder3D
-// (autoencoder_kl_cogvideox.py:755-814: conv_in, DownBlock3D x4 of plain-GroupNorm resnets + CogVideoXDownsample3D,
-// MidBlock3D, norm_out, conv_out), untiled or tiled (:1177-1203, 1300-1372), moments out; the posterior sample is
-// s2v_vae_gaussian_sample.  The handle is an s2v_vae whose plan was built by s2v_vae_enc_create: weights load through
-// s2v_vae_load_weight under the reference's "encoder.*" names and it is destroyed by s2v_vae_destroy.
-// Plan layout: stages[0 .. nb-1] = down blocks (StageL::up is the stride-2 downsampler conv), stages[nb] = mid block;
-// ConvL::level l works at (tile height >> l) x (tile width >> l).
-static int make_gn(s2v_vae* v, SNormL& n, const std::string& name, int C) {
-    n.C = C;
-    S2V_TRY(wmalloc(v, &n.gn_w, (int64_t)C * v->esz));
-    S2V_TRY(wmalloc(v, &n.gn_b, (int64_t)C * v->esz));
-    v->slots[name + ".weight"] = VSlot{0, n.gn_w, C, 1, 1, false};
-    v->slots[name + ".bias"] = VSlot{0, n.gn_b, C, 1, 1, false};
-    return 0;
-}
-static int make_resnet_gn(s2v_vae* v, ResnetL& r, const std::string& name, int cin, int cout, int level) {
-    r.cin = cin; r.cout = cout; r.has_sc = cin != cout;
-    S2V_TRY(make_gn(v, r.n1, name + ".norm1", cin));
-    S2V_TRY(make_conv(v, r.c1, name + ".conv1.conv", cin, cout, 3, level));
-    S2V_TRY(make_gn(v, r.n2, name + ".norm2", cout));
-    S2V_TRY(make_conv(v, r.c2, name + ".conv2.conv", cout, cout, 3, level));
-    if (r.has_sc) S2V_TRY(make_conv(v, r.sc, name + ".conv_shortcut", cin, cout, 0, level));
-    return 0;
-}
+// ENCODE of the reference image or a video (AutoencoderKLCogVideoX._encode / tiled_encode, autoencoder_kl_cogvideox.py:1177-1203, 1300-1372)
+// on a handle of s2v_vae_enc_create, untiled or tiled, moments out; the posterior sample is s2v_vae_gaussian_sample.
 
-static int build_encoder(s2v_vae* v) {
-    const s2v_vae_config* cfg = &v->cfg;
-    const int nb = cfg->num_blocks;
-    const int tlevel = (int)std::lround(std::log2((double)cfg->temporal_compression_ratio));
-    int r = make_conv(v, v->conv_in, "encoder.conv_in.conv", cfg->out_channels, cfg->block_out_channels[0], 3, 0);
-    v->stages.resize(nb + 1);
-    char nm[128];
-    int prev = cfg->block_out_channels[0], level = 0;
-    for (int b = 0; b < nb && !r; ++b) {
-        StageL& s = v->stages[b];
-        const int co = cfg->block_out_channels[b];
-        s.res.resize(cfg->layers_per_block);
-        for (int i = 0; i < cfg->layers_per_block && !r; ++i) {
-            snprintf(nm, sizeof(nm), "encoder.down_blocks.%d.resnets.%d", b, i);
-            r = make_resnet_gn(v, s.res[i], nm, i == 0 ? prev : co, co, level);
-        }
-        prev = co;
-        s.has_up = b != nb - 1;  // here: has a downsampler
-        s.compress_time = b < tlevel;
-        if (s.has_up && !r) {
-            snprintf(nm, sizeof(nm), "encoder.down_blocks.%d.downsamplers.0.conv", b);
-            r = make_conv(v, s.up, nm, co, co, 1, level);  // operand at the level it reads; output one level down
-            level++;
-        }
-    }
-    if (!r) {
-        v->stages[nb].res.resize(2);
-        for (int i = 0; i < 2 && !r; ++i) {
-            snprintf(nm, sizeof(nm), "encoder.mid_block.resnets.%d", i);
-            r = make_resnet_gn(v, v->stages[nb].res[i], nm, prev, prev, level);
-        }
-    }
-    if (!r) r = make_gn(v, v->norm_out, "encoder.norm_out", prev);
-    if (!r) r = make_conv(v, v->conv_out, "encoder.conv_out.conv", prev, 2 * v->Cz, 3, level);
-    return r;
-}
-
-extern "C" int s2v_vae_enc_create(const s2v_vae_config* cfg, s2v_vae** out) {
-    S2V_REQUIRE(cfg && out, "s2v_vae_enc_create: null argument");
-    S2V_REQUIRE(cfg->dtype == S2V_DTYPE_F32 || cfg->dtype == S2V_DTYPE_BF16 || cfg->dtype == S2V_DTYPE_F16, "s2v_vae_enc_create: unsupported dtype");
-    S2V_REQUIRE(cfg->num_blocks >= 1 && cfg->num_blocks <= 6, "s2v_vae_enc_create: 1..6 blocks");
-    s2v_vae* v = new s2v_vae();
-    v->cfg = *cfg;
-    v->dtype = cfg->dtype;
-    v->esz = cfg->dtype == S2V_DTYPE_F32 ? 4 : 2;
-    v->G = cfg->norm_num_groups;
-    v->Cz = cfg->latent_channels;
-    v->mfma = cfg->dtype == S2V_DTYPE_BF16 && !cfg->force_simple;
-    v->h16 = cfg->dtype == S2V_DTYPE_F16 && !cfg->force_simple;  // fp16: convolutions / shortcuts with cin % 64 == 0 on v_mfma_f32_32x32x16_f16 (gemm_f16)
-    v->encoder = true;
-    const int r = build_two_pass(v, build_encoder);
-    if (r) { s2v_vae_destroy(v); return r; }
-    *out = v;
-    return 0;
-}
-
-// Encoder frame batches (AutoencoderKLCogVideoX._encode, autoencoder_kl_cogvideox.py:1177-1202; num_sample_frames_batch_size = 8):
-// the first batch takes 8 + F % 8 frames, every later batch 8; one frame is one batch of one
-static std::vector<Batch> enc_frame_batches(int F) {
-    const int fbs = 8;
-    const int nb = F / fbs > 1 ? F / fbs : 1, rem = F % fbs;
-    std::vector<Batch> b;
-    for (int i = 0; i < nb; ++i) b.push_back({fbs * i + (i == 0 ? 0 : rem), std::min(fbs * (i + 1) + rem, F)});
-    return b;
-}
 // CogVideoXDownsample3D with compress_time: frame pairs averaged, the first frame kept alone when the count is odd
 static int down_frames(int F, int ct) { return !ct ? F : ((F & 1) ? (F + 1) / 2 : F / 2); }
 // frames at every level of one encoder pass over Fb input frames
@@ -903,7 +924,7 @@ static void enc_level_frames(s2v_vae* v, int Fb, int* fl) {
 }
 static int enc_latent_frames(s2v_vae* v, int F) {
     int tot = 0, fl[8];
-    for (auto b : enc_frame_batches(F)) {
+    for (auto b : frame_batches(F, ENC_FRAME_BATCH)) {
         enc_level_frames(v, b.e - b.s, fl);
         int lv = 0;
         for (auto& s : v->stages) lv += s.has_up ? 1 : 0;
@@ -929,31 +950,11 @@ static int enc_prepare(s2v_vae* v, int TH, int TW, int Fb = 1) {
     for (int i = 0; i < 8; ++i) v->fmax[i] = 0;
     int fl[8] = {0};
     enc_level_frames(v, Fb, fl);
-    int rc = 0;
-    int64_t dmax = 0;
-    for_each_conv(v, [&](ConvL& c) {
-        const int64_t H = TH >> c.level, W = TW >> c.level;
-        const int F = fl[c.level] + (c.kt == 3 ? 2 : 0);  // the downsampler's operand holds the pooled frames: at most fl[level]
-        c.pad_bytes = (int64_t)F * (H + 2) * (W + 2) * c.cin * v->esz + 1024;
-        if (!rc) rc = dmalloc(v, &c.pad, c.pad_bytes, true);
-        dmax = std::max(dmax, (int64_t)fl[c.level] * H * W * std::max(c.cin, c.cout) * v->esz);
-    });
-    if (rc) return rc;
-    v->dense_bytes = dmax + (int64_t)256 * 1024 * v->esz;
-    for (int i = 0; i < 3; ++i) S2V_TRY(dmalloc(v, &v->dense[i], v->dense_bytes, true));
+    S2V_TRY(alloc_operands(v, TH, TW, fl));  // the downsampler's operand holds the pooled frames: at most fl[level]
     S2V_TRY(dmalloc(v, &v->gn_part, gn_stats_scratch_bytes((int64_t)Fb * TH * TW, v->G) + 64, true));
     v->th = TH; v->tw = TW;
     for (int i = 0; i < 8; ++i) v->fmax[i] = fl[i];
     return 0;
-}
-
-static int run_gn_plain(s2v_vae* v, const SNormL& n, const void* x, int F, int H, int W, void* out_pad, int f_off, hipStream_t st) {
-    S2V_TRY(launch_gn_stats(x, (int64_t)F * H * W, n.C, v->G, v->sums, v->gn_part, v->dtype, st));  // statistics over the frame batch
-    SNormArgs a{};
-    a.x = x; a.F = F; a.H = H; a.W = W; a.C = n.C; a.G = v->G; a.sums = v->sums; a.eps = v->cfg.norm_eps;
-    a.gn_w = n.gn_w; a.gn_b = n.gn_b; a.Fz = 1; a.hz = 1; a.wz = 1; a.Cz = v->Cz;
-    a.out = out_pad; a.f_off = f_off; a.silu = 1;  // yt == nullptr: plain GroupNorm
-    return launch_snorm_apply(a, v->dtype, st);
 }
 
 // CogVideoXDownsample3D's spatial half, per frame: F.pad(x, (0,1,0,1)) then Conv2d(3x3, stride 2): the operand sits at (1,1) of its
@@ -964,10 +965,7 @@ static int run_conv_down(s2v_vae* v, ConvL& c, int F, int H, int W, void* out, h
     g.M = F * (H / 2) * (W / 2); g.N = c.cout; g.K = 9 * c.cin;
     g.conv = 1; g.cin = c.cin; g.Hp = H + 2; g.Wp = W + 2; g.oH = H / 2; g.oW = W / 2; g.kt = 1; g.cstride = 2;
     g.w_rows_padded = (int)rup64(c.cout, 256);
-    if (v->mfma && c.cin % 64 == 0) return launch_gemm_bf16(g, EPI_BIAS, st);
-    if (v->h16 && gemm_f16_ok(g, EPI_BIAS)) return launch_gemm_f16(g, EPI_BIAS, st);
-    g.valu_only = v->cfg.force_simple;
-    return launch_gemm_simple(g, EPI_BIAS, v->dtype, st);
+    return launch_gemm(v, g, EPI_BIAS, st);
 }
 
 // encoder pass over frames [fs, fs + Fb) (one frame batch) of the (th x tw) pixel window at (y0, x0) of video [3][Fv][H][W];
@@ -976,27 +974,11 @@ static int encode_batch(s2v_vae* v, const void* video, int Fv, int fs, int Fb, i
                         bool first, char* dst, int Fl, int f0, int* frames_out, hipStream_t st) {
     int cur = 0, t1 = 1, t2 = 2;
     int F = Fb, H = th, W = tw;
+    const ZqWin z{1, 1, 1};  // no zq: plain GroupNorm
     S2V_TRY(launch_image_to_padded(video, v->cfg.out_channels, Fb, Fv, fs, Himg, Wimg, y0, x0, th, tw, v->conv_in.pad, 2, v->dtype, st));
     S2V_TRY(run_conv(v, v->conv_in, F, H, W, first, EPI_BIAS, nullptr, v->dense[cur], st));
     for (auto& s : v->stages) {
-        for (auto& r : s.res) {
-            S2V_TRY(run_gn_plain(v, r.n1, v->dense[cur], F, H, W, r.c1.pad, 2, st));
-            S2V_TRY(run_conv(v, r.c1, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st));
-            S2V_TRY(run_gn_plain(v, r.n2, v->dense[t1], F, H, W, r.c2.pad, 2, st));
-            if (r.has_sc) {
-                GemmArgs g{};
-                g.A = v->dense[cur]; g.lda = r.cin; g.W = r.sc.w; g.ldw = r.cin; g.bias = r.sc.b;
-                g.C = v->dense[t2]; g.ldc = r.cout; g.M = F * H * W; g.N = r.cout; g.K = r.cin;
-                g.a_rows_padded = (int)rup64(g.M, 256);
-                if (v->mfma && r.cin % 64 == 0) S2V_TRY(launch_gemm_bf16(g, EPI_BIAS, st));
-                else if (v->h16 && gemm_f16_ok(g, EPI_BIAS)) S2V_TRY(launch_gemm_f16(g, EPI_BIAS, st));
-                else { g.valu_only = v->cfg.force_simple; S2V_TRY(launch_gemm_simple(g, EPI_BIAS, v->dtype, st)); }
-                S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[t2], v->dense[t2], st));
-                std::swap(cur, t2);
-            } else {
-                S2V_TRY(run_conv(v, r.c2, F, H, W, first, EPI_BIAS_ADD, v->dense[cur], v->dense[cur], st));
-            }
-        }
+        for (auto& r : s.res) S2V_TRY(run_resnet(v, r, F, H, W, z, first, cur, t1, t2, st));
         if (s.has_up) {  // downsampler: the temporal average pool (compress_time, more than one frame) is fused into the operand write
             if (s.compress_time && F > 1) {
                 S2V_TRY(launch_time_pool_to_padded(v->dense[cur], F, H, W, s.up.cin, s.up.pad, v->dtype, st));
@@ -1009,7 +991,7 @@ static int encode_batch(s2v_vae* v, const void* video, int Fv, int fs, int Fb, i
             H /= 2; W /= 2;
         }
     }
-    S2V_TRY(run_gn_plain(v, v->norm_out, v->dense[cur], F, H, W, v->conv_out.pad, 2, st));
+    S2V_TRY(run_norm(v, v->norm_out, v->dense[cur], F, H, W, z, v->conv_out.pad, st));
     S2V_TRY(run_conv(v, v->conv_out, F, H, W, first, EPI_BIAS, nullptr, v->dense[t1], st));
     *frames_out = F;
     return launch_to_ncfhw(v->dense[t1], F, H, W, 2 * v->Cz, dst, Fl, f0, v->dtype, st);
@@ -1021,7 +1003,7 @@ static int encode_window(s2v_vae* v, const void* video, int Fv, int Himg, int Wi
     S2V_TRY(set_layout(v, th, tw, st));
     int f0 = 0;
     bool first = true;
-    for (auto b : enc_frame_batches(Fv)) {
+    for (auto b : frame_batches(Fv, ENC_FRAME_BATCH)) {
         int fo = 0;
         S2V_TRY(encode_batch(v, video, Fv, b.s, b.e - b.s, Himg, Wimg, y0, x0, th, tw, first, dst, Fl, f0, &fo, st));
         f0 += fo;
@@ -1030,28 +1012,11 @@ static int encode_window(s2v_vae* v, const void* video, int Fv, int Himg, int Wi
     return 0;
 }
 
-struct EncTileGeo { int ts_h, ts_w, ov_h, ov_w, bl_h, bl_w, lim_h, lim_w; };
-static EncTileGeo enc_tile_geo(s2v_vae* v) {  // :1102-1114, 1317-1323 incl. the int() truncations
-    EncTileGeo t;
-    const int sc = spatial_scale(v);
-    t.ts_h = v->cfg.sample_height / 2; t.ts_w = v->cfg.sample_width / 2;
-    const int tl_h = (int)((double)t.ts_h / sc), tl_w = (int)((double)t.ts_w / sc);
-    t.ov_h = (int)(t.ts_h * (1.0 - 1.0 / 6.0)); t.ov_w = (int)(t.ts_w * (1.0 - 1.0 / 5.0));
-    t.bl_h = (int)(tl_h * (1.0 / 6.0)); t.bl_w = (int)(tl_w * (1.0 / 5.0));
-    t.lim_h = tl_h - t.bl_h; t.lim_w = tl_w - t.bl_w;
-    return t;
-}
-
 extern "C" int s2v_vae_encode_shape(s2v_vae* v, int32_t H, int32_t W, int32_t tiling, int32_t* ho, int32_t* wo) {
     S2V_REQUIRE(v && v->encoder && ho && wo && H >= 1 && W >= 1, "s2v_vae_encode_shape: bad argument");
-    const int sc = spatial_scale(v);
-    EncTileGeo t = enc_tile_geo(v);
-    if (!(tiling && (W > t.ts_w || H > t.ts_h))) { *ho = H / sc; *wo = W / sc; return 0; }
-    S2V_REQUIRE(t.ov_h > 0 && t.ov_w > 0, "s2v_vae_encode_shape: degenerate tile overlap");
-    int h = 0, w = 0;
-    for (int i = 0; i < H; i += t.ov_h) h += std::min(std::min(t.ts_h, H - i) / sc, t.lim_h);
-    for (int j = 0; j < W; j += t.ov_w) w += std::min(std::min(t.ts_w, W - j) / sc, t.lim_w);
-    *ho = h; *wo = w;
+    TilePlan p;
+    S2V_REQUIRE(tile_plan_of(v, true, H, W, tiling, &p), "s2v_vae_encode_shape: degenerate tile overlap");
+    *ho = p.out_h; *wo = p.out_w;
     return 0;
 }
 
@@ -1059,71 +1024,24 @@ static int encode_video(s2v_vae* v, const void* video, int F, int H, int W, int 
     const int sc = spatial_scale(v);
     const int Fl = enc_latent_frames(v, F);
     int fb_max = 0;
-    for (auto b : enc_frame_batches(F)) fb_max = std::max(fb_max, b.e - b.s);
-    EncTileGeo t = enc_tile_geo(v);
-    const bool tiled = tiling && (W > t.ts_w || H > t.ts_h);
-    if (!tiled) {
+    for (auto b : frame_batches(F, ENC_FRAME_BATCH)) fb_max = std::max(fb_max, b.e - b.s);
+    TilePlan p;
+    S2V_REQUIRE(tile_plan_of(v, true, H, W, tiling, &p), "s2v_vae_encode: degenerate tile overlap");
+    if (!p.tiled) {
         S2V_REQUIRE(H % sc == 0 && W % sc == 0, "s2v_vae_encode: image sides must be multiples of the spatial compression");
         S2V_TRY(enc_prepare(v, H, W, fb_max));
         return encode_window(v, video, F, H, W, 0, 0, H, W, (char*)moments, Fl, st);
     }
-    S2V_REQUIRE(t.ov_h > 0 && t.ov_w > 0, "s2v_vae_encode: degenerate tile overlap");
-    std::vector<int> is, js;
-    for (int i = 0; i < H; i += t.ov_h) is.push_back(i);
-    for (int j = 0; j < W; j += t.ov_w) js.push_back(j);
-    for (int i : is) S2V_REQUIRE(std::min(t.ts_h, H - i) % sc == 0, "s2v_vae_encode: tile height not a multiple of the spatial compression");
-    for (int j : js) S2V_REQUIRE(std::min(t.ts_w, W - j) % sc == 0, "s2v_vae_encode: tile width not a multiple of the spatial compression");
-    S2V_TRY(enc_prepare(v, std::min(t.ts_h, H), std::min(t.ts_w, W), fb_max));
-    const size_t nt = is.size() * js.size();
+    for (const Tile& t : p.tiles) S2V_REQUIRE(t.h % sc == 0, "s2v_vae_encode: tile height not a multiple of the spatial compression");
+    for (const Tile& t : p.tiles) S2V_REQUIRE(t.w % sc == 0, "s2v_vae_encode: tile width not a multiple of the spatial compression");
+    S2V_TRY(enc_prepare(v, p.tiles[0].h, p.tiles[0].w, fb_max));  // the first tile is the largest
     const int C = 2 * v->Cz;
-    // per-tile moments [2Cz][Fl][th/s][tw/s] (re-allocated only when the tiling or the latent frame count changes)
-    bool realloc_tiles = v->tiles.size() != nt || v->tiles_F != Fl;
-    for (size_t k = 0; !realloc_tiles && k < nt; ++k) {
-        const int th = std::min(t.ts_h, H - is[k / js.size()]) / sc, tw = std::min(t.ts_w, W - js[k % js.size()]) / sc;
-        if (v->tile_h[k] != th || v->tile_w[k] != tw) realloc_tiles = true;
+    S2V_TRY(ensure_tile_buffers(v, p, C, Fl));
+    for (size_t k = 0; k < p.tiles.size(); ++k) {
+        const Tile& t = p.tiles[k];
+        S2V_TRY(encode_window(v, video, F, H, W, t.y, t.x, t.h, t.w, v->tiles[k], Fl, st));
     }
-    if (realloc_tiles) {
-        S2V_CHECK_HIP(hipDeviceSynchronize());
-        for (char* p : v->tiles) (void)hipFree(p);
-        v->tiles.assign(nt, nullptr); v->tile_h.assign(nt, 0); v->tile_w.assign(nt, 0);
-        for (size_t k = 0; k < nt; ++k) {
-            const int th = std::min(t.ts_h, H - is[k / js.size()]) / sc, tw = std::min(t.ts_w, W - js[k % js.size()]) / sc;
-            v->tile_h[k] = th; v->tile_w[k] = tw;
-            S2V_CHECK_HIP(hipMalloc((void**)&v->tiles[k], (size_t)C * Fl * th * tw * v->esz + 16));
-        }
-        v->tiles_F = Fl;
-    }
-    for (size_t k = 0; k < nt; ++k)
-        S2V_TRY(encode_window(v, video, F, H, W, is[k / js.size()], js[k % js.size()], v->tile_h[k] * sc, v->tile_w[k] * sc, v->tiles[k],
-                              Fl, st));
-    int32_t ho, wo;
-    S2V_TRY(s2v_vae_encode_shape(v, H, W, 1, &ho, &wo));
-    // latent-space blends over every latent frame: a tile is [C * Fl] planes of th x tw
-    const int CF = C * Fl;
-    int y0 = 0;
-    for (size_t r = 0; r < is.size(); ++r) {
-        int x0 = 0, ch = 0;
-        for (size_t c = 0; c < js.size(); ++c) {
-            const size_t k = r * js.size() + c;
-            const int Ht = v->tile_h[k], Wt = v->tile_w[k];
-            if (r > 0) {
-                const size_t ka = (r - 1) * js.size() + c;
-                const int E = std::min(std::min(v->tile_h[ka], Ht), t.bl_h);
-                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, CF, E, 1, v->dtype, st));
-            }
-            if (c > 0) {
-                const size_t ka = k - 1;
-                const int E = std::min(std::min(v->tile_w[ka], Wt), t.bl_w);
-                S2V_TRY(launch_blend(v->tiles[ka], v->tile_h[ka], v->tile_w[ka], v->tiles[k], Ht, Wt, CF, E, 0, v->dtype, st));
-            }
-            ch = std::min(Ht, t.lim_h);
-            const int cw = std::min(Wt, t.lim_w);
-            S2V_TRY(launch_paste(v->tiles[k], Ht, Wt, ch, cw, moments, ho, wo, y0, x0, CF, v->dtype, st));
-            x0 += cw;
-        }
-        y0 += ch;
-    }
-    return 0;
+    return blend_and_paste(v, p, C * Fl, moments, st);  // latent-space blends over every latent frame
 }
 
 extern "C" int s2v_vae_encode(s2v_vae* v, const void* image, int32_t H, int32_t W, int32_t tiling, void* moments,

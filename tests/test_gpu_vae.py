@@ -45,6 +45,25 @@ def test_vae_tiny_fp32_vs_reference_golden(s2v, tiling):
     np.testing.assert_allclose((y.double() ** 2).sum(dim=(0, 1, 3, 4)).numpy(), g[name + "_sq"], rtol=1e-4)
 
 
+def test_vae_tiny_tiled_ragged_grid_vs_oracle(s2v):
+    """7 x 9 latents, the smallest tiled decode whose grid has two tile sizes in both axes (6 | 2 rows, 9 | 1 columns of latents) and an edge
+    tile smaller than the blend extent: the last column decodes to 8 pixels where the horizontal blend takes 16 (the 12 x 20 decode above has
+    edge tiles of 16 x 32 pixels against blends of 8 and 16) -- fp32 against the oracle's tiled decode, every pixel"""
+    g = load_golden("vae_tiny.npz")
+    sd = weights_of(g)
+    lat = t(g["latents"])[:, :2, :, :7, :9].contiguous()
+    with torch.no_grad():
+        exp = vae_ref.decode_latents(sd, TINY, lat, True)
+    vae = make_vae(s2v, TINY, torch.float32, sd)
+    vae.enable_tiling()
+    y = vae.decode_latents(lat.to(DEV)).cpu()
+    torch.cuda.synchronize()
+    assert y.shape == exp.shape and y.shape[3:] == (56, 72)  # crops of 40 + 16 rows, 64 + 8 columns
+    err = (y - exp).abs().max().item()
+    print(f"MEASURED vae tiny ragged tiled decode vs oracle: max-abs {err:.3e}")
+    assert err <= 1e-3, err
+
+
 def test_vae_even_single_frame_and_postprocess_vs_reference_golden(s2v):
     g = load_golden("vae_tiny.npz")
     vae = make_vae(s2v, TINY, torch.float32, weights_of(g))

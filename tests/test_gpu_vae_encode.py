@@ -47,6 +47,25 @@ def test_encode_tiny_fp32_vs_reference_golden(s2v, tiling):
     assert (lat - t(g[f"latent_{name}"])).abs().max().item() <= 1e-3
 
 
+def test_encode_tiny_tiled_ragged_grid_vs_oracle(s2v):
+    """56 x 72 pixels, the smallest tiled encode whose grid has two tile sizes in both axes (48 | 16 rows, 72 | 8 columns of pixels) and an edge
+    tile smaller than the blend extent: the last column encodes to 1 latent where the horizontal blend takes 2 (the 96 x 160 encode above has
+    edge tiles of 2 x 4 latents against blends of 1 and 2) -- fp32 against the oracle's tiled encode, every moment"""
+    g = load_golden("vae_enc_tiny.npz")
+    sd = weights_of(g)
+    x = t(g["image"])[..., :56, :72].contiguous()
+    with torch.no_grad():
+        exp = vae_ref.encode_moments(sd, TINY, x, True)
+    vae = make_vae(s2v, TINY, torch.float32, sd)
+    vae.enable_tiling()
+    mom = vae.encode(x.to(DEV)).latent_dist.parameters.cpu()
+    torch.cuda.synchronize()
+    assert mom.shape == exp.shape == (1, 32, 1, 7, 9)  # crops of 5 + 2 rows, 8 + 1 columns
+    err = (mom - exp).abs().max().item()
+    print(f"MEASURED vae tiny ragged tiled encode vs oracle: max-abs {err:.3e}")
+    assert err <= 1e-3, err
+
+
 def test_encode_small_window_and_errors(s2v):
     g = load_golden("vae_enc_tiny.npz")
     vae = make_vae(s2v, TINY, torch.float32, weights_of(g))
