@@ -30,7 +30,7 @@ class ModelConfigC(ctypes.Structure):
 
 class SchedCoefC(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("guidance", ctypes.c_float)] + [
-        (n, ctypes.c_float) for n in ("c_x0_x", "c_x0_v", "a_t", "b_t", "m1", "m2", "m3", "m4", "mn", "pad")
+        (n, ctypes.c_float) for n in ("c_x0_x", "c_x0_v", "a_t", "b_t", "m1", "m2", "m3", "m4", "mn", "guidance_subject")
     ]
 
 
@@ -40,6 +40,7 @@ class BlendC(ctypes.Structure):
     _fields_ = [("sqrt_alpha", ctypes.c_float), ("sqrt_one_minus_alpha", ctypes.c_float), ("last", ctypes.c_int32), ("keep_max", ctypes.c_int32)]
 
 
+SCHED_CFG_PAIR, SCHED_NP_F32, SCHED_OUT_F32, SCHED_TRIPLE = 1, 2, 4, 8   # s2v_sched_step flags (bit3: the subject-guidance triple [3, n])
 MASK_DTYPE_U8 = 3   # S2V_MASK_DTYPE_U8: a uint8 pixel mask, non-zero = repaint; for s2v_map_to_latent: levels 0..255
 
 
@@ -85,6 +86,8 @@ _SIGS = {
     "s2v_sched_step_masked": [_P, ctypes.POINTER(SchedCoefC), ctypes.POINTER(BlendC), _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32,
                               _I32, _P],
     "s2v_last_noise_pred": [_P, ctypes.POINTER(_P)],
+    "s2v_set_conditioning_triples": [_P, _P, _P, _P, _I32, _P],
+    "s2v_denoise_step_guided": [_P, _P, ctypes.POINTER(_F), ctypes.POINTER(SchedCoefC), ctypes.POINTER(BlendC), _P, _P, _I32, _P],
     "s2v_denoise_split_begin": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _I32, _I32, _P],
     "s2v_cfg_pair": [_P, ctypes.POINTER(_P), ctypes.POINTER(_I64)],
     "s2v_denoise_split_end": [_P, _P, _P, _P, _P],

@@ -76,8 +76,9 @@ struct GraphKey {
     const void *z0 = nullptr, *noise0 = nullptr, *mask = nullptr;   // the blend operands of the masked step (s2v_denoise_step_masked); null: unmasked
     int mode = 0;   // S2V_STEP_*: the step-cache mode the forward was captured in; every mode has an executable of its own (launch_captured)
     uint64_t amask = 0;   // s2v_attn_map_arm: the layers whose attention the mass kernel follows in this step; every mask has an executable of its own
+    int triple = 0;       // s2v_denoise_step_guided: the step of [u | r | f] triples, whose last kernel is another one than the pair step's
     bool same_but_mode(const GraphKey& o) const {
-        return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask;
+        return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask && triple == o.triple;
     }
     bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask; }
 };
@@ -156,6 +157,9 @@ struct s2v_ctx {
     // one reference per video (s2v_set_conditioning_refs): sample j reads the tokens of reference j mod n_ref at e1_cur + (j mod n_ref) * e1_stride.
     // n_ref = 1 is the workspace's e1; more references sit in e1x, allocated by that set-up call and freed with the workspace
     int n_ref = 1;
+    // what the conditioning holds: the CFG pairs [negative x b | positive x b] of s2v_set_conditioning(_refs), or the triples [u x b | r x b | f x b]
+    // of s2v_set_conditioning_triples.  B = 6 is three pairs or two triples by shape alone, so every step entry asks this
+    bool cond_triples = false;
     char *e1_cur = nullptr, *e1x = nullptr;
     int64_t e1_stride = 0, e1x_bytes = 0;
     float* t_dev = nullptr;
@@ -804,6 +808,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     c->M = (int64_t)B * c->Ntok;
     c->Mpad = rup(c->M, 256) + 256;
     c->have_rope = c->have_pos = c->have_cond = false;
+    c->cond_triples = false;
     c->split_kind = -1;
     const int64_t D = c->D, E = c->esz;
     const int64_t Cin4 = c->cfg.in_channels * 4, Cout4 = c->cfg.out_channels * 4;
@@ -1050,8 +1055,8 @@ extern "C" int s2v_set_conditioning_refs(s2v_ctx* c, const void* text_dev, const
         }
         e1 = c->e1x;
     }
-    if (e1 != c->e1_cur || n_ref != c->n_ref) drop_graph(c);
-    c->e1_cur = e1; c->n_ref = n_ref;
+    if (e1 != c->e1_cur || n_ref != c->n_ref || c->cond_triples) drop_graph(c);
+    c->e1_cur = e1; c->n_ref = n_ref; c->cond_triples = false;
     c->have_cond = false;
     // text_proj (cogvideox_transformer_3d.py:494).  The MFMA kernel stages 128-row tiles, so the operand is first
     // copied into the (padded, zero-initialised) Hb scratch.
@@ -1104,6 +1109,66 @@ extern "C" int s2v_set_conditioning_refs(s2v_ctx* c, const void* text_dev, const
 
 extern "C" int s2v_set_conditioning(s2v_ctx* c, const void* text_dev, const void* ref_latent_dev, s2v_stream stream) {
     return s2v_set_conditioning_refs(c, text_dev, ref_latent_dev, 1, stream);
+}
+
+// Subject guidance: the conditioning of b triples on a geometry of B = 3b samples [u x b | r x b | f x b] (include/s2v_hip.h).  The launches are
+// the pair set-up's: video v's [negative | positive] text pair through one M = 2T projection into X as scratch, its negative rows then moved to
+// samples u_v and r_v and its positive rows to f_v; every reference through the per-reference patch embedding.  The reference table is the e1x
+// buffer with one entry per SAMPLE, [null x b | ref x b | ref x b], so the forward's `j mod n_ref` (n_ref = B) stays the mapping: the f entry
+// is a copy of the r entry's rows, not a second embedding
+extern "C" int s2v_set_conditioning_triples(s2v_ctx* c, const void* text_dev, const void* ref_latents_dev, const void* null_ref_latents_dev,
+                                            int32_t n_null, s2v_stream stream) {
+    S2V_REQUIRE(c && c->ws && c->finalized, "s2v_set_conditioning_triples: geometry and weights must be set first");
+    S2V_REQUIRE(text_dev && ref_latents_dev && null_ref_latents_dev, "s2v_set_conditioning_triples: null input");
+    S2V_REQUIRE(!c->shard, "s2v_set_conditioning_triples: a shard context (s2v_set_shard) has no triple step: subject guidance runs on one GPU");
+    const int B = c->B, b = B / 3;
+    S2V_REQUIRE(B % 3 == 0 && b <= 2, "s2v_set_conditioning_triples: a geometry of B = 3b samples [u x b | r x b | f x b] with b = 1 or 2 videos is required");
+    S2V_REQUIRE(n_null == 1 || n_null == b, "s2v_set_conditioning_triples: n_null must be 1 (one null reference for every video) or b (one per video)");
+    sc_invalidate(c);
+    hipStream_t st = (hipStream_t)stream;
+    const int D = c->D;
+    const int64_t E = c->esz;
+    const int64_t need = (int64_t)B * c->e1_stride;
+    if (c->e1x_bytes < need) {
+        S2V_CHECK_HIP(hipDeviceSynchronize());
+        if (c->e1x) hipFree(c->e1x);
+        c->e1x = nullptr; c->e1x_bytes = 0;
+        if (c->e1_cur != c->e1) { c->e1_cur = c->e1; c->n_ref = 1; c->have_cond = false; drop_graph(c); }
+        S2V_CHECK_HIP(hipMalloc((void**)&c->e1x, need));
+        S2V_CHECK_HIP(hipMemset(c->e1x, 0, need));
+        c->e1x_bytes = need;
+    }
+    if (c->e1x != c->e1_cur || B != c->n_ref || !c->cond_triples) drop_graph(c);
+    c->e1_cur = c->e1x; c->n_ref = B; c->cond_triples = true;
+    c->have_cond = false;
+    const int TX = c->cfg.text_embed_dim;
+    if (c->T > 0) {
+        GemmArgs g{};
+        g.A = c->Hb; g.lda = TX; g.W = c->text_w; g.ldw = TX; g.bias = c->text_b;
+        g.C = c->X; g.ldc = D; g.M = 2 * c->T; g.N = D; g.K = TX;
+        const int64_t tb = (int64_t)c->T * TX * E, eb = (int64_t)c->T * D * E;
+        for (int v = 0; v < b; ++v) {
+            for (int h = 0; h < 2; ++h)
+                S2V_TRY(launch_convert2d((const char*)text_dev + (int64_t)(v + h * b) * tb, c->dtype, TX, c->Hb + h * tb, c->dtype, TX, c->T, TX, st));
+            S2V_TRY(linear(c, g, EPI_BIAS, st));
+            for (int s3 = 0; s3 < 3; ++s3)   // u and r: the negative rows; f: the positive rows
+                S2V_TRY(launch_copy_rows(c->X + (s3 == 2 ? eb : 0), D, nullptr, 0, c->e0 + (int64_t)(v + s3 * b) * eb, D, c->T, D, c->dtype, st));
+        }
+    }
+    const int K = c->cfg.in_channels * 4;
+    const int64_t ref_elems = (int64_t)c->cfg.in_channels * c->H * c->W;
+    for (int r = 0; r < 2 * b; ++r) {   // entries [0, b): the null references; [b, 2b): the references
+        const char* src = r < b ? (const char*)null_ref_latents_dev + (n_null == 1 ? 0 : r) * ref_elems * E : (const char*)ref_latents_dev + (r - b) * ref_elems * E;
+        S2V_TRY(launch_patchify(src, 0, 1, 1, c->cfg.in_channels, c->H, c->W, c->patches, c->dtype, st));
+        GemmArgs g{};
+        g.A = c->patches; g.lda = K; g.W = c->patch_w; g.ldw = K; g.bias = c->patch_b;
+        g.C = c->e1x + r * c->e1_stride; g.ldc = D; g.M = c->R; g.N = D; g.K = K;
+        if (c->R > 0) S2V_TRY(linear(c, g, EPI_BIAS, st));
+    }
+    for (int v = 0; v < b && c->R > 0; ++v)
+        S2V_TRY(launch_copy_rows(c->e1x + (b + v) * c->e1_stride, D, nullptr, 0, c->e1x + (2 * b + v) * c->e1_stride, D, c->R, D, c->dtype, st));
+    c->have_cond = true;
+    return 0;
 }
 
 // ---- one transformer block on the packed residual buffer X ------------------------------------------------
@@ -1745,7 +1810,7 @@ extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) 
 // ------------------------------------------------------------------------------------------------------
 static void fill_coef(SchedCoef& d, const s2v_sched_coef& s) {
     d.kind = s.kind; d.guidance = s.guidance; d.c_x0_x = s.c_x0_x; d.c_x0_v = s.c_x0_v; d.a_t = s.a_t; d.b_t = s.b_t;
-    d.m1 = s.m1; d.m2 = s.m2; d.m3 = s.m3; d.m4 = s.m4; d.mn = s.mn; d.pad = 0.f;
+    d.m1 = s.m1; d.m2 = s.m2; d.m3 = s.m3; d.m4 = s.m4; d.mn = s.mn; d.guidance_subject = s.guidance_subject;
 }
 
 static SchedBlend fill_blend(const s2v_blend& s) { return SchedBlend{s.sqrt_alpha, s.sqrt_one_minus_alpha, s.last != 0, s.keep_max}; }
@@ -1764,10 +1829,11 @@ extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const
     S2V_REQUIRE(coef_host->kind == 0 || noise, "s2v_sched_step: DPM step needs a noise tensor");
     S2V_REQUIRE(coef_host->kind != 2 || x0_hist, "s2v_sched_step: DPM multistep needs x0_hist");
     S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_sched_step: unsupported dtype");
+    S2V_REQUIRE((flags & 9) != 9, "s2v_sched_step: flags bit0 (the CFG pair [2, n]) and bit3 (the subject-guidance triple [3, n]) exclude each other");
     (void)c;
     SchedArgs a{};
     a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
-    a.noise = noise; a.n = n; a.nvid = 1; a.n_vid = n; a.cfg = flags & 1; a.np_f32 = (flags >> 1) & 1; a.out_f32 = (flags >> 2) & 1;
+    a.noise = noise; a.n = n; a.nvid = 1; a.n_vid = n; a.cfg = (flags & 8) ? SCHED_CFG_TRIPLE : flags & 1; a.np_f32 = (flags >> 1) & 1; a.out_f32 = (flags >> 2) & 1;
     a.coef = nullptr;
     fill_coef(a.cval, *coef_host);
     return launch_sched_step(a, dtype, (hipStream_t)stream);
@@ -1784,10 +1850,11 @@ extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host
     S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_sched_step_masked: unsupported dtype");
     S2V_REQUIRE(!(flags & 4), "s2v_sched_step_masked: the blend runs on the latents rounded to `dtype` (flags bit2, fp32 output, is refused)");
     S2V_REQUIRE(blend_host->keep_max >= 0 && blend_host->keep_max <= 255, "s2v_sched_step_masked: keep_max must be a level 0..255");
+    S2V_REQUIRE((flags & 9) != 9, "s2v_sched_step_masked: flags bit0 (the CFG pair [2, n]) and bit3 (the subject-guidance triple [3, n]) exclude each other");
     (void)c;
     SchedMaskArgs a{};
     a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
-    a.noise = noise; a.n = (int64_t)F * C * H * W; a.nvid = 1; a.n_vid = a.n; a.cfg = flags & 1; a.np_f32 = (flags >> 1) & 1;
+    a.noise = noise; a.n = (int64_t)F * C * H * W; a.nvid = 1; a.n_vid = a.n; a.cfg = (flags & 8) ? SCHED_CFG_TRIPLE : flags & 1; a.np_f32 = (flags >> 1) & 1;
     a.coef = nullptr;
     fill_coef(a.cval, *coef_host);
     a.z0 = z0; a.noise0 = noise0; a.mask = latent_mask; a.chw = C * H * W; a.hw = H * W; a.mask_vid = F * H * W;
@@ -1886,6 +1953,8 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
     const int mode = sc_take_arm(c);
     const uint64_t am = am_take_arm(c);
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
+    S2V_REQUIRE(!c->cond_triples, "s2v_denoise_step: the context is conditioned as subject-guidance triples [u x b | r x b | f x b] (s2v_set_conditioning_triples): "
+                                  "its step is s2v_denoise_step_guided");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
     const int b = c->B >= 2 ? c->B / 2 : 1;
     for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step: DPM needs noise and x0_hist");
@@ -1947,6 +2016,8 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
                                     "(s2v_denoise_split_begin / _end, s2v_denoise_step_cfg_parallel) have no masked form: masked video-to-video runs the "
                                     "CFG pairs of b videos, B = 2b, on one GPU");
     S2V_REQUIRE(c->B % 2 == 0, "s2v_denoise_step_masked: an even B = 2b (the CFG pairs of b videos) is required");
+    S2V_REQUIRE(!c->cond_triples, "s2v_denoise_step_masked: the context is conditioned as subject-guidance triples [u x b | r x b | f x b] "
+                                  "(s2v_set_conditioning_triples): its masked step is s2v_denoise_step_guided with blends");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step_masked: in/out channels must match");
     const int b = c->B / 2;
     S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_masked: s2v_set_blend has not set the blend operands of this geometry's b = B/2 videos");
@@ -1958,6 +2029,54 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     GraphKey key{latents, x0_hist, noise, -1};
     key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am;
     return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode, am); })));
+}
+
+// ---- subject guidance: the step of b triples [u x b | r x b | f x b] -----------------------------------------------------------------------------
+// forward on B = 3b samples sharing each video's latent (sample j embeds video j mod b), then the triple combine and the scheduler step in the
+// last kernel -- with `masked` the blend of s2v_set_blend behind it
+static int guided_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, bool masked) {
+    const int b = c->B / 3;
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, S2V_STEP_FULL, 0));
+    SchedMaskArgs a{};
+    a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
+    a.nvid = b; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
+    a.n = b * a.n_vid; a.cfg = SCHED_CFG_TRIPLE; a.coef = c->coef_dev;
+    if (!masked) return launch_sched_step(a, c->dtype, st);
+    a.z0 = c->blend_z0; a.noise0 = c->blend_noise0; a.mask = c->blend_mask;
+    a.chw = c->cfg.out_channels * c->H * c->W; a.hw = c->H * c->W; a.mask_vid = c->F * a.hw; a.blend = c->blend_dev;
+    return launch_sched_step_masked(a, c->dtype, st);
+}
+
+extern "C" int s2v_denoise_step_guided(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
+                                       float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
+    S2V_REQUIRE(c && latents && timesteps && coefs, "s2v_denoise_step_guided: null argument");
+    // the arms are one-shot and taken by every step entry, refused or not
+    const int mode = sc_take_arm(c);
+    const uint64_t am = am_take_arm(c);
+    S2V_REQUIRE(!c->shard, "s2v_denoise_step_guided: a shard context (s2v_set_shard) has no triple step: subject guidance runs on one GPU");
+    // a pending split lives on a B = 1 geometry, so it is named before the geometry is
+    S2V_REQUIRE(c->split_kind < 0, "s2v_denoise_step_guided: a CFG-parallel split is pending (s2v_denoise_split_begin): the split entries run CFG pairs, "
+                                   "subject guidance runs on one GPU");
+    S2V_REQUIRE(c->ws && c->B % 3 == 0 && c->B / 3 <= 2, "s2v_denoise_step_guided: a geometry of B = 3b samples [u x b | r x b | f x b] with b = 1 or 2 videos is required");
+    S2V_REQUIRE(c->have_cond && c->cond_triples, "s2v_denoise_step_guided: the conditioning was not set by s2v_set_conditioning_triples (the context holds "
+                                                 "CFG pairs, or no conditioning)");
+    S2V_REQUIRE(mode == S2V_STEP_FULL, "s2v_denoise_step_guided: a step-cache mode (s2v_step_cache_arm: CAPTURE / REUSE) is armed, and the step cache assumes CFG pairs");
+    S2V_REQUIRE(am == 0, "s2v_denoise_step_guided: an attention map is armed (s2v_attn_map_arm), and the attention map assumes CFG pairs");
+    S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step_guided: in/out channels must match");
+    const int b = c->B / 3;
+    for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step_guided: DPM needs noise and x0_hist");
+    if (blends) {
+        S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_guided: s2v_set_blend has not set the blend operands of this geometry's b = B/3 videos");
+        for (int k = 0; k < b; ++k) S2V_REQUIRE(blends[k].keep_max >= 0 && blends[k].keep_max <= 255, "s2v_denoise_step_guided: keep_max must be a level 0..255");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool masked = blends != nullptr;
+    S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
+    if (!use_graph) return guided_step_launches(c, latents, x0_hist, noise, st, masked);
+    GraphKey key{latents, x0_hist, noise, -1};
+    key.triple = 1;
+    if (masked) { key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; }
+    return launch_captured(c, key, st, [&](hipStream_t s) { return guided_step_launches(c, latents, x0_hist, noise, s, masked); });
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------

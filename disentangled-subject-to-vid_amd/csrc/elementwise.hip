@@ -950,7 +950,9 @@ int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void
 // A = SchedArgs: the step.  A = SchedMaskArgs: the step, then the masked video-to-video select on its rounded result (kernels.h): a cell is
 // kept iff its level is <= the record's keep_max (a 0 / 1 mask: keep_max = 0; a change map: the video's threshold of this step).  The
 // SchedArgs instantiation is the kernel it was before the masked form existed, kernel arguments included.
-template <typename T, typename A>
+// TRIPLE (subject guidance, kernels.h): noise_pred is [3, n] = [u | r | f] and v = (u + g_subject * (r - u)) + g_text * (f - r), five roundings in
+// that association.  A compile-time policy: the two pair instantiations hold no branch for it and take the arguments they took.
+template <typename T, typename A, bool TRIPLE = false>
 __global__ void sched_step_k(const A a) {
 #pragma clang fp contract(off)  // hipcc defaults to -ffp-contract=fast and __fmul_rn is a plain multiply in HIP
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // within video blockIdx.y
@@ -958,7 +960,18 @@ __global__ void sched_step_k(const A a) {
     const int64_t i = (int64_t)blockIdx.y * a.n_vid + j;
     const SchedCoef k = a.coef ? a.coef[blockIdx.y] : a.cval;
     float v;
-    if (a.np_f32) {
+    if constexpr (TRIPLE) {
+        float u, r, f;
+        if (a.np_f32) {
+            const float* np = (const float*)a.noise_pred;
+            u = np[i]; r = np[a.n + i]; f = np[2 * a.n + i];
+        } else {
+            const T* np = (const T*)a.noise_pred;
+            u = ET<T>::ld(np + i); r = ET<T>::ld(np + a.n + i); f = ET<T>::ld(np + 2 * a.n + i);
+        }
+        const float s = __fadd_rn(u, __fmul_rn(k.guidance_subject, __fsub_rn(r, u)));
+        v = __fadd_rn(s, __fmul_rn(k.guidance, __fsub_rn(f, r)));
+    } else if (a.np_f32) {
         const float* np = (const float*)a.noise_pred;
         v = a.cfg ? __fadd_rn(np[i], __fmul_rn(k.guidance, __fsub_rn(np[a.n + i], np[i]))) : np[i];
     } else {
@@ -1005,12 +1018,14 @@ __global__ void sched_step_k(const A a) {
 static int sched_step_checks(const SchedArgs& a) {
     S2V_REQUIRE(a.nvid >= 1 && a.n_vid >= 1 && (int64_t)a.nvid * a.n_vid == a.n, "sched_step: n must be nvid videos of n_vid elements");
     S2V_REQUIRE(a.coef || a.nvid == 1, "sched_step: several videos take their coefficient sets from device memory");
+    S2V_REQUIRE(a.cfg == 0 || a.cfg == 1 || a.cfg == SCHED_CFG_TRIPLE, "sched_step: cfg is 0 (one prediction), 1 (the CFG pair) or SCHED_CFG_TRIPLE (the subject-guidance triple)");
     return 0;
 }
 int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st) {
     S2V_TRY(sched_step_checks(a));
     dim3 grid((unsigned)((a.n_vid + 255) / 256), (unsigned)a.nvid);
-    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedArgs>), grid, dim3(256), 0, st, a))
+    if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedArgs, true>), grid, dim3(256), 0, st, a)) }
+    else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedArgs>), grid, dim3(256), 0, st, a)) }
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1022,7 +1037,8 @@ int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st) 
                 "sched_step_masked: a video is [F][C][H * W] elements over a mask plane of [F][H * W] cells");
     S2V_REQUIRE(a.n_vid < ((int64_t)1 << 31) && a.mask_vid == a.n_vid / a.chw * a.hw, "sched_step_masked: a video of fewer than 2^31 elements, mask_vid = F * H * W cells");
     dim3 grid((unsigned)((a.n_vid + 255) / 256), (unsigned)a.nvid);
-    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskArgs>), grid, dim3(256), 0, st, a))
+    if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskArgs, true>), grid, dim3(256), 0, st, a)) }
+    else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskArgs>), grid, dim3(256), 0, st, a)) }
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -350,15 +350,19 @@ int launch_tail_norm(const TailNormArgs& a, int dtype, hipStream_t st);
 struct SchedCoef {
     int kind; float guidance;
     float c_x0_x, c_x0_v, a_t, b_t, m1, m2, m3, m4, mn;
-    float pad;
+    float guidance_subject;   // the triple combine's subject scale (cfg = SCHED_CFG_TRIPLE); the pair paths never read it
 };
+// Subject guidance: three predictions per video, u (negative text, null reference), r (negative text, the reference), f (positive text, the
+// reference), combined as v = (u + guidance_subject * (r - u)) + guidance * (f - r) in fp32, every operation rounding on its own and in this
+// association.  With the u plane holding the r plane's bits r - u = +0, so v is the pair's r + guidance * (f - r) bit for bit whatever the scale.
+enum { SCHED_CFG_TRIPLE = 2 };
 struct SchedArgs {
-    const void* noise_pred;   // [2, n] model dtype (uncond, cond) or [1, n] when !cfg; n = nvid * n_vid, the conditional half n elements in
+    const void* noise_pred;   // [2, n] model dtype (uncond, cond), [1, n] when !cfg, or [3, n] (u, r, f) when cfg == SCHED_CFG_TRIPLE; n = nvid * n_vid, every plane n elements on
     const void* latents_in;   // [n] model dtype: nvid videos of n_vid elements
     void* latents_out;        // [n] model dtype (may alias latents_in)
     float* x0_hist;           // [n] fp32: read as x0_old (kind 2), overwritten with this step's x0 (may be null for DDIM)
     const void* noise;        // [n] model dtype, DPM only
-    int64_t n; int cfg;
+    int64_t n; int cfg;       // 0, 1 or SCHED_CFG_TRIPLE
     int nvid; int64_t n_vid;  // videos in this launch and the elements of one (n = nvid * n_vid)
     const SchedCoef* coef;    // device pointer to nvid consecutive sets, or null => use cval (nvid = 1)
     SchedCoef cval;

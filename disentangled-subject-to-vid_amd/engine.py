@@ -345,6 +345,7 @@ class S2VEngine:
             self._attn_auto_pending = True
         self._rope_key, self.have_rope = None, None
         self._cond_args = None
+        self.triples = False
         self._bump("rope", "cond")
 
     def clear_rope(self):
@@ -421,15 +422,44 @@ class S2VEngine:
             _lib.check(_lib.lib().s2v_set_conditioning_refs(self._h, _lib.ptr(text), _lib.ptr(ref), n_ref, _lib.stream_ptr()))
         torch.cuda.current_stream().synchronize()
         self._cond_args = (text, ref) if self.cfg.lora_runtime_rank > 0 else None
+        self.triples = False
         self._bump("cond")
 
     _cond_args = None
+    triples = False   # the conditioning holds subject-guidance triples [u x b | r x b | f x b] (set_conditioning_triples), not CFG pairs
+
+    def set_conditioning_triples(self, text, ref_latent, null_ref_latent=None):
+        """subject guidance on a geometry of B = 3b samples [u x b | r x b | f x b], b = 1 or 2 (s2v_set_conditioning_triples): text
+        [2b,T,text_embed_dim] = [negative x b | positive x b] (the negative rows serve the u and the r sample of their video), ref_latent
+        [b,1,C,H,W] one reference per video, null_ref_latent [1 or b,1,C,H,W] the reference of the u samples (None: zeros, the zero latent)"""
+        B, T, F, H, W = self.geometry
+        if B % 3 or B // 3 > 2:
+            raise _lib.S2VError(f"set_conditioning_triples: a geometry of B = 3b samples with b = 1 or 2 videos is required, got B = {B}")
+        b = B // 3
+        text = text.to(self.device, self.dtype).contiguous()
+        ref = ref_latent.to(self.device, self.dtype).contiguous()
+        if tuple(text.shape) != (2 * b, T, self.cfg.text_embed_dim):
+            raise _lib.S2VError(f"set_conditioning_triples: text embeddings must be [{2 * b},{T},{self.cfg.text_embed_dim}] "
+                                f"([negative x {b} | positive x {b}]), got {tuple(text.shape)}")
+        want = (1, self.cfg.in_channels, H, W)
+        if ref.ndim != 5 or tuple(ref.shape[1:]) != want or ref.shape[0] != b:
+            raise _lib.S2VError(f"set_conditioning_triples: ref_img_states must be [{b},1,{self.cfg.in_channels},{H},{W}] (one reference per video), "
+                                f"got {tuple(ref.shape)}")
+        null = torch.zeros_like(ref[:1]) if null_ref_latent is None else null_ref_latent.to(self.device, self.dtype).contiguous()
+        if null.ndim != 5 or tuple(null.shape[1:]) != want or null.shape[0] not in (1, b):
+            raise _lib.S2VError(f"set_conditioning_triples: negative_ref_img_states must be [1 or {b},1,{self.cfg.in_channels},{H},{W}], "
+                                f"got {tuple(null.shape)}")
+        _lib.check(_lib.lib().s2v_set_conditioning_triples(self._h, _lib.ptr(text), _lib.ptr(ref), _lib.ptr(null), null.shape[0], _lib.stream_ptr()))
+        torch.cuda.current_stream().synchronize()
+        self._cond_args = (text, ref, null) if self.cfg.lora_runtime_rank > 0 else None
+        self.triples = True
+        self._bump("cond")
 
     def _lora_changed(self):
         """patch_embed.proj / text_proj may have been re-merged: the hoisted conditioning is computed again from the inputs it was set with"""
         torch.cuda.current_stream().synchronize()
         if self.kind == _lib.CTX_MODEL and self._cond_args is not None and self.geometry is not None:
-            self.set_conditioning(*self._cond_args)
+            (self.set_conditioning_triples if self.triples else self.set_conditioning)(*self._cond_args)
 
     # ---- step cache (include/s2v_hip.h: s2v_step_cache_*) ------------------------------------------------------------------------------
     _CACHE_MODES = {None: _lib.STEP_FULL, "full": _lib.STEP_FULL, "capture": _lib.STEP_CAPTURE, "reuse": _lib.STEP_REUSE}
@@ -576,14 +606,14 @@ class S2VEngine:
     _blend = None
 
     def set_blend(self, z0, noise0, latent_mask):
-        """the blend operands of a masked call for the b = B/2 videos of the geometry: z0 and noise0 [b,F,C,H,W] in the model dtype, latent_mask
+        """the blend operands of a masked call for the b = B/2 videos of the geometry (B/3 under set_conditioning_triples): z0 and noise0 [b,F,C,H,W] in the model dtype, latent_mask
         uint8 [b,F,H,W] (mask_to_latent's 0 / 1, or map_to_latent's levels: a cell is kept where it is <= the record's keep_max); the tensors are held until clear_blend or the next set_blend.  Drops a captured step"""
         B, T, F, H, W = self.geometry
-        b = B // 2
+        b = B // 3 if self.triples else B // 2
         want = (b, F, self.cfg.in_channels, H, W)
         for name, x in (("z0", z0), ("noise0", noise0)):
             if x.dtype != self.dtype or tuple(x.shape) != want or not x.is_contiguous():
-                raise _lib.S2VError(f"set_blend: {name} must be contiguous {list(want)} in the model dtype for the b = B/2 videos of the geometry, "
+                raise _lib.S2VError(f"set_blend: {name} must be contiguous {list(want)} in the model dtype for the b videos of the geometry, "
                                     f"got {list(x.shape)} {x.dtype}")
         if latent_mask.dtype != torch.uint8 or tuple(latent_mask.shape) != (b, F, H, W) or not latent_mask.is_contiguous():
             raise _lib.S2VError(f"set_blend: latent_mask must be contiguous uint8 {[b, F, H, W]}, got {list(latent_mask.shape)} {latent_mask.dtype}")
@@ -596,17 +626,21 @@ class S2VEngine:
             _lib.check(_lib.lib().s2v_set_blend(self._h, None, None, None, 0))
             self._blend = None
 
-    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None):
+    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None, subject=False):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
         [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
         (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
         coef[k] -- its own kind, guidance and scalars (s2v_denoise_step_videos); a scalar beside a sequence is repeated.
         blend: the masked step (s2v_denoise_step_masked, after set_blend): one _lib.BlendC, or a sequence of b, video k blended with blend[k]
         cache: the step-cache mode of this step's forward (_arm; after step_cache_enable): "capture", "reuse" or None
-        attn_layers: the block indices whose attention mass this step adds to the attention map (after attn_map_enable; not with "reuse")"""
+        attn_layers: the block indices whose attention mass this step adds to the attention map (after attn_map_enable; not with "reuse")
+        subject: the subject-guidance step (s2v_denoise_step_guided, after set_conditioning_triples): b = B/3 videos of a geometry of B = 3b
+        samples [u x b | r x b | f x b], video k combined with coef[k].guidance_subject and coef[k].guidance; with blend its masked form"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
+        if subject:
+            return self._denoise_step_guided(latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers)
         if B > 2:
             if B % 2:
                 raise _lib.S2VError(f"denoise_step: a geometry of {B} samples is no whole number of CFG pairs")
@@ -637,12 +671,38 @@ class S2VEngine:
         else:
             _lib.check(_lib.lib().s2v_denoise_step(self._h, _lib.ptr(latents), float(timestep), ctypes.byref(coef),
                                                    _lib.ptr(x0_hist), _lib.ptr(noise), int(use_graph and not auto), _lib.stream_ptr()))
-        if auto:  # the first step of an "auto" engine runs eagerly; its census decides the format of every later step
-            slow, total = self.attn_slow_stats()
-            self.attn_slow_fraction = slow / total if total else 0.0
-            if self.attn_slow_fraction > self.AUTO_SLOW_FRACTION:
-                self.set_attn_p_format("bf16")
-            self._attn_auto_pending = False
+        if auto:
+            self._settle_attn_auto()
+
+    def _settle_attn_auto(self):
+        """the first step of an "auto" engine runs eagerly; its census decides the format of every later step"""
+        slow, total = self.attn_slow_stats()
+        self.attn_slow_fraction = slow / total if total else 0.0
+        if self.attn_slow_fraction > self.AUTO_SLOW_FRACTION:
+            self.set_attn_p_format("bf16")
+        self._attn_auto_pending = False
+
+    def _denoise_step_guided(self, latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers):
+        B, T, F, H, W = self.geometry
+        if B % 3:
+            raise _lib.S2VError(f"denoise_step(subject=True): a geometry of {B} samples is no whole number of triples [u | r | f]")
+        b = B // 3
+        want = (b, F, self.cfg.in_channels, H, W)
+        for name, x in (("latents", latents), ("x0_hist", x0_hist), ("noise", noise)):
+            if x is not None and (tuple(x.shape) != want or not x.is_contiguous()):
+                raise _lib.S2VError(f"denoise_step(subject=True): {name} must be contiguous {list(want)} for {b} videos per call, got {list(x.shape)}")
+        t_arr = (ctypes.c_float * b)(*[float(t) for t in _per_video("timestep", timestep, b)])
+        c_arr = (_lib.SchedCoefC * b)(*_per_video("coef", coef, b))
+        b_arr = None if blend is None else (_lib.BlendC * b)(*_per_video("blend", blend, b))
+        auto = self._attn_auto_pending
+        if auto:
+            self.attn_slow_stats(reset=True)
+        self._arm(cache)            # the library refuses an armed step by name: the step cache and the attention map assume pairs
+        self._arm_attn(attn_layers)
+        _lib.check(_lib.lib().s2v_denoise_step_guided(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
+                                                      int(use_graph and not auto), _lib.stream_ptr()))
+        if auto:
+            self._settle_attn_auto()
 
     # ---- CFG-parallel: this engine holds ONE sample of the CFG pair (geometry B = 1); include/s2v_hip.h, dist.CfgPair ---------------------------
     def cfg_pair(self):

@@ -27,6 +27,7 @@ from .schedulers import CogVideoXDPMScheduler, randn_videos  # noqa: F401
 
 
 MAX_VIDEOS = 4   # videos per call: the library runs at most S2V_MAX_BATCH = 8 samples, the CFG pairs of four videos
+MAX_SUBJECT_VIDEOS = 2   # ... and under subject guidance the triples of two videos, 6 samples
 
 
 def expand_prompts(embeds, num_videos_per_prompt=1):
@@ -38,6 +39,21 @@ def expand_prompts(embeds, num_videos_per_prompt=1):
 def cfg_text(negative_prompt_embeds, prompt_embeds, num_videos_per_prompt=1):
     """the transformer's text batch [negative x b | positive x b] (custom_cogvideox_pipe.py:196), b = P * num_videos_per_prompt"""
     return torch.cat([expand_prompts(negative_prompt_embeds, num_videos_per_prompt), expand_prompts(prompt_embeds, num_videos_per_prompt)], dim=0)
+
+
+def subject_layout(b):
+    """the samples of a subject-guidance step of b videos, in the library's order [u x b | r x b | f x b] (s2v_set_conditioning_triples): for
+    sample j {"sample": "u" / "r" / "f", "video": v, "text": its row of the call's [negative x b | positive x b] text batch (u and r both read
+    the negative row of their video), "ref": "null" or "ref", "entry": its row of the reference table [null x b | ref x b | ref x b], which is j
+    itself: the forward's `j mod n_ref` with n_ref = 3b}.  u = negative text + null reference, r = negative text + the reference, f = positive
+    text + the reference.  Host integers only"""
+    if b < 1 or b > MAX_SUBJECT_VIDEOS:
+        raise ValueError(f"subject guidance runs the triples of 1..{MAX_SUBJECT_VIDEOS} videos per step, got b = {b}")
+    out = []
+    for j in range(3 * b):
+        kind, v = "urf"[j // b], j % b
+        out.append(dict(sample=kind, video=v, text=v + (b if kind == "f" else 0), ref="null" if kind == "u" else "ref", entry=j))
+    return out
 
 
 class StepCache:
@@ -225,12 +241,54 @@ class S2VPipeline:
                 raise ValueError(f"The value of strength should in [0.0, 1.0] but is {st}")
         return tuple(out)
 
+    @staticmethod
+    def check_subject(subject_guidance_scale, guidance_scale, cfg_parallel=None, ulysses=None, step_cache=None, attention_map=None, fused=True):
+        """every refusal of a subject-guidance call that needs no video count (no device is touched)"""
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`subject_guidance_scale` together with `{name}`: the triple step runs on one GPU; "
+                                                          f"CFG-parallel and Ulysses run CFG pairs")
+        for name, arg in (("step_cache", step_cache), ("attention_map", attention_map)):
+            if arg is not None:
+                raise ValueError(f"`subject_guidance_scale` together with `{name}`: the step cache and the attention map assume CFG pairs")
+        if not fused:
+            raise ValueError("`subject_guidance_scale` together with fused=False: the triple combine lives in the fused step; fused=False is the "
+                             "reference's seam sequence")
+        for g in guidance_scale if isinstance(guidance_scale, (list, tuple)) else [guidance_scale]:
+            if g <= 1.0:
+                raise ValueError(f"`subject_guidance_scale` with guidance_scale = {g}: every guidance scale must be > 1 (subject guidance extends "
+                                 f"the CFG pair; without CFG there is nothing to extend)")
+        for g in subject_guidance_scale if isinstance(subject_guidance_scale, (list, tuple)) else [subject_guidance_scale]:
+            if isinstance(g, bool) or not isinstance(g, (int, float)) or not math.isfinite(g):
+                raise ValueError(f"`subject_guidance_scale` must be a finite number, or a list of them with one entry per video, got {g!r}")
+
+    @staticmethod
+    def check_subject_batch(b, subject_guidance_scale, negative_ref_img_states, ref_img_states):
+        """the subject scales as a list of b entries (a scalar is repeated; a list is prompt-major), after the refusals that need the video
+        count: more than MAX_SUBJECT_VIDEOS videos, a list of another length, a null reference that is not [1 | b, 1, C, h, w]"""
+        if b > MAX_SUBJECT_VIDEOS:
+            raise ValueError(f"`subject_guidance_scale` with {b} videos per call: at most {MAX_SUBJECT_VIDEOS} videos (the triple step runs three "
+                             f"samples per video, {3 * MAX_SUBJECT_VIDEOS} of the library's 8)")
+        if isinstance(subject_guidance_scale, (list, tuple)):
+            if len(subject_guidance_scale) != b:
+                raise ValueError(f"`subject_guidance_scale` is a list of {len(subject_guidance_scale)} entries for b = {b} videos: one entry per "
+                                 f"video (prompt-major), or a scalar for all")
+            scales = [float(g) for g in subject_guidance_scale]
+        else:
+            scales = [float(subject_guidance_scale)] * b
+        n = negative_ref_img_states
+        if n is not None and (n.ndim != 5 or n.shape[0] not in (1, b) or tuple(n.shape[1:]) != tuple(ref_img_states.shape[1:])):
+            raise ValueError(f"`negative_ref_img_states` must be [1 | {b}, {', '.join(str(x) for x in ref_img_states.shape[1:])}] (the shape of a "
+                             f"row of `ref_img_states`; one row, or one per video), got {tuple(n.shape)}")
+        return scales
+
     @classmethod
-    def video_plan(cls, scheduler, num_inference_steps, strength, guidance_scale, use_dynamic_cfg, dtype):
+    def video_plan(cls, scheduler, num_inference_steps, strength, guidance_scale, use_dynamic_cfg, dtype, guidance_subject=None):
         """everything the one-video call with these arguments does per step, in its order: {"num_inference_steps": the scheduler's count,
         "timesteps": its timesteps (strength: the last int(n * strength) of them; None: text-to-video, all), "steps": per step {"t",
         "t_back", "first" (DPM: no x0 history yet), "guidance" (the dynamic-CFG curve runs on the video's own index and count), "coef",
-        "draws" (noise draws from the video's generator: DPM draws once, twice on a multistep step)}}.  No device is touched"""
+        "draws" (noise draws from the video's generator: DPM draws once, twice on a multistep step)}}.  No device is touched.
+        guidance_subject: the subject scale of a subject-guidance call, constant over the plan (the dynamic-CFG curve modulates the text
+        scale only); None: a pair call, whose coefficient sets are built exactly as before"""
+        sub = {} if guidance_subject is None else {"guidance_subject": guidance_subject}
         n = int(num_inference_steps)
         ts = scheduler.timesteps_for(n)
         n_loop = n
@@ -246,9 +304,9 @@ class S2VPipeline:
                 g = 1 + guidance_scale * ((1 - math.cos(math.pi * ((n_loop - i) / n_loop) ** 5.0)) / 2)
             t_back = ts[i - 1] if is_dpm and i > 0 else None
             if is_dpm:
-                coef = scheduler.coef(t, t_back, i == 0, dtype, g, num_inference_steps=n)
+                coef = scheduler.coef(t, t_back, i == 0, dtype, g, num_inference_steps=n, **sub)
             else:
-                coef = scheduler.coef(t, dtype, g, num_inference_steps=n)
+                coef = scheduler.coef(t, dtype, g, num_inference_steps=n, **sub)
             steps.append(dict(t=t, t_back=t_back, first=i == 0, guidance=g, coef=coef, draws=(2 if coef.kind == 2 else 1) if is_dpm else 0))
         return dict(num_inference_steps=n, timesteps=ts, steps=steps)
 
@@ -395,7 +453,7 @@ class S2VPipeline:
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
                  video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None,
-                 attention_map=None):
+                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -442,7 +500,16 @@ class S2VPipeline:
         {"subject": [b, F_lat, H/16, W/16] fp32, "text": [n_spans, b, F_lat, H/16, W/16], "count", "layers", "steps", "skipped_steps"}: the
         positive halves of the CFG pairs, head mean, then the mean over the collected (layer, step) launches.  The latents are those of the call
         without it, bit for bit.  Scalars only; refused with per-video lists, several input videos, cfg_parallel=, ulysses=, fused=False and
-        fp8 QK^T ('fp8-qk', and 'fp8-auto' where it is active)."""
+        fp8 QK^T ('fp8-qk', and 'fp8-auto' where it is active).
+        subject_guidance_scale: a scale of its own for the reference image -- None (the call as it is without the feature, launch for launch), a
+        float, or a list with one entry per video (prompt-major).  Every step then runs three samples per video, u (negative prompt, the null
+        reference), r (negative prompt, the reference), f (prompt, the reference), and combines them in fp32 as
+            v = (u + subject_guidance_scale * (r - u)) + guidance_scale * (f - r)
+        so 1.0 is today's call mathematically.  use_dynamic_cfg modulates guidance_scale only.  negative_ref_img_states [1 | b, 1, C, h, w]: the
+        null reference (None: zeros, the zero latent; none is recommended); with negative_ref_img_states = ref_img_states the latents are the
+        plain call's bit for bit, whatever the scale.  At most 2 videos per call; composes with video= / strength, mask=, change_map=, paste_back,
+        use_graph and the per-video lists; refused with guidance_scale <= 1, cfg_parallel=, ulysses=, step_cache=, attention_map= and
+        fused=False."""
         self.step_cache_report = None
         self.attention_maps = None
         if change_map is not None and mask is not None:
@@ -453,7 +520,11 @@ class S2VPipeline:
             mask = change_map
         if mask is not None and video is None:
             self.check_mask(mask, None, 1, what=what)
-        per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength))
+        per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength, subject_guidance_scale))
+        if subject_guidance_scale is not None:
+            self.check_subject(subject_guidance_scale, guidance_scale, cfg_parallel, ulysses, step_cache, attention_map, fused)
+        elif negative_ref_img_states is not None:
+            raise ValueError("`negative_ref_img_states` applies only together with `subject_guidance_scale` (it is the reference of the third sample)")
         if not isinstance(strength, (list, tuple)) and (strength < 0 or strength > 1):
             raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if video is not None:
@@ -497,12 +568,23 @@ class S2VPipeline:
             attention_map = self.check_attention_map(attention_map, self.transformer.config.num_layers,
                                                      getattr(self.transformer.config, "weight_format", None), per_video, cfg_parallel, ulysses,
                                                      fused, video is not None and b > 1)
+        subject = None   # a subject-guidance call: the null references [1 | b, 1, C, h, w]; its scales ride in the plans' coefficient sets
+        sgs = [None] * b
+        if subject_guidance_scale is not None:
+            sgs = self.check_subject_batch(b, subject_guidance_scale, negative_ref_img_states, ref_img_states)
+            subject = torch.zeros_like(ref_img_states[:1]) if negative_ref_img_states is None else negative_ref_img_states
         own_plans = per_video or (video is not None and b > 1)   # every video on the plan of its own one-video call
-        per = [(guidance_scale, num_inference_steps, strength)]   # a call with scalars: one plan, built once and shared by all b videos
+        per = [(guidance_scale, num_inference_steps, strength, sgs[0])]   # a call with scalars: one plan, built once and shared by all b videos
         if own_plans:
-            per = list(zip(*self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses)))
-        plans = [self.video_plan(self.scheduler, n, st if video is not None else None, g, use_dynamic_cfg, self.transformer.dtype) for g, n, st in per]
+            per = list(zip(*self.check_per_video(b, guidance_scale, num_inference_steps, strength, video, cfg_parallel, ulysses), sgs))
+        plans = [self.video_plan(self.scheduler, n, st if video is not None else None, g, use_dynamic_cfg, self.transformer.dtype,
+                                 **({} if gs is None else {"guidance_subject": gs})) for g, n, st, gs in per]
         self.check_plans(plans, self.scheduler, generator)
+        if subject is not None:
+            return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
+                                 num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
+                                 callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
+                                 step_cache, attention_map, subject=subject)
         return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
                              num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                              callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
@@ -510,7 +592,7 @@ class S2VPipeline:
 
     def _denoise(self, plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator, latents,
                  output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video,
-                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map):
+                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None):
         """the one denoise loop: b = len(plans) videos, each on its video_plan; iteration i applies step i of every video that still has one.
         The videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers;
         when the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
@@ -520,7 +602,10 @@ class S2VPipeline:
         follow ONE plan of steps, and cfg_parallel / ulysses, which run one video, were refused with it.
         mask [1 | b,F,H,W] (check_mask): z0, noise0 and the latent masks follow the internal order and the shrinking prefix exactly as the
         latents do; video k blends at the next timestep of its own plan and is flagged on its own last step.  levels: the mask is a change
-        map, and video k keeps the cells of level <= change_map_plan(n_k)[i] after its step i, n_k the steps of its own plan"""
+        map, and video k keeps the cells of level <= change_map_plan(n_k)[i] after its step i, n_k the steps of its own plan
+        subject: a subject-guidance call (None: a pair call, which touches no triple entry) -- the null references [1 | b,1,C,h,w]; every
+        geometry is 3a samples [u x a | r x a | f x a] of the a active videos, conditioned by set_conditioning_triples and stepped by the
+        guided step with the subject scale of each video's coefficient sets; everything else of the loop is the pair call's"""
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         b = len(plans)
@@ -546,6 +631,10 @@ class S2VPipeline:
         ref = ref_img_states.to(dev, dt)
         if ref.shape[0] > 1:
             ref = internal(ref)
+        if subject is not None:
+            subject = subject.to(dev, dt)
+            if subject.shape[0] > 1:
+                subject = internal(subject)
         rope = ref_rope = None
         if tr.config.use_rotary_positional_embeddings:
             cos, sin = tables.rope_tables(height, width, F)
@@ -573,11 +662,17 @@ class S2VPipeline:
                 return ref[:a]
             return ref.expand(a, -1, -1, -1, -1).contiguous() if rows else ref
 
+        def condition(a):   # the hoisted conditioning of the a active videos: the CFG pairs, or the triples of a subject-guidance call
+            if subject is None:
+                eng.set_conditioning(active_text(a), active_ref(a, False))
+            else:   # the library lays [negative x a | positive x a] out as [u x a | r x a | f x a] (subject_layout)
+                eng.set_conditioning_triples(active_text(a), active_ref(a, True), subject[:a] if subject.shape[0] > 1 else subject)
+
         def set_active(a):
             # CFG-parallel: B = 1 with this rank's half of [negative | positive] (custom_cogvideox_pipe.py:196) and the un-duplicated reference tokens
-            eng.set_geometry(2 * a if cfg_parallel is None else 1, text.shape[1], F, H, W)
+            eng.set_geometry((2 * a if subject is None else 3 * a) if cfg_parallel is None else 1, text.shape[1], F, H, W)
             eng.prepare_tables(height, width)
-            eng.set_conditioning(active_text(a), active_ref(a, False))
+            condition(a)
             if mask is not None:   # prefixes of the same buffers, as latents[:a] is
                 eng.set_blend(z0[:a], noise0[:a], lat_mask[:a])
 
@@ -666,7 +761,7 @@ class S2VPipeline:
                         collect = am_steps is not None and i in am_steps and cache != "reuse"
                         eng.denoise_step(latents[:a], ts, coefs, x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph,
                                          blend=None if mask is None else [blends[p][i] for p in range(a)], cache=cache,
-                                         attn_layers=attention_map.layers if collect else None)
+                                         attn_layers=attention_map.layers if collect else None, **({} if subject is None else {"subject": True}))
                         if collect:
                             am_ran.append(i)
                 else:
@@ -715,7 +810,7 @@ class S2VPipeline:
                     if new_text is not text:
                         text = new_text.to(dev, dt)
                         if fused:  # the hoisted text projection of the active rows follows the new embeddings
-                            eng.set_conditioning(active_text(active), active_ref(active, False))
+                            condition(active)
                     negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
             if attention_map is not None:
                 self.attention_maps = self._read_attention_maps(eng, attention_map, b, am_ran, am_skipped)

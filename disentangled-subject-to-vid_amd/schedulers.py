@@ -149,14 +149,15 @@ class _SchedulerBase:
 
 
 class CogVideoXDDIMScheduler(_SchedulerBase):
-    def coef(self, timestep, dtype, guidance=1.0, num_inference_steps=None):
-        """scalars of scheduling_ddim_cogvideox.py:364-394 for one step"""
+    def coef(self, timestep, dtype, guidance=1.0, num_inference_steps=None, guidance_subject=0.0):
+        """scalars of scheduling_ddim_cogvideox.py:364-394 for one step; guidance_subject: the subject scale of the triple combine (only the
+        subject-guidance step reads it)"""
         _, _, a_t, a_prev = self._alphas(timestep, num_inference_steps)
         b_t = 1 - a_t
         at = ((1 - a_prev) / (1 - a_t)) ** 0.5
         bt = a_prev**0.5 - a_t**0.5 * at
         c = _lib.SchedCoefC()
-        c.kind, c.guidance = 0, float(np.float32(guidance))
+        c.kind, c.guidance, c.guidance_subject = 0, float(np.float32(guidance)), float(np.float32(guidance_subject))
         c.c_x0_x, c.c_x0_v = self._sc(a_t**0.5, dtype), _f32(b_t**0.5)
         c.a_t, c.b_t = self._sc(at, dtype), _f32(bt)
         return c
@@ -170,8 +171,8 @@ class CogVideoXDDIMScheduler(_SchedulerBase):
 
 
 class CogVideoXDPMScheduler(_SchedulerBase):
-    def coef(self, timestep, timestep_back, first, dtype, guidance=1.0, num_inference_steps=None):
-        """scalars of scheduling_dpm_cogvideox.py:391-434; `first` = no old_pred_original_sample yet"""
+    def coef(self, timestep, timestep_back, first, dtype, guidance=1.0, num_inference_steps=None, guidance_subject=0.0):
+        """scalars of scheduling_dpm_cogvideox.py:391-434; `first` = no old_pred_original_sample yet; guidance_subject as the DDIM coef's"""
         _, prev_t, a_t, a_prev = self._alphas(timestep, num_inference_steps)
         b_t = 1 - a_t
         lamb = ((a_t / (1 - a_t)) ** 0.5).log()
@@ -181,7 +182,7 @@ class CogVideoXDPMScheduler(_SchedulerBase):
         m2 = (-2 * h).expm1() * a_prev**0.5
         mn = (1 - a_prev) ** 0.5 * (1 - (-2 * h).exp()) ** 0.5
         c = _lib.SchedCoefC()
-        c.guidance = float(np.float32(guidance))
+        c.guidance, c.guidance_subject = float(np.float32(guidance)), float(np.float32(guidance_subject))
         c.c_x0_x, c.c_x0_v = self._sc(a_t**0.5, dtype), _f32(b_t**0.5)
         c.m1, c.m2, c.mn = self._sc(m1, dtype), _f32(m2), self._sc(mn, dtype)
         if first or prev_t < 0:

@@ -245,13 +245,19 @@ typedef struct s2v_sched_coef {
     int32_t kind;      /* 0 DDIM, 1 DPM first/last step, 2 DPM multistep */
     float guidance;    /* classifier-free guidance scale of this step */
     float c_x0_x, c_x0_v, a_t, b_t, m1, m2, m3, m4, mn;
-    float pad;
+    float guidance_subject;   /* subject guidance scale of the triple combine (flags bit3, s2v_denoise_step_guided); the pair paths never read it */
 } s2v_sched_coef;
 
 /* scheduler.step (+ optional CFG combine, custom_cogvideox_pipe.py:266-296); ctx may be NULL.
  * flags bit0: noise_pred is the CFG pair [2,n] (uncond, cond) and is combined with coef->guidance;
  *       bit1: noise_pred is fp32 (what the reference hands to scheduler.step after .float());
- *       bit2: latents_out is fp32 and un-rounded (scheduler.step's own return value) instead of `dtype`.
+ *       bit2: latents_out is fp32 and un-rounded (scheduler.step's own return value) instead of `dtype`;
+ *       bit3: noise_pred is the subject-guidance triple [3,n] = (u, r, f) -- u: negative text, null reference; r: negative text, the reference;
+ *             f: positive text, the reference -- combined in fp32 as
+ *                 v = (u + coef->guidance_subject * (r - u)) + coef->guidance * (f - r)
+ *             five operations that each round on their own, in this association.  guidance_subject = 1 is the pair's r + g (f - r)
+ *             mathematically, and a u plane that holds the r plane's bits gives the pair's result bit for bit for ANY guidance_subject
+ *             (r - u = +0).  Bit0 and bit3 together are refused.
  * latents in/out [n] (may alias); x0_hist fp32 [n] (DPM: read as old x0, then overwritten; may be NULL for DDIM);
  * noise [n] in `dtype` (DPM only). */
 S2V_API int s2v_sched_step(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags,
@@ -339,7 +345,29 @@ S2V_API int s2v_denoise_step_masked(s2v_ctx* ctx, void* latents, const float* ti
 S2V_API int s2v_sched_step_masked(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
                           const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0, const void* noise0,
                           const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype, s2v_stream stream);
-/* pointer to the [B,F,C,H,W] model output of the last s2v_denoise_step (context-owned, model dtype) */
+/* ---- subject guidance: a scale of its own for the reference image ------------------------------------------------------------------------------
+ * The CFG pair gives both samples the reference, so `guidance` amplifies text against no text.  Three samples per video separate the two:
+ * u (negative text, a null reference), r (negative text, the reference), f (positive text, the reference), combined as flags bit3 of
+ * s2v_sched_step states.  Geometry: B = 3b samples [u x b | r x b | f x b], b = 1 or 2 videos (S2V_MAX_BATCH stays 8).
+ * s2v_set_conditioning_triples: text [2b,T,text_embed_dim] = [negative x b | positive x b], ref_latents [b,1,C,H,W], null_ref_latents
+ * [n_null,1,C,H,W] with n_null = 1 (one for every video) or b.  Video v's [negative | positive] pair is projected by one launch of a one-video
+ * call's shape (M = 2T) and its negative rows go to samples u_v and r_v; every reference and null reference runs the per-reference patch
+ * embedding.  Samples r and f therefore hold the bits a pair call's conditioning holds, wherever the two geometries agree on split K (as
+ * s2v_set_conditioning_refs words it).  The reference table is one entry per sample, [null x b | ref x b | ref x b] (n_ref = B), allocated here
+ * and counted as workspace.  A change of layout (pairs <-> triples) drops a captured step; the context records which layout it holds, since
+ * B = 6 is three pairs or two triples by shape alone.
+ * s2v_denoise_step_guided: the whole step on that geometry -- the forward on the triples sharing each video's latent (`latents`, `x0_hist`,
+ * `noise` [b][F,C,H,W]; timesteps / coefs HOST arrays of b entries as s2v_denoise_step_videos), then the triple combine with
+ * coefs[k].guidance_subject and coefs[k].guidance and the scheduler step, in place.  blends != NULL: the masked form, b records, after
+ * s2v_set_blend for b videos.  One captured graph serves every step; it is another graph than a pair step's.
+ * Refused by name: B not a multiple of 3 or b > 2; conditioning not set by s2v_set_conditioning_triples; a shard context; a pending
+ * CFG-parallel split; an armed step-cache mode or attention map (both assume pairs).  s2v_denoise_step, _videos and _masked refuse a context
+ * conditioned as triples. */
+S2V_API int s2v_set_conditioning_triples(s2v_ctx* ctx, const void* text_dev, const void* ref_latents_dev, const void* null_ref_latents_dev,
+                                         int32_t n_null, s2v_stream stream);
+S2V_API int s2v_denoise_step_guided(s2v_ctx* ctx, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
+                                    float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream);
+/* pointer to the [B,F,C,H,W] model output of the last s2v_denoise_step (context-owned, model dtype); [3b,...] after s2v_denoise_step_guided */
 S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 
 /* ---- Step cache: a step whose timestep embedding barely moved skips the block stack ---------------------------------------------------------
