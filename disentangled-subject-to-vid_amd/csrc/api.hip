@@ -132,6 +132,8 @@ struct s2v_ctx {
     int sk_tiles = 0; float* sk_ws = nullptr; unsigned* sk_cnt = nullptr;  // split-K workspace of the geometry (0: none)
     unsigned* vt_amax = nullptr;             // AttnArgs::vt_amax: VT_AMAX_WORDS words (attn_p_format 1)
     int* attn_queue = nullptr;               // nine counters of the persistent attention launch (zero between launches)
+    char* kv_ws = nullptr;                   // AttnArgs::kv_ws: counters + partial slots of the KV-split q-blocks, carved with the geometry (in ws)
+    int64_t kv_ws_bytes = 0;
     unsigned long long* attn_stats = nullptr;  // AttnArgs::stats: 256 x [slow paths, (wave, KV tile) pairs] of the attn_q4 launches (s2v_attn_slow_stats)
     hipStream_t side = nullptr;              // fork/join stream for the row-tail launches of split GEMMs
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -841,6 +843,10 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     // never splits K: split-K changes the reduction order, and a rank's row count must not pick a different one than the single engine's
     c->sk_tiles = (!c->shard && c->mfma && ((c->M + 255) / 256) * ((D + 255) / 256) * 2 <= c->num_cus) ? c->num_cus : 0;
     const int64_t osk = carve((int64_t)c->sk_tiles * 262144), oskc = carve((int64_t)c->sk_tiles * 4);
+    // KV split of the four-wave attention launch (kernels.h attn_plan): counters + the partial slots of every head's split q-blocks, at the
+    // sequence the attention sees (gN) and the heads of this rank.  Every splitting format has the same plan; the fp8-QK^T formats do not split
+    c->kv_ws_bytes = ((c->mfma || c->h16) && !c->fp8_qk) ? attn_kv_ws_bytes(attn_plan((int)c->gN, ATTN_FMT_Q4), BH) : 0;
+    const int64_t okv = carve(c->kv_ws_bytes);
     // shard: the head-sharded full-N buffers, the exchange buffers and the row maps
     const int64_t P = c->sp, Dp = D / P, Mg = (int64_t)B * c->gN, Mgpad = rup(Mg, 256) + 256;
     // the O exchange: n rows of a head group are bf16 [n][D/p], or (fp8 engine) MX e4m3 [n][D/p] followed by the rows' scale dwords [n][D/(128p)],
@@ -869,6 +875,7 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     c->hq = (unsigned char*)(w + ohq); c->hs = (unsigned char*)(w + ohs);
     c->q8 = (unsigned char*)(w + oq8); c->q8s = (unsigned short*)(w + oq8s); c->k8 = (unsigned char*)(w + ok8); c->k8s = (unsigned*)(w + ok8s);
     c->sk_ws = (float*)(w + osk); c->sk_cnt = (unsigned*)(w + oskc);
+    c->kv_ws = c->kv_ws_bytes ? w + okv : nullptr;
     if (c->shard) {
         c->QKVh = w + oQh; c->Oh = w + oOh; c->sbuf = w + osb; c->rbuf = w + orb; c->nsend = w + ons; c->nrecv = w + onr; c->proj_full = w + opf;
         c->rmap = (int*)(w + ormap); c->nmap = (int*)(w + onmap);
@@ -1324,6 +1331,9 @@ static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w,
     a.B = c->B; a.H = o.H; a.Ntok = o.Ntok; a.scale = 0.125f;
     a.queue = c->attn_queue; a.num_cus = c->num_cus;  // launches of one context are ordered on its stream: one queue suffices
     a.p16 = p16 ? 1 : 0; a.vt_amax = c->vt_amax;
+    // the split workspace of the geometry where this call fits it (every caller at the geometry's own token count and heads does); a call of
+    // another shape through the AttnProcessor seam takes the process-wide one (attention_q4.hip), with the operator entries' restriction
+    if (c->kv_ws && attn_kv_ws_bytes(attn_plan(o.Ntok, ATTN_FMT_Q4), (int64_t)c->B * o.H) <= c->kv_ws_bytes) { a.kv_ws = c->kv_ws; a.kv_ws_bytes = c->kv_ws_bytes; }
     a.stats = c->attn_stats;
     a.valu_only = c->cfg.force_simple;
     a.stagger = c->attn_stagger;

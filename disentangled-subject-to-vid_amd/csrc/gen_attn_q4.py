@@ -16,7 +16,7 @@ fragment feeds two MFMAs; JB = 1 -> attn_q8, eight waves x 32 rows, two waves pe
 dimension 64 (16 MFMA = 512 matrix-pipe cycles against 80 softmax VALU per 32 rows) one wave per SIMD is issue-bound.
 Register file (per lane; numbers for JB = 2, the JB = 1 map is the same list packed):
   v[0:127]    S^T accumulators st[buf][j][kb] (16 each): buf = tile parity, j = 32-row block, kb = 32-key half
-  v[128:159]  -m of the rows of block j (16 copies: the C operand of the first MFMA of a chain)
+  v[128:159]  -m of the rows of block j (16 copies: the C operand of the first MFMA of a chain); OUT: the first copy of each block (v128, v144)
   v[160:191]  P as bf16 pairs pk[j][s] (4 each): B operand of the P.V step s (16 keys)
   v[192:199]  exp2 results in flight, two groups of four
   v[200:207]  row sums ps[set][j][x] of the tile whose P is being built (set = tile parity)
@@ -523,14 +523,15 @@ def main():
         for jb, name, f8, p16 in ((2, "Q4", False, False), (1, "Q8", False, False), (2, "Q4F", True, False), (2, "Q4H", False, True), (2, "Q4FH", True, True)):
             layout(jb, f8, p16)
             write_inc(os.path.join(here, f"attn_{name.lower()}_body.inc"), gen())
-            clob = [f"v{r}" for r in list(range(0, VIN)) + list(range(VS, VS + 12))] + [f"a{r}" for r in range(KF, VF + 32)]
+            negm = [NEGM + 16 * j for j in range(jb)]  # OUT: -m of the lane's row of block j (the first of its 16 copies): a KV-split part's reference exponent
+            clob = [f"v{r}" for r in list(range(0, VIN)) + list(range(VS, VS + 12)) if r not in negm] + [f"a{r}" for r in range(KF, VF + 32)]
             clob += [f"s{r}" for r in (S_T, S_END, S_KADV, S_VADV, S_THR, S_RET, S_X0, S_X1, S_ONES)]
             extra = []
             if f8:
                 clob += [f"s{r}" for r in (S_KSX, S_NTM1, S_KSA, S_KSA + 1)]
                 extra = [("KS", "v", KS, 4), ("QS", "v", QS, 2), ("KIN", "v", KIN, 4), ("KSB", "s", S_KSB, 2)]  # KS is in / out ("+"): the body reloads the ring
             for nm, cls, base, n in [("VIN", "v", VIN, 8), ("LRUN", "v", LRUN, 2), ("QF", "a", QF, (8 if f8 else 16) * jb), ("PTR", "s", S_KPTR, 4),
-                                     ("SIN", "s", S_NT, 4)] + extra + [(f"OT{j}", "a", OT + 32 * j, 32) for j in range(jb)]:
+                                     ("SIN", "s", S_NT, 4)] + extra + [(f"OT{j}", "a", OT + 32 * j, 32) for j in range(jb)] + [(f"NEGM{j}", "v", r, 1) for j, r in enumerate(negm)]:
                 f.write(define_regs(f"{name}_{nm}", cls, base, n))
             f.write(define_regs(f"{name}_CNT", "s", S_CNT))
             f.write(define_clobbers(f"{name}_CLOBBERS", clob))

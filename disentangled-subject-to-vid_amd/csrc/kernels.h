@@ -200,6 +200,9 @@ struct AttnArgs {
     int order;                 // persistent four-wave launch: 0 = a head's q-blocks on one XCD (default), 1 = dealt over the XCDs (experiment, attn_qx_persist_k)
     int stagger;               // persistent four-wave launch: workgroup (blockIdx >> 3) = slot s of its XCD starts s * stagger * 64 cycles late (0 = together); see attn_qx_persist_k
     int valu_only;             // fp32 only: stay on attn_simple_k (cfg.force_simple) instead of the fp32-MFMA kernel attn_f32m_k
+    // four-wave forms whose attn_plan splits: counters + partial slots (attn_kv_ws_bytes; the counters zero, which every launch restores).  The
+    // engine carves it with the geometry; null = the launch takes the process-wide one, grown on demand (operator entries: never under capture)
+    void* kv_ws; int64_t kv_ws_bytes;
 };
 // sequences up to this length run attn_pp (launch_attn_bf16), longer ones attn_q4 (profiles/r03_attn_short_sequences.txt: attn_pp 9 % ahead at
 // 4000 tokens, attn_q4 2 % ahead at 6000, 7 % at 8192); the fp8 engine's MX output is attn_q4's at any length
@@ -219,6 +222,56 @@ __host__ __device__ static inline int vt_f16_shift(unsigned amax_bits) {
     return s > 100 ? 100 : (s < -100 ? -100 : s);
 }
 static inline bool attn_runs_q4(int Ntok, bool mx_out) { return mx_out || Ntok > ATTN_PP_MAX_TOKENS; }
+// KV split of the four-wave launch (attention_q4.hip).  A head's q-blocks cost the same, so B * H * nqb items leave the last round of a
+// persistent launch mostly idle (C3: 7200 items on 256 workgroups = 28.125 rounds, run as 29; now 7008 whole items and 768 parts).  The trailing `split` q-blocks of every head are
+// therefore cut BY KEY RANGE into S parts of contiguous KV tiles [t[s], t[s + 1]); a part runs the unchanged body over its tiles and leaves
+// (unnormalised O, l, -m) in a workspace slot, and the last part to arrive merges the S slots in the order s = 0 .. S - 1 and runs the epilogue.
+// attn_plan is the ONLY place that decides the split, and it sees the token count and the format alone: B, the head count, the CU count, the
+// launch form and the entry point cannot enter, so a row's bits are a function of (Ntok, format, inputs) -- the bitwise B = 1 == half of B = 2,
+// head-shard and per-item == persistent tests rest on that.  Pure host code (tests/test_attn_plan_cpu.py through s2v_diag_attn_plan).
+enum { ATTN_FMT_Q4 = 0, ATTN_FMT_Q4H = 1, ATTN_FMT_Q4HH = 2, ATTN_FMT_Q4F = 3, ATTN_FMT_Q4FH = 4, ATTN_FMT_COUNT = 5 };
+#ifndef ATTN_KV_PARTS
+#define ATTN_KV_PARTS 4         // S: parts of a split q-block (4 and 8 measured: profiles/r19_attn_kv_split.txt)
+#endif
+#ifndef ATTN_KV_SPLIT_BLOCKS
+#define ATTN_KV_SPLIT_BLOCKS 2  // trailing q-blocks of a head that are split (1 and 2 measured)
+#endif
+#define ATTN_KV_MIN_TILES 8     // shortest part: the body pre-stages K tiles 0 .. 3 and V^T tiles 0 .. 1 and walks its last five tiles in phase B
+#define ATTN_KV_SLOT_BYTES (4 * 2 * 32 * 64 * 4 + 2 * 4 * 2 * 64 * 4)  // a part's slot: O^T fp32 [wave][j][register][lane], then l and -m [wave][j][lane]
+struct AttnPlan {
+    int whole;                 // q-blocks per head that run as one item over all KV tiles
+    int split;                 // trailing q-blocks per head cut by key range (0: no split; then S = 1)
+    int S;                     // parts per split q-block
+    int t[ATTN_KV_PARTS + 1];  // part s = KV tiles [t[s], t[s + 1]); t[0] = 0, t[S] = ceil(Ntok / 64)
+};
+// the head of the plan: whole / split / S.  __host__ __device__: the kernels recompute it from (Ntok, format) where they need it instead of
+// carrying it across the body, which leaves them no registers to spare
+__host__ __device__ static inline void attn_plan_head(int Ntok, int format, int& whole, int& split, int& S) {
+    const int nqb = (Ntok + 255) / 256, nt = (Ntok + 63) / 64;
+    whole = nqb; split = 0; S = 1;
+    // short sequences run attn_pp; the fp8-QK^T formats keep whole items (their block-scale ring is not offset by a part's first tile)
+    if (Ntok <= ATTN_PP_MAX_TOKENS || format == ATTN_FMT_Q4F || format == ATTN_FMT_Q4FH || format < 0 || format >= ATTN_FMT_COUNT) return;
+    int s = nt / ATTN_KV_MIN_TILES;
+    if (s > ATTN_KV_PARTS) s = ATTN_KV_PARTS;
+    const int sp = nqb < ATTN_KV_SPLIT_BLOCKS ? nqb : ATTN_KV_SPLIT_BLOCKS;
+    if (s < 2 || sp < 1) return;
+    whole = nqb - sp; split = sp; S = s;
+}
+// first KV tile of part s of S over nt tiles (s = S: nt): the first nt % S parts are one tile longer
+__host__ __device__ static inline int attn_part_tile(int nt, int S, int s) { return s * (nt / S) + (s < nt % S ? s : nt % S); }
+static inline AttnPlan attn_plan(int Ntok, int format) {
+    AttnPlan p{};
+    attn_plan_head(Ntok, format, p.whole, p.split, p.S);
+    for (int s = 0; s <= p.S; ++s) p.t[s] = attn_part_tile((Ntok + 63) / 64, p.S, s);
+    return p;
+}
+// bytes of AttnArgs::kv_ws for a launch of B * H <= ATTN_KV_MAX_BH heads: a head of fixed size -- 8 sub-item queue counters, then one arrival
+// counter per split q-block, all zero between launches -- then B * H * split * S slots; 0 when the plan does not split
+#define ATTN_KV_MAX_BH 4096
+#define ATTN_KV_WS_HEAD ((8 + ATTN_KV_MAX_BH * ATTN_KV_SPLIT_BLOCKS) * 4 + 224)  // a multiple of 256
+static inline int64_t attn_kv_ws_bytes(const AttnPlan& p, int64_t BH) {
+    return p.split == 0 ? 0 : ATTN_KV_WS_HEAD + BH * p.split * p.S * (int64_t)ATTN_KV_SLOT_BYTES;
+}
 // q / k of the (normalised, rotated) QKV buffer -> the MX e4m3 images above (elementwise.hip)
 int launch_qk_quant_mx(const void* qkv, int ld_qkv, int B, int H, int Ntok, int ntok_pad, float q_prescale, unsigned char* q8, unsigned short* q8s,
                        unsigned char* k8, unsigned* k8s, hipStream_t st);
