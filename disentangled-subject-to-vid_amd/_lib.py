@@ -132,6 +132,12 @@ _SIGS.update({
     "s2v_op_attn_mass": [_P, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P, _I32, _I32, _I32, _P],
     "s2v_op_attn_mass_mean": [_P, _I32, _I32, _I32, _I32, _I64, _P, _P],
 })
+# temporal windows (include/s2v_hip.h: s2v_set_windows, s2v_denoise_step_windows, s2v_op_window_blend)
+_SIGS.update({
+    "s2v_set_windows": [_P, _I32, _I32, _I32, ctypes.POINTER(_F)],
+    "s2v_denoise_step_windows": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],
+    "s2v_op_window_blend": [_P, _P, _P, _P, _F, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+})
 # replicas over RCCL behind the C ABI (csrc/rccl.hip); RCCL itself is bound at first use
 _SIGS.update({
     "s2v_rccl_available": [],

@@ -77,8 +77,10 @@ struct GraphKey {
     int mode = 0;   // S2V_STEP_*: the step-cache mode the forward was captured in; every mode has an executable of its own (launch_captured)
     uint64_t amask = 0;   // s2v_attn_map_arm: the layers whose attention the mass kernel follows in this step; every mask has an executable of its own
     int triple = 0;       // s2v_denoise_step_guided: the step of [u | r | f] triples, whose last kernel is another one than the pair step's
+    int windows = 0;      // s2v_denoise_step_windows: every forward and blend of a long latent's windows, then one scheduler step on the whole of it
     bool same_but_mode(const GraphKey& o) const {
-        return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask && triple == o.triple;
+        return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask && triple == o.triple &&
+               windows == o.windows;
     }
     bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask; }
 };
@@ -198,6 +200,12 @@ struct s2v_ctx {
     bool sc_valid = false;       // sc_delta is the residual of this geometry / conditioning / weights
     char *sc_delta = nullptr, *sc_in = nullptr;   // dense [B][V][D], model dtype; allocated beside the workspace, not carved from it
     int64_t sc_bytes = 0;        // of both buffers
+    // temporal windows (s2v_set_windows; include/s2v_hip.h): a long latent of win_L frames stepped as win_W windows of the geometry's F frames,
+    // win_s frames apart, win_pf windows per forward (B = 2 win_pf).  One allocation beside the workspace: the fp32 plane [win_L][C H W], then
+    // the weights [F] and their per-frame sums [win_L]
+    int win_L = 0, win_s = 0, win_pf = 0, win_W = 0;
+    float *win_acc = nullptr, *win_w = nullptr, *win_wsum = nullptr;
+    int64_t win_bytes = 0;
     int split_kind = -1;         // scheduler kind of the s2v_denoise_split_begin that has not met its s2v_denoise_split_end yet (-1: none pending)
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's live roofline figure)
     // + shader-clock stamps (s_memtime / s_memrealtime pairs written by a one-lane kernel right before and right after every profiled launch)
@@ -527,6 +535,7 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->t_dev) hipFree(c->t_dev);
     if (c->ws) hipFree(c->ws);
     if (c->e1x) hipFree(c->e1x);
+    if (c->win_acc) hipFree(c->win_acc);
     if (c->attn_queue) hipFree(c->attn_queue);
     if (c->vt_amax) hipFree(c->vt_amax);
     if (c->attn_stats) hipFree(c->attn_stats);
@@ -582,6 +591,13 @@ static int sc_alloc(s2v_ctx* c, int on) {
     if (on == 2 && hipMalloc((void**)&c->sc_in, bytes) != hipSuccess) { sc_free(c); return s2v_fail(__FILE__, __LINE__, "s2v_step_cache_enable: out of device memory", -2); }
     c->sc_bytes = on == 2 ? 2 * bytes : bytes; c->sc_on = on;
     return 0;
+}
+
+// temporal windows: the plane belongs to one geometry (the caller has synchronised the device and dropped the graphs)
+static void win_free(s2v_ctx* c) {
+    if (c->win_acc) hipFree(c->win_acc);
+    c->win_acc = c->win_w = c->win_wsum = nullptr;
+    c->win_bytes = 0; c->win_L = c->win_s = c->win_pf = c->win_W = 0;
 }
 
 // the references beyond the first (s2v_set_conditioning_refs) go with the workspace they were projected for
@@ -766,6 +782,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     drop_graph(c);
     sc_free(c);   // a shard context has no step cache
     am_free(c);   // ... and no attention map
+    win_free(c);  // ... and no temporal windows
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
     drop_refs(c);
     c->B = 0;
@@ -782,6 +799,11 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     S2V_REQUIRE(B >= 1 && B <= S2V_MAX_BATCH, "s2v_set_geometry: batch must be 1..8 (S2V_MAX_BATCH: the CFG pairs of at most four videos per call)");
     S2V_REQUIRE(T >= 0 && F >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "s2v_set_geometry: bad geometry");
     sc_invalidate(c);
+    if (c->win_acc) {   // temporal windows belong to the call that set them: every s2v_set_geometry, the same geometry again included, clears them
+        S2V_CHECK_HIP(hipDeviceSynchronize());
+        drop_graph(c);
+        win_free(c);
+    }
     if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
     if (c->shard) S2V_REQUIRE(F * (H / 2) * (W / 2) >= c->sp, "s2v_set_geometry: every rank of a shard needs at least one video row");
     S2V_CHECK_HIP(hipDeviceSynchronize());
@@ -1813,7 +1835,7 @@ extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, floa
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
     S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
     *arena = c->arena ? c->arena_bytes : 0;
-    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes : 0;
+    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes + c->win_bytes : 0;
     return 0;
 }
 
@@ -1965,6 +1987,8 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
     S2V_REQUIRE(!c->cond_triples, "s2v_denoise_step: the context is conditioned as subject-guidance triples [u x b | r x b | f x b] (s2v_set_conditioning_triples): "
                                   "its step is s2v_denoise_step_guided");
+    S2V_REQUIRE(!c->win_acc, "s2v_denoise_step: temporal windows are set (s2v_set_windows): the geometry is one forward's windows of a long latent, and "
+                             "its step is s2v_denoise_step_windows");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step: in/out channels must match");
     const int b = c->B >= 2 ? c->B / 2 : 1;
     for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step: DPM needs noise and x0_hist");
@@ -2028,6 +2052,8 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     S2V_REQUIRE(c->B % 2 == 0, "s2v_denoise_step_masked: an even B = 2b (the CFG pairs of b videos) is required");
     S2V_REQUIRE(!c->cond_triples, "s2v_denoise_step_masked: the context is conditioned as subject-guidance triples [u x b | r x b | f x b] "
                                   "(s2v_set_conditioning_triples): its masked step is s2v_denoise_step_guided with blends");
+    S2V_REQUIRE(!c->win_acc, "s2v_denoise_step_masked: temporal windows are set (s2v_set_windows): the windowed step (s2v_denoise_step_windows) has no "
+                             "masked form");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step_masked: in/out channels must match");
     const int b = c->B / 2;
     S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_masked: s2v_set_blend has not set the blend operands of this geometry's b = B/2 videos");
@@ -2070,6 +2096,8 @@ extern "C" int s2v_denoise_step_guided(s2v_ctx* c, void* latents, const float* t
     S2V_REQUIRE(c->ws && c->B % 3 == 0 && c->B / 3 <= 2, "s2v_denoise_step_guided: a geometry of B = 3b samples [u x b | r x b | f x b] with b = 1 or 2 videos is required");
     S2V_REQUIRE(c->have_cond && c->cond_triples, "s2v_denoise_step_guided: the conditioning was not set by s2v_set_conditioning_triples (the context holds "
                                                  "CFG pairs, or no conditioning)");
+    S2V_REQUIRE(!c->win_acc, "s2v_denoise_step_guided: temporal windows are set (s2v_set_windows): the windowed step (s2v_denoise_step_windows) runs "
+                             "CFG pairs");
     S2V_REQUIRE(mode == S2V_STEP_FULL, "s2v_denoise_step_guided: a step-cache mode (s2v_step_cache_arm: CAPTURE / REUSE) is armed, and the step cache assumes CFG pairs");
     S2V_REQUIRE(am == 0, "s2v_denoise_step_guided: an attention map is armed (s2v_attn_map_arm), and the attention map assumes CFG pairs");
     S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_denoise_step_guided: in/out channels must match");
@@ -2087,6 +2115,105 @@ extern "C" int s2v_denoise_step_guided(s2v_ctx* c, void* latents, const float* t
     key.triple = 1;
     if (masked) { key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; }
     return launch_captured(c, key, st, [&](hipStream_t s) { return guided_step_launches(c, latents, x0_hist, noise, s, masked); });
+}
+
+// ---- temporal windows: a long latent stepped as overlapping windows of the geometry's F frames (include/s2v_hip.h) ---------------------------
+extern "C" int s2v_set_windows(s2v_ctx* c, int32_t L, int32_t stride, int32_t per_forward, const float* weights) {
+    S2V_REQUIRE(c, "s2v_set_windows: null context");
+    if (L == 0) {
+        if (c->win_acc) { S2V_CHECK_HIP(hipDeviceSynchronize()); drop_graph(c); win_free(c); }
+        return 0;
+    }
+    S2V_REQUIRE(c->kind == S2V_CTX_MODEL, "s2v_set_windows: attention-only contexts (S2V_CTX_ATTN_*) run no step");
+    S2V_REQUIRE(!c->shard, "s2v_set_windows: a shard context (s2v_set_shard) has no windowed step: temporal windows run on one GPU");
+    S2V_REQUIRE(c->ws, "s2v_set_windows: call s2v_set_geometry first (B = 2 per_forward samples of F = the window's frames)");
+    S2V_REQUIRE(c->B != 1, "s2v_set_windows: a geometry with B = 1 is one sample of a CFG-parallel pair: the windowed step runs the CFG pairs of "
+                           "per_forward windows, B = 2 per_forward, on one GPU");
+    S2V_REQUIRE(!c->cond_triples, "s2v_set_windows: the context is conditioned as subject-guidance triples (s2v_set_conditioning_triples): the "
+                                  "windowed step runs CFG pairs");
+    S2V_REQUIRE(c->sc_arm == S2V_STEP_FULL, "s2v_set_windows: a step-cache mode is armed (s2v_step_cache_arm): the step cache holds one forward's "
+                                            "residual, a windowed step runs several");
+    S2V_REQUIRE(c->am_arm == 0, "s2v_set_windows: an attention map is armed (s2v_attn_map_arm): the attention map follows one forward per step, a "
+                                "windowed step runs several");
+    S2V_REQUIRE(per_forward >= 1 && 2 * per_forward <= S2V_MAX_BATCH && c->B == 2 * per_forward,
+                "s2v_set_windows: the geometry must hold B = 2 per_forward samples, [negative x per_forward | positive x per_forward], 1 <= per_forward <= 4");
+    const int F = c->F;
+    S2V_REQUIRE(weights && stride >= 1 && stride <= F && L >= F && (L - F) % stride == 0,
+                "s2v_set_windows: windows of the geometry's F frames, 1 <= stride <= F apart, must tile the L frames exactly: L >= F and (L - F) % stride == 0");
+    const int W = (L - F) / stride + 1;
+    S2V_REQUIRE(W % per_forward == 0, "s2v_set_windows: per_forward must divide the number of windows W = (L - F) / stride + 1");
+    S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_set_windows: in/out channels must match");
+    const int64_t chw = (int64_t)c->cfg.out_channels * c->H * c->W;
+    S2V_REQUIRE(L * chw < ((int64_t)1 << 31), "s2v_set_windows: a long latent of fewer than 2^31 elements");
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    drop_graph(c);
+    win_free(c);
+    // the sum of the weights over the windows that cover a frame, accumulated in window order as the plane is
+    std::vector<float> host((size_t)F + L, 0.f);
+    for (int j = 0; j < F; ++j) host[j] = weights[j];
+    for (int k = 0; k < W; ++k)
+        for (int j = 0; j < F; ++j) host[F + k * stride + j] += weights[j];
+    const int64_t plane = rup(L * chw * 4, 256);
+    S2V_CHECK_HIP(hipMalloc((void**)&c->win_acc, plane + (int64_t)host.size() * 4));
+    c->win_w = (float*)((char*)c->win_acc + plane); c->win_wsum = c->win_w + F;
+    c->win_bytes = plane + (int64_t)host.size() * 4;
+    S2V_CHECK_HIP(hipMemcpy(c->win_w, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    c->win_L = L; c->win_s = stride; c->win_pf = per_forward; c->win_W = W;
+    return 0;
+}
+
+static WindowBlendArgs window_blend_args(const void* noise_pred, float* acc, const float* w, const float* wsum, int L, int F, int s, int k0, int wb, int chw) {
+    WindowBlendArgs a{};
+    a.noise_pred = noise_pred; a.acc = acc; a.w = w; a.wsum = wsum; a.L = L; a.F = F; a.s = s; a.W = s >= 1 ? (L - F) / s + 1 : 0;
+    a.k0 = k0; a.wb = wb; a.chw = chw;
+    return a;
+}
+
+// W / per_forward rounds of [forward on the batch's windows, blend into the plane], then the scheduler step on the long latent from the plane
+static int windows_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st) {
+    const int pf = c->win_pf;
+    const int64_t chw = (int64_t)c->cfg.out_channels * c->H * c->W, hop = (int64_t)c->win_s * chw;
+    for (int k0 = 0; k0 < c->win_W; k0 += pf) {
+        // sample j of [negative x pf | positive x pf] embeds window k0 + j mod pf straight from the long latent (one window: the pair's stride of 0)
+        S2V_TRY(forward_impl(c, (const char*)latents + k0 * hop * c->esz, pf > 1 ? hop : 0, pf > 1 ? pf : 0, c->t_dev, c->noise_pred, st));
+        WindowBlendArgs w = window_blend_args(c->noise_pred, c->win_acc, c->win_w, c->win_wsum, c->win_L, c->F, c->win_s, k0, pf, (int)chw);
+        w.coef = c->coef_dev;
+        S2V_TRY(launch_window_blend(w, c->dtype, st));
+    }
+    SchedArgs a{};
+    a.noise_pred = c->win_acc; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
+    a.nvid = 1; a.n_vid = a.n = c->win_L * chw; a.cfg = 0; a.np_f32 = 1; a.coef = c->coef_dev;
+    return launch_sched_step(a, c->dtype, st);
+}
+
+extern "C" int s2v_denoise_step_windows(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host, float* x0_hist, const void* noise,
+                                        int32_t use_graph, s2v_stream stream) {
+    S2V_REQUIRE(c && latents && coef_host, "s2v_denoise_step_windows: null argument");
+    // the arms are one-shot and taken by every step entry, refused or not
+    const int mode = sc_take_arm(c);
+    const uint64_t am = am_take_arm(c);
+    S2V_REQUIRE(c->win_acc, "s2v_denoise_step_windows: no temporal windows are set (s2v_set_windows): a plain geometry steps with s2v_denoise_step");
+    S2V_REQUIRE(c->have_cond && !c->cond_triples, "s2v_denoise_step_windows: the conditioning must hold the CFG pairs [negative x per_forward | positive x per_forward] "
+                                                  "(s2v_set_conditioning)");
+    S2V_REQUIRE(mode == S2V_STEP_FULL, "s2v_denoise_step_windows: a step-cache mode (s2v_step_cache_arm: CAPTURE / REUSE) is armed: the step cache holds one "
+                                       "forward's residual, a windowed step runs several");
+    S2V_REQUIRE(am == 0, "s2v_denoise_step_windows: an attention map is armed (s2v_attn_map_arm): the attention map follows one forward per step, a "
+                         "windowed step runs several");
+    S2V_REQUIRE(coef_host->kind == 0 || (noise && x0_hist), "s2v_denoise_step_windows: DPM needs noise and x0_hist");
+    hipStream_t st = (hipStream_t)stream;
+    S2V_TRY(stage_step(c, timestep, coef_host, st));
+    if (!use_graph) return windows_step_launches(c, latents, x0_hist, noise, st);
+    GraphKey key{latents, x0_hist, noise, -1};
+    key.windows = 1;
+    return launch_captured(c, key, st, [&](hipStream_t s) { return windows_step_launches(c, latents, x0_hist, noise, s); });
+}
+
+extern "C" int s2v_op_window_blend(const void* noise_pred, float* acc, const float* weights, const float* wsum, float guidance, int32_t L, int32_t F,
+                                   int32_t stride, int32_t k0, int32_t wb, int32_t chw, int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_window_blend: unsupported dtype");
+    WindowBlendArgs a = window_blend_args(noise_pred, acc, weights, wsum, L, F, stride, k0, wb, chw);
+    a.gval = guidance;
+    return launch_window_blend(a, dtype, (hipStream_t)stream);
 }
 
 // ---- CFG-parallel (round 6): ONE video on TWO GPUs ---------------------------------------------------------------------------------

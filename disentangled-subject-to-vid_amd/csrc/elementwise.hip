@@ -1044,6 +1044,53 @@ int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st) 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Temporal windows: the blend of one forward's windows into the fp32 plane of the long latent (kernels.h).  A GATHER: one thread owns one
+// element of the plane inside the frames [k0 s, (k0 + wb - 1) s + F) this launch covers, and adds the contributions of the batch's windows
+// that cover its frame in ascending k.  The windows of a batch overlap, so a thread per window element would race on the plane, and atomics
+// would lose the order of the additions, which the bits depend on.
+// Frame f is covered by the windows k_first .. k_last, k_first = 0 for f < F, else (f - F) / s + 1, and k_last = min(W - 1, f / s).  Both
+// ends are decided PER FRAME, not per launch: the thread starts from +0 without reading the plane when k_first is in this batch (so the plane
+// never needs clearing between steps), and divides by wsum[f] on the way out when k_last is in this batch -- every frame is divided by the
+// batch that covers it last, no launch runs over frames it has nothing to add to.  The batches of a step are stream-ordered launches.
+template <typename T>
+__global__ void window_blend_k(const WindowBlendArgs a) {
+#pragma clang fp contract(off)  // as sched_step_k: every operation rounds on its own
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned chw = (unsigned)a.chw;
+    if (i >= (int64_t)((a.wb - 1) * a.s + a.F) * chw) return;
+    // 32-bit divisions: the launch requires a plane of fewer than 2^31 elements
+    const unsigned iu = (unsigned)i, e = iu % chw;
+    const int f = a.k0 * a.s + (int)(iu / chw);
+    const int k_first = f < a.F ? 0 : (f - a.F) / a.s + 1, k_last = min(a.W - 1, f / a.s);
+    const int ka = max(k_first, a.k0), kb = min(k_last, a.k0 + a.wb - 1);
+    const float g = a.coef ? a.coef->guidance : a.gval;
+    float* cell = a.acc + (int64_t)f * chw + e;
+    float acc = k_first >= a.k0 ? 0.f : *cell;
+    const int64_t win = (int64_t)a.F * chw;
+    const T* np = (const T*)a.noise_pred;
+    for (int k = ka; k <= kb; ++k) {
+        const int j = f - k * a.s;   // the frame's place in window k: 0 <= j < F by the bounds of k
+        const int64_t o = (k - a.k0) * win + (int64_t)j * chw + e;
+        const float u = ET<T>::ld(np + o), c = ET<T>::ld(np + a.wb * win + o);
+        const float v = __fadd_rn(u, __fmul_rn(g, __fsub_rn(c, u)));
+        acc = __fadd_rn(acc, __fmul_rn(a.w[j], v));
+    }
+    if (k_last <= a.k0 + a.wb - 1) acc = __fdiv_rn(acc, a.wsum[f]);
+    *cell = acc;
+}
+int launch_window_blend(const WindowBlendArgs& a, int dtype, hipStream_t st) {
+    S2V_REQUIRE(a.noise_pred && a.acc && a.w && a.wsum, "window_blend: null argument");
+    S2V_REQUIRE(a.F >= 1 && a.s >= 1 && a.s <= a.F && a.L >= a.F && (a.L - a.F) % a.s == 0 && a.W == (a.L - a.F) / a.s + 1,
+                "window_blend: W = (L - F) / s + 1 windows of F frames, 1 <= s <= F, must tile the L frames exactly");
+    S2V_REQUIRE(a.k0 >= 0 && a.wb >= 1 && a.k0 + a.wb <= a.W, "window_blend: the batch's windows k0 .. k0 + wb - 1 must lie inside 0 .. W - 1");
+    S2V_REQUIRE(a.chw >= 1 && (int64_t)a.L * a.chw < ((int64_t)1 << 31), "window_blend: a plane of fewer than 2^31 elements");
+    const int64_t n = (int64_t)((a.wb - 1) * a.s + a.F) * a.chw;
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(window_blend_k<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The pixel mask of masked video-to-video -> the latent mask (kernels.h).  One thread per latent cell: its 8 x 8 pixels of 1 or 4 frames,
 // a row of 8 mask values per load; with pixel_out the binarised rows are written on the way (8 bytes per store).
 template <typename M> struct MaskRow;   // the 8 mask values at p, binarised: byte k of the result is 0 or 1

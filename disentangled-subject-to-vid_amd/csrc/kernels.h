@@ -446,6 +446,26 @@ struct SchedMaskArgs : SchedArgs {     // latents_out is T (out_f32 is refused)
     SchedBlend bval;
 };
 int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st);
+// Temporal windows (include/s2v_hip.h): a long latent of L frames [L][chw] is denoised as W = (L - F) / s + 1 windows of F frames, window k over
+// frames [k s, k s + F), and the windows' predictions are averaged where they overlap.  One launch takes the forward of the wb windows
+// k0 .. k0 + wb - 1, noise_pred [negative x wb | positive x wb] of [F][chw] each, and adds them into the fp32 plane:
+//   v = u + g * (c - u)                      the pair combine of sched_step_k, same association
+//   acc[k s + j] = acc[k s + j] + w[j] * v   windows in ascending k, every operation rounding on its own
+// A frame whose first covering window is in this launch starts from +0 and its plane cell is not read; a frame whose last covering window is
+// in this launch leaves as acc / wsum[frame] (IEEE division), so after the launch of window W - 1 the plane is the averaged prediction, ready
+// for launch_sched_step with np_f32 = 1, cfg = 0.  The launches of a step run k0 = 0, wb, 2 wb, ... in order on one stream.
+struct WindowBlendArgs {
+    const void* noise_pred;   // [2 wb][F][chw] model dtype: the forward's output on the batch's windows
+    float* acc;               // [L][chw] fp32
+    const float* w;           // [F] fp32 device: the weight of window frame j
+    const float* wsum;        // [L] fp32 device: the sum of the weights that cover a frame, accumulated in window order
+    const SchedCoef* coef;    // device pointer to the step's coefficient set (its guidance is g), or null => gval
+    float gval;
+    int L, F, s, W;           // frames of the long latent and of a window, the stride between window starts, the number of windows
+    int k0, wb;               // this launch's windows
+    int chw;                  // C * H * W: the elements of a frame
+};
+int launch_window_blend(const WindowBlendArgs& a, int dtype, hipStream_t st);
 // pixel mask [F][H][W] (mdtype: S2V_F32 / S2V_BF16 / S2V_F16 binarised at 0.5, or S2V_MASK_U8: non-zero) -> latent mask uint8 [Fl][H/8][W/8],
 // a cell 1 if ANY pixel it covers is 1: the 8 x 8 block of pixel frame 0 (latent frame 0) or of pixel frames 4j-3 .. 4j (latent frame j >= 1),
 // the causal grouping of the VAE encode; Fl = (F - 1) / 4 + 1.  pixel_out (may be null): the binarised pixel mask, uint8 [F][H][W]

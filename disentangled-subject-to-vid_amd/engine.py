@@ -346,6 +346,7 @@ class S2VEngine:
         self._rope_key, self.have_rope = None, None
         self._cond_args = None
         self.triples = False
+        self.windows = None   # the library clears temporal windows with every set_geometry
         self._bump("rope", "cond")
 
     def clear_rope(self):
@@ -704,6 +705,43 @@ class S2VEngine:
         if auto:
             self._settle_attn_auto()
 
+    # ---- temporal windows (include/s2v_hip.h: s2v_set_windows, s2v_denoise_step_windows) -------------------------------------------------------
+    windows = None   # (L, stride, per_forward) while set
+
+    def set_windows(self, L, stride, weights, per_forward=1):
+        """a long latent of L frames is stepped as W = (L - F) / stride + 1 windows of the geometry's F frames, stride frames apart, per_forward
+        windows per forward: after set_geometry(2 * per_forward, T, F, H, W) and set_conditioning with the text pair repeated per_forward times
+        and one shared reference row.  weights: F fp32 values, the weight of each frame of a window (pipeline.window_plan).  Allocates the fp32
+        plane [L,C,H,W] (device_bytes counts it); set_geometry and clear_windows free it"""
+        w = [float(x) for x in weights]
+        _lib.check(_lib.lib().s2v_set_windows(self._h, int(L), int(stride), int(per_forward), (ctypes.c_float * len(w))(*w)))
+        self.windows = (int(L), int(stride), int(per_forward))
+
+    def clear_windows(self):
+        if self.windows is not None:
+            _lib.check(_lib.lib().s2v_set_windows(self._h, 0, 0, 0, None))
+            self.windows = None
+
+    def denoise_step_windows(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False):
+        """one iteration of the denoise loop on a long latent [1,L,C,H,W] (model dtype), updated in place, after set_windows: the forward on
+        every window, the windows' CFG pairs combined and averaged where they overlap, one scheduler step on the L frames
+        (s2v_denoise_step_windows); x0_hist (fp32) and noise have the shape of latents"""
+        if latents.dtype != self.dtype or not latents.is_contiguous():
+            raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
+        if self.windows is not None:   # without windows the library refuses by name
+            B, T, F, H, W = self.geometry
+            want = (1, self.windows[0], self.cfg.in_channels, H, W)
+            for name, x in (("latents", latents), ("x0_hist", x0_hist), ("noise", noise)):
+                if x is not None and (tuple(x.shape) != want or not x.is_contiguous()):
+                    raise _lib.S2VError(f"denoise_step_windows: {name} must be contiguous {list(want)} (the long latent), got {list(x.shape)}")
+        auto = self._attn_auto_pending
+        if auto:
+            self.attn_slow_stats(reset=True)
+        _lib.check(_lib.lib().s2v_denoise_step_windows(self._h, _lib.ptr(latents), float(timestep), ctypes.byref(coef), _lib.ptr(x0_hist),
+                                                       _lib.ptr(noise), int(use_graph and not auto), _lib.stream_ptr()))
+        if auto:
+            self._settle_attn_auto()
+
     # ---- CFG-parallel: this engine holds ONE sample of the CFG pair (geometry B = 1); include/s2v_hip.h, dist.CfgPair ---------------------------
     def cfg_pair(self):
         """the context-owned pair buffer [2, F, C, H, W] (model dtype): half `slot` is written by denoise_split_begin, the other by the exchange"""
@@ -743,6 +781,7 @@ class S2VEngine:
         _lib.check(_lib.lib().s2v_set_shard(self._h, int(world), int(rank)))
         if self.shard != (int(world), int(rank)):
             self.geometry = None
+            self.windows = None
         self.shard = (int(world), int(rank))
 
     shard = None

@@ -4,7 +4,7 @@ step), everything after them runs here.
 
 S2VPipeline.__call__ checks the arguments, plans every video's steps on the host (video_plan: a call with scalars is one plan shared by all
 its videos) and runs them in ONE loop (_denoise), whatever the call combines of several videos, per-video lists, video-to-video, masks,
-change maps, the step cache, the attention map, CFG-parallel and Ulysses.
+change maps, the step cache, the attention map, subject guidance, temporal windows (long videos), CFG-parallel and Ulysses.
 
 Two execution modes with identical results:
   fused=True  (default) one s2v_denoise_step per iteration: transformer on the CFG pair, fp32 CFG, scheduler step
@@ -145,6 +145,78 @@ def attention_map_to_change_map(m, lo, hi, num_frames):
     return level.repeat_interleave(reps, dim=1).contiguous()
 
 
+MAX_WINDOW_FRAMES = 49   # what one forward takes: 13 latent frames (the static positional embeddings)
+WINDOW_WEIGHTINGS = ("flat", "pyramid")
+
+
+def window_weights(F, weighting="pyramid"):
+    """the weight of each of the F latent frames of a window, as Python floats that fp32 holds exactly: "flat" all 1; "pyramid" 1, 2, ..., m,
+    ..., 2, 1 for odd F and 1 .. F/2, F/2 .. 1 for even F (F = 13: 1..7..1; F = 4: 1, 2, 2, 1)"""
+    if weighting not in WINDOW_WEIGHTINGS:
+        raise ValueError(f"temporal windows: weighting must be one of {WINDOW_WEIGHTINGS}, got {weighting!r}")
+    return [1.0 if weighting == "flat" else float(min(j + 1, F - j)) for j in range(F)]
+
+
+def window_plan(L, F, s, weighting="pyramid"):
+    """a long latent of L frames as W = (L - F) / s + 1 equally spaced windows of F frames, window k over latent frames [k s, k s + F):
+    {"L", "F", "s", "W", "starts": [k s], "weights": window_weights(F, weighting), "wsum": per frame the fp32 sum of the weights of the windows
+    that cover it, added up in window order (exact: the weights are small integers)}.  Requires 1 <= s <= F (no frame between two windows is
+    left out), L >= F and (L - F) % s == 0 (no clamped, unequally spaced last window); L = F is one window.  Host arithmetic only"""
+    if F < 1 or s < 1 or s > F:
+        raise ValueError(f"temporal windows: windows of F = {F} latent frames need a stride of 1 <= s <= F latent frames, got s = {s}")
+    if L < F or (L - F) % s:
+        k = max(0, (L - F) // s)
+        raise ValueError(f"temporal windows: L = {L} latent frames are no whole number of windows of F = {F} frames, s = {s} apart (L >= F and "
+                         f"(L - F) % s == 0 are required); the nearest that are: L = {F + k * s} and L = {F + (k + 1) * s}")
+    w = window_weights(F, weighting)
+    W = (L - F) // s + 1
+    wsum = np.zeros(L, dtype=np.float32)
+    for k in range(W):
+        wsum[k * s:k * s + F] += np.asarray(w, dtype=np.float32)
+    return dict(L=L, F=F, s=s, W=W, starts=[k * s for k in range(W)], weights=w, wsum=[float(x) for x in wsum])
+
+
+class TemporalWindows:
+    """long videos (S2VPipeline.__call__(num_frames=..., temporal_windows=...)): every step runs the model on overlapping windows of
+    window_frames frames, stride_frames apart, and averages their predictions with the `weighting` of window_weights where they overlap;
+    per_forward windows share one forward (2 * per_forward samples of the library's 8).  No length, stride or weighting is recommended"""
+
+    def __init__(self, window_frames=49, stride_frames=24, weighting="pyramid", per_forward=1):
+        self.window_frames, self.stride_frames, self.weighting, self.per_forward = window_frames, stride_frames, weighting, per_forward
+
+    def plan(self, num_frames):
+        """window_plan for a call of num_frames frames, with "per_forward" added, after every refusal of the definition: num_frames and
+        window_frames must be 4k + 1, window_frames <= 49, stride_frames a multiple of 4 with 1 <= stride_frames / 4 <= F, the windows must tile
+        the latent frames exactly, per_forward must divide the number of windows and 2 * per_forward <= 8.  A num_frames that does not fit is
+        refused with the two nearest that do"""
+        wf, sf, pf = self.window_frames, self.stride_frames, self.per_forward
+        if int(wf) != wf or wf < 1 or wf % 4 != 1 or wf > MAX_WINDOW_FRAMES:
+            raise ValueError(f"temporal windows: window_frames must be 4k + 1 and at most {MAX_WINDOW_FRAMES} (one forward's frames), got {wf}")
+        if int(sf) != sf or sf < 4 or sf % 4:
+            raise ValueError(f"temporal windows: stride_frames must be a positive multiple of 4 (whole latent frames), got {sf}")
+        F, s = (int(wf) - 1) // 4 + 1, int(sf) // 4
+        if s > F:
+            raise ValueError(f"temporal windows: stride_frames = {sf} is {s} latent frames, beyond the window's {F}: frames between two windows "
+                             f"would never be denoised (1 <= stride_frames / 4 <= {F})")
+        window_weights(F, self.weighting)
+        if int(pf) != pf or pf < 1 or 2 * pf > 2 * MAX_VIDEOS:
+            raise ValueError(f"temporal windows: per_forward must be 1..{MAX_VIDEOS} (a forward runs the CFG pairs of per_forward windows, at most "
+                             f"{2 * MAX_VIDEOS} samples), got {pf}")
+        nf = num_frames
+        k = max(0, ((int(nf) - 1) // 4 + 1 - F) // s) if nf >= 1 else 0
+        near = f"the nearest valid num_frames are {4 * (F + k * s - 1) + 1} and {4 * (F + (k + 1) * s - 1) + 1}"
+        if int(nf) != nf or nf < 1 or nf % 4 != 1:
+            raise ValueError(f"temporal windows: num_frames must be 4k + 1, got {nf}; with window_frames = {wf} and stride_frames = {sf} {near}")
+        L = (int(nf) - 1) // 4 + 1
+        if L < F or (L - F) % s:
+            raise ValueError(f"temporal windows: num_frames = {nf} is no whole number of windows of {wf} frames, {sf} apart; {near}")
+        plan = window_plan(L, F, s, self.weighting)
+        if plan["W"] % pf:
+            raise ValueError(f"temporal windows: per_forward = {pf} does not divide the {plan['W']} windows of num_frames = {nf}")
+        plan["per_forward"] = int(pf)
+        return plan
+
+
 def _one_gpu_only(cfg_parallel, ulysses, message):
     """the refusal of a feature that does not run under cfg_parallel= / ulysses=: message(name) for whichever was passed, cfg_parallel first"""
     for name, arg in (("cfg_parallel", cfg_parallel), ("ulysses", ulysses)):
@@ -279,6 +351,35 @@ class S2VPipeline:
             raise ValueError(f"`negative_ref_img_states` must be [1 | {b}, {', '.join(str(x) for x in ref_img_states.shape[1:])}] (the shape of a "
                              f"row of `ref_img_states`; one row, or one per video), got {tuple(n.shape)}")
         return scales
+
+    @staticmethod
+    def check_windows(temporal_windows, num_frames, b=1, mask=None, change_map=None, step_cache=None, attention_map=None,
+                      subject_guidance_scale=None, per_video=False, cfg_parallel=None, ulysses=None, fused=True):
+        """the TemporalWindows.plan of a long call, after every refusal of what the windowed step does not carry (no device is touched): the
+        step runs W forwards of CFG pairs that share one timestep, one text pair and one reference, and ends in one scheduler step on the
+        whole long latent"""
+        if not isinstance(temporal_windows, TemporalWindows):
+            raise ValueError(f"`temporal_windows` must be a TemporalWindows(window_frames, stride_frames, weighting, per_forward), got {temporal_windows!r}")
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`temporal_windows` together with `{name}`: the windowed step runs on one GPU; CFG-parallel "
+                                                          f"and Ulysses step one window's worth of frames")
+        for name, arg in (("mask", mask), ("change_map", change_map)):
+            if arg is not None:
+                raise ValueError(f"`temporal_windows` together with `{name}`: the windowed step has no masked form")
+        for name, arg in (("step_cache", step_cache), ("attention_map", attention_map)):
+            if arg is not None:
+                raise ValueError(f"`temporal_windows` together with `{name}`: the step cache and the attention map follow one forward per step, a "
+                                 f"windowed step runs one per window")
+        if subject_guidance_scale is not None:
+            raise ValueError("`temporal_windows` together with `subject_guidance_scale`: the windowed step combines CFG pairs, not triples")
+        if per_video:
+            raise ValueError("`temporal_windows` together with a per-video list (`guidance_scale`, `num_inference_steps`, `strength`): a windowed "
+                             "call is one long video on one plan, with scalars")
+        if b > 1:
+            raise ValueError(f"`temporal_windows` with {b} videos per call: the samples of a forward are the windows of ONE long video; one video per call")
+        if not fused:
+            raise ValueError("`temporal_windows` together with fused=False: the window blend lives in the fused step; fused=False is the reference's "
+                             "seam sequence")
+        return temporal_windows.plan(num_frames)
 
     @classmethod
     def video_plan(cls, scheduler, num_inference_steps, strength, guidance_scale, use_dynamic_cfg, dtype, guidance_subject=None):
@@ -453,7 +554,7 @@ class S2VPipeline:
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
                  video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None,
-                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None):
+                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None, temporal_windows=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -509,7 +610,15 @@ class S2VPipeline:
         null reference (None: zeros, the zero latent; none is recommended); with negative_ref_img_states = ref_img_states the latents are the
         plain call's bit for bit, whatever the scale.  At most 2 videos per call; composes with video= / strength, mask=, change_map=, paste_back,
         use_graph and the per-video lists; refused with guidance_scale <= 1, cfg_parallel=, ulysses=, step_cache=, attention_map= and
-        fused=False."""
+        fused=False.
+        temporal_windows: a TemporalWindows(window_frames, stride_frames, weighting, per_forward) -- long videos.  Without it num_frames > 49
+        is refused as ever.  With it num_frames (4k + 1, or the 8k + 1 frames of `video`) may be any length the windows tile exactly
+        (TemporalWindows.plan names the nearest that do): latents, the DPM noise and what the callback sees have all L = (num_frames - 1) / 4 + 1
+        latent frames; every step runs the model on each window of window_frames frames, combines each window's CFG pair, averages the windows
+        with their weights where they overlap and takes ONE scheduler step on the whole latent; the VAE decodes the long latent in one call.
+        All windows share the timestep, the prompt pair and the reference.  `video` / `strength` only move the start of the loop.  One video per
+        call on one GPU with scalars; refused with mask=, change_map=, step_cache=, attention_map=, subject_guidance_scale=, per-video lists,
+        cfg_parallel=, ulysses= and fused=False."""
         self.step_cache_report = None
         self.attention_maps = None
         if change_map is not None and mask is not None:
@@ -545,7 +654,12 @@ class S2VPipeline:
                 raise ValueError(f"`video` is {video.shape[3]}x{video.shape[4]} but height x width is {height}x{width}: resizing stays "
                                  "with the caller")
             num_frames = video.shape[2]
-        if num_frames > 49:
+        windows = None   # a long call: its window_plan
+        if temporal_windows is not None:
+            nb = prompt_embeds.shape[0] * num_videos_per_prompt if prompt_embeds is not None and prompt_embeds.ndim == 3 else 1
+            windows = self.check_windows(temporal_windows, num_frames, nb, None if levels else mask, change_map, step_cache, attention_map,
+                                         subject_guidance_scale, per_video, cfg_parallel, ulysses, fused)
+        elif num_frames > 49:
             raise ValueError("The number of frames must be less than or equal to 49 due to static positional embeddings.")
         self.check_inputs(height, width, prompt_embeds, negative_prompt_embeds)
         bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]
@@ -585,6 +699,11 @@ class S2VPipeline:
                                  num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                                  callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
                                  step_cache, attention_map, subject=subject)
+        if windows is not None:
+            return self._denoise(plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator,
+                                 latents, output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs,
+                                 cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map,
+                                 windows=windows)
         return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
                              num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                              callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
@@ -592,7 +711,7 @@ class S2VPipeline:
 
     def _denoise(self, plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator, latents,
                  output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video,
-                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None):
+                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None, windows=None):
         """the one denoise loop: b = len(plans) videos, each on its video_plan; iteration i applies step i of every video that still has one.
         The videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers;
         when the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
@@ -605,7 +724,10 @@ class S2VPipeline:
         map, and video k keeps the cells of level <= change_map_plan(n_k)[i] after its step i, n_k the steps of its own plan
         subject: a subject-guidance call (None: a pair call, which touches no triple entry) -- the null references [1 | b,1,C,h,w]; every
         geometry is 3a samples [u x a | r x a | f x a] of the a active videos, conditioned by set_conditioning_triples and stepped by the
-        guided step with the subject scale of each video's coefficient sets; everything else of the loop is the pair call's"""
+        guided step with the subject scale of each video's coefficient sets; everything else of the loop is the pair call's
+        windows: a long call (None: every other call, which touches no window entry) -- its window_plan.  One video whose latents, x0 history
+        and noise have L frames; the geometry is 2 per_forward samples of the WINDOW's F frames, conditioned with the text pair repeated
+        per_forward times, and every step is the windowed step on the whole long latent"""
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         b = len(plans)
@@ -628,6 +750,10 @@ class S2VPipeline:
             latents = self.prepare_latents(num_frames, height, width, dt, dev, generator, latents, b)
         latents = internal(latents.to(dt))   # internal order from here on
         F, H, W = latents.shape[1], latents.shape[3], latents.shape[4]
+        if windows is not None:
+            if F != windows["L"]:
+                raise ValueError(f"`latents` has {F} latent frames, num_frames = {num_frames} has {windows['L']}")
+            F = windows["F"]   # the geometry's frames are one window's; the buffers of the loop keep the long shape
         ref = ref_img_states.to(dev, dt)
         if ref.shape[0] > 1:
             ref = internal(ref)
@@ -663,16 +789,21 @@ class S2VPipeline:
             return ref.expand(a, -1, -1, -1, -1).contiguous() if rows else ref
 
         def condition(a):   # the hoisted conditioning of the a active videos: the CFG pairs, or the triples of a subject-guidance call
-            if subject is None:
+            if windows is not None:   # the one video's pair, [negative x per_forward | positive x per_forward], and its one reference row
+                eng.set_conditioning(active_text(1).repeat_interleave(windows["per_forward"], dim=0), ref)
+            elif subject is None:
                 eng.set_conditioning(active_text(a), active_ref(a, False))
             else:   # the library lays [negative x a | positive x a] out as [u x a | r x a | f x a] (subject_layout)
                 eng.set_conditioning_triples(active_text(a), active_ref(a, True), subject[:a] if subject.shape[0] > 1 else subject)
 
         def set_active(a):
             # CFG-parallel: B = 1 with this rank's half of [negative | positive] (custom_cogvideox_pipe.py:196) and the un-duplicated reference tokens
-            eng.set_geometry((2 * a if subject is None else 3 * a) if cfg_parallel is None else 1, text.shape[1], F, H, W)
+            samples = 2 * windows["per_forward"] if windows is not None else 2 * a if subject is None else 3 * a
+            eng.set_geometry(samples if cfg_parallel is None else 1, text.shape[1], F, H, W)
             eng.prepare_tables(height, width)
             condition(a)
+            if windows is not None:
+                eng.set_windows(windows["L"], windows["s"], windows["weights"], windows["per_forward"])
             if mask is not None:   # prefixes of the same buffers, as latents[:a] is
                 eng.set_blend(z0[:a], noise0[:a], lat_mask[:a])
 
@@ -743,7 +874,9 @@ class S2VPipeline:
                         for _ in range(steps[0]["draws"]):
                             self._draw(noise[:a], generator)
                     ts, coefs = [float(st["t"]) for st in steps], [st["coef"] for st in steps]
-                    if ulysses is not None:
+                    if windows is not None:
+                        eng.denoise_step_windows(latents, ts[0], coefs[0], x0_hist, noise, use_graph)
+                    elif ulysses is not None:
                         ulysses.step(eng, latents, ts[0], coefs[0], x0_hist, noise, use_graph)
                     elif cfg_parallel is not None:
                         cfg_parallel.step(eng, latents, ts[0], coefs[0], x0_hist, noise, use_graph)
@@ -815,6 +948,8 @@ class S2VPipeline:
             if attention_map is not None:
                 self.attention_maps = self._read_attention_maps(eng, attention_map, b, am_ran, am_skipped)
         finally:
+            if windows is not None:
+                eng.clear_windows()
             if fused and mask is not None:
                 eng.clear_blend()
             if sc_plan is not None:

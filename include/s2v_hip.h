@@ -370,6 +370,30 @@ S2V_API int s2v_denoise_step_guided(s2v_ctx* ctx, void* latents, const float* ti
 /* pointer to the [B,F,C,H,W] model output of the last s2v_denoise_step (context-owned, model dtype); [3b,...] after s2v_denoise_step_guided */
 S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 
+/* ---- Temporal windows: a long latent denoised as overlapping windows, averaged per step ----------------------------------------------------
+ * The model sees at most 13 latent frames (49 video frames).  A long latent [L][C][H W] is stepped as W = (L - F) / stride + 1 windows of the
+ * geometry's F frames, window k over latent frames [k stride, k stride + F): equally spaced, so a forward's windows are a pointer into the
+ * long latent and a stride.  With g the step's coef->guidance, weights w[F] and wsum[f] the sum of the weights of the windows covering frame f
+ * (added up in window order), one step is, in fp32, every operation rounding on its own:
+ *     acc = +0;   for k = 0 .. W - 1, frame j of window k:   v = u_k + g * (f_k - u_k);   acc[k stride + j] = acc[k stride + j] + w[j] * v
+ *     vbar = acc / wsum[frame]                                (IEEE division)
+ * and then the scheduler arithmetic of s2v_sched_step (flags bit1, no bit0) on the L frames from vbar.  Every window shares the step's
+ * timestep, the text pair and the reference.
+ * s2v_set_windows: after s2v_set_geometry with B = 2 per_forward ([negative x per_forward | positive x per_forward]: the text rows repeated
+ * per_forward times, one shared reference row) and F = the window's frames.  weights: HOST array [F].  Requires 1 <= stride <= F, L >= F,
+ * (L - F) % stride == 0 and per_forward dividing W.  Allocates the fp32 plane [L][C][H][W] with the weights and their sums behind it, counted
+ * by s2v_device_bytes as workspace; with windows never set s2v_device_bytes reports what it reports without this feature.  L = 0 clears and
+ * frees; s2v_set_geometry (the same geometry included) and s2v_set_shard clear too.  Setting or clearing drops a captured step.
+ * Refused by name: a shard context, B = 1 (a CFG-parallel half), a context conditioned as triples, an armed step-cache mode, an armed
+ * attention map, B != 2 per_forward.
+ * s2v_denoise_step_windows: the whole step -- latents / x0_hist / noise are [L][C][H][W] (model dtype / fp32 / model dtype), updated in place:
+ * W / per_forward rounds of the forward on the next per_forward windows followed by the blend kernel, then one scheduler step on the L frames.
+ * use_graph: one captured graph of its own key holds every forward of the step.  Refuses a context without windows; s2v_denoise_step,
+ * _videos, _masked and _guided refuse a context with windows. */
+S2V_API int s2v_set_windows(s2v_ctx* ctx, int32_t L, int32_t stride, int32_t per_forward, const float* weights);
+S2V_API int s2v_denoise_step_windows(s2v_ctx* ctx, void* latents, float timestep, const s2v_sched_coef* coef_host, float* x0_hist,
+                                     const void* noise, int32_t use_graph, s2v_stream stream);
+
 /* ---- Step cache: a step whose timestep embedding barely moved skips the block stack ---------------------------------------------------------
  * Opt-in state on a model context.  X is the packed residual buffer [B][Ntok][D]; its video rows are rows [T + R, T + R + V) of each sample.
  * The cache is dense [B][V][D] in the model dtype T.  Every forward (s2v_transformer_forward*, s2v_denoise_step, _videos, _masked) runs in the
@@ -678,6 +702,11 @@ S2V_API int s2v_t5_encode(s2v_t5* t5, const int64_t* input_ids_dev, int32_t B, i
  * against the dense cache [B][n]; op 0: cache = x; 1: cache = rnd(float(x) - float(cache)); 2: x = rnd(float(x) + float(cache)).  n, x_bstride
  * and the pointers in whole 16-byte vectors */
 S2V_API int s2v_op_step_cache(int32_t op, void* x, int64_t x_bstride, void* cache, int32_t B, int64_t n, int32_t dtype, s2v_stream stream);
+/* the temporal-window blend kernel on its own (one launch of s2v_denoise_step_windows): noise_pred [negative x wb | positive x wb] of [F][chw]
+ * each in `dtype`, the forward's output on windows k0 .. k0 + wb - 1; acc fp32 [L][chw]; weights [F] and wsum [L] fp32 in DEVICE memory.  A
+ * frame first covered by a window of this batch starts from +0 (its cell is not read); a frame last covered by one leaves divided by wsum */
+S2V_API int s2v_op_window_blend(const void* noise_pred, float* acc, const float* weights, const float* wsum, float guidance, int32_t L, int32_t F,
+                                int32_t stride, int32_t k0, int32_t wb, int32_t chw, int32_t dtype, s2v_stream stream);
 /* the attention-mass kernel on its own: qkv [B * Ntok][3 * H * 64] (q | k | v as s2v_op_attention takes them, 16-byte aligned; nothing past row
  * B * Ntok - 1 is read), query rows [q0, q0 + nq) of every sample, ranges_host n pairs (k0, k1) -> out [n][B][H][nq] fp32; accumulate != 0: out + mass
  * in one fp32 add.  An empty range gives exactly 0.  impl 0: v_mfma_f32_32x32x16 on bf16 / fp16 storage, q * 0.125 * log2 e rounded to the
