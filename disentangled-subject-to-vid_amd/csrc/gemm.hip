@@ -1221,7 +1221,7 @@ extern "C" __attribute__((visibility("default"))) int s2v_set_gemm_impl(int impl
 // gemm_plan of one GEMM as the engine issues it, without a device (tests/test_gemm_dispatch_cpu.py): M x N x K with the operands of linear()
 // (rows padded to 256, a bias, the gate + residual of the out-projection / FF2, the q/k-norm parameters).  flags: 1 fp16 operands, 2 a rotary
 // table (EPI_BIAS_QKNORM), 4 e4m3 operands (launch_gemm_fp8) with per-token scales of A, 8 (with 4) an MX image as A instead, 16 a VAE
-// convolution (kt = 3 over cin = K / 27 channels, launch_gemm_bf16 directly); bits 8 .. 9: GemmArgs::tile as a caller forces it (s2v_op_linear_planned); 32: no plan --
+// convolution (kt = 3 over cin = K / 27 channels, launch_gemm_bf16 directly), 64 its per-frame stride-2 form (cin = K / 9); bits 8 .. 9: GemmArgs::tile as a caller forces it (s2v_op_linear_planned); 32: no plan --
 // the kernel of ONE launch of M x N x K as given, operands exactly M and N rows (s2v_op_linear impl 0 / 4).  out = {splitk, tile, m_main, main, tail} (GemmPlan)
 static int gemm_kernel(const GemmArgs& a, int epi, int ncu);
 extern "C" __attribute__((visibility("default"))) int s2v_diag_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t flags, int32_t ncu,
@@ -1241,6 +1241,7 @@ extern "C" __attribute__((visibility("default"))) int s2v_diag_gemm_plan(int32_t
         else g.a_scale = (const float*)p;
     }
     if (flags & 16) { g.conv = 1; g.kt = 3; g.cin = K / 27; g.lda = 0; g.a_rows_padded = 0; }
+    if (flags & 64) { g.conv = 1; g.kt = 1; g.cin = K / 9; g.cstride = 2; g.lda = 0; g.a_rows_padded = 0; }  // the 9-tap stride-2 form (run_conv_down)
     if (flags & 32) {
         g.a_rows_padded = M; g.w_rows_padded = N;
         out[0] = 0; out[1] = 0; out[2] = M; out[3] = gemm_kernel(g, epi, ncu); out[4] = GEMM_NONE;

@@ -565,10 +565,17 @@ static void vae_gemm_log(const GemmArgs& g, int epi, bool mfma, const char* kind
 // the GEMM kernel of a convolution or a 1 x 1 shortcut: bf16 MFMA when the channel count fills its K tiles, fp16 MFMA where gemm_f16 takes
 // the shape, the generic kernel otherwise
 static bool gemm_is_bf16_mfma(const s2v_vae* v, const GemmArgs& g) { return v->mfma && (g.conv ? g.cin : g.K) % 64 == 0; }
+#ifdef S2V_DIAG
+static int g_vae_diag_route = 0;  // s2v_diag_vae_conv_run: which branch of launch_gemm the last GEMM took (1 bf16 MFMA, 2 fp16 MFMA, 3 gemm_f32m, 4 generic)
+#define S2V_VAE_ROUTE(r) g_vae_diag_route = (r)
+#else
+#define S2V_VAE_ROUTE(r) (void)0
+#endif
 static int launch_gemm(s2v_vae* v, GemmArgs& g, int epi, hipStream_t st) {
-    if (gemm_is_bf16_mfma(v, g)) return launch_gemm_bf16(g, epi, st);  // cout = 3 (conv_out) without the direct kernel: one padded 128-column tile
-    if (v->h16 && gemm_f16_ok(g, epi)) return launch_gemm_f16(g, epi, st);
+    if (gemm_is_bf16_mfma(v, g)) { S2V_VAE_ROUTE(1); return launch_gemm_bf16(g, epi, st); }  // cout = 3 (conv_out) without the direct kernel: one padded 128-column tile
+    if (v->h16 && gemm_f16_ok(g, epi)) { S2V_VAE_ROUTE(2); return launch_gemm_f16(g, epi, st); }
     g.valu_only = v->cfg.force_simple;
+    S2V_VAE_ROUTE(v->dtype == S2V_F32 && gemm_f32m_ok(g) ? 3 : 4);
     return launch_gemm_simple(g, epi, v->dtype, st);
 }
 // direct_dst (conv_out only): the [C][Ftot][H][W] tile output -- when the direct small-N kernel qualifies (launch_conv_out_direct) it writes there
@@ -1077,3 +1084,100 @@ extern "C" int s2v_vae_gaussian_sample(const void* moments, const void* noise, i
     S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_vae_gaussian_sample: unsupported dtype");
     return launch_gaussian_sample(moments, noise, (int64_t)latent_channels * n_spatial, out, dtype, (hipStream_t)stream);
 }
+
+#ifdef S2V_DIAG
+// =====================================================================================================================
+// ONE convolution layer of a handle, as decode_batch / encode_batch issue it (tests/test_gpu_vae_conv_exact.py, oracle/vae_conv_cases.py):
+// the product's capacity call, set_layout's ring clearing, one launch_* producer from a caller-owned source, run_conv / run_conv_down
+// with their cache copies and kernel choice, launch_to_ncfhw where conv_out did not run as the direct kernel.  Nothing here builds a
+// GemmArgs.  Diagnostics build only.
+static ConvL* conv_by_index(s2v_vae* v, int index) {
+    ConvL* hit = nullptr;
+    int i = 0;
+    for_each_conv(v, [&](ConvL& c) { if (i++ == index) hit = &c; });
+    return hit;
+}
+// out = {cin, cout, kt, level, number of convolutions of the handle}
+extern "C" __attribute__((visibility("default"))) int s2v_diag_vae_conv_info(s2v_vae* v, int32_t index, int32_t* out) {
+    S2V_REQUIRE(v && out, "s2v_diag_vae_conv_info: null argument");
+    int n = 0;
+    for_each_conv(v, [&](ConvL&) { n++; });
+    const ConvL* c = conv_by_index(v, index);
+    S2V_REQUIRE(c, "s2v_diag_vae_conv_info: no convolution of that index");
+    out[0] = c->cin; out[1] = c->cout; out[2] = c->kt; out[3] = c->level; out[4] = n;
+    return 0;
+}
+// the workspace for level-0 windows up to th x tw and `frames` frames per batch: prepare_tile_capacity (decoder) / enc_prepare (encoder)
+extern "C" __attribute__((visibility("default"))) int s2v_diag_vae_conv_prepare(s2v_vae* v, int32_t th, int32_t tw, int32_t frames) {
+    S2V_REQUIRE(v && th >= 1 && tw >= 1 && frames >= 1, "s2v_diag_vae_conv_prepare: bad argument");
+    if (v->encoder) return enc_prepare(v, th, tw, frames);
+    S2V_TRY(prepare_tile_capacity(v, th, tw, frames));
+    ws_activate(v, 0);
+    return 0;
+}
+enum { DIAG_PROD_DENSE2 = 0, DIAG_PROD_DENSE0 = 1, DIAG_PROD_UP = 2, DIAG_PROD_UP_CT = 3, DIAG_PROD_POOL = 4, DIAG_PROD_IMAGE = 5 };
+/* p: 0 layer (for_each_conv order)   1..3 F, H, W of the SOURCE as the producer takes it (upsample: before the doubling; time pool: before
+ *    the pooling; otherwise the convolution's own)   4 first   5 epilogue (EPI_BIAS / EPI_BIAS_ADD with `resid`)   6 producer (DIAG_PROD_*)
+ *    7..12 image window: Fall, fs, Himg, Wimg, y0, x0   13 output: 0 dense rows [M][cout], 1 the [cout][Ftot][H][W] tile   14 Ftot   15 f0
+ *    16 fill: 0 none, 1 a 16-bit, 2 a 32-bit pattern over the layer's whole operand buffer BEFORE the ring is cleared and the producer runs
+ *    17 the pattern   18 stride 2 (run_conv_down)
+ * info: 0 the direct kernel ran   1 route of the GEMM (1 bf16 MFMA, 2 fp16 MFMA, 3 gemm_f32m, 4 the generic kernel; 0 none)
+ *    2..4 F, H, W of the convolution's operand   5 output rows M */
+extern "C" __attribute__((visibility("default"))) int s2v_diag_vae_conv_run(s2v_vae* v, const int32_t* p, const void* src, const void* resid, void* out,
+                                                                             int32_t* info, s2v_stream stream) {
+    S2V_REQUIRE(v && p && src && out && info, "s2v_diag_vae_conv_run: null argument");
+    // run_conv's A/B switches of the diagnostics build would change what runs or what it returns
+    S2V_REQUIRE(!getenv("S2V_VAE_NO_DIRECT_CONV_OUT") && !getenv("S2V_VAE_ADD_EXPERIMENT"), "s2v_diag_vae_conv_run: unset S2V_VAE_NO_DIRECT_CONV_OUT and S2V_VAE_ADD_EXPERIMENT");
+    ConvL* cp = conv_by_index(v, p[0]);
+    S2V_REQUIRE(cp, "s2v_diag_vae_conv_run: no convolution of that index");
+    ConvL& c = *cp;
+    hipStream_t st = (hipStream_t)stream;
+    const int prod = p[6], epi = p[5], stride2 = p[18];
+    int F = p[1], H = p[2], W = p[3];
+    S2V_REQUIRE(F >= 1 && H >= 1 && W >= 1, "s2v_diag_vae_conv_run: bad geometry");
+    S2V_REQUIRE(c.kt == 3 || c.kt == 1, "s2v_diag_vae_conv_run: a 1 x 1 shortcut is no convolution layer");
+    S2V_REQUIRE(prod >= DIAG_PROD_DENSE2 && prod <= DIAG_PROD_IMAGE, "s2v_diag_vae_conv_run: unknown producer");
+    S2V_REQUIRE((c.kt == 3) == (prod == DIAG_PROD_DENSE2 || prod == DIAG_PROD_IMAGE), "s2v_diag_vae_conv_run: a causal layer's operand starts at frame 2, a per-frame layer's at frame 0");
+    S2V_REQUIRE(epi == EPI_BIAS || (epi == EPI_BIAS_ADD && resid), "s2v_diag_vae_conv_run: EPI_BIAS, or EPI_BIAS_ADD with a residual");
+    if (prod == DIAG_PROD_UP || prod == DIAG_PROD_UP_CT) { F = up_frames(F, prod == DIAG_PROD_UP_CT); H *= 2; W *= 2; }
+    if (prod == DIAG_PROD_POOL) { S2V_REQUIRE(F > 1, "s2v_diag_vae_conv_run: the time pool takes more than one frame"); F = down_frames(F, 1); }
+    if (stride2) S2V_REQUIRE(c.kt == 1 && H % 2 == 0 && W % 2 == 0 && epi == EPI_BIAS && p[13] == 0, "s2v_diag_vae_conv_run: stride 2 is a per-frame layer on even sides, bias only, dense rows");
+    // the level-0 window whose layout puts H x W at this layer's level, and the capacity of the workspace
+    const int th = v->encoder ? H << c.level : H >> c.level, tw = v->encoder ? W << c.level : W >> c.level;
+    S2V_REQUIRE(v->th > 0 && c.pad, "s2v_diag_vae_conv_run: no workspace (s2v_diag_vae_conv_prepare)");
+    S2V_REQUIRE(th >= 1 && tw >= 1 && th <= v->th && tw <= v->tw, "s2v_diag_vae_conv_run: window beyond the workspace's capacity");
+    const Operand o = operand_extent(v, c, th, tw, v->fmax);
+    S2V_REQUIRE(o.H == H && o.W == W, "s2v_diag_vae_conv_run: the sides are no window of this layer's level");
+    S2V_REQUIRE(F <= o.frames && o.padded_bytes(v, c) + 1024 <= c.pad_bytes, "s2v_diag_vae_conv_run: frames beyond the workspace's capacity");
+    if (prod == DIAG_PROD_POOL) S2V_REQUIRE(p[1] <= o.frames, "s2v_diag_vae_conv_run: frames beyond the workspace's capacity");
+    if (p[16]) {
+        S2V_REQUIRE((p[16] == 1 || p[16] == 2) && c.pad_bytes % 4 == 0, "s2v_diag_vae_conv_run: the fill is a 16- or a 32-bit pattern");
+        if (p[16] == 1) S2V_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)c.pad, (unsigned short)p[17], (size_t)c.pad_bytes / 2, st));
+        else S2V_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)c.pad, p[17], (size_t)c.pad_bytes / 4, st));
+        v->cur_h = v->cur_w = 0;  // no ring is valid any more
+    }
+    S2V_TRY(set_layout(v, th, tw, st, !v->encoder));  // as decode_window / encode_window
+    switch (prod) {
+        case DIAG_PROD_DENSE2: S2V_TRY(launch_dense_to_padded(src, F, H, W, c.cin, c.pad, 2, v->dtype, st)); break;
+        case DIAG_PROD_DENSE0: S2V_TRY(launch_dense_to_padded(src, F, H, W, c.cin, c.pad, 0, v->dtype, st)); break;
+        case DIAG_PROD_UP: case DIAG_PROD_UP_CT: S2V_TRY(launch_upsample(src, p[1], p[2], p[3], c.cin, prod == DIAG_PROD_UP_CT, c.pad, v->dtype, st)); break;
+        case DIAG_PROD_POOL: S2V_TRY(launch_time_pool_to_padded(src, p[1], H, W, c.cin, c.pad, v->dtype, st)); break;
+        default:
+            S2V_REQUIRE(p[11] >= 0 && p[12] >= 0 && p[11] + H <= p[9] && p[12] + W <= p[10], "s2v_diag_vae_conv_run: the window leaves the image");
+            S2V_TRY(launch_image_to_padded(src, c.cin, F, p[7], p[8], p[9], p[10], p[11], p[12], H, W, c.pad, 2, v->dtype, st));
+    }
+    bool direct = false;
+    g_vae_diag_route = 0;
+    const int M = stride2 ? F * (H / 2) * (W / 2) : F * H * W;
+    if (stride2) S2V_TRY(run_conv_down(v, c, F, H, W, out, st));
+    else if (p[13] == 0) S2V_TRY(run_conv(v, c, F, H, W, p[4] != 0, epi, resid, out, st));
+    else {
+        S2V_REQUIRE(p[15] >= 0 && p[15] + F <= p[14], "s2v_diag_vae_conv_run: the frames leave the tile");
+        S2V_REQUIRE((int64_t)M * c.cout * v->esz + (int64_t)256 * 1024 * v->esz <= v->dense_bytes, "s2v_diag_vae_conv_run: rows beyond the dense buffers");
+        S2V_TRY(run_conv(v, c, F, H, W, p[4] != 0, epi, resid, v->dense[1], st, (char*)out, p[14], p[15], &direct));
+        if (!direct) S2V_TRY(launch_to_ncfhw(v->dense[1], F, H, W, c.cout, out, p[14], p[15], v->dtype, st));
+    }
+    info[0] = direct; info[1] = g_vae_diag_route; info[2] = F; info[3] = H; info[4] = W; info[5] = M;
+    return 0;
+}
+#endif

@@ -71,28 +71,29 @@ def ulp(v):
 
 
 class Guarded:
-    """[GUARD + rows + GUARD][ld] elements of a sentinel bit pattern with `body` ([rows][cols]; None: NaN, bytes 0xA5) in the middle, columns < cols"""
+    """[guard + rows + guard][ld] elements of a sentinel bit pattern with `body` ([rows][cols]; None: NaN, bytes 0xA5) in the middle, columns < cols;
+    guard: GUARD rows unless the caller's kernels work in larger row tiles"""
 
-    def __init__(self, rows, cols, ld, dt, body=None, device="cpu"):
-        self.rows, self.cols, self.ld, self.dt = rows, cols, ld, dt
+    def __init__(self, rows, cols, ld, dt, body=None, device="cpu", guard=GUARD):
+        self.rows, self.cols, self.ld, self.dt, self.guard = rows, cols, ld, dt, guard
         self.es = torch.empty(0, dtype=dt).element_size()
         idt, self.sent = {1: (torch.uint8, 0x5A), 2: (torch.int16, 0x5A5A), 4: (torch.int32, 0x5A5A5A5A)}[self.es]
-        buf = torch.full((2 * GUARD + rows, ld), self.sent, dtype=idt)
+        buf = torch.full((2 * guard + rows, ld), self.sent, dtype=idt)
         if body is None:
             body = torch.full((rows, cols), 0xA5, dtype=dt) if self.es == 1 else torch.full((rows, cols), float("nan"), dtype=dt)
         init = body.to(dt)
-        buf[GUARD:GUARD + rows, :cols] = init.view(idt)
+        buf[guard:guard + rows, :cols] = init.view(idt)
         self.buf = buf.to(device)
 
     def body_ptr(self):
-        return self.buf.data_ptr() + GUARD * self.ld * self.es
+        return self.buf.data_ptr() + self.guard * self.ld * self.es
 
     def body(self):
-        return self.buf[GUARD:GUARD + self.rows, :self.cols].contiguous().view(self.dt)
+        return self.buf[self.guard:self.guard + self.rows, :self.cols].contiguous().view(self.dt)
 
     def guards_intact(self):
         g = self.buf.clone()
-        g[GUARD:GUARD + self.rows, :self.cols] = self.sent
+        g[self.guard:self.guard + self.rows, :self.cols] = self.sent
         return bool((g == self.sent).all().item())
 
 
