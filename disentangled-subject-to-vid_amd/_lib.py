@@ -132,6 +132,27 @@ _SIGS.update({
     "s2v_op_attn_mass": [_P, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P, _I32, _I32, _I32, _P],
     "s2v_op_attn_mass_mean": [_P, _I32, _I32, _I32, _I32, _I64, _P, _P],
 })
+# attention steering (include/s2v_hip.h: s2v_attn_steer_*, s2v_op_attention_steer)
+STEER_MAX_RANGES = 4
+
+
+class SteerRangeC(ctypes.Structure):
+    """s2v_attn_steer_range: keys [k0, k1) weighted by w on the samples whose bit is set in sample_mask"""
+    _fields_ = [("k0", ctypes.c_int32), ("k1", ctypes.c_int32), ("w", ctypes.c_float), ("sample_mask", ctypes.c_uint32)]
+
+
+class SteerRecordC(ctypes.Structure):
+    """s2v_attn_steer_record: the operator-level record, ranges as arrays plus the query range [q0, q1)"""
+    _fields_ = [("n", ctypes.c_int32), ("q0", ctypes.c_int32), ("q1", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("k0", ctypes.c_int32 * 4), ("k1", ctypes.c_int32 * 4), ("w", ctypes.c_float * 4), ("sample_mask", ctypes.c_uint32 * 4)]
+
+
+_SIGS.update({
+    "s2v_attn_steer_enable": [_P, _I32],
+    "s2v_attn_steer_set": [_P, _I32, ctypes.POINTER(SteerRangeC)],
+    "s2v_attn_steer_arm": [_P, ctypes.c_uint64],
+    "s2v_op_attention_steer": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(SteerRecordC), _P],
+})
 # temporal windows (include/s2v_hip.h: s2v_set_windows, s2v_denoise_step_windows, s2v_op_window_blend)
 _SIGS.update({
     "s2v_set_windows": [_P, _I32, _I32, _I32, ctypes.POINTER(_F)],

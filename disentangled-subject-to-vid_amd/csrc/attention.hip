@@ -15,6 +15,9 @@
 //     O^T = V^T . P^T accumulates with the query again on the lane axis.
 //     Softmax in the exp2 domain: Q is pre-multiplied by scale * log2(e) and the S^T accumulators start at -m_run (a
 //     loop-carried register block), so p = exp2(MFMA result) with no per-score fma.
+//  attn_pp_steer_k / attn_pp_steer_persist_k : attn_pp_item<ACCT, STEER = true> in the same two launch forms -- attention steering, a logit bias
+//     log2 w on up to four key ranges (kernels.h AttnSteerRec; include/s2v_hip.h "Attention steering"); what a steered layer of a bf16 engine
+//     runs at every length.  attn_simple_steer_k<T>: the same bias in the generic kernel (fp32 engines, and the cross-check).
 //  attn_bf16_k (S2V_DIAG builds only): the round-1 lock-step kernel with a per-tile row maximum, kept as the A/B reference.
 //  attn_simple_k<T> : one wave per query row, fp32 math, any dtype (CPU-reference-parity mode / cross-check).
 #define S2V_HOST
@@ -276,8 +279,17 @@ extern "C" __attribute__((visibility("default"))) int s2v_attn_debug_read_blocks
 extern "C" __attribute__((visibility("default"))) int s2v_attn_debug_read(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_dbg), sizeof(long long) * 64) == hipSuccess ? 0 : -1; }
 #endif
 // one work item = the 256 query rows (wg % nqb) of (sample, head) wg / nqb; all eight waves enter and leave it together
-template <bool ACCT>
-__device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg, char* smem) {
+// STEER (attention steering, kernels.h AttnSteerRec): the scores of the keys of up to four ranges get log2 w added on the query rows [q0, q1) of
+// the samples in the range's mask -- before the tail mask and before everything the softmax segment does (the sum vote, the slow path's
+// maximum, exp2), so the deferred maximum sees the biased scores.  A key is an accumulator row and a query a lane, so a KV tile is classified
+// wave-uniformly against the ranges: outside every range it runs the un-steered code; wholly inside one, 32 adds of one per-lane value;
+// straddling an edge, compares on the key index the tail mask computes (at most eight such tiles at any length).  The query range is the
+// per-lane factor (the addend is 0.0f on the other lanes).  A wave with no row in [q0, q1), and every wave of a sample outside the masks,
+// takes the un-steered path on every tile: those rows equal the un-steered launch bit for bit.  So do the rows outside [q0, q1) of a wave
+// that has rows inside, UNLESS a steered lane of that wave votes the wave into a slow path past tile 0 that the un-steered launch does not take
+// (or the reverse): the slow path re-sums the tile's p in another order, within rounding of the fast sum.  STEER = false: nothing below changes.
+template <bool ACCT, bool STEER = false>
+__device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg, char* smem, const AttnSteerRec* __restrict__ sr = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;
@@ -321,6 +333,26 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
         qf[kk] = *(const bf16x8*)(qkv + (size_t)q_ld * a.ld_qkv + h * 64 + kk * 16 + hi * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) qf[kk][e] = (__bf16)((float)qf[kk][e] * c0);
+    }
+
+    // STEER: this item's view of the record, wave-uniform (scalar registers): the ranges that apply to this sample and wave as a bit set, and their
+    // envelope [s_lo, s_hi) -- a tile outside it never looks at the record (both 0 when no range applies)
+    unsigned s_on = 0;
+    int s_lo = 0, s_hi = 0;
+    bool inq = false;
+    if constexpr (STEER) {
+        const int bu = __builtin_amdgcn_readfirstlane(b);
+        const int wq0 = __builtin_amdgcn_readfirstlane(qb) * 256 + wave * 32;
+        const int sq0 = sr->q0, sq1 = sr->q1, sn = min(sr->n, ATTN_STEER_MAX_RANGES);
+        if (wq0 < sq1 && wq0 + 32 > sq0) {
+            for (int r = sn - 1; r >= 0; --r)
+                if ((sr->sample_mask[r] >> bu) & 1u) {
+                    if (!s_on) s_hi = sr->k1[r];
+                    s_lo = sr->k0[r];
+                    s_on |= 1u << r;
+                }
+        }
+        inq = q_row >= sq0 && q_row < sq1;
     }
 
     // the S^T accumulators START at -m_run: this 16-register block is loop-carried and only rewritten on the slow path
@@ -367,6 +399,31 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
         // ---- softmax segment S(t)
         const long long u0 = now();
         const int kv0 = t * KV_TILE;
+        if constexpr (STEER) {
+            if (kv0 < s_hi && kv0 + KV_TILE > s_lo) {
+#pragma nounroll
+                for (int r = 0; r < ATTN_STEER_MAX_RANGES; ++r) {
+                    if (!((s_on >> r) & 1u)) continue;
+                    const int lo = max(sr->k0[r], kv0), up = min(sr->k1[r], kv0 + KV_TILE);
+                    if (lo >= up) continue;  // the tile holds no key of range r
+                    const float bl = inq ? sr->log2w[r] : 0.f;
+                    if (up - lo == KV_TILE) {  // interior tile
+#pragma unroll
+                        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) st[kb][e] += bl;
+                    } else {  // an edge of the range inside the tile: the key index of the tail mask, as an offset from the range's first key
+                        const unsigned len = (unsigned)(up - lo);
+                        const int kvb = kv0 - lo + 4 * hi;
+#pragma unroll
+                        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e)
+                                if ((unsigned)(kvb + kb * 32 + (e & 3) + 8 * (e >> 2)) < len) st[kb][e] += bl;
+                    }
+                }
+            }
+        }
         if (kv0 + KV_TILE > a.Ntok) {  // tail tile: mask keys >= Ntok
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -516,11 +573,20 @@ __global__ __launch_bounds__(512, 2) void attn_pp_k(const AttnArgs a, int nqb) {
     attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
     attn_pp_item<ACCT>(a, nqb, first + (int)(blockIdx.x >> 3), smem);
 }
+// the STEER = true instantiation of the same launch form: the record comes as one more pointer argument
+__global__ __launch_bounds__(512, 2) void attn_pp_steer_k(const AttnArgs a, int nqb, const AttnSteerRec* __restrict__ sr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int first, cnt;
+    attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
+    attn_pp_item<false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, sr);
+}
 // PERSISTENT form (the engine's launches): one workgroup per CU pulls items from its XCD's queue and, when that is empty, from the
 // other XCDs' queues.  The hardware hands every XCD exactly 1/8 of a grid, but the XCDs of one launch run a few percent apart in
 // clock: with static shares the launch ended 95-100 % apart per XCD plus a last round of 32 items on 256 slots (4.6 % of the
 // slot-time idle, tools/attn_harness timeline); pulled work ends within one item.  queue[0..7]: next item of XCD x, queue[8]:
 // workgroups done -- the last one to leave zeroes the nine counters for the next launch (they must be zero at the first).
+// TWIN: attn_pp_steer_persist_k below repeats this loop word for word (a shared function changed this kernel's schedule): a change to the
+// queue protocol here is made there as well.
 template <bool ACCT>
 __global__ __launch_bounds__(512, 2) void attn_pp_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -544,6 +610,38 @@ __global__ __launch_bounds__(512, 2) void attn_pp_persist_k(const AttnArgs a, in
         __syncthreads();
         if (wg < 0) break;
         attn_pp_item<ACCT>(a, nqb, wg, smem);
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&queue[8], 1) == (int)gridDim.x - 1) {
+            for (int i = 0; i < 9; ++i) __hip_atomic_store(&queue[i], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __threadfence();
+        }
+    }
+}
+// the STEER = true instantiation of the persistent form: the same loop (kept as a twin so that the kernel above keeps its code to the instruction)
+__global__ __launch_bounds__(512, 2) void attn_pp_steer_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue, const AttnSteerRec* __restrict__ sr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_item;
+    const int xcd = blockIdx.x & 7;
+    for (;;) {
+        if (threadIdx.x == 0) {
+            int wg = -1;
+            for (int k = 0; k < 8 && wg < 0; ++k) {
+                const int y = (xcd + k) & 7;
+                int first, cnt;
+                attn_xcd_range(total, y, first, cnt);
+                if (__hip_atomic_load(&queue[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= cnt) continue;  // drained: do not hammer it
+                const int i = atomicAdd(&queue[y], 1);
+                if (i < cnt) wg = first + i;
+            }
+            s_item = wg;
+        }
+        __syncthreads();  // also fences the previous item's LDS traffic from the next item's prologue
+        const int wg = s_item;
+        __syncthreads();
+        if (wg < 0) break;
+        attn_pp_item<false, true>(a, nqb, wg, smem, sr);
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -625,7 +723,57 @@ int launch_attn_bf16(const AttnArgs& a_in, hipStream_t st) {
     return launch_attn_q4(a, persist, st);
 }
 
+// a steered layer of a bf16 engine (and s2v_op_attention_steer impl 0): attn_pp<STEER> at every length, persistent under the rule above
+int launch_attn_bf16_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_bf16_steer: steer record missing");
+    S2V_REQUIRE(a.vt != nullptr, "attn_bf16_steer: V^T buffer missing");
+    S2V_REQUIRE(a.mx_q == nullptr && !a.p16, "attn_bf16_steer: attn_pp writes bf16 and reads bf16 V^T (no MX output, no attn_p_format 1)");
+    S2V_REQUIRE(a.ld_qkv % 8 == 0 && a.ntok_pad % 64 == 0, "attn_bf16_steer: bad leading dims");
+    S2V_REQUIRE(a.ntok_pad >= ((a.Ntok + 63) / 64) * 64, "attn_bf16_steer: ntok_pad too small");
+    S2V_REQUIRE(a.B >= 1 && a.B <= 32, "attn_bf16_steer: the sample masks hold 32 samples");
+    int nqb8 = (a.Ntok + 255) / 256;
+    int total = nqb8 * a.B * a.H;
+    const bool persist = a.queue != nullptr && total > 2 * a.num_cus && a.num_cus >= 8;
+    const void* fn = persist ? (const void*)attn_pp_steer_persist_k : (const void*)attn_pp_steer_k;
+    S2V_TRY(ensure_lds_attr(fn, 65536));
+    AttnArgs av = a;
+    if (persist) {
+        int* queue = a.queue;
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&total, (void*)&queue, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3((a.num_cus / 8) * 8), dim3(512), args, 65536, st));
+    } else {
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(total), dim3(512), args, 65536, st));
+    }
+    return 0;
+}
+
+// host: the record from n ranges, refused by name when a range, a weight or the query range is wrong
+int attn_steer_make(const char* who, int n, const int* k0, const int* k1, const float* w, const unsigned* sample_mask, int q0, int q1, int Ntok,
+                    AttnSteerRec* out) {
+    static thread_local char msg[256];
+#define STEER_REQUIRE(cond, ...) do { if (!(cond)) { snprintf(msg, sizeof(msg), __VA_ARGS__); S2V_REQUIRE(false, msg); } } while (0)
+    STEER_REQUIRE(n >= 0 && n <= ATTN_STEER_MAX_RANGES, "%s: 0..4 key ranges are accepted (n = %d)", who, n);
+    STEER_REQUIRE(n == 0 || (k0 && k1 && w && sample_mask), "%s: null range array", who);
+    STEER_REQUIRE(q0 >= 0 && q0 <= q1 && q1 <= Ntok, "%s: the query range [%d, %d) must lie inside [0, Ntok = %d)", who, q0, q1, Ntok);
+    AttnSteerRec r{};
+    r.n = n; r.q0 = q0; r.q1 = q1;
+    for (int i = 0; i < n; ++i) {
+        STEER_REQUIRE(k0[i] >= 0 && k0[i] < k1[i] && k1[i] <= Ntok, "%s: key range %d = [%d, %d) must be non-empty and inside [0, Ntok = %d)", who, i, k0[i], k1[i], Ntok);
+        STEER_REQUIRE(i == 0 || k0[i] >= k1[i - 1], "%s: key range %d = [%d, %d) overlaps or precedes range %d (ranges are disjoint and ascending)", who, i, k0[i], k1[i], i - 1);
+        STEER_REQUIRE(w[i] == w[i] && w[i] >= 1.52587890625e-05f && w[i] <= 65536.0f, "%s: weight %d = %g must be finite and inside [2^-16, 2^16] (no w = 0)", who, i, (double)w[i]);
+        r.k0[i] = k0[i]; r.k1[i] = k1[i]; r.sample_mask[i] = sample_mask[i];
+        r.log2w[i] = (float)log2((double)w[i]);
+        r.lnw[i] = (float)log((double)w[i]);
+    }
+#undef STEER_REQUIRE
+    *out = r;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------
+// TWIN: attn_simple_steer_k below repeats this body with the bias added to the score (a shared function changed this kernel's code): a change
+// here is made there as well.
 template <typename T>
 __global__ __launch_bounds__(256) void attn_simple_k(const AttnArgs a) {
     __shared__ float sq[4][64];
@@ -663,6 +811,52 @@ __global__ __launch_bounds__(256) void attn_simple_k(const AttnArgs a) {
     }
     if (active) ET<T>::st((T*)a.out + (size_t)(b * a.Ntok + q) * a.ld_out + h * 64 + lane, o / l);
 }
+// the steered form of attn_simple_k (a twin, so that the kernel above keeps its code): beta = ln w of the key's range (AttnSteerRec::lnw) is added
+// to the score of an in-range key before the maximum and expf, on the query rows and samples the record names.  Speed is no goal here: fp32 is
+// the parity mode, and this form is the second implementation the steered MFMA kernel is checked against.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_simple_steer_k(const AttnArgs a, const AttnSteerRec* __restrict__ sr) {
+    __shared__ float sq[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave, h = blockIdx.y, b = blockIdx.z;
+    const int D = a.H * 64;
+    const bool active = q < a.Ntok;
+    const T* base = (const T*)a.qkv + (size_t)b * a.Ntok * a.ld_qkv;
+    const int ql = active ? q : a.Ntok - 1;
+    sq[wave][lane] = ET<T>::ld(base + (size_t)ql * a.ld_qkv + h * 64 + lane) * a.scale;
+    __syncthreads();
+    const bool steer_row = q >= sr->q0 && q < sr->q1;
+    float m = -INFINITY, l = 0.f, o = 0.f;
+    for (int kv0 = 0; kv0 < a.Ntok; kv0 += 64) {
+        const int kv = kv0 + lane;
+        float s = -INFINITY;
+        if (kv < a.Ntok) {
+            const T* kp = base + (size_t)kv * a.ld_qkv + D + h * 64;
+            float acc = 0.f;
+#pragma unroll 8
+            for (int d = 0; d < 64; ++d) acc = fmaf(sq[wave][d], ET<T>::ld(kp + d), acc);
+            s = acc;
+            if (steer_row) {
+#pragma unroll
+                for (int r = 0; r < ATTN_STEER_MAX_RANGES; ++r)
+                    if (r < sr->n && kv >= sr->k0[r] && kv < sr->k1[r] && ((sr->sample_mask[r] >> b) & 1u)) s += sr->lnw[r];
+            }
+        }
+        const float mx = wave_max(s);
+        const float mn = fmaxf(m, mx);
+        const float alpha = expf(m - mn);
+        const float p = expf(s - mn);
+        l = l * alpha + wave_sum(p);
+        o *= alpha;
+        m = mn;
+        const int nv = min(64, a.Ntok - kv0);
+        for (int j = 0; j < nv; ++j) {
+            const float pj = __shfl(p, j, 64);
+            o = fmaf(pj, ET<T>::ld(base + (size_t)(kv0 + j) * a.ld_qkv + 2 * D + h * 64 + lane), o);
+        }
+    }
+    if (active) ET<T>::st((T*)a.out + (size_t)(b * a.Ntok + q) * a.ld_out + h * 64 + lane, o / l);
+}
 
 // fp16 model dtype: qkv / out fp16, a.vt = V^T [B][H][64][ntok_pad] fp16 in the k-slot order (launch_v_transpose moves 16-bit elements: the bf16
 // pass serves fp16 input unchanged)
@@ -681,6 +875,15 @@ int launch_attn_simple(const AttnArgs& a, int dtype, hipStream_t st) {
     if ((dtype == S2V_F32 || dtype == S2V_F16) && !a.valu_only) return launch_attn_f32m(a, dtype, st);
     dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
     S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_k<T>, grid, dim3(256), 0, st, a))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_attn_simple_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, int dtype, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_simple_steer: steer record missing");
+    S2V_REQUIRE(a.B >= 1 && a.B <= 32, "attn_simple_steer: the sample masks hold 32 samples");
+    dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_steer_k<T>, grid, dim3(256), 0, st, a, rec_dev))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

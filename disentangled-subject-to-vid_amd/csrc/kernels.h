@@ -296,6 +296,27 @@ int launch_attn_q4(const AttnArgs& a, bool persistent, hipStream_t st);
 // eight waves x 32 rows running the same fine-grained stream, two waves per SIMD
 int launch_attn_q8(const AttnArgs& a, bool persistent, hipStream_t st);
 
+// ---- attention steering: a logit bias on key ranges (include/s2v_hip.h, "Attention steering") --------------------
+//   out_i = sum_j softmax_j(s_ij + beta_b(i, j)) v_j,  s_ij = q_i . k_j / 8,
+//   beta_b(i, j) = ln w_r  when key j lies in range r = [k0[r], k1[r]), bit b of sample_mask[r] is set and query row i lies in [q0, q1); else 0.
+// The record as the kernels read it from DEVICE memory with uniform loads (it is data, not a launch argument: new weights re-capture nothing).
+// Ranges disjoint and ascending inside [0, Ntok), 2^-16 <= w <= 2^16 (attn_steer_make refuses anything else by name).
+#define ATTN_STEER_MAX_RANGES 4
+struct AttnSteerRec {
+    int n, q0, q1, pad;
+    int k0[ATTN_STEER_MAX_RANGES], k1[ATTN_STEER_MAX_RANGES];
+    float log2w[ATTN_STEER_MAX_RANGES];   // what the exp2-domain kernel (attn_pp) adds to its scores
+    float lnw[ATTN_STEER_MAX_RANGES];     // what the generic kernel (attn_simple_k, expf) adds: ln w rounded once, not log2 w times a rounded ln 2
+    unsigned sample_mask[ATTN_STEER_MAX_RANGES];
+};
+// host: check n ranges (k0, k1, w, sample_mask) and the query range against Ntok and fill the record; `who` prefixes the error
+int attn_steer_make(const char* who, int n, const int* k0, const int* k1, const float* w, const unsigned* sample_mask, int q0, int q1, int Ntok,
+                    AttnSteerRec* out);
+// attn_pp<STEER> at ANY length (bf16; persistent under launch_attn_bf16's rule), and the steered attn_simple_k (any dtype; the fp32 engine's steered
+// layers and the cross-check).  rec_dev: the record in device memory.  a.mx_q and a.p16 are refused: attn_pp writes bf16 and reads bf16 V^T only
+int launch_attn_bf16_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, hipStream_t st);
+int launch_attn_simple_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, int dtype, hipStream_t st);
+
 // ---- elementwise / normalisation ------------------------------------------------
 // LayerNorm(eps, affine w,b) then (1+scale)*y+shift with per-row-range modulation sets.
 // rows: [B*Ntok, D]; text rows use (shift_txt, scale_txt), other rows (shift_vid, scale_vid); all [B][mod_stride].

@@ -539,12 +539,40 @@ class S2VEngine:
             mask |= 1 << int(l)
         _lib.check(_lib.lib().s2v_attn_map_arm(self._h, mask))
 
+    # ---- attention steering (include/s2v_hip.h: s2v_attn_steer_*) -------------------------------------------------------------------------
+    def attn_steer_enable(self, on=True):
+        """after set_geometry: allocates the steer record's device table (holding a record that steers nothing); False frees it.  Drops a
+        captured step"""
+        _lib.check(_lib.lib().s2v_attn_steer_enable(self._h, int(bool(on))))
+
+    def attn_steer_set(self, ranges):
+        """up to four (k0, k1, w, sample_mask): the keys [k0, k1) of the samples whose bit is set weigh w times their softmax weight on the video
+        query rows, out_i = sum_j softmax_j(s_ij + ln w) v_j.  Disjoint, ascending, inside [0, Ntok), 2^-16 <= w <= 2^16.  A captured step is kept
+        and replays with the new weights"""
+        ranges = list(ranges)
+        if len(ranges) > _lib.STEER_MAX_RANGES or any(len(r) != 4 for r in ranges):
+            raise _lib.S2VError(f"attn_steer_set: at most {_lib.STEER_MAX_RANGES} ranges, each (k0, k1, w, sample_mask)")
+        arr = (_lib.SteerRangeC * max(1, len(ranges)))(*[_lib.SteerRangeC(int(k0), int(k1), float(w), int(m) & 0xFFFFFFFF) for k0, k1, w, m in ranges])
+        _lib.check(_lib.lib().s2v_attn_steer_set(self._h, len(ranges), arr))
+
+    def _arm_steer(self, steer_layers):
+        """the layers whose attention launch is the steered kernel in the next forward (one-shot; after attn_steer_enable)"""
+        if steer_layers is None:
+            return
+        mask = 0
+        for l in steer_layers:
+            if int(l) != l or l < 0 or l >= 64:
+                raise _lib.S2VError(f"steer_layers: {l!r} is no block index")
+            mask |= 1 << int(l)
+        _lib.check(_lib.lib().s2v_attn_steer_arm(self._h, mask))
+
     # ---- compute -------------------------------------------------------------------------------------------
-    def forward(self, latents, timesteps, shared_latent=False, cache=None, attn_layers=None):
+    def forward(self, latents, timesteps, shared_latent=False, cache=None, attn_layers=None, steer_layers=None):
         """CogVideoXTransformer3DModel.forward seam: latents [B,F,C,H,W]; with shared_latent [n,F,C,H,W], n dividing B: sample j embeds latent
         j mod n (n = 1: every sample the same latent; n = B/2: the CFG batch cat([latents] * 2) of B/2 videos without the copy).
         cache: the step-cache mode of this forward (_arm; after step_cache_enable)
-        attn_layers: the block indices whose attention mass is added to the attention map by this forward (after attn_map_enable)"""
+        attn_layers: the block indices whose attention mass is added to the attention map by this forward (after attn_map_enable)
+        steer_layers: the block indices whose attention runs steered in this forward (after attn_steer_enable / attn_steer_set)"""
         B, T, F, H, W = self.geometry
         lat = latents.to(self.device, self.dtype).contiguous()
         n_lat = lat.numel() // (F * self.cfg.in_channels * H * W)
@@ -557,6 +585,7 @@ class S2VEngine:
         out = torch.empty((B, F, self.cfg.out_channels, H, W), dtype=self.dtype, device=self.device)
         self._arm(cache)
         self._arm_attn(attn_layers)
+        self._arm_steer(steer_layers)
         if shared_latent and n_lat > 1:
             _lib.check(_lib.lib().s2v_transformer_forward_videos(self._h, _lib.ptr(lat), n_lat, _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr()))
             return out
@@ -627,7 +656,8 @@ class S2VEngine:
             _lib.check(_lib.lib().s2v_set_blend(self._h, None, None, None, 0))
             self._blend = None
 
-    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None, subject=False):
+    def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None, subject=False,
+                     steer_layers=None):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
         [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
         (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
@@ -635,13 +665,15 @@ class S2VEngine:
         blend: the masked step (s2v_denoise_step_masked, after set_blend): one _lib.BlendC, or a sequence of b, video k blended with blend[k]
         cache: the step-cache mode of this step's forward (_arm; after step_cache_enable): "capture", "reuse" or None
         attn_layers: the block indices whose attention mass this step adds to the attention map (after attn_map_enable; not with "reuse")
+        steer_layers: the block indices whose attention runs steered in this step (after attn_steer_enable / attn_steer_set; not with "reuse",
+        attn_layers or subject: the library refuses those by name)
         subject: the subject-guidance step (s2v_denoise_step_guided, after set_conditioning_triples): b = B/3 videos of a geometry of B = 3b
         samples [u x b | r x b | f x b], video k combined with coef[k].guidance_subject and coef[k].guidance; with blend its masked form"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
         if subject:
-            return self._denoise_step_guided(latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers)
+            return self._denoise_step_guided(latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers, steer_layers)
         if B > 2:
             if B % 2:
                 raise _lib.S2VError(f"denoise_step: a geometry of {B} samples is no whole number of CFG pairs")
@@ -663,6 +695,7 @@ class S2VEngine:
             self.attn_slow_stats(reset=True)
         self._arm(cache)
         self._arm_attn(attn_layers)
+        self._arm_steer(steer_layers)
         if blend is not None:
             _lib.check(_lib.lib().s2v_denoise_step_masked(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                           int(use_graph and not auto), _lib.stream_ptr()))
@@ -683,7 +716,7 @@ class S2VEngine:
             self.set_attn_p_format("bf16")
         self._attn_auto_pending = False
 
-    def _denoise_step_guided(self, latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers):
+    def _denoise_step_guided(self, latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers, steer_layers=None):
         B, T, F, H, W = self.geometry
         if B % 3:
             raise _lib.S2VError(f"denoise_step(subject=True): a geometry of {B} samples is no whole number of triples [u | r | f]")
@@ -700,6 +733,7 @@ class S2VEngine:
             self.attn_slow_stats(reset=True)
         self._arm(cache)            # the library refuses an armed step by name: the step cache and the attention map assume pairs
         self._arm_attn(attn_layers)
+        self._arm_steer(steer_layers)
         _lib.check(_lib.lib().s2v_denoise_step_guided(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                       int(use_graph and not auto), _lib.stream_ptr()))
         if auto:

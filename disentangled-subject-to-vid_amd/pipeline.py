@@ -113,6 +113,49 @@ class AttentionMap:
         self.text_spans = tuple(tuple(s) for s in text_spans)
 
 
+class AttentionSteer:
+    """what S2VPipeline.__call__(attention_steer=...) steers: on the blocks `layers` (an explicit list: no default is recommended) and the step
+    indices `steps` (None: every step) the joint attention of the video rows runs as softmax(s + ln w) on chosen keys -- `subject` weighs the
+    reference-image keys on every sample of the CFG pairs (both halves carry the reference, so the pair's difference stays text against no
+    text), `text_spans` up to three (k0, k1, w) token ranges of the prompt, applied to the positive halves only (the negative prompt has other
+    tokens).  w = 1 changes nothing; 2^-16 <= w <= 2^16.  No weight, layer or step is recommended"""
+
+    def __init__(self, layers, steps=None, subject=1.0, text_spans=()):
+        self.layers = layers
+        self.steps = steps
+        self.subject = subject
+        self.text_spans = tuple(tuple(s) for s in text_spans)
+
+
+STEER_W_MIN, STEER_W_MAX = 2.0 ** -16, 2.0 ** 16
+
+
+def attention_steer_ranges(st, T, R, b):
+    """the key ranges (k0, k1, w, sample_mask) of an AttentionSteer for b videos laid out [negative x b | positive x b] over [text T | reference R |
+    video]: the text spans, ascending, on the positive halves (bits b .. 2b - 1), then the reference keys [T, T + R) on all 2b samples.  Ranges
+    of weight 1 are left out: an empty list steers nothing.  Host integers only"""
+    pos, every = ((1 << b) - 1) << b, (1 << (2 * b)) - 1
+    spans = sorted((int(k0), int(k1), float(w)) for k0, k1, w in st.text_spans)
+    for i, (k0, k1, w) in enumerate(spans):
+        if k1 > T:
+            raise ValueError(f"`attention_steer`: the text span {(k0, k1)} reaches beyond the {T} prompt tokens")
+        if i and k0 < spans[i - 1][1]:
+            raise ValueError(f"`attention_steer`: the text spans {spans[i - 1][:2]} and {(k0, k1)} overlap")
+    out = [(k0, k1, w, pos) for k0, k1, w in spans if w != 1.0]
+    if float(st.subject) != 1.0:
+        out.append((T, T + R, float(st.subject), every))
+    return out
+
+
+def attention_steer_plan(st, n_steps):
+    """the step indices of a call of n_steps steps on which the layers of `st` run steered"""
+    want = list(range(n_steps)) if st.steps is None else sorted(set(int(i) for i in st.steps))
+    for i in want:
+        if i < 0 or i >= n_steps:
+            raise ValueError(f"`attention_steer`: step {i} is outside the {n_steps} steps this call runs")
+    return want
+
+
 def attention_map_plan(am, n_steps, sc_plan=None):
     """(collect, skipped): the step indices of a call of n_steps steps on which the layers of `am` are armed, and the requested ones that are
     not because the step-cache plan sc_plan (True = full) reuses them: a reuse step does not run the block stack.  Host integers only"""
@@ -513,6 +556,54 @@ class S2VPipeline:
                 raise ValueError(f"`attention_map`: a text span is a token range (k0, k1) with 0 <= k0 <= k1, got {sp!r}")
         return am
 
+    attention_steer_report = None
+
+    @staticmethod
+    def check_attention_steer(st, num_layers, dtype=None, weight_format=None, per_video=False, cfg_parallel=None, ulysses=None, fused=True,
+                              videos_path=False, attention_map=None, step_cache=None, subject_guidance_scale=None, temporal_windows=None):
+        """every refusal of a steered call that needs no step count and no geometry (no device is touched)"""
+        if not isinstance(st, AttentionSteer):
+            raise ValueError("`attention_steer` must be an AttentionSteer(layers, steps=None, subject=1.0, text_spans=())")
+        for name, arg, why in (("attention_map", attention_map, "the map reads the un-steered softmax"),
+                               ("step_cache", step_cache, "a reuse step runs no attention to steer"),
+                               ("subject_guidance_scale", subject_guidance_scale, "steering assumes CFG pairs, subject guidance runs triples"),
+                               ("temporal_windows", temporal_windows, "steering runs one forward per step, a windowed step runs several")):
+            if arg is not None:
+                raise ValueError(f"`attention_steer` together with `{name}`: {why}")
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`attention_steer` together with `{name}`: the steered attention runs on one GPU; "
+                                                          f"CFG-parallel and Ulysses split the attention it steers")
+        if not fused:
+            raise ValueError("`attention_steer` together with fused=False: the steered kernel runs inside the fused step; fused=False is the "
+                             "reference's seam sequence")
+        if per_video or videos_path:
+            raise ValueError("`attention_steer` together with per-video lists (or several input videos, which run per-video plans): one steer on one "
+                             "plan of steps is shared by the whole batch")
+        if dtype == torch.float16:
+            raise ValueError("`attention_steer` with an fp16 engine: the steered kernels serve bf16 (attn_pp) and fp32 (the generic form)")
+        if weight_format is not None:
+            raise ValueError(f"`attention_steer` with weight_format {weight_format!r}: the fp8 engines' attention writes the MX output, the steered "
+                             f"kernel writes bf16 only")
+        if not isinstance(st.layers, (list, tuple)) or len(st.layers) == 0:
+            raise ValueError("`attention_steer`: `layers` is an explicit, non-empty list of block indices (no default is recommended)")
+        for l in st.layers:
+            if int(l) != l or l < 0 or l >= num_layers:
+                raise ValueError(f"`attention_steer`: layer {l!r} is no block index of a model of {num_layers} blocks")
+        if len(set(int(l) for l in st.layers)) != len(st.layers):
+            raise ValueError("`attention_steer`: a layer is listed twice")
+        if st.steps is not None and (not isinstance(st.steps, (list, tuple)) or any(int(i) != i for i in st.steps)):
+            raise ValueError("`attention_steer`: `steps` is a list of step indices, or None for every step")
+        if len(st.text_spans) > 3:
+            raise ValueError(f"`attention_steer`: at most three text spans (four key ranges with the reference stream), got {len(st.text_spans)}")
+        ws = [("subject", st.subject)]
+        for sp in st.text_spans:
+            if len(sp) != 3 or int(sp[0]) != sp[0] or int(sp[1]) != sp[1] or sp[0] < 0 or sp[1] <= sp[0]:
+                raise ValueError(f"`attention_steer`: a text span is (k0, k1, w) with 0 <= k0 < k1, got {sp!r}")
+            ws.append((f"text span {tuple(sp[:2])}", sp[2]))
+        for name, w in ws:
+            if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < STEER_W_MIN or w > STEER_W_MAX:
+                raise ValueError(f"`attention_steer`: the weight of {name} must be finite and inside [2^-16, 2^16], got {w!r}")
+        return st
+
     @staticmethod
     def blend_plan(scheduler, plan, dtype, device="cpu", keep_max=None):
         """the masked step's record (scheduler.blend_record) for every step of a video_plan: step i blends at the video's NEXT timestep
@@ -554,7 +645,7 @@ class S2VPipeline:
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
                  video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None,
-                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None, temporal_windows=None):
+                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None, temporal_windows=None, attention_steer=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -618,9 +709,24 @@ class S2VPipeline:
         with their weights where they overlap and takes ONE scheduler step on the whole latent; the VAE decodes the long latent in one call.
         All windows share the timestep, the prompt pair and the reference.  `video` / `strength` only move the start of the loop.  One video per
         call on one GPU with scalars; refused with mask=, change_map=, step_cache=, attention_map=, subject_guidance_scale=, per-video lists,
-        cfg_parallel=, ulysses= and fused=False."""
+        cfg_parallel=, ulysses= and fused=False.
+        attention_steer: an AttentionSteer(layers, steps=None, subject=1.0, text_spans=()) -- on the listed steps (None: every step) the attention
+        of the listed blocks runs steered: for the video query rows, softmax(s + ln w) with w = `subject` on the reference-image keys of every
+        sample and w of each text span (k0, k1, w) on the positive halves.  Exact biased-softmax attention, no extra sample per video.  A call
+        whose weights are all 1 arms nothing: its launches and bits are those of the call without it.  Composes with video= / strength, mask=,
+        change_map=, paste_back, use_graph, both schedulers, runtime LoRA on bf16 and several videos per call with scalars (one steer shared by
+        all).  After the call `attention_steer_report` holds {"steps", "layers", "ranges"}.  Refused with attention_map=, step_cache=,
+        subject_guidance_scale=, temporal_windows=, cfg_parallel=, ulysses=, fused=False, per-video lists, several input videos, fp16 and fp8
+        engines.  No weight, layer or step is recommended."""
         self.step_cache_report = None
         self.attention_maps = None
+        self.attention_steer_report = None
+        if attention_steer is not None:   # refused before anything else looks at the arguments it excludes
+            nb_ = prompt_embeds.shape[0] * num_videos_per_prompt if prompt_embeds is not None and prompt_embeds.ndim == 3 else 1
+            attention_steer = self.check_attention_steer(
+                attention_steer, self.transformer.config.num_layers, self.transformer.dtype, getattr(self.transformer.config, "weight_format", None),
+                any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength)), cfg_parallel, ulysses, fused,
+                video is not None and nb_ > 1, attention_map, step_cache, subject_guidance_scale, temporal_windows)
         if change_map is not None and mask is not None:
             raise ValueError("`change_map` together with `mask`: both say which cells are kept; a change map of 0 and 255 alone is that mask")
         levels = change_map is not None   # from here on `mask` is the call's plane, read as levels 0..255 when `levels`
@@ -707,11 +813,11 @@ class S2VPipeline:
         return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
                              num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                              callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
-                             step_cache, attention_map)
+                             step_cache, attention_map, steer=attention_steer)
 
     def _denoise(self, plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator, latents,
                  output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video,
-                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None, windows=None):
+                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None, windows=None, steer=None):
         """the one denoise loop: b = len(plans) videos, each on its video_plan; iteration i applies step i of every video that still has one.
         The videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers;
         when the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
@@ -727,7 +833,9 @@ class S2VPipeline:
         guided step with the subject scale of each video's coefficient sets; everything else of the loop is the pair call's
         windows: a long call (None: every other call, which touches no window entry) -- its window_plan.  One video whose latents, x0 history
         and noise have L frames; the geometry is 2 per_forward samples of the WINDOW's F frames, conditioned with the text pair repeated
-        per_forward times, and every step is the windowed step on the whole long latent"""
+        per_forward times, and every step is the windowed step on the whole long latent
+        steer: a steered call (None: every other call, which touches no steer entry) -- its AttentionSteer, checked; scalars only, so the batch
+        never shrinks and the one geometry holds for the whole call"""
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         b = len(plans)
@@ -841,6 +949,12 @@ class S2VPipeline:
             if eng.fp8_qk_active:
                 raise ValueError("`attention_map` while fp8 QK^T is active at this geometry ('fp8-auto' beyond its token threshold): the map needs "
                                  "16-bit attention (None or 'fp8')")
+        st_steps, st_ranges = [], []
+        if steer is not None:   # the ranges and the steered steps, on the host, before the loop; all weights 1: nothing is enabled or armed
+            st_ranges = attention_steer_ranges(steer, text.shape[1], (H // 2) * (W // 2), b)
+            st_steps = attention_steer_plan(steer, lens[0]) if st_ranges else []
+            self.attention_steer_report = {"steps": list(st_steps), "layers": [int(l) for l in steer.layers] if st_ranges else [],
+                                           "ranges": list(st_ranges)}
         active = b
         old = [None] * b   # fused=False under DPM: every video's x0 of its last step
         last_t = [plans[k]["timesteps"][0] for k in order]
@@ -850,6 +964,9 @@ class S2VPipeline:
                 eng.step_cache_enable(True)
             if attention_map is not None:
                 eng.attn_map_enable(True, attention_map.text_spans)
+            if st_ranges:
+                eng.attn_steer_enable(True)
+                eng.attn_steer_set(st_ranges)
             for i in range(lens[0]):
                 if self.interrupt:
                     break
@@ -894,7 +1011,8 @@ class S2VPipeline:
                         collect = am_steps is not None and i in am_steps and cache != "reuse"
                         eng.denoise_step(latents[:a], ts, coefs, x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph,
                                          blend=None if mask is None else [blends[p][i] for p in range(a)], cache=cache,
-                                         attn_layers=attention_map.layers if collect else None, **({} if subject is None else {"subject": True}))
+                                         attn_layers=attention_map.layers if collect else None, **({} if subject is None else {"subject": True}),
+                                         **({"steer_layers": steer.layers} if st_ranges and i in st_steps else {}))
                         if collect:
                             am_ran.append(i)
                 else:
@@ -956,6 +1074,8 @@ class S2VPipeline:
                 eng.step_cache_enable(False)
             if attention_map is not None and eng.geometry is not None:
                 eng.attn_map_enable(False)
+            if st_ranges:
+                eng.attn_steer_enable(False)
         return self._finish(callers(latents), fused, output_type, return_dict, paste)
 
     @staticmethod

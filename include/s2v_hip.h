@@ -461,6 +461,61 @@ S2V_API int s2v_attn_map_arm(s2v_ctx* ctx, uint64_t layer_mask);
 S2V_API int s2v_attn_map_read(s2v_ctx* ctx, int32_t per_head, void* out_dev, int64_t* count, s2v_stream stream);
 S2V_API int s2v_attn_map_reset(s2v_ctx* ctx);
 
+/* ---- Attention steering: a logit bias on key ranges (prompt-to-prompt style reweighting, softmax(s + ln w)) -------------------------------------
+ * ONE definition, which the kernels (csrc/attention.hip), tests/attn_steer_ref.py and this comment state alike.  For sample b, head h, query row
+ * i and key j of the joint attention over [text T | reference R | video V]:
+ *     s_ij  = q_i . k_j / 8
+ *     out_i = sum_j softmax_j(s_ij + beta_b(i, j)) v_j
+ *     beta_b(i, j) = ln w_r  when all three hold: j lies in key range r = [k0_r, k1_r), bit b of that range's sample_mask is set, and i lies in the
+ *                    query range [q0, q1);  otherwise beta_b(i, j) = 0.
+ * At most four key ranges, disjoint and ascending, each non-empty and inside [0, Ntok); w finite with 2^-16 <= w <= 2^16 (no w = 0: a first key
+ * tile that is entirely -inf would break the kernel's adoption of the first tile's maximum); B <= 32 samples.  In the MFMA kernel the bias is
+ * log2 w, added to the exp2-domain score before the tail mask's -inf and before everything its softmax segment does (the row-sum vote of the
+ * deferred maximum, the slow path's maximum, exp2); the generic kernel adds ln w before its maximum and expf.
+ * Rows outside [q0, q1) and samples outside every mask are un-steered rows: a sample outside the masks, and a 32-row wave of the MFMA kernel with
+ * no row inside [q0, q1), run the un-steered code on every key tile and return the un-steered launch's bits (both attn_pp, i.e. bf16 up to 4608
+ * tokens; beyond, the un-steered product kernel is attn_q4, within rounding).  The rows outside [q0, q1) of a wave that also holds rows inside
+ * get 0.0f added and return the same bits unless a steered row of their wave changes the wave-wide vote of the deferred maximum past the first
+ * key tile (a row sum beyond 2^64): the slow path re-sums a tile in another order, within rounding.
+ * Engines: a steered layer of a bf16 engine runs attn_pp<STEER> at EVERY length (persistent under the rule of the un-steered launch); an fp32
+ * engine runs the steered generic kernel -- fp32 is the parity mode and its speed is no goal.  Un-steered layers, and every call with steering
+ * off, run the launches they run without this feature.
+ * s2v_attn_steer_enable: after s2v_set_geometry; on != 0 allocates the record's device table (counted by s2v_device_bytes as workspace while on) holding
+ * a record that steers nothing, on = 0 frees it.  Drops a captured step.  While off every entry runs what it runs without this feature.
+ * s2v_attn_steer_set: n <= 4 ranges; the query range is the geometry's video rows [T + R, Ntok).  Checks the ranges against the current geometry
+ * (inside [0, Ntok), order, overlap, weight bounds) with an error that names what is wrong, BEFORE anything is replaced; synchronises the device and
+ * uploads.  The table is data, not a launch argument: a captured step is kept and replays with the new weights.  A later s2v_set_geometry re-checks
+ * the held ranges; one that no longer fits refuses the geometry call and leaves steering off.
+ * s2v_attn_steer_arm: the layers (bit l = block l) of the NEXT forward only (s2v_transformer_forward*, s2v_denoise_step, _videos, _masked).  An
+ * armed step is another launch sequence: captured steps are kept per (step-cache mode, map layer mask, steer layer mask), and an un-armed step
+ * never replays an armed executable nor the reverse.
+ * Refused by name: fp16 engines; every fp8 weight format (their attention writes the MX output); attn_p_format 1 (fp16 V^T); shard contexts;
+ * attention-only contexts; triple-conditioned contexts and s2v_denoise_step_guided; contexts with temporal windows and s2v_denoise_step_windows;
+ * s2v_denoise_split_begin (CFG-parallel); an armed attention map or S2V_STEP_REUSE together with an armed steer, in either order of the two arms; a
+ * layer bit at or beyond num_layers; s2v_block_forward and the s2v_attn_forward* / AttnProcessor seams while a steer is armed. */
+typedef struct s2v_attn_steer_range {
+    int32_t k0, k1;          /* keys [k0, k1) of every sample's Ntok */
+    float w;                 /* the softmax weight of those keys is multiplied by w before normalisation */
+    uint32_t sample_mask;    /* bit b: the range applies to sample b */
+} s2v_attn_steer_range;
+/* the operator-level record: the ranges as arrays plus the query range */
+typedef struct s2v_attn_steer_record {
+    int32_t n, q0, q1, reserved;
+    int32_t k0[4], k1[4];
+    float w[4];
+    uint32_t sample_mask[4];
+} s2v_attn_steer_record;
+S2V_API int s2v_attn_steer_enable(s2v_ctx* ctx, int32_t on);
+S2V_API int s2v_attn_steer_set(s2v_ctx* ctx, int32_t n, const s2v_attn_steer_range* ranges_host);
+S2V_API int s2v_attn_steer_arm(s2v_ctx* ctx, uint64_t layer_mask);
+/* the steered kernel on its own: qkv / vt_scratch / out as s2v_op_attention takes them.  impl 0: attn_pp<STEER> (bf16, any Ntok, one workgroup
+ * per 256 query rows); impl 1: the steered generic kernel (any dtype).  The record is copied to ONE table per process on the device current at the
+ * first call, ordered on `stream`: such calls stay on that device and on the stream of the first call (another stream is refused by name), and
+ * the entry is not thread-safe -- a test and benchmark entry; contexts hold their own table.  Refused by name: a bad record (as
+ * s2v_attn_steer_set), impl 0 with another dtype than bf16 */
+S2V_API int s2v_op_attention_steer(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                   const s2v_attn_steer_record* record_host, s2v_stream stream);
+
 /* Live per-kernel timing for the roofline report (bench.py): HIP events are recorded on the launch stream around
  * every launch of a class; classes 0 qkv GEMM, 1 attention, 2 out-proj GEMM, 3 FF1 GEMM, 4 FF2 GEMM,
  * 5 LN-modulate, 6 qk-norm/rope/V^T, 7 the modulation GEMV, 8 the Ulysses packs, 9 the runtime-LoRA down-projections.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
