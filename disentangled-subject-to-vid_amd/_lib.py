@@ -153,6 +153,21 @@ _SIGS.update({
     "s2v_attn_steer_arm": [_P, ctypes.c_uint64],
     "s2v_op_attention_steer": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(SteerRecordC), _P],
 })
+# local attention in time (include/s2v_hip.h: s2v_attn_local_*, s2v_op_attention_local)
+_SIGS.update({
+    "s2v_attn_local_enable": [_P, _I32],
+    "s2v_attn_local_set": [_P, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
+    "s2v_attn_local_arm": [_P, ctypes.c_uint64],
+    "s2v_op_attention_local": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32), _P],
+})
+
+
+def i32_array(values):
+    """a ctypes int32 array of a sequence or tensor of integers (the row tables of local attention)"""
+    vals = [int(v) for v in (values.tolist() if hasattr(values, "tolist") else values)]
+    return (_I32 * max(1, len(vals)))(*vals)
+
+
 # temporal windows (include/s2v_hip.h: s2v_set_windows, s2v_denoise_step_windows, s2v_op_window_blend)
 _SIGS.update({
     "s2v_set_windows": [_P, _I32, _I32, _I32, ctypes.POINTER(_F)],

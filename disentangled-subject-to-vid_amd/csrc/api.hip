@@ -83,8 +83,9 @@ struct GraphKey {
         return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask && triple == o.triple &&
                windows == o.windows;
     }
-    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask && smask == o.smask; }
-    bool armed() const { return amask != 0 || smask != 0; }
+    uint64_t lmask = 0;   // s2v_attn_local_arm: the layers whose attention launch is the local kernel in this step; an executable per mask as well
+    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask && smask == o.smask && lmask == o.lmask; }
+    bool armed() const { return amask != 0 || smask != 0 || lmask != 0; }
 };
 
 // kernel classes of the per-class timing (ProfScope, s2v_profile_*): 8 = the Ulysses packs / unpacks, 9 = the LoRA down-projections
@@ -207,6 +208,14 @@ struct s2v_ctx {
     uint64_t st_arm = 0;         // the layers of the NEXT forward; st_run: of the forward that is running (run_block reads it)
     uint64_t st_run = 0;
     int64_t st_bytes() const { return st_tab ? (int64_t)sizeof(AttnSteerRec) : 0; }
+    // local attention in time (include/s2v_hip.h): the record the local kernels read (kernels.h "local attention"), in device memory of its own, sized
+    // for the geometry's Ntok; la_Ntok: the Ntok it was made for
+    bool la_on = false;
+    int* la_tab = nullptr;
+    int la_Ntok = 0;
+    uint64_t la_arm = 0;         // the layers of the NEXT forward; la_run: of the forward that is running (run_block reads it)
+    uint64_t la_run = 0;
+    int64_t la_bytes() const { return la_tab ? (int64_t)(attn_local_ints(la_Ntok) * sizeof(int)) : 0; }
     // step cache (include/s2v_hip.h): sc_delta holds IN between the two extra launches of a CAPTURE forward and the residual after it
     int sc_on = 0;               // s2v_step_cache_enable: 0 off, 1 the cache, 2 the cache + sc_in (IN of every forward, for the read-out)
     int sc_arm = 0;              // S2V_STEP_*: the mode of the next forward
@@ -550,6 +559,7 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->e1x) hipFree(c->e1x);
     if (c->win_acc) hipFree(c->win_acc);
     if (c->st_tab) hipFree(c->st_tab);
+    if (c->la_tab) hipFree(c->la_tab);
     if (c->attn_queue) hipFree(c->attn_queue);
     if (c->vt_amax) hipFree(c->vt_amax);
     if (c->attn_stats) hipFree(c->attn_stats);
@@ -612,6 +622,39 @@ static int st_check(s2v_ctx* c, const char* fn) {
     if (c->B > 32) return fail("the sample masks hold 32 samples");
     if (c->cond_triples) return fail("the context is conditioned as subject-guidance triples (s2v_set_conditioning_triples): steering assumes CFG pairs");
     if (c->win_acc) return fail("temporal windows are set (s2v_set_windows): steering runs one forward per step");
+    return 0;
+}
+
+// local attention: off frees the table (the caller has synchronised the device and dropped the graphs)
+static void la_free(s2v_ctx* c) {
+    if (c->la_tab) hipFree(c->la_tab);
+    c->la_tab = nullptr; c->la_on = false; c->la_Ntok = 0; c->la_arm = 0;
+}
+// the record of (P, lo, hi) at the current geometry, checked by attn_local_make before the table is touched, then copied to it
+static int la_upload(s2v_ctx* c, const char* who, int P, const int* lo, const int* hi) {
+    std::vector<int> r;
+    S2V_TRY(attn_local_make(who, P, c->Ntok, lo, hi, &r));
+    S2V_CHECK_HIP(hipDeviceSynchronize());   // a step on any stream may still read the table; a captured step is kept: the table is data
+    S2V_CHECK_HIP(hipMemcpy(c->la_tab, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+// the table every row of which sees every key: what enable leaves in place
+static int la_upload_dense(s2v_ctx* c, const char* who) {
+    std::vector<int> lo((size_t)c->Ntok, 1), hi((size_t)c->Ntok, c->Ntok);
+    return la_upload(c, who, 1, lo.data(), hi.data());
+}
+// what local attention cannot run on, by name (enable, arm and the forward ask)
+static int la_check(s2v_ctx* c, const char* fn) {
+    static thread_local std::string m;
+    auto fail = [&](const char* why) { m = std::string(fn) + ": " + why; return s2v_fail(__FILE__, __LINE__, m.c_str(), -1); };
+    if (c->kind != S2V_CTX_MODEL) return fail("attention-only contexts (S2V_CTX_ATTN_*) run no forward; the s2v_attn_forward* seams run no local attention");
+    if (c->shard) return fail("a shard context (s2v_set_shard) has no local attention: its attention sees a head group of all ranks' rows; local attention runs on one GPU");
+    if (c->dtype == S2V_DTYPE_F16) return fail("an fp16 engine has no local attention kernel (bf16 runs attn_pp<LOCAL>, fp32 the generic form)");
+    if (c->cfg.weight_format != 0) return fail("fp8 weight formats have no local attention: their attention writes the MX output, the local kernel writes bf16 only");
+    if (c->attn_p16) return fail("attn_p_format 1 keeps V^T in fp16; the local kernel reads bf16 V^T (s2v_set_attn_p_format 0)");
+    if (!c->ws) return fail("call s2v_set_geometry first (the row table is checked against the current geometry)");
+    if (c->cond_triples) return fail("the context is conditioned as subject-guidance triples (s2v_set_conditioning_triples): local attention assumes CFG pairs");
+    if (c->win_acc) return fail("temporal windows are set (s2v_set_windows): local attention runs one forward per step");
     return 0;
 }
 
@@ -825,6 +868,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     sc_free(c);   // a shard context has no step cache
     am_free(c);   // ... and no attention map
     st_free(c);   // ... and no attention steering
+    la_free(c);   // ... and no local attention
     win_free(c);  // ... and no temporal windows
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
     drop_refs(c);
@@ -990,6 +1034,9 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
         c->st_arm = 0;
         const int r = st_upload(c, "s2v_set_geometry (attention steering)");
         if (r != 0) { st_free(c); return r; }
+    }
+    if (c->la_on && c->la_Ntok != c->Ntok) {        // ... the local-attention table is one row per token: another Ntok switches the feature off
+        la_free(c);
     }
     return 0;
 }
@@ -1383,7 +1430,9 @@ enum { QK_DONE = 0, QK_STANDALONE = 1, QK_IN_QUANT = 2 };
 
 // (q/k-norm,) V^T, (fp8 QK^T: q and k as MX e4m3,) attention.  w: the layer's norm weights, for QK_STANDALONE / QK_IN_QUANT
 // steer: the record of a steered layer (s2v_attn_steer_arm) -- the attention launch is then attn_pp<STEER> (bf16) or the steered generic kernel (fp32)
-static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w, hipStream_t st, const AttnSteerRec* steer = nullptr) {
+// local: the record of a local layer (s2v_attn_local_arm) -- the attention launch is then attn_pp<LOCAL> (bf16) or the local generic kernel (fp32)
+static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w, hipStream_t st, const AttnSteerRec* steer = nullptr,
+                     const int* local = nullptr) {
     const bool mx = attn_mx_out(c), matrix = c->mfma || c->h16;
     // fp16 P / V^T is the four-wave kernels' (attn_q4h / attn_q4fh); short sequences run attn_pp on bf16 V^T
     const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(o.Ntok, mx));
@@ -1423,6 +1472,11 @@ static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w,
         S2V_REQUIRE(!mx && !p16 && !c->fp8_qk && !c->h16, "attention: a steered layer on an engine the steered kernels do not serve");
         return c->mfma ? launch_attn_bf16_steer(a, steer, st) : launch_attn_simple_steer(a, steer, c->dtype, st);
     }
+    if (local) {
+        S2V_REQUIRE(!mx && !p16 && !c->fp8_qk && !c->h16, "attention: a local layer on an engine the local kernels do not serve");
+        S2V_REQUIRE(o.Ntok == c->la_Ntok, "attention: the local-attention table was made for another Ntok");
+        return c->mfma ? launch_attn_bf16_local(a, local, st) : launch_attn_simple_local(a, local, c->dtype, st);
+    }
     if (c->fp8_qk) return launch_attn_q4f(a, true, st);
     if (c->mfma) return launch_attn_bf16(a, st);
     if (c->h16) return launch_attn_f16(a, st);   // fp16 dtype: q, k, V^T, P in fp16 on v_mfma_f32_32x32x16_f16
@@ -1444,7 +1498,8 @@ static int am_launch(s2v_ctx* c, hipStream_t st) {
     return launch_attn_mass(a, c->dtype, (c->mfma || c->h16) ? 0 : 1, st);
 }
 
-static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false, bool mass = false, bool steer = false) {
+static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequant = false, bool lora = false, bool mass = false, bool steer = false,
+                         bool local = false) {
     const int D = c->D, pX = D + 3 * c->lr;
     // fp8 QK^T (weight_format 2 / 3 beyond its token threshold): q and k reach the attention kernel only as MX e4m3 images, so their LayerNorm + rotary
     // embedding ride in the pass that makes the images (qk_norm_quant_mx_k: the same bytes moved, the same bits produced) and the projection keeps the plain
@@ -1453,7 +1508,8 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
     S2V_TRY(qkv_proj(c, w, pX, lora, epi_ok && !norm_in_quant, prequant, st));
     const AttnOperands o{c->QKV, 3 * D, c->cfg.num_heads, c->Ntok, c->Xn, pX, (unsigned char*)c->aq, c->hs, c->Mpad};
     S2V_REQUIRE(!steer || c->st_tab, "attention: a steered layer without s2v_attn_steer_enable");
-    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st, steer ? c->st_tab : nullptr));
+    S2V_REQUIRE(!local || c->la_tab, "attention: a local layer without s2v_attn_local_enable");
+    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st, steer ? c->st_tab : nullptr, local ? c->la_tab : nullptr));
     return mass ? am_launch(c, st) : 0;
 }
 
@@ -1526,7 +1582,7 @@ static int run_block(s2v_ctx* c, int l, const char* mod_base /* [B][mod_stride] 
         S2V_TRY(block_norm(c, l, half, mod_base, mod_stride, st, &prequant));
         const GemmArgs g = block_gate(c, half, mod_base, mod_stride);
         if (half == 0) {
-            S2V_TRY(run_attention(c, c->layers[l], st, prequant, c->lora_on(), (c->am_run >> l) & 1, (c->st_run >> l) & 1));
+            S2V_TRY(run_attention(c, c->layers[l], st, prequant, c->lora_on(), (c->am_run >> l) & 1, (c->st_run >> l) & 1, (c->la_run >> l) & 1));
             S2V_TRY(out_proj(c, c->layers[l], c->lora_on(), g, EPI_BIAS_GATE_RES, true, st));
         } else {
             S2V_TRY(block_ff(c, l, g, prequant, st));
@@ -1616,6 +1672,12 @@ static uint64_t st_take_arm(s2v_ctx* c) {
     c->st_arm = 0;
     return m;
 }
+// the local layer mask armed for the forward that is about to run (s2v_attn_local_arm): one-shot as well
+static uint64_t la_take_arm(s2v_ctx* c) {
+    const uint64_t m = c->la_on ? c->la_arm : 0;
+    c->la_arm = 0;
+    return m;
+}
 static int am_done(s2v_ctx* c, uint64_t am, int r) {
     if (r == 0) c->am_count += __builtin_popcountll(am);
     return r;
@@ -1624,7 +1686,7 @@ static int am_done(s2v_ctx* c, uint64_t am, int r) {
 // mode: S2V_STEP_* (include/s2v_hip.h); FULL is the forward as it is without a step cache
 // am: the layers whose attention the mass kernel follows (s2v_attn_map_arm; 0: the launches of a forward without the feature)
 static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, int n_lat, const float* t_dev, void* out,
-                        hipStream_t st, int mode = S2V_STEP_FULL, uint64_t am = 0, uint64_t sm = 0) {
+                        hipStream_t st, int mode = S2V_STEP_FULL, uint64_t am = 0, uint64_t sm = 0, uint64_t lm = 0) {
     S2V_REQUIRE(c->ws && c->finalized && c->have_cond, "transformer_forward: geometry, weights and conditioning required");
     S2V_REQUIRE(!c->cfg.use_rope || c->have_rope, "transformer_forward: RoPE tables missing (s2v_set_rope)");
     S2V_REQUIRE(c->cfg.use_rope || c->have_pos, "transformer_forward: sincos table missing (s2v_set_pos_embed)");
@@ -1636,6 +1698,14 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, in
     S2V_REQUIRE(!reuse || c->sc_valid, "transformer_forward: S2V_STEP_REUSE without a captured residual");
     S2V_REQUIRE(!am || !reuse, "transformer_forward: an attention map is armed (s2v_attn_map_arm) together with S2V_STEP_REUSE: the block stack does not run");
     S2V_REQUIRE(!am || (c->am_on && !c->fp8_qk), "transformer_forward: an attention map is armed without s2v_attn_map_enable, or while fp8 QK^T is active");
+    if (lm) {   // lm: the layers whose attention launch is the local kernel (s2v_attn_local_arm; 0: the launches of a forward without the feature)
+        S2V_REQUIRE(!reuse, "transformer_forward: local attention is armed (s2v_attn_local_arm) together with S2V_STEP_REUSE: the block stack does not run");
+        S2V_REQUIRE(!am, "transformer_forward: local attention is armed (s2v_attn_local_arm) together with an attention map (s2v_attn_map_arm): the map reads "
+                         "the un-windowed softmax");
+        S2V_REQUIRE(!sm, "transformer_forward: local attention is armed (s2v_attn_local_arm) together with attention steering (s2v_attn_steer_arm)");
+        S2V_REQUIRE(c->la_on && c->la_tab && c->la_Ntok == c->Ntok, "transformer_forward: local attention is armed without s2v_attn_local_enable");
+        S2V_TRY(la_check(c, "transformer_forward (local attention armed)"));
+    }
     if (sm) {   // sm: the layers whose attention launch is the steered kernel (s2v_attn_steer_arm; 0: the launches of a forward without the feature)
         S2V_REQUIRE(!reuse, "transformer_forward: attention steering is armed (s2v_attn_steer_arm) together with S2V_STEP_REUSE: the block stack does not run");
         S2V_REQUIRE(!am, "transformer_forward: attention steering is armed (s2v_attn_steer_arm) together with an attention map (s2v_attn_map_arm): the map reads "
@@ -1650,12 +1720,12 @@ static int forward_impl(s2v_ctx* c, const void* latents, int64_t lat_bstride, in
         S2V_TRY(sc_launch(c, SC_ADD, c->sc_delta, nullptr, st));                               // X_video = rnd(IN' + delta)
     } else {
         // 3. blocks
-        c->am_run = am; c->st_run = sm;
+        c->am_run = am; c->st_run = sm; c->la_run = lm;
         for (int l = 0; l < c->L; ++l) {
             const int r = run_block(c, l, c->mod + (int64_t)(2 * l) * c->mc * D * E, c->mod_rows, st);
-            if (r != 0) { c->am_run = 0; c->st_run = 0; return r; }
+            if (r != 0) { c->am_run = 0; c->st_run = 0; c->la_run = 0; return r; }
         }
-        c->am_run = 0; c->st_run = 0;
+        c->am_run = 0; c->st_run = 0; c->la_run = 0;
         if (mode == S2V_STEP_CAPTURE) S2V_TRY(sc_launch(c, SC_SUB, c->sc_delta, nullptr, st)); // delta = rnd(OUT - IN)
     }
     // 4. tail
@@ -1669,17 +1739,17 @@ extern "C" int s2v_transformer_forward(s2v_ctx* c, const void* latents, int64_t 
                                        void* out, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward: null argument");
     const int mode = sc_take_arm(c);
-    const uint64_t am = am_take_arm(c), sm = st_take_arm(c);
-    return am_done(c, am, sc_done(c, mode, forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream, mode, am, sm)));
+    const uint64_t am = am_take_arm(c), sm = st_take_arm(c), lm = la_take_arm(c);
+    return am_done(c, am, sc_done(c, mode, forward_impl(c, latents, lat_bstride, 0, timesteps_dev, out, (hipStream_t)stream, mode, am, sm, lm)));
 }
 
 extern "C" int s2v_transformer_forward_videos(s2v_ctx* c, const void* latents, int32_t n_lat, const float* timesteps_dev, void* out,
                                               s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps_dev && out, "s2v_transformer_forward_videos: null argument");
     const int mode = sc_take_arm(c);
-    const uint64_t am = am_take_arm(c), sm = st_take_arm(c);
+    const uint64_t am = am_take_arm(c), sm = st_take_arm(c), lm = la_take_arm(c);
     S2V_REQUIRE(c->ws && n_lat >= 1 && c->B % n_lat == 0, "s2v_transformer_forward_videos: n_lat must divide the geometry's batch (sample j embeds latent j mod n_lat)");
-    return am_done(c, am, sc_done(c, mode, forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream, mode, am, sm)));
+    return am_done(c, am, sc_done(c, mode, forward_impl(c, latents, (int64_t)c->F * c->cfg.in_channels * c->H * c->W, n_lat, timesteps_dev, out, (hipStream_t)stream, mode, am, sm, lm)));
 }
 
 // the residual streams of every sample between the caller's dense tensors (s0: n0 rows, s1: n1 rows, video: V rows per sample; n0 + n1 = T + R)
@@ -1706,6 +1776,7 @@ extern "C" int s2v_block_forward(s2v_ctx* c, int32_t layer, const void* hidden, 
     S2V_REQUIRE(c && c->ws && c->finalized, "s2v_block_forward: geometry and weights required");
     S2V_REQUIRE(!c->shard, "s2v_block_forward: a shard context (s2v_set_shard) runs the staged step only");
     S2V_REQUIRE(st_take_arm(c) == 0, "s2v_block_forward: attention steering is armed (s2v_attn_steer_arm): the block and AttnProcessor seams run no steered attention");
+    S2V_REQUIRE(la_take_arm(c) == 0, "s2v_block_forward: local attention is armed (s2v_attn_local_arm): the block and AttnProcessor seams run no local attention");
     S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_block_forward: bad layer");
     S2V_REQUIRE(hidden && enc1 && temb && out_hidden && out_enc1, "s2v_block_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -1737,6 +1808,7 @@ extern "C" int s2v_attn_forward(s2v_ctx* c, int32_t layer, const void* hidden, c
     S2V_REQUIRE(c && c->ws && c->finalized, "s2v_attn_forward: geometry and weights required");
     S2V_REQUIRE(!c->shard, "s2v_attn_forward: a shard context (s2v_set_shard) runs the staged step only");
     S2V_REQUIRE(st_take_arm(c) == 0, "s2v_attn_forward: attention steering is armed (s2v_attn_steer_arm): the AttnProcessor seams run no steered attention");
+    S2V_REQUIRE(la_take_arm(c) == 0, "s2v_attn_forward: local attention is armed (s2v_attn_local_arm): the AttnProcessor seams run no local attention");
     S2V_REQUIRE(layer >= 0 && layer < c->L, "s2v_attn_forward: bad layer");
     S2V_REQUIRE(hidden && encoder && out_hidden && out_encoder, "s2v_attn_forward: null argument");
     return attn_forward_impl(c, c->layers[layer], c->lora_on(), hidden, encoder, out_hidden, out_encoder, (hipStream_t)stream);
@@ -1748,6 +1820,7 @@ extern "C" int s2v_attn_forward_with(s2v_ctx* c, const s2v_ctx* wc, int32_t laye
     S2V_REQUIRE(c->ws, "s2v_attn_forward_with: the workspace context has no geometry (s2v_set_geometry)");
     S2V_REQUIRE(!c->shard && !wc->shard, "s2v_attn_forward_with: a shard context (s2v_set_shard) runs the staged step only");
     S2V_REQUIRE(st_take_arm(c) == 0, "s2v_attn_forward_with: attention steering is armed (s2v_attn_steer_arm): the AttnProcessor seams run no steered attention");
+    S2V_REQUIRE(la_take_arm(c) == 0, "s2v_attn_forward_with: local attention is armed (s2v_attn_local_arm): the AttnProcessor seams run no local attention");
     S2V_REQUIRE(wc->finalized && wc->kind != S2V_CTX_ATTN_WORKSPACE, "s2v_attn_forward_with: the weights are not loaded (s2v_finalize_weights)");
     S2V_REQUIRE(wc->dtype == c->dtype, "s2v_attn_forward_with: the weights context has another dtype");
     S2V_REQUIRE(wc->cfg.num_heads == c->cfg.num_heads && wc->D == c->D, "s2v_attn_forward_with: the weights context has another num_heads / inner dim");
@@ -1905,7 +1978,7 @@ extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, floa
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
     S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
     *arena = c->arena ? c->arena_bytes : 0;
-    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes + c->win_bytes + c->st_bytes() : 0;
+    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes + c->win_bytes + c->st_bytes() + c->la_bytes() : 0;
     return 0;
 }
 
@@ -2042,10 +2115,10 @@ static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* 
     return launch_sched_step(a, c->dtype, st);
 }
 
-static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am, uint64_t sm) {
+static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am, uint64_t sm, uint64_t lm) {
     // b videos: sample j of [negative x b | positive x b] embeds video j mod b straight from `latents` (one video: the stride of 0 it always had)
     const int b = c->B >= 2 ? c->B / 2 : 1;
-    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am, sm));
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am, sm, lm));
     return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b);
 }
 
@@ -2053,7 +2126,7 @@ static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* 
 static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, float* x0_hist, const void* noise,
                              int32_t use_graph, hipStream_t st) {
     const int mode = sc_take_arm(c);
-    const uint64_t am = am_take_arm(c), sm = st_take_arm(c);
+    const uint64_t am = am_take_arm(c), sm = st_take_arm(c), lm = la_take_arm(c);
     S2V_REQUIRE(c->ws && (c->B == 1 || c->B % 2 == 0), "s2v_denoise_step: geometry with B = 1 or an even B = 2b (the CFG pairs of b videos) required");
     S2V_REQUIRE(!c->cond_triples, "s2v_denoise_step: the context is conditioned as subject-guidance triples [u x b | r x b | f x b] (s2v_set_conditioning_triples): "
                                   "its step is s2v_denoise_step_guided");
@@ -2066,10 +2139,10 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
                                        "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
                                      : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
     S2V_TRY(stage_step(c, timesteps, coefs, b, st));
-    if (!use_graph) return am_done(c, am, sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode, am, sm)));
+    if (!use_graph) return am_done(c, am, sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode, am, sm, lm)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.mode = mode; key.amask = am; key.smask = sm;
-    return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode, am, sm); })));
+    key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm;
+    return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode, am, sm, lm); })));
 }
 
 extern "C" int s2v_denoise_step(s2v_ctx* c, void* latents, float timestep, const s2v_sched_coef* coef_host,
@@ -2098,9 +2171,9 @@ extern "C" int s2v_set_blend(s2v_ctx* c, const void* z0, const void* noise0, con
     return 0;
 }
 
-static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am, uint64_t sm) {
+static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am, uint64_t sm, uint64_t lm) {
     const int b = c->B / 2;
-    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am, sm));
+    S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am, sm, lm));
     SchedMaskArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
     a.nvid = b; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
@@ -2114,7 +2187,7 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
                                        float* x0_hist, const void* noise, int32_t use_graph, s2v_stream stream) {
     S2V_REQUIRE(c && latents && timesteps && coefs && blends, "s2v_denoise_step_masked: null argument");
     const int mode = sc_take_arm(c);
-    const uint64_t am = am_take_arm(c), sm = st_take_arm(c);
+    const uint64_t am = am_take_arm(c), sm = st_take_arm(c), lm = la_take_arm(c);
     S2V_REQUIRE(!c->shard, "s2v_denoise_step_masked: a shard context (s2v_set_shard) has no masked step: masked video-to-video runs on one GPU");
     S2V_REQUIRE(c->ws && c->B != 1, "s2v_denoise_step_masked: a geometry with B = 1 is one sample of a CFG-parallel pair, and the split entries "
                                     "(s2v_denoise_split_begin / _end, s2v_denoise_step_cfg_parallel) have no masked form: masked video-to-video runs the "
@@ -2131,10 +2204,10 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     for (int k = 0; k < b; ++k) S2V_REQUIRE(blends[k].keep_max >= 0 && blends[k].keep_max <= 255, "s2v_denoise_step_masked: keep_max must be a level 0..255");
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
-    if (!use_graph) return am_done(c, am, sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode, am, sm)));
+    if (!use_graph) return am_done(c, am, sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode, am, sm, lm)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am; key.smask = sm;
-    return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode, am, sm); })));
+    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm;
+    return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode, am, sm, lm); })));
 }
 
 // ---- subject guidance: the step of b triples [u x b | r x b | f x b] -----------------------------------------------------------------------------
@@ -2158,8 +2231,9 @@ extern "C" int s2v_denoise_step_guided(s2v_ctx* c, void* latents, const float* t
     S2V_REQUIRE(c && latents && timesteps && coefs, "s2v_denoise_step_guided: null argument");
     // the arms are one-shot and taken by every step entry, refused or not
     const int mode = sc_take_arm(c);
-    const uint64_t am = am_take_arm(c), sm = st_take_arm(c);
+    const uint64_t am = am_take_arm(c), sm = st_take_arm(c), lm = la_take_arm(c);
     S2V_REQUIRE(sm == 0, "s2v_denoise_step_guided: attention steering is armed (s2v_attn_steer_arm), and steering assumes CFG pairs");
+    S2V_REQUIRE(lm == 0, "s2v_denoise_step_guided: local attention is armed (s2v_attn_local_arm), and local attention assumes CFG pairs");
     S2V_REQUIRE(!c->shard, "s2v_denoise_step_guided: a shard context (s2v_set_shard) has no triple step: subject guidance runs on one GPU");
     // a pending split lives on a B = 1 geometry, so it is named before the geometry is
     S2V_REQUIRE(c->split_kind < 0, "s2v_denoise_step_guided: a CFG-parallel split is pending (s2v_denoise_split_begin): the split entries run CFG pairs, "
@@ -2265,6 +2339,8 @@ extern "C" int s2v_denoise_step_windows(s2v_ctx* c, void* latents, float timeste
     const uint64_t am = am_take_arm(c);
     S2V_REQUIRE(st_take_arm(c) == 0, "s2v_denoise_step_windows: attention steering is armed (s2v_attn_steer_arm): steering runs one forward per step, a windowed "
                                      "step runs several");
+    S2V_REQUIRE(la_take_arm(c) == 0, "s2v_denoise_step_windows: local attention is armed (s2v_attn_local_arm): local attention runs one forward per step, a "
+                                     "windowed step runs several");
     S2V_REQUIRE(c->win_acc, "s2v_denoise_step_windows: no temporal windows are set (s2v_set_windows): a plain geometry steps with s2v_denoise_step");
     S2V_REQUIRE(c->have_cond && !c->cond_triples, "s2v_denoise_step_windows: the conditioning must hold the CFG pairs [negative x per_forward | positive x per_forward] "
                                                   "(s2v_set_conditioning)");
@@ -2310,6 +2386,8 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
                                      "per rank: the attention map runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(st_take_arm(c) == 0, "s2v_denoise_split_begin: attention steering is armed (s2v_attn_steer_arm), and a CFG-parallel split holds one sample of the "
                                      "pair per rank: steering runs on one GPU (s2v_denoise_step)");
+    S2V_REQUIRE(la_take_arm(c) == 0, "s2v_denoise_split_begin: local attention is armed (s2v_attn_local_arm), and a CFG-parallel split holds one sample of the "
+                                     "pair per rank: local attention runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required; a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");
@@ -2652,6 +2730,7 @@ extern "C" int s2v_attn_map_arm(s2v_ctx* c, uint64_t layer_mask) {
                                 "runs with 16-bit attention (the plain \"fp8\" weight format included)");
         S2V_REQUIRE(c->L >= 64 || (layer_mask >> c->L) == 0, "s2v_attn_map_arm: a layer bit at or beyond num_layers is set");
         S2V_REQUIRE(c->st_arm == 0, "s2v_attn_map_arm: attention steering is armed for the next forward (s2v_attn_steer_arm): the map reads the un-steered softmax");
+        S2V_REQUIRE(c->la_arm == 0, "s2v_attn_map_arm: local attention is armed for the next forward (s2v_attn_local_arm): the map reads the un-windowed softmax");
         S2V_REQUIRE(c->sc_arm != S2V_STEP_REUSE, "s2v_attn_map_arm: S2V_STEP_REUSE is armed for the next forward (s2v_step_cache_arm): the block stack does not run, "
                                                  "there is no attention to follow");
     }
@@ -2700,6 +2779,7 @@ extern "C" int s2v_attn_steer_arm(s2v_ctx* c, uint64_t layer_mask) {
         S2V_TRY(st_check(c, "s2v_attn_steer_arm"));
         S2V_REQUIRE(c->L >= 64 || (layer_mask >> c->L) == 0, "s2v_attn_steer_arm: a layer bit at or beyond num_layers is set");
         S2V_REQUIRE(c->am_arm == 0, "s2v_attn_steer_arm: an attention map is armed for the next forward (s2v_attn_map_arm): the map reads the un-steered softmax");
+        S2V_REQUIRE(c->la_arm == 0, "s2v_attn_steer_arm: local attention is armed for the next forward (s2v_attn_local_arm): a layer runs one attention kernel");
         S2V_REQUIRE(c->sc_arm != S2V_STEP_REUSE, "s2v_attn_steer_arm: S2V_STEP_REUSE is armed for the next forward (s2v_step_cache_arm): the block stack does not run, "
                                                  "there is no attention to steer");
     }
@@ -2744,6 +2824,91 @@ extern "C" int s2v_op_attention_steer(const void* qkv, void* vt_scratch, void* o
     }
     a.valu_only = 1;
     return launch_attn_simple_steer(a, op_tab, dtype, st);
+}
+
+// ---- local attention in time (include/s2v_hip.h) --------------------------------------------------------------------------------------------
+extern "C" int s2v_attn_local_enable(s2v_ctx* c, int32_t on) {
+    S2V_REQUIRE(c, "s2v_attn_local_enable: null context");
+    if (!on) {
+        if (c->la_on) { S2V_CHECK_HIP(hipDeviceSynchronize()); drop_graph(c); }
+        la_free(c);
+        return 0;
+    }
+    S2V_TRY(la_check(c, "s2v_attn_local_enable"));
+    if (c->la_on) return 0;
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    drop_graph(c);
+    S2V_CHECK_HIP(hipMalloc((void**)&c->la_tab, attn_local_ints(c->Ntok) * sizeof(int)));
+    c->la_on = true; c->la_Ntok = c->Ntok; c->la_arm = 0;
+    const int r = la_upload_dense(c, "s2v_attn_local_enable");   // a table that windows nothing
+    if (r != 0) la_free(c);
+    return r;
+}
+
+extern "C" int s2v_attn_local_set(s2v_ctx* c, int32_t P, const int32_t* rows_lo, const int32_t* rows_hi) {
+    S2V_REQUIRE(c, "s2v_attn_local_set: null context");
+    S2V_REQUIRE(c->la_on && c->la_tab && c->la_Ntok == c->Ntok, "s2v_attn_local_set: local attention is not enabled (s2v_attn_local_enable)");
+    S2V_REQUIRE(rows_lo && rows_hi, "s2v_attn_local_set: null row table");
+    return la_upload(c, "s2v_attn_local_set", P, rows_lo, rows_hi);   // checked before anything is replaced; a captured step is kept: the table is data
+}
+
+extern "C" int s2v_attn_local_arm(s2v_ctx* c, uint64_t layer_mask) {
+    S2V_REQUIRE(c, "s2v_attn_local_arm: null context");
+    if (layer_mask) {
+        S2V_REQUIRE(c->la_on && c->la_tab, "s2v_attn_local_arm: local attention is not enabled (s2v_attn_local_enable)");
+        S2V_TRY(la_check(c, "s2v_attn_local_arm"));
+        S2V_REQUIRE(c->L >= 64 || (layer_mask >> c->L) == 0, "s2v_attn_local_arm: a layer bit at or beyond num_layers is set");
+        S2V_REQUIRE(c->am_arm == 0, "s2v_attn_local_arm: an attention map is armed for the next forward (s2v_attn_map_arm): the map reads the un-windowed softmax");
+        S2V_REQUIRE(c->st_arm == 0, "s2v_attn_local_arm: attention steering is armed for the next forward (s2v_attn_steer_arm): a layer runs one attention kernel");
+        S2V_REQUIRE(c->sc_arm != S2V_STEP_REUSE, "s2v_attn_local_arm: S2V_STEP_REUSE is armed for the next forward (s2v_step_cache_arm): the block stack does not run, "
+                                                 "there is no attention to window");
+    }
+    c->la_arm = layer_mask;
+    return 0;
+}
+
+extern "C" int s2v_op_attention_local(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                      int32_t P, const int32_t* rows_lo, const int32_t* rows_hi, s2v_stream stream) {
+    S2V_REQUIRE(qkv && out, "s2v_op_attention_local: null argument");
+    S2V_REQUIRE(B >= 1 && H >= 1 && Ntok >= 1, "s2v_op_attention_local: B >= 1, H >= 1, Ntok >= 1");
+    S2V_REQUIRE(impl == 0 || impl == 1, "s2v_op_attention_local: impl 0 (MFMA, bf16) or 1 (generic)");
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_attention_local: unsupported dtype");
+    S2V_REQUIRE(impl == 1 || (dtype == S2V_DTYPE_BF16 && vt_scratch), "s2v_op_attention_local: impl 0 is bf16 and needs vt_scratch");
+    std::vector<int> r;
+    S2V_TRY(attn_local_make("s2v_op_attention_local", P, Ntok, rows_lo, rows_hi, &r));
+    // operator level: one table per process, on the device of the first call, grown when a longer sequence comes.  The entry synchronises the stream
+    // before it replaces the table and uploads it with a blocking copy: a test and benchmark entry, not thread-safe; contexts hold their own table
+    static int* op_tab = nullptr;
+    static size_t op_ints = 0;
+    hipStream_t st = (hipStream_t)stream;
+    S2V_CHECK_HIP(hipStreamSynchronize(st));
+    if (r.size() > op_ints) {
+        if (op_tab) { S2V_CHECK_HIP(hipFree(op_tab)); op_tab = nullptr; op_ints = 0; }
+        S2V_CHECK_HIP(hipMalloc((void**)&op_tab, r.size() * sizeof(int)));
+        op_ints = r.size();
+    }
+    S2V_CHECK_HIP(hipMemcpy(op_tab, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
+    const int D = H * 64;
+    AttnArgs a{};
+    a.qkv = qkv; a.ld_qkv = 3 * D; a.out = out; a.ld_out = D; a.B = B; a.H = H; a.Ntok = Ntok; a.scale = 0.125f;
+    a.ntok_pad = (int)rup(Ntok, 64);
+    if (impl == 0) {
+        // the nine counters of the persistent form (zero between launches), so that this entry runs what a context runs at the same size
+        static int* op_queue = nullptr;
+        static int op_ncu = 0;
+        if (!op_queue) {
+            int dev = 0;
+            S2V_CHECK_HIP(hipGetDevice(&dev));
+            S2V_CHECK_HIP(hipDeviceGetAttribute(&op_ncu, hipDeviceAttributeMultiprocessorCount, dev));
+            S2V_CHECK_HIP(hipMalloc((void**)&op_queue, 64));
+            S2V_CHECK_HIP(hipMemset(op_queue, 0, 64));
+        }
+        a.vt = vt_scratch; a.queue = op_queue; a.num_cus = op_ncu;
+        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, nullptr));
+        return launch_attn_bf16_local(a, op_tab, st);
+    }
+    a.valu_only = 1;
+    return launch_attn_simple_local(a, op_tab, dtype, st);
 }
 
 extern "C" int s2v_attn_map_reset(s2v_ctx* c) {
@@ -2813,6 +2978,8 @@ extern "C" int s2v_step_cache_arm(s2v_ctx* c, int32_t mode) {
         S2V_REQUIRE(mode != S2V_STEP_REUSE || c->sc_valid, "s2v_step_cache_arm: no captured residual for this geometry / conditioning / weights");
         S2V_REQUIRE(mode != S2V_STEP_REUSE || !c->st_arm, "s2v_step_cache_arm: S2V_STEP_REUSE while attention steering is armed for the next forward (s2v_attn_steer_arm): "
                                                           "the block stack does not run, there is no attention to steer");
+        S2V_REQUIRE(mode != S2V_STEP_REUSE || !c->la_arm, "s2v_step_cache_arm: S2V_STEP_REUSE while local attention is armed for the next forward (s2v_attn_local_arm): "
+                                                          "the block stack does not run, there is no attention to window");
         S2V_REQUIRE(mode != S2V_STEP_REUSE || !c->am_arm, "s2v_step_cache_arm: S2V_STEP_REUSE while an attention map is armed for the next forward (s2v_attn_map_arm): "
                                                           "the block stack does not run, there is no attention to follow");
     }

@@ -18,6 +18,10 @@
 //  attn_pp_steer_k / attn_pp_steer_persist_k : attn_pp_item<ACCT, STEER = true> in the same two launch forms -- attention steering, a logit bias
 //     log2 w on up to four key ranges (kernels.h AttnSteerRec; include/s2v_hip.h "Attention steering"); what a steered layer of a bf16 engine
 //     runs at every length.  attn_simple_steer_k<T>: the same bias in the generic kernel (fp32 engines, and the cross-check).
+//  attn_pp_local_k / attn_pp_local_persist_k : attn_pp_item<ACCT, STEER, LOCAL = true> in the same two launch forms -- local attention in time:
+//     row i sees the keys [0, P) and [lo_i, hi_i); an item visits only the key tiles some row of it sees (kernels.h "local attention";
+//     include/s2v_hip.h "Local attention"); what a local layer of a bf16 engine runs at every length.  attn_simple_local_k<T>: the same mask
+//     in the generic kernel (fp32 engines, and the cross-check).
 //  attn_bf16_k (S2V_DIAG builds only): the round-1 lock-step kernel with a per-tile row maximum, kept as the A/B reference.
 //  attn_simple_k<T> : one wave per query row, fp32 math, any dtype (CPU-reference-parity mode / cross-check).
 #define S2V_HOST
@@ -288,8 +292,16 @@ extern "C" __attribute__((visibility("default"))) int s2v_attn_debug_read(long l
 // takes the un-steered path on every tile: those rows equal the un-steered launch bit for bit.  So do the rows outside [q0, q1) of a wave
 // that has rows inside, UNLESS a steered lane of that wave votes the wave into a slow path past tile 0 that the un-steered launch does not take
 // (or the reverse): the slow path re-sums the tile's p in another order, within rounding of the fast sum.  STEER = false: nothing below changes.
-template <bool ACCT, bool STEER = false>
-__device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg, char* smem, const AttnSteerRec* __restrict__ sr = nullptr) {
+// LOCAL (local attention in time, kernels.h "local attention"): row i sees the keys [0, P) and [lo_i, hi_i).  The item visits the prefix tiles
+// [0, np) and the tiles [w0, w1) of the envelope of its 256 rows (merged by the host where they touch): loop iteration j is tile
+// j < np ? j : j + (w0 - np).  Everything that is a position in the pipeline goes by the ITERATION -- the ring slot, the DMA clamp, the
+// fragment prefetch of t + 1 / t + 2, the t == 0 tests, the loop bound; everything that is a position in the sequence goes by the TILE --
+// kv0, the global addresses, the tail mask.  Per wave and tile, in scalar code: a tile every key of which every row of the wave sees runs
+// the untouched code; any other visited tile sets the scores of the keys a lane's own row does not see to -inf, before everything the softmax
+// segment does.  P >= 1 makes key 0 visible to every row, so iteration 0 (always tile 0) holds a finite score for every lane.
+template <bool ACCT, bool STEER = false, bool LOCAL = false>
+__device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg, char* smem, const AttnSteerRec* __restrict__ sr = nullptr,
+                                             const int* __restrict__ lr = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;
@@ -302,7 +314,23 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
     const bf16_t* qkv = (const bf16_t*)a.qkv + (size_t)b * a.Ntok * a.ld_qkv;
     const char* Kg = (const char*)(qkv + D + h * 64);
     const char* VTg = (const char*)((const bf16_t*)a.vt + (size_t)(b * a.H + h) * 64 * a.ntok_pad);
-    const int nt = (a.Ntok + KV_TILE - 1) / KV_TILE;
+    int nt = (a.Ntok + KV_TILE - 1) / KV_TILE;   // LOCAL: the number of loop iterations (visited tiles) of this item
+    int l_np = 0, l_gap = 0, l_P = 0, l_lomax = 0, l_himin = 0, lo_lane = 0, hi_lane = 0;
+    if constexpr (LOCAL) {
+        const int qbu = __builtin_amdgcn_readfirstlane(qb);
+        const int nq = lr[2];
+        const int* it = lr + ATTN_LOCAL_HDR + 4 * qbu;                       // (np, w0, w1, -)
+        const int* wv = lr + ATTN_LOCAL_HDR + 4 * nq + 2 * (qbu * 8 + wave); // (lo_max, hi_min) of the wave's 32 rows
+        const int* rw = lr + ATTN_LOCAL_HDR + 20 * nq + qbu * 256 + wave * 32 + fr;
+        l_P = lr[0];
+        l_np = it[0]; l_gap = it[1] - it[0]; nt = it[0] + (it[2] - it[1]);
+        l_lomax = wv[0]; l_himin = wv[1];
+        lo_lane = rw[0]; hi_lane = rw[256 * nq];   // the lane's own row's window (rows past Ntok are stored dense)
+    }
+    auto tix = [&](int j) -> int {  // iteration -> tile
+        if constexpr (LOCAL) return j < l_np ? j : j + l_gap;
+        else return j;
+    };
 
     // staging: this wave's piece = rows wave*8 .. +7 of a tile, lane = (row, 16-B chunk), chunk XOR on the SOURCE address;
     // global address = wave-uniform tile base (SGPR pair) + per-lane 32-bit offset
@@ -312,11 +340,11 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
     const unsigned offV = (unsigned)(2 * (srow * a.ntok_pad + sc * 8));
     const size_t k_tile_stride = (size_t)KV_TILE * a.ld_qkv * 2;
     auto dma_k = [&](int t) {  // tiles past the end are clamped (re-staged into a dead slot) so that every wave issues the same count
-        const int tc = min(t, nt - 1);
+        const int tc = tix(min(t, nt - 1));
         glds16_saddr(Kg + (size_t)tc * k_tile_stride, offK, smem + (t & 3) * 16384 + wave * 1024);
     };
     auto dma_v = [&](int t) {
-        const int tc = min(t, nt - 1);
+        const int tc = tix(min(t, nt - 1));
         glds16_saddr(VTg + (size_t)tc * (KV_TILE * 2), offV, smem + (t & 3) * 16384 + 8192 + wave * 1024);
     };
     dma_k(0); dma_v(0); dma_k(1); dma_v(1); dma_k(2); dma_k(3);
@@ -398,7 +426,7 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
     for (int t = 0; t < nt; ++t) {
         // ---- softmax segment S(t)
         const long long u0 = now();
-        const int kv0 = t * KV_TILE;
+        const int kv0 = tix(t) * KV_TILE;
         if constexpr (STEER) {
             if (kv0 < s_hi && kv0 + KV_TILE > s_lo) {
 #pragma nounroll
@@ -422,6 +450,22 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
                                 if ((unsigned)(kvb + kb * 32 + (e & 3) + 8 * (e >> 2)) < len) st[kb][e] += bl;
                     }
                 }
+            }
+        }
+        if constexpr (LOCAL) {
+            // whole: every key of the tile below Ntok is seen by every row of the wave -- inside the prefix, or inside [lo_max, hi_min) (reaching
+            // down through the prefix when lo_max == P: every row's window then starts where the prefix ends)
+            const int kend = min(kv0 + KV_TILE, a.Ntok);
+            const bool whole = kend <= l_P || (kend <= l_himin && (kv0 >= l_lomax || l_lomax <= l_P));
+            if (!whole) {
+                const unsigned len = (unsigned)(hi_lane - lo_lane);
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int kv = kv0 + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hi;
+                        if (!(kv < l_P || (unsigned)(kv - lo_lane) < len)) st[kb][e] = -INFINITY;
+                    }
             }
         }
         if (kv0 + KV_TILE > a.Ntok) {  // tail tile: mask keys >= Ntok
@@ -580,13 +624,20 @@ __global__ __launch_bounds__(512, 2) void attn_pp_steer_k(const AttnArgs a, int 
     attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
     attn_pp_item<false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, sr);
 }
+// the LOCAL = true instantiation of the same launch form: the record (kernels.h "local attention") comes as one more pointer argument
+__global__ __launch_bounds__(512, 2) void attn_pp_local_k(const AttnArgs a, int nqb, const int* __restrict__ lr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int first, cnt;
+    attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
+    attn_pp_item<false, false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, nullptr, lr);
+}
 // PERSISTENT form (the engine's launches): one workgroup per CU pulls items from its XCD's queue and, when that is empty, from the
 // other XCDs' queues.  The hardware hands every XCD exactly 1/8 of a grid, but the XCDs of one launch run a few percent apart in
 // clock: with static shares the launch ended 95-100 % apart per XCD plus a last round of 32 items on 256 slots (4.6 % of the
 // slot-time idle, tools/attn_harness timeline); pulled work ends within one item.  queue[0..7]: next item of XCD x, queue[8]:
 // workgroups done -- the last one to leave zeroes the nine counters for the next launch (they must be zero at the first).
-// TWIN: attn_pp_steer_persist_k below repeats this loop word for word (a shared function changed this kernel's schedule): a change to the
-// queue protocol here is made there as well.
+// TWIN: attn_pp_steer_persist_k and attn_pp_local_persist_k below repeat this loop word for word (a shared function changed this kernel's
+// schedule): a change to the queue protocol here is made there as well.
 template <bool ACCT>
 __global__ __launch_bounds__(512, 2) void attn_pp_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -642,6 +693,39 @@ __global__ __launch_bounds__(512, 2) void attn_pp_steer_persist_k(const AttnArgs
         __syncthreads();
         if (wg < 0) break;
         attn_pp_item<false, true>(a, nqb, wg, smem, sr);
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&queue[8], 1) == (int)gridDim.x - 1) {
+            for (int i = 0; i < 9; ++i) __hip_atomic_store(&queue[i], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __threadfence();
+        }
+    }
+}
+// the LOCAL = true instantiation of the persistent form: the same loop once more (a twin, as above); its items are of unequal length, which the
+// pulled queue evens out
+__global__ __launch_bounds__(512, 2) void attn_pp_local_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue, const int* __restrict__ lr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_item;
+    const int xcd = blockIdx.x & 7;
+    for (;;) {
+        if (threadIdx.x == 0) {
+            int wg = -1;
+            for (int k = 0; k < 8 && wg < 0; ++k) {
+                const int y = (xcd + k) & 7;
+                int first, cnt;
+                attn_xcd_range(total, y, first, cnt);
+                if (__hip_atomic_load(&queue[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= cnt) continue;  // drained: do not hammer it
+                const int i = atomicAdd(&queue[y], 1);
+                if (i < cnt) wg = first + i;
+            }
+            s_item = wg;
+        }
+        __syncthreads();  // also fences the previous item's LDS traffic from the next item's prologue
+        const int wg = s_item;
+        __syncthreads();
+        if (wg < 0) break;
+        attn_pp_item<false, false, true>(a, nqb, wg, smem, nullptr, lr);
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -744,6 +828,74 @@ int launch_attn_bf16_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, hipSt
     } else {
         void* args[] = {(void*)&av, (void*)&nqb8, (void*)&rec_dev};
         S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(total), dim3(512), args, 65536, st));
+    }
+    return 0;
+}
+
+// a local layer of a bf16 engine (and s2v_op_attention_local impl 0): attn_pp<LOCAL> at every length, persistent under the rule above
+int launch_attn_bf16_local(const AttnArgs& a, const int* rec_dev, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_bf16_local: local-attention record missing");
+    S2V_REQUIRE(a.vt != nullptr, "attn_bf16_local: V^T buffer missing");
+    S2V_REQUIRE(a.mx_q == nullptr && !a.p16, "attn_bf16_local: attn_pp writes bf16 and reads bf16 V^T (no MX output, no attn_p_format 1)");
+    S2V_REQUIRE(a.ld_qkv % 8 == 0 && a.ntok_pad % 64 == 0, "attn_bf16_local: bad leading dims");
+    S2V_REQUIRE(a.ntok_pad >= ((a.Ntok + 63) / 64) * 64, "attn_bf16_local: ntok_pad too small");
+    int nqb8 = (a.Ntok + 255) / 256;
+    int total = nqb8 * a.B * a.H;
+    const bool persist = a.queue != nullptr && total > 2 * a.num_cus && a.num_cus >= 8;
+    const void* fn = persist ? (const void*)attn_pp_local_persist_k : (const void*)attn_pp_local_k;
+    S2V_TRY(ensure_lds_attr(fn, 65536));
+    AttnArgs av = a;
+    if (persist) {
+        int* queue = a.queue;
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&total, (void*)&queue, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3((a.num_cus / 8) * 8), dim3(512), args, 65536, st));
+    } else {
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(total), dim3(512), args, 65536, st));
+    }
+    return 0;
+}
+
+// host: the record (kernels.h "local attention") from P and the row table, every bound refused by name; the item and wave tables are reduced
+// here, once per table, not by the kernel
+int attn_local_make(const char* who, int P, int Ntok, const int* lo, const int* hi, std::vector<int>* out) {
+    static thread_local char msg[256];
+#define LOCAL_REQUIRE(cond, ...) do { if (!(cond)) { snprintf(msg, sizeof(msg), __VA_ARGS__); S2V_REQUIRE(false, msg); } } while (0)
+    LOCAL_REQUIRE(Ntok >= 1, "%s: Ntok = %d must be at least 1", who, Ntok);
+    LOCAL_REQUIRE(lo && hi, "%s: null row table", who);
+    LOCAL_REQUIRE(P >= 1 && P <= Ntok, "%s: the prefix P = %d must lie inside [1, Ntok = %d] (key 0 is visible to every row)", who, P, Ntok);
+    for (int i = 0; i < Ntok; ++i)
+        LOCAL_REQUIRE(P <= lo[i] && lo[i] <= hi[i] && hi[i] <= Ntok, "%s: row %d has the window [%d, %d): P = %d <= lo <= hi <= Ntok = %d is required", who, i,
+                      lo[i], hi[i], P, Ntok);
+#undef LOCAL_REQUIRE
+    const int nqb = (Ntok + 255) / 256, npre = (P + KV_TILE - 1) / KV_TILE;
+    std::vector<int>& r = *out;
+    r.assign(attn_local_ints(Ntok), 0);
+    r[0] = P; r[1] = Ntok; r[2] = nqb;
+    int* item = r.data() + ATTN_LOCAL_HDR;
+    int* wave = item + 4 * nqb;
+    int* rlo = wave + 16 * nqb;
+    int* rhi = rlo + 256 * nqb;
+    for (int i = 0; i < 256 * nqb; ++i) { rlo[i] = i < Ntok ? lo[i] : P; rhi[i] = i < Ntok ? hi[i] : Ntok; }   // rows past Ntok: dense
+    for (int q = 0; q < nqb; ++q) {
+        int e0 = Ntok, e1 = 0;   // the envelope of the non-empty windows of the item's rows
+        for (int w = 0; w < 8; ++w) {
+            int lm = P, hm = Ntok;
+            bool any = false;
+            for (int i = q * 256 + w * 32; i < std::min(q * 256 + w * 32 + 32, Ntok); ++i) {
+                lm = any ? std::max(lm, lo[i]) : lo[i];
+                hm = any ? std::min(hm, hi[i]) : hi[i];
+                any = true;
+                if (lo[i] < hi[i]) { e0 = std::min(e0, lo[i]); e1 = std::max(e1, hi[i]); }
+            }
+            wave[2 * (q * 8 + w)] = lm; wave[2 * (q * 8 + w) + 1] = hm;
+        }
+        int np = npre, w0 = npre, w1 = npre;
+        if (e0 < e1) {
+            w0 = e0 / KV_TILE; w1 = (e1 + KV_TILE - 1) / KV_TILE;
+            if (w0 <= np) { np = std::max(np, w1); w0 = w1 = np; }   // the runs touch or overlap: one run
+        }
+        item[4 * q] = np; item[4 * q + 1] = w0; item[4 * q + 2] = w1; item[4 * q + 3] = np + (w1 - w0);
     }
     return 0;
 }
@@ -884,6 +1036,59 @@ int launch_attn_simple_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, int
     S2V_REQUIRE(a.B >= 1 && a.B <= 32, "attn_simple_steer: the sample masks hold 32 samples");
     dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
     S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_steer_k<T>, grid, dim3(256), 0, st, a, rec_dev))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the local form of attn_simple_k (a twin once more, so that the kernel above keeps its code): a key the row does not see gets the score -inf before
+// the maximum and expf, and a 64-key tile the row sees nothing of is skipped.  Tile 0 holds key 0, which every row sees (P >= 1), so the running
+// maximum is finite from the first tile on.  Speed is no goal here: it is what an fp32 engine runs on a local layer, and the second implementation
+// the MFMA kernel is checked against.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_simple_local_k(const AttnArgs a, const int* __restrict__ lr) {
+    __shared__ float sq[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave, h = blockIdx.y, b = blockIdx.z;
+    const int D = a.H * 64;
+    const bool active = q < a.Ntok;
+    const T* base = (const T*)a.qkv + (size_t)b * a.Ntok * a.ld_qkv;
+    const int ql = active ? q : a.Ntok - 1;
+    sq[wave][lane] = ET<T>::ld(base + (size_t)ql * a.ld_qkv + h * 64 + lane) * a.scale;
+    __syncthreads();
+    const int P = lr[0], nq = lr[2];
+    const int lo = lr[ATTN_LOCAL_HDR + 20 * nq + ql], up = lr[ATTN_LOCAL_HDR + 276 * nq + ql];
+    float m = -INFINITY, l = 0.f, o = 0.f;
+    for (int kv0 = 0; kv0 < a.Ntok; kv0 += 64) {
+        if (!(kv0 < P || (kv0 < up && kv0 + 64 > lo))) continue;  // the row sees no key of this tile
+        const int kv = kv0 + lane;
+        float s = -INFINITY;
+        if (kv < a.Ntok && (kv < P || (unsigned)(kv - lo) < (unsigned)(up - lo))) {
+            const T* kp = base + (size_t)kv * a.ld_qkv + D + h * 64;
+            float acc = 0.f;
+#pragma unroll 8
+            for (int d = 0; d < 64; ++d) acc = fmaf(sq[wave][d], ET<T>::ld(kp + d), acc);
+            s = acc;
+        }
+        const float mx = wave_max(s);
+        const float mn = fmaxf(m, mx);
+        const float alpha = expf(m - mn);
+        const float p = expf(s - mn);
+        l = l * alpha + wave_sum(p);
+        o *= alpha;
+        m = mn;
+        const int nv = min(64, a.Ntok - kv0);
+        for (int j = 0; j < nv; ++j) {
+            const float pj = __shfl(p, j, 64);
+            o = fmaf(pj, ET<T>::ld(base + (size_t)(kv0 + j) * a.ld_qkv + 2 * D + h * 64 + lane), o);
+        }
+    }
+    if (active) ET<T>::st((T*)a.out + (size_t)(b * a.Ntok + q) * a.ld_out + h * 64 + lane, o / l);
+}
+
+int launch_attn_simple_local(const AttnArgs& a, const int* rec_dev, int dtype, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_simple_local: local-attention record missing");
+    dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_local_k<T>, grid, dim3(256), 0, st, a, rec_dev))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

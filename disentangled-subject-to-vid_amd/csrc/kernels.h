@@ -317,6 +317,25 @@ int attn_steer_make(const char* who, int n, const int* k0, const int* k1, const 
 int launch_attn_bf16_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, hipStream_t st);
 int launch_attn_simple_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, int dtype, hipStream_t st);
 
+// ---- local attention in time: video rows attend a window of frames (include/s2v_hip.h, "Local attention") ------------
+//   out_i = sum_{j in vis(i)} softmax_{j in vis(i)}(s_ij) v_j,  s_ij = q_i . k_j / 8,  vis(i) = [0, P) union [lo_i, hi_i)
+// with one P and one row table (lo_i, hi_i) for every sample and head; 1 <= P <= Ntok, P <= lo_i <= hi_i <= Ntok (lo_i == hi_i: the prefix only).
+// The record as the kernels read it from DEVICE memory (data, not a launch argument: a new table re-captures nothing), all int32, nqb =
+// ceil(Ntok / 256):
+//   [0 .. 4)                 header  P, Ntok, nqb, 0
+//   [4 .. 4 + 4 nqb)         per 256-row work item  np, w0, w1, np + (w1 - w0): it visits the key tiles [0, np) and [w0, w1), w0 >= np
+//   [.. + 16 nqb)            per 32-row wave  lo_max, hi_min over its rows below Ntok (a wave with none: P, Ntok)
+//   [.. + 256 nqb) twice     lo_i, then hi_i, padded to 256 nqb rows with dense rows (P, Ntok)
+// attn_local_make (host) checks the table, refusing every bound by name, and reduces the item and wave tables.
+#define ATTN_LOCAL_HDR 4
+static inline size_t attn_local_ints(int Ntok) { return (size_t)ATTN_LOCAL_HDR + (size_t)((Ntok + 255) / 256) * (4 + 16 + 512); }
+#include <vector>
+int attn_local_make(const char* who, int P, int Ntok, const int* lo, const int* hi, std::vector<int>* out);
+// attn_pp<LOCAL> at ANY length (bf16; persistent under launch_attn_bf16's rule), and the local attn_simple_k (any dtype; the fp32 engine's local
+// layers and the cross-check).  rec_dev: the record in device memory, made for a.Ntok.  a.mx_q and a.p16 are refused as for steering
+int launch_attn_bf16_local(const AttnArgs& a, const int* rec_dev, hipStream_t st);
+int launch_attn_simple_local(const AttnArgs& a, const int* rec_dev, int dtype, hipStream_t st);
+
 // ---- elementwise / normalisation ------------------------------------------------
 // LayerNorm(eps, affine w,b) then (1+scale)*y+shift with per-row-range modulation sets.
 // rows: [B*Ntok, D]; text rows use (shift_txt, scale_txt), other rows (shift_vid, scale_vid); all [B][mod_stride].

@@ -566,13 +566,43 @@ class S2VEngine:
             mask |= 1 << int(l)
         _lib.check(_lib.lib().s2v_attn_steer_arm(self._h, mask))
 
+    # ---- local attention in time (include/s2v_hip.h: s2v_attn_local_*) -----------------------------------------------------------------------
+    def attn_local_enable(self, on=True):
+        """after set_geometry: allocates the local-attention record's device table (holding a table that windows nothing); False frees it.  Drops
+        a captured step"""
+        _lib.check(_lib.lib().s2v_attn_local_enable(self._h, int(bool(on))))
+
+    def attn_local_set(self, P, rows_lo, rows_hi):
+        """row i of every sample and head sees the keys [0, P) and [rows_lo[i], rows_hi[i]): out_i = sum over those keys of their softmax times v.
+        Ntok rows each, 1 <= P <= Ntok, P <= lo <= hi <= Ntok (lo == hi: the prefix only).  A captured step is kept and replays with the new table"""
+        B, T, F, H, W = self.geometry
+        if len(rows_lo) != len(rows_hi):
+            raise _lib.S2VError(f"attn_local_set: {len(rows_lo)} lower and {len(rows_hi)} upper bounds")
+        p = self.cfg.patch_size
+        ntok = T + (F + 1) * (H // p) * (W // p)   # [text | one reference frame | F latent frames]
+        if len(rows_lo) != ntok:
+            raise _lib.S2VError(f"attn_local_set: the row table has {len(rows_lo)} rows, the geometry {ntok} tokens")
+        _lib.check(_lib.lib().s2v_attn_local_set(self._h, int(P), _lib.i32_array(rows_lo), _lib.i32_array(rows_hi)))
+
+    def _arm_local(self, local_layers):
+        """the layers whose attention launch is the local kernel in the next forward (one-shot; after attn_local_enable)"""
+        if local_layers is None:
+            return
+        mask = 0
+        for l in local_layers:
+            if int(l) != l or l < 0 or l >= 64:
+                raise _lib.S2VError(f"local_layers: {l!r} is no block index")
+            mask |= 1 << int(l)
+        _lib.check(_lib.lib().s2v_attn_local_arm(self._h, mask))
+
     # ---- compute -------------------------------------------------------------------------------------------
-    def forward(self, latents, timesteps, shared_latent=False, cache=None, attn_layers=None, steer_layers=None):
+    def forward(self, latents, timesteps, shared_latent=False, cache=None, attn_layers=None, steer_layers=None, local_layers=None):
         """CogVideoXTransformer3DModel.forward seam: latents [B,F,C,H,W]; with shared_latent [n,F,C,H,W], n dividing B: sample j embeds latent
         j mod n (n = 1: every sample the same latent; n = B/2: the CFG batch cat([latents] * 2) of B/2 videos without the copy).
         cache: the step-cache mode of this forward (_arm; after step_cache_enable)
         attn_layers: the block indices whose attention mass is added to the attention map by this forward (after attn_map_enable)
-        steer_layers: the block indices whose attention runs steered in this forward (after attn_steer_enable / attn_steer_set)"""
+        steer_layers: the block indices whose attention runs steered in this forward (after attn_steer_enable / attn_steer_set)
+        local_layers: the block indices whose attention runs windowed in this forward (after attn_local_enable / attn_local_set)"""
         B, T, F, H, W = self.geometry
         lat = latents.to(self.device, self.dtype).contiguous()
         n_lat = lat.numel() // (F * self.cfg.in_channels * H * W)
@@ -586,6 +616,7 @@ class S2VEngine:
         self._arm(cache)
         self._arm_attn(attn_layers)
         self._arm_steer(steer_layers)
+        self._arm_local(local_layers)
         if shared_latent and n_lat > 1:
             _lib.check(_lib.lib().s2v_transformer_forward_videos(self._h, _lib.ptr(lat), n_lat, _lib.ptr(t), _lib.ptr(out), _lib.stream_ptr()))
             return out
@@ -657,7 +688,7 @@ class S2VEngine:
             self._blend = None
 
     def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None, subject=False,
-                     steer_layers=None):
+                     steer_layers=None, local_layers=None):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples
         [negative x b | positive x b] (b = 1 for B = 1 or 2); x0_hist (fp32) and noise have the shape of latents.  timestep and coef are scalars
         (one timestep and one SchedCoefC for every video: s2v_denoise_step) or sequences of b of each, video k at timestep[k] stepped with
@@ -667,13 +698,15 @@ class S2VEngine:
         attn_layers: the block indices whose attention mass this step adds to the attention map (after attn_map_enable; not with "reuse")
         steer_layers: the block indices whose attention runs steered in this step (after attn_steer_enable / attn_steer_set; not with "reuse",
         attn_layers or subject: the library refuses those by name)
+        local_layers: the block indices whose attention runs windowed in this step (after attn_local_enable / attn_local_set; not with "reuse",
+        attn_layers, steer_layers or subject: the library refuses those by name)
         subject: the subject-guidance step (s2v_denoise_step_guided, after set_conditioning_triples): b = B/3 videos of a geometry of B = 3b
         samples [u x b | r x b | f x b], video k combined with coef[k].guidance_subject and coef[k].guidance; with blend its masked form"""
         if latents.dtype != self.dtype or not latents.is_contiguous():
             raise _lib.S2VError("latents must be a contiguous model-dtype tensor (it is updated in place)")
         B, T, F, H, W = self.geometry
         if subject:
-            return self._denoise_step_guided(latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers, steer_layers)
+            return self._denoise_step_guided(latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers, steer_layers, local_layers)
         if B > 2:
             if B % 2:
                 raise _lib.S2VError(f"denoise_step: a geometry of {B} samples is no whole number of CFG pairs")
@@ -696,6 +729,7 @@ class S2VEngine:
         self._arm(cache)
         self._arm_attn(attn_layers)
         self._arm_steer(steer_layers)
+        self._arm_local(local_layers)
         if blend is not None:
             _lib.check(_lib.lib().s2v_denoise_step_masked(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                           int(use_graph and not auto), _lib.stream_ptr()))
@@ -716,7 +750,7 @@ class S2VEngine:
             self.set_attn_p_format("bf16")
         self._attn_auto_pending = False
 
-    def _denoise_step_guided(self, latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers, steer_layers=None):
+    def _denoise_step_guided(self, latents, timestep, coef, x0_hist, noise, use_graph, blend, cache, attn_layers, steer_layers=None, local_layers=None):
         B, T, F, H, W = self.geometry
         if B % 3:
             raise _lib.S2VError(f"denoise_step(subject=True): a geometry of {B} samples is no whole number of triples [u | r | f]")
@@ -734,6 +768,7 @@ class S2VEngine:
         self._arm(cache)            # the library refuses an armed step by name: the step cache and the attention map assume pairs
         self._arm_attn(attn_layers)
         self._arm_steer(steer_layers)
+        self._arm_local(local_layers)
         _lib.check(_lib.lib().s2v_denoise_step_guided(self._h, _lib.ptr(latents), t_arr, c_arr, b_arr, _lib.ptr(x0_hist), _lib.ptr(noise),
                                                       int(use_graph and not auto), _lib.stream_ptr()))
         if auto:

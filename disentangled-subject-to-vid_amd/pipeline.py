@@ -130,6 +130,67 @@ class AttentionSteer:
 STEER_W_MIN, STEER_W_MAX = 2.0 ** -16, 2.0 ** 16
 
 
+class LocalAttention:
+    """what S2VPipeline.__call__(local_attention=...) windows: on the blocks `layers` (an explicit non-empty list, or the string "all") and the
+    step indices `steps` (None: every step) a video row attends the text, the reference image and only the latent frames within `frames` of
+    its own -- the training-free temporal sliding window.  frames >= 0; a window that covers every frame arms nothing.  No window, layer or
+    step is recommended"""
+
+    def __init__(self, layers, frames, steps=None):
+        self.layers = layers
+        self.frames = frames
+        self.steps = steps
+
+
+def local_attention_table(T, R, F, S, frames):
+    """(P, lo, hi) of the sequence [text T | reference R | F latent frames of S rows]: P = T + R; the rows below P are dense (lo = P, hi =
+    Ntok); a video row of latent frame f sees the frames [f - frames, f + frames]: lo = P + max(0, f - frames) S, hi = P + min(F, f + frames + 1) S.
+    Host integers only"""
+    T, R, F, S, w = int(T), int(R), int(F), int(S), int(frames)
+    if T < 0 or R < 0 or T + R < 1 or F < 1 or S < 1 or w < 0:
+        raise ValueError(f"local attention: T + R >= 1, F >= 1, S >= 1 and frames >= 0 are required, got T = {T}, R = {R}, F = {F}, S = {S}, frames = {w}")
+    P = T + R
+    ntok = P + F * S
+    lo, hi = [P] * P, [ntok] * P
+    for f in range(F):
+        lo += [P + max(0, f - w) * S] * S
+        hi += [P + min(F, f + w + 1) * S] * S
+    return P, lo, hi
+
+
+def local_attention_items(P, lo, hi):
+    """the visit list of every 256-row work item of the kernel, [(np, w0, w1)]: the 64-key tiles [0, np) of the prefix and [w0, w1) of the envelope
+    of the item's non-empty windows, merged into the first run (w0 = w1 = np) where they touch or overlap"""
+    n = len(lo)
+    npre = (P + 63) // 64
+    out = []
+    for q0 in range(0, n, 256):
+        rows = [(a, b) for a, b in zip(lo[q0:q0 + 256], hi[q0:q0 + 256]) if a < b]
+        np_, w0, w1 = npre, npre, npre
+        if rows:
+            w0, w1 = min(a for a, _ in rows) // 64, (max(b for _, b in rows) + 63) // 64
+            if w0 <= np_:
+                np_ = max(np_, w1)
+                w0 = w1 = np_
+        out.append((np_, w0, w1))
+    return out
+
+
+def local_attention_share(P, lo, hi):
+    """the key tiles the local launch visits as a share of the dense launch's (counted per work item, on the host)"""
+    items = local_attention_items(P, lo, hi)
+    return sum(np_ + w1 - w0 for np_, w0, w1 in items) / (len(items) * ((len(lo) + 63) // 64))
+
+
+def local_attention_plan(la, n_steps):
+    """the step indices of a call of n_steps steps on which the layers of `la` run windowed"""
+    want = list(range(n_steps)) if la.steps is None else sorted(set(int(i) for i in la.steps))
+    for i in want:
+        if i < 0 or i >= n_steps:
+            raise ValueError(f"`local_attention`: step {i} is outside the {n_steps} steps this call runs")
+    return want
+
+
 def attention_steer_ranges(st, T, R, b):
     """the key ranges (k0, k1, w, sample_mask) of an AttentionSteer for b videos laid out [negative x b | positive x b] over [text T | reference R |
     video]: the text spans, ascending, on the positive halves (bits b .. 2b - 1), then the reference keys [T, T + R) on all 2b samples.  Ranges
@@ -604,6 +665,54 @@ class S2VPipeline:
                 raise ValueError(f"`attention_steer`: the weight of {name} must be finite and inside [2^-16, 2^16], got {w!r}")
         return st
 
+    local_attention_report = None
+
+    @staticmethod
+    def check_local_attention(la, num_layers, dtype=None, weight_format=None, per_video=False, cfg_parallel=None, ulysses=None, fused=True,
+                              videos_path=False, attention_map=None, attention_steer=None, step_cache=None, subject_guidance_scale=None,
+                              temporal_windows=None):
+        """every refusal of a call with local attention that needs no step count and no geometry (no device is touched); -> the layers as a list"""
+        if not isinstance(la, LocalAttention):
+            raise ValueError("`local_attention` must be a LocalAttention(layers, frames, steps=None)")
+        for name, arg, why in (("attention_map", attention_map, "the map reads the un-windowed softmax"),
+                               ("attention_steer", attention_steer, "a layer runs one attention kernel, the steered or the local one"),
+                               ("step_cache", step_cache, "a reuse step runs no attention to window"),
+                               ("subject_guidance_scale", subject_guidance_scale, "local attention assumes CFG pairs, subject guidance runs triples"),
+                               ("temporal_windows", temporal_windows, "local attention runs one forward per step, a windowed step runs several")):
+            if arg is not None:
+                raise ValueError(f"`local_attention` together with `{name}`: {why}")
+        _one_gpu_only(cfg_parallel, ulysses, lambda name: f"`local_attention` together with `{name}`: the local attention kernel runs on one GPU; "
+                                                          f"CFG-parallel and Ulysses split the attention it windows")
+        if not fused:
+            raise ValueError("`local_attention` together with fused=False: the local kernel runs inside the fused step; fused=False is the "
+                             "reference's seam sequence")
+        if per_video or videos_path:
+            raise ValueError("`local_attention` together with per-video lists (or several input videos, which run per-video plans): one table on one "
+                             "plan of steps is shared by the whole batch")
+        if dtype == torch.float16:
+            raise ValueError("`local_attention` with an fp16 engine: the local kernels serve bf16 (attn_pp) and fp32 (the generic form)")
+        if weight_format is not None:
+            raise ValueError(f"`local_attention` with weight_format {weight_format!r}: the fp8 engines' attention writes the MX output, the local "
+                             f"kernel writes bf16 only")
+        if isinstance(la.layers, str):
+            if la.layers != "all":
+                raise ValueError(f"`local_attention`: `layers` is an explicit, non-empty list of block indices or the string \"all\", got {la.layers!r}")
+            layers = list(range(num_layers))
+        else:
+            if not isinstance(la.layers, (list, tuple)) or len(la.layers) == 0:
+                raise ValueError("`local_attention`: `layers` is an explicit, non-empty list of block indices or the string \"all\"")
+            for l in la.layers:
+                if isinstance(l, bool) or int(l) != l or l < 0 or l >= num_layers:
+                    raise ValueError(f"`local_attention`: layer {l!r} is no block index of a model of {num_layers} blocks")
+            if len(set(int(l) for l in la.layers)) != len(la.layers):
+                raise ValueError("`local_attention`: a layer is listed twice")
+            layers = [int(l) for l in la.layers]
+        if isinstance(la.frames, bool) or not isinstance(la.frames, int) or la.frames < 0:
+            raise ValueError(f"`local_attention`: `frames` counts latent frames either side of the row's own, an integer >= 0, got {la.frames!r}")
+        if la.steps is not None and (not isinstance(la.steps, (list, tuple)) or any(int(i) != i for i in la.steps)):
+            raise ValueError("`local_attention`: `steps` is a list of step indices, or None for every step")
+        return layers
+
     @staticmethod
     def blend_plan(scheduler, plan, dtype, device="cpu", keep_max=None):
         """the masked step's record (scheduler.blend_record) for every step of a video_plan: step i blends at the video's NEXT timestep
@@ -645,7 +754,8 @@ class S2VPipeline:
                  latents=None, output_type="latent", return_dict=True, fused=True, use_graph=False,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
                  video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None,
-                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None, temporal_windows=None, attention_steer=None):
+                 attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None, temporal_windows=None, attention_steer=None,
+                 local_attention=None):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -717,10 +827,26 @@ class S2VPipeline:
         change_map=, paste_back, use_graph, both schedulers, runtime LoRA on bf16 and several videos per call with scalars (one steer shared by
         all).  After the call `attention_steer_report` holds {"steps", "layers", "ranges"}.  Refused with attention_map=, step_cache=,
         subject_guidance_scale=, temporal_windows=, cfg_parallel=, ulysses=, fused=False, per-video lists, several input videos, fp16 and fp8
-        engines.  No weight, layer or step is recommended."""
+        engines.  No weight, layer or step is recommended.
+        local_attention: a LocalAttention(layers, frames, steps=None) -- on the listed steps (None: every step) the attention of the listed blocks
+        (or "all") lets a video row see the text, the reference image and only the latent frames within `frames` of its own (exact masked
+        softmax; the kernel skips the key tiles no row of a work item sees).  A window that covers every frame (frames >= F - 1) arms nothing:
+        the launches and bits are those of the call without it.  Composes with video= / strength, mask=, change_map=, paste_back, use_graph,
+        both schedulers, runtime LoRA on bf16 and several videos per call with scalars (one table shared by all).  After the call
+        `local_attention_report` holds {"steps", "layers", "frames", "visited_tile_share"}.  Refused with attention_map=, attention_steer=,
+        step_cache=, subject_guidance_scale=, temporal_windows=, cfg_parallel=, ulysses=, fused=False, per-video lists, several input videos,
+        fp16 and fp8 engines.  No window, layer or step is recommended."""
         self.step_cache_report = None
         self.attention_maps = None
         self.attention_steer_report = None
+        self.local_attention_report = None
+        la_layers = None
+        if local_attention is not None:   # refused before anything else looks at the arguments it excludes
+            nb_ = prompt_embeds.shape[0] * num_videos_per_prompt if prompt_embeds is not None and prompt_embeds.ndim == 3 else 1
+            la_layers = self.check_local_attention(
+                local_attention, self.transformer.config.num_layers, self.transformer.dtype, getattr(self.transformer.config, "weight_format", None),
+                any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength)), cfg_parallel, ulysses, fused,
+                video is not None and nb_ > 1, attention_map, attention_steer, step_cache, subject_guidance_scale, temporal_windows)
         if attention_steer is not None:   # refused before anything else looks at the arguments it excludes
             nb_ = prompt_embeds.shape[0] * num_videos_per_prompt if prompt_embeds is not None and prompt_embeds.ndim == 3 else 1
             attention_steer = self.check_attention_steer(
@@ -813,11 +939,13 @@ class S2VPipeline:
         return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
                              num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                              callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
-                             step_cache, attention_map, steer=attention_steer)
+                             step_cache, attention_map, steer=attention_steer,
+                             local=None if local_attention is None else (local_attention, la_layers))
 
     def _denoise(self, plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator, latents,
                  output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video,
-                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None, windows=None, steer=None):
+                 num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None, windows=None, steer=None,
+                 local=None):
         """the one denoise loop: b = len(plans) videos, each on its video_plan; iteration i applies step i of every video that still has one.
         The videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers;
         when the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
@@ -835,7 +963,9 @@ class S2VPipeline:
         and noise have L frames; the geometry is 2 per_forward samples of the WINDOW's F frames, conditioned with the text pair repeated
         per_forward times, and every step is the windowed step on the whole long latent
         steer: a steered call (None: every other call, which touches no steer entry) -- its AttentionSteer, checked; scalars only, so the batch
-        never shrinks and the one geometry holds for the whole call"""
+        never shrinks and the one geometry holds for the whole call
+        local: a call with local attention (None: every other call, which touches no local entry) -- (its LocalAttention, the checked layer list);
+        scalars only as well"""
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         b = len(plans)
@@ -955,6 +1085,15 @@ class S2VPipeline:
             st_steps = attention_steer_plan(steer, lens[0]) if st_ranges else []
             self.attention_steer_report = {"steps": list(st_steps), "layers": [int(l) for l in steer.layers] if st_ranges else [],
                                            "ranges": list(st_ranges)}
+        la_steps, la_table = [], None
+        if local is not None:   # the table and the windowed steps, on the host, before the loop; a window over every frame: nothing is enabled or armed
+            la, la_layers = local
+            S_ = (H // 2) * (W // 2)
+            if la.frames < F - 1:
+                la_table = local_attention_table(text.shape[1], S_, F, S_, la.frames)
+                la_steps = local_attention_plan(la, lens[0])
+            self.local_attention_report = {"steps": list(la_steps), "layers": list(la_layers) if la_table else [], "frames": int(la.frames),
+                                           "visited_tile_share": local_attention_share(*la_table) if la_table else 1.0}
         active = b
         old = [None] * b   # fused=False under DPM: every video's x0 of its last step
         last_t = [plans[k]["timesteps"][0] for k in order]
@@ -967,6 +1106,9 @@ class S2VPipeline:
             if st_ranges:
                 eng.attn_steer_enable(True)
                 eng.attn_steer_set(st_ranges)
+            if la_table:
+                eng.attn_local_enable(True)
+                eng.attn_local_set(*la_table)
             for i in range(lens[0]):
                 if self.interrupt:
                     break
@@ -1012,7 +1154,8 @@ class S2VPipeline:
                         eng.denoise_step(latents[:a], ts, coefs, x0_hist[:a] if is_dpm else None, noise[:a] if is_dpm else None, use_graph,
                                          blend=None if mask is None else [blends[p][i] for p in range(a)], cache=cache,
                                          attn_layers=attention_map.layers if collect else None, **({} if subject is None else {"subject": True}),
-                                         **({"steer_layers": steer.layers} if st_ranges and i in st_steps else {}))
+                                         **({"steer_layers": steer.layers} if st_ranges and i in st_steps else {}),
+                                         **({"local_layers": la_layers} if la_table and i in la_steps else {}))
                         if collect:
                             am_ran.append(i)
                 else:
@@ -1076,6 +1219,8 @@ class S2VPipeline:
                 eng.attn_map_enable(False)
             if st_ranges:
                 eng.attn_steer_enable(False)
+            if la_table and eng.geometry is not None:
+                eng.attn_local_enable(False)
         return self._finish(callers(latents), fused, output_type, return_dict, paste)
 
     @staticmethod

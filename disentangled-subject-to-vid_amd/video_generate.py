@@ -46,7 +46,7 @@ def prompt_embeddings(text_encoder, input_ids, dtype=None):
 def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_ids, height=480, width=720, num_frames=49,
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
               video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, change_map_uint8=None, attention_map=None, subject_guidance_scale=None,
-              temporal_windows=None, attention_steer=None, **pipe_kwargs):
+              temporal_windows=None, attention_steer=None, local_attention=None, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
     `output_type` selects ("latent" / "pt").  A batch of prompt ids [P, T] (with num_videos_per_prompt through **pipe_kwargs: up to four
     videos per call) shares the one reference image and returns one video per row, [b, F, H, W, 3].
@@ -92,7 +92,13 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
 
     Attention steering: attention_steer=AttentionSteer(layers, steps, subject, text_spans) is passed through to S2VPipeline.__call__ -- a
     softmax weight on the reference-image keys and on token spans of the prompt (the spans count tokens of prompt_ids); the steered steps and
-    layers are in pipe.attention_steer_report after the call."""
+    layers are in pipe.attention_steer_report after the call.
+
+    Local attention: local_attention=LocalAttention(layers, frames, steps) is passed through to S2VPipeline.__call__ -- on those blocks and steps
+    a video row attends the text, the reference image and the latent frames within `frames` of its own; the windowed steps, the layers and the
+    share of key tiles the kernel visits are in pipe.local_attention_report after the call."""
+    if local_attention is not None:
+        pipe_kwargs = dict(pipe_kwargs, local_attention=local_attention)
     if attention_steer is not None:
         pipe_kwargs = dict(pipe_kwargs, attention_steer=attention_steer)
     if temporal_windows is not None:

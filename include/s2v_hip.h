@@ -516,6 +516,47 @@ S2V_API int s2v_attn_steer_arm(s2v_ctx* ctx, uint64_t layer_mask);
 S2V_API int s2v_op_attention_steer(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
                                    const s2v_attn_steer_record* record_host, s2v_stream stream);
 
+/* ---- Local attention in time: video rows attend a window of frames (the training-free temporal sliding window) ------------------------------------
+ * ONE definition, which the kernels (csrc/attention.hip), tests/attn_local_ref.py and this comment state alike.  For sample b, head h, query row
+ * i and key j of the joint attention over [text T | reference R | video V]:
+ *     s_ij   = q_i . k_j / 8
+ *     out_i  = sum_{j in vis(i)} softmax_{j in vis(i)}(s_ij) v_j
+ *     vis(i) = [0, P)  union  [lo_i, hi_i)
+ * Every sample and head uses the same P and the same row table (lo_i, hi_i), i in [0, Ntok).  Any table with 1 <= P <= Ntok and
+ * P <= lo_i <= hi_i <= Ntok is taken; lo_i == hi_i is an empty window: that row sees the prefix only.  P >= 1 is required: key 0 is then visible
+ * to every row, so the first key tile a work item visits holds a visible key for each of its rows, which the kernel's adoption of the first
+ * tile's maximum needs.  Anything outside these bounds is refused by name.
+ * The MFMA kernel (attn_pp<LOCAL>) visits, per 256-row work item, the 64-key tiles of the prefix and of the envelope of the item's windows, and
+ * skips every other tile; in a visited tile it sets the scores of the keys a row does not see to -inf, before everything its softmax segment does
+ * (the row-sum vote of the deferred maximum, the slow path's maximum, exp2).  A 32-row wave all of whose rows see all of a tile runs the
+ * un-windowed code on it: a table whose every row sees everything returns the bits of the un-windowed attn_pp, and so do the 32 rows of a wave
+ * whose rows are all dense (lo = P, hi = Ntok) inside a table that windows other waves.  The generic kernel masks before its maximum and expf.
+ * Engines: a local layer of a bf16 engine runs attn_pp<LOCAL> at EVERY length (persistent under the rule of the un-windowed launch); an fp32
+ * engine runs the local generic kernel -- fp32 is the parity mode and its speed is no goal.  Layers that are not local, and every call with the
+ * feature off, run the launches they run without it.
+ * s2v_attn_local_enable: after s2v_set_geometry; on != 0 allocates the record's device table for the geometry's Ntok (counted by s2v_device_bytes
+ * as workspace while on) holding a table that windows nothing, on = 0 frees it.  Drops a captured step.
+ * s2v_attn_local_set: P and two host arrays of Ntok rows, checked against the current geometry with an error that names what is wrong BEFORE
+ * anything is replaced; synchronises the device and uploads.  The table is data, not a launch argument: a captured step is kept and replays with
+ * the new table.  A later s2v_set_geometry with another Ntok switches the feature off (the table is one row per token).
+ * s2v_attn_local_arm: the layers (bit l = block l) of the NEXT forward only (s2v_transformer_forward*, s2v_denoise_step, _videos, _masked).  An
+ * armed step is another launch sequence: captured steps are kept per (step-cache mode, map mask, steer mask, local mask), and an un-armed step
+ * never replays an armed executable nor the reverse.
+ * Refused by name: fp16 engines; every fp8 weight format; attn_p_format 1 (fp16 V^T); shard contexts; attention-only contexts; triple-conditioned
+ * contexts and s2v_denoise_step_guided; contexts with temporal windows and s2v_denoise_step_windows; s2v_denoise_split_begin (CFG-parallel); an
+ * armed attention map, an armed steer or S2V_STEP_REUSE together with an armed local mask, in either order of the two arms; a layer bit at or
+ * beyond num_layers; s2v_block_forward and the s2v_attn_forward* / AttnProcessor seams while a local mask is armed. */
+S2V_API int s2v_attn_local_enable(s2v_ctx* ctx, int32_t on);
+S2V_API int s2v_attn_local_set(s2v_ctx* ctx, int32_t P, const int32_t* rows_lo, const int32_t* rows_hi);
+S2V_API int s2v_attn_local_arm(s2v_ctx* ctx, uint64_t layer_mask);
+/* the local kernel on its own: qkv / vt_scratch / out as s2v_op_attention takes them.  impl 0: attn_pp<LOCAL> (bf16, any Ntok, one work item
+ * per 256 query rows, persistent when the launch has more than two items per CU); impl 1: the local generic kernel (any dtype).  The record is
+ * made from (P, rows_lo, rows_hi) and copied to ONE table per process on the device current at the first call; the entry synchronises `stream`
+ * first and is not thread-safe -- a test and benchmark entry; contexts hold their own table.  Refused by name: a bad table (as
+ * s2v_attn_local_set), impl 0 with another dtype than bf16 */
+S2V_API int s2v_op_attention_local(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                   int32_t P, const int32_t* rows_lo, const int32_t* rows_hi, s2v_stream stream);
+
 /* Live per-kernel timing for the roofline report (bench.py): HIP events are recorded on the launch stream around
  * every launch of a class; classes 0 qkv GEMM, 1 attention, 2 out-proj GEMM, 3 FF1 GEMM, 4 FF2 GEMM,
  * 5 LN-modulate, 6 qk-norm/rope/V^T, 7 the modulation GEMV, 8 the Ulysses packs, 9 the runtime-LoRA down-projections.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
