@@ -174,6 +174,18 @@ _SIGS.update({
     "s2v_denoise_step_windows": [_P, _P, _F, ctypes.POINTER(SchedCoefC), _P, _P, _I32, _P],
     "s2v_op_window_blend": [_P, _P, _P, _P, _F, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
 })
+# guidance rescale (include/s2v_hip.h: s2v_set_guidance_rescale, s2v_guidance_rescale_read, s2v_op_cfg_stats, the RESCALE step forms)
+SCHED_RESCALE = 16                                # s2v_sched_step_rescale / s2v_sched_step_masked_rescale flags bit4
+CFG_STATS_CHUNK, CFG_LOG_STEPS, CFG_LOG_COLS = 4096, 1024, 4   # S2V_CFG_STATS_CHUNK, S2V_CFG_LOG_STEPS, S2V_MAX_BATCH / 2
+_SIGS.update({
+    "s2v_set_guidance_rescale": [_P, ctypes.POINTER(_F), _I32],
+    "s2v_guidance_rescale_read": [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_F), ctypes.POINTER(_F), ctypes.POINTER(_I32)],
+    "s2v_op_cfg_stats": [_P, _I32, _I32, _I64, ctypes.POINTER(_F), ctypes.POINTER(_F), ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_double),
+                         ctypes.POINTER(_F), _I32, _P],
+    "s2v_sched_step_rescale": [_P, ctypes.POINTER(SchedCoefC), _P, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P],
+    "s2v_sched_step_masked_rescale": [_P, ctypes.POINTER(SchedCoefC), ctypes.POINTER(BlendC), _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32,
+                                      _I32, _I32, _P, _P],
+})
 # replicas over RCCL behind the C ABI (csrc/rccl.hip); RCCL itself is bound at first use
 _SIGS.update({
     "s2v_rccl_available": [],

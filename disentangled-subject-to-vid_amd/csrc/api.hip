@@ -79,9 +79,10 @@ struct GraphKey {
     uint64_t smask = 0;   // s2v_attn_steer_arm: the layers whose attention launch is the steered kernel in this step; an executable per mask as well
     int triple = 0;       // s2v_denoise_step_guided: the step of [u | r | f] triples, whose last kernel is another one than the pair step's
     int windows = 0;      // s2v_denoise_step_windows: every forward and blend of a long latent's windows, then one scheduler step on the whole of it
+    int rescale = 0;      // s2v_set_guidance_rescale armed: two more launches and another last kernel, so an armed and an un-armed step never replay each other
     bool same_but_mode(const GraphKey& o) const {
         return latents == o.latents && x0 == o.x0 && noise == o.noise && slot == o.slot && z0 == o.z0 && noise0 == o.noise0 && mask == o.mask && triple == o.triple &&
-               windows == o.windows;
+               windows == o.windows && rescale == o.rescale;
     }
     uint64_t lmask = 0;   // s2v_attn_local_arm: the layers whose attention launch is the local kernel in this step; an executable per mask as well
     bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask && smask == o.smask && lmask == o.lmask; }
@@ -228,6 +229,15 @@ struct s2v_ctx {
     int win_L = 0, win_s = 0, win_pf = 0, win_W = 0;
     float *win_acc = nullptr, *win_w = nullptr, *win_wsum = nullptr;
     int64_t win_bytes = 0;
+    // guidance rescale (s2v_set_guidance_rescale; include/s2v_hip.h).  Armed <=> gr_buf: one allocation beside the workspace for the gr_b videos of the
+    // geometry -- the chunk partials [gr_b][chunks][4] fp64, then the sums [4][4] fp64, the factors [4] and phi [4] fp32.  The log (rows of factors,
+    // then the device-side count) is an allocation of its own that outlives a disarm: a shrinking batch arms again and goes on logging
+    char* gr_buf = nullptr;
+    double *gr_partials = nullptr, *gr_sums = nullptr;
+    float *gr_factors = nullptr, *gr_phi = nullptr, *gr_log = nullptr;
+    unsigned* gr_log_count = nullptr;
+    int gr_b = 0;
+    int64_t gr_bytes = 0, gr_log_bytes = 0;
     int split_kind = -1;         // scheduler kind of the s2v_denoise_split_begin that has not met its s2v_denoise_split_end yet (-1: none pending)
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's live roofline figure)
     // + shader-clock stamps (s_memtime / s_memrealtime pairs written by a one-lane kernel right before and right after every profiled launch)
@@ -558,6 +568,8 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->ws) hipFree(c->ws);
     if (c->e1x) hipFree(c->e1x);
     if (c->win_acc) hipFree(c->win_acc);
+    if (c->gr_buf) hipFree(c->gr_buf);
+    if (c->gr_log) hipFree(c->gr_log);
     if (c->st_tab) hipFree(c->st_tab);
     if (c->la_tab) hipFree(c->la_tab);
     if (c->attn_queue) hipFree(c->attn_queue);
@@ -683,6 +695,17 @@ static void win_free(s2v_ctx* c) {
     if (c->win_acc) hipFree(c->win_acc);
     c->win_acc = c->win_w = c->win_wsum = nullptr;
     c->win_bytes = 0; c->win_L = c->win_s = c->win_pf = c->win_W = 0;
+}
+
+// guidance rescale: the partials belong to one geometry (the caller has synchronised the device and dropped the graphs); the log stays
+static void gr_free(s2v_ctx* c) {
+    if (c->gr_buf) hipFree(c->gr_buf);
+    c->gr_buf = nullptr; c->gr_partials = c->gr_sums = nullptr; c->gr_factors = c->gr_phi = nullptr;
+    c->gr_b = 0; c->gr_bytes = 0;
+}
+static void gr_free_log(s2v_ctx* c) {
+    if (c->gr_log) hipFree(c->gr_log);
+    c->gr_log = nullptr; c->gr_log_count = nullptr; c->gr_log_bytes = 0;
 }
 
 // the references beyond the first (s2v_set_conditioning_refs) go with the workspace they were projected for
@@ -870,6 +893,7 @@ extern "C" int s2v_set_shard(s2v_ctx* c, int32_t world, int32_t rank) {
     st_free(c);   // ... and no attention steering
     la_free(c);   // ... and no local attention
     win_free(c);  // ... and no temporal windows
+    gr_free(c);   // ... and no guidance rescale
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; }  // the workspace is carved for the shard: s2v_set_geometry comes next
     drop_refs(c);
     c->B = 0;
@@ -890,6 +914,11 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
         S2V_CHECK_HIP(hipDeviceSynchronize());
         drop_graph(c);
         win_free(c);
+    }
+    if (c->gr_buf) {    // ... and so do the guidance-rescale values: the partials are sized for the geometry they were set on (the log stays)
+        S2V_CHECK_HIP(hipDeviceSynchronize());
+        drop_graph(c);
+        gr_free(c);
     }
     if (c->ws && B == c->B && T == c->gT && F == c->F && H == c->H && W == c->W) return 0;
     if (c->shard) S2V_REQUIRE(F * (H / 2) * (W / 2) >= c->sp, "s2v_set_geometry: every rank of a shard needs at least one video row");
@@ -1978,7 +2007,7 @@ extern "C" int s2v_lora_state(s2v_ctx* c, int32_t* attached, int32_t* rank, floa
 extern "C" int s2v_device_bytes(s2v_ctx* c, int64_t* arena, int64_t* workspace) {
     S2V_REQUIRE(c && arena && workspace, "s2v_device_bytes: null argument");
     *arena = c->arena ? c->arena_bytes : 0;
-    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes + c->win_bytes + c->st_bytes() + c->la_bytes() : 0;
+    *workspace = c->ws ? c->ws_bytes + c->e1x_bytes + c->sc_bytes + c->am_bytes + c->win_bytes + c->st_bytes() + c->la_bytes() + c->gr_bytes + (c->gr_buf ? c->gr_log_bytes : 0) : 0;
     return 0;
 }
 
@@ -1997,27 +2026,40 @@ extern "C" int s2v_add_noise(const void* sample, const void* noise, int64_t n, f
     return launch_add_noise(sample, noise, n, sqrt_alpha, sqrt_one_minus_alpha, out, dtype, (hipStream_t)stream);
 }
 
-extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags,
-                              const void* latents_in, void* latents_out, float* x0_hist, const void* noise, int64_t n,
-                              int32_t dtype, s2v_stream stream) {
+// s2v_sched_step (factors == null) and s2v_sched_step_rescale (its RESCALE form): one body, the entry's own wording for what differs
+static int sched_step_entry(const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags, const void* latents_in, void* latents_out,
+                            float* x0_hist, const void* noise, int64_t n, int32_t dtype, const float* factors, s2v_stream stream) {
     S2V_REQUIRE(coef_host && noise_pred && latents_in && latents_out, "s2v_sched_step: null argument");
     S2V_REQUIRE(coef_host->kind == 0 || noise, "s2v_sched_step: DPM step needs a noise tensor");
     S2V_REQUIRE(coef_host->kind != 2 || x0_hist, "s2v_sched_step: DPM multistep needs x0_hist");
     S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_sched_step: unsupported dtype");
     S2V_REQUIRE((flags & 9) != 9, "s2v_sched_step: flags bit0 (the CFG pair [2, n]) and bit3 (the subject-guidance triple [3, n]) exclude each other");
-    (void)c;
     SchedArgs a{};
     a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
     a.noise = noise; a.n = n; a.nvid = 1; a.n_vid = n; a.cfg = (flags & 8) ? SCHED_CFG_TRIPLE : flags & 1; a.np_f32 = (flags >> 1) & 1; a.out_f32 = (flags >> 2) & 1;
     a.coef = nullptr;
     fill_coef(a.cval, *coef_host);
-    return launch_sched_step(a, dtype, (hipStream_t)stream);
+    return launch_sched_step(a, dtype, (hipStream_t)stream, factors);
+}
+extern "C" int s2v_sched_step(s2v_ctx* c, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags,
+                              const void* latents_in, void* latents_out, float* x0_hist, const void* noise, int64_t n,
+                              int32_t dtype, s2v_stream stream) {
+    (void)c;
+    S2V_REQUIRE(!(flags & S2V_SCHED_RESCALE), "s2v_sched_step: flags bit4 (the RESCALE form of the guidance rescale) needs the device factor, which rides in s2v_sched_step_rescale");
+    return sched_step_entry(coef_host, noise_pred, flags, latents_in, latents_out, x0_hist, noise, n, dtype, nullptr, stream);
+}
+extern "C" int s2v_sched_step_rescale(s2v_ctx* c, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags, const void* latents_in,
+                                      void* latents_out, float* x0_hist, const void* noise, int64_t n, int32_t dtype, const float* factors,
+                                      s2v_stream stream) {
+    (void)c;
+    S2V_REQUIRE((flags & S2V_SCHED_RESCALE) && factors, "s2v_sched_step_rescale: flags bit4 (S2V_SCHED_RESCALE) and a device pointer to the video's factor are required");
+    return sched_step_entry(coef_host, noise_pred, flags, latents_in, latents_out, x0_hist, noise, n, dtype, factors, stream);
 }
 
-extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
-                                     const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0,
-                                     const void* noise0, const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype,
-                                     s2v_stream stream) {
+static int sched_step_masked_entry(const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
+                                   const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0,
+                                   const void* noise0, const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype,
+                                   const float* factors, s2v_stream stream) {
     S2V_REQUIRE(coef_host && blend_host && noise_pred && latents_in && latents_out && z0 && noise0 && latent_mask, "s2v_sched_step_masked: null argument");
     S2V_REQUIRE(F >= 1 && C >= 1 && H >= 1 && W >= 1, "s2v_sched_step_masked: the latent is [F, C, H, W]");
     S2V_REQUIRE(coef_host->kind == 0 || noise, "s2v_sched_step_masked: DPM step needs a noise tensor");
@@ -2026,7 +2068,6 @@ extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host
     S2V_REQUIRE(!(flags & 4), "s2v_sched_step_masked: the blend runs on the latents rounded to `dtype` (flags bit2, fp32 output, is refused)");
     S2V_REQUIRE(blend_host->keep_max >= 0 && blend_host->keep_max <= 255, "s2v_sched_step_masked: keep_max must be a level 0..255");
     S2V_REQUIRE((flags & 9) != 9, "s2v_sched_step_masked: flags bit0 (the CFG pair [2, n]) and bit3 (the subject-guidance triple [3, n]) exclude each other");
-    (void)c;
     SchedMaskArgs a{};
     a.noise_pred = noise_pred; a.latents_in = latents_in; a.latents_out = latents_out; a.x0_hist = x0_hist;
     a.noise = noise; a.n = (int64_t)F * C * H * W; a.nvid = 1; a.n_vid = a.n; a.cfg = (flags & 8) ? SCHED_CFG_TRIPLE : flags & 1; a.np_f32 = (flags >> 1) & 1;
@@ -2034,7 +2075,25 @@ extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host
     fill_coef(a.cval, *coef_host);
     a.z0 = z0; a.noise0 = noise0; a.mask = latent_mask; a.chw = C * H * W; a.hw = H * W; a.mask_vid = F * H * W;
     a.blend = nullptr; a.bval = fill_blend(*blend_host);
-    return launch_sched_step_masked(a, dtype, (hipStream_t)stream);
+    return launch_sched_step_masked(a, dtype, (hipStream_t)stream, factors);
+}
+extern "C" int s2v_sched_step_masked(s2v_ctx* c, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred, int32_t flags,
+                                     const void* latents_in, void* latents_out, float* x0_hist, const void* noise, const void* z0,
+                                     const void* noise0, const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H, int32_t W, int32_t dtype,
+                                     s2v_stream stream) {
+    (void)c;
+    S2V_REQUIRE(!(flags & S2V_SCHED_RESCALE), "s2v_sched_step_masked: flags bit4 (the RESCALE form of the guidance rescale) needs the device factor, which rides in s2v_sched_step_masked_rescale");
+    return sched_step_masked_entry(coef_host, blend_host, noise_pred, flags, latents_in, latents_out, x0_hist, noise, z0, noise0, latent_mask, F, C, H, W, dtype,
+                                   nullptr, stream);
+}
+extern "C" int s2v_sched_step_masked_rescale(s2v_ctx* c, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred,
+                                             int32_t flags, const void* latents_in, void* latents_out, float* x0_hist, const void* noise,
+                                             const void* z0, const void* noise0, const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H,
+                                             int32_t W, int32_t dtype, const float* factors, s2v_stream stream) {
+    (void)c;
+    S2V_REQUIRE((flags & S2V_SCHED_RESCALE) && factors, "s2v_sched_step_masked_rescale: flags bit4 (S2V_SCHED_RESCALE) and a device pointer to the video's factor are required");
+    return sched_step_masked_entry(coef_host, blend_host, noise_pred, flags, latents_in, latents_out, x0_hist, noise, z0, noise0, latent_mask, F, C, H, W, dtype,
+                                   factors, stream);
 }
 
 extern "C" int s2v_mask_to_latent(const void* mask, int32_t mask_dtype, int32_t F, int32_t H, int32_t W, uint8_t* latent_mask, uint8_t* pixel_mask,
@@ -2107,19 +2166,130 @@ static int launch_captured(s2v_ctx* c, const GraphKey& key, hipStream_t st, Body
 // (CFG +) scheduler step on the context's noise_pred with the coefficients stage_step uploaded, latents updated in place.  nvid videos:
 // latents / x0_hist / noise [nvid][F,C,H,W] and noise_pred [negative x nvid | positive x nvid], so the conditional half starts n elements in;
 // video k is stepped with the k-th uploaded coefficient set
-static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, int cfg_flag, hipStream_t st, int nvid = 1) {
+static int sched_on_pair(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, int cfg_flag, hipStream_t st, int nvid = 1, const float* factor = nullptr) {
     SchedArgs a{};
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
     a.nvid = nvid; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
     a.n = nvid * a.n_vid; a.cfg = cfg_flag; a.coef = c->coef_dev;
-    return launch_sched_step(a, c->dtype, st);
+    return launch_sched_step(a, c->dtype, st, factor);
+}
+
+// ---- guidance rescale (include/s2v_hip.h) ---------------------------------------------------------------------------------------------------
+static int64_t video_elems(const s2v_ctx* c) { return (int64_t)c->F * c->cfg.out_channels * c->H * c->W; }
+
+extern "C" int s2v_set_guidance_rescale(s2v_ctx* c, const float* phi, int32_t b) {
+    S2V_REQUIRE(c, "s2v_set_guidance_rescale: null context");
+    if (!phi && b == 0) {   // clear: nothing held, s2v_device_bytes as without the feature
+        if (c->gr_buf || c->gr_log) { S2V_CHECK_HIP(hipDeviceSynchronize()); drop_graph(c); gr_free(c); gr_free_log(c); }
+        return 0;
+    }
+    S2V_REQUIRE(phi && b >= 1 && b <= S2V_MAX_BATCH / 2, "s2v_set_guidance_rescale: phi values of 1 <= b <= 4 videos, or NULL with b = 0 to clear");
+    for (int k = 0; k < b; ++k)   // written so that NaN fails it
+        S2V_REQUIRE(phi[k] >= 0.f && phi[k] <= 1.f, "s2v_set_guidance_rescale: every phi must lie in [0, 1] (NaN is refused as well)");
+    S2V_REQUIRE(c->kind == S2V_CTX_MODEL, "s2v_set_guidance_rescale: attention-only contexts (S2V_CTX_ATTN_*) run no step");
+    S2V_REQUIRE(!c->shard, "s2v_set_guidance_rescale: a shard context (s2v_set_shard) has no rescaled step: the statistic spans the whole video, which no rank of a "
+                           "Ulysses group holds before the noise all-gather; guidance rescale runs on one GPU");
+    S2V_REQUIRE(c->ws, "s2v_set_guidance_rescale: call s2v_set_geometry first (the values belong to the geometry's videos)");
+    S2V_REQUIRE(c->B != 1, "s2v_set_guidance_rescale: a geometry with B = 1 runs no CFG (it is one sample of a CFG-parallel pair, and the split entries have no "
+                           "rescaled form): guidance rescale runs the CFG pairs or triples of b videos on one GPU");
+    S2V_REQUIRE(!c->win_acc, "s2v_set_guidance_rescale: temporal windows are set (s2v_set_windows): s2v_denoise_step_windows combines the windows before its one "
+                             "scheduler step, and a statistic per window is another feature");
+    S2V_REQUIRE((c->B % 2 == 0 && b == c->B / 2) || (c->B % 3 == 0 && b == c->B / 3),
+                "s2v_set_guidance_rescale: b must be the videos of the geometry (B / 2 for CFG pairs, B / 3 for subject-guidance triples)");
+    S2V_REQUIRE(c->cfg.in_channels == c->cfg.out_channels, "s2v_set_guidance_rescale: in/out channels must match");
+    bool any = false;
+    for (int k = 0; k < b; ++k) any = any || phi[k] != 0.f;
+    if (!any) {   // all zero arms nothing: the entries run the launches they ran (the log stays for a batch that arms again)
+        if (c->gr_buf) { S2V_CHECK_HIP(hipDeviceSynchronize()); drop_graph(c); gr_free(c); }
+        return 0;
+    }
+    S2V_CHECK_HIP(hipDeviceSynchronize());   // a step in flight may still read the values about to be replaced
+    if (!c->gr_buf || c->gr_b != b) {
+        drop_graph(c);
+        gr_free(c);
+        const int64_t part = rup((int64_t)b * cfg_stats_chunks(video_elems(c)) * 4 * 8, 256);
+        const int64_t bytes = part + (S2V_MAX_BATCH / 2) * (4 * 8 + 4 + 4);
+        S2V_CHECK_HIP(hipMalloc((void**)&c->gr_buf, bytes));
+        c->gr_partials = (double*)c->gr_buf; c->gr_sums = (double*)(c->gr_buf + part);
+        c->gr_factors = (float*)(c->gr_sums + (S2V_MAX_BATCH / 2) * 4); c->gr_phi = c->gr_factors + S2V_MAX_BATCH / 2;
+        S2V_CHECK_HIP(hipMemset(c->gr_buf + part, 0, bytes - part));
+        c->gr_bytes = bytes; c->gr_b = b;
+    }
+    if (!c->gr_log) {
+        const int64_t bytes = (int64_t)CFG_LOG_STEPS * CFG_LOG_COLS * 4 + 4;
+        S2V_CHECK_HIP(hipMalloc((void**)&c->gr_log, bytes));
+        S2V_CHECK_HIP(hipMemset(c->gr_log, 0, bytes));
+        c->gr_log_count = (unsigned*)(c->gr_log + CFG_LOG_STEPS * CFG_LOG_COLS); c->gr_log_bytes = bytes;
+    }
+    S2V_CHECK_HIP(hipMemcpy(c->gr_phi, phi, sizeof(float) * b, hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int s2v_guidance_rescale_read(s2v_ctx* c, double* sums, float* factors, float* log, int32_t* log_count) {
+    S2V_REQUIRE(c, "s2v_guidance_rescale_read: null context");
+    S2V_REQUIRE((!sums && !factors) || c->gr_buf, "s2v_guidance_rescale_read: sums and factors are those of an armed context (s2v_set_guidance_rescale with a non-zero phi)");
+    S2V_CHECK_HIP(hipDeviceSynchronize());
+    if (sums) S2V_CHECK_HIP(hipMemcpy(sums, c->gr_sums, sizeof(double) * 4 * c->gr_b, hipMemcpyDeviceToHost));
+    if (factors) S2V_CHECK_HIP(hipMemcpy(factors, c->gr_factors, sizeof(float) * c->gr_b, hipMemcpyDeviceToHost));
+    unsigned count = 0;
+    if (c->gr_log) S2V_CHECK_HIP(hipMemcpy(&count, c->gr_log_count, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (log && count) S2V_CHECK_HIP(hipMemcpy(log, c->gr_log, sizeof(float) * CFG_LOG_COLS * (count < CFG_LOG_STEPS ? count : CFG_LOG_STEPS), hipMemcpyDeviceToHost));
+    if (log_count) *log_count = (int32_t)count;
+    return 0;
+}
+
+// an armed step's two launches behind the forward: the statistics of the context's noise_pred on the b videos and their factors (logged)
+static int rescale_stats(s2v_ctx* c, int cfg, int b, hipStream_t st) {
+    CfgStatsArgs s{};
+    s.noise_pred = c->noise_pred; s.nvid = b; s.n_vid = video_elems(c); s.n = b * s.n_vid; s.cfg = cfg; s.coef = c->coef_dev; s.partials = c->gr_partials;
+    S2V_TRY(launch_cfg_stats(s, c->dtype, st));
+    CfgFinalArgs f{};
+    f.partials = c->gr_partials; f.chunks = cfg_stats_chunks(s.n_vid); f.nvid = b; f.n_vid = s.n_vid; f.phi = c->gr_phi; f.sums = c->gr_sums;
+    f.factors = c->gr_factors; f.log = c->gr_log; f.log_count = c->gr_log_count;
+    return launch_cfg_finalize(f, st);
+}
+
+extern "C" int s2v_op_cfg_stats(const void* noise_pred, int32_t flags, int32_t nvid, int64_t n_vid, const float* guidance, const float* guidance_subject,
+                                const float* phi, double* sums, float* factors, int32_t dtype, s2v_stream stream) {
+    S2V_REQUIRE(noise_pred && guidance && phi && sums && factors, "s2v_op_cfg_stats: null argument");
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_cfg_stats: unsupported dtype");
+    S2V_REQUIRE(((flags & 1) != 0) != ((flags & 8) != 0), "s2v_op_cfg_stats: flags bit0 (the CFG pair) or bit3 (the subject-guidance triple), exactly one of them");
+    S2V_REQUIRE(!(flags & 8) || guidance_subject, "s2v_op_cfg_stats: the triple needs guidance_subject");
+    S2V_REQUIRE(nvid >= 1 && nvid <= S2V_MAX_BATCH / 2 && n_vid >= 1, "s2v_op_cfg_stats: 1 <= nvid <= 4 videos of n_vid >= 1 elements");
+    for (int k = 0; k < nvid; ++k) S2V_REQUIRE(phi[k] >= 0.f && phi[k] <= 1.f, "s2v_op_cfg_stats: every phi must lie in [0, 1] (NaN is refused as well)");
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = cfg_stats_chunks(n_vid);
+    const int64_t part = rup((int64_t)nvid * chunks * 4 * 8, 256), coef_off = part + nvid * (4 * 8 + 4 + 4);
+    char* buf = nullptr;
+    S2V_CHECK_HIP(hipMalloc((void**)&buf, rup(coef_off, 16) + sizeof(SchedCoef) * nvid));
+    double* sums_dev = (double*)(buf + part);
+    float *factors_dev = (float*)(sums_dev + 4 * nvid), *phi_dev = factors_dev + nvid;
+    SchedCoef* coef_dev = (SchedCoef*)(buf + rup(coef_off, 16));
+    SchedCoef coefs[S2V_MAX_BATCH / 2] = {};
+    for (int k = 0; k < nvid; ++k) { coefs[k].guidance = guidance[k]; coefs[k].guidance_subject = guidance_subject ? guidance_subject[k] : 0.f; }
+    int r = 0;
+    auto hip = [&](hipError_t e) { if (e != hipSuccess && r == 0) r = s2v_fail(__FILE__, __LINE__, hipGetErrorString(e), -2); return e == hipSuccess; };
+    if (hip(hipMemcpy(coef_dev, coefs, sizeof(SchedCoef) * nvid, hipMemcpyHostToDevice)) && hip(hipMemcpy(phi_dev, phi, sizeof(float) * nvid, hipMemcpyHostToDevice))) {
+        CfgStatsArgs s{};
+        s.noise_pred = noise_pred; s.nvid = nvid; s.n_vid = n_vid; s.n = nvid * n_vid; s.cfg = (flags & 8) ? SCHED_CFG_TRIPLE : 1; s.coef = coef_dev;
+        s.np_f32 = (flags >> 1) & 1; s.partials = (double*)buf;
+        CfgFinalArgs f{};
+        f.partials = s.partials; f.chunks = chunks; f.nvid = nvid; f.n_vid = n_vid; f.phi = phi_dev; f.sums = sums_dev; f.factors = factors_dev;
+        r = launch_cfg_stats(s, dtype, st);
+        if (r == 0) r = launch_cfg_finalize(f, st);
+        if (r == 0 && hip(hipStreamSynchronize(st)) && hip(hipMemcpy(sums, sums_dev, sizeof(double) * 4 * nvid, hipMemcpyDeviceToHost)))
+            hip(hipMemcpy(factors, factors_dev, sizeof(float) * nvid, hipMemcpyDeviceToHost));
+    }
+    hipFree(buf);
+    return r;
 }
 
 static int step_launches(s2v_ctx* c, void* latents, float* x0_hist, const void* noise, hipStream_t st, int mode, uint64_t am, uint64_t sm, uint64_t lm) {
     // b videos: sample j of [negative x b | positive x b] embeds video j mod b straight from `latents` (one video: the stride of 0 it always had)
     const int b = c->B >= 2 ? c->B / 2 : 1;
     S2V_TRY(forward_impl(c, latents, b > 1 ? (int64_t)c->F * c->cfg.in_channels * c->H * c->W : 0, b > 1 ? b : 0, c->t_dev, c->noise_pred, st, mode, am, sm, lm));
-    return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b);
+    if (c->gr_buf) S2V_TRY(rescale_stats(c, 1, b, st));   // armed only on B >= 2 (s2v_set_guidance_rescale)
+    return sched_on_pair(c, latents, x0_hist, noise, c->B >= 2 ? 1 : 0, st, b, c->gr_buf ? c->gr_factors : nullptr);
 }
 
 // the whole step of b = B/2 videos (b = 1 for B = 1 or 2) at timesteps[b] and coefs[b]; s2v_denoise_step's wording serves both entries
@@ -2138,10 +2308,11 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
     S2V_REQUIRE(!c->shard, use_graph ? "s2v_denoise_step: hipGraph capture is not supported for a shard context (s2v_set_shard): its step is staged around "
                                        "the exchanges and runs eagerly (s2v_shard_step_* / s2v_denoise_step_ulysses)"
                                      : "s2v_denoise_step: a shard context (s2v_set_shard) runs the staged step (s2v_shard_step_* / s2v_denoise_step_ulysses)");
+    S2V_REQUIRE(!c->gr_buf || c->gr_b == b, "s2v_denoise_step: s2v_set_guidance_rescale set the values of another number of videos than this geometry's b = B/2");
     S2V_TRY(stage_step(c, timesteps, coefs, b, st));
     if (!use_graph) return am_done(c, am, sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode, am, sm, lm)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm;
+    key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm; key.rescale = c->gr_buf ? 1 : 0;
     return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode, am, sm, lm); })));
 }
 
@@ -2180,7 +2351,8 @@ static int masked_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const
     a.n = b * a.n_vid; a.cfg = 1; a.coef = c->coef_dev;
     a.z0 = c->blend_z0; a.noise0 = c->blend_noise0; a.mask = c->blend_mask;
     a.chw = c->cfg.out_channels * c->H * c->W; a.hw = c->H * c->W; a.mask_vid = c->F * a.hw; a.blend = c->blend_dev;
-    return launch_sched_step_masked(a, c->dtype, st);
+    if (c->gr_buf) S2V_TRY(rescale_stats(c, 1, b, st));   // over the whole video, kept cells included
+    return launch_sched_step_masked(a, c->dtype, st, c->gr_buf ? c->gr_factors : nullptr);
 }
 
 extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
@@ -2202,11 +2374,13 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_masked: s2v_set_blend has not set the blend operands of this geometry's b = B/2 videos");
     for (int k = 0; k < b; ++k) S2V_REQUIRE(coefs[k].kind == 0 || (noise && x0_hist), "s2v_denoise_step_masked: DPM needs noise and x0_hist");
     for (int k = 0; k < b; ++k) S2V_REQUIRE(blends[k].keep_max >= 0 && blends[k].keep_max <= 255, "s2v_denoise_step_masked: keep_max must be a level 0..255");
+    S2V_REQUIRE(!c->gr_buf || c->gr_b == b, "s2v_denoise_step_masked: s2v_set_guidance_rescale set the values of another number of videos than this geometry's b = B/2");
     hipStream_t st = (hipStream_t)stream;
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
     if (!use_graph) return am_done(c, am, sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode, am, sm, lm)));
     GraphKey key{latents, x0_hist, noise, -1};
     key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm;
+    key.rescale = c->gr_buf ? 1 : 0;
     return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode, am, sm, lm); })));
 }
 
@@ -2220,10 +2394,12 @@ static int guided_step_launches(s2v_ctx* c, void* latents, float* x0_hist, const
     a.noise_pred = c->noise_pred; a.latents_in = latents; a.latents_out = latents; a.x0_hist = x0_hist; a.noise = noise;
     a.nvid = b; a.n_vid = (int64_t)c->F * c->cfg.out_channels * c->H * c->W;
     a.n = b * a.n_vid; a.cfg = SCHED_CFG_TRIPLE; a.coef = c->coef_dev;
-    if (!masked) return launch_sched_step(a, c->dtype, st);
+    const float* factor = c->gr_buf ? c->gr_factors : nullptr;
+    if (factor) S2V_TRY(rescale_stats(c, SCHED_CFG_TRIPLE, b, st));   // f is the triple's f plane
+    if (!masked) return launch_sched_step(a, c->dtype, st, factor);
     a.z0 = c->blend_z0; a.noise0 = c->blend_noise0; a.mask = c->blend_mask;
     a.chw = c->cfg.out_channels * c->H * c->W; a.hw = c->H * c->W; a.mask_vid = c->F * a.hw; a.blend = c->blend_dev;
-    return launch_sched_step_masked(a, c->dtype, st);
+    return launch_sched_step_masked(a, c->dtype, st, factor);
 }
 
 extern "C" int s2v_denoise_step_guided(s2v_ctx* c, void* latents, const float* timesteps, const s2v_sched_coef* coefs, const s2v_blend* blends,
@@ -2252,12 +2428,13 @@ extern "C" int s2v_denoise_step_guided(s2v_ctx* c, void* latents, const float* t
         S2V_REQUIRE(c->blend_z0 && c->blend_b == b, "s2v_denoise_step_guided: s2v_set_blend has not set the blend operands of this geometry's b = B/3 videos");
         for (int k = 0; k < b; ++k) S2V_REQUIRE(blends[k].keep_max >= 0 && blends[k].keep_max <= 255, "s2v_denoise_step_guided: keep_max must be a level 0..255");
     }
+    S2V_REQUIRE(!c->gr_buf || c->gr_b == b, "s2v_denoise_step_guided: s2v_set_guidance_rescale set the values of another number of videos than this geometry's b = B/3");
     hipStream_t st = (hipStream_t)stream;
     const bool masked = blends != nullptr;
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
     if (!use_graph) return guided_step_launches(c, latents, x0_hist, noise, st, masked);
     GraphKey key{latents, x0_hist, noise, -1};
-    key.triple = 1;
+    key.triple = 1; key.rescale = c->gr_buf ? 1 : 0;
     if (masked) { key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; }
     return launch_captured(c, key, st, [&](hipStream_t s) { return guided_step_launches(c, latents, x0_hist, noise, s, masked); });
 }
@@ -2271,6 +2448,7 @@ extern "C" int s2v_set_windows(s2v_ctx* c, int32_t L, int32_t stride, int32_t pe
     }
     S2V_REQUIRE(c->kind == S2V_CTX_MODEL, "s2v_set_windows: attention-only contexts (S2V_CTX_ATTN_*) run no step");
     S2V_REQUIRE(!c->shard, "s2v_set_windows: a shard context (s2v_set_shard) has no windowed step: temporal windows run on one GPU");
+    S2V_REQUIRE(!c->gr_buf, "s2v_set_windows: guidance rescale is armed (s2v_set_guidance_rescale): the windowed step has no rescaled form");
     S2V_REQUIRE(c->ws, "s2v_set_windows: call s2v_set_geometry first (B = 2 per_forward samples of F = the window's frames)");
     S2V_REQUIRE(c->B != 1, "s2v_set_windows: a geometry with B = 1 is one sample of a CFG-parallel pair: the windowed step runs the CFG pairs of "
                            "per_forward windows, B = 2 per_forward, on one GPU");
@@ -2341,6 +2519,8 @@ extern "C" int s2v_denoise_step_windows(s2v_ctx* c, void* latents, float timeste
                                      "step runs several");
     S2V_REQUIRE(la_take_arm(c) == 0, "s2v_denoise_step_windows: local attention is armed (s2v_attn_local_arm): local attention runs one forward per step, a "
                                      "windowed step runs several");
+    S2V_REQUIRE(!c->gr_buf, "s2v_denoise_step_windows: guidance rescale is armed (s2v_set_guidance_rescale): the windows are combined before the one scheduler "
+                            "step, and a statistic per window is another feature");
     S2V_REQUIRE(c->win_acc, "s2v_denoise_step_windows: no temporal windows are set (s2v_set_windows): a plain geometry steps with s2v_denoise_step");
     S2V_REQUIRE(c->have_cond && !c->cond_triples, "s2v_denoise_step_windows: the conditioning must hold the CFG pairs [negative x per_forward | positive x per_forward] "
                                                   "(s2v_set_conditioning)");
@@ -2388,6 +2568,8 @@ extern "C" int s2v_denoise_split_begin(s2v_ctx* c, const void* latents, float ti
                                      "pair per rank: steering runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(la_take_arm(c) == 0, "s2v_denoise_split_begin: local attention is armed (s2v_attn_local_arm), and a CFG-parallel split holds one sample of the "
                                      "pair per rank: local attention runs on one GPU (s2v_denoise_step)");
+    S2V_REQUIRE(!c->gr_buf, "s2v_denoise_split_begin: guidance rescale is armed (s2v_set_guidance_rescale), and the CFG-parallel split entries have no rescaled "
+                            "form: guidance rescale runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(c->ws && c->B == 1, "s2v_denoise_split_begin: a geometry with B = 1 (one sample of the CFG pair per rank) is required; a batched call (several videos) runs on one GPU (s2v_denoise_step)");
     S2V_REQUIRE(!c->shard, "s2v_denoise_split_begin: CFG-parallel on a shard context is not supported");
     S2V_REQUIRE(slot == 0 || slot == 1, "s2v_denoise_split_begin: slot must be 0 (unconditional) or 1 (conditional)");

@@ -952,13 +952,11 @@ int launch_copy_rows(const void* src, int lds_, const void* add, int ldadd, void
 // SchedArgs instantiation is the kernel it was before the masked form existed, kernel arguments included.
 // TRIPLE (subject guidance, kernels.h): noise_pred is [3, n] = [u | r | f] and v = (u + g_subject * (r - u)) + g_text * (f - r), five roundings in
 // that association.  A compile-time policy: the two pair instantiations hold no branch for it and take the arguments they took.
-template <typename T, typename A, bool TRIPLE = false>
-__global__ void sched_step_k(const A a) {
+// The combine alone, element i of the planes: the guided prediction v as the step kernel uses it and as the statistics kernel of the guidance
+// rescale sums it (cfg_stats_k below) -- one function, so the two cannot drift
+template <typename T, bool TRIPLE, typename A>
+__device__ __forceinline__ float cfg_combine(const A& a, int64_t i, const SchedCoef& k) {
 #pragma clang fp contract(off)  // hipcc defaults to -ffp-contract=fast and __fmul_rn is a plain multiply in HIP
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // within video blockIdx.y
-    if (j >= a.n_vid) return;
-    const int64_t i = (int64_t)blockIdx.y * a.n_vid + j;
-    const SchedCoef k = a.coef ? a.coef[blockIdx.y] : a.cval;
     float v;
     if constexpr (TRIPLE) {
         float u, r, f;
@@ -983,6 +981,21 @@ __global__ void sched_step_k(const A a) {
             v = ET<T>::ld(np + i);
         }
     }
+    return v;
+}
+// RESCALE (guidance rescale, kernels.h): A carries the device factors of the videos, and v' = v * factor[video] is one more separately rounded
+// multiply ahead of the scheduler arithmetic.  A compile-time policy that the argument type carries (SchedRescaleArgs / SchedMaskRescaleArgs): the
+// instantiations on SchedArgs / SchedMaskArgs keep their names and arguments and hold no load or multiply for it.
+template <typename T, typename A, bool TRIPLE = false>
+__global__ void sched_step_k(const A a) {
+#pragma clang fp contract(off)  // hipcc defaults to -ffp-contract=fast and __fmul_rn is a plain multiply in HIP
+    constexpr bool RESCALE = std::is_same<A, SchedRescaleArgs>::value || std::is_same<A, SchedMaskRescaleArgs>::value;
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // within video blockIdx.y
+    if (j >= a.n_vid) return;
+    const int64_t i = (int64_t)blockIdx.y * a.n_vid + j;
+    const SchedCoef k = a.coef ? a.coef[blockIdx.y] : a.cval;
+    float v = cfg_combine<T, TRIPLE>(a, i, k);
+    if constexpr (RESCALE) v = __fmul_rn(v, a.factor[blockIdx.y]);
     const float x = ET<T>::ld((const T*)a.latents_in + i);
     const float x0 = __fsub_rn(ET<T>::rnd(__fmul_rn(x, k.c_x0_x)), __fmul_rn(k.c_x0_v, v));
     float prev;
@@ -995,7 +1008,7 @@ __global__ void sched_step_k(const A a) {
         prev = __fadd_rn(__fsub_rn(ET<T>::rnd(__fmul_rn(k.m1, x)), __fmul_rn(k.m2, d)), ET<T>::rnd(__fmul_rn(k.mn, nz)));
     }
     if (a.x0_hist) a.x0_hist[i] = x0;
-    if constexpr (std::is_same<A, SchedMaskArgs>::value) {
+    if constexpr (std::is_base_of<SchedMaskArgs, A>::value) {
         // the channel does not enter: element j of a video [F][C][hw] sits in cell j % hw of frame j / chw of the video's mask plane
         // (32-bit divisions: the launch requires a video of fewer than 2^31 elements)
         const unsigned ju = (unsigned)j, chw = (unsigned)a.chw, hw = (unsigned)a.hw;
@@ -1021,15 +1034,21 @@ static int sched_step_checks(const SchedArgs& a) {
     S2V_REQUIRE(a.cfg == 0 || a.cfg == 1 || a.cfg == SCHED_CFG_TRIPLE, "sched_step: cfg is 0 (one prediction), 1 (the CFG pair) or SCHED_CFG_TRIPLE (the subject-guidance triple)");
     return 0;
 }
-int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st) {
+int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st, const float* factor) {
     S2V_TRY(sched_step_checks(a));
     dim3 grid((unsigned)((a.n_vid + 255) / 256), (unsigned)a.nvid);
-    if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedArgs, true>), grid, dim3(256), 0, st, a)) }
+    if (factor) {   // the RESCALE form: the same arguments with the videos' factors behind them
+        SchedRescaleArgs r{};
+        static_cast<SchedArgs&>(r) = a; r.factor = factor;
+        if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedRescaleArgs, true>), grid, dim3(256), 0, st, r)) }
+        else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedRescaleArgs>), grid, dim3(256), 0, st, r)) }
+    }
+    else if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedArgs, true>), grid, dim3(256), 0, st, a)) }
     else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedArgs>), grid, dim3(256), 0, st, a)) }
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }
-int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st) {
+int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st, const float* factor) {
     S2V_TRY(sched_step_checks(a));
     S2V_REQUIRE(a.z0 && a.noise0 && a.mask, "sched_step_masked: z0, noise0 and the latent mask are required");
     S2V_REQUIRE(a.blend || a.nvid == 1, "sched_step_masked: several videos take their blend records from device memory");
@@ -1037,8 +1056,99 @@ int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st) 
                 "sched_step_masked: a video is [F][C][H * W] elements over a mask plane of [F][H * W] cells");
     S2V_REQUIRE(a.n_vid < ((int64_t)1 << 31) && a.mask_vid == a.n_vid / a.chw * a.hw, "sched_step_masked: a video of fewer than 2^31 elements, mask_vid = F * H * W cells");
     dim3 grid((unsigned)((a.n_vid + 255) / 256), (unsigned)a.nvid);
-    if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskArgs, true>), grid, dim3(256), 0, st, a)) }
+    if (factor) {
+        SchedMaskRescaleArgs r{};
+        static_cast<SchedMaskArgs&>(r) = a; r.factor = factor;
+        if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskRescaleArgs, true>), grid, dim3(256), 0, st, r)) }
+        else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskRescaleArgs>), grid, dim3(256), 0, st, r)) }
+    }
+    else if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskArgs, true>), grid, dim3(256), 0, st, a)) }
     else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((sched_step_k<T, SchedMaskArgs>), grid, dim3(256), 0, st, a)) }
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Guidance rescale (kernels.h; include/s2v_hip.h has the definition): the statistics of a video's text-conditioned prediction f and of its guided
+// prediction v, ahead of the step kernel that multiplies v by the video's factor.
+// cfg_stats_k: workgroup (chunk c, video blockIdx.y) owns the elements [c * CFG_STATS_CHUNK, min(n_vid, (c + 1) * CFG_STATS_CHUNK)) of its video.
+// Thread t adds its elements c * CFG_STATS_CHUNK + t + 256 r, r = 0, 1, ... ascending, into four fp64 accumulators that start from +0 (f, f * f,
+// v, v * v: the fp32 values widened first, so every square is exact); the 256 thread sums then meet in LDS in the halving tree
+// acc[t] += acc[t + s], s = 128, 64, ..., 1, and thread 0 stores the chunk's quadruple.  Nothing depends on the grid or on timing: no atomics.
+template <typename T, bool TRIPLE>
+__global__ __launch_bounds__(256) void cfg_stats_k(const CfgStatsArgs a) {
+#pragma clang fp contract(off)  // every fp64 add and multiply rounds on its own, as the restatements do
+    __shared__ double red[4][256];
+    const int t = threadIdx.x;
+    const int64_t lo = (int64_t)blockIdx.x * CFG_STATS_CHUNK;
+    const int64_t hi = lo + CFG_STATS_CHUNK < a.n_vid ? lo + CFG_STATS_CHUNK : a.n_vid;
+    const SchedCoef k = a.coef ? a.coef[blockIdx.y] : a.cval;
+    double sf = 0.0, sff = 0.0, sv = 0.0, svv = 0.0;
+    for (int64_t j = lo + t; j < hi; j += 256) {
+        const int64_t i = (int64_t)blockIdx.y * a.n_vid + j;
+        const int64_t fi = (TRIPLE ? 2 : 1) * a.n + i;   // the positive half of a pair, the f plane of a triple
+        const double f = a.np_f32 ? (double)((const float*)a.noise_pred)[fi] : (double)ET<T>::ld((const T*)a.noise_pred + fi);
+        const double v = (double)cfg_combine<T, TRIPLE>(a, i, k);
+        sf = sf + f; sff = sff + f * f; sv = sv + v; svv = svv + v * v;
+    }
+    red[0][t] = sf; red[1][t] = sff; red[2][t] = sv; red[3][t] = svv;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (t < s)
+            for (int q = 0; q < 4; ++q) red[q][t] = red[q][t] + red[q][t + s];
+        __syncthreads();
+    }
+    if (t < 4) a.partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + t] = red[t][0];
+}
+// cfg_finalize_k: one workgroup; thread k < nvid adds video k's chunk quadruples in ascending chunk order (from +0), stores the four sums and
+// derives the factor in fp64 (include/s2v_hip.h); threads 0 .. CFG_LOG_COLS - 1 append the row of factors (0 past nvid) to the log at the
+// device-side count, which thread 0 then advances with a plain store -- the launches of a stream are ordered, and a graph replay logs too.
+__global__ __launch_bounds__(64) void cfg_finalize_k(const CfgFinalArgs a) {
+#pragma clang fp contract(off)
+    const int k = threadIdx.x;
+    float factor = 0.f;
+    if (k < a.nvid) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        const double* p = a.partials + (int64_t)k * a.chunks * 4;
+        for (int c = 0; c < a.chunks; ++c)
+            for (int q = 0; q < 4; ++q) s[q] = s[q] + p[c * 4 + q];
+        for (int q = 0; q < 4; ++q) a.sums[k * 4 + q] = s[q];
+        const double phi = (double)a.phi[k], n = (double)a.n_vid;
+        factor = 1.0f;
+        if (phi != 0.0 && a.n_vid >= 2) {
+            const double std_f = sqrt((s[1] - s[0] * s[0] / n) / (n - 1.0));
+            const double std_v = sqrt((s[3] - s[2] * s[2] / n) / (n - 1.0));
+            if (isfinite(std_v) && std_v != 0.0) {
+                const double q = std_f / std_v;
+                if (isfinite(q)) factor = (float)(phi * q + (1.0 - phi));
+            }
+        }
+        a.factors[k] = factor;
+    }
+    if (a.log) {
+        const unsigned step = *a.log_count;
+        if (k < CFG_LOG_COLS && step < CFG_LOG_STEPS) a.log[step * CFG_LOG_COLS + k] = factor;
+        __syncthreads();
+        if (k == 0) *a.log_count = step + 1;
+    }
+}
+int cfg_stats_chunks(int64_t n_vid) { return (int)((n_vid + CFG_STATS_CHUNK - 1) / CFG_STATS_CHUNK); }
+int launch_cfg_stats(const CfgStatsArgs& a, int dtype, hipStream_t st) {
+    S2V_REQUIRE(a.noise_pred && a.partials, "cfg_stats: null argument");
+    S2V_REQUIRE(a.nvid >= 1 && a.n_vid >= 1 && (int64_t)a.nvid * a.n_vid == a.n, "cfg_stats: n must be nvid videos of n_vid elements");
+    S2V_REQUIRE(a.coef || a.nvid == 1, "cfg_stats: several videos take their coefficient sets from device memory");
+    S2V_REQUIRE(a.cfg == 1 || a.cfg == SCHED_CFG_TRIPLE, "cfg_stats: cfg is 1 (the CFG pair) or SCHED_CFG_TRIPLE (the subject-guidance triple): one prediction has no guided form");
+    dim3 grid((unsigned)cfg_stats_chunks(a.n_vid), (unsigned)a.nvid);
+    if (a.cfg == SCHED_CFG_TRIPLE) { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((cfg_stats_k<T, true>), grid, dim3(256), 0, st, a)) }
+    else { S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL((cfg_stats_k<T, false>), grid, dim3(256), 0, st, a)) }
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int launch_cfg_finalize(const CfgFinalArgs& a, hipStream_t st) {
+    S2V_REQUIRE(a.partials && a.phi && a.sums && a.factors, "cfg_finalize: null argument");
+    S2V_REQUIRE(a.nvid >= 1 && a.nvid <= CFG_LOG_COLS && a.n_vid >= 1 && a.chunks == cfg_stats_chunks(a.n_vid), "cfg_finalize: 1..4 videos of n_vid elements in the chunks of cfg_stats");
+    S2V_REQUIRE(!a.log == !a.log_count, "cfg_finalize: the log and its count go together");
+    hipLaunchKernelGGL(cfg_finalize_k, dim3(1), dim3(64), 0, st, a);
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

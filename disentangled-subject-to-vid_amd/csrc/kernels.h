@@ -462,7 +462,7 @@ struct SchedArgs {
     int np_f32;               // noise_pred is fp32 (the scheduler-object seam: model_output after .float())
     int out_f32;              // latents_out is fp32 and un-rounded (scheduler.step's return value)
 };
-int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st);
+int launch_sched_step(const SchedArgs& a, int dtype, hipStream_t st, const float* factor = nullptr);   // factor: the RESCALE form (below)
 // Masked video-to-video (pipeline_stable_diffusion_inpaint.py:1271-1285, the 4-channel branch, as a select): after the step has produced
 // `prev` rounded to T, an element whose latent cell has mask 0 is overwritten -- with add_noise(z0, noise0) at the video's NEXT timestep
 // (add_noise_k's arithmetic: rnd(rnd(sqrt_a * z0) + rnd(sqrt_1ma * noise0))), or on the video's last step with z0's own bits.  x0_hist
@@ -485,7 +485,35 @@ struct SchedMaskArgs : SchedArgs {     // latents_out is T (out_f32 is refused)
     const SchedBlend* blend;   // device pointer to nvid consecutive records, or null => use bval (nvid = 1)
     SchedBlend bval;
 };
-int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st);
+int launch_sched_step_masked(const SchedMaskArgs& a, int dtype, hipStream_t st, const float* factor = nullptr);
+// Guidance rescale (include/s2v_hip.h has the definition and the order of the sums).  Three launches on one stream: cfg_stats_k, one workgroup per
+// (chunk of CFG_STATS_CHUNK elements, video) writing the fp64 quadruple (sum f, sum f^2, sum v, sum v^2) of its chunk, v formed by the step
+// kernel's own combine; cfg_finalize_k, adding a video's quadruples in chunk order, deriving the fp32 factor and appending it to the log; and
+// the RESCALE form of sched_step_k, whose arguments are the step's with the device factors behind them: v' = v * factor[video], one more rounding.
+enum { CFG_STATS_CHUNK = 4096, CFG_LOG_STEPS = 1024, CFG_LOG_COLS = 4 };   // CFG_LOG_COLS = S2V_MAX_BATCH / 2
+struct SchedRescaleArgs : SchedArgs { const float* factor; };           // [nvid] fp32, device
+struct SchedMaskRescaleArgs : SchedMaskArgs { const float* factor; };
+struct CfgStatsArgs {
+    const void* noise_pred;   // [2, n] or [3, n] as SchedArgs::noise_pred; model dtype, or fp32 with np_f32
+    int64_t n; int cfg;       // 1 or SCHED_CFG_TRIPLE
+    int nvid; int64_t n_vid;
+    const SchedCoef* coef;    // device pointer to nvid consecutive sets (guidance, guidance_subject), or null => cval (nvid = 1)
+    SchedCoef cval;
+    int np_f32;
+    double* partials;         // [nvid][cfg_stats_chunks(n_vid)][4] fp64, device
+};
+struct CfgFinalArgs {
+    const double* partials; int chunks;
+    int nvid; int64_t n_vid;
+    const float* phi;         // [nvid] fp32, device
+    double* sums;             // [nvid][4] fp64, device: sum f, sum f^2, sum v, sum v^2
+    float* factors;           // [nvid] fp32, device
+    float* log;               // [CFG_LOG_STEPS][CFG_LOG_COLS] fp32, device, or null: row *log_count takes the factors (0 past nvid) while it is < CFG_LOG_STEPS
+    unsigned* log_count;      // device: advanced by every launch
+};
+int cfg_stats_chunks(int64_t n_vid);
+int launch_cfg_stats(const CfgStatsArgs& a, int dtype, hipStream_t st);
+int launch_cfg_finalize(const CfgFinalArgs& a, hipStream_t st);
 // Temporal windows (include/s2v_hip.h): a long latent of L frames [L][chw] is denoised as W = (L - F) / s + 1 windows of F frames, window k over
 // frames [k s, k s + F), and the windows' predictions are averaged where they overlap.  One launch takes the forward of the wb windows
 // k0 .. k0 + wb - 1, noise_pred [negative x wb | positive x wb] of [F][chw] each, and adds them into the fp32 plane:

@@ -687,6 +687,40 @@ class S2VEngine:
             _lib.check(_lib.lib().s2v_set_blend(self._h, None, None, None, 0))
             self._blend = None
 
+    # ---- guidance rescale (include/s2v_hip.h: s2v_set_guidance_rescale, s2v_guidance_rescale_read) ------------------------------------------
+    def set_guidance_rescale(self, phi):
+        """phi in [0, 1] for the videos of the geometry (B/2, or B/3 under set_conditioning_triples): a float for all of them or a sequence with
+        one entry per video; None clears (the factor log goes too).  Armed (any phi > 0), every denoise_step scales each video's guided
+        prediction by k = phi * std(f) / std(v) + 1 - phi before the scheduler arithmetic; all zero arms nothing.  The values live in device
+        memory: new values for the same videos keep a captured step.  set_geometry disarms (the log stays)"""
+        if phi is None:
+            _lib.check(_lib.lib().s2v_set_guidance_rescale(self._h, None, 0))
+            return
+        if self.geometry is None:
+            raise _lib.S2VError("set_guidance_rescale: call set_geometry first (the values belong to the geometry's videos)")
+        B = self.geometry[0]
+        b = B // 3 if self.triples else max(B // 2, 1)
+        vals = [float(p) for p in _per_video("guidance_rescale", phi, b)]
+        _lib.check(_lib.lib().s2v_set_guidance_rescale(self._h, (ctypes.c_float * b)(*vals), b))
+
+    def guidance_rescale_read(self, log_only=False):
+        """{"sums": [b][4] fp64 (sum f, sum f^2, sum v, sum v^2) and "factors": [b] of the last armed step (left out with log_only, or when
+        nothing is armed), "log": the factor rows [steps][4] of every armed step since the log was allocated (columns past the step's videos
+        are 0), "count": the steps logged}.  Synchronises the device"""
+        n = ctypes.c_int32()
+        log = (ctypes.c_float * (_lib.CFG_LOG_STEPS * _lib.CFG_LOG_COLS))()
+        _lib.check(_lib.lib().s2v_guidance_rescale_read(self._h, None, None, log, ctypes.byref(n)))
+        rows = min(n.value, _lib.CFG_LOG_STEPS)
+        out = {"log": [[log[r * _lib.CFG_LOG_COLS + k] for k in range(_lib.CFG_LOG_COLS)] for r in range(rows)], "count": n.value}
+        if not log_only and self.geometry is not None:
+            B = self.geometry[0]
+            b = B // 3 if self.triples else max(B // 2, 1)
+            sums, factors = (ctypes.c_double * (4 * b))(), (ctypes.c_float * b)()
+            if _lib.lib().s2v_guidance_rescale_read(self._h, sums, factors, None, None) == 0:   # refused: nothing is armed
+                out["sums"] = [[sums[4 * k + q] for q in range(4)] for k in range(b)]
+                out["factors"] = [factors[k] for k in range(b)]
+        return out
+
     def denoise_step(self, latents, timestep, coef, x0_hist=None, noise=None, use_graph=False, blend=None, cache=None, attn_layers=None, subject=False,
                      steer_layers=None, local_layers=None):
         """one iteration of the denoise loop, latents [b,F,C,H,W] (model dtype) updated in place: b = B/2 videos of a geometry of B = 2b samples

@@ -755,7 +755,7 @@ class S2VPipeline:
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), cfg_parallel=None, ulysses=None,
                  video=None, strength=0.8, num_videos_per_prompt=1, mask=None, paste_back=True, step_cache=None, change_map=None,
                  attention_map=None, subject_guidance_scale=None, negative_ref_img_states=None, temporal_windows=None, attention_steer=None,
-                 local_attention=None):
+                 local_attention=None, guidance_rescale=0.0):
         """Several videos per call (custom_cogvideox_pipe.py:126-219): prompt_embeds / negative_prompt_embeds [P,T,dim] and num_videos_per_prompt
         make b = P * num_videos_per_prompt <= 4 videos, prompt-major; ref_img_states has b rows (video k takes row k) or, beyond the reference,
         one row shared by all; latents [b,...]; generator may be a list of b generators (video k's initial latents and DPM noise come from
@@ -835,8 +835,22 @@ class S2VPipeline:
         both schedulers, runtime LoRA on bf16 and several videos per call with scalars (one table shared by all).  After the call
         `local_attention_report` holds {"steps", "layers", "frames", "visited_tile_share"}.  Refused with attention_map=, attention_steer=,
         step_cache=, subject_guidance_scale=, temporal_windows=, cfg_parallel=, ulysses=, fused=False, per-video lists, several input videos,
-        fp16 and fp8 engines.  No window, layer or step is recommended."""
+        fp16 and fp8 engines.  No window, layer or step is recommended.
+        guidance_rescale: phi in [0, 1] -- a float, or a list with one entry per video (prompt-major; a list makes the call a per-video call as
+        the other lists do).  Every step scales each video's guided prediction v by ONE factor k = phi * std(f) / std(v) + (1 - phi) before the
+        scheduler arithmetic, f the video's text-conditioned prediction (the triple's f under subject_guidance_scale=), both deviations over
+        all of the video's elements (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4; diffusers'
+        rescale_noise_cfg blends element by element, which is the same value with more roundings).  The statistics are a deterministic
+        device-side reduction behind the forward, inside the captured step; use_dynamic_cfg: they see the step's current scale.  0.0 is
+        exactly the call without the argument.  Composes with video= / strength, mask=, change_map= (the statistics cover the whole video),
+        paste_back, use_graph, both schedulers, the three dtypes, several videos per call and per-video lists, subject_guidance_scale=,
+        step_cache= (reuse steps included), attention_map=, attention_steer=, local_attention=, runtime LoRA and the fp8 weight formats.
+        After the call `guidance_rescale_report` holds {"phi": [b], "factors": [steps][b]} in the caller's order (None for a video whose plan
+        has ended; 1.0 where phi is 0), read once after the loop from the device log.  Refused with temporal_windows=, cfg_parallel=,
+        ulysses=, fused=False and values outside [0, 1].  No value is recommended."""
         self.step_cache_report = None
+        self.guidance_rescale_report = None
+        self.check_guidance_rescale(guidance_rescale, None, temporal_windows, cfg_parallel, ulysses, fused)   # refused before anything is encoded
         self.attention_maps = None
         self.attention_steer_report = None
         self.local_attention_report = None
@@ -861,7 +875,7 @@ class S2VPipeline:
             mask = change_map
         if mask is not None and video is None:
             self.check_mask(mask, None, 1, what=what)
-        per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength, subject_guidance_scale))
+        per_video = any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength, subject_guidance_scale, guidance_rescale))
         if subject_guidance_scale is not None:
             self.check_subject(subject_guidance_scale, guidance_scale, cfg_parallel, ulysses, step_cache, attention_map, fused)
         elif negative_ref_img_states is not None:
@@ -919,6 +933,7 @@ class S2VPipeline:
         if subject_guidance_scale is not None:
             sgs = self.check_subject_batch(b, subject_guidance_scale, negative_ref_img_states, ref_img_states)
             subject = torch.zeros_like(ref_img_states[:1]) if negative_ref_img_states is None else negative_ref_img_states
+        rescale = self.check_guidance_rescale(guidance_rescale, b, temporal_windows, cfg_parallel, ulysses, fused)   # [b] phi, or None: the call without it
         own_plans = per_video or (video is not None and b > 1)   # every video on the plan of its own one-video call
         per = [(guidance_scale, num_inference_steps, strength, sgs[0])]   # a call with scalars: one plan, built once and shared by all b videos
         if own_plans:
@@ -930,7 +945,7 @@ class S2VPipeline:
             return self._denoise(plans if own_plans else plans * b, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width,
                                  num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                                  callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
-                                 step_cache, attention_map, subject=subject)
+                                 step_cache, attention_map, subject=subject, rescale=rescale)
         if windows is not None:
             return self._denoise(plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator,
                                  latents, output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs,
@@ -940,12 +955,12 @@ class S2VPipeline:
                              num_frames, generator, latents, output_type, return_dict, fused, use_graph, callback_on_step_end,
                              callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video, num_videos_per_prompt, mask, paste_back, levels,
                              step_cache, attention_map, steer=attention_steer,
-                             local=None if local_attention is None else (local_attention, la_layers))
+                             local=None if local_attention is None else (local_attention, la_layers), rescale=rescale)
 
     def _denoise(self, plans, own_plans, prompt_embeds, negative_prompt_embeds, ref_img_states, height, width, num_frames, generator, latents,
                  output_type, return_dict, fused, use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs, cfg_parallel, ulysses, video,
                  num_videos_per_prompt, mask, paste_back, levels, step_cache, attention_map, subject=None, windows=None, steer=None,
-                 local=None):
+                 local=None, rescale=None):
         """the one denoise loop: b = len(plans) videos, each on its video_plan; iteration i applies step i of every video that still has one.
         The videos are held longest plan first (plan_order), so the unfinished ones are a prefix of the latents, x0 history and noise buffers;
         when the shortest plans end the batch shrinks to that prefix (geometry, tables and conditioning of the active rows) and the finished
@@ -965,7 +980,10 @@ class S2VPipeline:
         steer: a steered call (None: every other call, which touches no steer entry) -- its AttentionSteer, checked; scalars only, so the batch
         never shrinks and the one geometry holds for the whole call
         local: a call with local attention (None: every other call, which touches no local entry) -- (its LocalAttention, the checked layer list);
-        scalars only as well"""
+        scalars only as well
+        rescale: a call with guidance rescale (None: every other call, which touches no rescale entry) -- phi of the b videos in the caller's
+        order, not all zero.  The values follow the internal order and the shrinking prefix: every set_active sets those of the active videos
+        again (the library disarms with each new geometry), the log is cleared on entry and read once after the loop"""
         tr, sch = self.transformer, self.scheduler
         eng, dt, dev = tr.engine, tr.dtype, tr.device
         b = len(plans)
@@ -1044,6 +1062,8 @@ class S2VPipeline:
                 eng.set_windows(windows["L"], windows["s"], windows["weights"], windows["per_forward"])
             if mask is not None:   # prefixes of the same buffers, as latents[:a] is
                 eng.set_blend(z0[:a], noise0[:a], lat_mask[:a])
+            if rescale is not None:
+                eng.set_guidance_rescale([rescale[k] for k in order[:a]])
 
         if ulysses is not None and cfg_parallel is not None:
             raise ValueError("ulysses and cfg_parallel do not compose yet: a Ulysses group runs both samples of the CFG pair on every rank")
@@ -1057,6 +1077,9 @@ class S2VPipeline:
         if cfg_parallel is not None:  # both ranks compute from the same inputs or the video is garbage: checked once, collectively
             cfg_parallel.assert_same(latents=latents, ref_img_states=ref, text=text)
         x0_hist = noise = None
+        if rescale is not None:
+            eng.set_guidance_rescale(None)   # a fresh factor log for this call
+        gr_steps = []   # the active videos of every step run, for the report
         if fused:
             set_active(b)
             if is_dpm:
@@ -1118,6 +1141,7 @@ class S2VPipeline:
                     if fused:
                         set_active(a)
                 steps = [plans[order[p]]["steps"][i] for p in range(a)]
+                gr_steps.append(a)
                 for p, st in enumerate(steps):
                     last_t[p] = st["t"]
                 if own_plans:   # a finished video keeps its last value
@@ -1208,7 +1232,11 @@ class S2VPipeline:
                     negative_prompt_embeds = outs.get("negative_prompt_embeds", negative_prompt_embeds)
             if attention_map is not None:
                 self.attention_maps = self._read_attention_maps(eng, attention_map, b, am_ran, am_skipped)
+            if rescale is not None:
+                self.guidance_rescale_report = self.guidance_rescale_rows(rescale, order, gr_steps, eng.guidance_rescale_read(log_only=True)["log"])
         finally:
+            if rescale is not None:
+                eng.set_guidance_rescale(None)
             if windows is not None:
                 eng.clear_windows()
             if fused and mask is not None:
@@ -1222,6 +1250,47 @@ class S2VPipeline:
             if la_table and eng.geometry is not None:
                 eng.attn_local_enable(False)
         return self._finish(callers(latents), fused, output_type, return_dict, paste)
+
+    @staticmethod
+    def check_guidance_rescale(gr, b, temporal_windows=None, cfg_parallel=None, ulysses=None, fused=True):
+        """`guidance_rescale` as the phi of the b videos, or None when every value is 0 (the call without the argument); a list must have b
+        entries once b is known (b = None before that: a list is only checked for its values)"""
+        vals = list(gr) if isinstance(gr, (list, tuple)) else [gr]
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) <= 1.0:   # NaN fails the comparison
+                raise ValueError(f"`guidance_rescale` must be a float in [0, 1] or a list of them, one per video, got {gr!r}")
+        if isinstance(gr, (list, tuple)) and b is not None and len(vals) != b:
+            raise ValueError(f"`guidance_rescale` is a list of {len(vals)} entries for {b} videos: one per video, prompt-major")
+        if not isinstance(gr, (list, tuple)):
+            vals = vals * (b or 1)
+        if not any(float(v) != 0.0 for v in vals):
+            return None
+        if temporal_windows is not None:
+            raise ValueError("`guidance_rescale` together with `temporal_windows`: the windows are combined before the one scheduler step, and a "
+                             "statistic per window is another feature")
+        if cfg_parallel is not None:
+            raise ValueError("`guidance_rescale` together with `cfg_parallel`: the split step has no rescaled form; guidance rescale runs on one GPU")
+        if ulysses is not None:
+            raise ValueError("`guidance_rescale` together with `ulysses`: no rank holds the whole video's prediction before the gather; guidance "
+                             "rescale runs on one GPU")
+        if not fused:
+            raise ValueError("`guidance_rescale` runs inside the fused step; fused=False is the reference's seam sequence")
+        return [float(v) for v in vals]
+
+    @staticmethod
+    def guidance_rescale_rows(phi, order, active, log):
+        """the report of a call: phi [b] in the caller's order, `order` the internal order (position p holds caller's video order[p]), active[i]
+        the videos step i ran (a prefix of the internal order), log the device's factor rows, one per ARMED step (a step whose active videos
+        all have phi = 0 launches nothing and logs nothing).  factors[i][k]: video k's factor at step i -- None once its plan has ended"""
+        rows, r = [], 0
+        for a in active:
+            armed = any(phi[order[p]] != 0.0 for p in range(a))
+            row = [None] * len(phi)
+            for p in range(a):
+                row[order[p]] = float(log[r][p]) if armed else 1.0
+            r += armed
+            rows.append(row)
+        return {"phi": list(phi), "factors": rows}
 
     @staticmethod
     def _read_attention_maps(eng, am, b, steps, skipped):

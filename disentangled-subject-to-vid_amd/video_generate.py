@@ -46,7 +46,7 @@ def prompt_embeddings(text_encoder, input_ids, dtype=None):
 def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_ids, height=480, width=720, num_frames=49,
               num_inference_steps=50, guidance_scale=6.0, use_dynamic_cfg=False, seed=None, latents=None, output_type="np",
               video_uint8=None, strength=0.8, mask_uint8=None, paste_back=True, change_map_uint8=None, attention_map=None, subject_guidance_scale=None,
-              temporal_windows=None, attention_steer=None, local_attention=None, **pipe_kwargs):
+              temporal_windows=None, attention_steer=None, local_attention=None, guidance_rescale=0.0, **pipe_kwargs):
     """Returns the frames [F, H, W, 3] float32 in [0, 1] (what the reference hands to export_to_video), or whatever
     `output_type` selects ("latent" / "pt").  A batch of prompt ids [P, T] (with num_videos_per_prompt through **pipe_kwargs: up to four
     videos per call) shares the one reference image and returns one video per row, [b, F, H, W, 3].
@@ -87,6 +87,9 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
     comes through **pipe_kwargs.  (The reference's `local_reference_scale` is NOT this: the reference passes that name on and never reads
     it, so it has no meaning to follow.)
 
+    Guidance rescale: guidance_rescale (phi in [0, 1]: a float, or a list with one entry per video) is passed through to
+    S2VPipeline.__call__; the factors of every step are in pipe.guidance_rescale_report after the call.  0.0 passes nothing.
+
     Long videos: temporal_windows=TemporalWindows(window_frames, stride_frames, weighting, per_forward) is passed through to
     S2VPipeline.__call__; num_frames (or the input video's frame count) may then exceed 49 and the result has that many frames.
 
@@ -105,6 +108,8 @@ def inference(pipe, text_encoder, ref_image_uint8, prompt_ids, negative_prompt_i
         pipe_kwargs = dict(pipe_kwargs, temporal_windows=temporal_windows)
     if subject_guidance_scale is not None:
         pipe_kwargs = dict(pipe_kwargs, subject_guidance_scale=subject_guidance_scale)
+    if isinstance(guidance_rescale, (list, tuple)) or guidance_rescale != 0.0:   # 0.0: the call as it is without the argument
+        pipe_kwargs = dict(pipe_kwargs, guidance_rescale=guidance_rescale)
     if attention_map is not None:
         pipe_kwargs = dict(pipe_kwargs, attention_map=attention_map)
     if video_uint8 is not None:

@@ -258,6 +258,7 @@ typedef struct s2v_sched_coef {
  *             five operations that each round on their own, in this association.  guidance_subject = 1 is the pair's r + g (f - r)
  *             mathematically, and a u plane that holds the r plane's bits gives the pair's result bit for bit for ANY guidance_subject
  *             (r - u = +0).  Bit0 and bit3 together are refused.
+ *       bit4: the RESCALE form (guidance rescale, below): refused here by name -- the device factor rides in s2v_sched_step_rescale.
  * latents in/out [n] (may alias); x0_hist fp32 [n] (DPM: read as old x0, then overwritten; may be NULL for DDIM);
  * noise [n] in `dtype` (DPM only). */
 S2V_API int s2v_sched_step(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags,
@@ -393,6 +394,62 @@ S2V_API int s2v_last_noise_pred(s2v_ctx* ctx, void** dev_ptr);
 S2V_API int s2v_set_windows(s2v_ctx* ctx, int32_t L, int32_t stride, int32_t per_forward, const float* weights);
 S2V_API int s2v_denoise_step_windows(s2v_ctx* ctx, void* latents, float timestep, const s2v_sched_coef* coef_host, float* x0_hist,
                                      const void* noise, int32_t use_graph, s2v_stream stream);
+
+/* ---- Guidance rescale: the guided prediction scaled back to the spread of the text-conditioned one, per video ---------------------------------
+ * (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4; diffusers' rescale_noise_cfg,
+ * pipelines/stable_diffusion/pipeline_stable_diffusion.py:67-90.)  THE DEFINITION -- kernels and tests restate it.  For video k of a step:
+ *   n      = F C H W elements
+ *   f      its text-conditioned prediction as fp32: the positive half of a pair, the f plane of a triple
+ *   v      its guided prediction exactly as the step combines it (s2v_sched_step flags bit0 / bit3: the same separately rounded fp32 operations)
+ *   phi_k  in [0, 1]
+ * Four sums in fp64 over the fp32 values widened to fp64 (so every square is exact), each add rounding on its own:
+ *   Sf = sum f    Sff = sum f^2    Sv = sum v    Svv = sum v^2
+ * in THIS order, whatever the grid, the CU count or the timing (no floating-point atomics).  The video is cut into chunks of
+ * S2V_CFG_STATS_CHUNK = 4096 consecutive elements (the last one may be short).  Within chunk c, lane t of 256 adds its elements
+ * c 4096 + t + 256 r for r = 0, 1, ... in ascending r, starting from +0; the 256 lane sums meet in the halving tree
+ * lane[t] = lane[t] + lane[t + s] for t < s, s = 128, 64, ..., 1; lane[0] is the chunk's sum.  The video's sum adds the chunk sums in ascending
+ * c, starting from +0.
+ * Deviations with n - 1 in the divisor, as torch.std:    std_x = sqrt((Sxx - Sx Sx / n) / (n - 1))     (fp64, every operation rounding on its own)
+ * The factor, in fp64, rounded once to fp32:              k = float(phi (std_f / std_v) + (1 - phi))
+ * k = 1.0f exactly when phi == 0, when n < 2, when std_v is not finite (an inf or NaN anywhere in v), when std_v == 0, or when the quotient is
+ * not finite.  (A constant v has std_v == 0 exactly only where its sums are exact in fp64 -- small dyadic constants; the cancellation in
+ * Sxx - Sx Sx / n is the textbook one; fp64 sums over fp32 data keep it harmless unless the mean dwarfs the deviation.)
+ * The rescaled prediction is one more separately rounded fp32 multiply ahead of the scheduler arithmetic:    v' = v k
+ * A DELIBERATE DIFFERENCE from diffusers, which computes phi (v std_f / std_v) + (1 - phi) v element by element: one factor per video is the same
+ * value mathematically with fewer roundings.  The statistics cover the whole video, on a masked or change-map step too, as the reference's do.
+ *
+ * s2v_set_guidance_rescale: context state, like the blend operands.  phi: HOST array of b values for the b videos of the geometry (B = 2b pairs, or
+ * B = 3b triples).  The values live in device memory: new values for the same b re-capture nothing.  A first arming allocates, beside the
+ * workspace, the chunk partials [b][ceil(n / 4096)][4] fp64 with the sums, factors and phi behind them, and the factor log; s2v_device_bytes
+ * COUNTS both as workspace while the context is armed, and neither otherwise.  All values zero: nothing is armed -- the partials are freed, every step entry runs
+ * the launches it ran and returns the bytes it returned; the log is kept (a shrinking batch may arm again).  phi = NULL with b = 0 clears: the
+ * log is freed too and s2v_device_bytes reports what it reports without this feature.  s2v_set_geometry (the same geometry included) and
+ * s2v_set_shard disarm as all-zero values do.  Arming, disarming and a change of b drop a captured step.
+ * Armed, s2v_denoise_step, _videos, _masked and _guided (plain and masked) run, behind the forward: the statistics kernel, the finalize kernel,
+ * and the RESCALE form of the step kernel -- on every step-cache mode, reuse steps included.  The captured graph of an armed step has a key of its
+ * own.  Every finalize appends its b factors (0 in the columns past b) to row `count` of the log [S2V_CFG_LOG_STEPS][S2V_MAX_BATCH / 2] fp32 while
+ * count < S2V_CFG_LOG_STEPS and advances the device-side count, so graph replays log too.
+ * Refused by name: a value outside [0, 1] or NaN; b that is not the geometry's videos; no geometry; B = 1 (no CFG: the CFG-parallel split entries
+ * refuse an armed context too); a shard context; temporal windows (s2v_denoise_step_windows combines the windows before its one scheduler step, and
+ * a statistic per window is another feature); an attention-only context.
+ * s2v_guidance_rescale_read: synchronises the device.  sums [b][4] fp64 (Sf, Sff, Sv, Svv) and factors [b] of the LAST armed step (either may be
+ * NULL; non-NULL needs an armed context); log: HOST buffer of S2V_CFG_LOG_STEPS x S2V_MAX_BATCH / 2 floats receiving the first
+ * min(count, S2V_CFG_LOG_STEPS) rows (may be NULL); log_count: the steps logged since the log was allocated (may be NULL; 0 without a log). */
+#define S2V_CFG_STATS_CHUNK 4096
+#define S2V_CFG_LOG_STEPS 1024
+S2V_API int s2v_set_guidance_rescale(s2v_ctx* ctx, const float* phi, int32_t b);
+S2V_API int s2v_guidance_rescale_read(s2v_ctx* ctx, double* sums, float* factors, float* log, int32_t* log_count);
+/* The RESCALE form of s2v_sched_step / s2v_sched_step_masked: the same arguments with `flags` bit4 (S2V_SCHED_RESCALE) set and `factors`, a DEVICE
+ * pointer to the one fp32 factor of the one video, behind them: v' = v factors[0] ahead of the scheduler arithmetic.  (The two entries above keep
+ * their signatures and refuse bit4 by name, pointing here.) */
+#define S2V_SCHED_RESCALE 16
+S2V_API int s2v_sched_step_rescale(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const void* noise_pred, int32_t flags, const void* latents_in,
+                                   void* latents_out, float* x0_hist, const void* noise, int64_t n, int32_t dtype, const float* factors,
+                                   s2v_stream stream);
+S2V_API int s2v_sched_step_masked_rescale(s2v_ctx* ctx, const s2v_sched_coef* coef_host, const s2v_blend* blend_host, const void* noise_pred,
+                                          int32_t flags, const void* latents_in, void* latents_out, float* x0_hist, const void* noise,
+                                          const void* z0, const void* noise0, const uint8_t* latent_mask, int32_t F, int32_t C, int32_t H,
+                                          int32_t W, int32_t dtype, const float* factors, s2v_stream stream);
 
 /* ---- Step cache: a step whose timestep embedding barely moved skips the block stack ---------------------------------------------------------
  * Opt-in state on a model context.  X is the packed residual buffer [B][Ntok][D]; its video rows are rows [T + R, T + R + V) of each sample.
@@ -803,6 +860,13 @@ S2V_API int s2v_op_step_cache(int32_t op, void* x, int64_t x_bstride, void* cach
  * frame first covered by a window of this batch starts from +0 (its cell is not read); a frame last covered by one leaves divided by wsum */
 S2V_API int s2v_op_window_blend(const void* noise_pred, float* acc, const float* weights, const float* wsum, float guidance, int32_t L, int32_t F,
                                 int32_t stride, int32_t k0, int32_t wb, int32_t chw, int32_t dtype, s2v_stream stream);
+/* the guidance rescale's statistics and finalize kernels on their own (two launches of an armed step, no log): noise_pred the planes of nvid
+ * videos of n_vid elements each, [2, nvid n_vid] or [3, nvid n_vid], with `flags` as s2v_sched_step takes them (bit0 the pair, bit3 the triple --
+ * exactly one of them; bit1 fp32 planes); guidance / guidance_subject (NULL for a pair) / phi: HOST arrays of nvid values.  Returns, on the HOST
+ * and after synchronising `stream`, sums [nvid][4] fp64 (Sf, Sff, Sv, Svv) and factors [nvid] fp32 as the definition above states them.  The
+ * scratch it needs is allocated and freed inside the call */
+S2V_API int s2v_op_cfg_stats(const void* noise_pred, int32_t flags, int32_t nvid, int64_t n_vid, const float* guidance, const float* guidance_subject,
+                             const float* phi, double* sums, float* factors, int32_t dtype, s2v_stream stream);
 /* the attention-mass kernel on its own: qkv [B * Ntok][3 * H * 64] (q | k | v as s2v_op_attention takes them, 16-byte aligned; nothing past row
  * B * Ntok - 1 is read), query rows [q0, q0 + nq) of every sample, ranges_host n pairs (k0, k1) -> out [n][B][H][nq] fp32; accumulate != 0: out + mass
  * in one fp32 add.  An empty range gives exactly 0.  impl 0: v_mfma_f32_32x32x16 on bf16 / fp16 storage, q * 0.125 * log2 e rounded to the
