@@ -159,6 +159,8 @@ _SIGS.update({
     "s2v_attn_local_set": [_P, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
     "s2v_attn_local_arm": [_P, ctypes.c_uint64],
     "s2v_op_attention_local": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32), _P],
+    "s2v_attn_local_set_box": [_P, _I32, _I32] + [ctypes.POINTER(_I32)] * 4,
+    "s2v_op_attention_box": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32] + [ctypes.POINTER(_I32)] * 4 + [_P],
 })
 
 

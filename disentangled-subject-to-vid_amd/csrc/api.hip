@@ -85,7 +85,8 @@ struct GraphKey {
                windows == o.windows && rescale == o.rescale;
     }
     uint64_t lmask = 0;   // s2v_attn_local_arm: the layers whose attention launch is the local kernel in this step; an executable per mask as well
-    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask && smask == o.smask && lmask == o.lmask; }
+    int lkind = 0;        // ... and the kind of the table those layers read (0 a window table, 1 a box table): the kernel choice is baked into the executable
+    bool operator==(const GraphKey& o) const { return same_but_mode(o) && mode == o.mode && amask == o.amask && smask == o.smask && lmask == o.lmask && lkind == o.lkind; }
     bool armed() const { return amask != 0 || smask != 0 || lmask != 0; }
 };
 
@@ -216,7 +217,13 @@ struct s2v_ctx {
     int la_Ntok = 0;
     uint64_t la_arm = 0;         // the layers of the NEXT forward; la_run: of the forward that is running (run_block reads it)
     uint64_t la_run = 0;
-    int64_t la_bytes() const { return la_tab ? (int64_t)(attn_local_ints(la_Ntok) * sizeof(int)) : 0; }
+    // a context holds ONE table, of either kind: la_kind 0 the window table (la_tab), 1 the box table of local attention in space and time (la_box,
+    // allocated by the first s2v_attn_local_set_box and kept until the feature goes off, so that a captured step keeps its pointer)
+    int la_kind = 0;
+    int* la_box = nullptr;
+    int64_t la_bytes() const {
+        return (la_tab ? (int64_t)(attn_local_ints(la_Ntok) * sizeof(int)) : 0) + (la_box ? (int64_t)(attn_box_ints(la_Ntok) * sizeof(int)) : 0);
+    }
     // step cache (include/s2v_hip.h): sc_delta holds IN between the two extra launches of a CAPTURE forward and the residual after it
     int sc_on = 0;               // s2v_step_cache_enable: 0 off, 1 the cache, 2 the cache + sc_in (IN of every forward, for the read-out)
     int sc_arm = 0;              // S2V_STEP_*: the mode of the next forward
@@ -572,6 +579,7 @@ extern "C" void s2v_destroy(s2v_ctx* c) {
     if (c->gr_log) hipFree(c->gr_log);
     if (c->st_tab) hipFree(c->st_tab);
     if (c->la_tab) hipFree(c->la_tab);
+    if (c->la_box) hipFree(c->la_box);
     if (c->attn_queue) hipFree(c->attn_queue);
     if (c->vt_amax) hipFree(c->vt_amax);
     if (c->attn_stats) hipFree(c->attn_stats);
@@ -640,7 +648,8 @@ static int st_check(s2v_ctx* c, const char* fn) {
 // local attention: off frees the table (the caller has synchronised the device and dropped the graphs)
 static void la_free(s2v_ctx* c) {
     if (c->la_tab) hipFree(c->la_tab);
-    c->la_tab = nullptr; c->la_on = false; c->la_Ntok = 0; c->la_arm = 0;
+    if (c->la_box) hipFree(c->la_box);
+    c->la_tab = nullptr; c->la_box = nullptr; c->la_kind = 0; c->la_on = false; c->la_Ntok = 0; c->la_arm = 0;
 }
 // the record of (P, lo, hi) at the current geometry, checked by attn_local_make before the table is touched, then copied to it
 static int la_upload(s2v_ctx* c, const char* who, int P, const int* lo, const int* hi) {
@@ -1461,7 +1470,7 @@ enum { QK_DONE = 0, QK_STANDALONE = 1, QK_IN_QUANT = 2 };
 // steer: the record of a steered layer (s2v_attn_steer_arm) -- the attention launch is then attn_pp<STEER> (bf16) or the steered generic kernel (fp32)
 // local: the record of a local layer (s2v_attn_local_arm) -- the attention launch is then attn_pp<LOCAL> (bf16) or the local generic kernel (fp32)
 static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w, hipStream_t st, const AttnSteerRec* steer = nullptr,
-                     const int* local = nullptr) {
+                     const int* local = nullptr, bool box = false) {
     const bool mx = attn_mx_out(c), matrix = c->mfma || c->h16;
     // fp16 P / V^T is the four-wave kernels' (attn_q4h / attn_q4fh); short sequences run attn_pp on bf16 V^T
     const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(o.Ntok, mx));
@@ -1504,6 +1513,7 @@ static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w,
     if (local) {
         S2V_REQUIRE(!mx && !p16 && !c->fp8_qk && !c->h16, "attention: a local layer on an engine the local kernels do not serve");
         S2V_REQUIRE(o.Ntok == c->la_Ntok, "attention: the local-attention table was made for another Ntok");
+        if (box) return c->mfma ? launch_attn_bf16_box(a, local, st) : launch_attn_simple_box(a, local, c->dtype, st);   // box: `local` is the box record
         return c->mfma ? launch_attn_bf16_local(a, local, st) : launch_attn_simple_local(a, local, c->dtype, st);
     }
     if (c->fp8_qk) return launch_attn_q4f(a, true, st);
@@ -1538,7 +1548,10 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
     const AttnOperands o{c->QKV, 3 * D, c->cfg.num_heads, c->Ntok, c->Xn, pX, (unsigned char*)c->aq, c->hs, c->Mpad};
     S2V_REQUIRE(!steer || c->st_tab, "attention: a steered layer without s2v_attn_steer_enable");
     S2V_REQUIRE(!local || c->la_tab, "attention: a local layer without s2v_attn_local_enable");
-    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st, steer ? c->st_tab : nullptr, local ? c->la_tab : nullptr));
+    const bool box = local && c->la_kind == 1;
+    S2V_REQUIRE(!box || c->la_box, "attention: a box layer without s2v_attn_local_set_box");
+    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st, steer ? c->st_tab : nullptr,
+                      !local ? nullptr : box ? c->la_box : c->la_tab, box));
     return mass ? am_launch(c, st) : 0;
 }
 
@@ -2312,7 +2325,7 @@ static int denoise_step_impl(s2v_ctx* c, void* latents, const float* timesteps, 
     S2V_TRY(stage_step(c, timesteps, coefs, b, st));
     if (!use_graph) return am_done(c, am, sc_done(c, mode, step_launches(c, latents, x0_hist, noise, st, mode, am, sm, lm)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm; key.rescale = c->gr_buf ? 1 : 0;
+    key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm; key.lkind = lm ? c->la_kind : 0; key.rescale = c->gr_buf ? 1 : 0;
     return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return step_launches(c, latents, x0_hist, noise, s, mode, am, sm, lm); })));
 }
 
@@ -2379,7 +2392,7 @@ extern "C" int s2v_denoise_step_masked(s2v_ctx* c, void* latents, const float* t
     S2V_TRY(stage_step(c, timesteps, coefs, b, st, blends));
     if (!use_graph) return am_done(c, am, sc_done(c, mode, masked_step_launches(c, latents, x0_hist, noise, st, mode, am, sm, lm)));
     GraphKey key{latents, x0_hist, noise, -1};
-    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm;
+    key.z0 = c->blend_z0; key.noise0 = c->blend_noise0; key.mask = c->blend_mask; key.mode = mode; key.amask = am; key.smask = sm; key.lmask = lm; key.lkind = lm ? c->la_kind : 0;
     key.rescale = c->gr_buf ? 1 : 0;
     return am_done(c, am, sc_done(c, mode, launch_captured(c, key, st, [&](hipStream_t s) { return masked_step_launches(c, latents, x0_hist, noise, s, mode, am, sm, lm); })));
 }
@@ -3031,7 +3044,26 @@ extern "C" int s2v_attn_local_set(s2v_ctx* c, int32_t P, const int32_t* rows_lo,
     S2V_REQUIRE(c, "s2v_attn_local_set: null context");
     S2V_REQUIRE(c->la_on && c->la_tab && c->la_Ntok == c->Ntok, "s2v_attn_local_set: local attention is not enabled (s2v_attn_local_enable)");
     S2V_REQUIRE(rows_lo && rows_hi, "s2v_attn_local_set: null row table");
-    return la_upload(c, "s2v_attn_local_set", P, rows_lo, rows_hi);   // checked before anything is replaced; a captured step is kept: the table is data
+    S2V_TRY(la_upload(c, "s2v_attn_local_set", P, rows_lo, rows_hi));   // checked before anything is replaced; a captured step is kept: the table is data
+    if (c->la_kind != 0) { drop_graph(c); c->la_kind = 0; }   // ... unless the table it replaces was a box table: the captured steps launch the box kernel
+    return 0;
+}
+
+// the box table of local attention in space and time: checked by attn_box_make before anything is replaced, then uploaded to a table of its own.  It
+// replaces a window table (the captured steps launch the window kernel: dropped); a box table after a box table keeps them -- the table is data
+extern "C" int s2v_attn_local_set_box(s2v_ctx* c, int32_t P, int32_t S, const int32_t* rows_lo, const int32_t* rows_hi, const int32_t* offs_lo,
+                                      const int32_t* offs_hi) {
+    S2V_REQUIRE(c, "s2v_attn_local_set_box: null context");
+    S2V_TRY(la_check(c, "s2v_attn_local_set_box"));
+    S2V_REQUIRE(c->la_on && c->la_tab && c->la_Ntok == c->Ntok, "s2v_attn_local_set_box: local attention is not enabled (s2v_attn_local_enable)");
+    S2V_REQUIRE(rows_lo && rows_hi && offs_lo && offs_hi, "s2v_attn_local_set_box: null row table");
+    std::vector<int> r;
+    S2V_TRY(attn_box_make("s2v_attn_local_set_box", P, S, c->Ntok, rows_lo, rows_hi, offs_lo, offs_hi, &r));
+    S2V_CHECK_HIP(hipDeviceSynchronize());   // a step on any stream may still read the table
+    if (!c->la_box) S2V_CHECK_HIP(hipMalloc((void**)&c->la_box, attn_box_ints(c->Ntok) * sizeof(int)));
+    S2V_CHECK_HIP(hipMemcpy(c->la_box, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (c->la_kind != 1) { drop_graph(c); c->la_kind = 1; }
+    return 0;
 }
 
 extern "C" int s2v_attn_local_arm(s2v_ctx* c, uint64_t layer_mask) {
@@ -3091,6 +3123,67 @@ extern "C" int s2v_op_attention_local(const void* qkv, void* vt_scratch, void* o
     }
     a.valu_only = 1;
     return launch_attn_simple_local(a, op_tab, dtype, st);
+}
+
+// the box kernel on its own: s2v_op_attention_local with the box table (a table and counters of its own)
+extern "C" int s2v_op_attention_box(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                      int32_t P, int32_t S, const int32_t* rows_lo, const int32_t* rows_hi, const int32_t* offs_lo, const int32_t* offs_hi,
+                                    s2v_stream stream) {
+    S2V_REQUIRE(qkv && out, "s2v_op_attention_box: null argument");
+    S2V_REQUIRE(B >= 1 && H >= 1 && Ntok >= 1, "s2v_op_attention_box: B >= 1, H >= 1, Ntok >= 1");
+    S2V_REQUIRE(impl == 0 || impl == 1, "s2v_op_attention_box: impl 0 (MFMA, bf16) or 1 (generic)");
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_attention_box: unsupported dtype");
+    S2V_REQUIRE(impl == 1 || (dtype == S2V_DTYPE_BF16 && vt_scratch), "s2v_op_attention_box: impl 0 is bf16 and needs vt_scratch");
+    // operator level: one table per process, on the device of the first call, grown when a longer sequence comes.  The entry synchronises the stream
+    // before it replaces the table and uploads it with a blocking copy: a test and benchmark entry, not thread-safe; contexts hold their own table.
+    // The record is built and uploaded once per table: a call with the table of the call before it (compared word for word) launches on the
+    // record that is there, as a context's steps do between two s2v_attn_local_set_box
+    static int* op_tab = nullptr;
+    static size_t op_ints = 0;
+    static std::vector<int> op_key;   // P, S, Ntok and the four row arrays of the record in op_tab
+    hipStream_t st = (hipStream_t)stream;
+    const bool arrays = rows_lo && rows_hi && offs_lo && offs_hi;
+    bool same = arrays && op_tab && op_key.size() == 3 + 4 * (size_t)Ntok && op_key[0] == P && op_key[1] == S && op_key[2] == Ntok;
+    for (int k = 0; same && k < 4; ++k)
+        same = memcmp(op_key.data() + 3 + (size_t)k * Ntok, k == 0 ? rows_lo : k == 1 ? rows_hi : k == 2 ? offs_lo : offs_hi, (size_t)Ntok * sizeof(int)) == 0;
+    if (!same) {
+        std::vector<int> r;
+        S2V_TRY(attn_box_make("s2v_op_attention_box", P, S, Ntok, rows_lo, rows_hi, offs_lo, offs_hi, &r));   // refused before the device is touched
+        S2V_CHECK_HIP(hipStreamSynchronize(st));
+        op_key.clear();   // nothing is remembered while the table is being replaced
+        if (r.size() > op_ints) {
+            if (op_tab) { S2V_CHECK_HIP(hipFree(op_tab)); op_tab = nullptr; op_ints = 0; }
+            S2V_CHECK_HIP(hipMalloc((void**)&op_tab, r.size() * sizeof(int)));
+            op_ints = r.size();
+        }
+        S2V_CHECK_HIP(hipMemcpy(op_tab, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice));
+        op_key.reserve(3 + 4 * (size_t)Ntok);
+        op_key.push_back(P); op_key.push_back(S); op_key.push_back(Ntok);
+        for (const int32_t* p : {rows_lo, rows_hi, offs_lo, offs_hi}) op_key.insert(op_key.end(), p, p + Ntok);
+    } else {
+        S2V_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    const int D = H * 64;
+    AttnArgs a{};
+    a.qkv = qkv; a.ld_qkv = 3 * D; a.out = out; a.ld_out = D; a.B = B; a.H = H; a.Ntok = Ntok; a.scale = 0.125f;
+    a.ntok_pad = (int)rup(Ntok, 64);
+    if (impl == 0) {
+        // the nine counters of the persistent form (zero between launches), so that this entry runs what a context runs at the same size
+        static int* op_queue = nullptr;
+        static int op_ncu = 0;
+        if (!op_queue) {
+            int dev = 0;
+            S2V_CHECK_HIP(hipGetDevice(&dev));
+            S2V_CHECK_HIP(hipDeviceGetAttribute(&op_ncu, hipDeviceAttributeMultiprocessorCount, dev));
+            S2V_CHECK_HIP(hipMalloc((void**)&op_queue, 64));
+            S2V_CHECK_HIP(hipMemset(op_queue, 0, 64));
+        }
+        a.vt = vt_scratch; a.queue = op_queue; a.num_cus = op_ncu;
+        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, nullptr));
+        return launch_attn_bf16_box(a, op_tab, st);
+    }
+    a.valu_only = 1;
+    return launch_attn_simple_box(a, op_tab, dtype, st);
 }
 
 extern "C" int s2v_attn_map_reset(s2v_ctx* c) {

@@ -22,6 +22,9 @@
 //     row i sees the keys [0, P) and [lo_i, hi_i); an item visits only the key tiles some row of it sees (kernels.h "local attention";
 //     include/s2v_hip.h "Local attention"); what a local layer of a bf16 engine runs at every length.  attn_simple_local_k<T>: the same mask
 //     in the generic kernel (fp32 engines, and the cross-check).
+//  attn_pp_box_k / attn_pp_box_persist_k : attn_pp_item<ACCT, STEER, LOCAL, BOX = true> in the same two launch forms -- local attention in space and
+//     time: row i sees [0, P) and the keys of [lo_i, hi_i) whose offset in their frame lies in [olo_i, ohi_i); an item visits the tiles of a list the
+//     host made (kernels.h "local attention in space and time"; include/s2v_hip.h).  attn_simple_box_k<T>: the same mask in the generic kernel.
 //  attn_bf16_k (S2V_DIAG builds only): the round-1 lock-step kernel with a per-tile row maximum, kept as the A/B reference.
 //  attn_simple_k<T> : one wave per query row, fp32 math, any dtype (CPU-reference-parity mode / cross-check).
 #define S2V_HOST
@@ -299,7 +302,14 @@ extern "C" __attribute__((visibility("default"))) int s2v_attn_debug_read(long l
 // kv0, the global addresses, the tail mask.  Per wave and tile, in scalar code: a tile every key of which every row of the wave sees runs
 // the untouched code; any other visited tile sets the scores of the keys a lane's own row does not see to -inf, before everything the softmax
 // segment does.  P >= 1 makes key 0 visible to every row, so iteration 0 (always tile 0) holds a finite score for every lane.
-template <bool ACCT, bool STEER = false, bool LOCAL = false>
+// BOX (local attention in space and time, kernels.h): row i sees [0, P) and the keys j of [lo_i, hi_i) with olo_i <= (j - P) mod S < ohi_i.  The
+// item visits the tiles of its list in the record: loop iteration j is tile(j), and entry j also names the tiles of the iterations j + 1 .. j + 4
+// (clamped by the host), which is all the DMA of iteration j issues -- so the entry of iteration j + 1 is fetched at the top of iteration j and
+// waited for where the softmax segment ends, and no DMA issue waits on a load of its own entry.  ITERATION and TILE divide as for LOCAL.  Per
+// wave and tile the host's whole bit picks the untouched code; any other visited tile masks per lane, on the key index and on the key's offset
+// in its frame: the tile's first offset from the entry plus the key's position, less S once where it passes S (S >= 64: at most once per tile).
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+template <bool ACCT, bool STEER = false, bool LOCAL = false, bool BOX = false>
 __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg, char* smem, const AttnSteerRec* __restrict__ sr = nullptr,
                                              const int* __restrict__ lr = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -327,6 +337,21 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
         l_lomax = wv[0]; l_himin = wv[1];
         lo_lane = rw[0]; hi_lane = rw[256 * nq];   // the lane's own row's window (rows past Ntok are stored dense)
     }
+    // BOX: cur = the entry of the iteration that is running, nxt = of the next one; the lane's own row as (lo, hi - lo, olo, ohi - olo)
+    i32x8 cur = {0, 0, 0, 0, 0, 0, 0, 0}, nxt = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int* b_lst = nullptr;
+    int b_S = 0, b_lo = 0, b_olo = 0;
+    unsigned b_len = 0, b_olen = 0;
+    if constexpr (BOX) {
+        const int qbu = __builtin_amdgcn_readfirstlane(qb);
+        const int nq = lr[2], ntl = lr[4];
+        const int* rw = lr + ATTN_BOX_HDR + 8 * nq + qbu * 256 + wave * 32 + fr;
+        l_P = lr[0]; b_S = lr[3];
+        nt = lr[ATTN_BOX_HDR + 8 * qbu];
+        b_lst = lr + ATTN_BOX_HDR + 1032 * nq + 8 * ntl * qbu;
+        cur = *(const i32x8*)b_lst;
+        b_lo = rw[0]; b_len = (unsigned)rw[256 * nq]; b_olo = rw[512 * nq]; b_olen = (unsigned)rw[768 * nq];
+    }
     auto tix = [&](int j) -> int {  // iteration -> tile
         if constexpr (LOCAL) return j < l_np ? j : j + l_gap;
         else return j;
@@ -347,7 +372,14 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
         const int tc = tix(min(t, nt - 1));
         glds16_saddr(VTg + (size_t)tc * (KV_TILE * 2), offV, smem + (t & 3) * 16384 + 8192 + wave * 1024);
     };
-    dma_k(0); dma_v(0); dma_k(1); dma_v(1); dma_k(2); dma_k(3);
+    // BOX: the same two issues with the tile taken from the entry (clamped by the host), the ring slot from the iteration
+    auto dma_k_box = [&](int t, int tile) { glds16_saddr(Kg + (size_t)tile * k_tile_stride, offK, smem + (t & 3) * 16384 + wave * 1024); };
+    auto dma_v_box = [&](int t, int tile) { glds16_saddr(VTg + (size_t)tile * (KV_TILE * 2), offV, smem + (t & 3) * 16384 + 8192 + wave * 1024); };
+    if constexpr (BOX) {
+        dma_k_box(0, cur[0]); dma_v_box(0, cur[0]); dma_k_box(1, cur[5]); dma_v_box(1, cur[5]); dma_k_box(2, cur[3]); dma_k_box(3, cur[6]);
+    } else {
+        dma_k(0); dma_v(0); dma_k(1); dma_v(1); dma_k(2); dma_k(3);
+    }
 
     // Q fragments (B operand of S^T = K.Q^T): lane (q = fr, hi) holds Q[q][16kk + 8hi .. +8], pre-multiplied by
     // scale * log2(e) and rounded to bf16 once (the reference's math path rounds its scaled q and k to bf16 as well), so the
@@ -426,7 +458,19 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
     for (int t = 0; t < nt; ++t) {
         // ---- softmax segment S(t)
         const long long u0 = now();
-        const int kv0 = tix(t) * KV_TILE;
+        int kv0;
+        if constexpr (BOX) {
+            kv0 = cur[0] * KV_TILE;
+            // the entry of iteration t + 1, in flight across this segment (asm: the load is issued HERE and waited for below, by hand).
+            // INVARIANT the compiler is not told: the eight SGPRs of nxt are NOT valid between this asm and the lgkmcnt(0) asm below (its waitcnt
+            // insertion does not see a load issued from inline asm).  Nothing in between may name nxt: the only reads are `cur = nxt` at the
+            // loop's end.  A copy or spill of nxt ahead of the wait would read stale registers -- when this code or the compiler changes,
+            // check in the disassembly of attn_pp_box_k and attn_pp_box_persist_k that the destination octet is first read after the wait.
+            const int* ep = b_lst + 8 * min(t + 1, nt - 1);
+            asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(nxt) : "s"(ep));
+        } else {
+            kv0 = tix(t) * KV_TILE;
+        }
         if constexpr (STEER) {
             if (kv0 < s_hi && kv0 + KV_TILE > s_lo) {
 #pragma nounroll
@@ -465,6 +509,23 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
                     for (int e = 0; e < 16; ++e) {
                         const int kv = kv0 + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hi;
                         if (!(kv < l_P || (unsigned)(kv - lo_lane) < len)) st[kb][e] = -INFINITY;
+                    }
+            }
+        }
+        if constexpr (BOX) {
+            if (!((cur[2] >> wave) & 1)) {   // not whole for this wave (the host's bit)
+                const int kvb = kv0 + 4 * hi;
+                const unsigned ob = (unsigned)(cur[1] + 4 * hi);
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int kp = kb * 32 + (e & 3) + 8 * (e >> 2);
+                        const int kv = kvb + kp;
+                        const unsigned o = min(ob + (unsigned)kp, ob + (unsigned)kp - (unsigned)b_S);
+                        // bitwise on purpose: the short-circuit form compiles to a branch per key
+                        const bool seen = (kv < l_P) | (((unsigned)(kv - b_lo) < b_len) & (o - (unsigned)b_olo < b_olen));
+                        st[kb][e] = seen ? st[kb][e] : -INFINITY;
                     }
             }
         }
@@ -529,6 +590,7 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
         fence();
         const long long u1 = now();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (BOX) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nxt)::"memory");   // the next entry has landed (the K fragments are due here anyway)
         const long long u2 = now();
         __builtin_amdgcn_s_barrier();
         const long long u3 = now();
@@ -555,8 +617,14 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
             kf[i] = k_frag(min(t + 2, nt - 1), i);
             fence();
         }
-        dma_k(t + 4);
-        dma_v(t + 2);
+        if constexpr (BOX) {
+            dma_k_box(t + 4, cur[4]);
+            dma_v_box(t + 2, cur[3]);
+            cur = nxt;
+        } else {
+            dma_k(t + 4);
+            dma_v(t + 2);
+        }
         __builtin_amdgcn_s_setprio(0);
         fence();
         const long long u4 = now();
@@ -631,12 +699,19 @@ __global__ __launch_bounds__(512, 2) void attn_pp_local_k(const AttnArgs a, int 
     attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
     attn_pp_item<false, false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, nullptr, lr);
 }
+// the BOX = true instantiation of the same launch form: the record (kernels.h "local attention in space and time") as the one pointer argument
+__global__ __launch_bounds__(512, 2) void attn_pp_box_k(const AttnArgs a, int nqb, const int* __restrict__ lr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int first, cnt;
+    attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
+    attn_pp_item<false, false, false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, nullptr, lr);
+}
 // PERSISTENT form (the engine's launches): one workgroup per CU pulls items from its XCD's queue and, when that is empty, from the
 // other XCDs' queues.  The hardware hands every XCD exactly 1/8 of a grid, but the XCDs of one launch run a few percent apart in
 // clock: with static shares the launch ended 95-100 % apart per XCD plus a last round of 32 items on 256 slots (4.6 % of the
 // slot-time idle, tools/attn_harness timeline); pulled work ends within one item.  queue[0..7]: next item of XCD x, queue[8]:
 // workgroups done -- the last one to leave zeroes the nine counters for the next launch (they must be zero at the first).
-// TWIN: attn_pp_steer_persist_k and attn_pp_local_persist_k below repeat this loop word for word (a shared function changed this kernel's
+// TWIN: attn_pp_steer_persist_k, attn_pp_local_persist_k and attn_pp_box_persist_k below repeat this loop word for word (a shared function changed this kernel's
 // schedule): a change to the queue protocol here is made there as well.
 template <bool ACCT>
 __global__ __launch_bounds__(512, 2) void attn_pp_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue) {
@@ -726,6 +801,38 @@ __global__ __launch_bounds__(512, 2) void attn_pp_local_persist_k(const AttnArgs
         __syncthreads();
         if (wg < 0) break;
         attn_pp_item<false, false, true>(a, nqb, wg, smem, nullptr, lr);
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&queue[8], 1) == (int)gridDim.x - 1) {
+            for (int i = 0; i < 9; ++i) __hip_atomic_store(&queue[i], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __threadfence();
+        }
+    }
+}
+// the BOX = true instantiation of the persistent form: the same loop a fourth time (a twin, as above)
+__global__ __launch_bounds__(512, 2) void attn_pp_box_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue, const int* __restrict__ lr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_item;
+    const int xcd = blockIdx.x & 7;
+    for (;;) {
+        if (threadIdx.x == 0) {
+            int wg = -1;
+            for (int k = 0; k < 8 && wg < 0; ++k) {
+                const int y = (xcd + k) & 7;
+                int first, cnt;
+                attn_xcd_range(total, y, first, cnt);
+                if (__hip_atomic_load(&queue[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= cnt) continue;  // drained: do not hammer it
+                const int i = atomicAdd(&queue[y], 1);
+                if (i < cnt) wg = first + i;
+            }
+            s_item = wg;
+        }
+        __syncthreads();  // also fences the previous item's LDS traffic from the next item's prologue
+        const int wg = s_item;
+        __syncthreads();
+        if (wg < 0) break;
+        attn_pp_item<false, false, false, true>(a, nqb, wg, smem, nullptr, lr);
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -896,6 +1003,119 @@ int attn_local_make(const char* who, int P, int Ntok, const int* lo, const int* 
             if (w0 <= np) { np = std::max(np, w1); w0 = w1 = np; }   // the runs touch or overlap: one run
         }
         item[4 * q] = np; item[4 * q + 1] = w0; item[4 * q + 2] = w1; item[4 * q + 3] = np + (w1 - w0);
+    }
+    return 0;
+}
+
+// a box layer of a bf16 engine (and s2v_op_attention_box impl 0): attn_pp<BOX> at every length, persistent under the rule above
+int launch_attn_bf16_box(const AttnArgs& a, const int* rec_dev, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_bf16_box: local-attention record missing");
+    S2V_REQUIRE(a.vt != nullptr, "attn_bf16_box: V^T buffer missing");
+    S2V_REQUIRE(a.mx_q == nullptr && !a.p16, "attn_bf16_box: attn_pp writes bf16 and reads bf16 V^T (no MX output, no attn_p_format 1)");
+    S2V_REQUIRE(a.ld_qkv % 8 == 0 && a.ntok_pad % 64 == 0, "attn_bf16_box: bad leading dims");
+    S2V_REQUIRE(a.ntok_pad >= ((a.Ntok + 63) / 64) * 64, "attn_bf16_box: ntok_pad too small");
+    int nqb8 = (a.Ntok + 255) / 256;
+    int total = nqb8 * a.B * a.H;
+    const bool persist = a.queue != nullptr && total > 2 * a.num_cus && a.num_cus >= 8;
+    const void* fn = persist ? (const void*)attn_pp_box_persist_k : (const void*)attn_pp_box_k;
+    S2V_TRY(ensure_lds_attr(fn, 65536));
+    AttnArgs av = a;
+    if (persist) {
+        int* queue = a.queue;
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&total, (void*)&queue, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3((a.num_cus / 8) * 8), dim3(512), args, 65536, st));
+    } else {
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(total), dim3(512), args, 65536, st));
+    }
+    return 0;
+}
+
+// host: the record (kernels.h "local attention in space and time") from P, S and the row table, every bound refused by name; the visit lists
+// and the whole bits are made here, once per table, from each row's count of visible keys per tile
+int attn_box_make(const char* who, int P, int S, int Ntok, const int* lo, const int* hi, const int* olo, const int* ohi, std::vector<int>* out) {
+    static thread_local char msg[256];
+#define BOX_REQUIRE(cond, ...) do { if (!(cond)) { snprintf(msg, sizeof(msg), __VA_ARGS__); S2V_REQUIRE(false, msg); } } while (0)
+    BOX_REQUIRE(Ntok >= 1, "%s: Ntok = %d must be at least 1", who, Ntok);
+    BOX_REQUIRE(lo && hi && olo && ohi, "%s: null row table", who);
+    BOX_REQUIRE(P >= 1 && P <= Ntok, "%s: the prefix P = %d must lie inside [1, Ntok = %d] (key 0 is visible to every row)", who, P, Ntok);
+    BOX_REQUIRE(S >= KV_TILE, "%s: the period S = %d must be at least 64 (a 64-key tile holds at most one frame boundary)", who, S);
+    for (int i = 0; i < Ntok; ++i) {
+        BOX_REQUIRE(P <= lo[i] && lo[i] <= hi[i] && hi[i] <= Ntok, "%s: row %d has the window [%d, %d): P = %d <= lo <= hi <= Ntok = %d is required", who, i,
+                    lo[i], hi[i], P, Ntok);
+        BOX_REQUIRE(0 <= olo[i] && olo[i] <= ohi[i] && ohi[i] <= S, "%s: row %d has the offsets [%d, %d): 0 <= olo <= ohi <= S = %d is required", who, i,
+                    olo[i], ohi[i], S);
+    }
+#undef BOX_REQUIRE
+    const int nqb = (Ntok + 255) / 256, nt = (Ntok + KV_TILE - 1) / KV_TILE, npre = (P + KV_TILE - 1) / KV_TILE;
+    std::vector<int>& r = *out;
+    r.assign(attn_box_ints(Ntok), 0);
+    r[0] = P; r[1] = Ntok; r[2] = nqb; r[3] = S; r[4] = nt;
+    int* item = r.data() + ATTN_BOX_HDR;
+    int* rows = item + 8 * nqb;
+    int* list = rows + 1024 * nqb;
+    for (int i = 0; i < 256 * nqb; ++i) {   // rows past Ntok: dense
+        const bool in = i < Ntok;
+        rows[i] = in ? lo[i] : P;
+        rows[256 * nqb + i] = in ? hi[i] - lo[i] : Ntok - P;
+        rows[512 * nqb + i] = in ? olo[i] : 0;
+        rows[768 * nqb + i] = in ? ohi[i] - olo[i] : S;
+    }
+    // per row only the tiles it sees are touched (the prefix range, then its box in each frame, ascending and disjoint): cnt[t] = the keys of tile t
+    // the row sees, with the tiles listed in `hit` and cleared again; nfull[t] = the rows of the wave that see every key of tile t below Ntok
+    std::vector<int> cnt((size_t)nt, 0), any((size_t)nt), full((size_t)nt), nfull((size_t)nt, 0), hit, whit, seen;
+    auto add = [&](int a, int b) {   // the keys [a, b) are visible to the row
+        for (int t = a / KV_TILE; a < b; ++t) {
+            const int e = std::min(b, (t + 1) * KV_TILE);
+            if (cnt[t] == 0) hit.push_back(t);
+            cnt[t] += e - a;
+            a = e;
+        }
+    };
+    for (int q = 0; q < nqb; ++q) {
+        std::fill(any.begin(), any.end(), 0);
+        std::fill(full.begin(), full.end(), 0);
+        for (int w = 0; w < 8; ++w) {
+            const int i0 = q * 256 + w * 32, i1 = std::min(i0 + 32, Ntok);
+            if (i0 >= i1) {   // a wave with no row below Ntok: its rows are stored dense
+                for (int t = 0; t < nt; ++t) full[t] |= 1 << w;
+                continue;
+            }
+            whit.clear();
+            for (int i = i0; i < i1; ++i) {
+                hit.clear();
+                add(0, P);
+                if (lo[i] < hi[i] && olo[i] < ohi[i])
+                    for (long long base = P + (long long)((lo[i] - P) / S) * S; base < hi[i]; base += S)
+                        add((int)std::max<long long>(base + olo[i], lo[i]), (int)std::min<long long>(base + ohi[i], hi[i]));
+                for (int t : hit) {
+                    any[t] = 1;
+                    if (cnt[t] == std::min(KV_TILE, Ntok - t * KV_TILE)) {
+                        if (nfull[t] == 0) whit.push_back(t);
+                        ++nfull[t];
+                    }
+                    cnt[t] = 0;
+                }
+            }
+            for (int t : whit) {
+                if (nfull[t] == i1 - i0) full[t] |= 1 << w;
+                nfull[t] = 0;
+            }
+        }
+        seen.clear();
+        for (int t = 0; t < nt; ++t)
+            if (t < npre || any[t]) seen.push_back(t);
+        const int n = (int)seen.size();   // >= 1: P >= 1 puts tile 0 first
+        item[8 * q] = n;
+        auto tile = [&](int x) { return seen[std::min(x, n - 1)]; };
+        for (int j = 0; j < n; ++j) {
+            int* e = list + ((size_t)q * nt + j) * 8;
+            const int t = seen[j];
+            e[0] = t;
+            e[1] = (int)((((long long)t * KV_TILE - P) % S + S) % S);
+            e[2] = full[t];
+            e[3] = tile(j + 2); e[4] = tile(j + 4); e[5] = tile(j + 1); e[6] = tile(j + 3);
+        }
     }
     return 0;
 }
@@ -1089,6 +1309,61 @@ int launch_attn_simple_local(const AttnArgs& a, const int* rec_dev, int dtype, h
     S2V_REQUIRE(rec_dev != nullptr, "attn_simple_local: local-attention record missing");
     dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
     S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_local_k<T>, grid, dim3(256), 0, st, a, rec_dev))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the box form of attn_simple_k (a twin once more): a key the row does not see -- outside the prefix and outside the box of frames and frame offsets --
+// gets the score -inf before the maximum and expf, and a 64-key tile the row sees nothing of is skipped.  Tile 0 holds key 0, which every row
+// sees (P >= 1).  It is what an fp32 engine runs on a box layer, and the second implementation the MFMA kernel is checked against.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_simple_box_k(const AttnArgs a, const int* __restrict__ lr) {
+    __shared__ float sq[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave, h = blockIdx.y, b = blockIdx.z;
+    const int D = a.H * 64;
+    const bool active = q < a.Ntok;
+    const T* base = (const T*)a.qkv + (size_t)b * a.Ntok * a.ld_qkv;
+    const int ql = active ? q : a.Ntok - 1;
+    sq[wave][lane] = ET<T>::ld(base + (size_t)ql * a.ld_qkv + h * 64 + lane) * a.scale;
+    __syncthreads();
+    const int P = lr[0], nq = lr[2], S = lr[3];
+    const int* rw = lr + ATTN_BOX_HDR + 8 * nq + ql;
+    const int lo = rw[0], olo = rw[512 * nq];
+    const unsigned len = (unsigned)rw[256 * nq], olen = (unsigned)rw[768 * nq];
+    float m = -INFINITY, l = 0.f, o = 0.f;
+    for (int kv0 = 0; kv0 < a.Ntok; kv0 += 64) {
+        const int kv = kv0 + lane;
+        const bool vis = kv < a.Ntok && (kv < P || ((unsigned)(kv - lo) < len && (unsigned)((kv - P) % S - olo) < olen));
+        if (!__any(vis)) continue;  // the row sees no key of this tile
+        float s = -INFINITY;
+        if (vis) {
+            const T* kp = base + (size_t)kv * a.ld_qkv + D + h * 64;
+            float acc = 0.f;
+#pragma unroll 8
+            for (int d = 0; d < 64; ++d) acc = fmaf(sq[wave][d], ET<T>::ld(kp + d), acc);
+            s = acc;
+        }
+        const float mx = wave_max(s);
+        const float mn = fmaxf(m, mx);
+        const float alpha = expf(m - mn);
+        const float p = expf(s - mn);
+        l = l * alpha + wave_sum(p);
+        o *= alpha;
+        m = mn;
+        const int nv = min(64, a.Ntok - kv0);
+        for (int j = 0; j < nv; ++j) {
+            const float pj = __shfl(p, j, 64);
+            o = fmaf(pj, ET<T>::ld(base + (size_t)(kv0 + j) * a.ld_qkv + 2 * D + h * 64 + lane), o);
+        }
+    }
+    if (active) ET<T>::st((T*)a.out + (size_t)(b * a.Ntok + q) * a.ld_out + h * 64 + lane, o / l);
+}
+
+int launch_attn_simple_box(const AttnArgs& a, const int* rec_dev, int dtype, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_simple_box: local-attention record missing");
+    dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_box_k<T>, grid, dim3(256), 0, st, a, rec_dev))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

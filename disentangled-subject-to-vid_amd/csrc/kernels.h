@@ -336,6 +336,30 @@ int attn_local_make(const char* who, int P, int Ntok, const int* lo, const int* 
 int launch_attn_bf16_local(const AttnArgs& a, const int* rec_dev, hipStream_t st);
 int launch_attn_simple_local(const AttnArgs& a, const int* rec_dev, int dtype, hipStream_t st);
 
+// ---- local attention in space and time: a window of frames and of patch rows (include/s2v_hip.h, "Local attention in space and time") ------------
+//   vis(i) = [0, P) union { j : lo_i <= j < hi_i and olo_i <= (j - P) mod S < ohi_i }
+// with one P, one period S (the rows of a latent frame) and one row table (lo_i, hi_i, olo_i, ohi_i) for every sample and head; 1 <= P <= Ntok,
+// P <= lo_i <= hi_i <= Ntok, 0 <= olo_i <= ohi_i <= S, 64 <= S (a 64-key tile then holds at most one frame boundary).
+// The record as the kernels read it from DEVICE memory (data, not a launch argument), all int32, nqb = ceil(Ntok / 256), nt = ceil(Ntok / 64):
+//   [0 .. 8)                    header  P, Ntok, nqb, S, nt, 0, 0, 0
+//   [8 .. 8 + 8 nqb)            per 256-row work item  n (the tiles it visits, >= 1), 0 ...
+//   [.. + 256 nqb) four times   lo_i, hi_i - lo_i, olo_i, ohi_i - olo_i, padded to 256 nqb rows with dense rows (P, Ntok - P, 0, S)
+//   [.. + 8 nt nqb)             per work item nt entries of 8, the first n in use: entry j = tile(j), o(j), whole(j), tile(j + 2), tile(j + 4),
+//                               tile(j + 1), tile(j + 3), 0 with tile(x) the x-th visited tile, x clamped to n - 1 (what the pipeline stages ahead
+//                               of iteration j, so that no DMA issue waits on a load of its own); o(j) = (64 tile(j) - P) mod S, the frame offset
+//                               of the tile's first key; whole(j) bit w: every key of the tile below Ntok is seen by every row below Ntok of wave w
+// The visited tiles of an item are the prefix tiles [0, ceil(P / 64)) and, ascending, every later tile that holds a key some row of the item sees.
+// attn_box_make (host) checks the table, refusing every bound by name, and builds the lists and the whole bits: the kernel reduces nothing.
+#define ATTN_BOX_HDR 8
+static inline size_t attn_box_ints(int Ntok) {
+    const size_t nqb = (size_t)((Ntok + 255) / 256), nt = (size_t)((Ntok + 63) / 64);
+    return (size_t)ATTN_BOX_HDR + nqb * (8 + 1024 + 8 * nt);
+}
+int attn_box_make(const char* who, int P, int S, int Ntok, const int* lo, const int* hi, const int* olo, const int* ohi, std::vector<int>* out);
+// attn_pp<BOX> at ANY length (bf16; persistent under launch_attn_bf16's rule), and the box attn_simple_k (any dtype); as the local launches above
+int launch_attn_bf16_box(const AttnArgs& a, const int* rec_dev, hipStream_t st);
+int launch_attn_simple_box(const AttnArgs& a, const int* rec_dev, int dtype, hipStream_t st);
+
 // ---- elementwise / normalisation ------------------------------------------------
 // LayerNorm(eps, affine w,b) then (1+scale)*y+shift with per-row-range modulation sets.
 // rows: [B*Ntok, D]; text rows use (shift_txt, scale_txt), other rows (shift_vid, scale_vid); all [B][mod_stride].

@@ -584,6 +584,20 @@ class S2VEngine:
             raise _lib.S2VError(f"attn_local_set: the row table has {len(rows_lo)} rows, the geometry {ntok} tokens")
         _lib.check(_lib.lib().s2v_attn_local_set(self._h, int(P), _lib.i32_array(rows_lo), _lib.i32_array(rows_hi)))
 
+    def attn_local_set_box(self, P, S, rows_lo, rows_hi, offs_lo, offs_hi):
+        """the box table of local attention in space and time: row i sees the keys [0, P) and the keys j of [rows_lo[i], rows_hi[i]) whose offset in
+        their frame, (j - P) mod S, lies in [offs_lo[i], offs_hi[i]).  Ntok rows each, 1 <= P <= Ntok, P <= lo <= hi <= Ntok, 0 <= olo <= ohi <= S,
+        S >= 64.  Replaces a window table (attn_local_set) and the reverse -- the captured steps are then dropped; a new table of the same kind
+        keeps them"""
+        B, T, F, H, W = self.geometry
+        p = self.cfg.patch_size
+        ntok = T + (F + 1) * (H // p) * (W // p)   # [text | one reference frame | F latent frames]
+        for name, arr in (("rows_lo", rows_lo), ("rows_hi", rows_hi), ("offs_lo", offs_lo), ("offs_hi", offs_hi)):
+            if len(arr) != ntok:
+                raise _lib.S2VError(f"attn_local_set_box: {name} has {len(arr)} rows, the geometry {ntok} tokens")
+        _lib.check(_lib.lib().s2v_attn_local_set_box(self._h, int(P), int(S), _lib.i32_array(rows_lo), _lib.i32_array(rows_hi), _lib.i32_array(offs_lo),
+                                                     _lib.i32_array(offs_hi)))
+
     def _arm_local(self, local_layers):
         """the layers whose attention launch is the local kernel in the next forward (one-shot; after attn_local_enable)"""
         if local_layers is None:

@@ -133,13 +133,16 @@ STEER_W_MIN, STEER_W_MAX = 2.0 ** -16, 2.0 ** 16
 class LocalAttention:
     """what S2VPipeline.__call__(local_attention=...) windows: on the blocks `layers` (an explicit non-empty list, or the string "all") and the
     step indices `steps` (None: every step) a video row attends the text, the reference image and only the latent frames within `frames` of
-    its own -- the training-free temporal sliding window.  frames >= 0; a window that covers every frame arms nothing.  No window, layer or
-    step is recommended"""
+    its own -- the training-free temporal sliding window.  frames >= 0; a window that covers every frame arms nothing.
+    rows (None: no window in space) narrows space as well: a video row at patch row y of latent frame f sees the patch rows [y - rows, y + rows] of
+    the frames [f - frames, f + frames] -- the 3-D sliding window; rows >= 0 counts patch rows of H/16 x W/16 cells, and rows >= H/16 - 1 is the
+    call without it.  frames >= F - 1 with such a `rows` is the purely spatial window.  No window, layer or step is recommended"""
 
-    def __init__(self, layers, frames, steps=None):
+    def __init__(self, layers, frames, steps=None, rows=None):
         self.layers = layers
         self.frames = frames
         self.steps = steps
+        self.rows = rows
 
 
 def local_attention_table(T, R, F, S, frames):
@@ -180,6 +183,52 @@ def local_attention_share(P, lo, hi):
     """the key tiles the local launch visits as a share of the dense launch's (counted per work item, on the host)"""
     items = local_attention_items(P, lo, hi)
     return sum(np_ + w1 - w0 for np_, w0, w1 in items) / (len(items) * ((len(lo) + 63) // 64))
+
+
+def local_attention_box_table(T, R, F, Hp, Wp, frames, rows):
+    """(P, S, lo, hi, olo, ohi) of the sequence [text T | reference R | F latent frames of Hp patch rows of Wp cells, row-major]: P = T + R, S = Hp Wp;
+    the rows below P are dense (lo = P, hi = Ntok, olo = 0, ohi = S); a video row at patch row y of latent frame f sees the patch rows
+    [y - rows, y + rows] of the frames [f - frames, f + frames]: lo / hi as local_attention_table, olo = max(0, y - rows) Wp, ohi = min(Hp, y + rows
+    + 1) Wp.  Host integers only"""
+    T, R, F, Hp, Wp, w, r = int(T), int(R), int(F), int(Hp), int(Wp), int(frames), int(rows)
+    if T < 0 or R < 0 or T + R < 1 or F < 1 or Hp < 1 or Wp < 1 or w < 0 or r < 0:
+        raise ValueError(f"local attention: T + R >= 1, F >= 1, Hp >= 1, Wp >= 1, frames >= 0 and rows >= 0 are required, got T = {T}, R = {R}, F = {F}, "
+                         f"Hp = {Hp}, Wp = {Wp}, frames = {w}, rows = {r}")
+    S = Hp * Wp
+    P, lo, hi = local_attention_table(T, R, F, S, w)
+    olo, ohi = [0] * P, [S] * P
+    for f in range(F):
+        for y in range(Hp):
+            olo += [max(0, y - r) * Wp] * Wp
+            ohi += [min(Hp, y + r + 1) * Wp] * Wp
+    return P, S, lo, hi, olo, ohi
+
+
+def local_attention_box_items(P, S, lo, hi, olo, ohi):
+    """the exact visit list of every 256-row work item of the box kernel, a list of ascending 64-key tile indices per item: the prefix tiles
+    [0, ceil(P / 64)) and every later tile that holds a key some row of the item sees"""
+    n = len(lo)
+    npre = (P + 63) // 64
+    out = []
+    for q0 in range(0, n, 256):
+        tiles = set(range(npre))
+        for a, b, oa, ob in set(zip(lo[q0:q0 + 256], hi[q0:q0 + 256], olo[q0:q0 + 256], ohi[q0:q0 + 256])):
+            if a >= b or oa >= ob:
+                continue
+            base = P + (a - P) // S * S
+            while base < b:
+                x, y = max(base + oa, a), min(base + ob, b)
+                if x < y:
+                    tiles.update(range(x // 64, (y - 1) // 64 + 1))
+                base += S
+        out.append(sorted(tiles))
+    return out
+
+
+def local_attention_box_share(P, S, lo, hi, olo, ohi):
+    """the key tiles the box launch visits as a share of the dense launch's (counted per work item, on the host)"""
+    items = local_attention_box_items(P, S, lo, hi, olo, ohi)
+    return sum(len(t) for t in items) / (len(items) * ((len(lo) + 63) // 64))
 
 
 def local_attention_plan(la, n_steps):
@@ -711,6 +760,9 @@ class S2VPipeline:
             raise ValueError(f"`local_attention`: `frames` counts latent frames either side of the row's own, an integer >= 0, got {la.frames!r}")
         if la.steps is not None and (not isinstance(la.steps, (list, tuple)) or any(int(i) != i for i in la.steps)):
             raise ValueError("`local_attention`: `steps` is a list of step indices, or None for every step")
+        rows = getattr(la, "rows", None)
+        if rows is not None and (isinstance(rows, bool) or not isinstance(rows, int) or rows < 0):
+            raise ValueError(f"`local_attention`: `rows` counts patch rows either side of the row's own, an integer >= 0 or None, got {rows!r}")
         return layers
 
     @staticmethod
@@ -835,7 +887,10 @@ class S2VPipeline:
         both schedulers, runtime LoRA on bf16 and several videos per call with scalars (one table shared by all).  After the call
         `local_attention_report` holds {"steps", "layers", "frames", "visited_tile_share"}.  Refused with attention_map=, attention_steer=,
         step_cache=, subject_guidance_scale=, temporal_windows=, cfg_parallel=, ulysses=, fused=False, per-video lists, several input videos,
-        fp16 and fp8 engines.  No window, layer or step is recommended.
+        fp16 and fp8 engines.  No window, layer or step is recommended.  With rows= (LocalAttention) the window is three-dimensional: the patch
+        rows within `rows` of the row's own, in the frames within `frames` (the box table and kernel; frames >= F - 1: a purely spatial window);
+        rows=None or rows >= H/16 - 1 is the call without it, same launches, same bits; the report then also holds "rows", and its share is the
+        box launch's.  The compositions and refusals are the same.
         guidance_rescale: phi in [0, 1] -- a float, or a list with one entry per video (prompt-major; a list makes the call a per-video call as
         the other lists do).  Every step scales each video's guided prediction v by ONE factor k = phi * std(f) / std(v) + (1 - phi) before the
         scheduler arithmetic, f the video's text-conditioned prediction (the triple's f under subject_guidance_scale=), both deviations over
@@ -861,6 +916,12 @@ class S2VPipeline:
                 local_attention, self.transformer.config.num_layers, self.transformer.dtype, getattr(self.transformer.config, "weight_format", None),
                 any(isinstance(x, (list, tuple)) for x in (guidance_scale, num_inference_steps, strength)), cfg_parallel, ulysses, fused,
                 video is not None and nb_ > 1, attention_map, attention_steer, step_cache, subject_guidance_scale, temporal_windows)
+            la_rows_ = getattr(local_attention, "rows", None)
+            if la_rows_ is not None and height is not None and width is not None:   # the box form's own bound, before the engine is touched
+                hp_, wp_ = int(height) // 16, int(width) // 16
+                if la_rows_ < hp_ - 1 and hp_ * wp_ < 64:
+                    raise ValueError(f"`local_attention` with `rows`: a latent frame of {hp_ * wp_} cells is shorter than a 64-key tile; the box "
+                                     f"kernel needs at least 64 cells per frame")
         if attention_steer is not None:   # refused before anything else looks at the arguments it excludes
             nb_ = prompt_embeds.shape[0] * num_videos_per_prompt if prompt_embeds is not None and prompt_embeds.ndim == 3 else 1
             attention_steer = self.check_attention_steer(
@@ -1108,15 +1169,26 @@ class S2VPipeline:
             st_steps = attention_steer_plan(steer, lens[0]) if st_ranges else []
             self.attention_steer_report = {"steps": list(st_steps), "layers": [int(l) for l in steer.layers] if st_ranges else [],
                                            "ranges": list(st_ranges)}
-        la_steps, la_table = [], None
+        la_steps, la_table, la_box = [], None, False
         if local is not None:   # the table and the windowed steps, on the host, before the loop; a window over every frame: nothing is enabled or armed
             la, la_layers = local
             S_ = (H // 2) * (W // 2)
-            if la.frames < F - 1:
+            la_rows = getattr(la, "rows", None)
+            la_box = la_rows is not None and la_rows < H // 2 - 1   # a window of patch rows that narrows something: the box table and kernel
+            if la_box:
+                if S_ < 64:
+                    raise ValueError(f"`local_attention` with `rows`: a latent frame of {S_} cells is shorter than a 64-key tile; the box kernel needs "
+                                     f"at least 64 cells per frame")
+                la_table = local_attention_box_table(text.shape[1], S_, F, H // 2, W // 2, min(la.frames, F), la_rows)
+                la_steps = local_attention_plan(la, lens[0])
+            elif la.frames < F - 1:
                 la_table = local_attention_table(text.shape[1], S_, F, S_, la.frames)
                 la_steps = local_attention_plan(la, lens[0])
             self.local_attention_report = {"steps": list(la_steps), "layers": list(la_layers) if la_table else [], "frames": int(la.frames),
-                                           "visited_tile_share": local_attention_share(*la_table) if la_table else 1.0}
+                                           "visited_tile_share": 1.0 if not la_table else
+                                           local_attention_box_share(*la_table) if la_box else local_attention_share(*la_table)}
+            if la_rows is not None:
+                self.local_attention_report["rows"] = int(la_rows)
         active = b
         old = [None] * b   # fused=False under DPM: every video's x0 of its last step
         last_t = [plans[k]["timesteps"][0] for k in order]
@@ -1131,7 +1203,7 @@ class S2VPipeline:
                 eng.attn_steer_set(st_ranges)
             if la_table:
                 eng.attn_local_enable(True)
-                eng.attn_local_set(*la_table)
+                (eng.attn_local_set_box if la_box else eng.attn_local_set)(*la_table)
             for i in range(lens[0]):
                 if self.interrupt:
                     break

@@ -614,6 +614,39 @@ S2V_API int s2v_attn_local_arm(s2v_ctx* ctx, uint64_t layer_mask);
 S2V_API int s2v_op_attention_local(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
                                    int32_t P, const int32_t* rows_lo, const int32_t* rows_hi, s2v_stream stream);
 
+/* ---- Local attention in space and time: a window of frames and of patch rows (the 3-D sliding window) ------------------------------------------
+ * ONE definition, which the kernels (csrc/attention.hip), tests/attn_box_ref.py and this comment state alike.  For sample b, head h, query row i
+ * and key j:
+ *     s_ij   = q_i . k_j / 8
+ *     out_i  = sum_{j in vis(i)} softmax_{j in vis(i)}(s_ij) v_j
+ *     vis(i) = [0, P)  union  { j : lo_i <= j < hi_i  and  olo_i <= (j - P) mod S < ohi_i }
+ * One P, one period S (the rows of a latent frame: inside a frame the token order is row-major, so a window of patch rows is one contiguous
+ * range of offsets per frame) and one row table (lo_i, hi_i, olo_i, ohi_i), i in [0, Ntok), serve every sample and head.  Taken: 1 <= P <= Ntok,
+ * P <= lo_i <= hi_i <= Ntok, 0 <= olo_i <= ohi_i <= S, 64 <= S (a 64-key tile then holds at most one frame boundary); anything else is refused
+ * by name, with the row where a row is at fault.  olo = 0, ohi = S on every row is exactly the window table of "Local attention" above; an empty
+ * box (lo == hi or olo == ohi) leaves the row the prefix only; key 0 stays visible to every row, as the adoption of the first tile's maximum
+ * requires.
+ * The MFMA kernel (attn_pp<BOX>) visits, per 256-row work item, the prefix tiles [0, ceil(P / 64)) and after them, ascending, every later 64-key
+ * tile that holds a key some row of the item sees -- a list the host makes once per table (csrc/kernels.h, "local attention in space and time")
+ * and the kernel maps its loop iteration through, fetching each entry an iteration ahead of its use.  A 32-row wave all of whose rows see every
+ * key of a tile (a bit the host puts beside the entry) runs the un-windowed code on it; any other visited tile sets the scores of the keys a
+ * lane's row does not see to -inf where "Local attention" does, before everything the softmax segment does.  A table every row of which sees
+ * everything returns the bits of the un-windowed attn_pp, and so do the rows of a dense wave inside a table that boxes others; a table with full
+ * offsets returns the bits of s2v_op_attention_local on the same (lo, hi).  The generic kernel masks before its maximum and skips the tiles its
+ * row sees nothing of; it is what an fp32 engine runs on a box layer.
+ * s2v_attn_local_set_box: beside s2v_attn_local_set, after s2v_attn_local_enable; arming is s2v_attn_local_arm.  A context holds ONE table, of
+ * either kind: setting the other kind replaces it and drops the captured steps (the kernel choice is baked into them); a new table of the same
+ * kind keeps them and re-captures nothing.  Checked against the current geometry with an error that names what is wrong BEFORE anything is
+ * replaced; synchronises the device.  s2v_device_bytes counts the box table as workspace from the first call until the feature goes off.
+ * Refused by name: everything s2v_attn_local_enable / _set / _arm refuse, on the same engines, contexts and compositions. */
+S2V_API int s2v_attn_local_set_box(s2v_ctx* ctx, int32_t P, int32_t S, const int32_t* rows_lo, const int32_t* rows_hi, const int32_t* offs_lo,
+                                   const int32_t* offs_hi);
+/* the box kernel on its own, as s2v_op_attention_local: impl 0 attn_pp<BOX> (bf16, persistent when the launch has more than two items per CU),
+ * impl 1 the generic box kernel (any dtype).  One table per process; a test and benchmark entry, not thread-safe */
+S2V_API int s2v_op_attention_box(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                 int32_t P, int32_t S, const int32_t* rows_lo, const int32_t* rows_hi, const int32_t* offs_lo, const int32_t* offs_hi,
+                                 s2v_stream stream);
+
 /* Live per-kernel timing for the roofline report (bench.py): HIP events are recorded on the launch stream around
  * every launch of a class; classes 0 qkv GEMM, 1 attention, 2 out-proj GEMM, 3 FF1 GEMM, 4 FF2 GEMM,
  * 5 LN-modulate, 6 qk-norm/rope/V^T, 7 the modulation GEMV, 8 the Ulysses packs, 9 the runtime-LoRA down-projections.  Not recorded inside a captured graph.  s2v_profile_read synchronises the
