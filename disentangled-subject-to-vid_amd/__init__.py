@@ -7,7 +7,8 @@ from .engine import S2VEngine, map_to_latent, mask_to_latent  # noqa: F401
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler  # noqa: F401
 from .transformer import HipCogVideoXAttnProcessor2_0, HipCogVideoXBlock, HipCogVideoXTransformer3DModel  # noqa: F401
 from .pipeline import (AttentionMap, AttentionSteer, LocalAttention, S2VPipeline, StepCache, TemporalWindows, attention_map_plan,  # noqa: F401
-                       attention_map_to_change_map, attention_steer_plan, attention_steer_ranges, change_map_plan, local_attention_box_items,
+                       attention_map_to_change_map, attention_steer_live_share, attention_steer_map_ranges, attention_steer_plan, attention_steer_ranges,
+                       box_weight_map, change_map_plan, local_attention_box_items,
                        local_attention_box_share, local_attention_box_table, local_attention_items,
                        local_attention_plan, local_attention_share, local_attention_table, step_cache_plan, window_plan, window_weights)
 from .vae import HipAutoencoderKLCogVideoX  # noqa: F401

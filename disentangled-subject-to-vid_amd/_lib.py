@@ -170,6 +170,27 @@ def i32_array(values):
     return (_I32 * max(1, len(vals)))(*vals)
 
 
+# steering maps (include/s2v_hip.h: s2v_attn_steer_set_maps, s2v_op_attention_steer_map)
+STEER_MAP_MAX_PLANES = 16
+STEER_MAP_BATCH = 8
+
+
+class SteerMapRangeC(ctypes.Structure):
+    """s2v_attn_steer_map_range: keys [k0, k1) weighted per query row by plane[b] on sample b (-1: not on that sample)"""
+    _fields_ = [("k0", ctypes.c_int32), ("k1", ctypes.c_int32), ("plane", ctypes.c_int8 * 8)]
+
+
+class SteerMapRecordC(ctypes.Structure):
+    """s2v_attn_steer_map_record: the operator-level record, ranges as arrays plus the query range [q0, q1) and the plane count"""
+    _fields_ = [("n", ctypes.c_int32), ("q0", ctypes.c_int32), ("q1", ctypes.c_int32), ("k0", ctypes.c_int32 * 4), ("k1", ctypes.c_int32 * 4),
+                ("plane", (ctypes.c_int8 * 8) * 4), ("n_planes", ctypes.c_int32)]
+
+
+_SIGS.update({
+    "s2v_attn_steer_set_maps": [_P, _I32, ctypes.POINTER(SteerMapRangeC), _I32, ctypes.POINTER(_F)],
+    "s2v_op_attention_steer_map": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(SteerMapRecordC), ctypes.POINTER(_F), _P],
+    "s2v_attn_steer_map_wave_flags": [_I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_int8), ctypes.POINTER(_F), ctypes.POINTER(_I32)],
+})
 # temporal windows (include/s2v_hip.h: s2v_set_windows, s2v_denoise_step_windows, s2v_op_window_blend)
 _SIGS.update({
     "s2v_set_windows": [_P, _I32, _I32, _I32, ctypes.POINTER(_F)],

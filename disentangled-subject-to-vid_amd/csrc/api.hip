@@ -209,7 +209,17 @@ struct s2v_ctx {
     unsigned st_mask[ATTN_STEER_MAX_RANGES] = {};
     uint64_t st_arm = 0;         // the layers of the NEXT forward; st_run: of the forward that is running (run_block reads it)
     uint64_t st_run = 0;
-    int64_t st_bytes() const { return st_tab ? (int64_t)sizeof(AttnSteerRec) : 0; }
+    // steering maps: a context holds ONE record, scalar (st_kind 0, st_tab) or maps (st_kind 1, st_map: kernels.h AttnSteerMapRec with room for
+    // st_map_cap planes of st_map_V cells at st_map_Ntok tokens); the ranges, plane indices and weights as given, for a geometry change
+    int st_kind = 0;
+    AttnSteerMapRec* st_map = nullptr;
+    int st_map_cap = 0, st_map_V = 0, st_map_Ntok = 0, st_map_np = 0, st_map_n = 0;
+    int st_map_k0[ATTN_STEER_MAX_RANGES] = {}, st_map_k1[ATTN_STEER_MAX_RANGES] = {};
+    signed char st_map_plane[ATTN_STEER_MAX_RANGES][ATTN_STEER_MAP_BATCH] = {};
+    std::vector<float> st_map_w;
+    int64_t st_bytes() const {
+        return (st_tab ? (int64_t)sizeof(AttnSteerRec) : 0) + (st_map ? (int64_t)attn_steer_map_words(st_map_Ntok, st_map_V, st_map_cap) * 4 : 0);
+    }
     // local attention in time (include/s2v_hip.h): the record the local kernels read (kernels.h "local attention"), in device memory of its own, sized
     // for the geometry's Ntok; la_Ntok: the Ntok it was made for
     bool la_on = false;
@@ -620,7 +630,27 @@ static int am_alloc(s2v_ctx* c) {
 // attention steering: off frees the table (the caller has synchronised the device and dropped the graphs)
 static void st_free(s2v_ctx* c) {
     if (c->st_tab) hipFree(c->st_tab);
+    if (c->st_map) hipFree(c->st_map);
     c->st_tab = nullptr; c->st_on = false; c->st_n = 0; c->st_arm = 0;
+    c->st_map = nullptr; c->st_kind = 0; c->st_map_cap = c->st_map_V = c->st_map_Ntok = c->st_map_np = c->st_map_n = 0; c->st_map_w.clear();
+}
+// steering maps: the record of the held ranges, plane indices and weights at the current geometry, checked before anything is touched, then copied
+// to the table.  The table is kept where it holds the record (same Ntok and V, no more planes than its room): a captured step keeps its pointer;
+// otherwise it is allocated anew and *moved says so (the caller has synchronised, and drops the captured steps)
+static int st_map_upload(s2v_ctx* c, const char* who, int n, const int* k0, const int* k1, const signed char* plane, int n_planes, const float* planes, bool* moved) {
+    std::vector<int> r;
+    const bool fits = c->st_map && c->st_map_Ntok == c->Ntok && c->st_map_V == c->V && n_planes <= c->st_map_cap;
+    const int cap = fits ? c->st_map_cap : n_planes;
+    S2V_TRY(attn_steer_map_make(who, n, k0, k1, plane, n_planes, planes, c->T + c->R, c->Ntok, c->Ntok, c->B, cap, &r));
+    *moved = !fits;
+    if (!fits) {
+        if (c->st_map) hipFree(c->st_map);
+        c->st_map = nullptr;
+        S2V_CHECK_HIP(hipMalloc((void**)&c->st_map, r.size() * 4));
+        c->st_map_cap = cap; c->st_map_V = c->V; c->st_map_Ntok = c->Ntok;
+    }
+    S2V_CHECK_HIP(hipMemcpy(c->st_map, r.data(), r.size() * 4, hipMemcpyHostToDevice));
+    return 0;
 }
 // the record of the held ranges at the current geometry -- every sample's Ntok keys, the video rows as queries -- checked and copied to the table
 static int st_upload(s2v_ctx* c, const char* who) {
@@ -1070,7 +1100,19 @@ extern "C" int s2v_set_geometry(s2v_ctx* c, int32_t B, int32_t T, int32_t F, int
     if (c->am_on) S2V_TRY(am_alloc(c));             // ... and so does the attention map: re-sized, zeroed, the count at 0
     if (c->st_on) {                                 // ... and the steer record; a range that no longer fits refuses and leaves steering off
         c->st_arm = 0;
-        const int r = st_upload(c, "s2v_set_geometry (attention steering)");
+        int r = st_upload(c, "s2v_set_geometry (attention steering)");
+        if (r == 0 && c->st_kind == 1) {            // ... the maps are one weight per video cell: another V refuses by name, the same V re-makes the record
+            if (c->st_map_V != c->V) {
+                static thread_local char msg[200];
+                snprintf(msg, sizeof(msg), "s2v_set_geometry (steering maps): the held planes have %d cells, the new geometry has V = %d video rows; steering is off",
+                         c->st_map_V, c->V);
+                st_free(c);
+                S2V_REQUIRE(false, msg);
+            }
+            bool moved = false;
+            r = st_map_upload(c, "s2v_set_geometry (steering maps)", c->st_map_n, c->st_map_k0, c->st_map_k1, &c->st_map_plane[0][0], c->st_map_np,
+                              c->st_map_w.data(), &moved);
+        }
         if (r != 0) { st_free(c); return r; }
     }
     if (c->la_on && c->la_Ntok != c->Ntok) {        // ... the local-attention table is one row per token: another Ntok switches the feature off
@@ -1469,8 +1511,9 @@ enum { QK_DONE = 0, QK_STANDALONE = 1, QK_IN_QUANT = 2 };
 // (q/k-norm,) V^T, (fp8 QK^T: q and k as MX e4m3,) attention.  w: the layer's norm weights, for QK_STANDALONE / QK_IN_QUANT
 // steer: the record of a steered layer (s2v_attn_steer_arm) -- the attention launch is then attn_pp<STEER> (bf16) or the steered generic kernel (fp32)
 // local: the record of a local layer (s2v_attn_local_arm) -- the attention launch is then attn_pp<LOCAL> (bf16) or the local generic kernel (fp32)
+// smap: the map record of a steered layer while the context holds maps (s2v_attn_steer_set_maps) -- attn_pp<MAP> or the mapped generic kernel
 static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w, hipStream_t st, const AttnSteerRec* steer = nullptr,
-                     const int* local = nullptr, bool box = false) {
+                     const int* local = nullptr, bool box = false, const AttnSteerMapRec* smap = nullptr) {
     const bool mx = attn_mx_out(c), matrix = c->mfma || c->h16;
     // fp16 P / V^T is the four-wave kernels' (attn_q4h / attn_q4fh); short sequences run attn_pp on bf16 V^T
     const bool p16 = c->attn_p16 && c->mfma && (c->fp8_qk || attn_runs_q4(o.Ntok, mx));
@@ -1509,6 +1552,11 @@ static int attn_core(s2v_ctx* c, const AttnOperands& o, int qk, const LayerW* w,
     if (steer) {
         S2V_REQUIRE(!mx && !p16 && !c->fp8_qk && !c->h16, "attention: a steered layer on an engine the steered kernels do not serve");
         return c->mfma ? launch_attn_bf16_steer(a, steer, st) : launch_attn_simple_steer(a, steer, c->dtype, st);
+    }
+    if (smap) {
+        S2V_REQUIRE(!mx && !p16 && !c->fp8_qk && !c->h16, "attention: a mapped layer on an engine the steered kernels do not serve");
+        S2V_REQUIRE(o.Ntok == c->st_map_Ntok, "attention: the steering maps were made for another Ntok");
+        return c->mfma ? launch_attn_bf16_steer_map(a, smap, st) : launch_attn_simple_steer_map(a, smap, c->dtype, st);
     }
     if (local) {
         S2V_REQUIRE(!mx && !p16 && !c->fp8_qk && !c->h16, "attention: a local layer on an engine the local kernels do not serve");
@@ -1550,8 +1598,10 @@ static int run_attention(s2v_ctx* c, const LayerW& w, hipStream_t st, bool prequ
     S2V_REQUIRE(!local || c->la_tab, "attention: a local layer without s2v_attn_local_enable");
     const bool box = local && c->la_kind == 1;
     S2V_REQUIRE(!box || c->la_box, "attention: a box layer without s2v_attn_local_set_box");
-    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st, steer ? c->st_tab : nullptr,
-                      !local ? nullptr : box ? c->la_box : c->la_tab, box));
+    const bool maps = steer && c->st_kind == 1;
+    S2V_REQUIRE(!maps || c->st_map, "attention: a mapped layer without s2v_attn_steer_set_maps");
+    S2V_TRY(attn_core(c, o, norm_in_quant ? QK_IN_QUANT : epi_ok ? QK_DONE : QK_STANDALONE, &w, st, steer && !maps ? c->st_tab : nullptr,
+                      !local ? nullptr : box ? c->la_box : c->la_tab, box, maps ? c->st_map : nullptr));
     return mass ? am_launch(c, st) : 0;
 }
 
@@ -2961,9 +3011,38 @@ extern "C" int s2v_attn_steer_set(s2v_ctx* c, int32_t n, const s2v_attn_steer_ra
     AttnSteerRec r{};
     S2V_TRY(attn_steer_make("s2v_attn_steer_set", n, k0, k1, w, m, c->T + c->R, c->Ntok, c->Ntok, &r));   // checked before anything is replaced
     S2V_CHECK_HIP(hipDeviceSynchronize());   // a step on any stream may still read the table; a captured step is kept: the table is data
+    if (c->st_kind == 1) {                   // ... unless the context held maps: one record, of one kind -- the captured steps launch the map kernels
+        drop_graph(c);
+        if (c->st_map) hipFree(c->st_map);
+        c->st_map = nullptr; c->st_kind = 0; c->st_map_cap = c->st_map_V = c->st_map_Ntok = c->st_map_np = c->st_map_n = 0; c->st_map_w.clear();
+    }
     c->st_n = n;
     for (int i = 0; i < n; ++i) { c->st_k0[i] = k0[i]; c->st_k1[i] = k1[i]; c->st_w[i] = w[i]; c->st_mask[i] = m[i]; }
     S2V_CHECK_HIP(hipMemcpy(c->st_tab, &r, sizeof(r), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int s2v_attn_steer_set_maps(s2v_ctx* c, int32_t n, const s2v_attn_steer_map_range* ranges_host, int32_t n_planes, const float* planes_host) {
+    S2V_REQUIRE(c, "s2v_attn_steer_set_maps: null context");
+    S2V_REQUIRE(c->st_on && c->st_tab, "s2v_attn_steer_set_maps: attention steering is not enabled (s2v_attn_steer_enable)");
+    S2V_REQUIRE(n >= 0 && n <= ATTN_STEER_MAX_RANGES && (n == 0 || ranges_host), "s2v_attn_steer_set_maps: 0..4 key ranges are accepted");
+    int k0[ATTN_STEER_MAX_RANGES] = {}, k1[ATTN_STEER_MAX_RANGES] = {};
+    signed char pl[ATTN_STEER_MAX_RANGES][ATTN_STEER_MAP_BATCH];
+    for (int i = 0; i < ATTN_STEER_MAX_RANGES; ++i)
+        for (int b = 0; b < ATTN_STEER_MAP_BATCH; ++b) pl[i][b] = i < n ? ranges_host[i].plane[b] : -1;
+    for (int i = 0; i < n; ++i) { k0[i] = ranges_host[i].k0; k1[i] = ranges_host[i].k1; }
+    S2V_CHECK_HIP(hipDeviceSynchronize());   // a step on any stream may still read the table
+    bool moved = false;                      // st_map_upload makes and checks the whole record before it touches the table
+    const bool was_scalar = c->st_kind == 0;
+    S2V_TRY(st_map_upload(c, "s2v_attn_steer_set_maps", n, k0, k1, &pl[0][0], n_planes, planes_host, &moved));
+    if (moved || was_scalar) drop_graph(c);  // another table or another kind of record: the captured steps go; else they replay with the new maps
+    c->st_kind = 1; c->st_map_n = n; c->st_map_np = n_planes;
+    c->st_n = 0;   // the scalar record beside it is forgotten: a geometry change re-checks the maps' ranges only
+    for (int i = 0; i < ATTN_STEER_MAX_RANGES; ++i) {
+        c->st_map_k0[i] = k0[i]; c->st_map_k1[i] = k1[i];
+        for (int b = 0; b < ATTN_STEER_MAP_BATCH; ++b) c->st_map_plane[i][b] = pl[i][b];
+    }
+    c->st_map_w.assign(planes_host, planes_host + (size_t)n_planes * c->V);
     return 0;
 }
 
@@ -3019,6 +3098,79 @@ extern "C" int s2v_op_attention_steer(const void* qkv, void* vt_scratch, void* o
     }
     a.valu_only = 1;
     return launch_attn_simple_steer(a, op_tab, dtype, st);
+}
+
+extern "C" int s2v_op_attention_steer_map(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                          const s2v_attn_steer_map_record* record_host, const float* planes_host, s2v_stream stream) {
+    S2V_REQUIRE(qkv && out && record_host, "s2v_op_attention_steer_map: null argument");
+    S2V_REQUIRE(B >= 1 && B <= ATTN_STEER_MAP_BATCH && H >= 1 && Ntok >= 1, "s2v_op_attention_steer_map: 1 <= B <= 8 (a plane index per range and sample), H >= 1, Ntok >= 1");
+    S2V_REQUIRE(impl == 0 || impl == 1 || impl == 2, "s2v_op_attention_steer_map: impl 0 (MFMA, bf16), 1 (generic) or 2 (MFMA, bf16, the persistent launch)");
+    S2V_REQUIRE(dtype == S2V_DTYPE_F32 || dtype == S2V_DTYPE_BF16 || dtype == S2V_DTYPE_F16, "s2v_op_attention_steer_map: unsupported dtype");
+    S2V_REQUIRE(impl == 1 || (dtype == S2V_DTYPE_BF16 && vt_scratch), "s2v_op_attention_steer_map: impl 0 is bf16 and needs vt_scratch (and so is impl 2)");
+    // operator level: one table per process, grown as needed, as s2v_op_attention_steer keeps its record: one device, one stream.  The record is of
+    // any size, so a call with a NEW record synchronises the stream before the table is replaced and before its host copy goes; a call that repeats
+    // the last call's record, planes, B and Ntok byte for byte launches on the table as it stands (a benchmark times the launch, not the host's logs)
+    static int* op_tab = nullptr;
+    static size_t op_words = 0;
+    static bool op_bound = false;
+    static hipStream_t op_stream = nullptr;
+    static s2v_attn_steer_map_record op_rec{};
+    static std::vector<float> op_planes;
+    static int op_B = 0, op_Ntok = 0;
+    const bool shape_ok = record_host->n_planes >= 1 && record_host->n_planes <= ATTN_STEER_MAP_MAX_PLANES && record_host->q0 >= 0 && record_host->q0 < record_host->q1 &&
+                          record_host->q1 <= Ntok && planes_host;
+    const size_t n_w = shape_ok ? (size_t)record_host->n_planes * (record_host->q1 - record_host->q0) : 0;
+    const bool same = shape_ok && op_tab && op_bound && op_stream == (hipStream_t)stream && op_B == B && op_Ntok == Ntok &&
+                      memcmp(&op_rec, record_host, sizeof(op_rec)) == 0 && op_planes.size() == n_w && memcmp(op_planes.data(), planes_host, n_w * 4) == 0;
+    std::vector<int> r;
+    if (!same)
+        S2V_TRY(attn_steer_map_make("s2v_op_attention_steer_map", record_host->n, record_host->k0, record_host->k1, &record_host->plane[0][0],
+                                    record_host->n_planes, planes_host, record_host->q0, record_host->q1, Ntok, B, record_host->n_planes, &r));
+    S2V_REQUIRE(!op_bound || op_stream == (hipStream_t)stream, "s2v_op_attention_steer_map: another stream than the first call's: the process-wide record table is "
+                                                               "ordered on one stream (contexts hold their own table: s2v_attn_steer_set_maps)");
+    op_bound = true; op_stream = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)stream;
+    if (!same) {
+        S2V_CHECK_HIP(hipStreamSynchronize(st));
+        op_planes.clear();   // nothing is held while the table is in between
+        if (r.size() > op_words) {
+            if (op_tab) S2V_CHECK_HIP(hipFree(op_tab));
+            op_tab = nullptr; op_words = 0;
+            S2V_CHECK_HIP(hipMalloc((void**)&op_tab, r.size() * 4));
+            op_words = r.size();
+        }
+        S2V_CHECK_HIP(hipMemcpyAsync(op_tab, r.data(), r.size() * 4, hipMemcpyHostToDevice, st));
+        S2V_CHECK_HIP(hipStreamSynchronize(st));
+        op_rec = *record_host; op_B = B; op_Ntok = Ntok;
+        op_planes.assign(planes_host, planes_host + n_w);
+    }
+    const int D = H * 64;
+    AttnArgs a{};
+    a.qkv = qkv; a.ld_qkv = 3 * D; a.out = out; a.ld_out = D; a.B = B; a.H = H; a.Ntok = Ntok; a.scale = 0.125f;
+    a.ntok_pad = (int)rup(Ntok, 64);
+    if (impl == 0 || impl == 2) {
+        a.vt = vt_scratch;
+        if (impl == 2) {   // the persistent twin on a queue of the process (nine counters, zero between launches: the last workgroup zeroes them)
+            static int* op_queue = nullptr;
+            static int op_cus = 0;
+            if (!op_queue) {
+                int dev = 0;
+                hipDeviceProp_t prop;
+                S2V_CHECK_HIP(hipGetDevice(&dev));
+                S2V_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
+                S2V_CHECK_HIP(hipMalloc((void**)&op_queue, 9 * sizeof(int)));
+                S2V_CHECK_HIP(hipMemset(op_queue, 0, 9 * sizeof(int)));
+                S2V_CHECK_HIP(hipDeviceSynchronize());
+                op_cus = prop.multiProcessorCount;
+            }
+            S2V_REQUIRE(op_cus >= 8, "s2v_op_attention_steer_map: impl 2 needs a device of at least 8 compute units");
+            a.queue = op_queue; a.num_cus = op_cus;
+        }
+        S2V_TRY(launch_v_transpose(qkv, 3 * D, B, H, Ntok, vt_scratch, a.ntok_pad, st, nullptr));
+        return launch_attn_bf16_steer_map(a, (const AttnSteerMapRec*)op_tab, st, impl == 2);
+    }
+    a.valu_only = 1;
+    return launch_attn_simple_steer_map(a, (const AttnSteerMapRec*)op_tab, dtype, st);
 }
 
 // ---- local attention in time (include/s2v_hip.h) --------------------------------------------------------------------------------------------

@@ -18,6 +18,8 @@
 //  attn_pp_steer_k / attn_pp_steer_persist_k : attn_pp_item<ACCT, STEER = true> in the same two launch forms -- attention steering, a logit bias
 //     log2 w on up to four key ranges (kernels.h AttnSteerRec; include/s2v_hip.h "Attention steering"); what a steered layer of a bf16 engine
 //     runs at every length.  attn_simple_steer_k<T>: the same bias in the generic kernel (fp32 engines, and the cross-check).
+//  attn_pp_steer_map_k / attn_pp_steer_map_persist_k : attn_pp_item<.., MAP = true> -- steering maps, the same bias with a weight per query row
+//     (log2 W_p[row - q0], kernels.h AttnSteerMapRec) and a liveness bit per wave and range from the host; attn_simple_steer_map_k<T>: the generic twin.
 //  attn_pp_local_k / attn_pp_local_persist_k : attn_pp_item<ACCT, STEER, LOCAL = true> in the same two launch forms -- local attention in time:
 //     row i sees the keys [0, P) and [lo_i, hi_i); an item visits only the key tiles some row of it sees (kernels.h "local attention";
 //     include/s2v_hip.h "Local attention"); what a local layer of a bf16 engine runs at every length.  attn_simple_local_k<T>: the same mask
@@ -309,9 +311,14 @@ extern "C" __attribute__((visibility("default"))) int s2v_attn_debug_read(long l
 // wave and tile the host's whole bit picks the untouched code; any other visited tile masks per lane, on the key index and on the key's offset
 // in its frame: the tile's first offset from the entry plus the key's position, less S once where it passes S (S >= 64: at most once per tile).
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-template <bool ACCT, bool STEER = false, bool LOCAL = false, bool BOX = false>
+// MAP (steering maps, kernels.h AttnSteerMapRec): STEER with the lane's addend read from a table -- log2 W_p[row - q0] of the plane p = plane[r][b] of
+// each range, at most four values a lane, loaded once per work item and picked by selects in the rolled range loop (0.0f outside [q0, q1), which
+// holds every row at or past Ntok; the index is clamped, so no lane reads past a plane).  Tile classification is STEER's.  The ranges a wave looks
+// at come from the host's liveness table (one uniform load): a range none of whose planes' weights on the wave's rows differs from 1 is not live,
+// its envelope does not count, and a wave with no live range runs the un-steered code on every tile.
+template <bool ACCT, bool STEER = false, bool LOCAL = false, bool BOX = false, bool MAP = false>
 __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg, char* smem, const AttnSteerRec* __restrict__ sr = nullptr,
-                                             const int* __restrict__ lr = nullptr) {
+                                             const int* __restrict__ lr = nullptr, const AttnSteerMapRec* __restrict__ mr = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;
@@ -414,6 +421,31 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
         }
         inq = q_row >= sq0 && q_row < sq1;
     }
+    // MAP: the live ranges of this sample and wave from the host's table, their envelope, and the lane's own row's addend for each of them
+    float m_ad0 = 0.f, m_ad1 = 0.f, m_ad2 = 0.f, m_ad3 = 0.f;
+    if constexpr (MAP) {
+        const int bu = min(__builtin_amdgcn_readfirstlane(b), ATTN_STEER_MAP_BATCH - 1);
+        const int qbu = min(__builtin_amdgcn_readfirstlane(qb), mr->nqb - 1);
+        const int* mw = (const int*)mr;
+        s_on = (unsigned)mw[mr->off_live + (bu * mr->nqb + qbu) * 8 + wave] & 15u;
+        bool top = true;
+        for (int r = ATTN_STEER_MAX_RANGES - 1; r >= 0; --r)
+            if ((s_on >> r) & 1u) {
+                if (top) s_hi = mr->k1[r];
+                top = false;
+                s_lo = mr->k0[r];
+            }
+        const int sq0 = mr->q0, vq = mr->q1 - sq0;
+        inq = q_row >= sq0 && q_row < mr->q1;
+        const float* lp = (const float*)mr + mr->off_log2 + min(max(q_row - sq0, 0), vq - 1);
+        const int* pw = (const int*)mr->plane;   // plane[r][b] as bytes of two words per range: a scalar load and a bit-field extract
+        auto addend = [&](int r) -> float {
+            const int p = (int)(signed char)(pw[2 * r + (bu >> 2)] >> (8 * (bu & 3)));
+            const float v = lp[max(p, 0) * vq];
+            return (inq && ((s_on >> r) & 1u)) ? v : 0.f;
+        };
+        m_ad0 = addend(0); m_ad1 = addend(1); m_ad2 = addend(2); m_ad3 = addend(3);
+    }
 
     // the S^T accumulators START at -m_run: this 16-register block is loop-carried and only rewritten on the slow path
     f32x16 ot[2], st[2], negm16;
@@ -485,6 +517,31 @@ __device__ __forceinline__ void attn_pp_item(const AttnArgs& a, int nqb, int wg,
 #pragma unroll
                             for (int e = 0; e < 16; ++e) st[kb][e] += bl;
                     } else {  // an edge of the range inside the tile: the key index of the tail mask, as an offset from the range's first key
+                        const unsigned len = (unsigned)(up - lo);
+                        const int kvb = kv0 - lo + 4 * hi;
+#pragma unroll
+                        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e)
+                                if ((unsigned)(kvb + kb * 32 + (e & 3) + 8 * (e >> 2)) < len) st[kb][e] += bl;
+                    }
+                }
+            }
+        }
+        if constexpr (MAP) {
+            if (kv0 < s_hi && kv0 + KV_TILE > s_lo) {
+#pragma nounroll
+                for (int r = 0; r < ATTN_STEER_MAX_RANGES; ++r) {
+                    if (!((s_on >> r) & 1u)) continue;
+                    const int lo = max(mr->k0[r], kv0), up = min(mr->k1[r], kv0 + KV_TILE);
+                    if (lo >= up) continue;  // the tile holds no key of range r
+                    const float bl = r == 0 ? m_ad0 : r == 1 ? m_ad1 : r == 2 ? m_ad2 : m_ad3;
+                    if (up - lo == KV_TILE) {  // interior tile
+#pragma unroll
+                        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) st[kb][e] += bl;
+                    } else {  // an edge of the range inside the tile, as STEER
                         const unsigned len = (unsigned)(up - lo);
                         const int kvb = kv0 - lo + 4 * hi;
 #pragma unroll
@@ -706,12 +763,19 @@ __global__ __launch_bounds__(512, 2) void attn_pp_box_k(const AttnArgs a, int nq
     attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
     attn_pp_item<false, false, false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, nullptr, lr);
 }
+// the MAP = true instantiation of the same launch form: the map record (kernels.h AttnSteerMapRec) as the one pointer argument
+__global__ __launch_bounds__(512, 2) void attn_pp_steer_map_k(const AttnArgs a, int nqb, const AttnSteerMapRec* __restrict__ mr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int first, cnt;
+    attn_xcd_range((int)gridDim.x, blockIdx.x & 7, first, cnt);
+    attn_pp_item<false, false, false, false, true>(a, nqb, first + (int)(blockIdx.x >> 3), smem, nullptr, nullptr, mr);
+}
 // PERSISTENT form (the engine's launches): one workgroup per CU pulls items from its XCD's queue and, when that is empty, from the
 // other XCDs' queues.  The hardware hands every XCD exactly 1/8 of a grid, but the XCDs of one launch run a few percent apart in
 // clock: with static shares the launch ended 95-100 % apart per XCD plus a last round of 32 items on 256 slots (4.6 % of the
 // slot-time idle, tools/attn_harness timeline); pulled work ends within one item.  queue[0..7]: next item of XCD x, queue[8]:
 // workgroups done -- the last one to leave zeroes the nine counters for the next launch (they must be zero at the first).
-// TWIN: attn_pp_steer_persist_k, attn_pp_local_persist_k and attn_pp_box_persist_k below repeat this loop word for word (a shared function changed this kernel's
+// TWIN: attn_pp_steer_persist_k, attn_pp_local_persist_k, attn_pp_box_persist_k and attn_pp_steer_map_persist_k below repeat this loop word for word (a shared function changed this kernel's
 // schedule): a change to the queue protocol here is made there as well.
 template <bool ACCT>
 __global__ __launch_bounds__(512, 2) void attn_pp_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue) {
@@ -833,6 +897,39 @@ __global__ __launch_bounds__(512, 2) void attn_pp_box_persist_k(const AttnArgs a
         __syncthreads();
         if (wg < 0) break;
         attn_pp_item<false, false, false, true>(a, nqb, wg, smem, nullptr, lr);
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&queue[8], 1) == (int)gridDim.x - 1) {
+            for (int i = 0; i < 9; ++i) __hip_atomic_store(&queue[i], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __threadfence();
+        }
+    }
+}
+
+// the MAP = true instantiation of the persistent form: the same loop a fifth time (a twin, as above)
+__global__ __launch_bounds__(512, 2) void attn_pp_steer_map_persist_k(const AttnArgs a, int nqb, int total, int* __restrict__ queue, const AttnSteerMapRec* __restrict__ mr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_item;
+    const int xcd = blockIdx.x & 7;
+    for (;;) {
+        if (threadIdx.x == 0) {
+            int wg = -1;
+            for (int k = 0; k < 8 && wg < 0; ++k) {
+                const int y = (xcd + k) & 7;
+                int first, cnt;
+                attn_xcd_range(total, y, first, cnt);
+                if (__hip_atomic_load(&queue[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= cnt) continue;  // drained: do not hammer it
+                const int i = atomicAdd(&queue[y], 1);
+                if (i < cnt) wg = first + i;
+            }
+            s_item = wg;
+        }
+        __syncthreads();  // also fences the previous item's LDS traffic from the next item's prologue
+        const int wg = s_item;
+        __syncthreads();
+        if (wg < 0) break;
+        attn_pp_item<false, false, false, false, true>(a, nqb, wg, smem, nullptr, nullptr, mr);
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -1143,6 +1240,110 @@ int attn_steer_make(const char* who, int n, const int* k0, const int* k1, const 
     return 0;
 }
 
+// a mapped layer of a bf16 engine (and s2v_op_attention_steer_map impl 0): attn_pp<MAP> at every length, persistent under the rule above, or at
+// any item count with force_persist (s2v_op_attention_steer_map impl 2: the persistent twin at a test's size; idle workgroups find no item and leave)
+int launch_attn_bf16_steer_map(const AttnArgs& a, const AttnSteerMapRec* rec_dev, hipStream_t st, bool force_persist) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_bf16_steer_map: map record missing");
+    S2V_REQUIRE(a.vt != nullptr, "attn_bf16_steer_map: V^T buffer missing");
+    S2V_REQUIRE(a.mx_q == nullptr && !a.p16, "attn_bf16_steer_map: attn_pp writes bf16 and reads bf16 V^T (no MX output, no attn_p_format 1)");
+    S2V_REQUIRE(a.ld_qkv % 8 == 0 && a.ntok_pad % 64 == 0, "attn_bf16_steer_map: bad leading dims");
+    S2V_REQUIRE(a.ntok_pad >= ((a.Ntok + 63) / 64) * 64, "attn_bf16_steer_map: ntok_pad too small");
+    S2V_REQUIRE(a.B >= 1 && a.B <= ATTN_STEER_MAP_BATCH, "attn_bf16_steer_map: a plane index is held for 8 samples");
+    int nqb8 = (a.Ntok + 255) / 256;
+    int total = nqb8 * a.B * a.H;
+    const bool persist = a.queue != nullptr && a.num_cus >= 8 && (force_persist || total > 2 * a.num_cus);
+    const void* fn = persist ? (const void*)attn_pp_steer_map_persist_k : (const void*)attn_pp_steer_map_k;
+    S2V_TRY(ensure_lds_attr(fn, 65536));
+    AttnArgs av = a;
+    if (persist) {
+        int* queue = a.queue;
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&total, (void*)&queue, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3((a.num_cus / 8) * 8), dim3(512), args, 65536, st));
+    } else {
+        void* args[] = {(void*)&av, (void*)&nqb8, (void*)&rec_dev};
+        S2V_CHECK_HIP(hipLaunchKernel(fn, dim3(total), dim3(512), args, 65536, st));
+    }
+    return 0;
+}
+
+// host: the wave liveness table of a map record (kernels.h AttnSteerMapRec), from the weights themselves: w != 1, not log2 w != 0
+void attn_steer_map_wave_flags(int n, int q0, int q1, int Ntok, const signed char* plane, const float* planes, int* out) {
+    const int nqb = (Ntok + 255) / 256, V = q1 - q0;
+    for (int b = 0; b < ATTN_STEER_MAP_BATCH; ++b)
+        for (int w = 0; w < 8 * nqb; ++w) {
+            int bits = 0;
+            const int i0 = std::max(w * 32, q0), i1 = std::min(std::min(w * 32 + 32, q1), Ntok);
+            for (int r = 0; r < n; ++r) {
+                const int p = plane[r * ATTN_STEER_MAP_BATCH + b];
+                if (p < 0) continue;
+                for (int i = i0; i < i1; ++i)
+                    if (planes[(size_t)p * V + (i - q0)] != 1.0f) { bits |= 1 << r; break; }
+            }
+            out[(size_t)b * 8 * nqb + w] = bits;
+        }
+}
+
+int attn_steer_map_make(const char* who, int n, const int* k0, const int* k1, const signed char* plane, int n_planes, const float* planes,
+                        int q0, int q1, int Ntok, int B, int cap_planes, std::vector<int>* out) {
+    static thread_local char msg[256];
+#define MAP_REQUIRE(cond, ...) do { if (!(cond)) { snprintf(msg, sizeof(msg), __VA_ARGS__); S2V_REQUIRE(false, msg); } } while (0)
+    MAP_REQUIRE(n >= 0 && n <= ATTN_STEER_MAX_RANGES, "%s: 0..4 key ranges are accepted (n = %d)", who, n);
+    MAP_REQUIRE(n == 0 || (k0 && k1 && plane), "%s: null range array", who);
+    MAP_REQUIRE(B >= 1 && B <= ATTN_STEER_MAP_BATCH, "%s: 1 <= B <= 8 samples (a plane index is held per range and sample; B = %d)", who, B);
+    MAP_REQUIRE(q0 >= 0 && q0 < q1 && q1 <= Ntok, "%s: the query range [%d, %d) must be non-empty and lie inside [0, Ntok = %d) (a plane holds q1 - q0 weights)", who, q0,
+                q1, Ntok);
+    MAP_REQUIRE(n_planes >= 1 && n_planes <= ATTN_STEER_MAP_MAX_PLANES, "%s: 1..16 planes are accepted (n_planes = %d)", who, n_planes);
+    MAP_REQUIRE(cap_planes >= n_planes && cap_planes <= ATTN_STEER_MAP_MAX_PLANES, "%s: the allocation holds %d planes, the record has %d", who, cap_planes, n_planes);
+    MAP_REQUIRE(planes != nullptr, "%s: null plane pointer", who);
+    for (int i = 0; i < n; ++i) {
+        MAP_REQUIRE(k0[i] >= 0 && k0[i] < k1[i] && k1[i] <= Ntok, "%s: key range %d = [%d, %d) must be non-empty and inside [0, Ntok = %d)", who, i, k0[i], k1[i], Ntok);
+        MAP_REQUIRE(i == 0 || k0[i] >= k1[i - 1], "%s: key range %d = [%d, %d) overlaps or precedes range %d (ranges are disjoint and ascending)", who, i, k0[i], k1[i], i - 1);
+        for (int b = 0; b < ATTN_STEER_MAP_BATCH; ++b) {
+            const int p = plane[i * ATTN_STEER_MAP_BATCH + b];
+            MAP_REQUIRE(p >= -1 && p < n_planes, "%s: plane index %d of range %d, sample %d lies outside [-1, n_planes = %d)", who, p, i, b, n_planes);
+            MAP_REQUIRE(b < B || p == -1, "%s: range %d names plane %d on sample %d, at or beyond B = %d (such entries are -1)", who, i, p, b, B);
+        }
+    }
+    const int V = q1 - q0;
+    for (int p = 0; p < n_planes; ++p)
+        for (int v = 0; v < V; ++v) {
+            const float w = planes[(size_t)p * V + v];
+            MAP_REQUIRE(w == w && w >= 1.52587890625e-05f && w <= 65536.0f, "%s: plane %d, cell %d: weight %g must be finite and inside [2^-16, 2^16] (no w = 0)", who, p, v,
+                        (double)w);
+        }
+#undef MAP_REQUIRE
+    std::vector<int>& r = *out;
+    r.assign(attn_steer_map_words(Ntok, V, cap_planes), 0);
+    AttnSteerMapRec h{};
+    h.n = n; h.q0 = q0; h.q1 = q1; h.n_planes = n_planes;
+    for (int i = 0; i < ATTN_STEER_MAX_RANGES; ++i)
+        for (int b = 0; b < ATTN_STEER_MAP_BATCH; ++b) h.plane[i][b] = -1;
+    for (int i = 0; i < n; ++i) {
+        h.k0[i] = k0[i]; h.k1[i] = k1[i];
+        for (int b = 0; b < ATTN_STEER_MAP_BATCH; ++b) h.plane[i][b] = plane[i * ATTN_STEER_MAP_BATCH + b];
+    }
+    h.nqb = (Ntok + 255) / 256;
+    h.off_log2 = ATTN_STEER_MAP_HDR;
+    h.off_ln = h.off_log2 + cap_planes * V;
+    h.off_live = h.off_ln + cap_planes * V;
+    *(AttnSteerMapRec*)r.data() = h;
+    float* l2 = (float*)r.data() + h.off_log2;
+    float* ln = (float*)r.data() + h.off_ln;
+    for (size_t i = 0; i < (size_t)n_planes * V; ++i) {   // the expressions of attn_steer_make: a constant plane is the scalar record's bits
+        l2[i] = (float)log2((double)planes[i]);
+        ln[i] = (float)log((double)planes[i]);
+    }
+    attn_steer_map_wave_flags(n, q0, q1, Ntok, &h.plane[0][0], planes, r.data() + h.off_live);
+    return 0;
+}
+// the liveness table for a test against brute force: out is [8][8 ceil(Ntok / 256)] int32; no check beyond null pointers (the caller's record is valid)
+extern "C" __attribute__((visibility("default"))) int s2v_attn_steer_map_wave_flags(int n, int q0, int q1, int Ntok, const signed char* plane,
+                                                                                    const float* planes, int* out) {
+    S2V_REQUIRE(plane && planes && out && n >= 0 && n <= ATTN_STEER_MAX_RANGES && q0 >= 0 && q0 < q1 && q1 <= Ntok, "s2v_attn_steer_map_wave_flags: bad argument");
+    attn_steer_map_wave_flags(n, q0, q1, Ntok, plane, planes, out);
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // TWIN: attn_simple_steer_k below repeats this body with the bias added to the score (a shared function changed this kernel's code): a change
 // here is made there as well.
@@ -1256,6 +1457,66 @@ int launch_attn_simple_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, int
     S2V_REQUIRE(a.B >= 1 && a.B <= 32, "attn_simple_steer: the sample masks hold 32 samples");
     dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
     S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_steer_k<T>, grid, dim3(256), 0, st, a, rec_dev))
+    S2V_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the mapped form of attn_simple_steer_k (steering maps, kernels.h AttnSteerMapRec; a twin again): beta = ln W_p[q - q0] of the key's range and the
+// sample's plane.  It reads no liveness table: a weight of 1 adds ln 1 = 0.0f.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_simple_steer_map_k(const AttnArgs a, const AttnSteerMapRec* __restrict__ mr) {
+    __shared__ float sq[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wave, h = blockIdx.y, b = blockIdx.z;
+    const int D = a.H * 64;
+    const bool active = q < a.Ntok;
+    const T* base = (const T*)a.qkv + (size_t)b * a.Ntok * a.ld_qkv;
+    const int ql = active ? q : a.Ntok - 1;
+    sq[wave][lane] = ET<T>::ld(base + (size_t)ql * a.ld_qkv + h * 64 + lane) * a.scale;
+    __syncthreads();
+    const bool steer_row = q >= mr->q0 && q < mr->q1;
+    const int vq = mr->q1 - mr->q0;
+    const float* lp = (const float*)mr + mr->off_ln + min(max(q - mr->q0, 0), vq - 1);
+    const int bs = min(b, ATTN_STEER_MAP_BATCH - 1);
+    float m = -INFINITY, l = 0.f, o = 0.f;
+    for (int kv0 = 0; kv0 < a.Ntok; kv0 += 64) {
+        const int kv = kv0 + lane;
+        float s = -INFINITY;
+        if (kv < a.Ntok) {
+            const T* kp = base + (size_t)kv * a.ld_qkv + D + h * 64;
+            float acc = 0.f;
+#pragma unroll 8
+            for (int d = 0; d < 64; ++d) acc = fmaf(sq[wave][d], ET<T>::ld(kp + d), acc);
+            s = acc;
+            if (steer_row) {
+#pragma unroll
+                for (int r = 0; r < ATTN_STEER_MAX_RANGES; ++r) {
+                    const int p = mr->plane[r][bs];
+                    if (r < mr->n && kv >= mr->k0[r] && kv < mr->k1[r] && p >= 0) s += lp[p * vq];
+                }
+            }
+        }
+        const float mx = wave_max(s);
+        const float mn = fmaxf(m, mx);
+        const float alpha = expf(m - mn);
+        const float p = expf(s - mn);
+        l = l * alpha + wave_sum(p);
+        o *= alpha;
+        m = mn;
+        const int nv = min(64, a.Ntok - kv0);
+        for (int j = 0; j < nv; ++j) {
+            const float pj = __shfl(p, j, 64);
+            o = fmaf(pj, ET<T>::ld(base + (size_t)(kv0 + j) * a.ld_qkv + 2 * D + h * 64 + lane), o);
+        }
+    }
+    if (active) ET<T>::st((T*)a.out + (size_t)(b * a.Ntok + q) * a.ld_out + h * 64 + lane, o / l);
+}
+
+int launch_attn_simple_steer_map(const AttnArgs& a, const AttnSteerMapRec* rec_dev, int dtype, hipStream_t st) {
+    S2V_REQUIRE(rec_dev != nullptr, "attn_simple_steer_map: map record missing");
+    S2V_REQUIRE(a.B >= 1 && a.B <= ATTN_STEER_MAP_BATCH, "attn_simple_steer_map: a plane index is held for 8 samples");
+    dim3 grid((a.Ntok + 3) / 4, a.H, a.B);
+    S2V_DT_DISPATCH(dtype, hipLaunchKernelGGL(attn_simple_steer_map_k<T>, grid, dim3(256), 0, st, a, rec_dev))
     S2V_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -317,6 +317,38 @@ int attn_steer_make(const char* who, int n, const int* k0, const int* k1, const 
 int launch_attn_bf16_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, hipStream_t st);
 int launch_attn_simple_steer(const AttnArgs& a, const AttnSteerRec* rec_dev, int dtype, hipStream_t st);
 
+// ---- steering maps: the same bias with a weight per query row (include/s2v_hip.h, "Steering maps") ----------------
+//   beta_b(i, j) = ln W_p[i - q0]  when key j lies in range r = [k0[r], k1[r]), p = plane[r][b] >= 0 and q0 <= i < q1; else 0.
+// The record as the kernels read it from DEVICE memory (data, not a launch argument), 4-byte words, nqb = ceil(Ntok / 256), V = q1 - q0 >= 1:
+//   the header below (AttnSteerMapRec, ATTN_STEER_MAP_HDR words)
+//   [off_log2 ..)   log2 W_p[v], fp32 [n_planes][V]: what attn_pp<MAP> adds (the expression that fills AttnSteerRec::log2w)
+//   [off_ln ..)     ln W_p[v], fp32 [n_planes][V]: what the generic kernel adds (the expression that fills AttnSteerRec::lnw)
+//   [off_live ..)   wave liveness, int32 [ATTN_STEER_MAP_BATCH][8 nqb]: bit r of entry (b, 8 q + w) is set iff plane[r][b] >= 0 and some row of
+//                   [256 q + 32 w, +32) inside [q0, q1) has W_p != 1 -- a wave reads its entry with a uniform load and looks at its live ranges only
+// The offsets are in words from the record's start and leave room for the allocation's plane capacity, so a record with fewer planes fits in place.
+#define ATTN_STEER_MAP_MAX_PLANES 16
+#define ATTN_STEER_MAP_BATCH 8
+struct AttnSteerMapRec {
+    int n, q0, q1, n_planes;
+    int k0[ATTN_STEER_MAX_RANGES], k1[ATTN_STEER_MAX_RANGES];
+    signed char plane[ATTN_STEER_MAX_RANGES][ATTN_STEER_MAP_BATCH];
+    int off_log2, off_ln, off_live, nqb;
+};
+#define ATTN_STEER_MAP_HDR ((int)(sizeof(AttnSteerMapRec) / 4))
+// the words of a record at Ntok tokens, V query rows and room for cap_planes planes
+inline size_t attn_steer_map_words(int Ntok, int V, int cap_planes) {
+    return (size_t)ATTN_STEER_MAP_HDR + 2 * (size_t)cap_planes * V + (size_t)ATTN_STEER_MAP_BATCH * 8 * ((Ntok + 255) / 256);
+}
+// host: the liveness table alone, [ATTN_STEER_MAP_BATCH][8 nqb] (exported as s2v_attn_steer_map_wave_flags for the CPU test against brute force)
+void attn_steer_map_wave_flags(int n, int q0, int q1, int Ntok, const signed char* plane /* [4][8] */, const float* planes /* [.][q1 - q0] */, int* out);
+// host: check everything (ranges as attn_steer_make; 1 <= n_planes <= 16; plane indices inside [-1, n_planes) and -1 on samples >= B; every weight
+// finite inside [2^-16, 2^16], the error naming plane and cell) and build the record with room for cap_planes >= n_planes planes
+int attn_steer_map_make(const char* who, int n, const int* k0, const int* k1, const signed char* plane /* [4][8] */, int n_planes, const float* planes,
+                        int q0, int q1, int Ntok, int B, int cap_planes, std::vector<int>* out);
+// attn_pp<MAP> at ANY length (bf16; persistent under launch_attn_bf16's rule) and the mapped attn_simple_k (any dtype); as the STEER launches
+int launch_attn_bf16_steer_map(const AttnArgs& a, const AttnSteerMapRec* rec_dev, hipStream_t st, bool force_persist = false);
+int launch_attn_simple_steer_map(const AttnArgs& a, const AttnSteerMapRec* rec_dev, int dtype, hipStream_t st);
+
 // ---- local attention in time: video rows attend a window of frames (include/s2v_hip.h, "Local attention") ------------
 //   out_i = sum_{j in vis(i)} softmax_{j in vis(i)}(s_ij) v_j,  s_ij = q_i . k_j / 8,  vis(i) = [0, P) union [lo_i, hi_i)
 // with one P and one row table (lo_i, hi_i) for every sample and head; 1 <= P <= Ntok, P <= lo_i <= hi_i <= Ntok (lo_i == hi_i: the prefix only).

@@ -555,6 +555,28 @@ class S2VEngine:
         arr = (_lib.SteerRangeC * max(1, len(ranges)))(*[_lib.SteerRangeC(int(k0), int(k1), float(w), int(m) & 0xFFFFFFFF) for k0, k1, w, m in ranges])
         _lib.check(_lib.lib().s2v_attn_steer_set(self._h, len(ranges), arr))
 
+    def attn_steer_set_maps(self, ranges, planes):
+        """steering maps: up to four (k0, k1, plane) with plane a sequence of up to 8 plane indices, one per sample, -1 where the range does not apply
+        (missing entries are -1); planes [n_planes, V] fp32 weights per video cell (f * Hp + y) * Wp + x, n_planes <= 16, 2^-16 <= w <= 2^16:
+        out_i = sum_j softmax_j(s_ij + ln W_p[i - (T + R)]) v_j on the keys of the ranges.  Replaces a scalar record (attn_steer_set) and the reverse:
+        a context holds one.  A captured step is kept, and replays with the new maps, while the plane count fits the allocation"""
+        ranges = list(ranges)
+        if len(ranges) > _lib.STEER_MAX_RANGES or any(len(r) != 3 for r in ranges):
+            raise _lib.S2VError(f"attn_steer_set_maps: at most {_lib.STEER_MAX_RANGES} ranges, each (k0, k1, plane per sample)")
+        pl = np.ascontiguousarray(planes.detach().cpu().numpy() if hasattr(planes, "detach") else planes, dtype=np.float32)
+        V = self.geometry[2] * (self.geometry[3] // 2) * (self.geometry[4] // 2)
+        if pl.ndim != 2 or pl.shape[1] != V:
+            raise _lib.S2VError(f"attn_steer_set_maps: planes must be [n_planes, V = {V}] (one weight per video cell), got {tuple(pl.shape)}")
+        arr = (_lib.SteerMapRangeC * max(1, len(ranges)))()
+        for i, (k0, k1, idx) in enumerate(ranges):
+            idx = [int(x) for x in idx]
+            if len(idx) > _lib.STEER_MAP_BATCH or any(x < -128 or x > 127 for x in idx):
+                raise _lib.S2VError(f"attn_steer_set_maps: range {i} names {len(idx)} planes; at most {_lib.STEER_MAP_BATCH} int8 plane indices, one per sample")
+            arr[i].k0, arr[i].k1 = int(k0), int(k1)
+            for b in range(_lib.STEER_MAP_BATCH):
+                arr[i].plane[b] = idx[b] if b < len(idx) else -1
+        _lib.check(_lib.lib().s2v_attn_steer_set_maps(self._h, len(ranges), arr, pl.shape[0], pl.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+
     def _arm_steer(self, steer_layers):
         """the layers whose attention launch is the steered kernel in the next forward (one-shot; after attn_steer_enable)"""
         if steer_layers is None:

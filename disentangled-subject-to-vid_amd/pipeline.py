@@ -118,13 +118,23 @@ class AttentionSteer:
     indices `steps` (None: every step) the joint attention of the video rows runs as softmax(s + ln w) on chosen keys -- `subject` weighs the
     reference-image keys on every sample of the CFG pairs (both halves carry the reference, so the pair's difference stays text against no
     text), `text_spans` up to three (k0, k1, w) token ranges of the prompt, applied to the positive halves only (the negative prompt has other
-    tokens).  w = 1 changes nothing; 2^-16 <= w <= 2^16.  No weight, layer or step is recommended"""
+    tokens).  w = 1 changes nothing; 2^-16 <= w <= 2^16.  No weight, layer or step is recommended.
+    Steering maps: `subject_map` gives the reference keys a weight per video cell instead of one scalar -- [F_lat, Hp, Wp] (Hp = H / 16,
+    Wp = W / 16), or [b, F_lat, Hp, Wp] with one map per video (prompt-major, as generator lists), a tensor or ndarray of weights; it applies to
+    both samples of its video.  `text_span_maps` is None or a list aligned with `text_spans` whose entries are None or such a map, applied to
+    the positive sample only.  A map and a scalar != 1 on the same range is an error: one or the other (box_weight_map makes a map from boxes)"""
 
-    def __init__(self, layers, steps=None, subject=1.0, text_spans=()):
+    def __init__(self, layers, steps=None, subject=1.0, text_spans=(), subject_map=None, text_span_maps=None):
         self.layers = layers
         self.steps = steps
         self.subject = subject
         self.text_spans = tuple(tuple(s) for s in text_spans)
+        self.subject_map = subject_map
+        self.text_span_maps = text_span_maps
+
+    @property
+    def has_maps(self):
+        return self.subject_map is not None or (self.text_span_maps is not None and any(m is not None for m in self.text_span_maps))
 
 
 STEER_W_MIN, STEER_W_MAX = 2.0 ** -16, 2.0 ** 16
@@ -255,6 +265,102 @@ def attention_steer_ranges(st, T, R, b):
     if float(st.subject) != 1.0:
         out.append((T, T + R, float(st.subject), every))
     return out
+
+
+def box_weight_map(boxes, F_lat, Hp, Wp, inside, outside=1.0):
+    """a steering map [F_lat, Hp, Wp] (fp32) from boxes: `boxes` is one (x0, y0, x1, y1) in fractions of the frame, or one per latent frame; cell
+    (y, x) is inside iff its centre ((x + .5) / Wp, (y + .5) / Hp) lies in [x0, x1) x [y0, y1).  Host only"""
+    boxes = list(boxes)
+    if len(boxes) == 4 and not isinstance(boxes[0], (list, tuple)):
+        boxes = [tuple(boxes)] * F_lat
+    if len(boxes) != F_lat:
+        raise ValueError(f"box_weight_map: {len(boxes)} boxes for {F_lat} latent frames (one box, or one per latent frame)")
+    out = torch.full((F_lat, Hp, Wp), float(outside), dtype=torch.float32)
+    cx = (torch.arange(Wp, dtype=torch.float64) + 0.5) / Wp
+    cy = (torch.arange(Hp, dtype=torch.float64) + 0.5) / Hp
+    for f, bx in enumerate(boxes):
+        if len(bx) != 4:
+            raise ValueError(f"box_weight_map: the box of frame {f} is {bx!r}, not (x0, y0, x1, y1)")
+        x0, y0, x1, y1 = (float(v) for v in bx)
+        if not (0.0 <= x0 < x1 <= 1.0 and 0.0 <= y0 < y1 <= 1.0):
+            raise ValueError(f"box_weight_map: the box of frame {f} is {bx!r}: 0 <= x0 < x1 <= 1 and 0 <= y0 < y1 <= 1 in fractions of the frame")
+        m = ((cy >= y0) & (cy < y1))[:, None] & ((cx >= x0) & (cx < x1))[None]
+        out[f][m] = float(inside)
+    return out
+
+
+def _steer_map_planes(name, m, b, F, Hp, Wp):
+    """a map argument as fp32 [n, V] with n = 1 (shared) or b (one per video), checked by name"""
+    t = torch.as_tensor(m.detach().cpu() if hasattr(m, "detach") else m).to(torch.float32)
+    if tuple(t.shape) == (F, Hp, Wp):
+        t = t[None]
+    elif tuple(t.shape) != (b, F, Hp, Wp):
+        raise ValueError(f"`attention_steer`: {name} has the shape {tuple(t.shape)}; a map is [F_lat, Hp, Wp] = {(F, Hp, Wp)} or one per video, "
+                         f"{(b, F, Hp, Wp)}")
+    if not bool(torch.isfinite(t).all()) or float(t.min()) < STEER_W_MIN or float(t.max()) > STEER_W_MAX:
+        raise ValueError(f"`attention_steer`: the weights of {name} must be finite and inside [2^-16, 2^16]")
+    return t.reshape(t.shape[0], F * Hp * Wp)
+
+
+def attention_steer_map_ranges(st, T, R, b, F, Hp, Wp):
+    """(ranges, planes, mapped) of an AttentionSteer with maps, for b videos laid out [negative x b | positive x b]: ranges [(k0, k1, plane per
+    sample)] ascending (text spans on the positive halves, then the reference keys on every sample), planes fp32 [n_planes, V = F Hp Wp], mapped one
+    bool per range.  A range that carries only a scalar rides along as a constant plane; a range whose weights are all 1 is left out, and
+    ([], None, []) steers nothing.  Host only"""
+    if b > 4:
+        raise ValueError(f"`attention_steer` with maps in a call of {b} videos: a plane index is held for 8 samples, the CFG pairs of at most four "
+                         f"videos")
+    maps = list(st.text_span_maps) if st.text_span_maps is not None else [None] * len(st.text_spans)
+    if len(maps) != len(st.text_spans):
+        raise ValueError(f"`attention_steer`: `text_span_maps` has {len(maps)} entries for {len(st.text_spans)} text spans (a list aligned with "
+                         f"`text_spans`, None where a span has no map)")
+    spans = sorted(((int(k0), int(k1), float(w), m) for (k0, k1, w), m in zip(st.text_spans, maps)), key=lambda x: x[:2])
+    for i, (k0, k1, w, m) in enumerate(spans):
+        if k1 > T:
+            raise ValueError(f"`attention_steer`: the text span {(k0, k1)} reaches beyond the {T} prompt tokens")
+        if i and k0 < spans[i - 1][1]:
+            raise ValueError(f"`attention_steer`: the text spans {spans[i - 1][:2]} and {(k0, k1)} overlap")
+    V = F * Hp * Wp
+    todo = [(k0, k1, w, m, f"the map of text span {(k0, k1)}", False) for k0, k1, w, m in spans]
+    todo.append((T, T + R, float(st.subject), st.subject_map, "`subject_map`", True))
+    ranges, planes, mapped = [], [], []
+    for k0, k1, w, m, name, every in todo:
+        if m is not None and w != 1.0:
+            raise ValueError(f"`attention_steer`: {name} together with a scalar weight {w!r} on the same keys: one or the other")
+        pl = _steer_map_planes(name, m, b, F, Hp, Wp) if m is not None else torch.full((1, V), w, dtype=torch.float32)
+        if bool((pl == 1.0).all()):
+            continue
+        base = len(planes)
+        planes.extend(pl)
+        idx = [base + (v if pl.shape[0] > 1 else 0) for v in range(b)]
+        ranges.append((k0, k1, (idx if every else [-1] * b) + idx))
+        mapped.append(m is not None)
+    if not ranges:
+        return [], None, []
+    return ranges, torch.stack(planes).numpy(), mapped
+
+
+def attention_steer_live_share(ranges, planes, q0, Ntok, B):
+    """the share of the 32-row waves of the B samples, over the rows [0, Ntok), that look at some range: counted from the library's own
+    liveness table"""
+    import ctypes
+
+    import numpy as np
+
+    from . import _lib
+    nqb = (Ntok + 255) // 256
+    if len(ranges) > 4 or B > 8 or any(len(idx) > 8 for _, _, idx in ranges):
+        raise ValueError("attention_steer_live_share: at most four ranges, each with a plane index for at most 8 samples")
+    pl = (ctypes.c_int8 * 32)(*([-1] * 32))
+    for r, (_, _, idx) in enumerate(ranges):
+        for s_, p in enumerate(idx):
+            pl[r * 8 + s_] = p
+    w = np.ascontiguousarray(planes, dtype=np.float32)
+    out = np.zeros((8, 8 * nqb), dtype=np.int32)
+    _lib.check(_lib.lib().s2v_attn_steer_map_wave_flags(len(ranges), q0, Ntok, Ntok, pl, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    nw = (Ntok + 31) // 32
+    return float((out[:B, :nw] != 0).sum()) / float(B * nw)
 
 
 def attention_steer_plan(st, n_steps):
@@ -880,6 +986,8 @@ class S2VPipeline:
         all).  After the call `attention_steer_report` holds {"steps", "layers", "ranges"}.  Refused with attention_map=, step_cache=,
         subject_guidance_scale=, temporal_windows=, cfg_parallel=, ulysses=, fused=False, per-video lists, several input videos, fp16 and fp8
         engines.  No weight, layer or step is recommended.
+        With subject_map= / text_span_maps= (steering maps) the weight is per video cell, [F_lat, Hp, Wp] or one map per video of a batched
+        call; the report then also holds {"planes", "mapped", "live_wave_share"}; maps that are all ones arm nothing.
         local_attention: a LocalAttention(layers, frames, steps=None) -- on the listed steps (None: every step) the attention of the listed blocks
         (or "all") lets a video row see the text, the reference image and only the latent frames within `frames` of its own (exact masked
         softmax; the kernel skips the key tiles no row of a work item sees).  A window that covers every frame (frames >= F - 1) arms nothing:
@@ -1165,10 +1273,19 @@ class S2VPipeline:
                                  "16-bit attention (None or 'fp8')")
         st_steps, st_ranges = [], []
         if steer is not None:   # the ranges and the steered steps, on the host, before the loop; all weights 1: nothing is enabled or armed
-            st_ranges = attention_steer_ranges(steer, text.shape[1], (H // 2) * (W // 2), b)
+            st_planes = None
+            if steer.has_maps:   # steering maps: plane indices per sample instead of masks, and the planes beside them
+                st_ranges, st_planes, st_mapped = attention_steer_map_ranges(steer, text.shape[1], (H // 2) * (W // 2), b, F, H // 2, W // 2)
+            else:
+                st_ranges = attention_steer_ranges(steer, text.shape[1], (H // 2) * (W // 2), b)
             st_steps = attention_steer_plan(steer, lens[0]) if st_ranges else []
             self.attention_steer_report = {"steps": list(st_steps), "layers": [int(l) for l in steer.layers] if st_ranges else [],
                                            "ranges": list(st_ranges)}
+            if steer.has_maps:
+                n_tok = text.shape[1] + (H // 2) * (W // 2) * (F + 1)
+                self.attention_steer_report.update(
+                    planes=0 if st_planes is None else int(st_planes.shape[0]), mapped=list(st_mapped),
+                    live_wave_share=0.0 if st_planes is None else attention_steer_live_share(st_ranges, st_planes, n_tok - F * (H // 2) * (W // 2), n_tok, 2 * b))
         la_steps, la_table, la_box = [], None, False
         if local is not None:   # the table and the windowed steps, on the host, before the loop; a window over every frame: nothing is enabled or armed
             la, la_layers = local
@@ -1200,7 +1317,10 @@ class S2VPipeline:
                 eng.attn_map_enable(True, attention_map.text_spans)
             if st_ranges:
                 eng.attn_steer_enable(True)
-                eng.attn_steer_set(st_ranges)
+                if steer.has_maps:
+                    eng.attn_steer_set_maps(st_ranges, st_planes)
+                else:
+                    eng.attn_steer_set(st_ranges)
             if la_table:
                 eng.attn_local_enable(True)
                 (eng.attn_local_set_box if la_box else eng.attn_local_set)(*la_table)

@@ -573,6 +573,48 @@ S2V_API int s2v_attn_steer_arm(s2v_ctx* ctx, uint64_t layer_mask);
 S2V_API int s2v_op_attention_steer(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
                                    const s2v_attn_steer_record* record_host, s2v_stream stream);
 
+/* ---- Steering maps: the same bias with a weight per query row -- per video cell through the context entries ("put the subject here") ------------
+ * ONE definition, which the kernels (csrc/attention.hip, MAP), tests/attn_steer_map_ref.py and this comment state alike:
+ *     s_ij  = q_i . k_j / 8
+ *     out_i = sum_j softmax_j(s_ij + beta_b(i, j)) v_j
+ *     beta_b(i, j) = ln W_p[i - q0]  when j lies in key range r = [k0_r, k1_r), p = plane[r][b] >= 0, and q0 <= i < q1;  otherwise 0.
+ * Up to four key ranges, ascending and disjoint, as above; up to 16 planes W_p of q1 - q0 >= 1 fp32 weights each, finite with 2^-16 <= w <= 2^16;
+ * plane[r][b] is an int8 per range and sample (S2V_MAX_BATCH of them), -1: range r does not apply to sample b (it replaces sample_mask).  Through
+ * the context entries the query range is the video rows [T + R, Ntok) and a plane is indexed by video cell (f * Hp + y) * Wp + x, Hp = H / 2,
+ * Wp = W / 2 of the latent (H / 16, W / 16 of the pixels): tokens are frame-major, then row-major inside a frame.  The MFMA kernel adds log2 w, the
+ * generic kernel ln w, each rounded to fp32 once on the host by the expressions of the scalar record: a constant plane gives the scalar call's bits.
+ * Liveness: per sample and 32-row wave of the MFMA kernel the host keeps the ranges that have a weight != 1 on a row of the wave; a wave looks at
+ * those ranges only, and a wave with none runs the un-steered code on every tile and returns the un-steered launch's bits (attn_pp).
+ * s2v_attn_steer_set_maps: after s2v_attn_steer_enable.  planes_host is [n_planes][V].  Everything is checked before anything is replaced, by name:
+ * the ranges as s2v_attn_steer_set checks them, n_planes in 1..16, a plane index outside [-1, n_planes), a plane index on a sample >= B, a weight
+ * that is NaN or out of bounds (the message names plane and cell).  Synchronises the device, builds the log planes and the liveness table, uploads.
+ * The table is data: a later call with no more planes than the allocation holds keeps a captured step, which replays with the new maps.  A context
+ * holds ONE record, scalar (s2v_attn_steer_set) or maps: setting the other kind drops the captured steps.  The table counts in s2v_device_bytes as
+ * workspace while held; s2v_attn_steer_enable(0) frees it.  A later s2v_set_geometry with another V refuses by name and leaves steering off.
+ * s2v_attn_steer_enable / _arm are the entries above: an armed layer runs the map kernels while the held record is maps.  Everything the scalar
+ * record is refused on is refused here by the same entries. */
+typedef struct s2v_attn_steer_map_range {
+    int32_t k0, k1;                  /* keys [k0, k1) of every sample's Ntok */
+    int8_t plane[S2V_MAX_BATCH];     /* the plane of sample b, or -1 */
+} s2v_attn_steer_map_range;
+/* the operator-level record: the ranges as arrays plus the query range; the planes come beside it as [n_planes][q1 - q0] */
+typedef struct s2v_attn_steer_map_record {
+    int32_t n, q0, q1;
+    int32_t k0[4], k1[4];
+    int8_t plane[4][S2V_MAX_BATCH];
+    int32_t n_planes;
+} s2v_attn_steer_map_record;
+S2V_API int s2v_attn_steer_set_maps(s2v_ctx* ctx, int32_t n, const s2v_attn_steer_map_range* ranges_host, int32_t n_planes, const float* planes_host);
+/* the mapped kernel on its own, as s2v_op_attention_steer: impl 0 attn_pp<MAP> (bf16, one workgroup per 256 query rows), impl 1 the mapped generic
+ * kernel (any dtype), impl 2 attn_pp<MAP> in the persistent launch form the engine uses beyond two rounds of items, here at any size on a queue of
+ * the process (bf16; the same work items, so the bits of impl 0); one table per
+ * process on the first call's device and stream (another stream is refused by name); the call synchronises the stream.  B <= S2V_MAX_BATCH */
+S2V_API int s2v_op_attention_steer_map(const void* qkv, void* vt_scratch, void* out, int32_t B, int32_t H, int32_t Ntok, int32_t dtype, int32_t impl,
+                                       const s2v_attn_steer_map_record* record_host, const float* planes_host, s2v_stream stream);
+/* host only: the wave liveness table of a VALID record, out[S2V_MAX_BATCH][8 * ceil(Ntok / 256)] int32, bit r of entry (b, w): range r is live on
+ * the rows [32 w, 32 w + 32) of sample b.  plane is [4][S2V_MAX_BATCH], planes [.][q1 - q0] */
+S2V_API int s2v_attn_steer_map_wave_flags(int32_t n, int32_t q0, int32_t q1, int32_t Ntok, const int8_t* plane, const float* planes, int32_t* out);
+
 /* ---- Local attention in time: video rows attend a window of frames (the training-free temporal sliding window) ------------------------------------
  * ONE definition, which the kernels (csrc/attention.hip), tests/attn_local_ref.py and this comment state alike.  For sample b, head h, query row
  * i and key j of the joint attention over [text T | reference R | video V]:
